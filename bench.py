@@ -18,6 +18,11 @@ featurize one batch of frames into HBM rows + accumulate X^T X / X^T y of the en
 matrix cores (the rows never leave the GPU); for N > 1 the timed region ends with the ONE all_reduce of the packed
 pieces over RCCL.  --workload lead0 (2-element, no leading trim, F = 1798) is the bandwidth-heavier featurize case.
 
+--dump-outputs DIR: after the timed region, what its last step handed the caller, as DIR/<name>.npy (float64, <= 64 MB): featurize
+= every energy row + the force rows of a fixed seeded sample of atoms; fit = the summed pieces (parallel.unpack_pieces); eval =
+forces, energy, strain derivative.  The inputs are seeded, so two builds run with the same arguments compare output for output
+(energy rows and fit sums go through atomics: equal to the last bits, not bitwise).
+
 Extra objects on the JSON line:
   roofline      the dominant kernel launch group of a step, timed with HIP events on the launch stream.  Both
                 ceilings are reported: `hbm` = algorithmic bytes (28N+75+8F(3N+1) per frame x frames per
@@ -109,7 +114,12 @@ def main(argv=None):
     ap.add_argument("--no-traffic", action="store_true",
                     help="do not measure roofline.traffic in this run (two short child runs under rocprofv3 --pmc); the figure "
                          "of the committed PMC passes under profiles/ is quoted instead")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's share) as DIR/<name>.npy, float64, "
+                         f"at most {DUMP_LIMIT_BYTES // 1000000} MB in all (dump_outputs)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     distributed = "RANK" in os.environ and "MASTER_PORT" in os.environ      # launched by torch.distributed.run
     world = int(os.environ.get("WORLD_SIZE", "1")) if distributed else 1
@@ -245,6 +255,10 @@ def main(argv=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     value = world * B * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # (before anything else runs on the rows: the cpu_baseline's extra step and the extra lines reuse these buffers)
+        dump_outputs(args.dump_outputs, parallel.unpack_pieces(flat.cpu().numpy(), int(acc._keep.numel())) if fit else
+                     featurize_outputs(torch, d_xe, d_xf))
 
     # ---- sanity of what was timed: rows are finite and obey translation invariance -------------
     xf_sum = d_xf[:n_atoms].sum(dim=0).abs().max().item()
@@ -444,6 +458,9 @@ def eval_mode(args, torch, dist, dev, distributed, world, rank):
     if rank != 0:
         return None
     host = flat.cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(forces=host[:3 * n].reshape(n, 3), energy=host[3 * n:3 * n + 1],
+                                             strain_derivative=host[3 * n + 1:]))
     if moving:
         from uf3_amd.data.atoms import Atoms
         atoms = Atoms(numbers=atoms.get_atomic_numbers(), positions=d_pos.cpu().numpy(), cell=atoms.get_cell(), pbc=True)   # (what the last step saw)
@@ -481,6 +498,35 @@ def eval_mode(args, torch, dist, dev, distributed, world, rank):
                cpu_baseline=cpu)
     print(json.dumps(out), flush=True)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step, for output-by-output comparison of two builds
+# ---------------------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays):
+    """``arrays`` (name -> array) as ``out_dir/<name>.npy`` in float64; refuses more than DUMP_LIMIT_BYTES in all."""
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes of outputs, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def featurize_outputs(torch, d_xe, d_xf):
+    """The rows a featurize step hands its caller: every energy row ``x_e`` [frames][F], and the force rows [3][F] of a fixed
+    seeded sample of the batch's atoms (``x_f_sample``, the batch-wide atom indices in ``x_f_sample_atoms``), half the byte
+    cap -- the whole x_f of a headline step is 13 GB.  The sample depends on the batch's atom count and F only, so the same
+    arguments draw the same atoms."""
+    n_atoms, F = d_xf.shape[0], d_xf.shape[2]
+    k = min(n_atoms, DUMP_LIMIT_BYTES // 2 // (8 * (3 * F + 1)))
+    atoms = np.sort(np.random.default_rng(0).choice(n_atoms, k, replace=False))
+    rows = d_xf.index_select(0, torch.from_numpy(atoms).to(d_xf.device))
+    return dict(x_e=d_xe.cpu().numpy(), x_f_sample=rows.cpu().numpy(), x_f_sample_atoms=atoms)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -173,6 +173,30 @@ def test_bench_line_keeps_the_other_configurations_where_the_driver_looks():
     assert est is None or (est["label"] == "estimate" and est["frames_per_s_all_cores"] == pytest.approx(4.8 / est["reference_to_port_ratio"]))
 
 
+def test_bench_dump_outputs_is_a_fixed_sample_under_the_size_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every energy row and the force rows of a seeded sample of atoms, as many as the byte cap
+    allows, the same atoms on every call; float64 .npy files; more than the cap is refused.  --steps 0 is refused too."""
+    import torch
+    import bench
+    with pytest.raises(SystemExit):
+        bench.main(["--steps", "0"])
+    F, n_atoms = 10, 500
+    xe = torch.arange(4 * F, dtype=torch.float64).view(4, F)
+    xf = torch.randn((n_atoms, 3, 16), dtype=torch.float64)[:, :, :F]            # rows ld = 16 doubles apart, as --row-ld makes
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 100 * 8 * (3 * F + 1))
+    out = bench.featurize_outputs(torch, xe, xf)
+    atoms = out["x_f_sample_atoms"]
+    assert len(atoms) == 100 and np.all(np.diff(atoms) > 0)
+    assert np.array_equal(out["x_f_sample"], xf.numpy()[atoms]) and np.array_equal(out["x_e"], xe.numpy())
+    assert np.array_equal(bench.featurize_outputs(torch, xe, xf)["x_f_sample_atoms"], atoms)
+    bench.dump_outputs(str(tmp_path / "d"), out)
+    back = {name: np.load(tmp_path / "d" / (name + ".npy")) for name in out}
+    assert all(a.dtype == np.float64 for a in back.values()) and np.array_equal(back["x_f_sample_atoms"], atoms)
+    assert sum(a.nbytes for a in back.values()) <= bench.DUMP_LIMIT_BYTES
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "e"), dict(big=np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)))
+
+
 def test_single_frame_batch_is_refreshed_in_place():
     """_lib.FrameBatch.refresh (what UFCalculator does between the calls of an MD loop): positions, species, cell and boundary
     flags of the same-sized frame land in the arrays the C struct already points to; another atom count asks for a new batch."""
