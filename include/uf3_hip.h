@@ -15,6 +15,8 @@
  *   uf3_neighbors_debug   <- distances.py:48-69 / angles.py:289-346 index semantics
  *   uf3_pair_geometry, uf3_distance_matrix, uf3_direction_cosines
  *                         <- the free functions of distances.py:19-143, 212-235, 331-364 and angles.py:289-346
+ *   uf3_pair_histogram[_dev] <- uf3/data/analyze.py (DataAnalyzer.get_distances, update_histograms),
+ *                            distances.py:367-442 (summarize_distances)
  *
  * Conventions
  *   - every function returns 0 on success, a non-zero UF3_E* code otherwise;
@@ -324,6 +326,33 @@ int uf3_n3_lists_debug(uf3_basis *basis, int64_t natoms, int64_t *cap_out, int32
  */
 int uf3_pair_geometry(uf3_basis *basis, const uf3_frames *frame, const double *pos, const int32_t *z,
                       int64_t *pair_count, int64_t *pair_ij, double *pair_geo, int64_t pair_cap);
+
+/*
+ * Pair-distance histograms of a batch of frames: what DataAnalyzer.get_distances + update_histograms (uf3/data/analyze.py) and
+ * summarize_distances (uf3/representation/distances.py:367-442) build from cdist of each frame against its explicit supercell
+ * (geometry.get_supercell with r_cut = the basis' r_cut; a non-periodic frame against itself), without the n x 27 n matrix.
+ * Every ordered (centre i of the frame, image j of the supercell) pair whose distance d satisfies r_min < d <= r_max
+ * (upper_inclusive != 0, the analyzer's mask) or r_min < d < r_max (upper_inclusive == 0, summarize_distances'), with the
+ * range of the pair block of the two species, adds one to bin k of that pair: edges[k] <= d < edges[k+1], the last bin closed,
+ * d outside [edges[0], edges[n_bins]] not counted (np.histogram on an edge array).
+ *   basis      species and ranges: RawDeviceBasis-style, every pair at (r_min, r_max) and r_cut = the supercell's range
+ *   edges      [n_bins + 1] host, strictly increasing, edges[0] >= 0
+ *   noise      [n_noise][3] host or NULL: added to the supercell positions by reference supercell index (image_rank * N + atom,
+ *              block 0 = the frame itself) -- ase.Atoms.rattle of the supercell (analyze.py:get_distances): the centres stay put
+ *              and every atom also meets its own image at |noise|.  n_noise must cover the supercell of every frame
+ *   per_frame  0: out [P][n_bins] summed over the frames;  1: out [n_frames][P][n_bins]
+ *   out        int64 counts, overwritten; pair blocks in the basis' order
+ * UF3_EINVAL for n_bins < 1, edges not strictly increasing or starting below 0, a noise array shorter than a frame's supercell,
+ * null pointers.  The host entry reports UF3_ESPECIES for an element outside the basis; the _dev entry enqueues everything on the
+ * context's stream and waits for nothing (edges and noise are read before it returns), so its caller must pass species of the
+ * basis.
+ */
+int uf3_pair_histogram(uf3_basis *basis, const uf3_frames *frames, const double *pos, const int32_t *z, int32_t n_bins,
+                       const double *edges, int upper_inclusive, const double *noise, int64_t n_noise, int per_frame,
+                       int64_t *out);
+int uf3_pair_histogram_dev(uf3_basis *basis, const uf3_frames *frames, const double *d_pos, const int32_t *d_z, int32_t n_bins,
+                           const double *edges, int upper_inclusive, const double *noise, int64_t n_noise, int per_frame,
+                           int64_t *d_out);
 
 /*
  * Dense helpers behind the module-level functions of uf3.representation.distances / angles, for frames small enough

@@ -26,7 +26,8 @@ EXPORTS = ["uf3_ctx_create", "uf3_ctx_destroy", "uf3_ctx_set_stream", "uf3_ctx_s
            "uf3_pair_geometry", "uf3_distance_matrix", "uf3_direction_cosines",
            "uf3_ctx_md_skin", "uf3_ctx_md_stats",
            "uf3_featurize_ld_dev", "uf3_fit_create", "uf3_fit_destroy", "uf3_fit_reset", "uf3_fit_add", "uf3_fit_pack", "uf3_fit_info", "uf3_fit_use_flat", "uf3_fit_first_chunk",
-           "uf3_comm_unique_id", "uf3_comm_init", "uf3_comm_destroy", "uf3_comm_info", "uf3_allreduce_sum_f64", "uf3_gram_allreduce"]
+           "uf3_comm_unique_id", "uf3_comm_init", "uf3_comm_destroy", "uf3_comm_info", "uf3_allreduce_sum_f64", "uf3_gram_allreduce",
+           "uf3_pair_histogram", "uf3_pair_histogram_dev"]
 
 
 SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_device.h", os.path.join("..", "..", "include", "uf3_hip.h"))
@@ -178,6 +179,8 @@ def load():
         lib.uf3_direction_cosines.argtypes = [vp, vp, i64, vp, vp, vp, i64, i64, vp]
         lib.uf3_fit_rows_dev.argtypes = [vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, i32, vp]
         lib.uf3_fit_pack_dev.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, dbl, dbl, vp]
+        for name in ("uf3_pair_histogram", "uf3_pair_histogram_dev"):
+            getattr(lib, name).argtypes = [vp, C.POINTER(Frames), vp, vp, i32, vp, C.c_int, vp, i64, C.c_int, vp]
         _lib = lib
         return lib
 
@@ -530,3 +533,36 @@ def make_frames(offsets, cells, pbc):
     f.atom_offsets, f.cells, f.pbc = _addr(offsets), _addr(cells), _addr(pbc)
     f._keep = (offsets, cells, pbc)
     return f
+
+
+def _hist_args(edges, noise):
+    edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    if noise is not None:
+        noise = np.ascontiguousarray(noise, dtype=np.float64).reshape(-1, 3)
+    return edges, noise, (0 if noise is None else len(noise))
+
+
+def pair_histogram(dbasis, batch, edges, upper_inclusive=True, noise=None, per_frame=False):
+    """Pair-distance histograms of a ``FrameBatch`` (``uf3_pair_histogram``): int64 counts [P][n_bins] summed over the frames,
+    or [n_frames][P][n_bins] with ``per_frame``; pair blocks in the order of ``dbasis.pairs``.  ``noise`` [n][3]: added to the
+    supercell positions by reference supercell index (ASE's rattle of the explicit supercell)."""
+    edges, noise, n_noise = _hist_args(edges, noise)
+    n_bins = len(edges) - 1
+    n_pairs = len(dbasis.pairs)
+    out = np.zeros(((batch.n_frames,) if per_frame else ()) + (n_pairs, max(n_bins, 0)), dtype=np.int64)
+    ctx = dbasis.ctx
+    ctx.check(ctx.lib.uf3_pair_histogram(dbasis.handle, C.byref(batch.struct), _p(batch.pos), _p(batch.z), int(n_bins),
+                                         _p(edges), int(bool(upper_inclusive)), _p(noise), int(n_noise), int(bool(per_frame)),
+                                         _p(out)))
+    return out
+
+
+def pair_histogram_dev(dbasis, frames, d_pos, d_z, d_out, edges, upper_inclusive=True, noise=None, per_frame=False):
+    """``uf3_pair_histogram_dev``: positions [N][3] float64, species [N] int32 and the int64 output already in HBM (device
+    addresses as ints, e.g. ``tensor.data_ptr()``); enqueued on the context's stream, nothing waits.  ``frames``: a ``Frames``
+    struct (``make_frames``)."""
+    edges, noise, n_noise = _hist_args(edges, noise)
+    ctx = dbasis.ctx
+    ctx.check(ctx.lib.uf3_pair_histogram_dev(dbasis.handle, C.byref(frames), C.c_void_p(d_pos), C.c_void_p(d_z),
+                                             int(len(edges) - 1), _p(edges), int(bool(upper_inclusive)), _p(noise),
+                                             int(n_noise), int(bool(per_frame)), C.c_void_p(d_out)))

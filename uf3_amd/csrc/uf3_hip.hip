@@ -81,6 +81,7 @@ struct uf3_ctx {
         n3x_ent, n3x_off,               // extension lists (batches with atoms outside their cell; see N3Lists)
         bin_cnt,                        // atoms per cell-list bin (counting sort)
         part_sums,                      // per-workgroup energy / strain-derivative sums of the MD collection pass (see EvalArgs)
+        hist_edges, hist_noise,         // uf3_pair_histogram[_dev]: the caller's bin edges and supercell noise
         f3w;                            // hand-off buffer k_feat3_w -> k_featurize3<HO>: [atoms of a slice][list capacity][S][wsz] doubles
     int n3_cap = 0, cand_cap = 0;
     size_t bin_cnt_clean = 0;        // ints of bin_cnt known to be zero (k_bin_fill leaves the counts it used at zero)
@@ -3287,6 +3288,117 @@ extern "C" int uf3_fit_pack_dev(uf3_ctx *c, int32_t n_feat, const double *d_flat
                        d_c_frozen, n_frozen, n_energy_rows, n_force_rows, d_packed);
     HIPCHK(c, hipGetLastError());
     return UF3_OK;
+}
+
+// ------------------------------------------------------------------------------ pair-distance histograms
+// The reference's DataAnalyzer.get_distances + update_histograms (uf3/data/analyze.py) and summarize_distances
+// (uf3/representation/distances.py:367-442): cdist of the frame against its explicit supercell, masked, np.histogram per pair.
+// Here the cell list of prepare() enumerates the same (centre, image) pairs and k_pair_hist counts them into the bins.
+#define UF3_HIST_LDS_BYTES 65536     // LDS counters of one workgroup: [P][n_bins] int32 up to this size, global atomics beyond
+
+static int pair_hist_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, int32_t n_bins,
+                          const double *edges, int upper_incl, const double *noise, int64_t n_noise, int per_frame,
+                          int64_t *d_out) {
+    uf3_ctx *c = b->ctx;
+    if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, "bad uf3_frames");
+    if (n_bins < 1) return fail(c, UF3_EINVAL, "uf3_pair_histogram: n_bins must be >= 1");
+    if (!edges) return fail(c, UF3_EINVAL, "uf3_pair_histogram: null edges");
+    if (!(edges[0] >= 0.0)) return fail(c, UF3_EINVAL, "uf3_pair_histogram: edges must start at >= 0");
+    for (int k = 0; k < n_bins; k++)
+        if (!(edges[k + 1] > edges[k])) return fail(c, UF3_EINVAL, "uf3_pair_histogram: edges must be strictly increasing");
+    if (n_noise < 0 || (n_noise > 0 && !noise)) return fail(c, UF3_EINVAL, "uf3_pair_histogram: bad noise array");
+    const int nf = fr->n_frames, P = b->host.P;
+    // rows of the noise table the frames reach: the reference supercell of every frame (geometry.py:14-51)
+    int64_t need = 0;
+    for (int f = 0; f < nf; f++) {
+        const int64_t n = fr->atom_offsets[f + 1] - fr->atom_offsets[f];
+        int fac[3] = {0, 0, 0};
+        const uint8_t *pbc = fr->pbc + 3 * (size_t)f;
+        if (pbc[0] || pbc[1] || pbc[2]) reference_factors(fr->cells + 9 * (size_t)f, b->r_cut, fac);
+        int64_t cnt = 1;
+        for (int k = 0; k < 3; k++) cnt *= pbc[k] ? 2 * (int64_t)fac[k] + 1 : 1;
+        need = std::max(need, cnt * n);
+    }
+    double extra = 1e-9 * b->host.rsearch;          // (pairs at exactly r_max with the upper bound inclusive)
+    if (noise) {
+        if (n_noise < need) return fail(c, UF3_EINVAL, "uf3_pair_histogram: noise array shorter than a frame's supercell");
+        double m2 = 0;
+        for (int64_t q = 0; q < need; q++) m2 = std::max(m2, dot3(noise + 3 * q, noise + 3 * q));
+        extra += std::sqrt(m2) * (1.0 + 1e-12);     // a rattled image moves at most this far towards a centre
+    }
+    Prepared P_;
+    int rc = prepare(b, fr, d_pos, d_z, false, P_, false, 0, -1, extra);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    HIPCHK(c, c->hist_edges.ensure(8 * ((size_t)n_bins + 1)));
+    HIPCHK(c, hipMemcpyAsync(c->hist_edges.p, edges, 8 * ((size_t)n_bins + 1), hipMemcpyHostToDevice, st));
+    if (noise) {
+        HIPCHK(c, c->hist_noise.ensure(24 * (size_t)need));
+        HIPCHK(c, hipMemcpyAsync(c->hist_noise.p, noise, 24 * (size_t)need, hipMemcpyHostToDevice, st));
+    }
+    const size_t nh = (size_t)P * n_bins, n_out = (per_frame ? (size_t)nf : 1) * nh;
+    HIPCHK(c, hipMemsetAsync(d_out, 0, 8 * n_out, st));
+    double rmax = 0;
+    for (int p = 0; p < P; p++) rmax = std::max(rmax, b->host.pairs[p].rmax);
+    HistArgs a;
+    a.edges = c->hist_edges.as<double>();
+    a.noise = noise ? c->hist_noise.as<double>() : nullptr;
+    a.out = (unsigned long long *)d_out;
+    a.offsets = P_.d_offsets;
+    a.natoms = P_.natoms; a.n_bins = n_bins; a.per_frame = per_frame ? 1 : 0; a.upper_incl = upper_incl ? 1 : 0;
+    a.s_cut = rmax * rmax * (1.0 + 1e-12);
+    // runs of consecutive atoms per workgroup: about four workgroups per CU, 4 .. 256 atoms
+    int chunk = (int)((P_.natoms + 4LL * c->n_cu - 1) / (4LL * c->n_cu));
+    chunk = std::max(4, std::min(256, (chunk + 3) / 4 * 4));
+    a.chunk = chunk;
+    const unsigned grid = (unsigned)((P_.natoms + chunk - 1) / chunk);
+    const size_t lds = 4 * nh;
+    Timed tm(c, T_NBR);
+    if (lds <= (size_t)std::min(c->lds_max, UF3_HIST_LDS_BYTES))
+        hipLaunchKernelGGL(k_pair_hist<true>, dim3(grid), dim3(256), lds, st, b->dev, P_.geoms, P_.frame_of, P_.cl, d_pos, P_.spec, a);
+    else
+        hipLaunchKernelGGL(k_pair_hist<false>, dim3(grid), dim3(256), 0, st, b->dev, P_.geoms, P_.frame_of, P_.cl, d_pos, P_.spec, a);
+    HIPCHK(c, hipGetLastError());
+    return UF3_OK;
+}
+
+extern "C" int uf3_pair_histogram_dev(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, int32_t n_bins,
+                                      const double *edges, int upper_inclusive, const double *noise, int64_t n_noise,
+                                      int per_frame, int64_t *d_out) {
+    uf3_env_refresh();
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    uf3_ctx *c = b->ctx;
+    if (!d_pos || !d_z || !d_out) return fail(c, UF3_EINVAL, "uf3_pair_histogram_dev: null device array");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = pair_hist_impl(b, fr, d_pos, d_z, n_bins, edges, upper_inclusive, noise, n_noise, per_frame, d_out);
+    if (rc) return rc;
+    // (species outside the basis are not reported here -- nothing waits --: the status word is cleared for the calls that follow)
+    if (c->flags.p) HIPCHK(c, hipMemsetAsync(c->flags.p, 0, sizeof(int), c->stream));
+    return UF3_OK;
+}
+
+extern "C" int uf3_pair_histogram(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, int32_t n_bins,
+                                  const double *edges, int upper_inclusive, const double *noise, int64_t n_noise, int per_frame,
+                                  int64_t *out) {
+    uf3_env_refresh();
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    uf3_ctx *c = b->ctx;
+    if (!out) return fail(c, UF3_EINVAL, "uf3_pair_histogram: null out");
+    if (!fr || fr->n_frames < 1) return fail(c, UF3_EINVAL, "bad uf3_frames");
+    if (n_bins < 1) return fail(c, UF3_EINVAL, "uf3_pair_histogram: n_bins must be >= 1");
+    int natoms = 0;
+    int rc = upload_frames(c, fr, pos, z, natoms);
+    if (rc) return rc;
+    const size_t n_out = (per_frame ? (size_t)fr->n_frames : 1) * (size_t)b->host.P * (size_t)n_bins;
+    // (the output behind positions | species would move with the staging block: a buffer of its own)
+    HIPCHK(c, c->dbg.ensure(8 * n_out));
+    rc = pair_hist_impl(b, fr, (const double *)c->stage_cur, c->d_stage_z, n_bins, edges, upper_inclusive, noise, n_noise,
+                        per_frame, c->dbg.as<int64_t>());
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(out, c->dbg.p, 8 * n_out, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->pin_in_busy = false;
+    return check_flags(c);
 }
 
 // ------------------------------------------------------------------------------ neighbour debug

@@ -4074,3 +4074,98 @@ k_direction_cosines(const double *sup_pos, const long long *i_where, const long 
     const double kron = (double)((m == j) - (m == i));
     out[q] = __dmul_rn(kron, sup_pos[3 * j + c] - sup_pos[3 * i + c]) / rij[idx];
 }
+
+// ---------------------------------------------------------------------------------
+// pair-distance histograms (uf3_pair_histogram[_dev]; the reference's DataAnalyzer.get_distances / update_histograms,
+// uf3/data/analyze.py, and summarize_distances, uf3/representation/distances.py:367-442): every ordered (centre, image) pair of
+// the reference supercell inside its pair's range -> one count in bin k of its pair, e_k <= d < e_{k+1} (the last bin closed),
+// np.histogram's rule on the caller's edges.  Four waves per workgroup, a wave per centre, the workgroup on a run of `chunk`
+// consecutive atoms; LDS: int32 counters [P][n_bins] of the workgroup (LDS_HIST), flushed with one 64-bit global atomic per
+// non-zero counter -- at every frame boundary inside the run when per_frame --, or (counters beyond the LDS budget) a global
+// atomic per kept pair.
+// noise: [n_noise][3] offsets added to the NEIGHBOUR side, row = reference supercell index (ASE's rattle of the explicit
+// supercell, analyze.py:get_distances); the centres stay where they are, so each atom also meets its own image 0.
+// ---------------------------------------------------------------------------------
+struct HistArgs {
+    const double *edges;        // [n_bins + 1], strictly increasing
+    const double *noise;        // [n_noise][3] or null
+    unsigned long long *out;    // [n_frames or 1][P][n_bins]
+    const int64_t *offsets;     // [n_frames + 1] atom offsets
+    int natoms, n_bins, chunk, per_frame, upper_incl;
+    double s_cut;               // no root for squared distances above it (> the largest r_max^2, with margin)
+};
+
+// bin of d among the edges (numpy.histogram with an edge array: searchsorted, last bin closed); -1 outside [e_0, e_n]
+__device__ __forceinline__ int hist_bin(const double *e, int n, double d) {
+    const double e0 = e[0], en = e[n];
+    if (!(d >= e0 && d <= en)) return -1;
+    int k = (int)((d - e0) * n / (en - e0));
+    k = k < 0 ? 0 : (k > n - 1 ? n - 1 : k);
+    while (k > 0 && d < e[k]) --k;
+    while (k < n - 1 && d >= e[k + 1]) ++k;
+    return k;
+}
+
+template <bool LDS_HIST>
+__global__ void __launch_bounds__(256)
+k_pair_hist(const BasisDev *B, const FrameGeom *geoms, const int *frame_of, CellList cl, const double *pos,
+            const signed char *spec, HistArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    int *hist = (int *)smem;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int P = B->P, nb = a.n_bins, nh = P * nb;
+    const int lo = blockIdx.x * a.chunk, hi = min(a.natoms, lo + a.chunk);
+    if (LDS_HIST) {
+        for (int q = tid; q < nh; q += 256) hist[q] = 0;
+        __syncthreads();
+    }
+    auto add = [&](int f, int p, int k) {
+        if (LDS_HIST) atomicAdd(&hist[p * nb + k], 1);
+        else atomicAdd(a.out + (a.per_frame ? (size_t)f * nh : 0) + (size_t)p * nb + k, 1ULL);
+    };
+    auto flush = [&](int f) {
+        __syncthreads();
+        unsigned long long *o = a.out + (a.per_frame ? (size_t)f * nh : 0);
+        for (int q = tid; q < nh; q += 256) {
+            const int v = hist[q];
+            if (v) { atomicAdd(o + q, (unsigned long long)v); hist[q] = 0; }
+        }
+        __syncthreads();
+    };
+    int seg = lo;
+    while (seg < hi) {
+        const int f = frame_of[seg];
+        const int seg_hi = min(hi, (int)a.offsets[f + 1]);
+        const FrameGeom g = geoms[f];
+        for (int m = seg + wave; m < seg_hi; m += 4) {
+            const int sm = spec[m];
+            const double pm[3] = {pos[3 * (size_t)m], pos[3 * (size_t)m + 1], pos[3 * (size_t)m + 2]};
+            // neighbour = (position + image offset) + noise (tile_periodic_images, then Atoms.rattle), then cdist's root
+            auto visit = [&](double x, double y, double z, int sj, int s0, int s1, int s2, int j_local) {
+                double off[3];
+                for (int k = 0; k < 3; k++) off[k] = s0 * g.cell[k] + s1 * g.cell[3 + k] + s2 * g.cell[6 + k];
+                double qx = x + off[0], qy = y + off[1], qz = z + off[2];
+                if (a.noise) {
+                    const double *nz = a.noise + 3 * (size_t)supercell_index(g, s0, s1, s2, j_local);
+                    qx += nz[0]; qy += nz[1]; qz += nz[2];
+                }
+                const double s = norm3_sq_rn(qx - pm[0], qy - pm[1], qz - pm[2]);
+                if (s > a.s_cut) return;
+                const double d = sqrt(s);
+                const int p = B->pair_of[sm * UF3_MAX_SPECIES + sj];
+                const PairDev &pd = B->pairs[p];
+                if (d > pd.rmin && (a.upper_incl ? d <= pd.rmax : d < pd.rmax)) {
+                    const int k = hist_bin(a.edges, nb, d);
+                    if (k >= 0) add(f, p, k);
+                }
+            };
+            // the atom's own image 0, which for_each_candidate leaves out: at distance |noise| when the supercell is rattled
+            if (a.noise && lane == 0) visit(pm[0], pm[1], pm[2], sm, 0, 0, 0, m - g.atom_lo);
+            for_each_candidate(g, cl, m, [&](bool ok, const SlotRec &sr, int sj, int s0, int s1, int s2) {
+                if (ok) visit(sr.x, sr.y, sr.z, sj, s0, s1, s2, sr.atom - g.atom_lo);
+            });
+        }
+        if (LDS_HIST && (a.per_frame || seg_hi == hi)) flush(f);
+        seg = seg_hi;
+    }
+}

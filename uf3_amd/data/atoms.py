@@ -50,6 +50,16 @@ class Atoms:
     def set_positions(self, positions):
         self.positions = np.array(positions, dtype=np.float64).reshape(len(self), 3)
 
+    def rattle(self, stdev=0.001, seed=None, rng=None):
+        """Add Gaussian noise of standard deviation ``stdev`` to the positions, in place (``ase.Atoms.rattle``): the draws
+        come from ``rng`` (anything with ``normal(scale=, size=)``), else from ``np.random.RandomState(seed)``, seed 42 when
+        neither is given -- the same noise on every call."""
+        if seed is not None and rng is not None:
+            raise ValueError("Please do not provide both seed and rng.")
+        if rng is None:
+            rng = np.random.RandomState(42 if seed is None else seed)
+        self.set_positions(self.positions + rng.normal(scale=stdev, size=self.positions.shape))
+
     def get_atomic_numbers(self):
         return self.numbers.copy()
 

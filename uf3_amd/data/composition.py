@@ -97,6 +97,19 @@ def hash_to_symbols(hash_, n=2):
     return tuple(chemical_symbols[int(z)] for z in unpack_szudzik_hash([hash_], n)[0])
 
 
+def get_pair_hashes(species_set, symbols_set, pair_idx):
+    """Szudzik hashes of (i, j) pairs (composition.py:330-346): species_set = (numbers of the centres, numbers of the
+    neighbours), symbols_set the same as symbols, pair_idx = (i indices, j indices); each pair's two atomic numbers are put in
+    ``reference_X`` order before hashing."""
+    (zi, zj), (si, sj), (iw, jw) = species_set, symbols_set, pair_idx
+    zi, zj = np.asarray(zi)[iw], np.asarray(zj)[jw]
+    xi = np.array([reference_X[s] for s in np.asarray(si)[iw]], dtype=int).reshape(-1)
+    xj = np.array([reference_X[s] for s in np.asarray(sj)[jw]], dtype=int).reshape(-1)
+    swap = xj < xi
+    pair = np.stack([np.where(swap, zj, zi), np.where(swap, zi, zj)], axis=1)
+    return get_szudzik_hash(pair)
+
+
 def hash_gather(values, hashes):
     """{hash: the values carrying it}, hashes ascending (composition.py:350-359)."""
     values, hashes = np.asarray(values), np.asarray(hashes)

@@ -297,3 +297,48 @@ def distances_from_geometry(geom, supercell=None, r_min=0.0, r_max=10.0):
     """Legacy unary form: flattened distances in (r_min, r_max) (distances.py:280-304)."""
     dm = get_distance_matrix(geom, supercell)
     return dm[(dm > r_min) & (dm < r_max)]
+
+
+def summarize_distances(geometries, chemical_system, r_cut=12.0, n_bins=100, print_stats=True, min_peak_width=0.5,
+                        progress="bar"):
+    """
+    Per-pair histograms of the distances 0 < d < r_cut over a list of frames (distances.py:367-442), each frame's counts
+    weighted by 1 / density / n_frames / 2 (density = atoms per volume of a periodic frame, 1 for a cluster) and by a further
+    1 / 2 for a mixed pair, the sum divided by 4 pi r^2 at the bin centres.  The counts come from ``uf3_pair_histogram``
+    (per frame, frames in batches); ``progress`` is accepted and ignored.
+
+    Returns:
+        histogram_map (dict): pair tuple -> n_bins values.
+        bin_edges (np.ndarray): np.linspace(0, r_cut, n_bins + 1).
+        lower_bounds (dict): pair tuple -> left edge of the first non-empty bin.
+    """
+    from scipy import signal
+    from uf3_amd.data import analyze
+    geometries = list(geometries)
+    pair_tuples = chemical_system.interactions_map[2]
+    bin_edges = np.linspace(0, r_cut, n_bins + 1)
+    histogram_values = {pair: np.zeros(n_bins) for pair in pair_tuples}
+    n_entries = len(geometries)
+    species = sorted(set(int(z) for z in chemical_system.numbers)
+                     | set(int(z) for g in geometries for z in np.unique(g.get_atomic_numbers())))
+    counts, pairs = analyze.pair_histograms(geometries, species, bin_edges, 0.0, r_cut, upper_inclusive=False,
+                                            per_frame=True)
+    column = {p: pairs.index(tuple(sorted(composition.symbols2numbers(p)))) for p in pair_tuples}
+    for f, geom in enumerate(geometries):
+        density = len(geom) / geom.get_volume() if np.any(_pbc_of(geom)) else 1
+        for pair in pair_tuples:
+            frequencies = counts[f, column[pair]] / density / n_entries / 2
+            if pair[0] != pair[1]:
+                frequencies /= 2
+            histogram_values[pair] += frequencies
+    bin_centers = 0.5 * np.add(bin_edges[:-1], bin_edges[1:])
+    bin_span = int(np.ceil(min_peak_width / (bin_edges[1] - bin_edges[0])))
+    lower_bounds = {}
+    for pair in pair_tuples:
+        histogram_values[pair] /= bin_centers ** 2 * 4 * np.pi
+        lower_bounds[pair] = bin_edges[np.nonzero(histogram_values[pair])[0][0]]
+        if print_stats:
+            peaks = bin_centers[signal.find_peaks(histogram_values[pair], width=bin_span)[0]]
+            print(pair, 'Lower bound: {0:.3f} angstroms'.format(lower_bounds[pair]))
+            print(pair, 'Peaks (min width {} angstroms):'.format(min_peak_width), peaks)
+    return histogram_values, bin_edges, lower_bounds
