@@ -57,6 +57,7 @@ def lib():
         _LIB = C.CDLL(build())
         _LIB.uf3o_featurize.restype = C.c_int
         _LIB.uf3o_eval.restype = C.c_int
+        _LIB.uf3o_eval_virial.restype = C.c_int
         _LIB.uf3o_supercell.restype = C.c_int64
     return _LIB
 
@@ -199,12 +200,20 @@ def split_coefficients(ob, coefficients):
             np.ascontiguousarray(np.concatenate(c3)) if c3 else np.zeros(0))
 
 
-def evaluate(ob, atoms, coefficients, forces=True):
-    """Energy (and forces) of a model, calculator.py:156-343 restated."""
+def evaluate(ob, atoms, coefficients, forces=True, virial=False):
+    """Energy (and forces) of a model, calculator.py:156-343 restated.  With ``virial=True`` also the
+    strain derivative dE/d(strain) [6] (eV, Voigt xx, yy, zz, yz, xz, xy): returns (e, f, v)."""
     c1, c2, c3 = split_coefficients(ob, coefficients)
     fv = _FrameView(atoms)
     e = C.c_double(0.0)
     f = np.zeros((fv.c.n_atoms, 3)) if forces else None
+    if virial:
+        v = np.zeros(6)
+        rc = lib().uf3o_eval_virial(C.byref(ob.spec), C.byref(fv.c), _ptr(c1), _ptr(c2), _ptr(c3),
+                                    C.byref(e), _ptr(f), _ptr(v))
+        if rc:
+            raise RuntimeError(f"uf3o_eval_virial rc={rc}")
+        return e.value, f, v
     rc = lib().uf3o_eval(C.byref(ob.spec), C.byref(fv.c), _ptr(c1), _ptr(c2), _ptr(c3),
                          C.byref(e), _ptr(f))
     if rc:

@@ -596,13 +596,28 @@ static void spline3(const trio_view *tv, const double *c, double rl, double rm, 
     *val = v; grad[0] = g0; grad[1] = g1; grad[2] = g2;
 }
 
+/* Voigt order (xx, yy, zz, yz, xz, xy) */
+static const int VOIGT[6][2] = {{0, 0}, {1, 1}, {2, 2}, {1, 2}, {0, 2}, {0, 1}};
+
+/* virial6 += g * r (x) r / |r| for one energy term g(|r|) of the bond vector r (Voigt) */
+static void strain_add(double *virial6, double g, const double *ra, const double *rb, double r) {
+    for (int v = 0; v < 6; v++) {
+        int a = VOIGT[v][0], b = VOIGT[v][1];
+        virial6[v] += g * (rb[a] - ra[a]) * (rb[b] - ra[b]) / r;
+    }
+}
+
 /*
  * Energy and forces of a fitted model (calculator.py:156-343).
  *   c1 [S] one-body, c2 concatenated pair coefficient vectors (nk-4 each, ALL bases),
  *   c3 concatenated full L*M*N grids (decompress_3B output) per trio.
+ * virial6 (may be NULL): dE/dt for the symmetric strain eps_ab = eps_ba = t/2 (t on the diagonal), Voigt order -- the
+ * construction of the reference's numerical stress (calculator.py:399-404) -- from the energy terms alone: every term
+ * V(r_1 .. r_k) of the sum over real i and supercell j (pairs) or real centres (trios) contributes
+ * sum_legs dV/dr_l r_l,a r_l,b / r_l, with r_l the leg's image vector.
  */
-int uf3o_eval(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
-              double *energy, double *forces) {
+static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
+                       double *energy, double *forces, double *virial6) {
     supercell_t sc;
     grid_t g;
     for (int a = 0; a < f->n_atoms; a++) if (species_index(s, f->z[a]) < 0) return 2;
@@ -615,6 +630,7 @@ int uf3o_eval(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const d
     build_grid(&sc, h * (1.0 + 1e-9) + 1e-9, &g);
     double e = 0.0;
     if (forces) memset(forces, 0, sizeof(double) * 3 * (size_t)N);
+    if (virial6) memset(virial6, 0, sizeof(double) * 6);
     for (int a = 0; a < N; a++) e += c1[species_index(s, f->z[a])];
     /* pair part */
     const double **pk = (const double **)malloc(sizeof(double *) * (size_t)(s->n_pairs + 1));
@@ -641,6 +657,7 @@ int uf3o_eval(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const d
             }
             e += phi;
             if (forces) for (int k = 0; k < 3; k++) forces[3 * i + k] += 2.0 * dphi * (rj[k] - ri[k]) / d;
+            if (virial6) strain_add(virial6, dphi, ri, rj, d);
         }
     }
     /* trio part: real centres for the energy, all centres (ghost: real j) for the forces */
@@ -678,6 +695,11 @@ int uf3o_eval(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const d
                 double val, gr[3];
                 spline3(tv, tc[t], rij, rik, rjk, &val, gr);
                 if (!ghost) e += val;
+                if (virial6 && !ghost) {          /* legs ij, ik, jk of the centre's own triplet */
+                    strain_add(virial6, gr[0], ri, rj, rij);
+                    strain_add(virial6, gr[1], ri, rk, rik);
+                    strain_add(virial6, gr[2], rj, rk, rjk);
+                }
                 if (forces) {
                     int idx[3] = {i, j, k};
                     for (int who = 0; who < 3; who++) {
@@ -699,4 +721,15 @@ int uf3o_eval(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const d
     free(cand); free((void *)pk); free((void *)pc); if (v) free_trio_views(s, v);
     free_grid(&g); free_supercell(&sc);
     return 0;
+}
+
+int uf3o_eval(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
+              double *energy, double *forces) {
+    return eval_worker(s, f, c1, c2, c3, energy, forces, NULL);
+}
+
+/* uf3o_eval plus the strain derivative virial6 [6] (eV, Voigt xx, yy, zz, yz, xz, xy; stress = virial6 / volume) */
+int uf3o_eval_virial(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
+                     double *energy, double *forces, double *virial6) {
+    return eval_worker(s, f, c1, c2, c3, energy, forces, virial6);
 }

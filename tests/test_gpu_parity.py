@@ -1268,9 +1268,10 @@ def test_evaluator_on_the_ragged_binary_fcc_frame():
     model = ls.WeightedLinearModel(basis)
     model.coefficients = coeff
     e, f, _, v = calculator.UFCalculator(model).evaluate_frames([atoms], virial=True)
-    e_ref, f_ref = O.evaluate(O.OracleBasis(basis), atoms, coeff)
+    e_ref, f_ref, v_ref = O.evaluate(O.OracleBasis(basis), atoms, coeff, virial=True)
     assert abs(e[0] - e_ref) <= TOL * abs(e_ref)
     assert rel_err(f, f_ref) < TOL and worst_elementwise(f, f_ref) <= 1.0
+    assert worst_elementwise(v[0], v_ref, rtol=1e-9, floor=1e-11) <= 1.0
     assert np.abs(f.sum(axis=0)).max() < 1e-9 * np.abs(f).max() * len(atoms) ** 0.5
     x_e, x_f, _ = process.BasisFeaturizer(basis).featurize_frames([atoms])
     assert abs(x_e[0] @ coeff - e[0]) <= 1e-10 * abs(e[0]) and rel_err(x_f @ coeff, f) < TOL     # E = x_e c, F = X_f c (the force rows carry the sign)

@@ -2320,6 +2320,7 @@ static int eval_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, co
                 A.lds_per_wave = (int)cw_per_wave; A.cw_recs_bytes = (int)cw_recs; A.cw_c2 = (int)n2;
             }
             if (!cw && (int)lds > c->lds_max) return fail(c, UF3_EOVERFLOW, "3-body neighbour list does not fit in LDS");
+            bool cap16 = false;
             if (two_pass) {
                 if (!md_step) {
                     HIPCHK(c, c->nbr_f.ensure(24 * (size_t)P.natoms * cap));
@@ -2340,7 +2341,7 @@ static int eval_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, co
                 {
                     // instance: strain derivative | list capacity 16 as a constant | candidates from the persistent lists | centre
                     // legs from per-bond tables (one set of 3-body legs, T <= 64, short lists: the usual case)
-                    const bool cap16 = cap == 16 && !uf3_env("UF3_EVAL_NO_CAP16");
+                    cap16 = cap == 16 && !uf3_env("UF3_EVAL_NO_CAP16");
                     const int inst = (A.virial ? 1 : 0) | (cap16 ? 2 : 0) | (md_step ? 4 : 0) | (tab ? 8 : 0);
 #define UF3_EVAL_CW_CASE(I) case I: {                                                                                                  \
         static std::mutex mu; static size_t have[64] = {0};                                                                           \
@@ -2395,6 +2396,12 @@ static int eval_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, co
                 if (A.virial) hipLaunchKernelGGL((k_eval<true, true>), dim3((unsigned)((atom_end - atom_begin + 7) / 8 * 8)), dim3(64), lds, st, A);
                 else hipLaunchKernelGGL((k_eval<true, false>), dim3((unsigned)((atom_end - atom_begin + 7) / 8 * 8)), dim3(64), lds, st, A);
             }
+            // (UF3_DEBUG_LDS: which k_eval instance ran -- tests assert the route they mean to reach; atom range, centre range
+            // and whole batch alike)
+            if (c->env_debug_lds && atom_end > atom_begin)
+                fprintf(stderr, "uf3: k_eval cw=%d win=%d tab=%d gather=%d md=%d cap16=%d vir=%d centres=%d part_sums=%d cap=%d atoms=%lld\n",
+                        (int)cw, (int)win, (int)tab, (int)!two_pass, (int)md_step, (int)cap16, (int)(A.virial != nullptr), (int)centres,
+                        (int)part_sums, (int)cap, (long long)(atom_end - atom_begin));
             // (one workgroup per frame and component: wide for big frames, the loop is a latency chain)
             const int sum_threads = P.natoms / P.n_frames >= 2048 ? 1024 : 256;
             // (into the caller's pinned block: the launch's last workgroup signals the host itself; flags[12] counts workgroups)

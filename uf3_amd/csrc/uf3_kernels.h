@@ -3153,13 +3153,15 @@ k_eval(EvalArgs A) {
                 if (!act || !trio_value(B, A.c3, trio, rl, rm, rn, want_f || want_v, val, gr)) continue;
                 good = true;
             }
-            // (CW: a lane without a triplet carries zeros through the force arithmetic below -- every lane takes part in the gather)
+            // (CW: a lane without a triplet carries zeros through the force arithmetic below -- every lane takes part in the gather;
+            // selected, not multiplied: its legs may have length 0 -- two list entries at one point -- and 0 * (1 / 0) is NaN)
+            const bool live = !CW || good;
             e += val;
             if (want_f || (CW && want_v)) {   // F_m = -dV/dR_m = gl * u_ij + gm * u_ik
-                const double a = gr[0] * fast_rcp(rl), b = gr[1] * fast_rcp(rm);
+                const double a = live ? gr[0] * fast_rcp(rl) : 0.0, b = live ? gr[1] * fast_rcp(rm) : 0.0;
                 fx += a * ox[aa] + b * ox[bb]; fy += a * oy[aa] + b * oy[bb]; fz += a * oz[aa] + b * oz[bb];
                 if (!GATHER) {   // F_j = -gl u_ij + gn (R_k - R_j) / rn,  F_k = -gm u_ik - gn (R_k - R_j) / rn
-                    const double cc = gr[2] * fast_rcp(rn);
+                    const double cc = live ? gr[2] * fast_rcp(rn) : 0.0;
                     const double cx = cc * (ox[bb] - ox[aa]), cy = cc * (oy[bb] - oy[aa]), cz = cc * (oz[bb] - oz[aa]);
                     if (CW) {
                         // Six ds_add_f64 per lane onto 14 addresses were 15 % of the kernel (34 of 230 us at 50 k atoms: a wave's adds
