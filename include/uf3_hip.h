@@ -355,6 +355,34 @@ int uf3_pair_histogram_dev(uf3_basis *basis, const uf3_frames *frames, const dou
                            int64_t *d_out);
 
 /*
+ * Batched fp64 solve-and-score of a cut-off / regulariser scan (uf3_amd.regression.optimize.CutoffScan).  Device buffers,
+ * everything enqueued on the context's stream, nothing waited for.
+ *   slots      [n_folds][2 n^2 + 2 n + 6]: one uf3_fit_pack_dev buffer per fold, G_e | G_f | o_e | o_f | m_e | m_f over the
+ *              n = n_cols unfrozen columns of the large basis (1 <= n_folds <= 32)
+ *   cols       column maps of the lower bases, concatenated: basis b has m_b = col_off[b+1] - col_off[b] columns, cols[col_off[b]
+ *              + i] the position of its column i among the n (int32)
+ *   reg_rc, reg_v, reg_off   per lower basis the unit regulariser pieces P_k = R_k^T R_k (k = ridge 1b, 2b, 3b, curvature 2b,
+ *              3b) in COO over its m_b columns: entries reg_off[b] .. reg_off[b+1], (row, col) int32 pairs, 5 values each; one
+ *              entry per (row, col)
+ *   sys        [n_sys][6] int64: basis, held-out fold (-1: none), workspace offset (doubles), solution offset (doubles), first
+ *              row (the prefix sum of m over the systems before it; total_rows = the sum over all), unused
+ *   sys_w      [n_sys][7]: alpha_e, alpha_f, lambda[5]
+ *   ws         ws_len doubles; system s uses m*m + 2m of them from its offset: A (row-major; on return L in the lower triangle,
+ *              A's strict upper triangle untouched), the diagonal of A, the right-hand side b
+ *   x          x_len doubles: the solution of system s at its offset
+ *   sse        [n_sys][4]: squared errors of the solution, energy (per-atom rows) and force, on the training slots and on the
+ *              held-out slot: c^T G c - 2 c^T o + sum y^2, unclamped (zero for the held-out pair when fold = -1; NaN on failure)
+ *   status     [n_sys]: 0, or j + 1 where j is the first pivot <= 0 or not finite; -1 / -2 / -3 for a workspace or solution
+ *              offset out of range, a column outside [0, n), m above 4096
+ * A = alpha_e sum_{f != fold} G_e,f[cols, cols] + alpha_f sum_{f != fold} G_f,f[cols, cols] + sum_k lambda_k P_k, b likewise from
+ * the ordinates; solved by Cholesky (trailing updates on the fp64 matrix cores).
+ */
+int uf3_scan_solve_dev(uf3_ctx *ctx, int32_t n_cols, int32_t n_folds, const double *d_slots, const int32_t *d_cols,
+                       const int64_t *d_col_off, const int32_t *d_reg_rc, const double *d_reg_v, const int64_t *d_reg_off,
+                       int32_t n_sys, int64_t total_rows, const int64_t *d_sys, const double *d_sys_w, double *d_ws,
+                       int64_t ws_len, double *d_x, int64_t x_len, double *d_sse, int32_t *d_status);
+
+/*
  * Dense helpers behind the module-level functions of uf3.representation.distances / angles, for frames small enough
  * for an n x m matrix (the reference's own limit).  Host buffers.
  *   uf3_distance_matrix     out [na][nb] = |a_i - b_j| in scipy cdist's order of operations (get_distance_matrix,

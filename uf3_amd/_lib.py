@@ -27,7 +27,7 @@ EXPORTS = ["uf3_ctx_create", "uf3_ctx_destroy", "uf3_ctx_set_stream", "uf3_ctx_s
            "uf3_ctx_md_skin", "uf3_ctx_md_stats",
            "uf3_featurize_ld_dev", "uf3_fit_create", "uf3_fit_destroy", "uf3_fit_reset", "uf3_fit_add", "uf3_fit_pack", "uf3_fit_info", "uf3_fit_use_flat", "uf3_fit_first_chunk",
            "uf3_comm_unique_id", "uf3_comm_init", "uf3_comm_destroy", "uf3_comm_info", "uf3_allreduce_sum_f64", "uf3_gram_allreduce",
-           "uf3_pair_histogram", "uf3_pair_histogram_dev"]
+           "uf3_pair_histogram", "uf3_pair_histogram_dev", "uf3_scan_solve_dev"]
 
 
 SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_device.h", os.path.join("..", "..", "include", "uf3_hip.h"))
@@ -181,6 +181,7 @@ def load():
         lib.uf3_fit_pack_dev.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, dbl, dbl, vp]
         for name in ("uf3_pair_histogram", "uf3_pair_histogram_dev"):
             getattr(lib, name).argtypes = [vp, C.POINTER(Frames), vp, vp, i32, vp, C.c_int, vp, i64, C.c_int, vp]
+        lib.uf3_scan_solve_dev.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp]
         _lib = lib
         return lib
 
@@ -566,3 +567,13 @@ def pair_histogram_dev(dbasis, frames, d_pos, d_z, d_out, edges, upper_inclusive
     ctx.check(ctx.lib.uf3_pair_histogram_dev(dbasis.handle, C.byref(frames), C.c_void_p(d_pos), C.c_void_p(d_z),
                                              int(len(edges) - 1), _p(edges), int(bool(upper_inclusive)), _p(noise),
                                              int(n_noise), int(bool(per_frame)), C.c_void_p(d_out)))
+
+
+def scan_solve_dev(ctx, n_cols, n_folds, d_slots, d_cols, d_col_off, d_reg_rc, d_reg_v, d_reg_off, n_sys, total_rows, d_sys,
+                   d_sys_w, d_ws, ws_len, d_x, x_len, d_sse, d_status):
+    """``uf3_scan_solve_dev`` (include/uf3_hip.h): every argument past the sizes a device address as an int (e.g.
+    ``tensor.data_ptr()``); enqueued on the context's stream, nothing waits."""
+    v = C.c_void_p
+    ctx.check(ctx.lib.uf3_scan_solve_dev(ctx.handle, int(n_cols), int(n_folds), v(d_slots), v(d_cols), v(d_col_off),
+                                         v(d_reg_rc), v(d_reg_v), v(d_reg_off), int(n_sys), int(total_rows), v(d_sys),
+                                         v(d_sys_w), v(d_ws), int(ws_len), v(d_x), int(x_len), v(d_sse), v(d_status)))

@@ -3408,6 +3408,39 @@ extern "C" int uf3_pair_histogram(uf3_basis *b, const uf3_frames *fr, const doub
     return check_flags(c);
 }
 
+// ------------------------------------------------------------------------------ cut-off / regulariser scans
+// k_scan_assemble (one wave per system row, every system of the batch in one grid) then k_scan_solve (one workgroup per
+// system): systems of different sizes share both launches, each paying for its own rows only.
+extern "C" int uf3_scan_solve_dev(uf3_ctx *c, int32_t n_cols, int32_t n_folds, const double *d_slots, const int32_t *d_cols,
+                                  const int64_t *d_col_off, const int32_t *d_reg_rc, const double *d_reg_v,
+                                  const int64_t *d_reg_off, int32_t n_sys, int64_t total_rows, const int64_t *d_sys,
+                                  const double *d_sys_w, double *d_ws, int64_t ws_len, double *d_x, int64_t x_len,
+                                  double *d_sse, int32_t *d_status) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "null ctx");
+    if (n_cols < 1 || n_folds < 1 || n_folds > UF3_SCAN_MAX_FOLDS || n_sys < 0 || total_rows < 0 || ws_len < 0 || x_len < 0)
+        return fail(c, UF3_EINVAL, "uf3_scan_solve_dev: bad sizes (1 <= n_folds <= 32)");
+    if (n_sys == 0) return UF3_OK;
+    if (!d_slots || !d_cols || !d_col_off || !d_reg_off || !d_sys || !d_sys_w || !d_ws || !d_x || !d_sse || !d_status)
+        return fail(c, UF3_EINVAL, "uf3_scan_solve_dev: null device array");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ensure_frag(c);
+    if (rc) return rc;
+    ScanArgs a;
+    a.n = n_cols; a.n_folds = n_folds; a.n_sys = n_sys;
+    a.total_rows = total_rows; a.ws_len = ws_len; a.x_len = x_len;
+    a.slots = d_slots; a.cols = d_cols; a.col_off = d_col_off; a.reg_rc = d_reg_rc; a.reg_v = d_reg_v; a.reg_off = d_reg_off;
+    a.sys = d_sys; a.w = d_sys_w; a.frag = c->frag.as<int>();
+    a.ws = d_ws; a.x = d_x; a.sse = d_sse; a.status = d_status;
+    HIPCHK(c, hipMemsetAsync(d_status, 0, sizeof(int32_t) * (size_t)n_sys, c->stream));
+    if (total_rows > 0) {
+        hipLaunchKernelGGL(k_scan_assemble, dim3((unsigned)((total_rows + 3) / 4)), dim3(256), 0, c->stream, a);
+        HIPCHK(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_scan_solve, dim3((unsigned)n_sys), dim3(256), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    return UF3_OK;
+}
+
 // ------------------------------------------------------------------------------ neighbour debug
 static int neighbors_impl(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z,
                           int64_t *pair_count, int64_t *pair_ij, double *pair_geo, int64_t pair_cap, int64_t *n3_count,

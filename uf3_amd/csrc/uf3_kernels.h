@@ -4171,3 +4171,288 @@ k_pair_hist(const BasisDev *B, const FrameGeom *geoms, const int *frame_of, Cell
         seg = seg_hi;
     }
 }
+
+// ---------------------------------------------------------------------------------
+// cut-off / regulariser scans: batched fp64 solve-and-score over index-mapped sub-Grams (uf3_scan_solve_dev)
+// ---------------------------------------------------------------------------------
+// Every system s of a batch is (lower basis b, held-out fold k or -1, alpha_e, alpha_f, lambda[5]); its m columns are
+// cols_b[0 .. m) among the n unfrozen columns of the fold slots.  Workspace of a system at ws + ws_off:
+//   A [m][m] row-major | d [m] (diagonal of A) | r [m] (right-hand side)
+// A is assembled in full; the factorisation writes L into the lower triangle and the diagonal only, so the strict upper
+// triangle, d and r still hold the system when a pivot fails (the host solves it again from them).
+#define UF3_SCAN_SYS 6          // int64 per system: basis, fold, ws_off, x_off, first row, pad
+#define UF3_SCAN_W 7            // doubles per system: alpha_e, alpha_f, lambda[5]
+#define UF3_SCAN_MAX_COLS 4096  // solution vector of the largest system in LDS
+#define UF3_SCAN_MAX_FOLDS 32
+
+struct ScanArgs {
+    int n, n_folds, n_sys;
+    int64_t total_rows, ws_len, x_len;
+    const double *slots;        // [n_folds][2 n^2 + 2 n + 6]: G_e | G_f | o_e | o_f | m_e | m_f
+    const int *cols;            // column maps, concatenated
+    const int64_t *col_off;     // [n_bases + 1]
+    const int *reg_rc;          // [nnz][2] (row, col) among the lower basis' unfrozen columns
+    const double *reg_v;        // [nnz][5] unit pieces P_k
+    const int64_t *reg_off;     // [n_bases + 1]
+    const int64_t *sys;         // [n_sys][UF3_SCAN_SYS]
+    const double *w;            // [n_sys][UF3_SCAN_W]
+    const int *frag;            // v_mfma_f64_16x16x4 accumulator layout (k_mfma_probe)
+    double *ws, *x, *sse;       // sse [n_sys][4]: train e, train f, held-out e, held-out f
+    int *status;                // [n_sys]: 0, j + 1 for the first pivot j <= 0 or not finite, < 0 bad arguments
+};
+
+__device__ __forceinline__ size_t scan_slot_len(int n) { return 2 * (size_t)n * n + 2 * (size_t)n + 6; }
+
+// one wave per row of one system: A[i][:] = alpha_e sum_f G_e,f[ci][cols] + alpha_f sum_f G_f,f[ci][cols] over the training
+// slots (f != held-out fold), r[i] likewise from the ordinates
+__global__ void __launch_bounds__(256)
+k_scan_assemble(ScanArgs a) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + wave;
+    if (row >= a.total_rows) return;
+    int lo = 0, hi = a.n_sys - 1;                  // last system whose first row <= row
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.sys[(size_t)mid * UF3_SCAN_SYS + 4] <= row) lo = mid; else hi = mid - 1;
+    }
+    const int64_t *sy = a.sys + (size_t)lo * UF3_SCAN_SYS;
+    const int b = (int)sy[0], fold = (int)sy[1];
+    const int64_t c0 = a.col_off[b];
+    const int m = (int)(a.col_off[b + 1] - c0);
+    const int i = (int)(row - sy[4]);
+    const int64_t need = sy[2] + (int64_t)m * m + 2 * (int64_t)m;
+    if (i < 0 || i >= m || sy[2] < 0 || need > a.ws_len || sy[3] < 0 || sy[3] + m > a.x_len) {
+        if (lane == 0) a.status[lo] = -1;
+        return;
+    }
+    const int *cols = a.cols + c0;
+    const int ci = cols[i];
+    if (ci < 0 || ci >= a.n) { if (lane == 0) a.status[lo] = -2; return; }
+    const double ae = a.w[(size_t)lo * UF3_SCAN_W], af = a.w[(size_t)lo * UF3_SCAN_W + 1];
+    const size_t n = (size_t)a.n, L = scan_slot_len(a.n);
+    double *A = a.ws + sy[2];
+    for (int j = lane; j < m; j += 64) {
+        int cj = cols[j];
+        cj = (cj >= 0 && cj < a.n) ? cj : ci;      // (every entry is checked as some row's ci)
+        double ge = 0.0, gf = 0.0;
+        for (int f = 0; f < a.n_folds; f++) {
+            if (f == fold) continue;
+            const double *sl = a.slots + f * L;
+            ge += sl[(size_t)ci * n + cj];
+            gf += sl[n * n + (size_t)ci * n + cj];
+        }
+        A[(size_t)i * m + j] = ae * ge + af * gf;
+    }
+    if (lane == 0) {
+        double oe = 0.0, of = 0.0;
+        for (int f = 0; f < a.n_folds; f++) {
+            if (f == fold) continue;
+            const double *sl = a.slots + f * L;
+            oe += sl[2 * n * n + ci];
+            of += sl[2 * n * n + n + ci];
+        }
+        A[(size_t)m * m + m + i] = ae * oe + af * of;
+    }
+}
+
+// 16 x 16 diagonal block (LDS, stride 17) factorised in place by one wave; 0 or the first failing pivot (1-based)
+__device__ __forceinline__ int scan_potrf16(double (*D)[17], int kb, int lane) {
+    for (int j = 0; j < kb; j++) {
+        const double dj = D[j][j];
+        if (!(dj > 0.0) || !__builtin_isfinite(dj)) return j + 1;
+        const double lj = sqrt(dj);
+        wave_sync();
+        if (lane == 0) D[j][j] = lj;
+        if (lane > j && lane < kb) D[lane][j] /= lj;
+        wave_sync();
+        const int r = lane >> 2;                   // trailing part of the block: lane -> row, four columns
+        for (int q = 0; q < 4; q++) {
+            const int c = (lane & 3) * 4 + q;
+            if (r > j && c > j && c <= r && r < kb) D[r][c] -= D[r][j] * D[c][j];
+        }
+        wave_sync();
+    }
+    return 0;
+}
+
+// one workgroup per system: regulariser add, right-looking blocked Cholesky (16-column panels, trailing updates on
+// v_mfma_f64_16x16x4), the two triangular solves, and the squared-error pieces of the solution on every fold slot
+__global__ void __launch_bounds__(256)
+k_scan_solve(ScanArgs a) {
+    __shared__ double D[16][17];
+    __shared__ double xs[UF3_SCAN_MAX_COLS];
+    __shared__ double part[4][UF3_SCAN_MAX_FOLDS][4];
+    __shared__ int bad_s;
+    const int s = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int64_t *sy = a.sys + (size_t)s * UF3_SCAN_SYS;
+    const int b = (int)sy[0], fold = (int)sy[1];
+    const int64_t c0 = a.col_off[b];
+    const int m = (int)(a.col_off[b + 1] - c0);
+    if (a.status[s] != 0) return;                  // (bad arguments, reported by k_scan_assemble)
+    if (m > UF3_SCAN_MAX_COLS || m < 1) { if (tid == 0) a.status[s] = -3; return; }
+    double *A = a.ws + sy[2], *dg = A + (size_t)m * m, *rhs = dg + m;
+    const double *w = a.w + (size_t)s * UF3_SCAN_W;
+    {   // + sum_k lambda_k P_k (the pattern holds every (row, col) once), then the diagonal is saved
+        const int64_t e0 = a.reg_off[b], e1 = a.reg_off[b + 1];
+        for (int64_t e = e0 + tid; e < e1; e += 256) {
+            const int r = a.reg_rc[2 * e], c = a.reg_rc[2 * e + 1];
+            if (r < 0 || r >= m || c < 0 || c >= m) continue;
+            const double *v = a.reg_v + 5 * e;
+            A[(size_t)r * m + c] += w[2] * v[0] + w[3] * v[1] + w[4] * v[2] + w[5] * v[3] + w[6] * v[4];
+        }
+        __syncthreads();
+        for (int i = tid; i < m; i += 256) dg[i] = A[(size_t)i * m + i];
+        __syncthreads();
+    }
+    int fr[4], fc[4];
+    for (int v = 0; v < 4; v++) { fr[v] = a.frag[(lane * 4 + v) * 2]; fc[v] = a.frag[(lane * 4 + v) * 2 + 1]; }
+    int bad = 0;
+    for (int k0 = 0; k0 < m; k0 += 16) {
+        const int kb = min(16, m - k0);
+        {   // diagonal block: load, factorise (wave 0), store L11
+            const int r = tid >> 4, c = tid & 15;
+            D[r][c] = (r < kb && c <= r) ? A[(size_t)(k0 + r) * m + k0 + c] : 0.0;
+            __syncthreads();
+            if (wave == 0) {
+                const int bb = scan_potrf16(D, kb, lane);
+                if (lane == 0) bad_s = bb ? k0 + bb : 0;
+            }
+            __syncthreads();
+            bad = bad_s;
+            if (bad) break;
+            if (r < kb && c <= r) A[(size_t)(k0 + r) * m + k0 + c] = D[r][c];
+        }
+        const int rest = m - k0 - 16;              // rows below the panel (kb == 16 whenever rest > 0)
+        if (rest <= 0) break;
+        for (int i = k0 + 16 + tid; i < m; i += 256) {     // panel: L21 = A21 L11^-T, one row per thread
+            double *row = A + (size_t)i * m + k0;
+            double t[16];
+#pragma unroll
+            for (int j = 0; j < 16; j++) t[j] = row[j];
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                double v = t[j];
+#pragma unroll
+                for (int q = 0; q < j; q++) v -= t[q] * D[j][q];
+                t[j] = v / D[j][j];
+            }
+#pragma unroll
+            for (int j = 0; j < 16; j++) row[j] = t[j];
+        }
+        __syncthreads();
+        // trailing update A22 -= L21 L21^T: lower 16 x 16 tiles dealt to the waves, K = 16 in four MFMA steps
+        // (A operand lane l: L21[tile row l % 16][k = l / 16 + 4 q]; B operand likewise from the column tile)
+        const int T = (rest + 15) >> 4, n_tiles = T * (T + 1) / 2;
+        const int li = lane & 15, lk = lane >> 4;
+        for (int t = wave; t < n_tiles; t += 4) {
+            int ti = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
+            while ((ti + 1) * (ti + 2) / 2 <= t) ti++;
+            while (ti * (ti + 1) / 2 > t) ti--;
+            const int tj = t - ti * (ti + 1) / 2;
+            const int R = k0 + 16 + ti * 16, Cb = k0 + 16 + tj * 16;
+            const bool va = R + li < m, vb = Cb + li < m;
+            const double *pa = A + (size_t)(va ? R + li : k0) * m + k0 + lk;
+            const double *pb = A + (size_t)(vb ? Cb + li : k0) * m + k0 + lk;
+            double xa[4], xb[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) { xa[q] = pa[4 * q]; xb[q] = pb[4 * q]; }
+            double4_t acc = {0, 0, 0, 0};
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(va ? xa[q] : 0.0, vb ? xb[q] : 0.0, acc, 0, 0, 0);
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+                const int gi = R + fr[v], gj = Cb + fc[v];
+                if (gi < m && gj < m && (ti != tj || fc[v] <= fr[v])) A[(size_t)gi * m + gj] -= acc[v];
+            }
+        }
+        __syncthreads();
+    }
+    if (bad) {
+        if (tid == 0) a.status[s] = bad;
+        if (tid < 4) a.sse[4 * (size_t)s + tid] = __builtin_nan("");
+        return;
+    }
+    // L y = r, then L^T x = y, in place in xs: 16-row blocks solved by wave 0, the rows beyond updated by the workgroup
+    for (int i = tid; i < m; i += 256) xs[i] = rhs[i];
+    __syncthreads();
+    for (int k0 = 0; k0 < m; k0 += 16) {
+        const int kb = min(16, m - k0);
+        if (wave == 0) {
+            for (int j = k0; j < k0 + kb; j++) {
+                wave_sync();
+                const double yj = xs[j] / A[(size_t)j * m + j];
+                wave_sync();
+                if (lane == 0) xs[j] = yj;
+                if (lane > j - k0 && lane < kb) xs[k0 + lane] -= A[(size_t)(k0 + lane) * m + j] * yj;
+            }
+        }
+        __syncthreads();
+        for (int i = k0 + kb + tid; i < m; i += 256) {
+            const double *row = A + (size_t)i * m + k0;
+            double v = 0.0;
+            for (int q = 0; q < kb; q++) v += row[q] * xs[k0 + q];
+            xs[i] -= v;
+        }
+        __syncthreads();
+    }
+    for (int k0 = ((m - 1) / 16) * 16; k0 >= 0; k0 -= 16) {
+        const int kb = min(16, m - k0);
+        if (wave == 0) {
+            for (int j = k0 + kb - 1; j >= k0; j--) {
+                wave_sync();
+                const double xj = xs[j] / A[(size_t)j * m + j];
+                wave_sync();
+                if (lane == 0) xs[j] = xj;
+                if (lane < j - k0) xs[k0 + lane] -= A[(size_t)j * m + k0 + lane] * xj;
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < k0; i += 256) {
+            double v = 0.0;
+            for (int q = 0; q < kb; q++) v += A[(size_t)(k0 + q) * m + i] * xs[k0 + q];
+            xs[i] -= v;
+        }
+        __syncthreads();
+    }
+    double *xo = a.x + sy[3];
+    for (int i = tid; i < m; i += 256) xo[i] = xs[i];
+    // per fold slot: x^T G_e x, x^T o_e, x^T G_f x, x^T o_f -- one wave per row, lanes along the row
+    const int *cols = a.cols + c0;
+    const size_t n = (size_t)a.n, L = scan_slot_len(a.n);
+    for (int f = 0; f < a.n_folds; f++) {
+        const double *sl = a.slots + f * L;
+        double qe = 0.0, qf = 0.0, le = 0.0, lf = 0.0;
+        for (int i = wave; i < m; i += 4) {
+            const size_t ci = (size_t)cols[i];
+            const double *ge = sl + ci * n, *gf = sl + n * n + ci * n;
+            double se = 0.0, sf = 0.0;
+            for (int j = lane; j < m; j += 64) {
+                const int cj = cols[j];
+                se += ge[cj] * xs[j];
+                sf += gf[cj] * xs[j];
+            }
+            qe += xs[i] * se;
+            qf += xs[i] * sf;
+            if (lane == 0) { le += xs[i] * sl[2 * n * n + ci]; lf += xs[i] * sl[2 * n * n + n + ci]; }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            qe += __shfl_xor(qe, o); qf += __shfl_xor(qf, o);
+            le += __shfl_xor(le, o); lf += __shfl_xor(lf, o);
+        }
+        if (lane == 0) { part[wave][f][0] = qe; part[wave][f][1] = le; part[wave][f][2] = qf; part[wave][f][3] = lf; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double out[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int f = 0; f < a.n_folds; f++) {
+            const double *mo = a.slots + f * L + 2 * n * n + 2 * n;      // m_e[3] | m_f[3]
+            double q[4];
+            for (int u = 0; u < 4; u++) q[u] = part[0][f][u] + part[1][f][u] + part[2][f][u] + part[3][f][u];
+            const int held = f == fold ? 2 : 0;
+            out[held] += q[0] - 2.0 * q[1] + mo[2];
+            out[held + 1] += q[2] - 2.0 * q[3] + mo[5];
+        }
+        for (int u = 0; u < 4; u++) a.sse[4 * (size_t)s + u] = out[u];
+    }
+}
