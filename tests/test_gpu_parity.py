@@ -2255,10 +2255,9 @@ def test_neighbour_indices_bit_exact_within_an_ulp_of_every_cutoff():
     assert rel_err(x_e[0], o["xe"]) < TOL and rel_err(x_f, o["xf"]) < TOL
 
 
-def test_hand_off_launch_pair_matches_the_one_kernel_launch_and_the_oracle():
-    """UF3_F3_HANDOFF=1 (the measured experiment of round 6, DESIGN 3.6: k_feat3_w computes the neighbour role's stage-1 sums
-    once, at the centre, and k_featurize3<HO> reads them back): same rows as the default launch and as the oracle -- one, two and
-    three species, list capacities 16 and 24, several frames per slice and one frame per slice."""
+def test_default_3body_launch_matches_the_oracle_on_one_to_three_species_and_list_capacity_24():
+    """The default k_featurize3 launch on one, two and three species and list capacities 16 and 24, several frames in one call:
+    a repeat call on the context (capacities now tuned) gives the same rows, and the last frame's rows agree with the oracle."""
     cases = [(synthetic.notebook_basis(['W']), [synthetic.config_c2()[0]]),
              (synthetic.notebook_basis(['Mo', 'W']), [synthetic.lattice_frame("bcc", (6, 6, 6), 3.165, [42, 74], s) for s in (1, 2, 3)]),
              (synthetic.notebook_basis(['Mo', 'Nb', 'W']), [synthetic.lattice_frame("bcc", (6, 6, 6), 3.2, [41, 42, 74], 5)]),
@@ -2266,18 +2265,11 @@ def test_hand_off_launch_pair_matches_the_one_kernel_launch_and_the_oracle():
     for basis, frames in cases:
         fz = process.BasisFeaturizer(basis)
         e0, f0, off = fz.featurize_frames(frames)
-        for slice_atoms in ("", "1"):
-            os.environ["UF3_F3_HANDOFF"] = "1"
-            if slice_atoms:
-                os.environ["UF3_F3_SLICE"] = slice_atoms
-            try:
-                e1, f1, _ = fz.featurize_frames(frames)
-            finally:
-                os.environ.pop("UF3_F3_HANDOFF", None)
-                os.environ.pop("UF3_F3_SLICE", None)
-            assert rel_err(e1, e0) < 1e-12 and rel_err(f1, f0) < 1e-12
+        e1, f1, _ = fz.featurize_frames(frames)
+        assert rel_err(e1, e0) < 1e-12 and rel_err(f1, f0) < 1e-12
         ref = O.featurize(O.OracleBasis(basis), frames[-1])
-        assert rel_err(f1[off[-2]:off[-1]], ref["xf"]) < TOL and rel_err(e1[-1], ref["xe"]) < TOL
+        for e, f in ((e0, f0), (e1, f1)):
+            assert rel_err(f[off[-2]:off[-1]], ref["xf"]) < TOL and rel_err(e[-1], ref["xe"]) < TOL
 
 
 def test_sharded_evaluator_and_feature_batch_on_one_gpu():

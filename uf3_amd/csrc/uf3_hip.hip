@@ -81,8 +81,7 @@ struct uf3_ctx {
         n3x_ent, n3x_off,               // extension lists (batches with atoms outside their cell; see N3Lists)
         bin_cnt,                        // atoms per cell-list bin (counting sort)
         part_sums,                      // per-workgroup energy / strain-derivative sums of the MD collection pass (see EvalArgs)
-        hist_edges, hist_noise,         // uf3_pair_histogram[_dev]: the caller's bin edges and supercell noise
-        f3w;                            // hand-off buffer k_feat3_w -> k_featurize3<HO>: [atoms of a slice][list capacity][S][wsz] doubles
+        hist_edges, hist_noise;         // uf3_pair_histogram[_dev]: the caller's bin edges and supercell noise
     int n3_cap = 0, cand_cap = 0;
     size_t bin_cnt_clean = 0;        // ints of bin_cnt known to be zero (k_bin_fill leaves the counts it used at zero)
     int n3_last_cap = 0, n3_last_natoms = 0;   // layout of the 3-body lists in the workspace right now (uf3_n3_lists_debug)
@@ -114,8 +113,7 @@ struct uf3_ctx {
     char *stage_cur = nullptr;          // the block that holds the current host-entry batch: stage_bar or stage_pos
     size_t staged_in_dev = 0;           // bytes of positions | species the host entry has stored into stage_pos already (0: none)
     // environment switches of the featurizer's asynchronous path, re-read at the top of every featurizer call (read_f3_env)
-    bool env_no_feat3 = false, env_f3_no_cap16 = false, env_f3_no_select = false, env_debug_lds = false;
-    int env_f3_bps = 24;
+    bool env_no_feat3 = false, env_debug_lds = false;
     unsigned eval_seq = 0;              // sequence number of the last small evaluator call whose tail kernel signals through the pinned block
     bool tail_signalled = false;        // ... and whether the last eval_impl's k_frame_sum signals
     bool pin_in_busy = false;           // a kernel that reads pin_in directly has been launched and not yet waited for
@@ -265,10 +263,7 @@ extern "C" const char *uf3_build_id(void) { return UF3_BUILD_ID; }
 // them between calls on one shared context -- ADVICE round 5)
 static void read_f3_env(uf3_ctx *c) {
     c->env_no_feat3 = uf3_env("UF3_NO_FEAT3") != nullptr;
-    c->env_f3_no_cap16 = uf3_env("UF3_F3_NO_CAP16") != nullptr;
-    c->env_f3_no_select = uf3_env("UF3_F3_NO_SELECT") != nullptr;
     c->env_debug_lds = uf3_env("UF3_DEBUG_LDS") != nullptr;
-    c->env_f3_bps = uf3_env("UF3_F3_BPS") ? std::max(1, atoi(uf3_env("UF3_F3_BPS"))) : 24;
 }
 
 extern "C" int uf3_ctx_create(int device, uf3_ctx **out) {
@@ -309,7 +304,7 @@ extern "C" void uf3_ctx_destroy(uf3_ctx *c) {
     Buf *all[] = {&c->geoms, &c->offsets, &c->frame_of, &c->atom_bin, &c->atom_wrap, &c->spec, &c->key_in,
                   &c->key_out, &c->val_in, &c->val_out, &c->sort_tmp, &c->bin_start, &c->slots, &c->flags, &c->n3_cnt, &c->n3_int, &c->n3_dbl, &c->e_atom, &c->nbr_f, &c->coeff,
                   &c->stage_pos, &c->stage_z, &c->stage_out, &c->stage_out2, &c->sp_rows, &c->sp_seg, &c->gram_tij, &c->frag, &c->dbg, &c->halo, &c->n3x_ent, &c->n3x_off,
-                  &c->bin_cnt, &c->f3w, &c->coeff_cw, &c->part_sums};
+                  &c->bin_cnt, &c->coeff_cw, &c->part_sums};
     for (Buf *b : all) b->release();
     for (Buf &b : c->gram_tiles) b.release();
     if (c->comm) uf3_comm_destroy(c);
@@ -599,14 +594,13 @@ extern "C" int uf3_basis_create(uf3_ctx *c, const uf3_basis_spec *s, uf3_basis *
         // specialisation (modes 6-9); wider windows stay on the generic kernels
         DenseLayout dl = dense_layout(td.ext[0], td.ext[1], td.ext[2]);
         const int dmode = dense_mode_for(td.ext[0], td.ext[1], td.ext[2]);
-        if (dmode && !uf3_env("UF3_NO_MFMA_FEAT") && (dmode <= 7 || !uf3_env("UF3_NO_WIDE_MFMA"))) {
+        if (dmode && !uf3_env("UF3_NO_MFMA_FEAT")) {
             td.dense = dmode;
             b->dense_stride[dmode] = std::max(b->dense_stride[dmode], dl.stride);
             b->dense_dump[dmode] = std::max(b->dense_dump[dmode], td.ext[0] * dl.cw);
         }
         td.grouped = 0; td.gthr0 = -1e300; td.gthr2 = 1e300;
-        if (td.dense == 7 && td.ext[1] == 3 && td.ext[0] <= 3 && td.ext[2] >= 6 && td.ext[2] <= 9 && td.nsrc <= 2 && td.ncol <= 128 &&
-            !uf3_env("UF3_NO_NGROUP")) {
+        if (td.dense == 7 && td.ext[1] == 3 && td.ext[0] <= 3 && td.ext[2] >= 6 && td.ext[2] <= 9 && td.nsrc <= 2 && td.ncol <= 128) {
             // first window bin f = interval - 3 - lo_n: f <= 1 -> group 0 (bins 0..4), f >= 4 -> group 2 (bins 4..8)
             const double *tn = legn_knots[t];
             const int nk = td.leg[2].nk, i_lo = 3, i_hi = nk - 5;
@@ -618,7 +612,7 @@ extern "C" int uf3_basis_create(uf3_ctx *c, const uf3_basis_spec *s, uf3_basis *
         // wide windows (mode 9, two row tiles): cut the intervals of leg n into at most three bands whose records touch at most
         // three neighbouring column tiles (trio_block_banded); windows that do not fit keep the dense loop
         td.banded = 0; td.band_tile[0] = td.band_tile[1] = td.band_tile[2] = 0;
-        if (td.dense == 9 && dl.stride == 64 && (4 * td.ext[0] + 15) / 16 == 2 && !uf3_env("UF3_NO_BANDS")) {
+        if (td.dense == 9 && dl.stride == 64 && (4 * td.ext[0] + 15) / 16 == 2) {
             const double *tn = legn_knots[t];
             const int i_lo = 3, i_hi = td.leg[2].nk - 5, n_ct = (td.ext[1] * td.ext[2] + 15) / 16;
             auto tiles_of = [&](int i, int &t0, int &t1) {
@@ -802,14 +796,14 @@ extern "C" int uf3_basis_create(uf3_ctx *c, const uf3_basis_spec *s, uf3_basis *
     if (!trios.empty())
         HIPCHK(c, hipMemcpy(b->d_trios, trios.data(), sizeof(TrioDev) * trios.size(), hipMemcpyHostToDevice));
     h.trios = b->d_trios; h.recs = b->d_recs; h.lut = b->d_lut;
-    h.pairs_uniform = !uf3_env("UF3_NO_UNIFORM_LEGS");
+    h.pairs_uniform = 1;
     for (int a = 0; a < UF3_MAX_SPECIES * UF3_MAX_SPECIES; a++) h.pair_col[a] = h.pair_of[a] >= 0 ? h.pairs[h.pair_of[a]].col : 0;
     for (int p2 = 1; p2 < h.P && h.pairs_uniform; p2++) {
         const PairDev &a = h.pairs[0], &q = h.pairs[p2];
         if (a.leg.rec_off != q.leg.rec_off || a.leg.nk != q.leg.nk || a.leg.t0 != q.leg.t0 || a.leg.tlast != q.leg.tlast ||
             a.leg.inv_h != q.leg.inv_h || a.rmin != q.rmin || a.rmax != q.rmax || a.nb != q.nb) h.pairs_uniform = 0;
     }
-    h.trio_legs_uniform = h.T > 0 && !uf3_env("UF3_NO_UNIFORM_LEGS");
+    h.trio_legs_uniform = h.T > 0;
     for (int t = 1; t < h.T && h.trio_legs_uniform; t++) {
         for (int d = 0; d < 3; d++) {
             const LegDev &a = trios[0].leg[d], &q = trios[t].leg[d];
@@ -860,7 +854,7 @@ extern "C" int uf3_basis_create(uf3_ctx *c, const uf3_basis_spec *s, uf3_basis *
             const bool shape = prr > 0 && prr * b->f3_nr >= ep &&
                                ((ep >= 1 && ep <= 3 && prr * en <= 31 && en <= 9) || (ep == 4 && en <= 11) || ((ep == 5 || ep == 6) && en <= 13));
             ok = t0.lo[0] == t0.lo[1] && t0.ext[0] == t0.ext[1] && same_leg(t0.leg[0], t0.leg[1]) && shape &&
-                 t0.leg[0].nk >= 8 && t0.leg[2].nk >= 8 && !(ep > 3 && uf3_env("UF3_NO_FEAT3_WIDE"));
+                 t0.leg[0].nk >= 8 && t0.leg[2].nk >= 8;
             for (int t = 0; t < h.T && ok; t++) {
                 const TrioDev &td = trios[t];
                 for (int a = 0; a < 3; a++) ok = ok && td.lo[a] == t0.lo[a] && td.ext[a] == t0.ext[a];
@@ -1057,7 +1051,7 @@ static int make_geom(uf3_ctx *c, const uf3_basis *b, const uf3_frames *fr, int f
     if (!invert3(eff, g.inv)) return fail(c, UF3_EINVAL, "cell is singular along a periodic direction");
     double rs = b->host.rsearch + extra;
     // bins of half the search radius (scan radius 2): 125 bins cover 15.6 r^3 instead of 27 r^3 for 27 full-size bins
-    const double bin_frac = uf3_env("UF3_BIN_FRAC") ? atof(uf3_env("UF3_BIN_FRAC")) : 0.5;
+    const double bin_frac = 0.5;
     if (n_per) {
         reference_factors(cell, b->r_cut, g.fac);
         for (int k = 0; k < 3; k++) if (!g.per[k]) g.fac[k] = 0;
@@ -1326,7 +1320,7 @@ static int prepare(uf3_basis *b, const uf3_frames *fr, const double *d_pos, cons
                        c->atom_wrap.as<int>(), c->spec.as<signed char>(), c->key_in.as<int>(), c->bin_cnt.as<int>(), flags);
     // (up to 16 384 bins -- frames of about 20 k atoms: one workgroup walking 36 k counts of the 50 k-atom frame took 40 us longer than the
     // library scan's two launches)
-    if ((size_t)nbins + 1 <= 16384 && !uf3_env("UF3_NO_SMALL_SCAN"))
+    if ((size_t)nbins + 1 <= 16384)
         hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, (const int *)c->bin_cnt.as<int>(), c->bin_start.as<int>(), nbins + 1);
     else {
         size_t tmp_bytes = 0;
@@ -1437,12 +1431,6 @@ static size_t feat3_lds_bytes(const uf3_basis *b, int cap, bool e_lds) {
     const size_t ints = ((size_t)WPB * per_wave_i + 3) & ~(size_t)3;
     return (e_d + rows_d + WPB * (list_d + tq_d + stage_d)) * 8 + ints * 4 + (size_t)b->n_f3src * 2 + 32;
 }
-// ... of k_feat3_w: window rows | per wave: list, bond values, stage | ints
-static size_t feat3w_lds_bytes(const uf3_basis *b, int cap) {
-    const size_t rows_d = (size_t)b->n_f3rows * 18;
-    const size_t per_wave_d = 8 * (size_t)cap + F3WCfg::STAGE, per_wave_i = 4 * (size_t)cap + (UF3_MAX_SPECIES + 2);
-    return (rows_d + WPB * per_wave_d) * 8 + WPB * per_wave_i * 4 + 32;
-}
 #define UF3_LDS_LIMIT ((size_t)160 * 1024 - 512)
 
 static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z,
@@ -1497,7 +1485,7 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
     A.dsrc = b->d_dsrc; A.n_dsrc = (int)b->n_dsrc;
     A.gsrc = b->d_gsrc; A.n_gsrc = (int)b->n_gsrc; A.gsrc_lds = 0;
     const int dense_modes = (1 << 6) | (1 << 7) | (1 << 8) | (1 << 9);
-    const bool dsrc_ok = (b->modes & dense_modes) && b->n_dsrc * sizeof(int) <= 8192 && !uf3_env("UF3_NO_LDS_DSRC");
+    const bool dsrc_ok = (b->modes & dense_modes) && b->n_dsrc * sizeof(int) <= 8192;
     A.dsrc_lds = dsrc_ok;
     if (b->modes & dense_modes) { rc = ensure_frag(c); if (rc) return rc; A.frag = c->frag.as<int>(); }
     A.geoms = P.geoms; A.frame_of = P.frame_of; A.cl = P.cl;
@@ -1554,7 +1542,7 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
                            feat3_lds_bytes(b, cap, want_e && !A.e_direct) <= UF3_LDS_LIMIT;
         // (the pair launch below leaves the batch's longest 3-body list in flags[7] when k_featurize3 can use it: see there)
         A.n3_seen = nullptr;
-        if (feat3 && has3 && cap > 16 && !c->env_f3_no_cap16 && !c->env_f3_no_select) {
+        if (feat3 && has3 && cap > 16) {
             A.n3_seen = c->flags.as<int>() + 7;
             HIPCHK(c, hipMemsetAsync(A.n3_seen, 0, sizeof(int), st));
         }
@@ -1567,15 +1555,15 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
                 const bool dense_mode = mode >= 6;
                 // knot records go to LDS when the block then still reaches the occupancy its registers allow
                 // (10: mode 7 with grouped windows only -- the force launches of a basis whose mode-7 blocks are all grouped)
-                const int launch_mode = (mode == 7 && want_f && b->all_grouped7 && !img_launch && !uf3_env("UF3_NO_GROUPED_ONLY")) ? 10
-                                        : ((mode == 9 && want_f && b->all_banded9 && !img_launch && !uf3_env("UF3_NO_GROUPED_ONLY")) ? 11 : mode);
+                const int launch_mode = (mode == 7 && want_f && b->all_grouped7 && !img_launch) ? 10
+                                        : ((mode == 9 && want_f && b->all_banded9 && !img_launch) ? 11 : mode);
                 // (a grouped-only launch reads the window rows, not the knot records of the legs)
                 A.trio_rec_lo = (int)(launch_mode == 10 ? b->wrow_lo : b->trio_rec_lo);
                 size_t n_rec_mode = mode == 0 ? b->n_pair_recs : b->n_recs - (size_t)A.trio_rec_lo;
                 const int S = b->host.S;
                 const size_t cu_lds = 160 * 1024 - 1024;
                 if (dense_mode) A.dsrc_lds = dsrc_ok && !(mode == 7 && want_f && b->all_grouped7);
-                const bool gsrc_wanted = mode == 7 && want_f && b->dense_grouped[7] && b->n_gsrc > 0 && b->n_gsrc * 2 <= 4096 && !uf3_env("UF3_NO_LDS_GSRC");
+                const bool gsrc_wanted = mode == 7 && want_f && b->dense_grouped[7] && b->n_gsrc > 0 && b->n_gsrc * 2 <= 4096;
                 const size_t gsrc_bytes = gsrc_wanted ? b->n_gsrc * 2 : 0;
                 A.gsrc_lds = gsrc_wanted;
                 size_t lds_extra = ((dense_mode && A.dsrc_lds) ? sizeof(int) * b->n_dsrc : 0) + gsrc_bytes;
@@ -1592,14 +1580,14 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
                     auto stage_for = [&](int nr) { return std::max(dump, (nr + (nr & 1) + (grouped ? 2 : 0)) * stride); };
                     // (21 records = 63 staging lanes = one walk step: a block of <= 63 items is one step and three passes)
                     A.dense_nrec = nrec_max; A.dense_stage = stage_for(nrec_max);
-                    if (mode <= 7 && !uf3_env("UF3_NO_OCC3")) {
+                    if (mode <= 7) {
                         // records per staging pass: as many as the stage allows; fewer (smaller stage) if that lets a third
                         // workgroup onto the CU -- the kernel is latency-bound.  Three workgroups per CU need <= 52 KB each
                         // (LDS is granted in coarse granules: 53 KB did not fit).  Candidates in order of preference: the
                         // knot records / window rows in LDS first, then more records per pass
                         const int tries[3] = {nrec_max, std::min(nrec_max, 20), std::min(nrec_max, 15)};
                         const size_t budget = (WPB == 4 ? 52 : 13 * WPB) * 1024;      // (12 waves per CU: 3 x 4 or 2 x 6)
-                        const bool dsrc_allowed = A.dsrc_lds, recs_allowed = !uf3_env("UF3_NO_LDS_RECS") && !(img_launch && mode != 0);
+                        const bool dsrc_allowed = A.dsrc_lds, recs_allowed = !(img_launch && mode != 0);
                         for (int q = 0; q < 12 && !found; q++) {
                             // (the records / window rows in LDS first: a staging lane reads eleven 16-byte pieces of them per pass)
                             const int nr = tries[(q % 6) / 2];
@@ -1618,7 +1606,7 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
                     lds_plain = feat_lds_bytes(F, S, cap, A.cand_cap, want_e && !A.e_direct, 0, mode, A.dense_stage, A.dense_nrec, A.n_pair_cols) + lds_extra;
                     lds_recs = feat_lds_bytes(F, S, cap, A.cand_cap, want_e && !A.e_direct, n_rec_mode, mode, A.dense_stage, A.dense_nrec, A.n_pair_cols) + lds_extra;
                     const size_t lds_target = cu_lds / (mode == 0 ? 4 : 2);
-                    recs_lds = lds_recs <= lds_target && !uf3_env("UF3_NO_LDS_RECS") && !(img_launch && mode != 0);
+                    recs_lds = lds_recs <= lds_target && !(img_launch && mode != 0);
                     lds = recs_lds ? lds_recs : lds_plain;
                 }
                 if (lds > UF3_LDS_LIMIT && mode == 0 && !c->cand_tuned && c->cand_cap > 64) {
@@ -1715,7 +1703,6 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
                 feat3_shape(b, ep, stage, nrec);
                 (void)stage; (void)nrec;
                 const int nr = b->f3_nr;
-                G.wbuf = nullptr; G.wsz = 0; G.m_lo = 0;
         /* (the dynamic-LDS attribute belongs to the kernel instance on a device: one process-wide high-water mark each) */   \
 #define UF3_F3_ATTR(KERNEL, lds)                                                                                           \
     do {                                                                                                                   \
@@ -1727,48 +1714,32 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
             hv = (lds);                                                                                                    \
         }                                                                                                                  \
     } while (0)
-#define UF3_F3_LAUNCH1(E, EFv, NRv, CAPv, HOv)                                                                              \
+#define UF3_F3_LAUNCH1(E, EFv, NRv, CAPv)                                                                                   \
     do {                                                                                                                   \
-        UF3_F3_ATTR((k_featurize3<E, EFv, NRv, CAPv, HOv>), lds);                                                          \
-        hipLaunchKernelGGL((k_featurize3<E, EFv, NRv, CAPv, HOv>), dim3(grid), dim3(WPB * WAVE), lds, st, G);               \
+        UF3_F3_ATTR((k_featurize3<E, EFv, NRv, CAPv>), lds);                                                               \
+        hipLaunchKernelGGL((k_featurize3<E, EFv, NRv, CAPv>), dim3(grid), dim3(WPB * WAVE), lds, st, G);                    \
     } while (0)
 #define UF3_F3_LAUNCH(E, EFv, NRv)                                                                                          \
-    do { if (lcap == 16 && !c->env_f3_no_cap16) UF3_F3_LAUNCH1(E, EFv, NRv, 16, false); else UF3_F3_LAUNCH1(E, EFv, NRv, 0, false); } while (0)
-#define UF3_F3W_LAUNCH1(CAPv)                                                                                               \
-    do {                                                                                                                   \
-        UF3_F3_ATTR((k_feat3_w<3, CAPv>), lds);                                                                            \
-        hipLaunchKernelGGL((k_feat3_w<3, CAPv>), dim3(grid), dim3(WPB * WAVE), lds, st, G);                                 \
-    } while (0)
-                // the launch's grid over the atoms m_lo .. natoms - 1 (G.m_lo, G.natoms)
-                auto f3_grid = [&](size_t lds) -> unsigned {
-                    const int n_at = G.natoms - G.m_lo;
-                    int per_cu = std::max(1, std::min(8, (int)((size_t)(160 * 1024) / lds)));
-                    const int bps = c->env_f3_bps;
-                    int n_blocks = std::min((n_at + WPB - 1) / WPB, c->n_cu * per_cu * bps);
-                    int apb = ((n_at + n_blocks - 1) / n_blocks + WPB - 1) / WPB * WPB;
-                    n_blocks = (n_at + apb - 1) / apb;
-                    G.atoms_per_block = apb;
-                    return (unsigned)((n_blocks + 7) / 8 * 8);
-                };
+    do { if (lcap == 16) UF3_F3_LAUNCH1(E, EFv, NRv, 16); else UF3_F3_LAUNCH1(E, EFv, NRv, 0); } while (0)
                 // one launch laid out for lists of up to `lcap` entries (the batch's list array keeps the context's capacity as
                 // its stride); sel_mode: see Feat3Args
-                auto launch_f3 = [&](int lcap, int sel_mode, bool ho) -> int {
+                auto launch_f3 = [&](int lcap, int sel_mode) -> int {
                     G.sel_mode = sel_mode;
                     const size_t lds = feat3_lds_bytes(b, lcap, want_e && !A.e_direct);      // (<= UF3_LDS_LIMIT: checked where feat3 was decided)
-                    const unsigned grid = f3_grid(lds);
+                    // the grid over all atoms: 24 workgroups per resident slot
+                    const int per_cu = std::max(1, std::min(8, (int)((size_t)(160 * 1024) / lds)));
+                    int n_blocks = std::min((G.natoms + WPB - 1) / WPB, c->n_cu * per_cu * 24);
+                    const int apb = ((G.natoms + n_blocks - 1) / n_blocks + WPB - 1) / WPB * WPB;
+                    n_blocks = (G.natoms + apb - 1) / apb;
+                    G.atoms_per_block = apb;
+                    const unsigned grid = (unsigned)((n_blocks + 7) / 8 * 8);
                     if (c->env_debug_lds)
-                        fprintf(stderr, "uf3 featurize3: lds %zu B, cap %d (lists %d apart), selection %d, hand-off %d, blocks %u x %d atoms, window %d x %d, %d round(s)\n",
-                                lds, lcap, cap, sel_mode, (int)ho, grid, G.atoms_per_block, G.ext_p, G.ext_n, nr);
+                        fprintf(stderr, "uf3 featurize3: lds %zu B, cap %d (lists %d apart), selection %d, blocks %u x %d atoms, window %d x %d, %d round(s)\n",
+                                lds, lcap, cap, sel_mode, grid, G.atoms_per_block, G.ext_p, G.ext_n, nr);
                     switch (ep) {
                         case 3:      // (the default trims: the list capacity as a constant also at 24 and 32 -- fcc and denser cells)
-                            if (ho) {        // (the measured experiment of round 6: capacity 16 as a constant, everything else generic)
-                                if (lcap == 16 && !c->env_f3_no_cap16) { if (want_e) UF3_F3_LAUNCH1(true, 3, 1, 16, true); else UF3_F3_LAUNCH1(false, 3, 1, 16, true); }
-                                else { if (want_e) UF3_F3_LAUNCH1(true, 3, 1, 0, true); else UF3_F3_LAUNCH1(false, 3, 1, 0, true); }
-                            }
-                            else if ((lcap == 24 || lcap == 32) && !c->env_f3_no_cap16) {
-                                if (lcap == 24) { if (want_e) UF3_F3_LAUNCH1(true, 3, 1, 24, false); else UF3_F3_LAUNCH1(false, 3, 1, 24, false); }
-                                else { if (want_e) UF3_F3_LAUNCH1(true, 3, 1, 32, false); else UF3_F3_LAUNCH1(false, 3, 1, 32, false); }
-                            }
+                            if (lcap == 24) { if (want_e) UF3_F3_LAUNCH1(true, 3, 1, 24); else UF3_F3_LAUNCH1(false, 3, 1, 24); }
+                            else if (lcap == 32) { if (want_e) UF3_F3_LAUNCH1(true, 3, 1, 32); else UF3_F3_LAUNCH1(false, 3, 1, 32); }
                             else if (want_e) UF3_F3_LAUNCH(true, 3, 1); else UF3_F3_LAUNCH(false, 3, 1);
                             break;
                         case 4: if (want_e) UF3_F3_LAUNCH(true, 4, 2); else UF3_F3_LAUNCH(false, 4, 2); break;
@@ -1777,79 +1748,26 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
                     }
                     return UF3_OK;
                 };
-                // the producer of the hand-off (k_feat3_w) over the same atoms, same instance selection
-                auto launch_f3w = [&](int lcap, int sel_mode) -> int {
-                    G.sel_mode = sel_mode;
-                    const size_t lds = feat3w_lds_bytes(b, lcap);
-                    const unsigned grid = f3_grid(lds);
-                    if (c->env_debug_lds)
-                        fprintf(stderr, "uf3 feat3_w: lds %zu B, cap %d (lists %d apart), selection %d, blocks %u x %d atoms, atoms %d .. %d\n",
-                                lds, lcap, cap, sel_mode, grid, G.atoms_per_block, G.m_lo, G.natoms);
-                    if (lcap == 16 && !c->env_f3_no_cap16) UF3_F3W_LAUNCH1(16); else UF3_F3W_LAUNCH1(0);
-                    return UF3_OK;
-                };
                 // The lists of this batch were built just now at the context's capacity -- an estimate on a context's first call,
                 // what the densest batch so far needed later on -- but the instance that serves most cells is the one laid out for 16
                 // entries (4 workgroups per CU, LDS offsets as immediates).  Which one applies is known on the device only: the list
                 // build leaves the batch's longest list in flags[7], and two launches follow of which one leaves at once.
-                auto launch_pair = [&](bool producer, bool ho) -> int {
-                    if (A.n3_seen && cap > 16) {
-                        int r1 = producer ? launch_f3w(16, 1) : launch_f3(16, 1, ho);
-                        if (r1) return r1;
-                        return producer ? launch_f3w(cap, 2) : launch_f3(cap, 2, ho);
-                    }
-                    return producer ? launch_f3w(cap, 0) : launch_f3(cap, 0, ho);
-                };
-                // Hand-off (round 6; UF3_F3_HANDOFF=1 only -- it was built, measured and LOST: 4460-4630 against
-                // 6410 frames/s): the neighbour role's stage-1 sums are computed once, by the centre (k_feat3_w), and
-                // reach the neighbours through HBM: slices of whole frames, producer then consumer, one buffer re-used by every slice
-                const int ho_default = 0;
-                // (looked at on every call: tests and A/B runs flip it between calls on one context)
-                const int ho_env = uf3_env("UF3_F3_HANDOFF") ? atoi(uf3_env("UF3_F3_HANDOFF")) : ho_default;
-                const int slice_env = uf3_env("UF3_F3_SLICE") ? std::max(0, atoi(uf3_env("UF3_F3_SLICE"))) : 0;
-                const bool handoff = ho_env != 0 && ep == 3 && nr == 1 && feat3w_lds_bytes(b, cap) <= UF3_LDS_LIMIT;
-                if (!handoff) {
-                    int r1 = launch_pair(false, false);
+                if (A.n3_seen && cap > 16) {
+                    int r1 = launch_f3(16, 1);
+                    if (!r1) r1 = launch_f3(cap, 2);
                     if (r1) return r1;
                 } else {
-                    const int S_ = b->host.S;
-                    G.wsz = (G.ext_p * G.ext_n * 4 + 15) / 16 * 16;
-                    const size_t per_atom = (size_t)cap * S_ * G.wsz * sizeof(double);
-                    const int64_t slice_target = slice_env > 0 ? slice_env : 320000;
-                    const int64_t *off = fr->atom_offsets;
-                    // (slices: runs of whole frames of at most slice_target atoms, at least one frame)
-                    int64_t widest = 0;
-                    for (int f0 = 0; f0 < P.n_frames;) {
-                        int f1 = f0 + 1;
-                        while (f1 < P.n_frames && off[f1 + 1] - off[f0] <= slice_target) f1++;
-                        widest = std::max(widest, off[f1] - off[f0]);
-                        f0 = f1;
-                    }
-                    HIPCHK(c, c->f3w.ensure(per_atom * (size_t)widest));
-                    G.wbuf = c->f3w.as<double>();
-                    for (int f0 = 0; f0 < P.n_frames;) {
-                        int f1 = f0 + 1;
-                        while (f1 < P.n_frames && off[f1 + 1] - off[f0] <= slice_target) f1++;
-                        G.m_lo = (int)off[f0]; G.natoms = (int)off[f1];
-                        if (G.natoms > G.m_lo) {
-                            int r1 = launch_pair(true, true);
-                            if (r1) return r1;
-                            r1 = launch_pair(false, true);
-                            if (r1) return r1;
-                        }
-                        f0 = f1;
-                    }
-                    G.m_lo = 0; G.natoms = P.natoms;
+                    int r1 = launch_f3(cap, 0);
+                    if (r1) return r1;
                 }
 #undef UF3_F3_LAUNCH
 #undef UF3_F3_LAUNCH1
-#undef UF3_F3W_LAUNCH1
 #undef UF3_F3_ATTR
             }
         }
         HIPCHK(c, hipGetLastError());
         if (restart) continue;
-        if ((!has3 || c->n3_tuned) && c->cand_tuned && !old_n3 && !uf3_env("UF3_SYNC_FEATURIZE")) {
+        if ((!has3 || c->n3_tuned) && c->cand_tuned && !old_n3) {
             // capacities known from earlier calls: do not wait.  The status words follow the launches into a pinned
             // slot; the next call on this context / uf3_ctx_synchronize looks at them (UF3_ERETRY if they overflowed)
             int slot = -1;
@@ -1955,7 +1873,7 @@ static int upload_frames(uf3_ctx *c, const uf3_frames *fr, const double *pos, co
     bool bar = defer_small && c->bar_ok && bp + bz + geo_room <= UF3_BAR_LIMIT;
     if (bar && !c->bar_tested) {
         c->bar_tested = true;
-        if (!uf3_env("UF3_BAR_NO_SELFTEST")) c->bar_ok = bar = bar_self_test(c);
+        c->bar_ok = bar = bar_self_test(c);
         if (uf3_env("UF3_BAR_FORCE_FAIL")) c->bar_ok = bar = false;       // (tests: the fall-back route on a box where the test passes)
     }
     // (a block of its own: the big batches' staging block stays ordinary device memory)
@@ -2040,7 +1958,7 @@ static int md_build(uf3_basis *b, const uf3_frames *fr, const double *d_pos, con
     uf3_ctx *c = b->ctx;
     uf3_ctx::MdState &md = c->md;
     md.valid = false; md.stale = false;
-    const bool defer = may_defer && md.cap_tuned && !md.verify_next && md.basis == b && md.cap > 0 && !uf3_env("UF3_MD_SYNC_BUILD");
+    const bool defer = may_defer && md.cap_tuned && !md.verify_next && md.basis == b && md.cap > 0;
     int rc = prepare(b, fr, d_pos, d_z, false, P, false, 0, -1, md.skin);      // cell list at r_cut + skin
     if (rc) return rc;
     hipStream_t st = c->stream;
@@ -3137,7 +3055,7 @@ extern "C" int uf3_gram_dev(uf3_ctx *c, const double *dx, const double *dy, int6
     // (up to two column ranges the patches are mostly padding: one wave per 32 x 32 tile with direct loads is faster there --
     // measured 0.62 against 0.81 ms at F = 73, 960 k rows)
     // (and below ~64 k rows the row chunks get too short for the slab pipeline: 0.24 against 0.21 ms at 30 001 x 425)
-    if (n_feat > 128 && n_rows >= 65536 && !uf3_env("UF3_GRAM_DIRECT")) {
+    if (n_feat > 128 && n_rows >= 65536) {
         // LDS-tiled kernel: patches of 64 x 64 packed into workgroups (at most four patches on at most four column ranges)
         Timed tm(c, T_GRAM);
         rc = launch_gram_tiled(c, dx, dy, n_rows, n_rows, n_feat, ld, d_gram, d_ord, nullptr, nullptr, nullptr, n_feat);
@@ -3146,7 +3064,7 @@ extern "C" int uf3_gram_dev(uf3_ctx *c, const double *dx, const double *dy, int6
         HIPCHK(c, hipGetLastError());
         return UF3_OK;
     }
-    if (n_feat <= GS_LDW && n_rows >= 16384 && !uf3_env("UF3_GRAM_DIRECT")) {
+    if (n_feat <= GS_LDW && n_rows >= 16384) {
         // narrow matrices: slabs of 32 rows through LDS, every row read once (k_gram_small); about eight workgroups per CU
         const int64_t want_blocks = (int64_t)c->n_cu * 8;
         int64_t rpb = (n_rows + want_blocks - 1) / want_blocks;
@@ -3206,7 +3124,7 @@ extern "C" int uf3_gram_force_rows_dev(uf3_basis *b, const double *d_x_f, const 
     for (int sp = 0; sp < S; sp++) widest = std::max(widest, b->sp_ncols[sp]);
     // One species, a narrow matrix or short segments: the plain product (same result; the zero columns are multiplied).  Also
     // when no species leaves out at least one 64-column range's worth of columns.
-    if (S < 2 || F <= 128 || 3 * n_atoms / S < 65536 || (widest + 63) / 64 >= (F + 63) / 64 || uf3_env("UF3_GRAM_DENSE"))
+    if (S < 2 || F <= 128 || 3 * n_atoms / S < 65536 || (widest + 63) / 64 >= (F + 63) / 64)
         return uf3_gram_dev(c, d_x_f, d_y_f, 3 * n_atoms, F, ld, accumulate, d_gram, d_ord);
     HIPCHK(c, hipSetDevice(c->device));
     int rc = ensure_frag(c);
