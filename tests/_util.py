@@ -45,6 +45,8 @@ def load_case(name):
 FEATURE_CASES = ["case_steel", "case_h2o", "case_h2o_lead0", "case_ch4", "case_ch4_lead0",
                  "case_w128_2body", "case_w16", "case_w16_lead0", "case_w54", "case_nexe32",
                  "case_nexe32_lead0", "case_ternary24_slab", "case_w16_sym1", "case_w16_sym3"]
+# captures beyond three species (tests/golden/make_species_golden.py): case -> the atomic numbers its frame and basis hold
+SPECIES_CASES = {"case_bcc24_s4": [24, 42, 73, 74], "case_bcc16_s8": [1, 6, 28, 40, 42, 74, 78, 92]}
 
 
 def rel_err(a, b):

@@ -11,7 +11,7 @@ import pytest
 from oracle import oracle as O
 from uf3_amd.data.atoms import Atoms, read_extxyz
 from uf3_amd.regression import least_squares as ls
-from _util import GOLDEN, FEATURE_CASES, basis_from_meta, load_case, rel_err, decode_basis_kwargs
+from _util import GOLDEN, FEATURE_CASES, SPECIES_CASES, basis_from_meta, load_case, rel_err, decode_basis_kwargs
 
 TOL = 1e-10  # oracle vs reference feature rows (observed ~1e-15)
 
@@ -29,6 +29,29 @@ def test_feature_rows_and_neighbor_indices(name):
         assert np.array_equal(out["pairs"][pair], d[f"pair{p}_ij"])
     if basis.degree > 2:
         assert np.array_equal(out["n3"], d["n3_ij"])
+    assert out["supercell"]["m"] == int(d["n_supercell"][0])
+
+
+@pytest.mark.parametrize("name", list(SPECIES_CASES))
+def test_feature_rows_beyond_three_species(name):
+    """Four and eight species (Z = 1 ... 92): the oracle's rows and neighbour indices against the reference's.  Every species is
+    in the frame and every pair block of the energy row is touched; every trio block at four species, 274 of 288 at eight (two
+    atoms per species in a 16-atom cell leave a few trios without a triplet)."""
+    d, meta, atoms = load_case(name)
+    basis = basis_from_meta(meta)
+    assert basis.chemical_system.numbers == SPECIES_CASES[name]
+    assert sorted(set(atoms.get_atomic_numbers().tolist())) == SPECIES_CASES[name]
+    ob = O.OracleBasis(basis)
+    out = O.featurize(ob, atoms, energy=True, forces=True, indices=True)
+    assert rel_err(out["xe"], d["xe"]) < TOL and rel_err(out["xf"], d["xf"]) < TOL
+    sizes, offsets = basis.get_interaction_partitions()
+    touched = {k for k, size in sizes.items() if not isinstance(k, str) and np.abs(d["xe"][offsets[k]:offsets[k] + size]).max() > 0}
+    assert set(basis.interactions_map[2]) <= touched
+    assert len(touched & set(basis.interactions_map[3])) == {4: 40, 8: 274}[len(SPECIES_CASES[name])]
+    assert len(basis.interactions_map[2]) == len(SPECIES_CASES[name]) * (len(SPECIES_CASES[name]) + 1) // 2
+    for p, pair in enumerate(basis.interactions_map[2]):
+        assert np.array_equal(out["pairs"][pair], d[f"pair{p}_ij"])
+    assert np.array_equal(out["n3"], d["n3_ij"])
     assert out["supercell"]["m"] == int(d["n_supercell"][0])
 
 
