@@ -666,6 +666,9 @@ def _check_against_oracle(basis, frames, tol=TOL):
         ref = O.featurize(ob, atoms)
         assert rel_err(x_e[k], ref["xe"]) < tol, k
         assert rel_err(x_f[off[k]:off[k + 1]], ref["xf"]) < tol, k
+        # ... and entry by entry: a small column (or a dropped triplet near a cut-off) cannot hide behind the largest entry
+        assert worst_elementwise(x_e[k], ref["xe"], rtol=tol) <= 1.0, k
+        assert worst_elementwise(x_f[off[k]:off[k + 1]], ref["xf"], rtol=tol) <= 1.0, k
     return x_e, x_f
 
 
@@ -1890,6 +1893,7 @@ def test_random_bases_and_cells_against_oracle(seed):
         e, f, _ = calculator.UFCalculator(model).evaluate_frames([atoms])
         e_ref, f_ref = O.evaluate(O.OracleBasis(basis), atoms, coeff)
         assert abs(e[0] - e_ref) <= TOL * max(1.0, abs(e_ref)) and rel_err(f, f_ref) < TOL
+        assert worst_elementwise(f, f_ref, TOL) <= 1.0
 
 
 def _nccl_fit_worker(rank, world, port, out_dir):

@@ -5,9 +5,6 @@ tests/test_oracle_virial.py) on every route and kernel instance, frame by frame 
 alongside.  Every test runs on a fresh context made with UF3_DEBUG_LDS set, whose evaluator names on stderr the k_eval instance
 each call launched: the tests assert that the route they mean to reach is the one that ran.
 """
-import gc
-import re
-
 import numpy as np
 import pytest
 
@@ -16,43 +13,11 @@ from uf3_amd import synthetic, _lib
 from uf3_amd.data.atoms import Atoms
 from uf3_amd.forcefield import calculator
 from uf3_amd.regression import least_squares as ls
-from _util import worst_elementwise
+from _util import dbg, worst_elementwise  # noqa: F401  (dbg: the fixture)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9                  # energies (relative) and forces (entry by entry), as in tests/test_gpu_parity.py
 MOW, NUMS = ['Mo', 'W'], [42, 74]
-
-
-@pytest.fixture
-def dbg(monkeypatch, capfd):
-    """A fresh context that reports its k_eval launches; ``dbg.launches()`` returns (and clears) the flags of every launch
-    since the last look.  Device tables of the bases a test makes belong to that context and are dropped with it."""
-    monkeypatch.setenv("UF3_DEBUG_LDS", "1")
-    monkeypatch.setattr(_lib, "_contexts", {})
-    bases, seen = [], set()
-
-    class Dbg:
-        @staticmethod
-        def basis(b):
-            bases.append(b)
-            return b
-
-        @staticmethod
-        def launches():
-            out = []
-            for line in capfd.readouterr().err.splitlines():
-                m = re.match(r"uf3: k_eval (.*)", line)
-                if m:
-                    out.append({k: int(v) for k, v in (kv.split("=") for kv in m.group(1).split())})
-            seen.update(" ".join(f"{k}={v}" for k, v in d.items() if k not in ("atoms", "cap")) for d in out)
-            return out
-
-    yield Dbg
-    Dbg.launches()
-    print("k_eval instances reached:\n  " + "\n  ".join(sorted(seen)))
-    for b in bases:
-        _lib.drop_device_basis(b)
-    gc.collect()
 
 
 def _model(basis, seed):
