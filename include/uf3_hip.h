@@ -157,6 +157,11 @@ int uf3_fit_use_flat(uf3_fit *fit, double *d_flat);
 /* a call's first chunk holds this fraction of max_atoms_per_chunk and the following ones double it up to the limit (default
  * 0.125: the GPU starts after a short pack and later packs hide behind the previous chunk's kernels; 1: equal chunks) */
 int uf3_fit_first_chunk(uf3_fit *fit, double fraction);
+/* The chunk plan uf3_fit_add makes for these frames, computed on the host alone (no device, no context; test surface):
+ * n_chunks chunks, chunk k ending behind frame chunk_ends[k] (room for n_frames entries; NULL: the count only).  A chunk
+ * holds at most max_atoms atoms (<= 0: 320000) unless it is a single frame. */
+int uf3_fit_plan_debug(int32_t n_frames, const int64_t *atom_counts, int64_t max_atoms, double first_fraction,
+                       int32_t *chunk_ends, int32_t *n_chunks);
 
 /* RCCL behind the C ABI (round 5; SURVEY 8b's `uf3_gram_allreduce`).  One process per GPU.  The one exchange of the path is
  * the SUM over the ranks of the packed normal-equation pieces [G_e | G_f | o_e | o_f | m_e | m_f] (and, for a decomposed
@@ -208,7 +213,9 @@ int uf3_featurize_ld_dev(uf3_basis *basis, const uf3_frames *frames, const doubl
 
 /*
  * Normal-equation pieces of a row block: gram[F][F] (+)= X^T X, ord[F] (+)= X^T y, with
- * X [n_rows][ld] row-major (first F columns used).  accumulate = 0 overwrites.
+ * X [n_rows][ld] row-major (first F columns used).  accumulate = 0 overwrites.  y or ord may be NULL:
+ * then X^T y is not formed, and ord (when given) is zeroed by accumulate = 0 and left as it is by accumulate = 1.
+ * With UF3_DEBUG_LDS set every launch reports its kernel on stderr ("uf3: gram kernel=mfma|small|tiled|tiled_sub ...").
  */
 int uf3_gram(uf3_ctx *ctx, const double *x, const double *y, int64_t n_rows, int32_t n_feat,
              int64_t ld, int accumulate, double *gram, double *ord);

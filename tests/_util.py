@@ -4,6 +4,7 @@ import gc
 import json
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
@@ -279,11 +280,23 @@ def equivalence_cases():
 # ------------------------------------------------------------------------------------------------
 @pytest.fixture
 def dbg(monkeypatch, capfd):
-    """A fresh context that reports its k_eval launches; ``dbg.launches()`` returns (and clears) the flags of every launch
-    since the last look.  Device tables of the bases a test makes belong to that context and are dropped with it."""
+    """A fresh context that reports its k_eval and Gram launches; ``dbg.launches()`` returns (and clears) the flags of every
+    k_eval launch since the last look, ``dbg.grams()`` those of every Gram launch (``kernel`` is mfma, small, tiled or
+    tiled_sub; the other fields are integers).  Device tables of the bases a test makes belong to that context and are dropped
+    with it."""
     monkeypatch.setenv("UF3_DEBUG_LDS", "1")
     monkeypatch.setattr(_lib, "_contexts", {})
     bases, seen = [], set()
+    pending = {"k_eval": [], "gram": []}
+
+    def read():
+        cap = capfd.readouterr()
+        sys.stdout.write(cap.out)                  # (what the test printed stays in its report)
+        for line in cap.err.splitlines():
+            m = re.match(r"uf3: (k_eval|gram) (.*)", line)
+            if m:
+                pending[m.group(1)].append({k: int(v) if v.lstrip("-").isdigit() else v
+                                            for k, v in (kv.split("=") for kv in m.group(2).split())})
 
     class Dbg:
         @staticmethod
@@ -293,17 +306,22 @@ def dbg(monkeypatch, capfd):
 
         @staticmethod
         def launches():
-            out = []
-            for line in capfd.readouterr().err.splitlines():
-                m = re.match(r"uf3: k_eval (.*)", line)
-                if m:
-                    out.append({k: int(v) for k, v in (kv.split("=") for kv in m.group(1).split())})
+            read()
+            out, pending["k_eval"] = pending["k_eval"], []
             seen.update(" ".join(f"{k}={v}" for k, v in d.items() if k not in ("atoms", "cap")) for d in out)
+            return out
+
+        @staticmethod
+        def grams():
+            read()
+            out, pending["gram"] = pending["gram"], []
+            seen.update(f"gram kernel={d['kernel']}" for d in out)
             return out
 
     yield Dbg
     Dbg.launches()
-    print("k_eval instances reached:\n  " + "\n  ".join(sorted(seen)))
+    Dbg.grams()
+    print("k_eval instances and Gram kernels reached:\n  " + "\n  ".join(sorted(seen)))
     for b in bases:
         _lib.drop_device_basis(b)
     gc.collect()

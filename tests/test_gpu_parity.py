@@ -185,6 +185,12 @@ def test_slab_gram_kernel_for_narrow_matrices(shape):
     assert np.abs(g - ref).max() < 1e-12 * np.abs(ref).max()
     assert np.allclose(o, x.T @ y, rtol=1e-11, atol=1e-9)
     assert np.array_equal(g, g.T)
+    # accumulate mode: the same rows again on top of the first result
+    ctx = _lib.get_context()
+    ctx.check(ctx.lib.uf3_gram(ctx.handle, _lib._p(x), _lib._p(y), shape[0], shape[1], shape[1], 1, _lib._p(g), _lib._p(o)))
+    assert np.abs(g - 2 * ref).max() < 2e-12 * np.abs(ref).max()
+    assert np.allclose(o, 2 * (x.T @ y), rtol=1e-11, atol=2e-9)
+    assert np.array_equal(g, g.T)
 
 
 @pytest.mark.parametrize("shape", [(65536, 129), (70013, 257), (66001, 434), (65551, 333)])

@@ -90,6 +90,8 @@ struct uf3_ctx {
     int gram_plan_np[UF3_MAX_SPECIES + 1] = {0}, gram_plan_blocks[UF3_MAX_SPECIES + 1] = {0}, gram_plan_next = 0;   // workgroup plans of k_gram_tiled held in
                                                      // gram_tiles[] (each for this many 64-column ranges; 0: none)
     int gram_direct_feat = 0;                        // tile-pair table of k_gram_mfma held in gram_tij (for this n_feat; 0: none)
+    hipEvent_t sp_done = nullptr;                    // recorded behind the last launch that read sp_rows / sp_seg (on whichever stream)
+    bool sp_done_live = false;
     bool n3_tuned = false;           // capacity re-sized once to the lists actually seen
     bool cand_tuned = false;         // a featurizer call has completed with the current candidate capacity
     // status words of asynchronous featurizer calls: copied to pinned slots behind the launches, looked at later
@@ -313,6 +315,7 @@ extern "C" void uf3_ctx_destroy(uf3_ctx *c) {
     c->pin_in.release(); c->pin_geo.release(); c->pin_out.release(); c->pin_flags.release(); c->pin_eval.release();
     for (auto &pd : c->pending_chk) if (pd.ev) hipEventDestroy(pd.ev);
     if (c->pin_in_done) hipEventDestroy(c->pin_in_done);
+    if (c->sp_done) hipEventDestroy(c->sp_done);
     if (c->pin_geo_done) hipEventDestroy(c->pin_geo_done);
     for (auto &v : c->pending) for (auto &p : v) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     if (c->own_stream) hipStreamDestroy(c->own_stream);
@@ -2624,6 +2627,74 @@ extern "C" int uf3_fit_create(uf3_basis *b, int with_forces, int64_t max_atoms_p
     return UF3_OK;
 }
 
+// The chunks of one uf3_fit_add call, [first, second) frame ranges (round 6: the plan, not the loop, decides).  The ramp:
+// first_fraction of the limit, then doubling -- the GPU starts after a short pack, and the pack of chunk k + 1 (host, about half
+// the GPU's time per frame on a one-species basis) hides behind the kernels of chunk k.  Behind the ramp the remaining frames are
+// spread EVENLY over the fewest chunks of at most the limit (128 frames of 10 k atoms used to end on a 4-frame chunk --
+// 4 + 8 + 16 + 3 x 32 + 4 -- whose launches fill the GPU for a fraction of their tails).  When no even spread keeps every chunk
+// of two or more frames within the limit (uneven frames: [73, 109, 103] at a limit of 120 .. 200), the tail is packed greedily,
+// which always does.  A chunk exceeds max_atoms only when it is a single frame.  Host only (uf3_fit_plan_debug).
+static void fit_plan(int n_frames, const int64_t *atom_counts, int64_t max_atoms, double first_fraction,
+                     std::vector<std::pair<int, int>> &plan) {
+    plan.clear();
+    double fr_ = first_fraction;
+    int s0 = 0;
+    while (s0 < n_frames && fr_ < 1.0) {
+        const int64_t limit = std::max<int64_t>(1, (int64_t)(max_atoms * fr_));
+        fr_ = std::min(1.0, 2.0 * fr_);
+        int s1 = s0;
+        int64_t atoms = 0;
+        while (s1 < n_frames && (s1 == s0 || atoms + atom_counts[s1] <= limit)) atoms += atom_counts[s1++];
+        plan.emplace_back(s0, s1);
+        s0 = s1;
+    }
+    if (s0 >= n_frames) return;
+    int64_t rest = 0;
+    for (int i = s0; i < n_frames; i++) rest += atom_counts[i];
+    for (int64_t n_chunks = (rest + max_atoms - 1) / max_atoms;; n_chunks++) {
+        // chunk k ends behind the first frame at which the running atom count reaches (k + 1) / n_chunks of the rest
+        std::vector<std::pair<int, int>> tail;
+        int q0 = s0;
+        int64_t run = 0;
+        bool fits = true;
+        for (int64_t k = 0; k < n_chunks && q0 < n_frames; k++) {
+            const int64_t target = (rest * (k + 1) + n_chunks - 1) / n_chunks;
+            int q1 = q0;
+            int64_t atoms = 0;
+            while (q1 < n_frames && (q1 == q0 || run + atoms < target)) atoms += atom_counts[q1++];
+            if (k == n_chunks - 1) while (q1 < n_frames) atoms += atom_counts[q1++];
+            fits = fits && (atoms <= max_atoms || q1 == q0 + 1);
+            run += atoms;
+            tail.emplace_back(q0, q1);
+            q0 = q1;
+        }
+        if (fits) { plan.insert(plan.end(), tail.begin(), tail.end()); return; }
+        if (n_chunks >= n_frames - s0) break;
+    }
+    // no even spread fits: greedy, each chunk as many frames as stay within the limit
+    while (s0 < n_frames) {
+        int s1 = s0;
+        int64_t atoms = 0;
+        while (s1 < n_frames && (s1 == s0 || atoms + atom_counts[s1] <= max_atoms)) atoms += atom_counts[s1++];
+        plan.emplace_back(s0, s1);
+        s0 = s1;
+    }
+}
+
+extern "C" int uf3_fit_plan_debug(int32_t n_frames, const int64_t *atom_counts, int64_t max_atoms, double first_fraction,
+                                  int32_t *chunk_ends, int32_t *n_chunks) {
+    if (n_frames < 0 || (n_frames && !atom_counts) || !n_chunks || !(first_fraction > 0.0) || first_fraction > 1.0)
+        return fail(nullptr, UF3_EINVAL, "uf3_fit_plan_debug: bad argument");
+    for (int i = 0; i < n_frames; i++)
+        if (atom_counts[i] <= 0) return fail(nullptr, UF3_EINVAL, "uf3_fit_plan_debug: a frame without atoms");
+    std::vector<std::pair<int, int>> plan;
+    fit_plan(n_frames, atom_counts, max_atoms > 0 ? max_atoms : 320000, first_fraction, plan);
+    *n_chunks = (int32_t)plan.size();
+    if (chunk_ends)
+        for (size_t k = 0; k < plan.size(); k++) chunk_ends[k] = plan[k].second;
+    return UF3_OK;
+}
+
 // frames: n_frames entries each of atom_counts / pos[f] ([N_f][3]) / z[f] ([N_f], int64 when z_is_int64 else int32) / cells
 // ([n_frames][9]) / pbc ([n_frames][3]) / energies (total energy of the frame) / forces[f] ([N_f][3]; null array: no forces)
 extern "C" int uf3_fit_add(uf3_fit *f, int32_t n_frames, const int64_t *atom_counts, const double *const *pos, const void *const *z,
@@ -2639,50 +2710,11 @@ extern "C" int uf3_fit_add(uf3_fit *f, int32_t n_frames, const int64_t *atom_cou
     int start = 0;
     for (int i = 0; i < n_frames; i++)
         if (atom_counts[i] <= 0) return fail(c, UF3_EINVAL, "uf3_fit_add: a frame without atoms (its per-atom energy target is undefined)");
-    // chunk sizes grow geometrically from first_fraction of the limit: the GPU starts after a short pack, and the pack of
-    // chunk k + 1 (host, about half the GPU's time per frame on a one-species basis) hides behind the kernels of chunk k
-    // The chunks of this call, planned ahead (round 6: the plan, not the loop, decides).  The ramp: first_fraction of the limit, then
-    // doubling -- the GPU starts after a short pack.  Behind the ramp the remaining frames are spread EVENLY over the fewest chunks
-    // of at most the limit (128 frames of 10 k atoms used to end on a 4-frame chunk -- 4 + 8 + 16 + 3 x 32 + 4 -- whose launches
-    // fill the GPU for a fraction of their tails).  Every buffer is sized ONCE for the largest chunk (a Buf that grows chunk by
+    // the chunks of this call, planned ahead (fit_plan).  Every buffer is sized ONCE for the largest chunk (a Buf that grows chunk by
     // chunk frees and allocates -- an implicit device synchronisation -- in the middle of the copy / compute overlap).
     std::vector<std::pair<int, int>> plan;
     {
-        double fr_ = f->first_fraction;
-        int s0 = 0;
-        while (s0 < n_frames && fr_ < 1.0) {
-            const int64_t limit = std::max<int64_t>(1, (int64_t)(f->max_atoms * fr_));
-            fr_ = std::min(1.0, 2.0 * fr_);
-            int s1 = s0;
-            int64_t atoms = 0;
-            while (s1 < n_frames && (s1 == s0 || atoms + atom_counts[s1] <= limit)) atoms += atom_counts[s1++];
-            plan.emplace_back(s0, s1);
-            s0 = s1;
-        }
-        if (s0 < n_frames) {
-            int64_t rest = 0;
-            for (int i = s0; i < n_frames; i++) rest += atom_counts[i];
-            int64_t n_chunks = (rest + f->max_atoms - 1) / f->max_atoms;
-            for (;; n_chunks++) {
-                // chunk k ends behind the first frame at which the running atom count reaches (k + 1) / n_chunks of the rest
-                std::vector<std::pair<int, int>> tail;
-                int q0 = s0;
-                int64_t run = 0;
-                bool fits = true;
-                for (int64_t k = 0; k < n_chunks && q0 < n_frames; k++) {
-                    const int64_t target = (rest * (k + 1) + n_chunks - 1) / n_chunks;
-                    int q1 = q0;
-                    int64_t atoms = 0;
-                    while (q1 < n_frames && (q1 == q0 || run + atoms < target)) atoms += atom_counts[q1++];
-                    if (k == n_chunks - 1) while (q1 < n_frames) atoms += atom_counts[q1++];
-                    fits = fits && (atoms <= f->max_atoms || q1 == q0 + 1);
-                    run += atoms;
-                    tail.emplace_back(q0, q1);
-                    q0 = q1;
-                }
-                if (fits || n_chunks >= n_frames - s0) { plan.insert(plan.end(), tail.begin(), tail.end()); break; }
-            }
-        }
+        fit_plan(n_frames, atom_counts, f->max_atoms, f->first_fraction, plan);
         int64_t big_atoms = 0, big_block = 0;
         int big_nf = 0;
         for (const auto &ch : plan) {
@@ -2938,7 +2970,7 @@ static int ensure_frag(uf3_ctx *c) {
 // to hold (the chunks are cut for it; workgroups past the segment leave at once).  Accumulates the upper triangle.
 static int launch_gram_tiled(uf3_ctx *c, const double *dx, const double *dy, int64_t n_rows, int64_t n_rows_plan, int n_feat,
                              int64_t ld, double *d_gram, double *d_ord, const int *rowmap, const int *seg, const int *colmap,
-                             int n_cols) {
+                             int n_cols, int accumulate) {
     hipStream_t st = c->stream;
     const int np = (n_cols + 63) / 64;
     // LDS-tiled kernel: patches of 64 x 64 packed into workgroups (at most four patches on at most four column ranges)
@@ -2946,6 +2978,7 @@ static int launch_gram_tiled(uf3_ctx *c, const double *dx, const double *dy, int
     // (one slot per species' column subset + the full matrix: a basis of UF3_MAX_SPECIES species never evicts)
     const int n_slots = UF3_MAX_SPECIES + 1;
     for (int q = 0; q < n_slots; q++) if (c->gram_plan_np[q] == np) ps = q;
+    const bool plan_new = ps < 0;
     if (ps < 0) {
         ps = c->gram_plan_next;
         c->gram_plan_next = (ps + 1) % n_slots;
@@ -3035,6 +3068,11 @@ static int launch_gram_tiled(uf3_ctx *c, const double *dx, const double *dy, int
                            ld, (int)rpc, bpc, (const GramBlock *)c->gram_tiles[ps].p, c->frag.as<int>(), d_gram, d_ord,
                            (const int *)nullptr, (const int *)nullptr, (const int *)nullptr, n_feat);
     HIPCHK(c, hipGetLastError());
+    // (UF3_DEBUG_LDS: which Gram kernel ran, as the k_eval lines -- tests assert the route they mean to reach)
+    if (c->env_debug_lds)
+        fprintf(stderr, "uf3: gram kernel=%s rows=%lld feat=%d ld=%lld acc=%d ord=%d cols=%d plan_slot=%d plan_new=%d\n",
+                rowmap ? "tiled_sub" : "tiled", (long long)n_rows, n_feat, (long long)ld, accumulate ? 1 : 0, (d_ord && dy) ? 1 : 0,
+                n_cols, ps, (int)plan_new);
     return UF3_OK;
 }
 
@@ -3043,6 +3081,7 @@ extern "C" int uf3_gram_dev(uf3_ctx *c, const double *dx, const double *dy, int6
     uf3_env_refresh();
     if (!c) return fail(nullptr, UF3_EINVAL, "null ctx");
     if (!dx || !d_gram || n_feat < 1 || ld < n_feat || n_rows < 0) return fail(c, UF3_EINVAL, "uf3_gram: bad argument");
+    read_f3_env(c);
     HIPCHK(c, hipSetDevice(c->device));
     int rc = ensure_frag(c);
     if (rc) return rc;
@@ -3058,7 +3097,7 @@ extern "C" int uf3_gram_dev(uf3_ctx *c, const double *dx, const double *dy, int6
     if (n_feat > 128 && n_rows >= 65536) {
         // LDS-tiled kernel: patches of 64 x 64 packed into workgroups (at most four patches on at most four column ranges)
         Timed tm(c, T_GRAM);
-        rc = launch_gram_tiled(c, dx, dy, n_rows, n_rows, n_feat, ld, d_gram, d_ord, nullptr, nullptr, nullptr, n_feat);
+        rc = launch_gram_tiled(c, dx, dy, n_rows, n_rows, n_feat, ld, d_gram, d_ord, nullptr, nullptr, nullptr, n_feat, accumulate);
         if (rc) return rc;
         hipLaunchKernelGGL(k_gram_mirror, dim3((n_feat + 255) / 256, n_feat), dim3(256), 0, st, d_gram, n_feat);
         HIPCHK(c, hipGetLastError());
@@ -3075,6 +3114,9 @@ extern "C" int uf3_gram_dev(uf3_ctx *c, const double *dx, const double *dy, int6
                            rpb, c->frag.as<int>(), d_gram, d_ord);
         hipLaunchKernelGGL(k_gram_mirror, dim3((n_feat + 255) / 256, n_feat), dim3(256), 0, st, d_gram, n_feat);
         HIPCHK(c, hipGetLastError());
+        if (c->env_debug_lds)
+            fprintf(stderr, "uf3: gram kernel=small rows=%lld feat=%d ld=%lld acc=%d ord=%d\n", (long long)n_rows, n_feat, (long long)ld,
+                    accumulate ? 1 : 0, (d_ord && dy) ? 1 : 0);
         return UF3_OK;
     }
     // tile-pair table of the direct kernel: built and uploaded when n_feat changes (its own buffer and key: a fit that sends
@@ -3082,13 +3124,17 @@ extern "C" int uf3_gram_dev(uf3_ctx *c, const double *dx, const double *dy, int6
     const int nt = (n_feat + 31) / 32;
     size_t np = (size_t)nt * (nt + 1) / 2;
     np = (np + 3) / 4 * 4;
-    if (c->gram_direct_feat != n_feat) {
+    const bool table_new = c->gram_direct_feat != n_feat;
+    if (table_new) {
         std::vector<int> tij;
         for (int i = 0; i < nt; i++) for (int j = i; j < nt; j++) tij.push_back(i);
         while (tij.size() < np) tij.push_back(-1);
         for (int i = 0; i < nt; i++) for (int j = i; j < nt; j++) tij.push_back(j);
         while (tij.size() < 2 * np) tij.push_back(-1);
         c->gram_direct_feat = 0;
+        // (a k_gram_mfma on this or an earlier stream of the context may still be reading the table this one overwrites in place
+        // when it fits the buffer: the same order as the tiled plan's)
+        if (c->gram_tij.p) HIPCHK(c, hipDeviceSynchronize());
         HIPCHK(c, c->gram_tij.ensure(8 * np));
         HIPCHK(c, hipMemcpyAsync(c->gram_tij.p, tij.data(), 8 * np, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipStreamSynchronize(st));                           // (tij is a local)
@@ -3109,6 +3155,9 @@ extern "C" int uf3_gram_dev(uf3_ctx *c, const double *dx, const double *dy, int6
         hipLaunchKernelGGL(k_gram_mirror, dim3((n_feat + 255) / 256, n_feat), dim3(256), 0, st, d_gram, n_feat);
     }
     HIPCHK(c, hipGetLastError());
+    if (c->env_debug_lds)
+        fprintf(stderr, "uf3: gram kernel=mfma rows=%lld feat=%d ld=%lld acc=%d ord=%d table_new=%d\n", (long long)n_rows, n_feat,
+                (long long)ld, accumulate ? 1 : 0, (d_ord && dy) ? 1 : 0, (int)table_new);
     return UF3_OK;
 }
 
@@ -3120,6 +3169,7 @@ extern "C" int uf3_gram_force_rows_dev(uf3_basis *b, const double *d_x_f, const 
     const int F = b->host.F, S = b->host.S;
     if (!d_x_f || !d_gram || !d_z || n_atoms < 0 || ld < F || 3 * n_atoms > INT32_MAX)
         return fail(c, UF3_EINVAL, "uf3_gram_force_rows_dev: bad argument");
+    read_f3_env(c);
     int widest = 0;
     for (int sp = 0; sp < S; sp++) widest = std::max(widest, b->sp_ncols[sp]);
     // One species, a narrow matrix or short segments: the plain product (same result; the zero columns are multiplied).  Also
@@ -3141,6 +3191,9 @@ extern "C" int uf3_gram_force_rows_dev(uf3_basis *b, const double *d_x_f, const 
     HIPCHK(c, c->sp_seg.ensure(sizeof(int) * 3 * UF3_MAX_SPECIES));
     int *seg = c->sp_seg.as<int>(), *cursor = seg + 2 * UF3_MAX_SPECIES, *rows = c->sp_rows.as<int>();
     Timed tm(c, T_GRAM);
+    // the lists are refilled in place: after the previous call's launches that read them, whichever stream they ran on
+    if (!c->sp_done) HIPCHK(c, hipEventCreateWithFlags(&c->sp_done, hipEventDisableTiming));
+    if (c->sp_done_live) HIPCHK(c, hipStreamWaitEvent(st, c->sp_done, 0));
     HIPCHK(c, hipMemsetAsync(seg, 0, sizeof(int) * 3 * UF3_MAX_SPECIES, st));
     // (the whole list: k_species_rows skips atoms whose species is outside the basis, so entries between the end of the segments
     // and 3 n_atoms would otherwise be uninitialised row indices for the kernel's one-slab-ahead prefetch; 12 bytes per atom)
@@ -3151,9 +3204,11 @@ extern "C" int uf3_gram_force_rows_dev(uf3_basis *b, const double *d_x_f, const 
     for (int sp = 0; sp < S; sp++) {
         if (b->sp_ncols[sp] == 0) continue;
         rc = launch_gram_tiled(c, d_x_f, d_y_f, 3 * n_atoms, 3 * n_atoms / S, F, ld, d_gram, d_ord, rows, seg + 2 * sp,
-                               b->d_sp_cols + (size_t)sp * F, b->sp_ncols[sp]);
+                               b->d_sp_cols + (size_t)sp * F, b->sp_ncols[sp], accumulate);
         if (rc) return rc;
     }
+    HIPCHK(c, hipEventRecord(c->sp_done, st));
+    c->sp_done_live = true;
     hipLaunchKernelGGL(k_gram_mirror, dim3((F + 255) / 256, F), dim3(256), 0, st, d_gram, F);
     HIPCHK(c, hipGetLastError());
     return UF3_OK;
