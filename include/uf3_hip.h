@@ -106,7 +106,7 @@ int uf3_ctx_use_own_stream(uf3_ctx *ctx);
 int uf3_ctx_synchronize(uf3_ctx *ctx);
 const char *uf3_last_error(const uf3_ctx *ctx);
 /* Which sources this binary was compiled from: the first 16 hex digits of the sha256 over uf3_hip.hip, uf3_kernels.h,
- * uf3_feat3.h, uf3_device.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
+ * uf3_feat3.h, uf3_device.h, uf3_md.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
  * outside it).  __graft_entry__.build() rebuilds when it differs from the tree's, smoke() prints it. */
 const char *uf3_build_id(void);
 /* timing of the dominant kernel: (re)start / read accumulated HIP-event time in ms and launches */
@@ -388,6 +388,44 @@ int uf3_scan_solve_dev(uf3_ctx *ctx, int32_t n_cols, int32_t n_folds, const doub
                        const int64_t *d_col_off, const int32_t *d_reg_rc, const double *d_reg_v, const int64_t *d_reg_off,
                        int32_t n_sys, int64_t total_rows, const int64_t *d_sys, const double *d_sys_w, double *d_ws,
                        int64_t ws_len, double *d_x, int64_t x_len, double *d_sse, int32_t *d_status);
+
+/*
+ * Molecular dynamics on the device (uf3_amd.forcefield.md.MolecularDynamics; kernels in uf3_md.h).  The object owns positions
+ * (kept UNWRAPPED: the evaluator bins wrapped copies itself), velocities, forces, inverse masses and species of a batch of frames
+ * in HBM and steps them with velocity Verlet (friction 0) or BAOAB Langevin dynamics; the forces come from the evaluator
+ * (uf3_eval[_virial]_dev's code path) between two fused integrator launches.  Units: Angstrom, fs, amu, eV, K.
+ *   uf3_md_create          copies frames, positions [N][3], velocities [N][3] (NULL: zero), species, masses [N] and the model
+ *                          (c1 / c2 / c3 as for uf3_eval) into the object; no evaluation yet.  Masses positive and finite.
+ *   uf3_md_set_state       host arrays in; NULL keeps that part.  New positions invalidate the forces.
+ *   uf3_md_get_state       host arrays out; NULL skips.  Forces / energies of positions set since the last evaluation are
+ *                          evaluated first.
+ *   uf3_md_init_velocities Maxwell-Boltzmann velocities at temperature_K from the Philox stream (draws 2, 3 of the current
+ *                          step), each frame's centre-of-mass velocity removed; exact_temperature: each frame rescaled to
+ *                          exactly temperature_K with 3N degrees of freedom (a frame whose kinetic energy is 0 stays at rest).
+ *   uf3_md_run             n_steps steps of dt_fs; friction_per_fs > 0: Langevin at temperature_K, 0: NVE.  Normals of atom i
+ *                          in the step opened at absolute step s: Philox4x32-10, counter (i, s lo, s hi, 0 / 1), key (seed lo,
+ *                          seed hi), Box-Muller -- run(a); run(b) equals run(a + b).  The context's MD skin is `skin` for the
+ *                          run and the caller's again on return (also on errors); the change drops the neighbour lists, so
+ *                          every run starts with one list build.  A 2-body-only basis never takes the MD route and rebuilds its
+ *                          lists on every step.  thermo_every > 0: one record per frame after every thermo_every-th step of the
+ *                          run, [PE, KE] or, with_stress, [PE, KE, W (6), K (6)] (W = dE/d(strain), Voigt order; K = sum m v (x) v,
+ *                          eV); thermo must then hold n_steps / thermo_every records (NULL when none is due).  A force call that
+ *                          fails returns its code; the step counter then counts the completed steps and the state is that of
+ *                          the failed step's drift.
+ *   uf3_md_info            absolute step counter, atoms, frames.
+ *   uf3_philox_debug       Philox4x32-10 on the device for caller-given counters [n][4] and keys [n][2] (tests).
+ */
+typedef struct uf3_md uf3_md;
+int uf3_md_create(uf3_basis *basis, const uf3_frames *frames, const double *pos, const double *vel, const int32_t *z,
+                  const double *masses, const double *c1, const double *c2, const double *c3, uf3_md **out);
+void uf3_md_destroy(uf3_md *md);
+int uf3_md_set_state(uf3_md *md, const double *pos, const double *vel);
+int uf3_md_get_state(uf3_md *md, double *pos, double *vel, double *forces, double *energies /*[n_frames]*/);
+int uf3_md_init_velocities(uf3_md *md, double temperature_K, uint64_t seed, int exact_temperature);
+int uf3_md_run(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed, double skin,
+               int64_t thermo_every, int with_stress, double *thermo);
+int uf3_md_info(const uf3_md *md, int64_t *step, int64_t *n_atoms, int32_t *n_frames);
+int uf3_philox_debug(uf3_ctx *ctx, int64_t n, const uint32_t *counters, const uint32_t *keys, uint32_t *out);
 
 /*
  * Dense helpers behind the module-level functions of uf3.representation.distances / angles, for frames small enough

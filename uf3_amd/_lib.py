@@ -28,10 +28,12 @@ EXPORTS = ["uf3_ctx_create", "uf3_ctx_destroy", "uf3_ctx_set_stream", "uf3_ctx_s
            "uf3_featurize_ld_dev", "uf3_fit_create", "uf3_fit_destroy", "uf3_fit_reset", "uf3_fit_add", "uf3_fit_pack", "uf3_fit_info", "uf3_fit_use_flat", "uf3_fit_first_chunk",
            "uf3_fit_plan_debug",
            "uf3_comm_unique_id", "uf3_comm_init", "uf3_comm_destroy", "uf3_comm_info", "uf3_allreduce_sum_f64", "uf3_gram_allreduce",
-           "uf3_pair_histogram", "uf3_pair_histogram_dev", "uf3_scan_solve_dev"]
+           "uf3_pair_histogram", "uf3_pair_histogram_dev", "uf3_scan_solve_dev",
+           "uf3_md_create", "uf3_md_destroy", "uf3_md_set_state", "uf3_md_get_state", "uf3_md_init_velocities", "uf3_md_run",
+           "uf3_md_info", "uf3_philox_debug"]
 
 
-SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_device.h", os.path.join("..", "..", "include", "uf3_hip.h"))
+SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_device.h", "uf3_md.h", os.path.join("..", "..", "include", "uf3_hip.h"))
 
 
 def source_build_id(csrc_dir=None):
@@ -184,6 +186,15 @@ def load():
         for name in ("uf3_pair_histogram", "uf3_pair_histogram_dev"):
             getattr(lib, name).argtypes = [vp, C.POINTER(Frames), vp, vp, i32, vp, C.c_int, vp, i64, C.c_int, vp]
         lib.uf3_scan_solve_dev.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp]
+        lib.uf3_md_create.argtypes = [vp, C.POINTER(Frames), vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
+        lib.uf3_md_destroy.argtypes = [vp]
+        lib.uf3_md_destroy.restype = None
+        lib.uf3_md_set_state.argtypes = [vp, vp, vp]
+        lib.uf3_md_get_state.argtypes = [vp, vp, vp, vp, vp]
+        lib.uf3_md_init_velocities.argtypes = [vp, dbl, C.c_uint64, C.c_int]
+        lib.uf3_md_run.argtypes = [vp, i64, dbl, dbl, dbl, C.c_uint64, dbl, i64, C.c_int, vp]
+        lib.uf3_md_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]
+        lib.uf3_philox_debug.argtypes = [vp, i64, vp, vp, vp]
         _lib = lib
         return lib
 

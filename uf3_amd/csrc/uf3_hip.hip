@@ -16,6 +16,7 @@
 #include "../../include/uf3_hip.h"
 #include "uf3_kernels.h"
 #include "uf3_feat3.h"
+#include "uf3_md.h"
 #include <chrono>
 #include <dlfcn.h>
 
@@ -3554,6 +3555,263 @@ extern "C" int uf3_direction_cosines(uf3_ctx *c, const double *sup_pos, int64_t 
                        (long long)n_d, (long long)n_atoms, d_out);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, d_out, 8 * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return UF3_OK;
+}
+
+// ------------------------------------------------------------------------------ molecular dynamics (uf3_md_*, uf3_md.h)
+// A library-owned state: positions (unwrapped), velocities, forces, inverse masses and species in HBM, stepped by k_md_step
+// between calls of the evaluator (eval_impl, unchanged).  Between two launches the velocities are at integer time t and the
+// forces are F(t): a launch closes step t with a half-kick and opens step t + 1 (half-kick, drift; BAOAB's A-O-A with friction).
+struct uf3_md {
+    uf3_basis *b = nullptr;
+    uf3_ctx *c = nullptr;
+    int32_t n_frames = 0;
+    int64_t natoms = 0;
+    std::vector<int64_t> offsets;
+    std::vector<double> cells;
+    std::vector<uint8_t> pbc;
+    uf3_frames fr{};
+    std::vector<double> c1, c2, c3;             // the model (host copies: eval_impl takes host coefficients)
+    Buf pos, vel, frc, inv_m, z, offsets_dev, energies, virials, kin, ring;
+    int64_t step = 0;                           // absolute step counter (feeds the random numbers)
+    bool forces_valid = false;                  // frc / energies describe pos
+};
+
+extern "C" void uf3_md_destroy(uf3_md *md) {
+    if (!md) return;
+    hipSetDevice(md->c->device);
+    hipStreamSynchronize(md->c->stream);
+    for (Buf *p : {&md->pos, &md->vel, &md->frc, &md->inv_m, &md->z, &md->offsets_dev, &md->energies, &md->virials, &md->kin, &md->ring})
+        p->release();
+    delete md;
+}
+
+static bool md_finite(const double *a, size_t n) {
+    for (size_t i = 0; i < n; i++) if (!std::isfinite(a[i])) return false;
+    return true;
+}
+
+static int md_upload(uf3_md *md, const double *pos, const double *vel) {
+    uf3_ctx *c = md->c;
+    const size_t n3 = 3 * (size_t)md->natoms;
+    if (pos && !md_finite(pos, n3)) return fail(c, UF3_EINVAL, "uf3_md: positions must be finite");
+    if (vel && !md_finite(vel, n3)) return fail(c, UF3_EINVAL, "uf3_md: velocities must be finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (pos) HIPCHK(c, hipMemcpyAsync(md->pos.p, pos, 8 * n3, hipMemcpyHostToDevice, c->stream));
+    if (vel) HIPCHK(c, hipMemcpyAsync(md->vel.p, vel, 8 * n3, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (pos) md->forces_valid = false;
+    return UF3_OK;
+}
+
+extern "C" int uf3_md_create(uf3_basis *b, const uf3_frames *fr, const double *pos, const double *vel, const int32_t *z,
+                             const double *masses, const double *c1, const double *c2, const double *c3, uf3_md **out) {
+    if (!b || !out) return fail(b ? b->ctx : nullptr, UF3_EINVAL, "uf3_md_create: null argument");
+    uf3_ctx *c = b->ctx;
+    if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, "uf3_md_create: bad uf3_frames");
+    if (!pos || !z || !masses || !c1 || (b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, "uf3_md_create: null argument");
+    const int nf = fr->n_frames;
+    if (fr->atom_offsets[0] != 0) return fail(c, UF3_EINVAL, "uf3_md_create: atom_offsets[0] must be 0");
+    for (int f = 0; f < nf; f++)
+        if (fr->atom_offsets[f + 1] <= fr->atom_offsets[f]) return fail(c, UF3_EINVAL, "uf3_md_create: every frame needs an atom");
+    const int64_t n = fr->atom_offsets[nf];
+    if (n >= (1LL << 28)) return fail(c, UF3_EINVAL, "uf3_md_create: batch must hold 1 .. 2^28 atoms");
+    std::vector<double> inv(n);
+    for (int64_t i = 0; i < n; i++) {
+        if (!(masses[i] > 0.0) || !std::isfinite(masses[i])) return fail(c, UF3_EINVAL, "uf3_md_create: masses must be positive and finite");
+        inv[i] = 1.0 / masses[i];
+    }
+    if (!md_finite(fr->cells, 9 * (size_t)nf)) return fail(c, UF3_EINVAL, "uf3_md_create: cells must be finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    uf3_md *md = new uf3_md();
+    md->b = b; md->c = c; md->n_frames = nf; md->natoms = n;
+    md->offsets.assign(fr->atom_offsets, fr->atom_offsets + nf + 1);
+    md->cells.assign(fr->cells, fr->cells + 9 * (size_t)nf);
+    md->pbc.assign(fr->pbc, fr->pbc + 3 * (size_t)nf);
+    md->fr.n_frames = nf; md->fr.atom_offsets = md->offsets.data(); md->fr.cells = md->cells.data(); md->fr.pbc = md->pbc.data();
+    md->c1.assign(c1, c1 + b->host.S);
+    md->c2.assign(c2 ? c2 : c1, (c2 ? c2 : c1) + b->c2_len); md->c2.push_back(0.0);
+    md->c3.assign(c3 ? c3 : c1, (c3 ? c3 : c1) + b->c3_len); md->c3.push_back(0.0);
+    auto bail = [&](int rc) { uf3_md_destroy(md); return rc; };
+    const size_t n3 = 3 * (size_t)n;
+    if (md->pos.ensure(8 * n3) || md->vel.ensure(8 * n3) || md->frc.ensure(8 * n3) || md->inv_m.ensure(8 * (size_t)n) ||
+        md->z.ensure(4 * (size_t)n) || md->offsets_dev.ensure(8 * (size_t)(nf + 1)) || md->energies.ensure(8 * (size_t)nf) ||
+        md->virials.ensure(48 * (size_t)nf))
+        return bail(fail(c, UF3_ENOMEM, "uf3_md_create: out of device memory"));
+    if (hipMemcpyAsync(md->inv_m.p, inv.data(), 8 * (size_t)n, hipMemcpyHostToDevice, c->stream) ||
+        hipMemcpyAsync(md->z.p, z, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream) ||
+        hipMemcpyAsync(md->offsets_dev.p, md->offsets.data(), 8 * (size_t)(nf + 1), hipMemcpyHostToDevice, c->stream) ||
+        hipMemsetAsync(md->vel.p, 0, 8 * n3, c->stream))
+        return bail(fail(c, UF3_EHIP, "uf3_md_create: upload failed"));
+    int rc = md_upload(md, pos, vel);
+    if (rc) return bail(rc);
+    *out = md;
+    return UF3_OK;
+}
+
+extern "C" int uf3_md_set_state(uf3_md *md, const double *pos, const double *vel) {
+    if (!md) return fail(nullptr, UF3_EINVAL, "null md");
+    return md_upload(md, pos, vel);
+}
+
+// F(t) and the per-frame energies (and strain derivatives) of the current positions
+static int md_forces(uf3_md *md, bool virial) {
+    int rc = eval_impl(md->b, &md->fr, md->pos.as<double>(), md->z.as<int32_t>(), md->c1.data(), md->c2.data(), md->c3.data(),
+                       md->energies.as<double>(), md->frc.as<double>(), virial ? md->virials.as<double>() : nullptr);
+    md->forces_valid = rc == UF3_OK;
+    return rc;
+}
+
+extern "C" int uf3_md_get_state(uf3_md *md, double *pos, double *vel, double *forces, double *energies) {
+    if (!md) return fail(nullptr, UF3_EINVAL, "null md");
+    uf3_ctx *c = md->c;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((forces || energies) && !md->forces_valid) {        // (positions set since the last evaluation: evaluate them now)
+        int rc = md_forces(md, false);
+        if (rc) return rc;
+    }
+    const size_t n3 = 3 * (size_t)md->natoms;
+    if (pos) HIPCHK(c, hipMemcpyAsync(pos, md->pos.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
+    if (vel) HIPCHK(c, hipMemcpyAsync(vel, md->vel.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
+    if (forces) HIPCHK(c, hipMemcpyAsync(forces, md->frc.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
+    if (energies) HIPCHK(c, hipMemcpyAsync(energies, md->energies.p, 8 * (size_t)md->n_frames, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return UF3_OK;
+}
+
+extern "C" int uf3_md_init_velocities(uf3_md *md, double temperature_K, uint64_t seed, int exact_temperature) {
+    if (!md) return fail(nullptr, UF3_EINVAL, "null md");
+    uf3_ctx *c = md->c;
+    if (!(temperature_K >= 0.0) || !std::isfinite(temperature_K)) return fail(c, UF3_EINVAL, "uf3_md_init_velocities: temperature must be finite and >= 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_md_init_velocities, dim3((unsigned)((md->natoms + 255) / 256)), dim3(256), 0, c->stream, md->vel.as<double>(),
+                       (const double *)md->inv_m.as<double>(), (long long)md->natoms, UF3_MD_KB * temperature_K, (unsigned long long)seed,
+                       (unsigned long long)md->step);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_md_init_com, dim3((unsigned)md->n_frames), dim3(UF3_MD_THREADS), 0, c->stream, md->vel.as<double>(),
+                       (const double *)md->inv_m.as<double>(), (const int64_t *)md->offsets_dev.as<int64_t>(), UF3_MD_KB * temperature_K,
+                       exact_temperature ? 1 : 0);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return UF3_OK;
+}
+
+// one k_md_step launch (+ the frame sums of a thermo record when `record` >= 0)
+static int md_launch(uf3_md *md, MdStepArgs &A, bool langevin, int64_t record, int width) {
+    uf3_ctx *c = md->c;
+    const bool thermo = record >= 0;
+    const dim3 g((unsigned)((md->natoms + 255) / 256)), blk(256);
+    if (langevin) {
+        if (thermo) hipLaunchKernelGGL((k_md_step<true, true>), g, blk, 0, c->stream, A);
+        else hipLaunchKernelGGL((k_md_step<true, false>), g, blk, 0, c->stream, A);
+    } else {
+        if (thermo) hipLaunchKernelGGL((k_md_step<false, true>), g, blk, 0, c->stream, A);
+        else hipLaunchKernelGGL((k_md_step<false, false>), g, blk, 0, c->stream, A);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (thermo) {
+        hipLaunchKernelGGL(k_md_thermo, dim3((unsigned)md->n_frames), dim3(UF3_MD_THREADS), 0, c->stream, (const double *)md->kin.as<double>(),
+                           (long long)md->natoms, (const int64_t *)md->offsets_dev.as<int64_t>(), (const double *)md->energies.as<double>(),
+                           (const double *)md->virials.as<double>(), md->ring.as<double>() + (size_t)record * md->n_frames * width, width);
+        HIPCHK(c, hipGetLastError());
+    }
+    return UF3_OK;
+}
+
+static int md_run(uf3_md *md, int64_t n_steps, double dt, double T, double gamma, uint64_t seed, int64_t every, bool stress,
+                  double *thermo) {
+    uf3_ctx *c = md->c;
+    const int width = stress ? 14 : 2;
+    const int64_t n_rec = every ? n_steps / every : 0;
+    if (n_rec) {
+        HIPCHK(c, md->ring.ensure(8 * (size_t)n_rec * md->n_frames * width));
+        HIPCHK(c, md->kin.ensure(56 * (size_t)md->natoms));
+    }
+    if (!md->forces_valid) {
+        int rc = md_forces(md, false);
+        if (rc) return rc;
+    }
+    const bool langevin = gamma > 0.0;
+    MdStepArgs A;
+    A.pos = md->pos.as<double>(); A.vel = md->vel.as<double>(); A.frc = md->frc.as<double>(); A.inv_m = md->inv_m.as<double>();
+    A.kin = md->kin.as<double>(); A.n = md->natoms; A.dt = dt;
+    A.c = std::exp(-gamma * dt); A.kT = UF3_MD_KB * T; A.seed = (unsigned long long)seed;
+    const int64_t t0 = md->step;
+    for (int64_t k = 1; k <= n_steps; k++) {
+        // closes step k - 1 of the run (its record, if due) and opens step k
+        A.step = (unsigned long long)(t0 + k - 1); A.close = k > 1; A.open = 1;
+        const bool rec = k > 1 && every && (k - 1) % every == 0;
+        int rc = md_launch(md, A, langevin, rec ? (k - 1) / every - 1 : -1, width);
+        md->forces_valid = false;
+        md->step = t0 + k - 1;
+        if (rc) return rc;
+        rc = md_forces(md, stress && every && k % every == 0);
+        if (rc) return rc;
+    }
+    // the closing half-kick of the last step
+    A.step = (unsigned long long)(t0 + n_steps - 1); A.close = 1; A.open = 0;
+    const bool rec = every && n_steps % every == 0;
+    int rc = md_launch(md, A, langevin, rec ? n_steps / every - 1 : -1, width);
+    if (rc) return rc;
+    md->step = t0 + n_steps;
+    if (n_rec) HIPCHK(c, hipMemcpyAsync(thermo, md->ring.p, 8 * (size_t)n_rec * md->n_frames * width, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return UF3_OK;
+}
+
+extern "C" int uf3_md_run(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
+                          double skin, int64_t thermo_every, int with_stress, double *thermo) {
+    if (!md) return fail(nullptr, UF3_EINVAL, "null md");
+    uf3_ctx *c = md->c;
+    if (n_steps < 0) return fail(c, UF3_EINVAL, "uf3_md_run: n_steps must be >= 0");
+    if (!(dt_fs > 0.0) || !std::isfinite(dt_fs)) return fail(c, UF3_EINVAL, "uf3_md_run: dt must be positive and finite");
+    if (!(temperature_K >= 0.0) || !std::isfinite(temperature_K)) return fail(c, UF3_EINVAL, "uf3_md_run: temperature must be finite and >= 0");
+    if (!(friction_per_fs >= 0.0) || !std::isfinite(friction_per_fs)) return fail(c, UF3_EINVAL, "uf3_md_run: friction must be finite and >= 0");
+    if (thermo_every < 0) return fail(c, UF3_EINVAL, "uf3_md_run: thermo_every must be >= 0");
+    if (!(skin >= 0.0) || skin > 4.0) return fail(c, UF3_EINVAL, "uf3_md_run: skin must lie in [0, 4] Angstrom");
+    const int64_t n_rec = thermo_every ? n_steps / thermo_every : 0;
+    if ((n_rec > 0) != (thermo != nullptr))
+        return fail(c, UF3_EINVAL, n_rec ? "uf3_md_run: thermo records are due but the thermo buffer is NULL"
+                                         : "uf3_md_run: a thermo buffer was given but no record is due");
+    if (n_steps == 0) return UF3_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    // the run's skin for its own duration, the caller's back on every way out (a change of skin drops the lists: each run
+    // starts with one list build)
+    const double caller_skin = c->md.skin;
+    int rc = uf3_ctx_md_skin(c, skin);
+    if (rc) return rc;
+    rc = md_run(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, thermo_every, with_stress != 0, thermo);
+    if (rc) {
+        const std::string msg = c->err;
+        uf3_ctx_md_skin(c, caller_skin);
+        return fail(c, rc, msg);
+    }
+    return uf3_ctx_md_skin(c, caller_skin);
+}
+
+extern "C" int uf3_md_info(const uf3_md *md, int64_t *step, int64_t *n_atoms, int32_t *n_frames) {
+    if (!md) return fail(nullptr, UF3_EINVAL, "null md");
+    if (step) *step = md->step;
+    if (n_atoms) *n_atoms = md->natoms;
+    if (n_frames) *n_frames = md->n_frames;
+    return UF3_OK;
+}
+
+extern "C" int uf3_philox_debug(uf3_ctx *c, int64_t n, const uint32_t *counters, const uint32_t *keys, uint32_t *out) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "null ctx");
+    if (n < 0 || n > (1LL << 26) || (n && (!counters || !keys || !out))) return fail(c, UF3_EINVAL, "uf3_philox_debug: bad argument");
+    if (!n) return UF3_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->dbg.ensure(40 * (size_t)n));
+    uint4 *d_ctr = c->dbg.as<uint4>(), *d_out = d_ctr + n;
+    uint2 *d_key = (uint2 *)(d_out + n);
+    HIPCHK(c, hipMemcpyAsync(d_ctr, counters, 16 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_key, keys, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_philox_debug, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (long long)n, (const uint4 *)d_ctr,
+                       (const uint2 *)d_key, d_out);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_out, 16 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return UF3_OK;
 }

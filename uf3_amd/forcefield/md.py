@@ -1,0 +1,281 @@
+"""
+``MolecularDynamics``: velocity Verlet (NVE) and Langevin (BAOAB, NVT) dynamics of a batch of frames, stepped on the device
+(``uf3_md_*`` in ``libuf3hip.so``).  Positions, velocities and forces stay in HBM between steps; the forces are the
+evaluator's (``UFCalculator``'s model, its MD route with a neighbour-list skin), the integrator is one fused kernel between
+two force calls.  Many small replicas in one batch cost no more machinery than one large frame.
+
+Units: Angstrom, fs, amu, eV, K.  Positions are kept unwrapped (``get_positions(wrap=True)`` wraps a copy).  Random numbers
+are counter-based (Philox4x32-10 on (atom, absolute step, draw), keyed by the seed), so ``run(60)`` equals
+``run(25); run(35)`` and the trajectory does not depend on how the batch is launched.
+
+    md = MolecularDynamics(calc, atoms_list, timestep_fs=1.0, masses={'W': 183.84}, temperature_K=300, friction_per_fs=0.01)
+    md.initialize_velocities(300, exact=True)
+    rec = md.run(1000, thermo_every=10, stress=True)      # rec['temperature'][k, frame], rec['pressure'], ...
+
+Each ``run`` starts with one neighbour-list build (it sets the context's skin for its own duration and puts the caller's
+back).  A basis without 3-body terms never takes the evaluator's MD route and rebuilds its lists on every step: correct,
+only slower.
+"""
+import ctypes as C
+import numbers
+import os
+
+import numpy as np
+
+from uf3_amd import _lib
+from uf3_amd.data.composition import atomic_numbers, chemical_symbols
+
+ACC = 0.009648533215665327       # eV / (Angstrom amu) -> Angstrom / fs^2
+KE_UNIT = 103.64269652680505     # amu Angstrom^2 / fs^2 -> eV
+KB = 8.617333262e-5              # eV / K
+ASE_TIME_FS = 10.180505          # one ASE time unit in fs (sqrt(KE_UNIT)): ASE velocities / ASE_TIME_FS = Angstrom / fs
+
+
+def kinetic_energy(velocities, masses):
+    """1/2 sum m v^2 in eV of velocities [N, 3] (Angstrom / fs) and masses [N] (amu)."""
+    v = np.asarray(velocities, dtype=float).reshape(-1, 3)
+    return 0.5 * float(np.sum(np.asarray(masses, dtype=float) * np.sum(v * v, axis=1))) * KE_UNIT
+
+
+def temperature(kinetic_energy_eV, n_atoms):
+    """2 KE / (3 N k_B), K (3N degrees of freedom, as ASE's ``get_temperature``)."""
+    return 2.0 * np.asarray(kinetic_energy_eV, dtype=float) / (3.0 * np.asarray(n_atoms, dtype=float) * KB)
+
+
+def _frames_of(atoms_or_list):
+    frames = list(atoms_or_list) if isinstance(atoms_or_list, (list, tuple)) else [atoms_or_list]
+    if not frames:
+        raise ValueError("MolecularDynamics: no frames")
+    for k, a in enumerate(frames):
+        if len(a) < 1:
+            raise ValueError(f"MolecularDynamics: frame {k} has no atoms")
+    return frames
+
+
+def resolve_masses(frames, masses=None):
+    """Masses [N] (amu) of the concatenated frames from ``{symbol or Z: amu}``, a per-atom array, or ``get_masses()`` of the
+    frames (real ASE objects).  There is no built-in mass table: anything else raises ``ValueError`` naming the species that
+    lack a mass."""
+    frames = _frames_of(frames)
+    z = np.concatenate([np.asarray(a.get_atomic_numbers(), dtype=np.int64).reshape(-1) for a in frames])
+    if masses is None:
+        if all(hasattr(a, "get_masses") for a in frames):
+            m = np.concatenate([np.asarray(a.get_masses(), dtype=float).reshape(-1) for a in frames])
+        else:
+            missing = sorted({chemical_symbols[int(q)] for q in z})
+            raise ValueError(f"MolecularDynamics: no masses for {', '.join(missing)}: pass masses={{symbol: amu}} or a "
+                             "per-atom array (there is no built-in mass table)")
+    elif isinstance(masses, dict):
+        table = {}
+        for key, value in masses.items():
+            zk = int(key) if isinstance(key, numbers.Integral) else atomic_numbers.get(str(key))
+            if zk is None:
+                raise ValueError(f"MolecularDynamics: unknown element {key!r} in masses")
+            table[zk] = float(value)
+        missing = sorted({int(q) for q in z} - set(table))
+        if missing:
+            raise ValueError(f"MolecularDynamics: no mass for {', '.join(chemical_symbols[q] for q in missing)}")
+        m = np.array([table[int(q)] for q in z], dtype=float)
+    else:
+        m = np.asarray(masses, dtype=float).reshape(-1)
+        if m.shape != z.shape:
+            raise ValueError(f"MolecularDynamics: {m.size} masses for {z.size} atoms")
+    if m.shape != z.shape:
+        raise ValueError(f"MolecularDynamics: {m.size} masses for {z.size} atoms")
+    if not np.all(np.isfinite(m)) or np.any(m <= 0):
+        raise ValueError("MolecularDynamics: masses must be positive and finite")
+    return np.ascontiguousarray(m)
+
+
+def thermo_records(raw, n_atoms, volumes, first_step, every, stress=False):
+    """The dict ``run`` returns from raw records [n_rec, n_frames, 2 or 14] ([PE, KE] or [PE, KE, W (6), K (6)], eV): step,
+    potential_energy, kinetic_energy, temperature [n_rec, n_frames]; with stress also stress [n_rec, n_frames, 6] =
+    (W - K) / V (ASE's include_ideal_gas convention, the sign of ``UFCalculator.get_stress``; NaN for frames without a volume)
+    and pressure = -trace / 3."""
+    raw = np.asarray(raw, dtype=float)
+    n_rec = raw.shape[0]
+    out = dict(step=first_step + every * np.arange(1, n_rec + 1, dtype=np.int64),
+               potential_energy=raw[..., 0].copy(), kinetic_energy=raw[..., 1].copy(),
+               temperature=temperature(raw[..., 1], np.asarray(n_atoms, dtype=float)[None, :]))
+    if stress:
+        vol = np.asarray(volumes, dtype=float)
+        inv = np.where(vol > 0, 1.0 / np.where(vol > 0, vol, 1.0), np.nan)
+        s = (raw[..., 2:8] - raw[..., 8:14]) * inv[None, :, None]
+        out["stress"] = s
+        out["pressure"] = -(s[..., 0] + s[..., 1] + s[..., 2]) / 3.0
+    return out
+
+
+def _check_real(name, value, lo=0.0, strict=False, hi=None):
+    try:
+        x = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"MolecularDynamics: {name} must be a number") from None
+    if not np.isfinite(x) or (x <= lo if strict else x < lo) or (hi is not None and x > hi):
+        bound = f"> {lo}" if strict else f">= {lo}"
+        raise ValueError(f"MolecularDynamics: {name} must be finite and {bound}" + (f" and <= {hi}" if hi is not None else "")
+                         + f", got {value!r}")
+    return x
+
+
+def _check_int(name, value, lo=0, hi=None):
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or value < lo or (hi is not None and value > hi):
+        raise ValueError(f"MolecularDynamics: {name} must be an integer >= {lo}" + (f" and <= {hi}" if hi is not None else "")
+                         + f", got {value!r}")
+    return int(value)
+
+
+class MolecularDynamics:
+    def __init__(self, calculator, atoms_or_list, timestep_fs, masses=None, temperature_K=0.0, friction_per_fs=0.0, seed=0,
+                 skin=0.5, device=None):
+        self.handle = None
+        # every argument is checked before the device is touched
+        self.timestep_fs = _check_real("timestep_fs", timestep_fs, strict=True)
+        self.temperature_K = _check_real("temperature_K", temperature_K)
+        self.friction_per_fs = _check_real("friction_per_fs", friction_per_fs)
+        self.seed = _check_int("seed", seed, 0, (1 << 64) - 1)
+        self.skin = _check_real("skin", skin, hi=4.0)
+        self._list = isinstance(atoms_or_list, (list, tuple))
+        self.frames = _frames_of(atoms_or_list)
+        self.masses = resolve_masses(self.frames, masses)
+        vel = None
+        if all(hasattr(a, "get_velocities") for a in self.frames):
+            vel = np.concatenate([np.asarray(a.get_velocities(), dtype=float).reshape(-1, 3) for a in self.frames]) / ASE_TIME_FS
+            if not np.all(np.isfinite(vel)):
+                raise ValueError("MolecularDynamics: velocities must be finite")
+        self.calculator = calculator
+        self._batch = _lib.FrameBatch(self.frames)
+        if not np.all(np.isfinite(self._batch.pos)):
+            raise ValueError("MolecularDynamics: positions must be finite")
+        self.n_atoms = np.diff(self._batch.offsets).astype(np.int64)
+        self.volumes = np.abs(np.linalg.det(self._batch.cells))
+        self.ctx = _lib.get_context(calculator.device if device is None else device)
+        self._dbasis = _lib.device_basis(calculator.bspline_config, self.ctx)
+        self._pid = os.getpid()
+        vel = None if vel is None else np.ascontiguousarray(vel)
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.uf3_md_create(self._dbasis.handle, C.byref(self._batch.struct), _lib._p(self._batch.pos),
+                                                  _lib._p(vel), _lib._p(self._batch.z), _lib._p(self.masses),
+                                                  _lib._p(calculator._c1), _lib._p(calculator._c2), _lib._p(calculator._c3),
+                                                  C.byref(h)))
+        self.handle = h
+
+    # ---- lifecycle --------------------------------------------------------------------------------------------------------
+    def _live(self):
+        if not self.handle:
+            raise RuntimeError("MolecularDynamics: the object is closed")
+        return self.handle
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if os.getpid() == self._pid and self.ctx.handle:
+                self.ctx.lib.uf3_md_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- state ------------------------------------------------------------------------------------------------------------
+    @property
+    def step(self):
+        s = C.c_int64()
+        self.ctx.check(self.ctx.lib.uf3_md_info(self._live(), C.byref(s), None, None))
+        return s.value
+
+    def _get(self, which):
+        n = self._batch.n_atoms
+        out = np.empty(self._batch.n_frames) if which == "energies" else np.empty((n, 3))
+        args = {k: None for k in ("pos", "vel", "forces", "energies")}
+        args[which] = _lib._p(out)
+        self.ctx.check(self.ctx.lib.uf3_md_get_state(self._live(), args["pos"], args["vel"], args["forces"], args["energies"]))
+        return out
+
+    def get_positions(self, wrap=False):
+        """[N, 3] Angstrom, frames concatenated; unwrapped unless ``wrap`` (into the cell along periodic directions)."""
+        pos = self._get("pos")
+        if wrap:
+            off = self._batch.offsets
+            for k in range(self._batch.n_frames):
+                per = self._batch.pbc[k].astype(bool)
+                if not per.any():
+                    continue
+                cell = self._batch.cells[k]
+                frac = pos[off[k]:off[k + 1]] @ np.linalg.inv(cell)
+                frac[:, per] -= np.floor(frac[:, per])
+                pos[off[k]:off[k + 1]] = frac @ cell
+        return pos
+
+    def get_velocities(self):
+        """[N, 3] Angstrom / fs."""
+        return self._get("vel")
+
+    def get_forces(self):
+        """[N, 3] eV / Angstrom at the current positions."""
+        return self._get("forces")
+
+    def get_potential_energies(self):
+        """[n_frames] eV at the current positions."""
+        return self._get("energies")
+
+    def get_atoms(self):
+        """The frames at the current (unwrapped) positions: a list when a list was given, else one object."""
+        from uf3_amd.data.atoms import Atoms
+        pos, off = self.get_positions(), self._batch.offsets
+        out = [Atoms(numbers=a.get_atomic_numbers(), positions=pos[off[k]:off[k + 1]], cell=a.get_cell(), pbc=a.get_pbc())
+               for k, a in enumerate(self.frames)]
+        return out if self._list else out[0]
+
+    def _state_array(self, name, x):
+        a = np.ascontiguousarray(np.asarray(x, dtype=float))
+        if a.shape != (self._batch.n_atoms, 3):
+            raise ValueError(f"MolecularDynamics: {name} must be [{self._batch.n_atoms}, 3], got {np.shape(x)}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"MolecularDynamics: {name} must be finite")
+        return a
+
+    def set_positions(self, positions):
+        """[N, 3] Angstrom (frames concatenated); the forces are evaluated again before the next step."""
+        p = self._state_array("positions", positions)
+        self.ctx.check(self.ctx.lib.uf3_md_set_state(self._live(), _lib._p(p), None))
+
+    def set_velocities(self, velocities):
+        """[N, 3] Angstrom / fs (frames concatenated)."""
+        v = self._state_array("velocities", velocities)
+        self.ctx.check(self.ctx.lib.uf3_md_set_state(self._live(), None, _lib._p(v)))
+
+    # ---- dynamics ---------------------------------------------------------------------------------------------------------
+    def initialize_velocities(self, temperature_K, seed=None, exact=False):
+        """Maxwell-Boltzmann velocities at ``temperature_K`` (Philox stream of ``seed``, default the object's, at the current
+        step), each frame's centre-of-mass velocity removed; ``exact``: each frame rescaled to exactly ``temperature_K``."""
+        t = _check_real("temperature_K", temperature_K)
+        s = self.seed if seed is None else _check_int("seed", seed, 0, (1 << 64) - 1)
+        self.ctx.check(self.ctx.lib.uf3_md_init_velocities(self._live(), t, s, int(bool(exact))))
+
+    def run(self, n_steps, thermo_every=0, stress=False):
+        """``n_steps`` steps (Langevin when ``friction_per_fs`` > 0, else NVE).  Returns the thermo records of every
+        ``thermo_every``-th step (see ``thermo_records``; empty arrays when ``thermo_every`` is 0)."""
+        n_steps = _check_int("n_steps", n_steps)
+        every = _check_int("thermo_every", thermo_every)
+        dt = _check_real("timestep_fs", self.timestep_fs, strict=True)
+        temp = _check_real("temperature_K", self.temperature_K)
+        gamma = _check_real("friction_per_fs", self.friction_per_fs)
+        skin = _check_real("skin", self.skin, hi=4.0)
+        seed = _check_int("seed", self.seed, 0, (1 << 64) - 1)
+        handle = self._live()
+        first = self.step
+        n_rec = n_steps // every if every else 0
+        width = 14 if stress else 2
+        raw = np.zeros((n_rec, self._batch.n_frames, width))
+        self.ctx.check(self.ctx.lib.uf3_md_run(handle, n_steps, dt, temp, gamma, seed, skin, every, int(bool(stress)),
+                                               _lib._p(raw) if n_rec else None))
+        return thermo_records(raw, self.n_atoms, self.volumes, first, max(every, 1), stress)
