@@ -106,7 +106,7 @@ int uf3_ctx_use_own_stream(uf3_ctx *ctx);
 int uf3_ctx_synchronize(uf3_ctx *ctx);
 const char *uf3_last_error(const uf3_ctx *ctx);
 /* Which sources this binary was compiled from: the first 16 hex digits of the sha256 over uf3_hip.hip, uf3_kernels.h,
- * uf3_feat3.h, uf3_device.h, uf3_md.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
+ * uf3_feat3.h, uf3_device.h, uf3_md.h, uf3_hessian.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
  * outside it).  __graft_entry__.build() rebuilds when it differs from the tree's, smoke() prints it. */
 const char *uf3_build_id(void);
 /* timing of the dominant kernel: (re)start / read accumulated HIP-event time in ms and launches */
@@ -426,6 +426,26 @@ int uf3_md_run(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, 
                int64_t thermo_every, int with_stress, double *thermo);
 int uf3_md_info(const uf3_md *md, int64_t *step, int64_t *n_atoms, int32_t *n_frames);
 int uf3_philox_debug(uf3_ctx *ctx, int64_t n, const uint32_t *counters, const uint32_t *keys, uint32_t *out);
+
+/*
+ * Analytic second derivatives of the energy uf3_eval computes, for ONE frame (uf3_hessian.h; the Gamma-point force constants
+ * of the frame, periodic images folded onto their parent atom).  Rows m in [row_begin, row_end) (R rows), all N atoms as columns.
+ *   hess  [3R][3N]  d2E / dx_{m,a} dx_{p,b}
+ *   mixed [3R][6]   d2E / dx_{m,a} dt_v (NULL: not formed): t_v the strain of uf3_eval_virial (Voigt xx, yy, zz, yz, xz, xy;
+ *                   eps_ab = eps_ba = t / 2 off the diagonal; cell and positions map through I + eps); = -dF_{m,a} / dt_v
+ *   born  [6][6]    d2E / dt_u dt_v at fixed fractional coordinates (clamped ions; NULL: not formed; whole frame only)
+ * The neighbour lists are the call's own (skin 0): the context's MD lists and its evaluator state are left as they were.
+ * Every row is written by one thread in a fixed order: the results are bitwise repeatable, and the rows of a slab are the
+ * rows of the whole call.  Errors: more than one frame, an empty or out-of-range row span, born with a partial span
+ * (UF3_EINVAL); atoms more than 500 cells apart along a periodic axis (UF3_EINVAL: wrap them first); an element outside the
+ * basis (UF3_ESPECIES).  uf3_hessian: host buffers; _dev: device pos, z and outputs
+ * (coefficients on the host, as uf3_eval_dev).
+ */
+int uf3_hessian(uf3_basis *basis, const uf3_frames *frames, const double *pos, const int32_t *z, const double *c1,
+                const double *c2, const double *c3, int64_t row_begin, int64_t row_end, double *hess, double *mixed, double *born);
+int uf3_hessian_dev(uf3_basis *basis, const uf3_frames *frames, const double *d_pos, const int32_t *d_z, const double *c1,
+                    const double *c2, const double *c3, int64_t row_begin, int64_t row_end, double *d_hess, double *d_mixed,
+                    double *d_born);
 
 /*
  * Dense helpers behind the module-level functions of uf3.representation.distances / angles, for frames small enough

@@ -1,6 +1,7 @@
 // uf3_hip.hip -- C ABI (include/uf3_hip.h) of the MI355X-native UF3 hot path:
 // contexts, device-resident basis tables, per-call frame geometry, kernel launches.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -17,6 +18,7 @@
 #include "uf3_kernels.h"
 #include "uf3_feat3.h"
 #include "uf3_md.h"
+#include "uf3_hessian.h"
 #include <chrono>
 #include <dlfcn.h>
 
@@ -82,7 +84,8 @@ struct uf3_ctx {
         n3x_ent, n3x_off,               // extension lists (batches with atoms outside their cell; see N3Lists)
         bin_cnt,                        // atoms per cell-list bin (counting sort)
         part_sums,                      // per-workgroup energy / strain-derivative sums of the MD collection pass (see EvalArgs)
-        hist_edges, hist_noise;         // uf3_pair_histogram[_dev]: the caller's bin edges and supercell noise
+        hist_edges, hist_noise,         // uf3_pair_histogram[_dev]: the caller's bin edges and supercell noise
+        hs_spec, hs_cnt, hs_ent, hs_coeff, hs_part, hs_io;   // uf3_hessian[_dev]: its own lists, model copy, Born shares, host staging
     int n3_cap = 0, cand_cap = 0;
     size_t bin_cnt_clean = 0;        // ints of bin_cnt known to be zero (k_bin_fill leaves the counts it used at zero)
     int n3_last_cap = 0, n3_last_natoms = 0;   // layout of the 3-body lists in the workspace right now (uf3_n3_lists_debug)
@@ -307,7 +310,8 @@ extern "C" void uf3_ctx_destroy(uf3_ctx *c) {
     Buf *all[] = {&c->geoms, &c->offsets, &c->frame_of, &c->atom_bin, &c->atom_wrap, &c->spec, &c->key_in,
                   &c->key_out, &c->val_in, &c->val_out, &c->sort_tmp, &c->bin_start, &c->slots, &c->flags, &c->n3_cnt, &c->n3_int, &c->n3_dbl, &c->e_atom, &c->nbr_f, &c->coeff,
                   &c->stage_pos, &c->stage_z, &c->stage_out, &c->stage_out2, &c->sp_rows, &c->sp_seg, &c->gram_tij, &c->frag, &c->dbg, &c->halo, &c->n3x_ent, &c->n3x_off,
-                  &c->bin_cnt, &c->coeff_cw, &c->part_sums};
+                  &c->bin_cnt, &c->coeff_cw, &c->part_sums,
+                  &c->hs_spec, &c->hs_cnt, &c->hs_ent, &c->hs_coeff, &c->hs_part, &c->hs_io};
     for (Buf *b : all) b->release();
     for (Buf &b : c->gram_tiles) b.release();
     if (c->comm) uf3_comm_destroy(c);
@@ -3813,6 +3817,156 @@ extern "C" int uf3_philox_debug(uf3_ctx *c, int64_t n, const uint32_t *counters,
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, d_out, 16 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return UF3_OK;
+}
+
+// ------------------------------------------------------------------------------ analytic Hessian (uf3_hessian.h)
+static int hessian_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, const double *c1,
+                        const double *c2, const double *c3, int64_t row_begin, int64_t row_end, double *d_hess, double *d_mixed,
+                        double *d_born) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    uf3_ctx *c = b->ctx;
+    if (!fr || fr->n_frames != 1 || !fr->atom_offsets || !fr->cells || !fr->pbc)
+        return fail(c, UF3_EINVAL, "uf3_hessian: exactly one frame");
+    if (!d_pos || !d_z || !c1 || !d_hess) return fail(c, UF3_EINVAL, "uf3_hessian: null argument");
+    if ((b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, "uf3_hessian: missing coefficients");
+    const int64_t N = fr->atom_offsets[1] - fr->atom_offsets[0];
+    if (fr->atom_offsets[0] != 0 || N < 1 || N > (int64_t)1 << 30) return fail(c, UF3_EINVAL, "uf3_hessian: bad atom count");
+    if (row_begin < 0 || row_end > N || row_begin >= row_end)
+        return fail(c, UF3_EINVAL, "uf3_hessian: row span [" + std::to_string(row_begin) + ", " + std::to_string(row_end) +
+                                       ") empty or outside the frame's " + std::to_string(N) + " atoms");
+    if (d_born && (row_begin != 0 || row_end != N))
+        return fail(c, UF3_EINVAL, "uf3_hessian: born needs the whole frame's rows");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int n = (int)N;
+    HessArgs A;
+    A.B = b->dev; A.pos = d_pos; A.natoms = n;
+    // cell: the periodic rows as given; a non-periodic axis gets a unit vector orthogonal to what is there already, so that the
+    // fractional coordinates along the periodic axes bound the image distance whatever the other rows hold
+    double cell[9], comp[9];
+    for (int k = 0; k < 9; k++) cell[k] = fr->cells[k];
+    int per[3];
+    for (int k = 0; k < 3; k++) per[k] = fr->pbc[k] ? 1 : 0;
+    {
+        std::vector<std::array<double, 3>> basis_v;
+        for (int k = 0; k < 3; k++) if (per[k]) basis_v.push_back({cell[3 * k], cell[3 * k + 1], cell[3 * k + 2]});
+        for (int k = 0; k < 3; k++) {
+            if (per[k]) { for (int q = 0; q < 3; q++) comp[3 * k + q] = cell[3 * k + q]; continue; }
+            // orthonormal complement: the unit axis with the largest remainder after removing the span so far
+            std::array<double, 3> best = {0, 0, 0};
+            double best_n = -1;
+            for (int e = 0; e < 3; e++) {
+                std::array<double, 3> v = {0, 0, 0};
+                v[e] = 1.0;
+                std::vector<std::array<double, 3>> ortho;
+                for (auto w : basis_v) {
+                    for (auto &o : ortho) { double t = w[0] * o[0] + w[1] * o[1] + w[2] * o[2]; for (int q = 0; q < 3; q++) w[q] -= t * o[q]; }
+                    double nn = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+                    if (nn > 0) { for (int q = 0; q < 3; q++) w[q] /= nn; ortho.push_back(w); }
+                }
+                for (auto &o : ortho) { double t = v[0] * o[0] + v[1] * o[1] + v[2] * o[2]; for (int q = 0; q < 3; q++) v[q] -= t * o[q]; }
+                double nn = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+                if (nn > best_n) { best_n = nn; for (int q = 0; q < 3; q++) best[q] = v[q] / nn; }
+            }
+            basis_v.push_back(best);
+            for (int q = 0; q < 3; q++) comp[3 * k + q] = best[q];
+        }
+    }
+    double inv[9];
+    if (!invert3(comp, inv)) return fail(c, UF3_EINVAL, "uf3_hessian: singular cell");
+    const double reach = std::max(b->host.rmax2, b->host.T > 0 ? b->host.rmax3 : 0.0);
+    for (int k = 0; k < 9; k++) { A.cell[k] = per[k / 3] ? cell[k] : 0.0; A.inv[k] = inv[k]; }
+    for (int k = 0; k < 3; k++) {
+        A.per[k] = per[k];
+        // |image distance| >= h_k |f_k + s_k| with h_k = 1 / |column k of inv|: |s_k| <= reach / h_k + 1/2 around the nearest image
+        const double h = 1.0 / std::sqrt(inv[k] * inv[k] + inv[3 + k] * inv[3 + k] + inv[6 + k] * inv[6 + k]);
+        A.nimg[k] = per[k] ? (int)std::floor(reach / h + 0.5 + 1e-6) : 0;
+        if (A.nimg[k] > 64) return fail(c, UF3_EINVAL, "uf3_hessian: cell far thinner than the cut-off");
+    }
+    // species
+    HIPCHK(c, c->hs_spec.ensure(sizeof(int) * ((size_t)n + 1)));
+    int *d_spec = c->hs_spec.as<int>(), *d_bad = d_spec + n;
+    HIPCHK(c, hipMemsetAsync(d_bad, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_hess_species, dim3((n + 255) / 256), dim3(256), 0, st, (const BasisDev *)b->dev, d_z, n, d_spec, d_bad);
+    int bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (bad) return fail(c, UF3_ESPECIES, "uf3_hessian: the frame contains an element outside the basis");
+    A.spec = d_spec;
+    // model: the library's own copy (the evaluator's model cache is left alone)
+    const size_t n2 = b->c2_len, n3 = b->c3_len;
+    HIPCHK(c, c->hs_coeff.ensure(8 * (n2 + n3 + 1)));
+    double *dc = c->hs_coeff.as<double>();
+    if (n2) HIPCHK(c, hipMemcpyAsync(dc, c2, 8 * n2, hipMemcpyHostToDevice, st));
+    if (n3) HIPCHK(c, hipMemcpyAsync(dc + n2, c3, 8 * n3, hipMemcpyHostToDevice, st));
+    A.c2 = dc; A.c3 = dc + n2;
+    // lists: count, size, fill (every atom: the centres of the rows' triplets may lie anywhere in the frame)
+    HIPCHK(c, c->hs_cnt.ensure(sizeof(int) * (size_t)n));
+    A.cnt = c->hs_cnt.as<int>(); A.cap = 0; A.ent = nullptr; A.bad = d_bad;      // (d_bad is 0: the species check passed)
+    hipLaunchKernelGGL(k_hess_lists<false>, dim3(n), dim3(64), 0, st, A);
+    std::vector<int> cnt((size_t)n);
+    HIPCHK(c, hipMemcpyAsync(cnt.data(), A.cnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (bad) return fail(c, UF3_EINVAL, "uf3_hessian: atoms lie more than 500 cells apart along a periodic axis: wrap the positions");
+    const int cap = std::max(1, *std::max_element(cnt.begin(), cnt.end()));
+    HIPCHK(c, c->hs_ent.ensure(sizeof(HessNbr) * (size_t)n * cap));
+    A.cap = cap; A.ent = c->hs_ent.as<HessNbr>();
+    hipLaunchKernelGGL(k_hess_lists<true>, dim3(n), dim3(64), 0, st, A);
+    // rows
+    const int64_t R = row_end - row_begin;
+    A.row_begin = row_begin; A.row_end = row_end; A.ld = 3 * N;
+    A.hess = d_hess; A.mixed = d_mixed;
+    HIPCHK(c, hipMemsetAsync(d_hess, 0, sizeof(double) * 9 * (size_t)R * (size_t)N, st));
+    if (d_mixed) HIPCHK(c, hipMemsetAsync(d_mixed, 0, sizeof(double) * 18 * (size_t)R, st));
+    A.born_part = nullptr;
+    if (d_born) {
+        HIPCHK(c, c->hs_part.ensure(sizeof(double) * 36 * (size_t)R));
+        A.born_part = c->hs_part.as<double>();
+        HIPCHK(c, hipMemsetAsync(A.born_part, 0, sizeof(double) * 36 * (size_t)R, st));
+    }
+    hipLaunchKernelGGL(k_hessian, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, st, A);
+    if (d_born) hipLaunchKernelGGL(k_hess_born_sum, dim3(36), dim3(256), 0, st, (const double *)A.born_part, (long long)R, d_born);
+    HIPCHK(c, hipGetLastError());
+    return UF3_OK;
+}
+
+extern "C" int uf3_hessian_dev(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, const double *c1,
+                               const double *c2, const double *c3, int64_t row_begin, int64_t row_end, double *d_hess,
+                               double *d_mixed, double *d_born) {
+    return hessian_impl(b, fr, d_pos, d_z, c1, c2, c3, row_begin, row_end, d_hess, d_mixed, d_born);
+}
+
+extern "C" int uf3_hessian(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1,
+                           const double *c2, const double *c3, int64_t row_begin, int64_t row_end, double *hess, double *mixed,
+                           double *born) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    uf3_ctx *c = b->ctx;
+    if (!fr || fr->n_frames != 1 || !fr->atom_offsets) return fail(c, UF3_EINVAL, "uf3_hessian: exactly one frame");
+    if (!pos || !z || !hess) return fail(c, UF3_EINVAL, "uf3_hessian: null argument");
+    const int64_t N = fr->atom_offsets[1] - fr->atom_offsets[0];
+    if (N < 1 || row_begin < 0 || row_end > N || row_begin >= row_end) return hessian_impl(b, fr, pos, z, c1, c2, c3, row_begin, row_end, hess, mixed, born);
+    const int64_t R = row_end - row_begin;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t b_pos = 24 * (size_t)N, b_z = (4 * (size_t)N + 15) / 16 * 16, b_h = 72 * (size_t)R * (size_t)N,
+                 b_m = mixed ? 144 * (size_t)R : 0, b_b = born ? 36 * 8 : 0;
+    HIPCHK(c, c->hs_io.ensure(b_pos + b_z + b_h + b_m + b_b));
+    char *base = c->hs_io.as<char>();
+    double *d_pos = (double *)base;
+    int32_t *d_z = (int32_t *)(base + b_pos);
+    double *d_h = (double *)(base + b_pos + b_z), *d_m = mixed ? (double *)(base + b_pos + b_z + b_h) : nullptr,
+           *d_b = born ? (double *)(base + b_pos + b_z + b_h + b_m) : nullptr;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(d_pos, pos, b_pos, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_z, z, 4 * (size_t)N, hipMemcpyHostToDevice, st));
+    int rc = hessian_impl(b, fr, d_pos, d_z, c1, c2, c3, row_begin, row_end, d_h, d_m, d_b);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(hess, d_h, b_h, hipMemcpyDeviceToHost, st));
+    if (mixed) HIPCHK(c, hipMemcpyAsync(mixed, d_m, b_m, hipMemcpyDeviceToHost, st));
+    if (born) HIPCHK(c, hipMemcpyAsync(born, d_b, b_b, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (c->hs_io.cap > ((size_t)1 << 30)) c->hs_io.release();      // (a large slab's staging is not kept for the context's lifetime)
     return UF3_OK;
 }
 

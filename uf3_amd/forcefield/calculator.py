@@ -305,3 +305,28 @@ class UFCalculator(_Base):
                 pos = pos + step_x
         return Atoms(numbers=numbers, positions=pos, cell=cell, pbc=pbc)
 
+
+    def get_hessian(self, atoms, rows=None, strain=False):
+        """Exact second derivatives of the energy on the device (``harmonic.hessian``): H [3N, 3N] (or the rows of ``rows``),
+        with ``strain=True`` also the mixed position / strain derivatives, the clamped-ion strain term and the virial."""
+        from . import harmonic
+        return harmonic.hessian(self, atoms, rows=rows, strain=strain)
+
+    def get_elastic_constants(self, atoms, n=5, d=1.0):
+        """
+        [C11, C12, C44, B] in GPa (reference: calculator.py:449-467) from the exact second derivatives of the energy, ions
+        relaxed (``harmonic.elastic_tensor``).  ``n`` and ``d`` (the reference's number and size of finite distortions) are
+        accepted and unused: nothing is sampled.  B = (C11 + 2 C12) / 3 from the same tensor, where the reference fits a
+        Birch-Murnaghan equation of state.  A tensor without cubic form in the cell's frame (1e-6 of its largest entry)
+        raises ValueError: ``harmonic.elastic_tensor`` gives the full tensor.
+        """
+        from . import harmonic
+        return harmonic.cubic_constants(harmonic.elastic_tensor(self, atoms)["C"])
+
+    def get_phonon_data(self, atoms, n_super=5, disp=0.05, resolution=30, path=None, masses=None):
+        """(force_constants, path_data, bands_dict) in the reference's shapes (calculator.py:469-487) from the device Hessian
+        of the n_super^3 supercell (``harmonic.band_structure``).  ``disp`` (the reference's finite displacement) is accepted
+        and unused.  Masses: ``masses`` ({symbol or Z: amu} or per-atom), else ``atoms.get_masses()`` -- which ASE frames have
+        and the package's own ``Atoms`` does not: pass ``masses`` with those (there is no built-in mass table)."""
+        from . import harmonic
+        return harmonic.band_structure(self, atoms, path=path, n_super=n_super, resolution=resolution, masses=masses)
