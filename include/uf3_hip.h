@@ -106,7 +106,7 @@ int uf3_ctx_use_own_stream(uf3_ctx *ctx);
 int uf3_ctx_synchronize(uf3_ctx *ctx);
 const char *uf3_last_error(const uf3_ctx *ctx);
 /* Which sources this binary was compiled from: the first 16 hex digits of the sha256 over uf3_hip.hip, uf3_kernels.h,
- * uf3_feat3.h, uf3_device.h, uf3_md.h, uf3_hessian.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
+ * uf3_feat3.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
  * outside it).  __graft_entry__.build() rebuilds when it differs from the tree's, smoke() prints it. */
 const char *uf3_build_id(void);
 /* timing of the dominant kernel: (re)start / read accumulated HIP-event time in ms and launches */
@@ -426,6 +426,37 @@ int uf3_md_run(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, 
                int64_t thermo_every, int with_stress, double *thermo);
 int uf3_md_info(const uf3_md *md, int64_t *step, int64_t *n_atoms, int32_t *n_frames);
 int uf3_philox_debug(uf3_ctx *ctx, int64_t n, const uint32_t *counters, const uint32_t *keys, uint32_t *out);
+
+/*
+ * Batched structure relaxation on the device (uf3_amd.forcefield.relax.Relaxation; kernels in uf3_relax.h): FIRE in ASE's
+ * formulation (N_min 5, f_inc 1.1, f_dec 0.5, alpha_start 0.1, f_alpha 0.99; mass-free), every frame its own optimiser.  The
+ * object owns positions (kept UNWRAPPED), velocities, forces and the per-frame state in HBM; the forces come from the evaluator.
+ *   uf3_relax_create     copies frames, positions [N][3], species, an optional per-atom fixed mask [N] (0 / 1; NULL: none;
+ *                        refused with relax_cell) and the model (c1 / c2 / c3 as for uf3_eval); no evaluation yet.  relax_cell:
+ *                        frames periodic along all three axes also relax their cell (x = q D, cell = cell0 D, cell coordinates
+ *                        n D; force on them -D^-T W / n, W the strain derivative of uf3_eval_virial); other frames positions only.
+ *   uf3_relax_run        evaluations 0 .. max_steps; after each, a frame still running is tested -- converged when every atom's
+ *                        |F_i| < fmax (and, with the cell, every row of D^-T W / n) -- and, but after the last, moved by one FIRE
+ *                        step (dt: the first step's time step; dt_max; maxstep: the trust radius over the frame's whole step,
+ *                        cell rows included).  Non-finite forces, energy or strain derivative freeze the frame (status 2);
+ *                        converged frames (status 1) are never moved again; status 0: still running.  The FIRE state carries
+ *                        over between runs.  The context's MD skin is `skin` for a positions-only run and 0 for a cell run,
+ *                        the caller's again on return (also on errors).  The host looks at the device every check_every
+ *                        steps and stops when no frame runs; cell runs wait for the new cells every step.  record_every > 0:
+ *                        records [max_steps / record_every + 1][n_frames][2] (energy, criterion) of evaluations 0,
+ *                        record_every, ...; rows after a stop repeat each frame's final values (NULL when record_every is 0).
+ *   uf3_relax_get_state  host arrays out, NULL skips: positions [N][3], cells [n_frames][9], forces [N][3] (Cartesian) and
+ *                        energies [n_frames] of the current positions (evaluated first if they moved since), status, steps
+ *                        (moves made) and the last criterion [n_frames] (NaN before the first run).
+ */
+typedef struct uf3_relax uf3_relax;
+int uf3_relax_create(uf3_basis *basis, const uf3_frames *frames, const double *pos, const int32_t *z, const uint8_t *fixed,
+                     const double *c1, const double *c2, const double *c3, int relax_cell, uf3_relax **out);
+void uf3_relax_destroy(uf3_relax *r);
+int uf3_relax_run(uf3_relax *r, int64_t max_steps, double fmax, double dt, double dt_max, double maxstep, double skin,
+                  int64_t check_every, int64_t record_every, double *records);
+int uf3_relax_get_state(uf3_relax *r, double *pos, double *cells /*[n_frames][9]*/, double *forces, double *energies,
+                        int32_t *status, int64_t *steps, double *fmax /*[n_frames]*/);
 
 /*
  * Analytic second derivatives of the energy uf3_eval computes, for ONE frame (uf3_hessian.h; the Gamma-point force constants

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <string>
@@ -19,6 +20,7 @@
 #include "uf3_feat3.h"
 #include "uf3_md.h"
 #include "uf3_hessian.h"
+#include "uf3_relax.h"
 #include <chrono>
 #include <dlfcn.h>
 
@@ -3817,6 +3819,265 @@ extern "C" int uf3_philox_debug(uf3_ctx *c, int64_t n, const uint32_t *counters,
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, d_out, 16 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return UF3_OK;
+}
+
+// ------------------------------------------------------------------------------ structure relaxation (uf3_relax_*, uf3_relax.h)
+// A library-owned FIRE state for a batch of frames: positions (unwrapped), velocities, forces, the per-frame optimiser state and,
+// in cell runs, the scaled coordinates q (x = q D) in HBM.  Every step is one evaluator call (eval_impl, unchanged) and three
+// launches; positions-only runs wait for the device only every check_every steps.  Cell runs copy the new cells back every step
+// (the evaluator reads them from the host uf3_frames) and run on the rebuild route (skin 0: the MD route's key holds the cells).
+struct uf3_relax {
+    uf3_basis *b = nullptr;
+    uf3_ctx *c = nullptr;
+    int32_t n_frames = 0;
+    int64_t natoms = 0;
+    int n_blocks = 0;
+    bool cell_run = false;                      // some frame has the cell as a degree of freedom
+    bool has_fixed = false;
+    std::vector<int64_t> offsets;
+    std::vector<double> cells;                  // the current cells (host: what eval_impl reads)
+    std::vector<uint8_t> pbc;
+    uf3_frames fr{};
+    std::vector<double> c1, c2, c3;
+    std::vector<RelaxFrame> st_host;
+    Buf pos, q, vel, frc, z, fixed, energies, virials, offsets_dev, blk_frame, blk_lo, blk_n, frame_blk, frame_of, st, coef,
+        partial, cells_dev, ring;
+    bool forces_valid = false;                  // frc / energies (/ virials in a cell run) describe pos
+};
+
+extern "C" void uf3_relax_destroy(uf3_relax *r) {
+    if (!r) return;
+    hipSetDevice(r->c->device);
+    hipStreamSynchronize(r->c->stream);
+    for (Buf *p : {&r->pos, &r->q, &r->vel, &r->frc, &r->z, &r->fixed, &r->energies, &r->virials, &r->offsets_dev, &r->blk_frame,
+                   &r->blk_lo, &r->blk_n, &r->frame_blk, &r->frame_of, &r->st, &r->coef, &r->partial, &r->cells_dev, &r->ring})
+        p->release();
+    delete r;
+}
+
+extern "C" int uf3_relax_create(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const uint8_t *fixed,
+                                const double *c1, const double *c2, const double *c3, int relax_cell, uf3_relax **out) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "uf3_relax_create: basis is NULL");
+    uf3_ctx *c = b->ctx;
+    if (!out) return fail(c, UF3_EINVAL, "uf3_relax_create: out is NULL");
+    if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, "uf3_relax_create: bad uf3_frames");
+    if (!pos) return fail(c, UF3_EINVAL, "uf3_relax_create: pos is NULL");
+    if (!z) return fail(c, UF3_EINVAL, "uf3_relax_create: z is NULL");
+    if (!c1 || (b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, "uf3_relax_create: missing coefficients (c1 / c2 / c3)");
+    if (relax_cell != 0 && relax_cell != 1) return fail(c, UF3_EINVAL, "uf3_relax_create: relax_cell must be 0 or 1");
+    if (relax_cell && fixed) return fail(c, UF3_EINVAL, "uf3_relax_create: fixed atoms together with relax_cell are not supported");
+    const int nf = fr->n_frames;
+    if (fr->atom_offsets[0] != 0) return fail(c, UF3_EINVAL, "uf3_relax_create: atom_offsets[0] must be 0");
+    for (int f = 0; f < nf; f++)
+        if (fr->atom_offsets[f + 1] <= fr->atom_offsets[f]) return fail(c, UF3_EINVAL, "uf3_relax_create: every frame needs an atom");
+    const int64_t n = fr->atom_offsets[nf];
+    if (n >= (1LL << 28)) return fail(c, UF3_EINVAL, "uf3_relax_create: batch must hold 1 .. 2^28 atoms");
+    if (!md_finite(pos, 3 * (size_t)n)) return fail(c, UF3_EINVAL, "uf3_relax_create: pos must be finite");
+    if (!md_finite(fr->cells, 9 * (size_t)nf)) return fail(c, UF3_EINVAL, "uf3_relax_create: cells must be finite");
+    if (fixed)
+        for (int64_t i = 0; i < n; i++)
+            if (fixed[i] > 1) return fail(c, UF3_EINVAL, "uf3_relax_create: fixed must hold 0 or 1 per atom");
+    // the chunk table: chunks of <= UF3_RELAX_THREADS atoms from each frame's first atom
+    std::vector<int> blk_frame, blk_n, frame_blk(1, 0), frame_of(n);
+    std::vector<long long> blk_lo;
+    for (int f = 0; f < nf; f++) {
+        for (int64_t lo = fr->atom_offsets[f]; lo < fr->atom_offsets[f + 1]; lo += UF3_RELAX_THREADS) {
+            blk_frame.push_back(f);
+            blk_lo.push_back(lo);
+            blk_n.push_back((int)std::min<int64_t>(UF3_RELAX_THREADS, fr->atom_offsets[f + 1] - lo));
+        }
+        frame_blk.push_back((int)blk_frame.size());
+        for (int64_t i = fr->atom_offsets[f]; i < fr->atom_offsets[f + 1]; i++) frame_of[i] = f;
+    }
+    const int nb = (int)blk_frame.size();
+    std::vector<RelaxFrame> st(nf);
+    bool cell_run = false;
+    for (int f = 0; f < nf; f++) {
+        RelaxFrame &S = st[f];
+        memset(&S, 0, sizeof(S));
+        const double *cl = fr->cells + 9 * (size_t)f;
+        const double det = cl[0] * (cl[4] * cl[8] - cl[5] * cl[7]) - cl[1] * (cl[3] * cl[8] - cl[5] * cl[6]) +
+                           cl[2] * (cl[3] * cl[7] - cl[4] * cl[6]);
+        const bool periodic = fr->pbc[3 * f] && fr->pbc[3 * f + 1] && fr->pbc[3 * f + 2];
+        if (relax_cell && periodic && det == 0.0) return fail(c, UF3_EINVAL, "uf3_relax_create: a periodic frame's cell is singular");
+        S.cellf = relax_cell && periodic;
+        cell_run = cell_run || S.cellf;
+        S.dt = 0.0; S.alpha = UF3_FIRE_ASTART;
+        S.e_last = S.fmax_last = std::numeric_limits<double>::quiet_NaN();
+        for (int k = 0; k < 9; k++) { S.D[k] = (k % 4 == 0) ? 1.0 : 0.0; S.cell0[k] = cl[k]; }
+        S.first = 1; S.status = UF3_RELAX_RUNNING;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    uf3_relax *r = new uf3_relax();
+    r->b = b; r->c = c; r->n_frames = nf; r->natoms = n; r->n_blocks = nb; r->cell_run = cell_run; r->has_fixed = fixed != nullptr;
+    r->offsets.assign(fr->atom_offsets, fr->atom_offsets + nf + 1);
+    r->cells.assign(fr->cells, fr->cells + 9 * (size_t)nf);
+    r->pbc.assign(fr->pbc, fr->pbc + 3 * (size_t)nf);
+    r->fr.n_frames = nf; r->fr.atom_offsets = r->offsets.data(); r->fr.cells = r->cells.data(); r->fr.pbc = r->pbc.data();
+    r->c1.assign(c1, c1 + b->host.S);
+    r->c2.assign(c2 ? c2 : c1, (c2 ? c2 : c1) + b->c2_len); r->c2.push_back(0.0);
+    r->c3.assign(c3 ? c3 : c1, (c3 ? c3 : c1) + b->c3_len); r->c3.push_back(0.0);
+    r->st_host = st;
+    auto bail = [&](int rc) { uf3_relax_destroy(r); return rc; };
+    const size_t n3 = 3 * (size_t)n;
+    if (r->pos.ensure(8 * n3) || (cell_run && r->q.ensure(8 * n3)) || r->vel.ensure(8 * n3) || r->frc.ensure(8 * n3) ||
+        r->z.ensure(4 * (size_t)n) || (fixed && r->fixed.ensure((size_t)n)) || r->energies.ensure(8 * (size_t)nf) ||
+        r->virials.ensure(48 * (size_t)nf) || r->offsets_dev.ensure(8 * (size_t)(nf + 1)) || r->blk_frame.ensure(4 * (size_t)nb) ||
+        r->blk_lo.ensure(8 * (size_t)nb) || r->blk_n.ensure(4 * (size_t)nb) || r->frame_blk.ensure(4 * (size_t)(nf + 1)) ||
+        r->frame_of.ensure(4 * (size_t)n) || r->st.ensure(sizeof(RelaxFrame) * (size_t)nf) ||
+        r->coef.ensure(sizeof(RelaxCoef) * (size_t)nf) || r->partial.ensure(32 * (size_t)nb) || r->cells_dev.ensure(72 * (size_t)nf))
+        return bail(fail(c, UF3_ENOMEM, "uf3_relax_create: out of device memory"));
+    hipStream_t s = c->stream;
+    if (hipMemcpyAsync(r->pos.p, pos, 8 * n3, hipMemcpyHostToDevice, s) ||
+        (cell_run && hipMemcpyAsync(r->q.p, pos, 8 * n3, hipMemcpyHostToDevice, s)) ||
+        hipMemsetAsync(r->vel.p, 0, 8 * n3, s) || hipMemcpyAsync(r->z.p, z, 4 * (size_t)n, hipMemcpyHostToDevice, s) ||
+        (fixed && hipMemcpyAsync(r->fixed.p, fixed, (size_t)n, hipMemcpyHostToDevice, s)) ||
+        hipMemcpyAsync(r->offsets_dev.p, r->offsets.data(), 8 * (size_t)(nf + 1), hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(r->blk_frame.p, blk_frame.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(r->blk_lo.p, blk_lo.data(), 8 * (size_t)nb, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(r->blk_n.p, blk_n.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(r->frame_blk.p, frame_blk.data(), 4 * (size_t)(nf + 1), hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(r->frame_of.p, frame_of.data(), 4 * (size_t)n, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(r->st.p, st.data(), sizeof(RelaxFrame) * (size_t)nf, hipMemcpyHostToDevice, s) ||
+        hipMemsetAsync(r->coef.p, 0, sizeof(RelaxCoef) * (size_t)nf, s) ||
+        hipMemcpyAsync(r->cells_dev.p, r->cells.data(), 72 * (size_t)nf, hipMemcpyHostToDevice, s) || hipStreamSynchronize(s))
+        return bail(fail(c, UF3_EHIP, "uf3_relax_create: upload failed"));
+    *out = r;
+    return UF3_OK;
+}
+
+static int relax_forces(uf3_relax *r) {
+    int rc = eval_impl(r->b, &r->fr, r->pos.as<double>(), r->z.as<int32_t>(), r->c1.data(), r->c2.data(), r->c3.data(),
+                       r->energies.as<double>(), r->frc.as<double>(), r->cell_run ? r->virials.as<double>() : nullptr);
+    r->forces_valid = rc == UF3_OK;
+    return rc;
+}
+
+static int relax_fetch_state(uf3_relax *r) {
+    uf3_ctx *c = r->c;
+    HIPCHK(c, hipMemcpyAsync(r->st_host.data(), r->st.p, sizeof(RelaxFrame) * (size_t)r->n_frames, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return UF3_OK;
+}
+
+// evaluations k = 0 .. max_steps; each but the last may move the frames still running
+static int relax_run(uf3_relax *r, int64_t max_steps, double fmax, double dt, double dt_max, double maxstep, int64_t every,
+                     int64_t rec_every, double *records) {
+    uf3_ctx *c = r->c;
+    hipStream_t s = c->stream;
+    const int nf = r->n_frames;
+    const int64_t n_rec = rec_every ? max_steps / rec_every + 1 : 0;
+    if (n_rec) HIPCHK(c, r->ring.ensure(16 * (size_t)n_rec * nf));
+    RelaxPartialArgs P;
+    P.frc = r->frc.as<double>(); P.vel = r->vel.as<double>(); P.fixed = r->has_fixed ? r->fixed.as<uint8_t>() : nullptr;
+    P.blk_frame = r->blk_frame.as<int>(); P.blk_lo = r->blk_lo.as<long long>(); P.blk_n = r->blk_n.as<int>();
+    P.st = r->st.as<RelaxFrame>(); P.partial = r->partial.as<double>();
+    RelaxFrameArgs F;
+    F.partial = r->partial.as<double>(); F.frame_blk = r->frame_blk.as<int>(); F.offsets = r->offsets_dev.as<long long>();
+    F.energies = r->energies.as<double>(); F.virials = r->cell_run ? r->virials.as<double>() : nullptr;
+    F.st = r->st.as<RelaxFrame>(); F.coef = r->coef.as<RelaxCoef>(); F.cells = r->cells_dev.as<double>();
+    F.fmax = fmax; F.dt0 = dt; F.dt_max = dt_max; F.maxstep = maxstep;
+    RelaxMoveArgs M;
+    M.pos = r->pos.as<double>(); M.vel = r->vel.as<double>(); M.q = r->cell_run ? r->q.as<double>() : nullptr;
+    M.frc = r->frc.as<double>(); M.fixed = P.fixed; M.frame_of = r->frame_of.as<int>(); M.coef = r->coef.as<RelaxCoef>();
+    M.n = r->natoms;
+    int64_t last = max_steps;                   // the last evaluation made
+    for (int64_t k = 0; k <= max_steps; k++) {
+        if (!(k == 0 && r->forces_valid)) {     // (a run continues from the previous run's last evaluation)
+            int rc = relax_forces(r);
+            if (rc) return rc;
+        }
+        hipLaunchKernelGGL(k_relax_partial, dim3((unsigned)r->n_blocks), dim3(UF3_RELAX_THREADS), 0, s, P);
+        HIPCHK(c, hipGetLastError());
+        F.rec = (n_rec && k % rec_every == 0) ? r->ring.as<double>() + 2 * (size_t)nf * (size_t)(k / rec_every) : nullptr;
+        F.can_move = k < max_steps;
+        hipLaunchKernelGGL(k_relax_frame, dim3((unsigned)nf), dim3(UF3_RELAX_THREADS), 0, s, F);
+        HIPCHK(c, hipGetLastError());
+        if (k == max_steps) break;
+        hipLaunchKernelGGL(k_relax_move, dim3((unsigned)((r->natoms + UF3_RELAX_THREADS - 1) / UF3_RELAX_THREADS)),
+                           dim3(UF3_RELAX_THREADS), 0, s, M);
+        HIPCHK(c, hipGetLastError());
+        r->forces_valid = false;
+        if (r->cell_run) {                      // (the evaluator and its list build read the cells on the host)
+            HIPCHK(c, hipMemcpyAsync(r->cells.data(), r->cells_dev.p, 72 * (size_t)nf, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+        }
+        if ((k + 1) % every == 0) {             // poll: stop once no frame runs (nothing moved in this step then)
+            int rc = relax_fetch_state(r);
+            if (rc) return rc;
+            bool running = false;
+            for (int f = 0; f < nf; f++) running = running || r->st_host[f].status == UF3_RELAX_RUNNING;
+            if (!running) { last = k; r->forces_valid = true; break; }
+        }
+    }
+    int rc = relax_fetch_state(r);
+    if (rc) return rc;
+    if (n_rec) {
+        // rows after the last evaluation repeat each frame's final values (no frame ran any more)
+        const int64_t written = last / rec_every + 1;
+        HIPCHK(c, hipMemcpyAsync(records, r->ring.p, 16 * (size_t)written * nf, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        for (int64_t j = written; j < n_rec; j++)
+            for (int f = 0; f < nf; f++) {
+                records[2 * (j * nf + f)] = r->st_host[f].e_last;
+                records[2 * (j * nf + f) + 1] = r->st_host[f].fmax_last;
+            }
+    }
+    return UF3_OK;
+}
+
+extern "C" int uf3_relax_run(uf3_relax *r, int64_t max_steps, double fmax, double dt, double dt_max, double maxstep, double skin,
+                             int64_t check_every, int64_t record_every, double *records) {
+    if (!r) return fail(nullptr, UF3_EINVAL, "uf3_relax_run: relax is NULL");
+    uf3_ctx *c = r->c;
+    if (max_steps < 0) return fail(c, UF3_EINVAL, "uf3_relax_run: max_steps must be >= 0");
+    if (!(fmax > 0.0) || !std::isfinite(fmax)) return fail(c, UF3_EINVAL, "uf3_relax_run: fmax must be positive and finite");
+    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, UF3_EINVAL, "uf3_relax_run: dt must be positive and finite");
+    if (!(dt_max > 0.0) || !std::isfinite(dt_max)) return fail(c, UF3_EINVAL, "uf3_relax_run: dt_max must be positive and finite");
+    if (!(maxstep > 0.0) || !std::isfinite(maxstep)) return fail(c, UF3_EINVAL, "uf3_relax_run: maxstep must be positive and finite");
+    if (!(skin >= 0.0) || skin > 4.0) return fail(c, UF3_EINVAL, "uf3_relax_run: skin must lie in [0, 4] Angstrom");
+    if (check_every < 1) return fail(c, UF3_EINVAL, "uf3_relax_run: check_every must be >= 1");
+    if (record_every < 0) return fail(c, UF3_EINVAL, "uf3_relax_run: record_every must be >= 0");
+    if ((record_every > 0) != (records != nullptr))
+        return fail(c, UF3_EINVAL, record_every ? "uf3_relax_run: records are due but the records buffer is NULL"
+                                                : "uf3_relax_run: a records buffer was given but no record is due");
+    HIPCHK(c, hipSetDevice(c->device));
+    // the run's skin for its own duration (0 in a cell run: the MD route's list key holds the cells), the caller's back on
+    // every way out
+    const double caller_skin = c->md.skin;
+    int rc = uf3_ctx_md_skin(c, r->cell_run ? 0.0 : skin);
+    if (rc) return rc;
+    rc = relax_run(r, max_steps, fmax, dt, dt_max, maxstep, check_every, record_every, records);
+    if (rc) {
+        const std::string msg = c->err;
+        uf3_ctx_md_skin(c, caller_skin);
+        return fail(c, rc, msg);
+    }
+    return uf3_ctx_md_skin(c, caller_skin);
+}
+
+extern "C" int uf3_relax_get_state(uf3_relax *r, double *pos, double *cells, double *forces, double *energies, int32_t *status,
+                                   int64_t *steps, double *fmax) {
+    if (!r) return fail(nullptr, UF3_EINVAL, "uf3_relax_get_state: relax is NULL");
+    uf3_ctx *c = r->c;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((forces || energies) && !r->forces_valid) {
+        int rc = relax_forces(r);
+        if (rc) return rc;
+    }
+    const size_t n3 = 3 * (size_t)r->natoms;
+    if (pos) HIPCHK(c, hipMemcpyAsync(pos, r->pos.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
+    if (forces) HIPCHK(c, hipMemcpyAsync(forces, r->frc.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
+    if (energies) HIPCHK(c, hipMemcpyAsync(energies, r->energies.p, 8 * (size_t)r->n_frames, hipMemcpyDeviceToHost, c->stream));
+    int rc = relax_fetch_state(r);
+    if (rc) return rc;
+    if (cells) memcpy(cells, r->cells.data(), 72 * (size_t)r->n_frames);
+    for (int f = 0; f < r->n_frames; f++) {
+        if (status) status[f] = r->st_host[f].status;
+        if (steps) steps[f] = r->st_host[f].steps;
+        if (fmax) fmax[f] = r->st_host[f].fmax_last;
+    }
     return UF3_OK;
 }
 

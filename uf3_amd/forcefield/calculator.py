@@ -305,6 +305,26 @@ class UFCalculator(_Base):
                 pos = pos + step_x
         return Atoms(numbers=numbers, positions=pos, cell=cell, pbc=pbc)
 
+    def relax_frames(self, frames, fmax=0.05, relax_cell=False, max_steps=2000, **kw):
+        """
+        Relax a batch of frames at once on the device (``relax.Relaxation``: FIRE in ASE's formulation, every frame its own
+        optimiser; with ``relax_cell`` fully periodic frames also relax their cell).  ``kw``: ``fixed``, ``skin``, ``device``
+        (the object's) and ``dt``, ``dt_max``, ``maxstep``, ``check_every`` (``run``'s).  Returns (relaxed frames, info), info
+        as ``Relaxation.run`` returns it; warns (RuntimeWarning) when a frame did not converge.  ``relax_fmax`` is the
+        one-frame host loop it does not replace.
+        """
+        import warnings
+        from .relax import Relaxation
+        make = {k: kw.pop(k) for k in ("fixed", "skin", "device") if k in kw}
+        with Relaxation(self, frames, relax_cell=relax_cell, **make) as rel:
+            info = rel.run(max_steps, fmax=fmax, **kw)
+            out = rel.get_atoms()
+        if not np.all(info["converged"]):
+            bad = [k for k, ok in enumerate(info["converged"]) if not ok]
+            warnings.warn(f"relax_frames: {len(bad)} of {len(info['converged'])} frames did not converge (frames {bad[:10]}"
+                          f"{', ...' if len(bad) > 10 else ''})", RuntimeWarning)
+        return out, info
+
 
     def get_hessian(self, atoms, rows=None, strain=False):
         """Exact second derivatives of the energy on the device (``harmonic.hessian``): H [3N, 3N] (or the rows of ``rows``),
