@@ -158,7 +158,7 @@ k_featurize3(Feat3Args A) {
     const size_t list_d = 5 * (size_t)cap + ((5 * cap) & 1), tq_d = (size_t)cap * EF * 4;
     constexpr size_t stage_d = Cfg::STAGE;
     const size_t per_wave_d = list_d + tq_d + stage_d;
-    const size_t per_wave_i = 2 * (size_t)cap + 2 * ((size_t)cap + 1) + (UF3_MAX_SPECIES + 2) + (size_t)cap * (S + 1) + 2 * NREC + cap;
+    const size_t per_wave_i = 2 * (size_t)cap + 2 * ((size_t)cap + 1) + (UF3_MAX_SPECIES + 2) + (size_t)cap * (S + 1) + cap;
     double *wd = rows_lds + rows_d + (size_t)wave * per_wave_d;
     int *wi = (int *)(rows_lds + rows_d + (size_t)WPB * per_wave_d) + (size_t)wave * per_wave_i;
     double *ox = wd, *oy = ox + cap, *oz = oy + cap, *orr = oz + cap, *oir = orr + cap;
@@ -167,8 +167,7 @@ k_featurize3(Feat3Args A) {
     double *zq = stage + (Cfg::STAGE - 4);                            // a quad of zeros
     int *oparent = wi, *oshift = wi + cap, *noff = wi + 2 * cap, *nbase = noff + cap + 1, *so = nbase + cap + 1;
     int *osbp = so + (UF3_MAX_SPECIES + 2);                           // first window row of every own bond
-    int *hdrs = osbp + cap;                       // [NREC + NREC] key | first n slot of the records of a pass
-    int *ospoff = hdrs + 2 * NREC;                // [cap][S + 1] (last: the only array whose place depends on S)
+    int *ospoff = osbp + cap;                     // [cap][S + 1] (last: the only array whose place depends on S)
     const int sp_stride = S + 1;
     unsigned short *fsrc_l = (unsigned short *)((int *)(rows_lds + rows_d + (size_t)WPB * per_wave_d) + (((size_t)WPB * per_wave_i + 3) & ~(size_t)3));
 
@@ -413,8 +412,11 @@ k_featurize3(Feat3Args A) {
                 cur = -1;
             }
             // ---- neighbour role: m is a neighbour of the centre e (fixed bond (m, e)); k runs over e's list.  The valid items of
-            // a step are compacted into the stage in order (runs of a fixed bond are found with one ballot); what a lane needs of
-            // a record besides its operands -- the first n slot -- it reads itself (no per-record work on the scalar unit).
+            // a step are compacted into the stage in order.  A record's header -- its fixed bond and its first n slot -- does not
+            // go through LDS memory: the lane that made the record pushes it to the lane of the record's slot (one ds_permute per
+            // pass), runs of a fixed bond are one DPP shift, one compare and one ballot over those lanes, and the first n
+            // slots of two consecutive records reach stage 1 through ONE v_readlane as scalar operands: no LDS read and no wait in
+            // front of a trip's addresses.
             if (nbr && !UF3_SKIP(8)) {
                 const int sx = sm == t_sa ? t_sb : t_sa;
                 const int rc_lo = so[t_sc], ncen = so[t_sc + 1] - rc_lo;
@@ -471,7 +473,8 @@ k_featurize3(Feat3Args A) {
                     }
                     for (int sp0 = 0; sp0 < nv; sp0 += NREC) {
                         const int slot = rank - sp0;
-                        if (valid && slot >= 0 && slot < NREC) {
+                        const bool put = valid && slot >= 0 && slot < NREC;
+                        if (put) {
                             double *rp = stage + (size_t)slot * RS_N;
                             if (EF > 4) {
 #pragma unroll
@@ -487,27 +490,36 @@ k_featurize3(Feat3Args A) {
                                 *(double2 *)(rp + EFP + 4 * u) = double2{a3[0] * bd[u], a3[1] * bd[u]};
                                 *(double2 *)(rp + EFP + 2 + 4 * u) = double2{a3[2] * bd[u], bn[u]};
                             }
-                            hdrs[slot] = e; hdrs[NREC + slot] = sbn * 32;      // (byte offset of the first n slot's quad)
                         }
+                        // the header (fixed bond | 32 x first n slot << 16) to the lane of the slot: one crossbar trip; lanes without a
+                        // record push to lane 63, which is no slot
+                        static_assert(NREC <= 32 && NREC < WAVE, "lane 63 must stay free of records, lane s + 1 must exist");
+                        const int got = __builtin_amdgcn_ds_permute((put ? slot : WAVE - 1) << 2, e | (sbn << 21));
+                        const int end = min(NREC, nv - sp0);
                         wave_sync();
-                        const int r_end = min(NREC, nv - sp0);
-                        const int v_key = hdrs[min(lane, NREC - 1)], v_prev = hdrs[min(max(lane - 1, 0), NREC - 1)];
-                        unsigned long long gm = __ballot(lane < r_end && (lane == 0 || v_key != v_prev));
+                        // lane s: key of record s | first n slots (byte offsets of their quads) of records s and s + 1, 16 bits each
+                        const int v_key = got & 0xffff, v_sb1 = got >> 16;
+                        const int v_sb = v_sb1 | (__builtin_amdgcn_update_dpp(0, v_sb1, 0x130, 0xf, 0xf, false) << 16);   // wave_shl:1
+                        const int v_prev = __builtin_amdgcn_update_dpp(v_key, v_key, 0x138, 0xf, 0xf, false);   // wave_shr:1
+                        unsigned long long gm = __ballot(lane < end && (lane == 0 || v_key != v_prev));
                         while (gm && !UF3_SKIP(1)) {
                             const int g0 = __builtin_ctzll(gm);
                             gm &= gm - 1;
-                            const int g1 = gm ? __builtin_ctzll(gm) : r_end;
+                            const int g1 = gm ? __builtin_ctzll(gm) : end;
                             const int key = __builtin_amdgcn_readlane(v_key, g0);
                             if (key != cur) { flush(false); cur = key; }
                             wmask |= smask;
                             const double *rp = stage + (size_t)g0 * RS_N;
-                            const int *sp = hdrs + NREC + g0;
-                            int cnt = g1 - g0;
+                            int gi = g0, cnt = g1 - g0;
                             auto body = [&](auto tag) {
                                 constexpr int CNT = decltype(tag)::value;
-                                int sb[CNT];
+                                int sb[CNT];                        // wave-uniform: scalar operands of the subtraction below
 #pragma unroll
-                                for (int i = 0; i < CNT; i++) sb[i] = ((const __attribute__((address_space(3))) int *)sp)[i];
+                                for (int i = 0; i < CNT; i += 2) {
+                                    const int w = __builtin_amdgcn_readlane(v_sb, gi + i);
+                                    sb[i] = w & 0xffff;
+                                    if (i + 1 < CNT) sb[i + 1] = (unsigned)w >> 16;
+                                }
 #pragma unroll
                                 for (int r = 0; r < NR; r++) {
                                     if (EF > 4 && !((smask >> r) & 1)) continue;
@@ -515,16 +527,16 @@ k_featurize3(Feat3Args A) {
                                     F3Pair tt[CNT];
 #pragma unroll
                                     for (int i = 0; i < CNT; i++) {
-                                        const unsigned off = (unsigned)(n32_lane[r] - sb[i]);          // 32 (n - first slot)
-                                        const char *qa = (const char *)(rp + i * RS_N + EFP + 2 * half) + off;
-                                        qa = off < 128u ? qa : (const char *)zq;
+                                        const unsigned off_n = (unsigned)(n32_lane[r] - sb[i]);        // 32 (n - first slot)
+                                        const char *qa = (const char *)(rp + i * RS_N + EFP + 2 * half) + off_n;
+                                        qa = off_n < 128u ? qa : (const char *)zq;
                                         bq[i] = ((F3LdsDoubles)rp)[i * RS_N + p_lane[r]];
                                         tt[i] = *(F3LdsPairs)(const F3Pair *)qa;
                                     }
 #pragma unroll
                                     for (int i = 0; i < CNT; i++) { ws[r][0] = fma(bq[i], tt[i].x, ws[r][0]); ws[r][1] = fma(bq[i], tt[i].y, ws[r][1]); }
                                 }
-                                rp += CNT * RS_N; sp += CNT; cnt -= CNT;
+                                rp += CNT * RS_N; gi += CNT; cnt -= CNT;
                             };
                             while (cnt >= 4) body(std::integral_constant<int, 4>{});
                             if (cnt == 3) body(std::integral_constant<int, 3>{});

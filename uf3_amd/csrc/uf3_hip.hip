@@ -1434,10 +1434,11 @@ static void feat3_shape(const uf3_basis *b, int &ep, int &stage, int &nrec) {
 static size_t feat3_lds_bytes(const uf3_basis *b, int cap, bool e_lds) {
     int ep, stage, nrec;
     feat3_shape(b, ep, stage, nrec);
+    (void)nrec;                  // (the records' headers travel in registers: uf3_feat3.h)
     const int F = b->host.F, S = b->host.S;
     const size_t e_d = e_lds ? (size_t)F + (F & 1) : 0, rows_d = (size_t)b->n_f3rows * 18;
     const size_t list_d = 5 * (size_t)cap + ((5 * cap) & 1), tq_d = (size_t)cap * ep * 4, stage_d = (size_t)stage;
-    const size_t per_wave_i = 2 * (size_t)cap + 2 * ((size_t)cap + 1) + (UF3_MAX_SPECIES + 2) + (size_t)cap * (S + 1) + 2 * (size_t)nrec + (size_t)cap;
+    const size_t per_wave_i = 2 * (size_t)cap + 2 * ((size_t)cap + 1) + (UF3_MAX_SPECIES + 2) + (size_t)cap * (S + 1) + (size_t)cap;
     const size_t ints = ((size_t)WPB * per_wave_i + 3) & ~(size_t)3;
     return (e_d + rows_d + WPB * (list_d + tq_d + stage_d)) * 8 + ints * 4 + (size_t)b->n_f3src * 2 + 32;
 }
