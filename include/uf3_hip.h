@@ -106,7 +106,7 @@ int uf3_ctx_use_own_stream(uf3_ctx *ctx);
 int uf3_ctx_synchronize(uf3_ctx *ctx);
 const char *uf3_last_error(const uf3_ctx *ctx);
 /* Which sources this binary was compiled from: the first 16 hex digits of the sha256 over uf3_hip.hip, uf3_kernels.h,
- * uf3_feat3.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
+ * uf3_feat3.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
  * outside it).  __graft_entry__.build() rebuilds when it differs from the tree's, smoke() prints it. */
 const char *uf3_build_id(void);
 /* timing of the dominant kernel: (re)start / read accumulated HIP-event time in ms and launches */
@@ -477,6 +477,58 @@ int uf3_hessian(uf3_basis *basis, const uf3_frames *frames, const double *pos, c
 int uf3_hessian_dev(uf3_basis *basis, const uf3_frames *frames, const double *d_pos, const int32_t *d_z, const double *c1,
                     const double *c2, const double *c3, int64_t row_begin, int64_t row_end, double *d_hess, double *d_mixed,
                     double *d_born);
+
+/*
+ * Phonons on a q-mesh (uf3_phonon.h): eigenvalues of the dynamical matrix at many wave vectors, the density of states and the
+ * harmonic thermodynamics.  They take a context and no basis: nothing here depends on the potential.  Units: eV, Angstrom,
+ * amu, THz, K.  Every entry exists twice -- host buffers, or (_dev) device buffers for the large arrays, enqueued on the
+ * context's stream without waiting; the small descriptive arrays (terms, term_w, edges, samples, temps) are host arrays in
+ * both, checked before anything is launched.
+ *
+ * uf3_phonon_mesh: lam [nq][3N], the eigenvalues of D(q) in ascending order (eV / (amu A^2)), and status [nq], the number of
+ * Jacobi sweeps taken or -1 where the cap of 30 sweeps was reached (lam of that q is then not converged).
+ *   fc [3N][3 n_sc_atoms]  force-constant rows of the cell's N atoms against the atoms of a supercell, atom p of the supercell
+ *                          an image of atom p mod N: what uf3_hessian writes for rows [0, N) of an n^3 supercell
+ *   inv_sqrt_mass [N]      1 / sqrt(amu)
+ *   terms [n_terms][5]     (i, p, n0, n1, n2): block row i < N, supercell atom p, integer lattice triple n of the chosen image;
+ *   term_w [n_terms]       its weight (1 / multiplicity of equivalent images)
+ *   q [nq][3]              reduced wave vectors
+ * D_ij(q) = sum over the terms (i, p) with p mod N = j of w exp(2 pi i q.n) fc[i, p] / sqrt(m_i m_j), then (D + D^H) / 2; q.n is
+ * reduced mod 1 before the sine and cosine.  Every sum has one order (the caller's term order within a block) and nothing is
+ * accumulated atomically: lam is bitwise repeatable, and a mesh cut into several calls gives the bits of one call.  N <= 2 runs
+ * one lane per q-point with the matrix in registers, larger cells one wave per q-point with D(q) in LDS (16 (3N)^2 bytes): the
+ * limit is N <= 32 (3N = 96, 147 456 bytes of the 160 KiB of a CU).  Errors (UF3_EINVAL, nothing launched): N < 1 or above the
+ * limit, nq < 1, n_sc_atoms not a multiple of N, a term whose atom indices lie outside [0, N) x [0, n_sc_atoms), null pointers.
+ *
+ * uf3_phonon_dos: from lam [nq][n_modes] and integer q-weights wq [nq] (NULL: all 1), with f = sign(lam) sqrt|lam| * 15.633302
+ * THz (imaginary modes negative).  Either output may be NULL, not both:
+ *   counts [n_bins]   int64 weighted histogram over edges [n_bins + 1] (THz, strictly increasing), numpy's rule: bins half open,
+ *                     the last one closed, values outside dropped
+ *   dos [n_samples]   g(f_s) = sum_q w_q sum_modes exp(-(f_s - f)^2 / 2 sigma^2) / (sigma sqrt(2 pi)) / sum_q w_q, in fixed-order
+ *                     partial sums (no floating-point atomics: bitwise repeatable)
+ * Errors (UF3_EINVAL): nq < 1, both outputs NULL, edges not strictly increasing, sigma <= 0, missing edges / samples.
+ *
+ * uf3_phonon_thermo: per primitive cell, out [n_temps][4] = F, U (eV), S, C_v (eV / K) at temps [n_temps] (K, >= 0), *zpe the
+ * zero-point energy (eV) and *excluded the summed weight of the modes with f <= cutoff_thz, which are left out of every sum
+ * (imaginary modes among them).  Per mode, x = h f / k_B T: F = hf / 2 + k_B T log(1 - e^-x), U = hf (1 / 2 + 1 / (e^x - 1)),
+ * S = k_B (x / (e^x - 1) - log(1 - e^-x)), C_v = k_B x^2 e^x / (e^x - 1)^2; T = 0: F = U = zpe, S = C_v = 0; each sum divided by
+ * sum_q w_q.  h = 4.135667696e-3 eV / THz, k_B = 8.617333262e-5 eV / K.  Fixed-order sums.  Errors (UF3_EINVAL): nq < 1, a
+ * negative or non-finite temperature or cut-off, null pointers.
+ */
+int uf3_phonon_mesh(uf3_ctx *ctx, int32_t n_atoms, int64_t n_sc_atoms, const double *fc, const double *inv_sqrt_mass,
+                    int64_t n_terms, const int32_t *terms, const double *term_w, int64_t nq, const double *q, double *lam,
+                    int32_t *status);
+int uf3_phonon_mesh_dev(uf3_ctx *ctx, int32_t n_atoms, int64_t n_sc_atoms, const double *d_fc, const double *d_inv_sqrt_mass,
+                        int64_t n_terms, const int32_t *terms, const double *term_w, int64_t nq, const double *d_q, double *d_lam,
+                        int32_t *d_status);
+int uf3_phonon_dos(uf3_ctx *ctx, int32_t n_modes, int64_t nq, const double *lam, const int64_t *wq, int32_t n_bins,
+                   const double *edges, int64_t *counts, int32_t n_samples, const double *samples, double sigma, double *dos);
+int uf3_phonon_dos_dev(uf3_ctx *ctx, int32_t n_modes, int64_t nq, const double *d_lam, const int64_t *d_wq, int32_t n_bins,
+                       const double *edges, int64_t *d_counts, int32_t n_samples, const double *samples, double sigma, double *d_dos);
+int uf3_phonon_thermo(uf3_ctx *ctx, int32_t n_modes, int64_t nq, const double *lam, const int64_t *wq, int32_t n_temps,
+                      const double *temps, double cutoff_thz, double *out, double *zpe, int64_t *excluded);
+int uf3_phonon_thermo_dev(uf3_ctx *ctx, int32_t n_modes, int64_t nq, const double *d_lam, const int64_t *d_wq, int32_t n_temps,
+                          const double *temps, double cutoff_thz, double *d_out, double *d_zpe, int64_t *d_excluded);
 
 /*
  * Dense helpers behind the module-level functions of uf3.representation.distances / angles, for frames small enough

@@ -21,6 +21,7 @@
 #include "uf3_md.h"
 #include "uf3_hessian.h"
 #include "uf3_relax.h"
+#include "uf3_phonon.h"
 #include <chrono>
 #include <dlfcn.h>
 
@@ -87,7 +88,9 @@ struct uf3_ctx {
         bin_cnt,                        // atoms per cell-list bin (counting sort)
         part_sums,                      // per-workgroup energy / strain-derivative sums of the MD collection pass (see EvalArgs)
         hist_edges, hist_noise,         // uf3_pair_histogram[_dev]: the caller's bin edges and supercell noise
-        hs_spec, hs_cnt, hs_ent, hs_coeff, hs_part, hs_io;   // uf3_hessian[_dev]: its own lists, model copy, Born shares, host staging
+        hs_spec, hs_cnt, hs_ent, hs_coeff, hs_part, hs_io,   // uf3_hessian[_dev]: its own lists, model copy, Born shares, host staging
+        ph_ws, ph_part, ph_io;          // uf3_phonon_*: sorted terms and small inputs | smearing partials | host staging
+    std::vector<char> ph_stage;         // host image of ph_ws (kept alive behind the asynchronous copy)
     int n3_cap = 0, cand_cap = 0;
     size_t bin_cnt_clean = 0;        // ints of bin_cnt known to be zero (k_bin_fill leaves the counts it used at zero)
     int n3_last_cap = 0, n3_last_natoms = 0;   // layout of the 3-body lists in the workspace right now (uf3_n3_lists_debug)
@@ -313,7 +316,8 @@ extern "C" void uf3_ctx_destroy(uf3_ctx *c) {
                   &c->key_out, &c->val_in, &c->val_out, &c->sort_tmp, &c->bin_start, &c->slots, &c->flags, &c->n3_cnt, &c->n3_int, &c->n3_dbl, &c->e_atom, &c->nbr_f, &c->coeff,
                   &c->stage_pos, &c->stage_z, &c->stage_out, &c->stage_out2, &c->sp_rows, &c->sp_seg, &c->gram_tij, &c->frag, &c->dbg, &c->halo, &c->n3x_ent, &c->n3x_off,
                   &c->bin_cnt, &c->coeff_cw, &c->part_sums,
-                  &c->hs_spec, &c->hs_cnt, &c->hs_ent, &c->hs_coeff, &c->hs_part, &c->hs_io};
+                  &c->hs_spec, &c->hs_cnt, &c->hs_ent, &c->hs_coeff, &c->hs_part, &c->hs_io,
+                  &c->ph_ws, &c->ph_part, &c->ph_io};
     for (Buf *b : all) b->release();
     for (Buf &b : c->gram_tiles) b.release();
     if (c->comm) uf3_comm_destroy(c);
@@ -4229,6 +4233,272 @@ extern "C" int uf3_hessian(uf3_basis *b, const uf3_frames *fr, const double *pos
     if (born) HIPCHK(c, hipMemcpyAsync(born, d_b, b_b, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     if (c->hs_io.cap > ((size_t)1 << 30)) c->hs_io.release();      // (a large slab's staging is not kept for the context's lifetime)
+    return UF3_OK;
+}
+
+// ------------------------------------------------------------------------------ phonons on a q-mesh (uf3_phonon.h)
+static int phonon_mesh_impl(uf3_ctx *c, int32_t n_atoms, int64_t n_sc, const double *d_fc, const double *d_ism, int64_t n_terms,
+                            const int32_t *terms, const double *term_w, int64_t nq, const double *d_q, double *d_lam,
+                            int32_t *d_status) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "uf3_phonon_mesh: ctx is NULL");
+    if (n_atoms < 1) return fail(c, UF3_EINVAL, "uf3_phonon_mesh: no atoms");
+    if (n_atoms > PH_MAX_ATOMS)
+        return fail(c, UF3_EINVAL, "uf3_phonon_mesh: " + std::to_string(n_atoms) + " atoms in the cell, the limit is " +
+                                       std::to_string(PH_MAX_ATOMS) + " (D(q), 16 (3N)^2 bytes, is held in LDS)");
+    if (nq < 1 || nq > (int64_t)1 << 30) return fail(c, UF3_EINVAL, "uf3_phonon_mesh: nq must be in [1, 2^30]");
+    if (n_sc < n_atoms || n_sc % n_atoms || n_sc > (int64_t)1 << 24)
+        return fail(c, UF3_EINVAL, "uf3_phonon_mesh: the supercell's atom count must be a multiple of the cell's");
+    if (n_terms < 1 || n_terms > (int64_t)1 << 28) return fail(c, UF3_EINVAL, "uf3_phonon_mesh: n_terms must be in [1, 2^28]");
+    if (!d_fc || !d_ism || !terms || !term_w || !d_q || !d_lam || !d_status)
+        return fail(c, UF3_EINVAL, "uf3_phonon_mesh: null argument");
+    const int N = n_atoms, nb = N * N;
+    // stable counting sort of the terms by block (i, p mod N)
+    std::vector<int> off((size_t)nb + 1, 0);
+    for (int64_t e = 0; e < n_terms; e++) {
+        const int32_t *t = terms + 5 * e;
+        if (t[0] < 0 || t[0] >= N || t[1] < 0 || t[1] >= n_sc)
+            return fail(c, UF3_EINVAL, "uf3_phonon_mesh: term " + std::to_string(e) + " names atom (" + std::to_string(t[0]) + ", " +
+                                           std::to_string(t[1]) + ") outside the cell's " + std::to_string(N) + " or the supercell's " +
+                                           std::to_string(n_sc) + " atoms");
+        if (std::abs(t[2]) > (1 << 20) || std::abs(t[3]) > (1 << 20) || std::abs(t[4]) > (1 << 20) || !std::isfinite(term_w[e]))
+            return fail(c, UF3_EINVAL, "uf3_phonon_mesh: term " + std::to_string(e) + " has a lattice vector beyond 2^20 cells or a weight that is not finite");
+        off[(size_t)t[0] * N + t[1] % N + 1]++;
+    }
+    for (int k = 0; k < nb; k++) off[k + 1] += off[k];
+    const size_t b_t = sizeof(PhTerm) * (size_t)n_terms, b_w = 8 * (size_t)n_terms, b_o = (4 * ((size_t)nb + 1) + 15) / 16 * 16;
+    c->ph_stage.resize(b_t + b_w + b_o);
+    PhTerm *ht = (PhTerm *)c->ph_stage.data();
+    double *hw = (double *)(c->ph_stage.data() + b_t);
+    {
+        std::vector<int> cur(off.begin(), off.end() - 1);
+        for (int64_t e = 0; e < n_terms; e++) {
+            const int32_t *t = terms + 5 * e;
+            const int at = cur[(size_t)t[0] * N + t[1] % N]++;
+            ht[at].p = t[1]; ht[at].n0 = t[2]; ht[at].n1 = t[3]; ht[at].n2 = t[4];
+            hw[at] = term_w[e];
+        }
+    }
+    memcpy(c->ph_stage.data() + b_t + b_w, off.data(), 4 * ((size_t)nb + 1));
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    HIPCHK(c, c->ph_ws.ensure(c->ph_stage.size()));
+    char *ws = c->ph_ws.as<char>();
+    HIPCHK(c, hipMemcpyAsync(ws, c->ph_stage.data(), c->ph_stage.size(), hipMemcpyHostToDevice, st));
+    PhMeshArgs A;
+    A.fc = d_fc; A.inv_sqrt_mass = d_ism; A.terms = (const PhTerm *)ws; A.term_w = (const double *)(ws + b_t);
+    A.block_off = (const int *)(ws + b_t + b_w); A.q = d_q; A.lam = d_lam; A.status = d_status;
+    A.nq = nq; A.ld = 3 * n_sc; A.natoms = N;
+    uf3_env_refresh();
+    const bool force_wave = uf3_env("UF3_PHONON_WAVE") != nullptr;      // measurements: the wave-per-q kernel at 3N <= 6 as well
+    if (N <= 2 && !force_wave) {
+        const unsigned g = (unsigned)((nq + 63) / 64);
+        if (N == 1) hipLaunchKernelGGL(k_ph_mesh_lane<1>, dim3(g), dim3(64), 0, st, A);
+        else hipLaunchKernelGGL(k_ph_mesh_lane<2>, dim3(g), dim3(64), 0, st, A);
+    } else {
+        const size_t lds = ph_wave_lds(3 * N);
+        if (lds > 65536) {      // (more than 64 KB of dynamic LDS is an opt-in per kernel and device: one high-water mark each)
+            static std::mutex mu; static size_t have[64] = {0};
+            std::lock_guard<std::mutex> lk(mu);
+            size_t &hv = have[c->device & 63];
+            if (lds > hv) {
+                HIPCHK(c, hipFuncSetAttribute((const void *)k_ph_mesh_wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                hv = lds;
+            }
+        }
+        hipLaunchKernelGGL(k_ph_mesh_wave, dim3((unsigned)nq), dim3(64), lds, st, A);
+    }
+    HIPCHK(c, hipGetLastError());
+    return UF3_OK;
+}
+
+extern "C" int uf3_phonon_mesh_dev(uf3_ctx *c, int32_t n_atoms, int64_t n_sc_atoms, const double *d_fc, const double *d_inv_sqrt_mass,
+                                   int64_t n_terms, const int32_t *terms, const double *term_w, int64_t nq, const double *d_q,
+                                   double *d_lam, int32_t *d_status) {
+    return phonon_mesh_impl(c, n_atoms, n_sc_atoms, d_fc, d_inv_sqrt_mass, n_terms, terms, term_w, nq, d_q, d_lam, d_status);
+}
+
+extern "C" int uf3_phonon_mesh(uf3_ctx *c, int32_t n_atoms, int64_t n_sc_atoms, const double *fc, const double *inv_sqrt_mass,
+                               int64_t n_terms, const int32_t *terms, const double *term_w, int64_t nq, const double *q, double *lam,
+                               int32_t *status) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "uf3_phonon_mesh: ctx is NULL");
+    if (!fc || !inv_sqrt_mass || !q || !lam || !status) return fail(c, UF3_EINVAL, "uf3_phonon_mesh: null argument");
+    if (n_atoms < 1 || n_atoms > PH_MAX_ATOMS || nq < 1 || nq > (int64_t)1 << 30 || n_sc_atoms < n_atoms || n_sc_atoms > (int64_t)1 << 24)
+        return phonon_mesh_impl(c, n_atoms, n_sc_atoms, fc, inv_sqrt_mass, n_terms, terms, term_w, nq, q, lam, status);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n3 = 3 * (size_t)n_atoms;
+    const size_t b_fc = 8 * n3 * 3 * (size_t)n_sc_atoms, b_m = (8 * (size_t)n_atoms + 15) / 16 * 16, b_q = 24 * (size_t)nq,
+                 b_l = 8 * n3 * (size_t)nq, b_s = 4 * (size_t)nq;
+    HIPCHK(c, c->ph_io.ensure(b_fc + b_m + b_q + b_l + b_s));
+    char *base = c->ph_io.as<char>();
+    double *d_fc = (double *)base, *d_m = (double *)(base + b_fc), *d_q = (double *)(base + b_fc + b_m),
+           *d_l = (double *)(base + b_fc + b_m + b_q);
+    int32_t *d_s = (int32_t *)(base + b_fc + b_m + b_q + b_l);
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(d_fc, fc, b_fc, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_m, inv_sqrt_mass, 8 * (size_t)n_atoms, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_q, q, b_q, hipMemcpyHostToDevice, st));
+    int rc = phonon_mesh_impl(c, n_atoms, n_sc_atoms, d_fc, d_m, n_terms, terms, term_w, nq, d_q, d_l, d_s);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(lam, d_l, b_l, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(status, d_s, b_s, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return UF3_OK;
+}
+
+// the sum of the q-weights and the caller's small host arrays (a | b) into ph_ws: [wsum | a | b]
+static int phonon_small_inputs(uf3_ctx *c, const int64_t *d_wq, int64_t nq, const double *a, size_t na, const double *b, size_t nb,
+                               long long **d_wsum, double **d_a, double **d_b) {
+    hipStream_t st = c->stream;
+    c->ph_stage.resize(8 * (na + nb + 2));
+    double *h = (double *)c->ph_stage.data();
+    h[0] = h[1] = 0.0;
+    if (na) memcpy(h + 2, a, 8 * na);
+    if (nb) memcpy(h + 2 + na, b, 8 * nb);
+    HIPCHK(c, c->ph_ws.ensure(c->ph_stage.size()));
+    HIPCHK(c, hipMemcpyAsync(c->ph_ws.p, h, c->ph_stage.size(), hipMemcpyHostToDevice, st));
+    *d_wsum = c->ph_ws.as<long long>();
+    *d_a = c->ph_ws.as<double>() + 2;
+    *d_b = c->ph_ws.as<double>() + 2 + na;
+    hipLaunchKernelGGL(k_ph_wsum, dim3(1), dim3(256), 0, st, (const long long *)d_wq, (long long)nq, *d_wsum);
+    return UF3_OK;
+}
+
+static int phonon_dos_impl(uf3_ctx *c, int32_t n_modes, int64_t nq, const double *d_lam, const int64_t *d_wq, int32_t n_bins,
+                           const double *edges, int64_t *d_counts, int32_t n_samples, const double *samples, double sigma,
+                           double *d_dos) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "uf3_phonon_dos: ctx is NULL");
+    if (n_modes < 1 || n_modes > PH_MAX_DIM) return fail(c, UF3_EINVAL, "uf3_phonon_dos: modes per q-point must be in [1, " + std::to_string(PH_MAX_DIM) + "]");
+    if (nq < 1 || nq > (int64_t)1 << 30) return fail(c, UF3_EINVAL, "uf3_phonon_dos: nq must be in [1, 2^30]");
+    if (!d_lam) return fail(c, UF3_EINVAL, "uf3_phonon_dos: null eigenvalues");
+    if (!d_counts && !d_dos) return fail(c, UF3_EINVAL, "uf3_phonon_dos: neither output asked for (counts and dos both NULL)");
+    if (d_counts) {
+        if (n_bins < 1 || n_bins > (1 << 24) || !edges) return fail(c, UF3_EINVAL, "uf3_phonon_dos: counts need n_bins in [1, 2^24] and edges");
+        for (int k = 0; k <= n_bins; k++)
+            if (!std::isfinite(edges[k]) || (k && !(edges[k] > edges[k - 1])))
+                return fail(c, UF3_EINVAL, "uf3_phonon_dos: edges must be finite and strictly increasing");
+    } else n_bins = 0;
+    if (d_dos) {
+        if (n_samples < 1 || n_samples > (1 << 24) || !samples) return fail(c, UF3_EINVAL, "uf3_phonon_dos: dos needs n_samples in [1, 2^24] and sample frequencies");
+        if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(c, UF3_EINVAL, "uf3_phonon_dos: sigma must be positive and finite");
+        for (int k = 0; k < n_samples; k++)
+            if (!std::isfinite(samples[k])) return fail(c, UF3_EINVAL, "uf3_phonon_dos: sample frequencies must be finite");
+    } else n_samples = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    long long *d_wsum;
+    double *d_edges, *d_samples;
+    int rc = phonon_small_inputs(c, d_wq, nq, edges, n_bins ? (size_t)n_bins + 1 : 0, samples, (size_t)n_samples, &d_wsum, &d_edges, &d_samples);
+    if (rc) return rc;
+    const long long total = (long long)nq * n_modes;
+    if (d_counts) {
+        HIPCHK(c, hipMemsetAsync(d_counts, 0, 8 * (size_t)n_bins, st));
+        hipLaunchKernelGGL(k_ph_hist, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_lam, (const long long *)d_wq, total,
+                           (int)n_modes, (const double *)d_edges, (int)n_bins, (unsigned long long *)d_counts);
+    }
+    if (d_dos) {
+        // chunks: a function of the sizes alone (at most 1024 of them, whole tiles), so the sums do not depend on the device
+        long long chunk = std::max<long long>(4096, (total + 1023) / 1024);
+        chunk = (chunk + PH_DOS_TILE - 1) / PH_DOS_TILE * PH_DOS_TILE;
+        const int n_chunks = (int)((total + chunk - 1) / chunk);
+        HIPCHK(c, c->ph_part.ensure(8 * (size_t)n_chunks * (size_t)n_samples));
+        double *part = c->ph_part.as<double>();
+        const unsigned gs = (unsigned)((n_samples + 255) / 256);
+        hipLaunchKernelGGL(k_ph_dos_part, dim3(gs, (unsigned)n_chunks), dim3(256), 0, st, d_lam, (const long long *)d_wq, total, (int)n_modes,
+                           chunk, (const double *)d_samples, (int)n_samples, 1.0 / sigma, part);
+        hipLaunchKernelGGL(k_ph_dos_sum, dim3(gs), dim3(256), 0, st, (const double *)part, n_chunks, (int)n_samples, 1.0 / sigma,
+                           (const long long *)d_wsum, d_dos);
+    }
+    HIPCHK(c, hipGetLastError());
+    return UF3_OK;
+}
+
+extern "C" int uf3_phonon_dos_dev(uf3_ctx *c, int32_t n_modes, int64_t nq, const double *d_lam, const int64_t *d_wq, int32_t n_bins,
+                                  const double *edges, int64_t *d_counts, int32_t n_samples, const double *samples, double sigma,
+                                  double *d_dos) {
+    return phonon_dos_impl(c, n_modes, nq, d_lam, d_wq, n_bins, edges, d_counts, n_samples, samples, sigma, d_dos);
+}
+
+// lam | wq of a host entry into ph_io; *d_wq NULL when wq is
+static int phonon_stage_modes(uf3_ctx *c, int32_t n_modes, int64_t nq, const double *lam, const int64_t *wq, size_t extra, double **d_lam,
+                              int64_t **d_wq, char **d_extra) {
+    const size_t b_l = 8 * (size_t)n_modes * (size_t)nq, b_w = wq ? 8 * (size_t)nq : 0;
+    HIPCHK(c, c->ph_io.ensure(b_l + b_w + extra));
+    char *base = c->ph_io.as<char>();
+    *d_lam = (double *)base; *d_wq = wq ? (int64_t *)(base + b_l) : nullptr; *d_extra = base + b_l + b_w;
+    HIPCHK(c, hipMemcpyAsync(*d_lam, lam, b_l, hipMemcpyHostToDevice, c->stream));
+    if (wq) HIPCHK(c, hipMemcpyAsync(*d_wq, wq, b_w, hipMemcpyHostToDevice, c->stream));
+    return UF3_OK;
+}
+
+extern "C" int uf3_phonon_dos(uf3_ctx *c, int32_t n_modes, int64_t nq, const double *lam, const int64_t *wq, int32_t n_bins,
+                              const double *edges, int64_t *counts, int32_t n_samples, const double *samples, double sigma, double *dos) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "uf3_phonon_dos: ctx is NULL");
+    if (!lam || n_modes < 1 || n_modes > PH_MAX_DIM || nq < 1 || nq > (int64_t)1 << 30 || (!counts && !dos) ||
+        (counts && (n_bins < 1 || n_bins > (1 << 24))) || (dos && (n_samples < 1 || n_samples > (1 << 24))))
+        return phonon_dos_impl(c, n_modes, nq, lam, wq, n_bins, edges, counts, n_samples, samples, sigma, dos);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t b_c = counts ? 8 * (size_t)n_bins : 0, b_d = dos ? 8 * (size_t)n_samples : 0;
+    double *d_lam; int64_t *d_wq; char *d_out;
+    int rc = phonon_stage_modes(c, n_modes, nq, lam, wq, b_c + b_d, &d_lam, &d_wq, &d_out);
+    if (rc) return rc;
+    int64_t *d_c = counts ? (int64_t *)d_out : nullptr;
+    double *d_d = dos ? (double *)(d_out + b_c) : nullptr;
+    rc = phonon_dos_impl(c, n_modes, nq, d_lam, d_wq, n_bins, edges, d_c, n_samples, samples, sigma, d_d);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    if (counts) HIPCHK(c, hipMemcpyAsync(counts, d_c, b_c, hipMemcpyDeviceToHost, st));
+    if (dos) HIPCHK(c, hipMemcpyAsync(dos, d_d, b_d, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return UF3_OK;
+}
+
+static int phonon_thermo_impl(uf3_ctx *c, int32_t n_modes, int64_t nq, const double *d_lam, const int64_t *d_wq, int32_t n_temps,
+                              const double *temps, double cutoff_thz, double *d_out, double *d_zpe, int64_t *d_excluded) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "uf3_phonon_thermo: ctx is NULL");
+    if (n_modes < 1 || n_modes > PH_MAX_DIM) return fail(c, UF3_EINVAL, "uf3_phonon_thermo: modes per q-point must be in [1, " + std::to_string(PH_MAX_DIM) + "]");
+    if (nq < 1 || nq > (int64_t)1 << 30) return fail(c, UF3_EINVAL, "uf3_phonon_thermo: nq must be in [1, 2^30]");
+    if (n_temps < 1 || n_temps > 65535) return fail(c, UF3_EINVAL, "uf3_phonon_thermo: the number of temperatures must be in [1, 65535]");
+    if (!d_lam || !temps || !d_out || !d_zpe || !d_excluded) return fail(c, UF3_EINVAL, "uf3_phonon_thermo: null argument");
+    for (int k = 0; k < n_temps; k++)
+        if (!(temps[k] >= 0.0) || !std::isfinite(temps[k]))
+            return fail(c, UF3_EINVAL, "uf3_phonon_thermo: temperatures must be finite and not negative");
+    if (!(cutoff_thz >= 0.0) || !std::isfinite(cutoff_thz)) return fail(c, UF3_EINVAL, "uf3_phonon_thermo: the cut-off must be finite and not negative");
+    HIPCHK(c, hipSetDevice(c->device));
+    long long *d_wsum;
+    double *d_t, *d_none;
+    int rc = phonon_small_inputs(c, d_wq, nq, temps, (size_t)n_temps, nullptr, 0, &d_wsum, &d_t, &d_none);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_ph_thermo, dim3((unsigned)n_temps), dim3(256), 0, c->stream, d_lam, (const long long *)d_wq, (long long)nq * n_modes,
+                       (int)n_modes, (const double *)d_t, cutoff_thz, (const long long *)d_wsum, d_out, d_zpe, (long long *)d_excluded);
+    HIPCHK(c, hipGetLastError());
+    return UF3_OK;
+}
+
+extern "C" int uf3_phonon_thermo_dev(uf3_ctx *c, int32_t n_modes, int64_t nq, const double *d_lam, const int64_t *d_wq, int32_t n_temps,
+                                     const double *temps, double cutoff_thz, double *d_out, double *d_zpe, int64_t *d_excluded) {
+    return phonon_thermo_impl(c, n_modes, nq, d_lam, d_wq, n_temps, temps, cutoff_thz, d_out, d_zpe, d_excluded);
+}
+
+extern "C" int uf3_phonon_thermo(uf3_ctx *c, int32_t n_modes, int64_t nq, const double *lam, const int64_t *wq, int32_t n_temps,
+                                 const double *temps, double cutoff_thz, double *out, double *zpe, int64_t *excluded) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "uf3_phonon_thermo: ctx is NULL");
+    if (!lam || !out || !zpe || !excluded || n_modes < 1 || n_modes > PH_MAX_DIM || nq < 1 || nq > (int64_t)1 << 30 || n_temps < 1 ||
+        n_temps > 65535)
+        return phonon_thermo_impl(c, n_modes, nq, lam, wq, n_temps, temps, cutoff_thz, out, zpe, excluded);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t b_o = 32 * (size_t)n_temps;
+    double *d_lam; int64_t *d_wq; char *d_x;
+    int rc = phonon_stage_modes(c, n_modes, nq, lam, wq, b_o + 16, &d_lam, &d_wq, &d_x);
+    if (rc) return rc;
+    double *d_o = (double *)d_x, *d_z = (double *)(d_x + b_o);
+    int64_t *d_e = (int64_t *)(d_x + b_o + 8);
+    rc = phonon_thermo_impl(c, n_modes, nq, d_lam, d_wq, n_temps, temps, cutoff_thz, d_o, d_z, d_e);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(out, d_o, b_o, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(zpe, d_z, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(excluded, d_e, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
     return UF3_OK;
 }
 

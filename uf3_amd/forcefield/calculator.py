@@ -350,3 +350,21 @@ class UFCalculator(_Base):
         and the package's own ``Atoms`` does not: pass ``masses`` with those (there is no built-in mass table)."""
         from . import harmonic
         return harmonic.band_structure(self, atoms, path=path, n_super=n_super, resolution=resolution, masses=masses)
+
+    def get_phonon_dos(self, atoms, mesh=(20, 20, 20), n_super=5, masses=None, sigma=None, **kwargs):
+        """Phonon density of states on a q-mesh (``harmonic.density_of_states``, its dict): ``frequencies`` and ``dos`` (states
+        per THz per cell), ``edges`` and ``counts`` (int64 histogram), ``n_imaginary``.  D(q), its eigenvalues and the DOS are
+        computed on the device from one Hessian of the n_super^3 supercell.  Where phonopy's ``run_total_dos`` uses the
+        tetrahedron method by default, this smears with Gaussians of width ``sigma`` (THz); the mesh is reduced by time
+        reversal only.  Masses: as for ``get_phonon_data``."""
+        from . import harmonic
+        return harmonic.density_of_states(self, atoms, mesh, n_super=n_super, masses=masses, sigma=sigma, **kwargs)
+
+    def get_thermal_properties(self, atoms, temperatures, mesh=(20, 20, 20), n_super=5, masses=None, cutoff_THz=1e-3, **kwargs):
+        """Harmonic free energy, internal energy (eV per cell), entropy and heat capacity (eV / K per cell) at ``temperatures``
+        (K) from a q-mesh (``harmonic.thermal_properties``, its dict, with ``zero_point_energy`` and ``n_excluded``), on the
+        device.  phonopy's ``run_thermal_properties`` reports kJ / mol and J / K / mol; modes at or below ``cutoff_THz`` are
+        left out and counted, as phonopy's cutoff_frequency does.  Masses: as for ``get_phonon_data``."""
+        from . import harmonic
+        return harmonic.thermal_properties(self, atoms, temperatures, mesh, n_super=n_super, masses=masses,
+                                           cutoff_THz=cutoff_THz, **kwargs)

@@ -22,6 +22,9 @@ from .md import resolve_masses
 
 EV_PER_A3_GPA = 160.21766208           # 1 eV / Angstrom^3 in GPa
 THZ = 15.633302                        # sqrt(eV / (amu Angstrom^2)) / (2 pi), in THz
+PLANCK_EV_PER_THZ = 4.135667696e-3     # h in eV / THz (CODATA 2018)
+KB_EV_PER_K = 8.617333262e-5           # k_B in eV / K (CODATA 2018)
+MESH_MAX_ATOMS = 32                    # uf3_phonon_mesh: D(q) of a wave lives in LDS, 16 (3N)^2 bytes
 
 _VOIGT = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))
 
@@ -303,6 +306,262 @@ def band_structure(calc, atoms, path=None, n_super=5, resolution=30, masses=None
     path_data = {"point_coords": coords, "path": segs}
     bands = {"qpoints": qs, "distances": dists, "frequencies": freqs, "eigenvectors": vecs}
     return fc, path_data, bands
+
+
+# ------------------------------------------------------------------------------------------- phonons on a q-mesh (device)
+# DESIGN.md section 3.12.  D(q) and its eigenvalues at every q-point of a mesh, the density of states and the harmonic
+# thermodynamics run on the device (uf3_phonon_mesh / _dos / _thermo); the force constants come from one uf3_hessian call per
+# structure.  Out of scope: eigenvectors on the mesh (projected DOS, thermal displacements), the tetrahedron method, point-group
+# reduction of the mesh, non-analytic (LO-TO) corrections, the quasi-harmonic volume loop, plotting.
+def qmesh(mesh, gamma_centred=True, time_reversal=True):
+    """Regular mesh of reduced wave vectors: ``(q [nq, 3] in [0, 1), weights int64 [nq])``.  q_k = a_k / n_k, a_k = 0 .. n_k - 1,
+    or (a_k + 1/2) / n_k with ``gamma_centred=False``.  With ``time_reversal`` one of each pair (q, -q mod 1) is kept with
+    weight 2 (the first in mesh order), self-conjugate points with weight 1; the weights always sum to n_1 n_2 n_3.  There is
+    no point-group reduction."""
+    mesh = np.asarray(mesh, dtype=np.int64).reshape(-1)
+    if mesh.shape != (3,) or np.any(mesh < 1):
+        raise ValueError("harmonic.qmesh: mesh must be three positive integers")
+    a = np.stack(np.meshgrid(*(np.arange(n) for n in mesh), indexing="ij"), axis=-1).reshape(-1, 3)
+    weights = np.ones(len(a), dtype=np.int64)
+    if time_reversal:
+        partner = (-a) % mesh if gamma_centred else mesh - 1 - a
+        own = np.ravel_multi_index(tuple(a.T), tuple(mesh))
+        other = np.ravel_multi_index(tuple(partner.T), tuple(mesh))
+        keep = own <= other
+        weights = np.where(own == other, 1, 2).astype(np.int64)[keep]
+        a = a[keep]
+    q = (a + (0.0 if gamma_centred else 0.5)) / mesh
+    return np.ascontiguousarray(q), np.ascontiguousarray(weights)
+
+
+def image_terms(atoms, n_super, tol=1e-5):
+    """``minimum_image_weights`` as a flat list for the device: ``(terms int32 [n_terms, 5], weights [n_terms])``, one record
+    (i, p, n0, n1, n2) per chosen image -- primitive atom i, supercell atom p, and the lattice vector R = n @ cell of that
+    image as integers (R is ``base + around[near]`` there, an integer combination of the cell's rows) -- in the order of that
+    function: i, then p, then the images in its order."""
+    n_super = int(n_super)
+    if n_super < 1:
+        raise ValueError("harmonic: n_super must be >= 1")
+    cell = np.asarray(atoms.get_cell(), dtype=float).reshape(3, 3)
+    pos = np.asarray(atoms.get_positions(), dtype=float).reshape(-1, 3)
+    n = len(pos)
+    shifts_i = np.array(list(itertools.product(range(n_super), repeat=3)), dtype=np.int64)
+    around_i = np.array(list(itertools.product((-2, -1, 0, 1, 2), repeat=3)), dtype=np.int64)
+    base = shifts_i.astype(float) @ cell
+    around = around_i.astype(float) @ (cell * n_super)
+    terms, weights = [], []
+    for i in range(n):
+        # v [image, j, around, 3], evaluated in minimum_image_weights's order: ((base + pos_j) - pos_i) + around
+        v = ((base[:, None, :] + pos[None, :, :]) - pos[i])[:, :, None, :] + around[None, None, :, :]
+        d = np.sqrt((v * v).sum(axis=-1))
+        near = d <= d.min(axis=-1, keepdims=True) + tol
+        t_idx, j_idx, k_idx = np.nonzero(near)
+        mult = near.sum(axis=-1)
+        rec = np.empty((len(t_idx), 5), dtype=np.int32)
+        rec[:, 0] = i
+        rec[:, 1] = t_idx * n + j_idx
+        rec[:, 2:] = shifts_i[t_idx] + n_super * around_i[k_idx]
+        terms.append(rec)
+        weights.append(1.0 / mult[t_idx, j_idx])
+    return np.ascontiguousarray(np.concatenate(terms)), np.ascontiguousarray(np.concatenate(weights))
+
+
+def eigenvalues_to_frequencies(lam):
+    """THz from eigenvalues of D (eV / (amu A^2)); negative numbers for imaginary modes (``frequencies_from``'s rule)."""
+    lam = np.asarray(lam, dtype=float)
+    return np.sign(lam) * np.sqrt(np.abs(lam)) * THZ
+
+
+def _mesh_context(device=None):
+    return _lib.get_context(device)
+
+
+def mesh_eigenvalues(fc_rows, atoms, qpoints, n_super, masses, device=None):
+    """Eigenvalues of D(q) on the device (``uf3_phonon_mesh``): ``(lam [nq, 3N] ascending, eV / (amu A^2); sweeps int32 [nq])``.
+    fc_rows [N, N_sc, 3, 3] and per-atom masses as for ``dynamical_matrices``, whose D(q) this diagonalises (the same sum in
+    another order: agreement to rounding).  Cells of more than ``MESH_MAX_ATOMS`` atoms raise ValueError -- there is no host
+    fallback; a q-point whose Jacobi iteration hits its sweep cap raises RuntimeError."""
+    n = _frame(atoms)
+    if n > MESH_MAX_ATOMS:
+        raise ValueError(f"harmonic: the q-mesh eigensolver takes cells of at most {MESH_MAX_ATOMS} atoms (D(q) is held in LDS), "
+                         f"this one has {n}")
+    fc = np.asarray(fc_rows, dtype=float)
+    n_sc = n * int(n_super) ** 3
+    if fc.shape != (n, n_sc, 3, 3):
+        raise ValueError(f"harmonic.mesh_eigenvalues: fc_rows must be [{n}, {n_sc}, 3, 3], got {fc.shape}")
+    q = np.ascontiguousarray(np.atleast_2d(np.asarray(qpoints, dtype=float)))
+    if q.ndim != 2 or q.shape[1] != 3 or len(q) < 1:
+        raise ValueError("harmonic.mesh_eigenvalues: qpoints must be [nq, 3] with nq >= 1")
+    m = np.asarray(masses, dtype=float).reshape(-1)
+    if m.shape != (n,) or np.any(m <= 0):
+        raise ValueError("harmonic.mesh_eigenvalues: one positive mass per atom")
+    flat = np.ascontiguousarray(fc.transpose(0, 2, 1, 3).reshape(3 * n, 3 * n_sc))
+    inv_sqrt_m = np.ascontiguousarray(1.0 / np.sqrt(m))
+    terms, w = image_terms(atoms, n_super)
+    lam = np.empty((len(q), 3 * n))
+    status = np.empty(len(q), dtype=np.int32)
+    ctx = _mesh_context(device)
+    addr = _lib._addr
+    ctx.check(ctx.lib.uf3_phonon_mesh(ctx.handle, n, n_sc, addr(flat), addr(inv_sqrt_m), len(terms), addr(terms), addr(w), len(q),
+                                      addr(q), addr(lam), addr(status)))
+    if np.any(status < 0):
+        bad = np.flatnonzero(status < 0)
+        raise RuntimeError(f"harmonic.mesh_eigenvalues: the Jacobi iteration did not converge within its sweep cap at {len(bad)} "
+                           f"q-point(s), the first q = {q[bad[0]].tolist()}")
+    return lam, status
+
+
+def _weights(weights, nq):
+    if weights is None:
+        return None
+    w = np.ascontiguousarray(weights, dtype=np.int64).reshape(-1)
+    if w.shape != (nq,) or np.any(w < 0):
+        raise ValueError("harmonic: one non-negative integer weight per q-point")
+    return w
+
+
+def dos_from_eigenvalues(lam, weights=None, edges=None, samples=None, sigma=None, device=None):
+    """``uf3_phonon_dos`` on eigenvalues lam [nq, n_modes]: ``(counts int64 [len(edges) - 1] or None, dos [len(samples)] or
+    None)``.  counts: numpy's histogram rule over ``edges`` (THz), weighted by the integer q-weights.  dos: Gaussians of width
+    ``sigma`` (THz) at ``samples``, normalised per q-point (its integral is the number of modes per cell)."""
+    lam = np.ascontiguousarray(lam, dtype=float)
+    if lam.ndim != 2 or lam.size == 0:
+        raise ValueError("harmonic.dos_from_eigenvalues: lam must be [nq, n_modes]")
+    nq, nm = lam.shape
+    w = _weights(weights, nq)
+    counts = dos = None
+    if edges is not None:
+        edges = np.ascontiguousarray(edges, dtype=float).reshape(-1)
+        if len(edges) < 2 or np.any(np.diff(edges) <= 0):
+            raise ValueError("harmonic.dos_from_eigenvalues: edges must be strictly increasing")
+        counts = np.zeros(len(edges) - 1, dtype=np.int64)
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=float).reshape(-1)
+        if sigma is None or not float(sigma) > 0:
+            raise ValueError("harmonic.dos_from_eigenvalues: sigma must be positive")
+        dos = np.zeros(len(samples))
+    if counts is None and dos is None:
+        raise ValueError("harmonic.dos_from_eigenvalues: give edges, samples or both")
+    ctx = _mesh_context(device)
+    addr = _lib._addr
+    ctx.check(ctx.lib.uf3_phonon_dos(ctx.handle, nm, nq, addr(lam), addr(w), 0 if counts is None else len(counts), addr(edges),
+                                     addr(counts), 0 if dos is None else len(dos), addr(samples),
+                                     float(sigma) if dos is not None else 0.0, addr(dos)))
+    return counts, dos
+
+
+def thermo_from_eigenvalues(lam, temperatures, weights=None, cutoff_THz=1e-3, device=None):
+    """``uf3_phonon_thermo`` on eigenvalues lam [nq, n_modes]: dict of ``temperatures`` (K), ``free_energy``, ``internal_energy``
+    (eV per cell), ``entropy``, ``heat_capacity`` (eV / K per cell), each [nT]; ``zero_point_energy`` (eV) and ``n_excluded``, the
+    summed q-weight of the modes with f <= cutoff_THz, which are left out of every sum."""
+    lam = np.ascontiguousarray(lam, dtype=float)
+    if lam.ndim != 2 or lam.size == 0:
+        raise ValueError("harmonic.thermo_from_eigenvalues: lam must be [nq, n_modes]")
+    nq, nm = lam.shape
+    w = _weights(weights, nq)
+    T = np.ascontiguousarray(np.atleast_1d(np.asarray(temperatures, dtype=float)).reshape(-1))
+    if len(T) < 1 or not np.all(np.isfinite(T)) or np.any(T < 0):
+        raise ValueError("harmonic.thermo_from_eigenvalues: temperatures must be finite and >= 0")
+    if not float(cutoff_THz) >= 0:
+        raise ValueError("harmonic.thermo_from_eigenvalues: cutoff_THz must be >= 0")
+    out = np.empty((len(T), 4))
+    zpe = np.empty(1)
+    n_excl = np.empty(1, dtype=np.int64)
+    ctx = _mesh_context(device)
+    addr = _lib._addr
+    ctx.check(ctx.lib.uf3_phonon_thermo(ctx.handle, nm, nq, addr(lam), addr(w), len(T), addr(T), float(cutoff_THz), addr(out),
+                                        addr(zpe), addr(n_excl)))
+    return {"temperatures": T, "free_energy": out[:, 0].copy(), "internal_energy": out[:, 1].copy(), "entropy": out[:, 2].copy(),
+            "heat_capacity": out[:, 3].copy(), "zero_point_energy": float(zpe[0]), "n_excluded": int(n_excl[0])}
+
+
+def _mesh_points(mesh, qpoints, gamma_centred, time_reversal):
+    if (mesh is None) == (qpoints is None):
+        raise ValueError("harmonic: give either mesh or qpoints")
+    if mesh is not None:
+        return qmesh(mesh, gamma_centred=gamma_centred, time_reversal=time_reversal)
+    q = np.ascontiguousarray(np.atleast_2d(np.asarray(qpoints, dtype=float)))
+    return q, np.ones(len(q), dtype=np.int64)
+
+
+def _mesh_lambda(calc, atoms, mesh, qpoints, n_super, masses, gamma_centred, time_reversal, what):
+    _periodic(atoms, what)
+    n = _frame(atoms)
+    if n > MESH_MAX_ATOMS:
+        raise ValueError(f"harmonic: the q-mesh eigensolver takes cells of at most {MESH_MAX_ATOMS} atoms (D(q) is held in LDS), "
+                         f"this one has {n}")
+    m = _masses(atoms, masses)
+    q, w = _mesh_points(mesh, qpoints, gamma_centred, time_reversal)
+    fc = _supercell_rows(calc, atoms, n_super)
+    lam, _ = mesh_eigenvalues(fc, atoms, q, n_super, m, device=calc.device)
+    return lam, q, w
+
+
+def mesh_frequencies(calc, atoms, mesh=None, qpoints=None, n_super=5, masses=None, gamma_centred=True, time_reversal=True):
+    """Phonon frequencies on a q-mesh, diagonalised on the device: ``(frequencies [nq, 3N] THz ascending, q [nq, 3] reduced,
+    weights int64 [nq])``.  ``mesh`` (n1, n2, n3): ``qmesh``'s points; or explicit ``qpoints`` (weights 1).  Force constants
+    and conventions are ``phonon_frequencies``'s (one device Hessian of the n_super^3 supercell, phonopy's minimum-image
+    weights, ``md.resolve_masses`` rules), and so are the numbers, to rounding.  Eigenvalues only: no eigenvectors on the
+    mesh.  Cells of more than 32 atoms raise ValueError."""
+    lam, q, w = _mesh_lambda(calc, atoms, mesh, qpoints, n_super, masses, gamma_centred, time_reversal, "mesh_frequencies")
+    return eigenvalues_to_frequencies(lam), q, w
+
+
+def density_of_states(calc, atoms, mesh, n_super=5, masses=None, sigma=None, frequencies=None, n_samples=401, edges=None,
+                      n_bins=100, cutoff_THz=1e-3, gamma_centred=True, time_reversal=True):
+    """
+    Phonon density of states on a q-mesh, all on the device.  dict:
+      ``frequencies`` [n_samples] THz   the sample points (given, or evenly spaced from min(f) - 6 sigma to max(f) + 6 sigma)
+      ``dos`` [n_samples]               Gaussian-smeared states per THz per cell (integral: 3N); ``sigma`` THz, default 1/100 of
+                                        the largest frequency
+      ``edges`` [n_bins + 1], ``counts`` int64 [n_bins]   weighted histogram of the mode frequencies (numpy's bin rule; Sigma
+                                        counts = 3N n1 n2 n3 when the edges cover every mode)
+      ``n_imaginary``                   summed q-weight of the modes below -cutoff_THz; anything non-zero also raises a
+                                        RuntimeWarning: the structure is dynamically unstable
+      ``sigma``, ``qpoints``, ``weights``, ``mode_frequencies`` [nq, 3N]
+    Gaussian smearing where phonopy's default is the tetrahedron method; no point-group reduction of the mesh (time reversal
+    only); no projected DOS.
+    """
+    lam, q, w = _mesh_lambda(calc, atoms, mesh, None, n_super, masses, gamma_centred, time_reversal, "density_of_states")
+    f = eigenvalues_to_frequencies(lam)
+    f_max = max(float(np.abs(f).max()), 1e-6)
+    sigma = f_max / 100.0 if sigma is None else float(sigma)
+    if not sigma > 0:
+        raise ValueError("harmonic.density_of_states: sigma must be positive")
+    if frequencies is None:
+        frequencies = np.linspace(float(f.min()) - 6 * sigma, float(f.max()) + 6 * sigma, int(n_samples))
+    if edges is None:
+        pad = 1e-9 * f_max
+        edges = np.linspace(min(float(f.min()), 0.0) - pad, float(f.max()) + pad, int(n_bins) + 1)
+    edges = np.asarray(edges, dtype=float)
+    counts, dos = dos_from_eigenvalues(lam, w, edges=edges, samples=frequencies, sigma=sigma, device=calc.device)
+    n_imag = int((w[:, None] * (f < -float(cutoff_THz))).sum())
+    if n_imag:
+        warnings.warn(f"harmonic.density_of_states: {n_imag} imaginary mode(s) on the mesh (lowest {f.min():.4g} THz): the "
+                      "structure is dynamically unstable", RuntimeWarning)
+    return {"frequencies": np.asarray(frequencies, dtype=float), "dos": dos, "edges": edges, "counts": counts,
+            "n_imaginary": n_imag, "sigma": sigma, "qpoints": q, "weights": w, "mode_frequencies": f}
+
+
+def thermal_properties(calc, atoms, temperatures, mesh, n_super=5, masses=None, cutoff_THz=1e-3, gamma_centred=True,
+                       time_reversal=True):
+    """
+    Harmonic thermodynamics of the crystal from a q-mesh, all on the device.  dict of arrays per temperature (K):
+    ``free_energy``, ``internal_energy`` (eV per cell), ``entropy``, ``heat_capacity`` (eV / K per cell), with ``temperatures``,
+    ``zero_point_energy`` (eV per cell), ``n_excluded`` -- the summed q-weight of the modes with f <= cutoff_THz (the three
+    acoustic modes at Gamma; imaginary modes too), which are left out of every sum -- and ``n_imaginary`` (modes below
+    -cutoff_THz; non-zero raises a RuntimeWarning).  Units differ from phonopy's (kJ / mol, J / K / mol): eV per cell here.
+    No quasi-harmonic volume loop.
+    """
+    lam, q, w = _mesh_lambda(calc, atoms, mesh, None, n_super, masses, gamma_centred, time_reversal, "thermal_properties")
+    res = thermo_from_eigenvalues(lam, temperatures, w, cutoff_THz=cutoff_THz, device=calc.device)
+    f = eigenvalues_to_frequencies(lam)
+    n_imag = int((w[:, None] * (f < -float(cutoff_THz))).sum())
+    if n_imag:
+        warnings.warn(f"harmonic.thermal_properties: {n_imag} imaginary mode(s) on the mesh (lowest {f.min():.4g} THz) are left "
+                      "out of the sums: the structure is dynamically unstable", RuntimeWarning)
+    res["n_imaginary"] = n_imag
+    return res
 
 
 # ----------------------------------------------------------------------------------------------------- elastic constants
