@@ -23,6 +23,12 @@ pieces over RCCL.  --workload lead0 (2-element, no leading trim, F = 1798) is th
 forces, energy, strain derivative.  The inputs are seeded, so two builds run with the same arguments compare output for output
 (energy rows and fit sums go through atomics: equal to the last bits, not bitwise).
 
+A plain run does what the headline needs and no more: set up, warm up, time the K steps, write --dump-outputs, print the
+line.  Its `roofline` holds what the timed steps themselves measured (HIP events of the launch group, the algorithmic bytes);
+every figure that takes a run of its own -- the realised pair / triplet counts behind the fp64 figures, a roofline.traffic
+measured in the run, cpu_baseline, extra -- is null or absent.  --full adds all of them, after the timed region (--no-cpu-baseline, --no-extra and
+--no-traffic take single ones out again).
+
 Extra objects on the JSON line:
   roofline      the dominant kernel launch group of a step, timed with HIP events on the launch stream.  Both
                 ceilings are reported: `hbm` = algorithmic bytes (28N+75+8F(3N+1) per frame x frames per
@@ -30,11 +36,11 @@ Extra objects on the JSON line:
                 limiter: on MI355X an fp64 MFMA holds the SIMD's vector issue while it runs
                 (tools/experiments/dp_pipe_bench.hip), so matrix and vector fp64 work add up -- the launch is bound by
                 fp64 issue ("mfma" in the contract's vocabulary), not by HBM, at these F.  `traffic` is measured in the run
-                (N = 1, featurize mode): two short child runs of this command under `rocprofv3 --pmc` (FETCH_SIZE, WRITE_SIZE,
+                (--full, N = 1, featurize mode): two short child runs of this command under `rocprofv3 --pmc` (FETCH_SIZE, WRITE_SIZE,
                 separate passes), after the timed region; --no-traffic, or a box without the profiler, quotes the committed
                 PMC passes under profiles/ instead, labelled as such.
-  cpu_baseline  the oracle (oracle/uf3_oracle.c, "port") timed on rank 0 on frames of the same workload.
-  extra         (N = 1, default mode only; measured AFTER the headline's timed region) one sub-line per other BASELINE
+  cpu_baseline  (--full) the oracle (oracle/uf3_oracle.c, "port") timed on rank 0 on frames of the same workload.
+  extra         (--full, N = 1, default mode only; measured AFTER the headline's timed region) one sub-line per other BASELINE
                 configuration, each with ms_per_step and its own roofline: fit_w (config 4: W, F = 73, featurize + X^T X /
                 X^T y), fit_c4 (the same at F = 434), lead0 (F = 1798: the bandwidth-heavier featurize case), eval_50k
                 (config 5: ternary 50k-atom frame, uf3_eval_dev loop, with the oracle's evaluator as cpu_baseline) and
@@ -86,8 +92,8 @@ def spawn_ranks(n_gpus, argv, device_count=None, runner=None, port=None):
     return int(runner(rank_command(n_gpus, argv, port), env=env))
 
 
-def main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
+def parse_args(argv):
+    """(parser, arguments); without --full the arguments ask for nothing beside the headline"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks = GPUs of this node (default: WORLD_SIZE under torch.distributed.run, else 1); without a "
@@ -109,10 +115,14 @@ def main(argv=None):
     ap.add_argument("--row-ld", type=int, default=0,
                     help="doubles between consecutive force rows in HBM (featurize mode): 0 = F (dense rows, the default), -1 = F "
                          "rounded up to a multiple of 16 (every row on 128-byte lines of its own), else the stride itself")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the sub-lines of the other BASELINE configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the realised pair / triplet "
+                         "counts behind the roofline's fp64 figures, roofline.traffic, cpu_baseline and the sub-lines of the other "
+                         "BASELINE configurations (off by default: a plain run sets up, warms up, times, dumps and prints)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the sub-lines of the other BASELINE configurations")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="do not measure roofline.traffic in this run (two short child runs under rocprofv3 --pmc); the figure "
+                    help="with --full: do not measure roofline.traffic in this run (two short child runs under rocprofv3 --pmc); the figure "
                          "of the committed PMC passes under profiles/ is quoted instead")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (rank 0's share) as DIR/<name>.npy, float64, "
@@ -120,6 +130,14 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:      # (a plain run: nothing beside the headline)
+        args.no_cpu_baseline = args.no_extra = args.no_traffic = True
+    return ap, args
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    ap, args = parse_args(argv)
 
     distributed = "RANK" in os.environ and "MASTER_PORT" in os.environ      # launched by torch.distributed.run
     world = int(os.environ.get("WORLD_SIZE", "1")) if distributed else 1
@@ -274,9 +292,10 @@ def main(argv=None):
         hbm_gbs = bytes_per_launch / (launch_ms * 1e-3) / 1e9
         # algorithmic fp64 work of the featurizer: ~100 flop per directed pair, ~3.1 kflop per triplet
         # (p, T as realised on frame 0 of this batch, from the device's own lists -- not the ideal lattice's 58 / 91)
-        pairs_per_atom, trip_per_atom = realised_counts(fz, frames[0])
-        flops_frame = n_atoms * (100.0 * pairs_per_atom + 3100.0 * trip_per_atom)
-        feat_tf = flops_frame * B / (launch_ms * 1e-3) / 1e12
+        # (a run of its own on the device: --full only; without it the fp64 figures of the roofline are null)
+        counts = realised_counts(fz, frames[0]) if args.full else None
+        flops_frame = _featurizer_flops(n_atoms, counts) if counts else None
+        feat_tf = flops_frame * B / (launch_ms * 1e-3) / 1e12 if counts else None
         # HBM bytes per launch from the PMC passes of this same command (separate rocprofv3 --pmc FETCH_SIZE /
         # WRITE_SIZE runs, summary committed under profiles/); null when the workload differs
         traffic, traffic_source = None, None
@@ -296,17 +315,17 @@ def main(argv=None):
         hbm = dict(achieved=round(hbm_gbs, 2), peak=8000.0, unit="GB/s", frac=round(hbm_gbs / 8000.0, 5),
                    algorithmic_bytes_per_launch=bytes_per_launch)
         if not fit:
-            roofline = dict(bound="mfma", achieved=round(feat_tf, 3), peak=78.6, unit="TFLOP/s", frac=round(feat_tf / 78.6, 5),
+            roofline = dict(bound="mfma", achieved=_round(feat_tf, 3), peak=78.6, unit="TFLOP/s", frac=_round(_over(feat_tf, 78.6), 5),
                             traffic=traffic, traffic_source=traffic_source, hbm=hbm,
                             bound_note="compute roofline = the fp64 peak, 78.6 TF (vector and matrix fp64 are one pipe on MI355X, "
                                        "tools/experiments/dp_pipe_bench.hip); since round 4 the 3-body rows come from the vector units "
                                        "alone (k_featurize3: ~5400 vector instructions and ~6100 LDS cycles per atom, LDS ~80 % busy); "
                                        "achieved = ALGORITHMIC flops (SURVEY 8d), the HBM view is in `hbm`",
                             kernel=feat_kernel, launch_ms=round(launch_ms, 4), launches=launches,
-                            algorithmic_flops_per_launch=flops_frame * B,
-                            realised_per_atom=dict(pairs=round(pairs_per_atom, 2), triplet_candidates=round(trip_per_atom, 2),
+                            algorithmic_flops_per_launch=flops_frame * B if counts else None,
+                            realised_per_atom=dict(pairs=round(counts[0], 2), triplet_candidates=round(counts[1], 2),
                                                    note="frame 0 of the batch, from the device's lists (uf3_neighbors_debug); the ideal "
-                                                        "bcc lattice has 58 / 91"),
+                                                        "bcc lattice has 58 / 91") if counts else None,
                             executed_fp64=_executed_fp64(n_atoms, F, B, launch_ms),
                             neighbor_ms_per_step=round(timing["neighbor_ms"] / args.steps, 4))
         else:
@@ -319,8 +338,8 @@ def main(argv=None):
             gram_flops_full = 2.0 * (3 * n_atoms + 1) * n_keep * n_keep * B
             gram_ms = timing["gram_ms"] / args.steps
             gram_tf = gram_flops / (gram_ms * 1e-3) / 1e12
-            step_tf = (flops_frame * B + gram_flops) / (1e-3 * 1e3 * elapsed / args.steps) / 1e12
-            roofline = dict(bound="mfma", achieved=round(step_tf, 3), peak=78.6, unit="TFLOP/s", frac=round(step_tf / 78.6, 5),
+            step_tf = (flops_frame * B + gram_flops) / (1e-3 * 1e3 * elapsed / args.steps) / 1e12 if counts else None
+            roofline = dict(bound="mfma", achieved=_round(step_tf, 3), peak=78.6, unit="TFLOP/s", frac=_round(_over(step_tf, 78.6), 5),
                             traffic=None, hbm=hbm,
                             bound_note="whole step (featurizer + X^T X): fp64 flops (featurizer: SURVEY 8d per pair / triplet; Gram: "
                                        "the upper-triangle tiles of the dense product; the species-wise launches of a multi-element batch execute fewer) / step time; "
@@ -462,11 +481,12 @@ def eval_mode(args, torch, dist, dev, distributed, world, rank):
         dump_outputs(args.dump_outputs, dict(forces=host[:3 * n].reshape(n, 3), energy=host[3 * n:3 * n + 1],
                                              strain_derivative=host[3 * n + 1:]))
     if moving:
-        from uf3_amd.data.atoms import Atoms
-        atoms = Atoms(numbers=atoms.get_atomic_numbers(), positions=d_pos.cpu().numpy(), cell=atoms.get_cell(), pbc=True)   # (what the last step saw)
+        if args.full:
+            from uf3_amd.data.atoms import Atoms
+            atoms = Atoms(numbers=atoms.get_atomic_numbers(), positions=d_pos.cpu().numpy(), cell=atoms.get_cell(), pbc=True)   # (what the last step saw)
         md_stats = ctx.md_stats()
         ev.close()
-    counts = _counts_of(basis, atoms, dev.index)              # (p, T of the frame the last step saw)
+    counts = _counts_of(basis, atoms, dev.index) if args.full else None      # (p, T of the frame the last step saw: a run of its own)
     f, e = host[:3 * n].reshape(n, 3), float(host[3 * n])
     assert os.environ.get("UF3_BENCH_NOCHECK") or (np.isfinite(host).all() and np.abs(f.sum(0)).max() < 1e-8 * max(1.0, np.abs(f).max()) * n ** 0.5)
     dt = elapsed / args.steps
@@ -491,8 +511,8 @@ def eval_mode(args, torch, dist, dev, distributed, world, rank):
                                if moving else None),
                            rccl_world_size=dist.get_world_size() if distributed else 1, forced_collective=forced,
                            collective=("uf3_allreduce_sum_f64 (librccl behind the C ABI)" if native else "torch.distributed all_reduce (RCCL)")),
-               roofline=_roof(_eval_flops(n, counts), 52.0 * n + 75 + 8.0 * len(calc._c3), dt,
-                              "mfma", realised_per_atom=_counts_note(counts),
+               roofline=_roof(_eval_flops(n, counts) if counts else None, 52.0 * n + 75 + 8.0 * len(calc._c3), dt,
+                              "mfma", realised_per_atom=_counts_note(counts) if counts else None,
                               note="flops = N (100 p + 700 T) at the realised p, T: every triplet once at its centre; 700 flop per triplet is "
                                    "this build's own price (SURVEY 8d prices the evaluator by bytes only)"),
                cpu_baseline=cpu)
@@ -635,12 +655,22 @@ def _counts_note(counts):
                 note="realised on this line's own frame, from the device's lists (uf3_neighbors_debug)")
 
 
+def _round(x, digits):
+    """round(), with None (a figure this run did not measure) passed through"""
+    return None if x is None else round(x, digits)
+
+
+def _over(x, y):
+    return None if x is None else x / y
+
+
 def _roof(flops, bytes_, seconds, bound, **more):
-    tf, gbs = flops / seconds / 1e12, bytes_ / seconds / 1e9
-    main = (dict(bound="mfma", achieved=round(tf, 3), peak=PEAK_FP64_TF, unit="TFLOP/s", frac=round(tf / PEAK_FP64_TF, 5))
+    """``flops`` None: the realised counts were not taken (a plain run) -- the fp64 figures are null"""
+    tf, gbs = _over(_over(flops, seconds), 1e12), bytes_ / seconds / 1e9
+    main = (dict(bound="mfma", achieved=_round(tf, 3), peak=PEAK_FP64_TF, unit="TFLOP/s", frac=_round(_over(tf, PEAK_FP64_TF), 5))
             if bound == "mfma" else
             dict(bound="hbm", achieved=round(gbs, 2), peak=PEAK_HBM_GBS, unit="GB/s", frac=round(gbs / PEAK_HBM_GBS, 5)))
-    main.update(fp64=dict(achieved=round(tf, 3), peak=PEAK_FP64_TF, unit="TFLOP/s", frac=round(tf / PEAK_FP64_TF, 5),
+    main.update(fp64=dict(achieved=_round(tf, 3), peak=PEAK_FP64_TF, unit="TFLOP/s", frac=_round(_over(tf, PEAK_FP64_TF), 5),
                           algorithmic_flops_per_step=flops),
                 hbm=dict(achieved=round(gbs, 2), peak=PEAK_HBM_GBS, unit="GB/s", frac=round(gbs / PEAK_HBM_GBS, 5),
                          algorithmic_bytes_per_step=bytes_), traffic=None)

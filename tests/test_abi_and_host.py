@@ -173,6 +173,25 @@ def test_bench_line_keeps_the_other_configurations_where_the_driver_looks():
     assert est is None or (est["label"] == "estimate" and est["frames_per_s_all_cores"] == pytest.approx(4.8 / est["reference_to_port_ratio"]))
 
 
+def test_bench_plain_run_asks_for_nothing_beside_the_headline():
+    """bench.py: without --full the CPU baseline, the sub-lines of the other configurations and the traffic passes are all
+    off, whatever the --no-* switches say; --full turns them on and the switches take single ones out again.  A roofline
+    without the realised counts (a plain run) keeps its bytes view and says null for the fp64 figures."""
+    import bench
+    _, plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not plain.full and plain.no_cpu_baseline and plain.no_extra and plain.no_traffic
+    assert (plain.steps, plain.warmup, plain.gpus, plain.dump_outputs) == (3, 1, 1, None)
+    _, full = bench.parse_args(["--full"])
+    assert full.full and not (full.no_cpu_baseline or full.no_extra or full.no_traffic)
+    _, some = bench.parse_args(["--full", "--no-traffic"])
+    assert some.no_traffic and not (some.no_cpu_baseline or some.no_extra)
+    lean = bench._roof(None, 8e9, 1e-3, "mfma", realised_per_atom=None)
+    assert lean["bound"] == "mfma" and lean["achieved"] is None and lean["frac"] is None and lean["fp64"]["frac"] is None
+    assert lean["hbm"]["achieved"] == pytest.approx(8000.0) and lean["hbm"]["frac"] == pytest.approx(1.0)
+    whole = bench._roof(78.6e9, 8e9, 1e-3, "mfma")
+    assert whole["achieved"] == pytest.approx(78.6) and whole["fp64"]["frac"] == pytest.approx(1.0)
+
+
 def test_bench_dump_outputs_is_a_fixed_sample_under_the_size_cap(tmp_path, monkeypatch):
     """bench.py --dump-outputs: every energy row and the force rows of a seeded sample of atoms, as many as the byte cap
     allows, the same atoms on every call; float64 .npy files; more than the cap is refused.  --steps 0 is refused too."""

@@ -2134,6 +2134,36 @@ def test_bench_under_the_launcher_runs_rccl_on_device_buffers(mode):
         values[native] = out["value"]
 
 
+@pytest.mark.parametrize("mode", ["featurize", "eval"])
+def test_bench_plain_run_is_the_headline_alone_and_full_adds_the_rest(mode):
+    """bench.py on a small workload, each run a process of its own: a plain run prints the headline with the figures its timed
+    steps measured and none that takes a run of its own (no CPU baseline, no sub-lines, no realised counts, so no fp64 figures);
+    --full prints the same headline fields with the CPU baseline (GPU against the oracle to 1e-9 inside) and the fp64 roofline."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    argv = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--mode", mode, "--atoms", "2000"]
+    argv += ["--frames-per-step", "4"] if mode != "eval" else []
+    lines = {}
+    for full in (False, True):
+        more = ["--full", "--no-traffic", "--cpu-workers", "1"] if full else []
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + argv + more, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        found = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(found) == 1, res.stdout[-2000:]
+        lines[full] = json.loads(found[0])
+    plain, whole = lines[False], lines[True]
+    for out in (plain, whole):
+        assert out["unit"] == ("frames/s" if mode != "eval" else "atom-steps/s") and out["higher_is_better"] is True and out["dtype"] == "f64"
+        assert out["steps"] == 2 and out["warmup"] == 1 and np.isfinite(out["value"]) and out["value"] > 0 and out["ms_per_step"] > 0
+    assert plain["metric"] == whole["metric"] and plain["config"]["workload"] == whole["config"]["workload"]
+    assert plain["cpu_baseline"] is None and "extra" not in plain
+    assert plain["roofline"]["achieved"] is None and plain["roofline"]["realised_per_atom"] is None
+    assert plain["roofline"]["hbm"]["achieved"] > 0
+    assert whole["cpu_baseline"]["value"] > 0 and whole["roofline"]["achieved"] > 0
+    assert whole["roofline"]["realised_per_atom"]["pairs"] > 0
+
+
 def test_random_call_sequences_on_one_context_do_not_depend_on_its_history():
     """A short run of tools/experiments/state_fuzz.py (its header: one process, the shared context, three bases x five kinds of
     frames, a seeded random sequence of featurize / evaluate / fit calls, every result against the oracle): capacities that only

@@ -24,7 +24,7 @@ $T rocprofv3 --pmc SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD
 # the evaluator's MD route against the rebuild-everything route: counters per atom and kernel times (tools/md_counters.sh)
 bash tools/md_counters.sh > $RUN/eval_counters.txt 2>&1
 # the same trace over the whole default run: the sub-lines of the other BASELINE configurations (fit, lead-0, evaluator) included
-$T rocprofv3 --kernel-trace --stats -d $RUN/trace_extra -o x --output-format csv -- python bench.py --no-cpu-baseline --no-traffic > $RUN/bench_traced_extra.json 2>/dev/null
+$T rocprofv3 --kernel-trace --stats -d $RUN/trace_extra -o x --output-format csv -- python bench.py --full --no-cpu-baseline --no-traffic > $RUN/bench_traced_extra.json 2>/dev/null
 $T python tools/bench_kernels.py > $RUN/kernels.json 2> $RUN/kernels.err
-timeout 400 python bench.py --steps 20 --warmup 5 > $RUN/bench_default.json 2> $RUN/bench_default.err
+timeout 400 python bench.py --full --steps 20 --warmup 5 > $RUN/bench_default.json 2> $RUN/bench_default.err
 cut -c1-200 $RUN/bench_default.json
