@@ -413,6 +413,27 @@ int uf3_scan_solve_dev(uf3_ctx *ctx, int32_t n_cols, int32_t n_folds, const doub
  *                          fails returns its code; the step counter then counts the completed steps and the state is that of
  *                          the failed step's drift.
  *   uf3_md_info            absolute step counter, atoms, frames.
+ *   uf3_md_run_npt         n_steps steps at constant pressure (kernels in uf3_npt.h): isotropic Martyna-Tobias-
+ *                          Klein dynamics, every frame its own piston.  A frame's cell is s * (the cell it was created with);
+ *                          v_eps = d ln s / dt.  pressure_eV_A3: the target P0; barostat_time_fs: tau_p of the piston mass
+ *                          W_p = (3N + 3) k_B piston_temperature_K tau_p^2 (piston_temperature_K > 0 always; the Python layer
+ *                          passes temperature_K unless told otherwise).  friction_per_fs and barostat_friction_per_fs both 0:
+ *                          NPH, which conserves H = KE + PE + P0 V + W_p v_eps^2 / 2; otherwise the atoms get uf3_md_run's O-step
+ *                          and the piston v_eps = c_p v_eps + sqrt((1 - c_p^2) k_B temperature_K / W_p) xi (pure damping at
+ *                          temperature_K = 0).  Random numbers: the atoms' counters are uf3_md_run's, (i, s lo, s hi, 0 / 1) with
+ *                          i < 2^28; the piston of frame f draws from counter (2^31 | f, s lo, s hi, 0), which no atom's
+ *                          counter can equal.  run(a); run(b) does the arithmetic of run(a + b).  Every frame must be periodic
+ *                          along all three axes.  For its own duration the call puts the context's MD state into a "cells
+ *                          live on the device" mode next to the run's skin: the evaluator's list key stops comparing cells, its
+ *                          kernels read the frame's current cell rows from the device copy the integrator updates, and the
+ *                          displacement test is made against reference positions that are scaled along with the cell, with the
+ *                          per-frame limit (s (skin + r_cut) - r_cut) / 2, s relative to the build; a scale outside the range
+ *                          over which the build's image ranges hold voids the lists.  The host reads the cells back in front of
+ *                          a list build and at the end of the run only.  Skin and mode are the caller's again on return, also on
+ *                          errors.  Records, when thermo_every > 0: [PE, KE, W (6), K (6), V, s, H] (17 doubles) per frame.
+ *   uf3_md_get_cells       the current cells [n_frames][9], scales s [n_frames] and strain rates v_eps [n_frames] (1/fs); NULL
+ *                          skips.  Before the first constant-pressure run: the cells of uf3_md_create, 1 and 0.
+ *   uf3_ctx_md_live        1 while the context's MD state is in the "cells live on the device" mode (tests), else 0.
  *   uf3_philox_debug       Philox4x32-10 on the device for caller-given counters [n][4] and keys [n][2] (tests).
  */
 typedef struct uf3_md uf3_md;
@@ -425,6 +446,11 @@ int uf3_md_init_velocities(uf3_md *md, double temperature_K, uint64_t seed, int 
 int uf3_md_run(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed, double skin,
                int64_t thermo_every, int with_stress, double *thermo);
 int uf3_md_info(const uf3_md *md, int64_t *step, int64_t *n_atoms, int32_t *n_frames);
+int uf3_md_run_npt(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, double pressure_eV_A3,
+                   double barostat_time_fs, double barostat_friction_per_fs, double piston_temperature_K, uint64_t seed,
+                   double skin, int64_t thermo_every, double *thermo);
+int uf3_md_get_cells(uf3_md *md, double *cells, double *scales, double *strain_rates);
+int uf3_ctx_md_live(uf3_ctx *ctx, int32_t *live);
 int uf3_philox_debug(uf3_ctx *ctx, int64_t n, const uint32_t *counters, const uint32_t *keys, uint32_t *out);
 
 /*

@@ -8,6 +8,9 @@ One process, two workloads: one 50 000-atom bcc-W frame (tests/golden/model_unar
   (a) walk      a seeded +-0.01 A random walk applied with torch ``add_`` + ``uf3_eval_dev`` (skin 0.5 A)
   (b) nve       ``MolecularDynamics.run`` at friction 0 (velocity Verlet), 300 K initial velocities
   (c) langevin  the same with friction 0.01 / fs at 300 K (BAOAB)
+  (d) nve_stress  (b) recording the stress on every step: the strain derivative every step, as constant pressure needs it
+  (e) nph       constant pressure 0, barostat time 500 fs, no friction (uf3_md_run_npt)
+  (f) npt       the same with friction 0.01 / fs on the atoms and 0.002 / fs on the piston
 Prints ms/step, atom-steps/s, the ratios (b)/(a) and (c)/(a) and the neighbour-list builds of each loop, then one JSON line.
 (b) and (c) time one ``run`` call each, which starts with one list build."""
 import argparse
@@ -73,16 +76,19 @@ def walk_loop(calc, frames, steps, warmup, dev):
         ctx.restore_stream(prev)
 
 
-def md_loop(calc, frames, steps, warmup, friction):
+def md_loop(calc, frames, steps, warmup, friction, stress=False, **barostat):
     with md.MolecularDynamics(calc, frames, 1.0, masses=MASSES, temperature_K=300.0, friction_per_fs=friction, seed=5,
-                              skin=SKIN) as dyn:
+                              skin=SKIN, **barostat) as dyn:
         dyn.initialize_velocities(300.0)
         dyn.run(warmup)
         ctx = dyn.ctx
         ctx.synchronize()
         b0 = ctx.md_stats()["builds"]
         t0 = time.perf_counter()
-        dyn.run(steps)                       # (returns after its device synchronisation)
+        if stress:
+            dyn.run(steps, thermo_every=1, stress=True)
+        else:
+            dyn.run(steps)                   # (returns after its device synchronisation)
         dt = (time.perf_counter() - t0) / steps
         return dt, ctx.md_stats()["builds"] - b0
 
@@ -103,14 +109,24 @@ def main(argv=None):
         row = {}
         for loop, fn in (("walk", lambda: walk_loop(calc, frames, args.steps, args.warmup, dev)),
                          ("nve", lambda: md_loop(calc, frames, args.steps, args.warmup, 0.0)),
-                         ("langevin", lambda: md_loop(calc, frames, args.steps, args.warmup, 0.01))):
+                         ("langevin", lambda: md_loop(calc, frames, args.steps, args.warmup, 0.01)),
+                         ("nve_stress", lambda: md_loop(calc, frames, args.steps, args.warmup, 0.0, stress=True)),
+                         ("nph", lambda: md_loop(calc, frames, args.steps, args.warmup, 0.0, pressure_eV_A3=0.0,
+                                                 barostat_time_fs=500.0)),
+                         ("npt", lambda: md_loop(calc, frames, args.steps, args.warmup, 0.01, pressure_eV_A3=0.0,
+                                                 barostat_time_fs=500.0, barostat_friction_per_fs=0.002))):
             dt, builds = fn()
             row[loop] = dict(ms_per_step=round(dt * 1e3, 4), atom_steps_per_s=round(n / dt), builds=int(builds))
-            print(f"{name:16s} {loop:9s} {dt * 1e3:8.3f} ms/step  {n / dt / 1e6:8.1f} M atom-steps/s  builds {builds}")
+            print(f"{name:16s} {loop:10s} {dt * 1e3:8.3f} ms/step  {n / dt / 1e6:8.1f} M atom-steps/s  builds {builds}")
         row["nve_over_walk"] = round(row["nve"]["ms_per_step"] / row["walk"]["ms_per_step"], 4)
         row["langevin_over_walk"] = round(row["langevin"]["ms_per_step"] / row["walk"]["ms_per_step"], 4)
+        for loop in ("nph", "npt"):
+            row[loop + "_over_nve"] = round(row[loop]["ms_per_step"] / row["nve"]["ms_per_step"], 4)
+            row[loop + "_over_nve_stress"] = round(row[loop]["ms_per_step"] / row["nve_stress"]["ms_per_step"], 4)
         row["atoms"] = n
-        print(f"{name:16s} nve/walk {row['nve_over_walk']:.3f}  langevin/walk {row['langevin_over_walk']:.3f}")
+        print(f"{name:16s} nve/walk {row['nve_over_walk']:.3f}  langevin/walk {row['langevin_over_walk']:.3f}  "
+              f"nph/nve {row['nph_over_nve']:.3f}  npt/nve {row['npt_over_nve']:.3f}  nph/nve+stress {row['nph_over_nve_stress']:.3f}  "
+              f"npt/nve+stress {row['npt_over_nve_stress']:.3f}")
         result[name] = row
     print(json.dumps(dict(tool="bench_md", steps=args.steps, warmup=args.warmup, **result)))
 

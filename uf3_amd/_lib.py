@@ -30,13 +30,13 @@ EXPORTS = ["uf3_ctx_create", "uf3_ctx_destroy", "uf3_ctx_set_stream", "uf3_ctx_s
            "uf3_comm_unique_id", "uf3_comm_init", "uf3_comm_destroy", "uf3_comm_info", "uf3_allreduce_sum_f64", "uf3_gram_allreduce",
            "uf3_pair_histogram", "uf3_pair_histogram_dev", "uf3_scan_solve_dev",
            "uf3_md_create", "uf3_md_destroy", "uf3_md_set_state", "uf3_md_get_state", "uf3_md_init_velocities", "uf3_md_run",
-           "uf3_md_info", "uf3_philox_debug", "uf3_hessian", "uf3_hessian_dev",
+           "uf3_md_info", "uf3_md_run_npt", "uf3_md_get_cells", "uf3_ctx_md_live", "uf3_philox_debug", "uf3_hessian", "uf3_hessian_dev",
            "uf3_relax_create", "uf3_relax_destroy", "uf3_relax_run", "uf3_relax_get_state",
            "uf3_phonon_mesh", "uf3_phonon_mesh_dev", "uf3_phonon_dos", "uf3_phonon_dos_dev", "uf3_phonon_thermo",
            "uf3_phonon_thermo_dev"]
 
 
-SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_device.h", "uf3_md.h", "uf3_hessian.h", "uf3_relax.h", "uf3_phonon.h", os.path.join("..", "..", "include", "uf3_hip.h"))
+SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_device.h", "uf3_md.h", "uf3_hessian.h", "uf3_relax.h", "uf3_phonon.h", "uf3_npt.h", os.path.join("..", "..", "include", "uf3_hip.h"))
 
 
 def source_build_id(csrc_dir=None):
@@ -197,6 +197,9 @@ def load():
         lib.uf3_md_init_velocities.argtypes = [vp, dbl, C.c_uint64, C.c_int]
         lib.uf3_md_run.argtypes = [vp, i64, dbl, dbl, dbl, C.c_uint64, dbl, i64, C.c_int, vp]
         lib.uf3_md_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]
+        lib.uf3_md_run_npt.argtypes = [vp, i64, dbl, dbl, dbl, dbl, dbl, dbl, dbl, C.c_uint64, dbl, i64, vp]
+        lib.uf3_md_get_cells.argtypes = [vp, vp, vp, vp]
+        lib.uf3_ctx_md_live.argtypes = [vp, C.POINTER(i32)]
         lib.uf3_philox_debug.argtypes = [vp, i64, vp, vp, vp]
         for name in ("uf3_hessian", "uf3_hessian_dev"):
             getattr(lib, name).argtypes = [vp, C.POINTER(Frames), vp, vp, vp, vp, vp, i64, i64, vp, vp, vp]
@@ -311,6 +314,12 @@ class Context:
         b, s, r = C.c_int64(), C.c_int64(), C.c_int64()
         self.check(self.lib.uf3_ctx_md_stats(self.handle, C.byref(b), C.byref(s), C.byref(r)))
         return dict(builds=b.value, steps=s.value, redone=r.value)
+
+    def md_live(self):
+        """True while the MD state is in the "cells live on the device" mode (inside a constant-pressure run only)."""
+        live = C.c_int32()
+        self.check(self.lib.uf3_ctx_md_live(self.handle, C.byref(live)))
+        return bool(live.value)
 
     def __del__(self):
         try:

@@ -19,6 +19,7 @@
 #include "uf3_kernels.h"
 #include "uf3_feat3.h"
 #include "uf3_md.h"
+#include "uf3_npt.h"
 #include "uf3_hessian.h"
 #include "uf3_relax.h"
 #include "uf3_phonon.h"
@@ -156,6 +157,12 @@ struct uf3_ctx {
         size_t inbox_zeroed = 0;                          // bytes of inbox known to hold no stamp of a future launch
         size_t geo_bytes = 0;
         long long builds = 0, steps = 0, redone = 0;
+        // "the cells live on the device" (uf3_md_run_npt alone sets it, for its own duration): the integrator keeps the current
+        // cells in live_dev [n_frames][9] and in `geo`; the key does not compare cells, and the host copy live_host (what the
+        // caller's uf3_frames points at) is refreshed only in front of a list build
+        bool live = false;
+        const double *live_dev = nullptr;
+        double *live_host = nullptr;
     } md;
     // RCCL communicator of this rank (uf3_comm_init): the library is opened at run time (no link dependency), see rccl_api()
     void *comm = nullptr;
@@ -1963,7 +1970,14 @@ static bool md_key_matches(const uf3_ctx::MdState &md, const uf3_basis *b, const
     if (!md.valid || md.basis != b || !fr || !fr->atom_offsets || !fr->cells || !fr->pbc || fr->n_frames != md.n_frames) return false;
     const size_t nf = (size_t)fr->n_frames;
     return fr->atom_offsets[nf] == md.natoms && !memcmp(fr->atom_offsets, md.offsets.data(), 8 * (nf + 1)) &&
-           !memcmp(fr->cells, md.cells.data(), 72 * nf) && !memcmp(fr->pbc, md.pbc.data(), 3 * nf);
+           (md.live || !memcmp(fr->cells, md.cells.data(), 72 * nf)) && !memcmp(fr->pbc, md.pbc.data(), 3 * nf);
+}
+
+// cells that live on the device: the host's copy brought up to date (in front of anything that reads the cells on the host)
+static int md_live_fetch(uf3_ctx *c, const uf3_frames *fr) {
+    HIPCHK(c, hipMemcpyAsync(c->md.live_host, c->md.live_dev, 72 * (size_t)fr->n_frames, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return UF3_OK;
 }
 
 // may_defer: the caller's step has a verdict of its own (status words read behind its last kernel) and nothing zeroes them between
@@ -2099,11 +2113,17 @@ static int eval_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, co
     c->md_step = md_step;
     const bool was_clean = c->md.flags_clean;      // (true only straight after an MD step of eval_host that set no status word)
     c->md.flags_clean = false;
+    if (c->md.live && (!md_step || c->md.stale || !md_key_matches(c->md, b, fr))) {
+        rc = md_live_fetch(c, fr);                  // (a list build or the rebuild route is due: both read the cells on the host)
+        if (rc) return rc;
+    }
     if (md_step) {
         HIPCHK(c, hipSetDevice(c->device));
         if (c->md.stale || !md_key_matches(c->md, b, fr)) {
             rc = md_build(b, fr, d_pos, d_z, P, true);
             if (rc) return rc;
+        } else if (c->md.live) {
+            // (the integrator's frame kernel has zeroed the step's status words and its move kernel has raised those of the list test)
         } else if (c->staged_in_dev && d_pos == (const double *)c->stage_cur) {
             // positions | species are in the device block already (upload_frames, through the BAR).  k_md_fetch also zeroed the
             // step's status words: needed only when they are not known to be zero (was_clean: the previous call was an MD step
@@ -2393,6 +2413,7 @@ static int eval_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, co
                     // new lists from these positions, and again
                     if (attempt >= 5) return fail(c, UF3_EOVERFLOW, "MD neighbour lists did not settle");
                     c->md.redone++;
+                    if (c->md.live) { rc = md_live_fetch(c, fr); if (rc) return rc; }
                     rc = md_build(b, fr, d_pos, d_z, P);
                     if (rc) return rc;
                     md_prepared(c, P);
@@ -3587,13 +3608,21 @@ struct uf3_md {
     Buf pos, vel, frc, inv_m, z, offsets_dev, energies, virials, kin, ring;
     int64_t step = 0;                           // absolute step counter (feeds the random numbers)
     bool forces_valid = false;                  // frc / energies describe pos
+    // constant-pressure runs (uf3_md_run_npt, uf3_npt.h): chunk table, pistons, the current cells on the device
+    Buf blk_frame, blk_lo, blk_n, frame_blk, frame_of, npt_st, npt_coef, npt_partial, cells_dev;
+    int n_blocks = 0;
+    bool npt_ready = false;
+    bool virials_valid = false;                 // virials describe pos and cells (with forces_valid)
+    bool g_valid = false;                       // the pistons' g_close belongs to the current state
 };
 
 extern "C" void uf3_md_destroy(uf3_md *md) {
     if (!md) return;
     hipSetDevice(md->c->device);
     hipStreamSynchronize(md->c->stream);
-    for (Buf *p : {&md->pos, &md->vel, &md->frc, &md->inv_m, &md->z, &md->offsets_dev, &md->energies, &md->virials, &md->kin, &md->ring})
+    for (Buf *p : {&md->pos, &md->vel, &md->frc, &md->inv_m, &md->z, &md->offsets_dev, &md->energies, &md->virials, &md->kin, &md->ring,
+                   &md->blk_frame, &md->blk_lo, &md->blk_n, &md->frame_blk, &md->frame_of, &md->npt_st, &md->npt_coef, &md->npt_partial,
+                   &md->cells_dev})
         p->release();
     delete md;
 }
@@ -3613,6 +3642,7 @@ static int md_upload(uf3_md *md, const double *pos, const double *vel) {
     if (vel) HIPCHK(c, hipMemcpyAsync(md->vel.p, vel, 8 * n3, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (pos) md->forces_valid = false;
+    md->g_valid = false;
     return UF3_OK;
 }
 
@@ -3671,6 +3701,7 @@ static int md_forces(uf3_md *md, bool virial) {
     int rc = eval_impl(md->b, &md->fr, md->pos.as<double>(), md->z.as<int32_t>(), md->c1.data(), md->c2.data(), md->c3.data(),
                        md->energies.as<double>(), md->frc.as<double>(), virial ? md->virials.as<double>() : nullptr);
     md->forces_valid = rc == UF3_OK;
+    md->virials_valid = md->forces_valid && virial;
     return rc;
 }
 
@@ -3705,6 +3736,7 @@ extern "C" int uf3_md_init_velocities(uf3_md *md, double temperature_K, uint64_t
                        exact_temperature ? 1 : 0);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    md->g_valid = false;
     return UF3_OK;
 }
 
@@ -3799,6 +3831,227 @@ extern "C" int uf3_md_run(uf3_md *md, int64_t n_steps, double dt_fs, double temp
         return fail(c, rc, msg);
     }
     return uf3_ctx_md_skin(c, caller_skin);
+}
+
+
+// ------------------------------------------------------------------------------ constant pressure (uf3_md_run_npt, uf3_npt.h)
+// The same state as above plus one piston per frame.  Between two force calls: k_npt_partial, k_npt_frame, k_npt_move.  The
+// cells change on every step and stay on the device: the evaluator runs on its persistent lists in the "cells live" mode of
+// its MD state (eval_impl), and the host's copy is refreshed in front of a list build and at the end of the run.
+static int npt_init(uf3_md *md) {
+    if (md->npt_ready) return UF3_OK;
+    uf3_ctx *c = md->c;
+    const int nf = md->n_frames;
+    const int64_t n = md->natoms;
+    std::vector<int> blk_frame, blk_n, frame_blk(1, 0), frame_of(n);
+    std::vector<long long> blk_lo;
+    std::vector<NptFrame> st(nf);
+    for (int f = 0; f < nf; f++) {
+        for (int64_t lo = md->offsets[f]; lo < md->offsets[f + 1]; lo += UF3_NPT_THREADS) {
+            blk_frame.push_back(f);
+            blk_lo.push_back(lo);
+            blk_n.push_back((int)std::min<int64_t>(UF3_NPT_THREADS, md->offsets[f + 1] - lo));
+        }
+        frame_blk.push_back((int)blk_frame.size());
+        for (int64_t i = md->offsets[f]; i < md->offsets[f + 1]; i++) frame_of[i] = f;
+        if (!(md->pbc[3 * f] && md->pbc[3 * f + 1] && md->pbc[3 * f + 2]))
+            return fail(c, UF3_EINVAL, "uf3_md_run_npt: every frame must be periodic along all three axes");
+        NptFrame &S = st[f];
+        memset(&S, 0, sizeof(S));
+        const double *cl = md->cells.data() + 9 * (size_t)f;
+        double nrm[3][3];
+        cross3(cl + 3, cl + 6, nrm[0]); cross3(cl + 6, cl, nrm[1]); cross3(cl, cl + 3, nrm[2]);
+        const double vol = std::fabs(dot3(cl, nrm[0]));
+        if (!(vol > 0.0) || !std::isfinite(vol)) return fail(c, UF3_EINVAL, "uf3_md_run_npt: a frame's cell is singular");
+        S.s = S.s_closed = S.s_build = 1.0;
+        for (int k = 0; k < 9; k++) S.cell0[k] = cl[k];
+        S.vol0 = vol;
+        for (int k = 0; k < 3; k++) S.hgt0[k] = vol / norm3(nrm[k]);
+    }
+    const int nb = (int)blk_frame.size();
+    HIPCHK(c, hipSetDevice(c->device));
+    if (md->blk_frame.ensure(4 * (size_t)nb) || md->blk_lo.ensure(8 * (size_t)nb) || md->blk_n.ensure(4 * (size_t)nb) ||
+        md->frame_blk.ensure(4 * (size_t)(nf + 1)) || md->frame_of.ensure(4 * (size_t)n) || md->npt_st.ensure(sizeof(NptFrame) * (size_t)nf) ||
+        md->npt_coef.ensure(sizeof(NptCoef) * (size_t)nf) || md->npt_partial.ensure(24 * (size_t)nb) || md->cells_dev.ensure(72 * (size_t)nf))
+        return fail(c, UF3_ENOMEM, "uf3_md_run_npt: out of device memory");
+    hipStream_t s = c->stream;
+    if (hipMemcpyAsync(md->blk_frame.p, blk_frame.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(md->blk_lo.p, blk_lo.data(), 8 * (size_t)nb, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(md->blk_n.p, blk_n.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(md->frame_blk.p, frame_blk.data(), 4 * (size_t)(nf + 1), hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(md->frame_of.p, frame_of.data(), 4 * (size_t)n, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(md->npt_st.p, st.data(), sizeof(NptFrame) * (size_t)nf, hipMemcpyHostToDevice, s) ||
+        hipMemsetAsync(md->npt_coef.p, 0, sizeof(NptCoef) * (size_t)nf, s) ||
+        hipMemcpyAsync(md->cells_dev.p, md->cells.data(), 72 * (size_t)nf, hipMemcpyHostToDevice, s) || hipStreamSynchronize(s))
+        return fail(c, UF3_EHIP, "uf3_md_run_npt: upload failed");
+    md->n_blocks = nb;
+    md->npt_ready = true;
+    return UF3_OK;
+}
+
+// the three launches between two force calls (+ the frame sums of a thermo record when `record` >= 0)
+static int npt_launch(uf3_md *md, NptArgs &A, int64_t record) {
+    uf3_ctx *c = md->c;
+    hipStream_t s = c->stream;
+    // the evaluator's persistent copies, while its lists are this run's
+    const bool lists = c->md.live && c->md.valid && c->md.natoms == md->natoms && c->md.n_frames == md->n_frames;
+    A.geo = lists ? c->md.geo.as<FrameGeom>() : nullptr;
+    A.pos_ref = lists ? c->md.pos_ref.as<double>() : nullptr;
+    A.thermo = record >= 0;
+    hipLaunchKernelGGL(k_npt_partial, dim3((unsigned)md->n_blocks), dim3(UF3_NPT_THREADS), 0, s, A);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_npt_frame, dim3((unsigned)md->n_frames), dim3(UF3_NPT_THREADS), 0, s, A);
+    HIPCHK(c, hipGetLastError());
+    const dim3 g((unsigned)((md->natoms + UF3_NPT_THREADS - 1) / UF3_NPT_THREADS)), blk(UF3_NPT_THREADS);
+    if (A.langevin) {
+        if (A.thermo) hipLaunchKernelGGL((k_npt_move<true, true>), g, blk, 0, s, A);
+        else hipLaunchKernelGGL((k_npt_move<true, false>), g, blk, 0, s, A);
+    } else {
+        if (A.thermo) hipLaunchKernelGGL((k_npt_move<false, true>), g, blk, 0, s, A);
+        else hipLaunchKernelGGL((k_npt_move<false, false>), g, blk, 0, s, A);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (A.thermo) {
+        hipLaunchKernelGGL(k_npt_thermo, dim3((unsigned)md->n_frames), dim3(UF3_MD_THREADS), 0, s, A, (const double *)md->energies.as<double>(),
+                           md->ring.as<double>() + (size_t)record * md->n_frames * UF3_NPT_REC);
+        HIPCHK(c, hipGetLastError());
+    }
+    A.rebuilt = 0;
+    return UF3_OK;
+}
+
+// forces, energies and strain derivatives of the current positions and cells; *rebuilt: the evaluator built its lists on the way
+static int npt_forces(uf3_md *md, NptArgs &A) {
+    const long long before = md->c->md.builds;
+    int rc = md_forces(md, true);
+    if (md->c->md.builds != before) A.rebuilt = 1;
+    return rc;
+}
+
+static int npt_run(uf3_md *md, int64_t n_steps, double dt, double T, double gamma, double p0, double tau, double gamma_p, double Tp,
+                   uint64_t seed, double skin, int64_t every, double *thermo) {
+    uf3_ctx *c = md->c;
+    const int64_t n_rec = every ? n_steps / every : 0;
+    if (n_rec) HIPCHK(c, md->ring.ensure(8 * (size_t)n_rec * md->n_frames * UF3_NPT_REC));
+    HIPCHK(c, md->kin.ensure(56 * (size_t)md->natoms));
+    if (!c->flags.p) { HIPCHK(c, c->flags.ensure(64)); HIPCHK(c, hipMemsetAsync(c->flags.p, 0, 64, c->stream)); }
+    NptArgs A;
+    memset(&A, 0, sizeof(A));
+    A.pos = md->pos.as<double>(); A.vel = md->vel.as<double>(); A.frc = md->frc.as<double>(); A.inv_m = md->inv_m.as<double>();
+    A.kin = md->kin.as<double>(); A.frame_of = md->frame_of.as<int>(); A.n = md->natoms;
+    A.blk_frame = md->blk_frame.as<int>(); A.blk_n = md->blk_n.as<int>(); A.frame_blk = md->frame_blk.as<int>();
+    A.blk_lo = md->blk_lo.as<long long>(); A.partial = md->npt_partial.as<double>();
+    A.offsets = md->offsets_dev.as<long long>(); A.virials = md->virials.as<double>();
+    A.st = md->npt_st.as<NptFrame>(); A.coef = md->npt_coef.as<NptCoef>(); A.cells = md->cells_dev.as<double>();
+    A.flags = c->flags.as<int>();
+    A.dt = dt; A.p0 = p0; A.tau2_kTp = tau * tau * UF3_MD_KB * Tp; A.kT = UF3_MD_KB * T;
+    A.c = std::exp(-gamma * dt); A.cp = std::exp(-gamma_p * dt);
+    A.r_cut = md->b->host.rsearch; A.skin = skin;
+    A.seed = (unsigned long long)seed;
+    A.langevin = gamma > 0.0 || gamma_p > 0.0;
+    if (!(md->forces_valid && md->virials_valid)) {
+        md->g_valid = false;
+        int rc = npt_forces(md, A);
+        if (rc) return rc;
+    }
+    const int64_t t0 = md->step;
+    for (int64_t k = 1; k <= n_steps; k++) {
+        // closes step k - 1 of the run (its record, if due) and opens step k
+        A.step = (unsigned long long)(t0 + k - 1); A.close = k > 1; A.open = 1; A.use_g = md->g_valid;
+        const bool rec = k > 1 && every && (k - 1) % every == 0;
+        int rc = npt_launch(md, A, rec ? (k - 1) / every - 1 : -1);
+        md->forces_valid = false; md->virials_valid = false; md->g_valid = false;
+        md->step = t0 + k - 1;
+        if (rc) return rc;
+        rc = npt_forces(md, A);
+        if (rc) return rc;
+    }
+    A.step = (unsigned long long)(t0 + n_steps - 1); A.close = 1; A.open = 0; A.use_g = 0;
+    const bool rec = every && n_steps % every == 0;
+    int rc = npt_launch(md, A, rec ? n_steps / every - 1 : -1);
+    if (rc) return rc;
+    md->step = t0 + n_steps;
+    md->g_valid = true;
+    if (n_rec) HIPCHK(c, hipMemcpyAsync(thermo, md->ring.p, 8 * (size_t)n_rec * md->n_frames * UF3_NPT_REC, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(md->cells.data(), md->cells_dev.p, 72 * (size_t)md->n_frames, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return UF3_OK;
+}
+
+extern "C" int uf3_md_run_npt(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs,
+                              double pressure_eV_A3, double barostat_time_fs, double barostat_friction_per_fs,
+                              double piston_temperature_K, uint64_t seed, double skin, int64_t thermo_every, double *thermo) {
+    if (!md) return fail(nullptr, UF3_EINVAL, "null md");
+    uf3_ctx *c = md->c;
+    if (n_steps < 0) return fail(c, UF3_EINVAL, "uf3_md_run_npt: n_steps must be >= 0");
+    if (!(dt_fs > 0.0) || !std::isfinite(dt_fs)) return fail(c, UF3_EINVAL, "uf3_md_run_npt: dt must be positive and finite");
+    if (!(temperature_K >= 0.0) || !std::isfinite(temperature_K)) return fail(c, UF3_EINVAL, "uf3_md_run_npt: temperature must be finite and >= 0");
+    if (!(friction_per_fs >= 0.0) || !std::isfinite(friction_per_fs)) return fail(c, UF3_EINVAL, "uf3_md_run_npt: friction must be finite and >= 0");
+    if (!std::isfinite(pressure_eV_A3)) return fail(c, UF3_EINVAL, "uf3_md_run_npt: pressure must be finite");
+    if (!(barostat_time_fs > 0.0) || !std::isfinite(barostat_time_fs)) return fail(c, UF3_EINVAL, "uf3_md_run_npt: barostat time must be positive and finite");
+    if (!(barostat_friction_per_fs >= 0.0) || !std::isfinite(barostat_friction_per_fs))
+        return fail(c, UF3_EINVAL, "uf3_md_run_npt: barostat friction must be finite and >= 0");
+    if (!(piston_temperature_K > 0.0) || !std::isfinite(piston_temperature_K))
+        return fail(c, UF3_EINVAL, "uf3_md_run_npt: piston temperature must be positive and finite");
+    if (thermo_every < 0) return fail(c, UF3_EINVAL, "uf3_md_run_npt: thermo_every must be >= 0");
+    if (!(skin >= 0.0) || skin > 4.0) return fail(c, UF3_EINVAL, "uf3_md_run_npt: skin must lie in [0, 4] Angstrom");
+    const int64_t n_rec = thermo_every ? n_steps / thermo_every : 0;
+    if ((n_rec > 0) != (thermo != nullptr))
+        return fail(c, UF3_EINVAL, n_rec ? "uf3_md_run_npt: thermo records are due but the thermo buffer is NULL"
+                                         : "uf3_md_run_npt: a thermo buffer was given but no record is due");
+    int rc = npt_init(md);
+    if (rc) return rc;
+    if (n_steps == 0) return UF3_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    // the run's skin and the "cells live" mode for its own duration; the caller's skin and mode back on every way out.  Lists
+    // from before the run are dropped on the way in (their cells are not compared any more), the run's own on the way out
+    const double caller_skin = c->md.skin;
+    const bool caller_live = c->md.live;
+    const double *caller_dev = c->md.live_dev;
+    double *caller_host = c->md.live_host;
+    rc = uf3_ctx_md_skin(c, skin);
+    if (rc) return rc;
+    c->md.valid = false;
+    c->md.live = true; c->md.live_dev = md->cells_dev.as<double>(); c->md.live_host = md->cells.data();
+    rc = npt_run(md, n_steps, dt_fs, temperature_K, friction_per_fs, pressure_eV_A3, barostat_time_fs, barostat_friction_per_fs,
+                 piston_temperature_K, seed, skin, thermo_every, thermo);
+    const std::string msg = c->err;
+    if (rc) {
+        // (the device's cells are the state: the host's copy follows them, whatever stopped the run)
+        hipMemcpyAsync(md->cells.data(), md->cells_dev.p, 72 * (size_t)md->n_frames, hipMemcpyDeviceToHost, c->stream);
+        hipStreamSynchronize(c->stream);
+        md->forces_valid = false; md->virials_valid = false; md->g_valid = false;
+    }
+    c->md.valid = false;
+    c->md.live = caller_live; c->md.live_dev = caller_dev; c->md.live_host = caller_host;
+    const int rs = uf3_ctx_md_skin(c, caller_skin);
+    return rc ? fail(c, rc, msg) : rs;
+}
+
+extern "C" int uf3_md_get_cells(uf3_md *md, double *cells, double *scales, double *strain_rates) {
+    if (!md) return fail(nullptr, UF3_EINVAL, "null md");
+    uf3_ctx *c = md->c;
+    const int nf = md->n_frames;
+    if (cells) memcpy(cells, md->cells.data(), 72 * (size_t)nf);
+    if (scales || strain_rates) {
+        std::vector<NptFrame> st(nf);
+        if (md->npt_ready) {
+            HIPCHK(c, hipSetDevice(c->device));
+            HIPCHK(c, hipMemcpyAsync(st.data(), md->npt_st.p, sizeof(NptFrame) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        for (int f = 0; f < nf; f++) {
+            if (scales) scales[f] = md->npt_ready ? st[f].s : 1.0;
+            if (strain_rates) strain_rates[f] = md->npt_ready ? st[f].veps : 0.0;
+        }
+    }
+    return UF3_OK;
+}
+
+extern "C" int uf3_ctx_md_live(uf3_ctx *c, int32_t *live) {
+    if (!c || !live) return fail(c, UF3_EINVAL, "uf3_ctx_md_live: null argument");
+    *live = c->md.live ? 1 : 0;
+    return UF3_OK;
 }
 
 extern "C" int uf3_md_info(const uf3_md *md, int64_t *step, int64_t *n_atoms, int32_t *n_frames) {

@@ -12,6 +12,13 @@ are counter-based (Philox4x32-10 on (atom, absolute step, draw), keyed by the se
     md.initialize_velocities(300, exact=True)
     rec = md.run(1000, thermo_every=10, stress=True)      # rec['temperature'][k, frame], rec['pressure'], ...
 
+Constant pressure (isotropic Martyna-Tobias-Klein, every frame its own piston): a ``pressure_eV_A3``
+makes every ``run`` an NPH run (no friction) or an NPT run (Langevin on the atoms and on the piston); the cells change on
+the device and ``dyn.cells`` / ``dyn.volumes`` follow them.
+
+    npt = MolecularDynamics(calc, atoms_list, 1.0, masses=..., temperature_K=300, friction_per_fs=0.01, pressure_eV_A3=0.0,
+                            barostat_time_fs=500.0, barostat_friction_per_fs=0.002)
+
 Each ``run`` starts with one neighbour-list build (it sets the context's skin for its own duration and puts the caller's
 back).  A basis without 3-body terms never takes the evaluator's MD route and rebuilds its lists on every step: correct,
 only slower.
@@ -106,14 +113,28 @@ def thermo_records(raw, n_atoms, volumes, first_step, every, stress=False):
     return out
 
 
+def npt_records(raw, n_atoms, first_step, every):
+    """The dict a constant-pressure ``run`` returns from raw records [n_rec, n_frames, 17] ([PE, KE, W (6), K (6), V, s, H]):
+    ``thermo_records``' entries with the stress and pressure of each step's own volume, and volume, cell_scale, conserved."""
+    raw = np.asarray(raw, dtype=float)
+    out = thermo_records(raw[..., :14], n_atoms, np.ones(raw.shape[1]), first_step, every, stress=True)
+    vol = raw[..., 14]
+    out["stress"] = out["stress"] / vol[..., None]
+    out["pressure"] = out["pressure"] / vol
+    out["volume"] = vol.copy()
+    out["cell_scale"] = raw[..., 15].copy()
+    out["conserved"] = raw[..., 16].copy()
+    return out
+
+
 def _check_real(name, value, lo=0.0, strict=False, hi=None):
     try:
         x = float(value)
     except (TypeError, ValueError):
         raise ValueError(f"MolecularDynamics: {name} must be a number") from None
-    if not np.isfinite(x) or (x <= lo if strict else x < lo) or (hi is not None and x > hi):
-        bound = f"> {lo}" if strict else f">= {lo}"
-        raise ValueError(f"MolecularDynamics: {name} must be finite and {bound}" + (f" and <= {hi}" if hi is not None else "")
+    if not np.isfinite(x) or (lo is not None and (x <= lo if strict else x < lo)) or (hi is not None and x > hi):
+        bound = "" if lo is None else (f" and > {lo}" if strict else f" and >= {lo}")
+        raise ValueError(f"MolecularDynamics: {name} must be finite{bound}" + (f" and <= {hi}" if hi is not None else "")
                          + f", got {value!r}")
     return x
 
@@ -127,7 +148,8 @@ def _check_int(name, value, lo=0, hi=None):
 
 class MolecularDynamics:
     def __init__(self, calculator, atoms_or_list, timestep_fs, masses=None, temperature_K=0.0, friction_per_fs=0.0, seed=0,
-                 skin=0.5, device=None):
+                 skin=0.5, device=None, pressure_eV_A3=None, barostat_time_fs=None, barostat_friction_per_fs=0.0,
+                 piston_temperature_K=None):
         self.handle = None
         # every argument is checked before the device is touched
         self.timestep_fs = _check_real("timestep_fs", timestep_fs, strict=True)
@@ -135,9 +157,19 @@ class MolecularDynamics:
         self.friction_per_fs = _check_real("friction_per_fs", friction_per_fs)
         self.seed = _check_int("seed", seed, 0, (1 << 64) - 1)
         self.skin = _check_real("skin", skin, hi=4.0)
+        self.pressure_eV_A3 = self.barostat_time_fs = self.piston_temperature_K = None
+        self.barostat_friction_per_fs = 0.0
+        self._check_barostat(pressure_eV_A3, barostat_time_fs, barostat_friction_per_fs, piston_temperature_K)
         self._list = isinstance(atoms_or_list, (list, tuple))
         self.frames = _frames_of(atoms_or_list)
         self.masses = resolve_masses(self.frames, masses)
+        if self.pressure_eV_A3 is not None:
+            for k, a in enumerate(self.frames):
+                if not np.all(np.asarray(a.get_pbc() if hasattr(a, "get_pbc") else a.pbc, dtype=bool)):
+                    raise ValueError(f"MolecularDynamics: frame {k} is not periodic along all three axes: it cannot be run at "
+                                     "a pressure (and barostatted and positions-only frames do not mix in one object)")
+                if not abs(np.linalg.det(np.asarray(a.get_cell(), dtype=float).reshape(3, 3))) > 0:
+                    raise ValueError(f"MolecularDynamics: frame {k} has a singular cell")
         vel = None
         if all(hasattr(a, "get_velocities") for a in self.frames):
             vel = np.concatenate([np.asarray(a.get_velocities(), dtype=float).reshape(-1, 3) for a in self.frames]) / ASE_TIME_FS
@@ -148,7 +180,7 @@ class MolecularDynamics:
         if not np.all(np.isfinite(self._batch.pos)):
             raise ValueError("MolecularDynamics: positions must be finite")
         self.n_atoms = np.diff(self._batch.offsets).astype(np.int64)
-        self.volumes = np.abs(np.linalg.det(self._batch.cells))
+        self._cell_scale = np.ones(self._batch.n_frames)
         self.ctx = _lib.get_context(calculator.device if device is None else device)
         self._dbasis = _lib.device_basis(calculator.bspline_config, self.ctx)
         self._pid = os.getpid()
@@ -159,6 +191,28 @@ class MolecularDynamics:
                                                   _lib._p(calculator._c1), _lib._p(calculator._c2), _lib._p(calculator._c3),
                                                   C.byref(h)))
         self.handle = h
+
+    def _check_barostat(self, pressure, tau, gamma_p, t_piston):
+        """The constant-pressure arguments, checked as a set (nothing touches the device); returns what a run passes on."""
+        if pressure is None:
+            if tau is not None or t_piston is not None or _check_real("barostat_friction_per_fs", gamma_p) != 0.0:
+                raise ValueError("MolecularDynamics: barostat_time_fs, barostat_friction_per_fs and piston_temperature_K need a "
+                                 "pressure_eV_A3")
+            return None
+        p = _check_real("pressure_eV_A3", pressure, lo=None)
+        if tau is None:
+            raise ValueError("MolecularDynamics: pressure_eV_A3 needs a barostat_time_fs")
+        tau = _check_real("barostat_time_fs", tau, strict=True)
+        gamma_p = _check_real("barostat_friction_per_fs", gamma_p)
+        t_bath = _check_real("temperature_K", self.temperature_K)
+        if t_piston is None:
+            if not t_bath > 0:
+                raise ValueError("MolecularDynamics: with temperature_K = 0 the piston mass needs a piston_temperature_K > 0")
+            t_p = t_bath
+        else:
+            t_p = _check_real("piston_temperature_K", t_piston, strict=True)
+        self.pressure_eV_A3, self.barostat_time_fs, self.barostat_friction_per_fs, self.piston_temperature_K = p, tau, gamma_p, t_piston
+        return p, tau, gamma_p, t_p
 
     # ---- lifecycle --------------------------------------------------------------------------------------------------------
     def _live(self):
@@ -191,6 +245,32 @@ class MolecularDynamics:
         s = C.c_int64()
         self.ctx.check(self.ctx.lib.uf3_md_info(self._live(), C.byref(s), None, None))
         return s.value
+
+    @property
+    def cells(self):
+        """[n_frames, 3, 3] the current cells (those of the frames given, unless the object runs at a pressure)."""
+        return self._batch.cells.copy()
+
+    @property
+    def volumes(self):
+        """[n_frames] the current volumes."""
+        return np.abs(np.linalg.det(self._batch.cells))
+
+    @property
+    def cell_scales(self):
+        """[n_frames] the current cells' scale s relative to the frames given."""
+        return self._cell_scale.copy()
+
+    @property
+    def strain_rates(self):
+        """[n_frames] the pistons' v_eps = d ln s / dt, 1/fs (0 without a pressure)."""
+        out = np.zeros(self._batch.n_frames)
+        self.ctx.check(self.ctx.lib.uf3_md_get_cells(self._live(), None, None, _lib._p(out)))
+        return out
+
+    def _fetch_cells(self):
+        # (in place: the C struct of the batch points at this array)
+        self.ctx.lib.uf3_md_get_cells(self._live(), _lib._p(self._batch.cells), _lib._p(self._cell_scale), None)
 
     def _get(self, which):
         n = self._batch.n_atoms
@@ -231,7 +311,7 @@ class MolecularDynamics:
         """The frames at the current (unwrapped) positions: a list when a list was given, else one object."""
         from uf3_amd.data.atoms import Atoms
         pos, off = self.get_positions(), self._batch.offsets
-        out = [Atoms(numbers=a.get_atomic_numbers(), positions=pos[off[k]:off[k + 1]], cell=a.get_cell(), pbc=a.get_pbc())
+        out = [Atoms(numbers=a.get_atomic_numbers(), positions=pos[off[k]:off[k + 1]], cell=self._batch.cells[k].copy(), pbc=a.get_pbc())
                for k, a in enumerate(self.frames)]
         return out if self._list else out[0]
 
@@ -262,8 +342,9 @@ class MolecularDynamics:
         self.ctx.check(self.ctx.lib.uf3_md_init_velocities(self._live(), t, s, int(bool(exact))))
 
     def run(self, n_steps, thermo_every=0, stress=False):
-        """``n_steps`` steps (Langevin when ``friction_per_fs`` > 0, else NVE).  Returns the thermo records of every
-        ``thermo_every``-th step (see ``thermo_records``; empty arrays when ``thermo_every`` is 0)."""
+        """``n_steps`` steps (Langevin when ``friction_per_fs`` > 0, else NVE; at a pressure NPT / NPH).  Returns the thermo
+        records of every ``thermo_every``-th step (see ``thermo_records``; empty arrays when ``thermo_every`` is 0).  At a
+        pressure the records always carry stress and pressure (of that step's volume), volume, cell_scale and conserved."""
         n_steps = _check_int("n_steps", n_steps)
         every = _check_int("thermo_every", thermo_every)
         dt = _check_real("timestep_fs", self.timestep_fs, strict=True)
@@ -271,9 +352,19 @@ class MolecularDynamics:
         gamma = _check_real("friction_per_fs", self.friction_per_fs)
         skin = _check_real("skin", self.skin, hi=4.0)
         seed = _check_int("seed", self.seed, 0, (1 << 64) - 1)
+        baro = self._check_barostat(getattr(self, "pressure_eV_A3", None), getattr(self, "barostat_time_fs", None),
+                                    getattr(self, "barostat_friction_per_fs", 0.0), getattr(self, "piston_temperature_K", None))
         handle = self._live()
         first = self.step
         n_rec = n_steps // every if every else 0
+        if baro is not None:
+            raw = np.zeros((n_rec, self._batch.n_frames, 17))
+            try:
+                self.ctx.check(self.ctx.lib.uf3_md_run_npt(handle, n_steps, dt, temp, gamma, baro[0], baro[1], baro[2], baro[3], seed,
+                                                           skin, every, _lib._p(raw) if n_rec else None))
+            finally:
+                self._fetch_cells()
+            return npt_records(raw, self.n_atoms, first, max(every, 1))
         width = 14 if stress else 2
         raw = np.zeros((n_rec, self._batch.n_frames, width))
         self.ctx.check(self.ctx.lib.uf3_md_run(handle, n_steps, dt, temp, gamma, seed, skin, every, int(bool(stress)),
