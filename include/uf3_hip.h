@@ -106,7 +106,7 @@ int uf3_ctx_use_own_stream(uf3_ctx *ctx);
 int uf3_ctx_synchronize(uf3_ctx *ctx);
 const char *uf3_last_error(const uf3_ctx *ctx);
 /* Which sources this binary was compiled from: the first 16 hex digits of the sha256 over uf3_hip.hip, uf3_kernels.h,
- * uf3_feat3.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
+ * uf3_feat3.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h, uf3_npt.h, uf3_neb.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
  * outside it).  __graft_entry__.build() rebuilds when it differs from the tree's, smoke() prints it. */
 const char *uf3_build_id(void);
 /* timing of the dominant kernel: (re)start / read accumulated HIP-event time in ms and launches */
@@ -483,6 +483,44 @@ int uf3_relax_run(uf3_relax *r, int64_t max_steps, double fmax, double dt, doubl
                   int64_t check_every, int64_t record_every, double *records);
 int uf3_relax_get_state(uf3_relax *r, double *pos, double *cells /*[n_frames][9]*/, double *forces, double *energies,
                         int32_t *status, int64_t *steps, double *fmax /*[n_frames]*/);
+
+/*
+ * Batched nudged elastic bands on the device (uf3_amd.forcefield.neb.NudgedElasticBand; kernels in uf3_neb.h).  A band is M >= 3
+ * consecutive frames (images) of equal atom count, species, cell and pbc; images 0 and M - 1 are end points: evaluated for their
+ * energies, never moved.  Interior image i: t+ = R_{i+1} - R_i, t- = R_i - R_{i-1} as stored (positions are kept UNWRAPPED, no
+ * minimum image), the improved tangent of Henkelman & Jonsson (2000) from the neighbours' energies, g = F - (F.tau^) tau^ +
+ * k (|t+| - |t-|) tau^; with climb the interior image of highest energy at that evaluation (ties: the lowest index) has
+ * g = F - 2 (F.tau^) tau^ instead.  Rows of fixed atoms are 0 in t+, t- and g.  One FIRE (uf3_relax_run's constants and rules,
+ * maxstep over the whole vector) per band over all its interior images; criterion: the largest per-atom |g|.
+ *   uf3_neb_create     copies frames, positions [N][3], species, an optional fixed mask [N] (0 / 1; NULL: none), the model, the
+ *                      bands (band b: frames band_first_frame[b] .. band_first_frame[b + 1] - 1; [0] = 0, [n_bands] = n_frames)
+ *                      and one spring constant per band (eV / A^2).  UF3_EINVAL: a band of fewer than 3 images; images of a band
+ *                      that differ in atom count, species, cell, pbc or fixed mask; neighbouring images with identical
+ *                      positions; a spring that is not positive and finite.
+ *   uf3_neb_run        evaluations 0 .. max_steps; after each, a band still running is tested -- converged (status 1) when its
+ *                      criterion < fmax; frozen (status 2) on a non-finite energy or force anywhere in the band, |tau| = 0 or
+ *                      a non-finite sum -- and, but after the last, moved by one FIRE step.  State carries over between runs;
+ *                      a converged band is tested again by the next run (its fmax and climb may differ) and moves only if it
+ *                      fails that test; a frozen band stays frozen.
+ *                      The context's MD skin is `skin` during the run, the caller's again on return (also on errors).  The
+ *                      host looks at the device every check_every steps.  record_every > 0: records
+ *                      [max_steps / record_every + 1][n_frames + 2 n_bands] of evaluations 0, record_every, ...: the energy of
+ *                      every frame, then per band (criterion, climbing image as a double, -1: none); rows after a stop repeat
+ *                      the final values (NULL when record_every is 0).
+ *   uf3_neb_get_state  host arrays out, NULL skips: positions, true forces and NEB forces g [N][3] (0 on end points, fixed
+ *                      atoms and images whose tangent vanishes; tangents as in the last run) and energies [n_frames] of the current positions (evaluated first if
+ *                      they moved since); per band status, steps (moves made), the last criterion (NaN before the first run)
+ *                      and the image that climbed at the last evaluation (index within the band, or -1).
+ */
+typedef struct uf3_neb uf3_neb;
+int uf3_neb_create(uf3_basis *basis, const uf3_frames *frames, const double *pos, const int32_t *z, const uint8_t *fixed,
+                   const double *c1, const double *c2, const double *c3, int32_t n_bands,
+                   const int32_t *band_first_frame /*[n_bands + 1]*/, const double *spring /*[n_bands]*/, uf3_neb **out);
+void uf3_neb_destroy(uf3_neb *neb);
+int uf3_neb_run(uf3_neb *neb, int64_t max_steps, double fmax, double dt, double dt_max, double maxstep, double skin, int climb,
+                int64_t check_every, int64_t record_every, double *records);
+int uf3_neb_get_state(uf3_neb *neb, double *pos, double *forces, double *neb_forces, double *energies, int32_t *status,
+                      int64_t *steps, double *criterion, int32_t *climbing /*[n_bands]*/);
 
 /*
  * Analytic second derivatives of the energy uf3_eval computes, for ONE frame (uf3_hessian.h; the Gamma-point force constants

@@ -22,6 +22,7 @@
 #include "uf3_npt.h"
 #include "uf3_hessian.h"
 #include "uf3_relax.h"
+#include "uf3_neb.h"
 #include "uf3_phonon.h"
 #include <chrono>
 #include <dlfcn.h>
@@ -4335,6 +4336,312 @@ extern "C" int uf3_relax_get_state(uf3_relax *r, double *pos, double *cells, dou
         if (status) status[f] = r->st_host[f].status;
         if (steps) steps[f] = r->st_host[f].steps;
         if (fmax) fmax[f] = r->st_host[f].fmax_last;
+    }
+    return UF3_OK;
+}
+
+// ------------------------------------------------------------------------------ nudged elastic bands (uf3_neb_*, uf3_neb.h)
+// A library-owned set of bands: positions (unwrapped), velocities, true forces, NEB forces, the per-band optimiser state in HBM.
+// Every step is one evaluator call over all frames (eval_impl, unchanged; the end points are evaluated with the rest because
+// their energies are needed) and four launches; the host waits for the device only every check_every steps.
+struct uf3_neb {
+    uf3_basis *b = nullptr;
+    uf3_ctx *c = nullptr;
+    int32_t n_frames = 0, n_bands = 0;
+    int64_t natoms = 0;
+    int n_blocks = 0;
+    bool has_fixed = false;
+    std::vector<int64_t> offsets;
+    std::vector<double> cells;
+    std::vector<uint8_t> pbc;
+    uf3_frames fr{};
+    std::vector<double> c1, c2, c3;
+    std::vector<NebBand> st_host;
+    std::vector<double> e_last_host;
+    Buf pos, vel, frc, g, z, fixed, energies, e_last, offsets_dev, blk_frame, blk_lo, blk_n, frame_blk, frame_of, frame_band, st, coef,
+        img, partial, cmax, ring;
+    bool forces_valid = false;                  // frc / energies describe pos
+    bool g_valid = false;                       // g describes pos (and the climb flag of the last run)
+    int last_climb = 0;
+};
+
+extern "C" void uf3_neb_destroy(uf3_neb *r) {
+    if (!r) return;
+    hipSetDevice(r->c->device);
+    hipStreamSynchronize(r->c->stream);
+    for (Buf *p : {&r->pos, &r->vel, &r->frc, &r->g, &r->z, &r->fixed, &r->energies, &r->e_last, &r->offsets_dev, &r->blk_frame,
+                   &r->blk_lo, &r->blk_n, &r->frame_blk, &r->frame_of, &r->frame_band, &r->st, &r->coef, &r->img, &r->partial,
+                   &r->cmax, &r->ring})
+        p->release();
+    delete r;
+}
+
+extern "C" int uf3_neb_create(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const uint8_t *fixed,
+                              const double *c1, const double *c2, const double *c3, int32_t n_bands, const int32_t *band_first_frame,
+                              const double *spring, uf3_neb **out) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "uf3_neb_create: basis is NULL");
+    uf3_ctx *c = b->ctx;
+    if (!out) return fail(c, UF3_EINVAL, "uf3_neb_create: out is NULL");
+    if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, "uf3_neb_create: bad uf3_frames");
+    if (!pos) return fail(c, UF3_EINVAL, "uf3_neb_create: pos is NULL");
+    if (!z) return fail(c, UF3_EINVAL, "uf3_neb_create: z is NULL");
+    if (!c1 || (b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, "uf3_neb_create: missing coefficients (c1 / c2 / c3)");
+    if (n_bands < 1 || !band_first_frame || !spring) return fail(c, UF3_EINVAL, "uf3_neb_create: needs a band, band_first_frame and spring");
+    const int nf = fr->n_frames;
+    if (fr->atom_offsets[0] != 0) return fail(c, UF3_EINVAL, "uf3_neb_create: atom_offsets[0] must be 0");
+    for (int f = 0; f < nf; f++)
+        if (fr->atom_offsets[f + 1] <= fr->atom_offsets[f]) return fail(c, UF3_EINVAL, "uf3_neb_create: every frame needs an atom");
+    const int64_t n = fr->atom_offsets[nf];
+    if (n >= (1LL << 28)) return fail(c, UF3_EINVAL, "uf3_neb_create: batch must hold 1 .. 2^28 atoms");
+    if (!md_finite(pos, 3 * (size_t)n)) return fail(c, UF3_EINVAL, "uf3_neb_create: pos must be finite");
+    if (!md_finite(fr->cells, 9 * (size_t)nf)) return fail(c, UF3_EINVAL, "uf3_neb_create: cells must be finite");
+    if (fixed)
+        for (int64_t i = 0; i < n; i++)
+            if (fixed[i] > 1) return fail(c, UF3_EINVAL, "uf3_neb_create: fixed must hold 0 or 1 per atom");
+    if (band_first_frame[0] != 0 || band_first_frame[n_bands] != nf)
+        return fail(c, UF3_EINVAL, "uf3_neb_create: band_first_frame must run from 0 to n_frames");
+    std::vector<NebBand> st(n_bands);
+    std::vector<int> frame_band(nf);
+    for (int bd = 0; bd < n_bands; bd++) {
+        const int f0 = band_first_frame[bd], M = band_first_frame[bd + 1] - f0;
+        const std::string who = "uf3_neb_create: band " + std::to_string(bd);
+        if (M < 3) return fail(c, UF3_EINVAL, who + " has " + std::to_string(M) + " images; a band needs at least 3");
+        if (!(spring[bd] > 0.0) || !std::isfinite(spring[bd])) return fail(c, UF3_EINVAL, who + ": spring must be positive and finite");
+        const int64_t lo0 = fr->atom_offsets[f0], na = fr->atom_offsets[f0 + 1] - lo0;
+        for (int j = 1; j < M; j++) {
+            const int f = f0 + j;
+            const int64_t lo = fr->atom_offsets[f];
+            const std::string img = who + ", image " + std::to_string(j);
+            if (fr->atom_offsets[f + 1] - lo != na) return fail(c, UF3_EINVAL, img + ": atom count differs from image 0");
+            if (memcmp(z + lo, z + lo0, 4 * (size_t)na)) return fail(c, UF3_EINVAL, img + ": species differ from image 0");
+            if (memcmp(fr->cells + 9 * (size_t)f, fr->cells + 9 * (size_t)f0, 72)) return fail(c, UF3_EINVAL, img + ": cell differs from image 0");
+            for (int k = 0; k < 3; k++)
+                if ((fr->pbc[3 * f + k] != 0) != (fr->pbc[3 * f0 + k] != 0)) return fail(c, UF3_EINVAL, img + ": pbc differs from image 0");
+            if (fixed && memcmp(fixed + lo, fixed + lo0, (size_t)na)) return fail(c, UF3_EINVAL, img + ": fixed mask differs from image 0");
+            bool same = true;
+            for (int64_t q = 0; q < 3 * na && same; q++) same = pos[3 * lo + q] == pos[3 * (lo - na) + q];
+            if (same) return fail(c, UF3_EINVAL, img + ": positions identical to image " + std::to_string(j - 1));
+        }
+        NebBand &S = st[bd];
+        memset(&S, 0, sizeof(S));
+        S.dt = 0.0; S.alpha = UF3_FIRE_ASTART; S.spring = spring[bd];
+        S.crit_last = std::numeric_limits<double>::quiet_NaN();
+        S.first = 1; S.status = UF3_RELAX_RUNNING; S.climbing = -1; S.frame0 = f0; S.n_img = M;
+        for (int j = 0; j < M; j++) frame_band[f0 + j] = bd;
+    }
+    // the chunk table: chunks of <= UF3_RELAX_THREADS atoms from each frame's first atom
+    std::vector<int> blk_frame, blk_n, frame_blk(1, 0), frame_of(n);
+    std::vector<long long> blk_lo;
+    for (int f = 0; f < nf; f++) {
+        for (int64_t lo = fr->atom_offsets[f]; lo < fr->atom_offsets[f + 1]; lo += UF3_RELAX_THREADS) {
+            blk_frame.push_back(f);
+            blk_lo.push_back(lo);
+            blk_n.push_back((int)std::min<int64_t>(UF3_RELAX_THREADS, fr->atom_offsets[f + 1] - lo));
+        }
+        frame_blk.push_back((int)blk_frame.size());
+        for (int64_t i = fr->atom_offsets[f]; i < fr->atom_offsets[f + 1]; i++) frame_of[i] = f;
+    }
+    const int nb = (int)blk_frame.size();
+    HIPCHK(c, hipSetDevice(c->device));
+    uf3_neb *r = new uf3_neb();
+    r->b = b; r->c = c; r->n_frames = nf; r->n_bands = n_bands; r->natoms = n; r->n_blocks = nb; r->has_fixed = fixed != nullptr;
+    r->offsets.assign(fr->atom_offsets, fr->atom_offsets + nf + 1);
+    r->cells.assign(fr->cells, fr->cells + 9 * (size_t)nf);
+    r->pbc.assign(fr->pbc, fr->pbc + 3 * (size_t)nf);
+    r->fr.n_frames = nf; r->fr.atom_offsets = r->offsets.data(); r->fr.cells = r->cells.data(); r->fr.pbc = r->pbc.data();
+    r->c1.assign(c1, c1 + b->host.S);
+    r->c2.assign(c2 ? c2 : c1, (c2 ? c2 : c1) + b->c2_len); r->c2.push_back(0.0);
+    r->c3.assign(c3 ? c3 : c1, (c3 ? c3 : c1) + b->c3_len); r->c3.push_back(0.0);
+    r->st_host = st;
+    r->e_last_host.assign(nf, std::numeric_limits<double>::quiet_NaN());
+    auto bail = [&](int rc) { uf3_neb_destroy(r); return rc; };
+    const size_t n3 = 3 * (size_t)n;
+    if (r->pos.ensure(8 * n3) || r->vel.ensure(8 * n3) || r->frc.ensure(8 * n3) || r->g.ensure(8 * n3) || r->z.ensure(4 * (size_t)n) ||
+        (fixed && r->fixed.ensure((size_t)n)) || r->energies.ensure(8 * (size_t)nf) || r->e_last.ensure(8 * (size_t)nf) ||
+        r->offsets_dev.ensure(8 * (size_t)(nf + 1)) || r->blk_frame.ensure(4 * (size_t)nb) || r->blk_lo.ensure(8 * (size_t)nb) ||
+        r->blk_n.ensure(4 * (size_t)nb) || r->frame_blk.ensure(4 * (size_t)(nf + 1)) || r->frame_of.ensure(4 * (size_t)n) ||
+        r->frame_band.ensure(4 * (size_t)nf) || r->st.ensure(sizeof(NebBand) * (size_t)n_bands) ||
+        r->coef.ensure(sizeof(NebCoef) * (size_t)n_bands) || r->img.ensure(sizeof(NebImage) * (size_t)nf) ||
+        r->partial.ensure(8 * UF3_NEB_NSUM * (size_t)nb) || r->cmax.ensure(8 * (size_t)nb))
+        return bail(fail(c, UF3_ENOMEM, "uf3_neb_create: out of device memory"));
+    hipStream_t s = c->stream;
+    if (hipMemcpyAsync(r->pos.p, pos, 8 * n3, hipMemcpyHostToDevice, s) || hipMemsetAsync(r->vel.p, 0, 8 * n3, s) ||
+        hipMemsetAsync(r->g.p, 0, 8 * n3, s) || hipMemcpyAsync(r->z.p, z, 4 * (size_t)n, hipMemcpyHostToDevice, s) ||
+        (fixed && hipMemcpyAsync(r->fixed.p, fixed, (size_t)n, hipMemcpyHostToDevice, s)) ||
+        hipMemcpyAsync(r->e_last.p, r->e_last_host.data(), 8 * (size_t)nf, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(r->offsets_dev.p, r->offsets.data(), 8 * (size_t)(nf + 1), hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(r->blk_frame.p, blk_frame.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(r->blk_lo.p, blk_lo.data(), 8 * (size_t)nb, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(r->blk_n.p, blk_n.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(r->frame_blk.p, frame_blk.data(), 4 * (size_t)(nf + 1), hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(r->frame_of.p, frame_of.data(), 4 * (size_t)n, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(r->frame_band.p, frame_band.data(), 4 * (size_t)nf, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(r->st.p, st.data(), sizeof(NebBand) * (size_t)n_bands, hipMemcpyHostToDevice, s) ||
+        hipMemsetAsync(r->coef.p, 0, sizeof(NebCoef) * (size_t)n_bands, s) ||
+        hipMemsetAsync(r->img.p, 0, sizeof(NebImage) * (size_t)nf, s) ||
+        hipMemsetAsync(r->partial.p, 0, 8 * UF3_NEB_NSUM * (size_t)nb, s) || hipMemsetAsync(r->cmax.p, 0, 8 * (size_t)nb, s) ||
+        hipStreamSynchronize(s))
+        return bail(fail(c, UF3_EHIP, "uf3_neb_create: upload failed"));
+    *out = r;
+    return UF3_OK;
+}
+
+static int neb_evaluate(uf3_neb *r) {
+    int rc = eval_impl(r->b, &r->fr, r->pos.as<double>(), r->z.as<int32_t>(), r->c1.data(), r->c2.data(), r->c3.data(),
+                       r->energies.as<double>(), r->frc.as<double>(), nullptr);
+    r->forces_valid = rc == UF3_OK;
+    r->g_valid = false;
+    return rc;
+}
+
+static int neb_fetch_state(uf3_neb *r) {
+    uf3_ctx *c = r->c;
+    HIPCHK(c, hipMemcpyAsync(r->st_host.data(), r->st.p, sizeof(NebBand) * (size_t)r->n_bands, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return UF3_OK;
+}
+
+static NebChunkArgs neb_chunk_args(uf3_neb *r, int climb, int all) {
+    NebChunkArgs P;
+    P.pos = r->pos.as<double>(); P.frc = r->frc.as<double>(); P.vel = r->vel.as<double>();
+    P.fixed = r->has_fixed ? r->fixed.as<uint8_t>() : nullptr;
+    P.blk_frame = r->blk_frame.as<int>(); P.blk_lo = r->blk_lo.as<long long>(); P.blk_n = r->blk_n.as<int>();
+    P.frame_blk = r->frame_blk.as<int>(); P.frame_band = r->frame_band.as<int>(); P.offsets = r->offsets_dev.as<long long>();
+    P.energies = r->energies.as<double>(); P.bands = r->st.as<NebBand>(); P.partial = r->partial.as<double>();
+    P.g = r->g.as<double>(); P.cmax = r->cmax.as<double>(); P.img = r->img.as<NebImage>();
+    P.climb = climb; P.all = all;
+    return P;
+}
+
+// evaluations k = 0 .. max_steps; each but the last may move the bands still running
+static int neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt, double dt_max, double maxstep, int climb, int64_t every,
+                   int64_t rec_every, double *records) {
+    uf3_ctx *c = r->c;
+    hipStream_t s = c->stream;
+    const int nf = r->n_frames, nbd = r->n_bands;
+    const size_t row = (size_t)nf + 2 * (size_t)nbd;
+    const int64_t n_rec = rec_every ? max_steps / rec_every + 1 : 0;
+    if (n_rec) HIPCHK(c, r->ring.ensure(8 * (size_t)n_rec * row));
+    const NebChunkArgs P = neb_chunk_args(r, climb, 0);
+    NebBandArgs F;
+    F.cmax = r->cmax.as<double>(); F.frame_blk = r->frame_blk.as<int>(); F.energies = r->energies.as<double>();
+    F.img = r->img.as<NebImage>(); F.bands = r->st.as<NebBand>(); F.coef = r->coef.as<NebCoef>(); F.e_last = r->e_last.as<double>();
+    F.fmax = fmax; F.dt0 = dt; F.dt_max = dt_max; F.maxstep = maxstep; F.n_frames = nf; F.climb = climb;
+    NebMoveArgs M;
+    M.pos = r->pos.as<double>(); M.vel = r->vel.as<double>(); M.g = r->g.as<double>(); M.fixed = P.fixed;
+    M.frame_of = r->frame_of.as<int>(); M.frame_band = r->frame_band.as<int>(); M.bands = r->st.as<NebBand>();
+    M.coef = r->coef.as<NebCoef>(); M.n = r->natoms;
+    r->last_climb = climb;
+    hipLaunchKernelGGL(k_neb_rearm, dim3((unsigned)((nbd + UF3_RELAX_THREADS - 1) / UF3_RELAX_THREADS)), dim3(UF3_RELAX_THREADS), 0, s,
+                       r->st.as<NebBand>(), nbd);
+    HIPCHK(c, hipGetLastError());
+    int64_t last = max_steps;                   // the last evaluation made
+    for (int64_t k = 0; k <= max_steps; k++) {
+        if (!(k == 0 && r->forces_valid)) {     // (a run continues from the previous run's last evaluation)
+            int rc = neb_evaluate(r);
+            if (rc) return rc;
+        }
+        hipLaunchKernelGGL(k_neb_partial, dim3((unsigned)r->n_blocks), dim3(UF3_RELAX_THREADS), 0, s, P);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k_neb_force, dim3((unsigned)r->n_blocks), dim3(UF3_RELAX_THREADS), 0, s, P);
+        HIPCHK(c, hipGetLastError());
+        F.rec = (n_rec && k % rec_every == 0) ? r->ring.as<double>() + row * (size_t)(k / rec_every) : nullptr;
+        F.can_move = k < max_steps;
+        hipLaunchKernelGGL(k_neb_band, dim3((unsigned)nbd), dim3(UF3_RELAX_THREADS), 0, s, F);
+        HIPCHK(c, hipGetLastError());
+        r->g_valid = false;                     // (frozen bands' rows are older than this evaluation: get_state forms them all)
+        if (k == max_steps) break;
+        hipLaunchKernelGGL(k_neb_move, dim3((unsigned)((r->natoms + UF3_RELAX_THREADS - 1) / UF3_RELAX_THREADS)),
+                           dim3(UF3_RELAX_THREADS), 0, s, M);
+        HIPCHK(c, hipGetLastError());
+        r->forces_valid = false;
+        if ((k + 1) % every == 0) {             // poll: stop once no band runs (nothing moved in this step then)
+            int rc = neb_fetch_state(r);
+            if (rc) return rc;
+            bool running = false;
+            for (int bd = 0; bd < nbd; bd++) running = running || r->st_host[bd].status == UF3_RELAX_RUNNING;
+            if (!running) { last = k; r->forces_valid = true; break; }
+        }
+    }
+    int rc = neb_fetch_state(r);
+    if (rc) return rc;
+    if (n_rec) {
+        // rows after the last evaluation repeat the final values (no band ran any more)
+        const int64_t written = last / rec_every + 1;
+        HIPCHK(c, hipMemcpyAsync(records, r->ring.p, 8 * (size_t)written * row, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(r->e_last_host.data(), r->e_last.p, 8 * (size_t)nf, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        for (int64_t j = written; j < n_rec; j++) {
+            double *out = records + (size_t)j * row;
+            for (int f = 0; f < nf; f++) out[f] = r->e_last_host[f];
+            for (int bd = 0; bd < nbd; bd++) {
+                out[nf + 2 * bd] = r->st_host[bd].crit_last;
+                out[nf + 2 * bd + 1] = (double)r->st_host[bd].climbing;
+            }
+        }
+    }
+    return UF3_OK;
+}
+
+extern "C" int uf3_neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt, double dt_max, double maxstep, double skin,
+                           int climb, int64_t check_every, int64_t record_every, double *records) {
+    if (!r) return fail(nullptr, UF3_EINVAL, "uf3_neb_run: neb is NULL");
+    uf3_ctx *c = r->c;
+    if (max_steps < 0) return fail(c, UF3_EINVAL, "uf3_neb_run: max_steps must be >= 0");
+    if (!(fmax > 0.0) || !std::isfinite(fmax)) return fail(c, UF3_EINVAL, "uf3_neb_run: fmax must be positive and finite");
+    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, UF3_EINVAL, "uf3_neb_run: dt must be positive and finite");
+    if (!(dt_max > 0.0) || !std::isfinite(dt_max)) return fail(c, UF3_EINVAL, "uf3_neb_run: dt_max must be positive and finite");
+    if (!(maxstep > 0.0) || !std::isfinite(maxstep)) return fail(c, UF3_EINVAL, "uf3_neb_run: maxstep must be positive and finite");
+    if (!(skin >= 0.0) || skin > 4.0) return fail(c, UF3_EINVAL, "uf3_neb_run: skin must lie in [0, 4] Angstrom");
+    if (climb != 0 && climb != 1) return fail(c, UF3_EINVAL, "uf3_neb_run: climb must be 0 or 1");
+    if (check_every < 1) return fail(c, UF3_EINVAL, "uf3_neb_run: check_every must be >= 1");
+    if (record_every < 0) return fail(c, UF3_EINVAL, "uf3_neb_run: record_every must be >= 0");
+    if ((record_every > 0) != (records != nullptr))
+        return fail(c, UF3_EINVAL, record_every ? "uf3_neb_run: records are due but the records buffer is NULL"
+                                                : "uf3_neb_run: a records buffer was given but no record is due");
+    HIPCHK(c, hipSetDevice(c->device));
+    // the run's skin for its own duration, the caller's back on every way out
+    const double caller_skin = c->md.skin;
+    int rc = uf3_ctx_md_skin(c, skin);
+    if (rc) return rc;
+    rc = neb_run(r, max_steps, fmax, dt, dt_max, maxstep, climb, check_every, record_every, records);
+    if (rc) {
+        const std::string msg = c->err;
+        uf3_ctx_md_skin(c, caller_skin);
+        return fail(c, rc, msg);
+    }
+    return uf3_ctx_md_skin(c, caller_skin);
+}
+
+extern "C" int uf3_neb_get_state(uf3_neb *r, double *pos, double *forces, double *neb_forces, double *energies, int32_t *status,
+                                 int64_t *steps, double *criterion, int32_t *climbing) {
+    if (!r) return fail(nullptr, UF3_EINVAL, "uf3_neb_get_state: neb is NULL");
+    uf3_ctx *c = r->c;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((forces || energies || neb_forces) && !r->forces_valid) {
+        int rc = neb_evaluate(r);
+        if (rc) return rc;
+    }
+    if (neb_forces && !r->g_valid) {            // g of every band at these positions, frozen bands included; no state changes
+        const NebChunkArgs P = neb_chunk_args(r, r->last_climb, 1);
+        hipLaunchKernelGGL(k_neb_partial, dim3((unsigned)r->n_blocks), dim3(UF3_RELAX_THREADS), 0, c->stream, P);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k_neb_force, dim3((unsigned)r->n_blocks), dim3(UF3_RELAX_THREADS), 0, c->stream, P);
+        HIPCHK(c, hipGetLastError());
+        r->g_valid = true;
+    }
+    const size_t n3 = 3 * (size_t)r->natoms;
+    if (pos) HIPCHK(c, hipMemcpyAsync(pos, r->pos.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
+    if (forces) HIPCHK(c, hipMemcpyAsync(forces, r->frc.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
+    if (neb_forces) HIPCHK(c, hipMemcpyAsync(neb_forces, r->g.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
+    if (energies) HIPCHK(c, hipMemcpyAsync(energies, r->energies.p, 8 * (size_t)r->n_frames, hipMemcpyDeviceToHost, c->stream));
+    int rc = neb_fetch_state(r);
+    if (rc) return rc;
+    for (int bd = 0; bd < r->n_bands; bd++) {
+        if (status) status[bd] = r->st_host[bd].status;
+        if (steps) steps[bd] = r->st_host[bd].steps;
+        if (criterion) criterion[bd] = r->st_host[bd].crit_last;
+        if (climbing) climbing[bd] = r->st_host[bd].climbing;
     }
     return UF3_OK;
 }

@@ -325,6 +325,29 @@ class UFCalculator(_Base):
                           f"{', ...' if len(bad) > 10 else ''})", RuntimeWarning)
         return out, info
 
+    def neb_bands(self, bands, fmax=0.05, climb=True, max_steps=2000, **kw):
+        """
+        Nudged elastic bands at once on the device (``neb.NudgedElasticBand``: improved tangents, one FIRE per band).  ``bands``:
+        one band (a list of frames, end points included; ``neb.interpolate`` makes one) or a list of bands.  With ``climb`` the
+        bands first run to ``fmax`` without a climbing image, then with one; both phases share ``max_steps``.  ``kw``:
+        ``spring``, ``fixed``, ``skin``, ``device`` (the object's) and ``dt``, ``dt_max``, ``maxstep``, ``check_every``
+        (``run``'s).  Returns (bands, info), info as ``NudgedElasticBand.run`` returns it (``barrier``, ``energies``, ...);
+        warns (RuntimeWarning) for every band that did not converge.
+        """
+        import warnings
+        from .neb import NudgedElasticBand
+        make = {k: kw.pop(k) for k in ("spring", "fixed", "skin", "device") if k in kw}
+        with NudgedElasticBand(self, bands, **make) as band:
+            info = band.run(max_steps, fmax=fmax, climb=False, **kw)
+            if climb:
+                left = max_steps - int(info["steps"].max())
+                info = band.run(max(left, 0), fmax=fmax, climb=True, **kw)
+            out = band.get_images()
+        for k, status in enumerate(info["status"]):
+            if status != "converged":
+                warnings.warn(f"neb_bands: band {k} did not converge ({status} after {info['steps'][k]} steps, criterion "
+                              f"{info['criterion'][k]:.3g} eV/A)", RuntimeWarning)
+        return out, info
 
     def get_hessian(self, atoms, rows=None, strain=False):
         """Exact second derivatives of the energy on the device (``harmonic.hessian``): H [3N, 3N] (or the rows of ``rows``),

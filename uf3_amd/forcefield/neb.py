@@ -1,0 +1,273 @@
+"""
+``NudgedElasticBand``: nudged elastic bands on the device (``uf3_neb_*`` in ``libuf3hip.so``) -- migration barriers from a fitted
+potential.  A band is a list of M >= 3 ``Atoms`` of equal atom count, species, cell and pbc; the first and the last are end
+points and never move.  Positions, forces and every band's optimiser state stay in HBM; each step is one evaluator call over all
+images of all bands (``UFCalculator``'s model, its MD route with a neighbour-list skin) and four small kernels.
+
+The tangent is the improved tangent of Henkelman & Jonsson (2000); an ordinary image feels the true force perpendicular to the
+tangent and the spring force ``k (|R_{i+1} - R_i| - |R_i - R_{i-1}|)`` along it; with ``climb`` the interior image of highest
+energy at each evaluation feels the true force with its tangent component reversed and no spring.  Differences between
+neighbouring images are taken as stored (positions are kept unwrapped, there is no minimum-image step): ``interpolate`` builds
+bands for which that is right.  One FIRE (``Relaxation``'s constants and rules; ``maxstep`` bounds the norm of the band's whole
+step) runs per band over all its interior images, as ASE optimises a band; a band has converged when every atom of every interior
+image has |g_i| < ``fmax``.  A non-finite energy or force anywhere in a band, or a vanishing tangent, freezes that band alone with
+status ``"nonfinite"``.
+
+    images = neb.interpolate(initial, final, 7)
+    with NudgedElasticBand(calc, images) as band:
+        band.run(500, fmax=0.05)
+        out = band.run(1500, fmax=0.05, climb=True)      # out["barrier"], out["energies"], out["climbing_image"] per band
+
+``run`` may be called again: the FIRE state carries over, and ``run(a); run(b)`` follows ``run(a + b)``.  A band that converged
+is tested again by the next run, whose ``fmax`` and ``climb`` may differ, and moves only if it fails that test.
+"""
+import ctypes as C
+import numbers
+import os
+
+import numpy as np
+
+from uf3_amd import _lib
+from uf3_amd.forcefield.relax import STATUS
+
+
+def _check_real(name, value, lo=0.0, strict=False, hi=None):
+    try:
+        x = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"NudgedElasticBand: {name} must be a number") from None
+    if not np.isfinite(x) or (x <= lo if strict else x < lo) or (hi is not None and x > hi):
+        bound = f"> {lo}" if strict else f">= {lo}"
+        raise ValueError(f"NudgedElasticBand: {name} must be finite and {bound}" + (f" and <= {hi}" if hi is not None else "")
+                         + f", got {value!r}")
+    return x
+
+
+def _check_int(name, value, lo=0):
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or value < lo:
+        raise ValueError(f"NudgedElasticBand: {name} must be an integer >= {lo}, got {value!r}")
+    return int(value)
+
+
+def _axes(cell, pbc):
+    """The cell with the rows of its non-periodic axes replaced by unit vectors orthogonal to the rows already there, so that it
+    can be inverted: the fraction along a non-periodic axis is taken along that direction, not along the stored cell row (which
+    may be zero), and is never wrapped."""
+    full = np.array(cell, dtype=float).reshape(3, 3)
+    full[~pbc] = 0.0
+    for k in np.flatnonzero(~pbc):
+        full[k] = np.linalg.svd(full)[2][-1]             # (row k is zero: the last right singular vector spans the gap)
+    return full
+
+
+def interpolate(initial, final, n_images, mic=True):
+    """``n_images`` frames from ``initial`` to ``final``, end points included, by linear interpolation of the positions.  With
+    ``mic`` the displacement ``final - initial`` is wrapped to the minimum image along the periodic axes once, and the last
+    image is ``initial + d``, unwrapped: neighbouring images then differ by d / (n_images - 1) as stored."""
+    from uf3_amd.data.atoms import Atoms
+    n_images = _check_int("n_images", n_images, 2)
+    if len(initial) != len(final):
+        raise ValueError(f"interpolate: the end points hold {len(initial)} and {len(final)} atoms")
+    z = np.asarray(initial.get_atomic_numbers())
+    if not np.array_equal(z, np.asarray(final.get_atomic_numbers())):
+        raise ValueError("interpolate: the end points differ in species")
+    cell = np.array(initial.get_cell(), dtype=float).reshape(3, 3)
+    if not np.array_equal(cell, np.array(final.get_cell(), dtype=float).reshape(3, 3)):
+        raise ValueError("interpolate: the end points differ in cell")
+    pbc = np.asarray(initial.get_pbc(), dtype=bool).reshape(3)
+    if not np.array_equal(pbc, np.asarray(final.get_pbc(), dtype=bool).reshape(3)):
+        raise ValueError("interpolate: the end points differ in pbc")
+    x0 = np.asarray(initial.get_positions(), dtype=float)
+    d = np.asarray(final.get_positions(), dtype=float) - x0
+    if mic and pbc.any():
+        full = _axes(cell, pbc)
+        frac = d @ np.linalg.inv(full)
+        frac[:, pbc] -= np.round(frac[:, pbc])
+        d = frac @ full
+    return [Atoms(numbers=z, positions=x0 + d * (k / (n_images - 1)), cell=cell, pbc=pbc) for k in range(n_images)]
+
+
+def _bands_of(bands):
+    if isinstance(bands, (list, tuple)) and bands and isinstance(bands[0], (list, tuple)):
+        return False, [list(b) for b in bands]
+    if not isinstance(bands, (list, tuple)):
+        raise ValueError("NudgedElasticBand: bands must be a list of Atoms or a list of such lists")
+    return True, [list(bands)]
+
+
+def _check_band(k, band):
+    if len(band) < 3:
+        raise ValueError(f"NudgedElasticBand: band {k} has {len(band)} images; a band needs at least 3")
+    a0 = band[0]
+    if len(a0) < 1:
+        raise ValueError(f"NudgedElasticBand: band {k} has no atoms")
+    z0 = np.asarray(a0.get_atomic_numbers())
+    c0 = np.array(a0.get_cell(), dtype=float).reshape(3, 3)
+    p0 = np.asarray(a0.get_pbc(), dtype=bool).reshape(3)
+    for j, a in enumerate(band[1:], 1):
+        if len(a) != len(a0):
+            raise ValueError(f"NudgedElasticBand: band {k}, image {j}: atom count differs from image 0")
+        if not np.array_equal(np.asarray(a.get_atomic_numbers()), z0):
+            raise ValueError(f"NudgedElasticBand: band {k}, image {j}: species differ from image 0")
+        if not np.array_equal(np.array(a.get_cell(), dtype=float).reshape(3, 3), c0):
+            raise ValueError(f"NudgedElasticBand: band {k}, image {j}: cell differs from image 0")
+        if not np.array_equal(np.asarray(a.get_pbc(), dtype=bool).reshape(3), p0):
+            raise ValueError(f"NudgedElasticBand: band {k}, image {j}: pbc differs from image 0")
+        if np.array_equal(np.asarray(a.get_positions(), dtype=float), np.asarray(band[j - 1].get_positions(), dtype=float)):
+            raise ValueError(f"NudgedElasticBand: band {k}, image {j}: positions identical to image {j - 1}")
+
+
+class NudgedElasticBand:
+    def __init__(self, calc, bands, spring=0.1, fixed=None, skin=0.5, device=None):
+        """``bands``: one band (a list of ``Atoms``) or a list of bands.  ``spring`` (eV / Angstrom^2): a scalar or one value
+        per band.  ``fixed``: boolean mask [sum N] over the concatenated images of all bands (ASE's FixAtoms), the same in
+        every image of a band: those atoms feel no force, never move and do not enter tangents or spring lengths.  ``skin``
+        (Angstrom): the evaluator's neighbour-list skin during runs."""
+        self.handle = None
+        # every argument is checked before the device is touched
+        self.skin = _check_real("skin", skin, hi=4.0)
+        self._single, self.bands = _bands_of(bands)
+        for k, band in enumerate(self.bands):
+            _check_band(k, band)
+        nb = len(self.bands)
+        sp = np.asarray(spring, dtype=float)
+        if sp.ndim == 0:
+            sp = np.full(nb, float(sp))
+        if sp.shape != (nb,):
+            raise ValueError(f"NudgedElasticBand: spring must be a scalar or hold one value per band ({nb}), got shape {sp.shape}")
+        if not np.all(np.isfinite(sp)) or np.any(sp <= 0.0):
+            raise ValueError("NudgedElasticBand: spring must be positive and finite")
+        self.spring = np.ascontiguousarray(sp)
+        self.frames = [a for band in self.bands for a in band]
+        self.band_first = np.ascontiguousarray(np.cumsum([0] + [len(b) for b in self.bands]), dtype=np.int32)
+        self.calculator = calc
+        self._batch = _lib.FrameBatch(self.frames)
+        if not np.all(np.isfinite(self._batch.pos)):
+            raise ValueError("NudgedElasticBand: positions must be finite")
+        if not np.all(np.isfinite(self._batch.cells)):
+            raise ValueError("NudgedElasticBand: cells must be finite")
+        self.fixed = None
+        if fixed is not None:
+            m = np.asarray(fixed)
+            if m.dtype != bool:
+                raise ValueError("NudgedElasticBand: fixed must be a boolean mask over the concatenated atoms")
+            m = m.reshape(-1)
+            if m.size != self._batch.n_atoms:
+                raise ValueError(f"NudgedElasticBand: fixed holds {m.size} entries for {self._batch.n_atoms} atoms")
+            off = self._batch.offsets
+            for k in range(nb):
+                f0, f1 = self.band_first[k], self.band_first[k + 1]
+                for f in range(f0 + 1, f1):
+                    if not np.array_equal(m[off[f]:off[f + 1]], m[off[f0]:off[f0 + 1]]):
+                        raise ValueError(f"NudgedElasticBand: band {k}, image {f - f0}: fixed mask differs from image 0")
+            self.fixed = np.ascontiguousarray(m.astype(np.uint8))
+        self.ctx = _lib.get_context(calc.device if device is None else device)
+        self._dbasis = _lib.device_basis(calc.bspline_config, self.ctx)
+        self._pid = os.getpid()
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.uf3_neb_create(self._dbasis.handle, C.byref(self._batch.struct), _lib._p(self._batch.pos),
+                                                   _lib._p(self._batch.z), _lib._p(self.fixed), _lib._p(calc._c1),
+                                                   _lib._p(calc._c2), _lib._p(calc._c3), nb, _lib._p(self.band_first),
+                                                   _lib._p(self.spring), C.byref(h)))
+        self.handle = h
+
+    # ---- lifecycle --------------------------------------------------------------------------------------------------------
+    def _live(self):
+        if not self.handle:
+            raise RuntimeError("NudgedElasticBand: the object is closed")
+        return self.handle
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if os.getpid() == self._pid and self.ctx.handle:
+                self.ctx.lib.uf3_neb_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- state ------------------------------------------------------------------------------------------------------------
+    def _state(self, *which):
+        nf, n, nb = self._batch.n_frames, self._batch.n_atoms, len(self.bands)
+        shapes = dict(pos=((n, 3), float), forces=((n, 3), float), neb_forces=((n, 3), float), energies=((nf,), float),
+                      status=((nb,), np.int32), steps=((nb,), np.int64), criterion=((nb,), float), climbing=((nb,), np.int32))
+        out = {k: np.empty(*shapes[k]) for k in which}
+        args = [_lib._p(out[k]) if k in out else None for k in shapes]
+        self.ctx.check(self.ctx.lib.uf3_neb_get_state(self._live(), *args))
+        return out
+
+    def _per_band(self, x):
+        return [x[self.band_first[k]:self.band_first[k + 1]].copy() for k in range(len(self.bands))]
+
+    def get_positions(self):
+        """[N, 3] Angstrom, the images of all bands concatenated, unwrapped."""
+        return self._state("pos")["pos"]
+
+    def get_forces(self):
+        """[N, 3] eV / Angstrom: the true forces at the current positions."""
+        return self._state("forces")["forces"]
+
+    def get_neb_forces(self):
+        """[N, 3] eV / Angstrom: the NEB forces g at the current positions (0 on end points and fixed atoms; climbing as in
+        the last run)."""
+        return self._state("neb_forces")["neb_forces"]
+
+    def get_potential_energies(self):
+        """One array [M] per band, eV, at the current positions."""
+        return self._per_band(self._state("energies")["energies"])
+
+    def get_images(self):
+        """The bands at the current positions: a list of lists of ``Atoms`` (one list when one band was given)."""
+        from uf3_amd.data.atoms import Atoms
+        x = self._state("pos")["pos"]
+        off = self._batch.offsets
+        flat = [Atoms(numbers=a.get_atomic_numbers(), positions=x[off[k]:off[k + 1]], cell=a.get_cell(), pbc=a.get_pbc())
+                for k, a in enumerate(self.frames)]
+        out = [flat[self.band_first[k]:self.band_first[k + 1]] for k in range(len(self.bands))]
+        return out[0] if self._single else out
+
+    # ---- optimisation -----------------------------------------------------------------------------------------------------
+    def run(self, max_steps, fmax=0.05, climb=False, dt=0.1, dt_max=1.0, maxstep=0.2, check_every=10, record_every=0):
+        """Up to ``max_steps`` FIRE steps of every band still running (evaluations 0 .. max_steps).  Returns per band:
+        ``status`` ("running" | "converged" | "nonfinite"), ``converged`` (bool), ``steps`` (moves made in all runs so far),
+        ``criterion`` (the largest per-atom |g|), ``energies`` (a list of arrays [M]), ``barrier`` (max E - E_0),
+        ``reverse_barrier`` (max E - E_{M-1}) and ``climbing_image`` (index within the band, -1: none) at the last evaluation;
+        with ``record_every`` > 0 also ``records``: ``iteration`` [n_rec], ``energies`` [n_rec, n_frames], ``criterion`` and
+        ``climbing_image`` [n_rec, n_bands] of evaluations 0, record_every, ... (after every band stopped, the final values
+        repeat)."""
+        max_steps = _check_int("max_steps", max_steps)
+        fmax = _check_real("fmax", fmax, strict=True)
+        if not isinstance(climb, (bool, np.bool_)):
+            raise ValueError(f"NudgedElasticBand: climb must be True or False, got {climb!r}")
+        dt = _check_real("dt", dt, strict=True)
+        dt_max = _check_real("dt_max", dt_max, strict=True)
+        maxstep = _check_real("maxstep", maxstep, strict=True)
+        check_every = _check_int("check_every", check_every, 1)
+        record_every = _check_int("record_every", record_every)
+        skin = _check_real("skin", self.skin, hi=4.0)
+        handle = self._live()
+        nf, nb = self._batch.n_frames, len(self.bands)
+        n_rec = max_steps // record_every + 1 if record_every else 0
+        raw = np.zeros((n_rec, nf + 2 * nb))
+        self.ctx.check(self.ctx.lib.uf3_neb_run(handle, max_steps, fmax, dt, dt_max, maxstep, skin, int(climb), check_every,
+                                                record_every, _lib._p(raw) if n_rec else None))
+        s = self._state("status", "steps", "criterion", "climbing", "energies")   # (the last evaluation's: nothing has moved since)
+        energies = self._per_band(s["energies"])
+        out = dict(status=[STATUS[int(x)] for x in s["status"]], converged=s["status"] == 1, steps=s["steps"],
+                   criterion=s["criterion"], energies=energies, barrier=np.array([e.max() - e[0] for e in energies]),
+                   reverse_barrier=np.array([e.max() - e[-1] for e in energies]), climbing_image=s["climbing"])
+        if n_rec:
+            tail = raw[:, nf:].reshape(n_rec, nb, 2)
+            out["records"] = dict(iteration=record_every * np.arange(n_rec, dtype=np.int64), energies=raw[:, :nf].copy(),
+                                  criterion=tail[..., 0].copy(), climbing_image=tail[..., 1].astype(np.int32))
+        return out
