@@ -106,7 +106,7 @@ int uf3_ctx_use_own_stream(uf3_ctx *ctx);
 int uf3_ctx_synchronize(uf3_ctx *ctx);
 const char *uf3_last_error(const uf3_ctx *ctx);
 /* Which sources this binary was compiled from: the first 16 hex digits of the sha256 over uf3_hip.hip, uf3_kernels.h,
- * uf3_feat3.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h, uf3_npt.h, uf3_neb.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
+ * uf3_feat3.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h, uf3_npt.h, uf3_neb.h, uf3_mc.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
  * outside it).  __graft_entry__.build() rebuilds when it differs from the tree's, smoke() prints it. */
 const char *uf3_build_id(void);
 /* timing of the dominant kernel: (re)start / read accumulated HIP-event time in ms and launches */
@@ -521,6 +521,54 @@ int uf3_neb_run(uf3_neb *neb, int64_t max_steps, double fmax, double dt, double 
                 int64_t check_every, int64_t record_every, double *records);
 int uf3_neb_get_state(uf3_neb *neb, double *pos, double *forces, double *neb_forces, double *energies, int32_t *status,
                       int64_t *steps, double *criterion, int32_t *climbing /*[n_bands]*/);
+
+/*
+ * Batched species-swap Monte Carlo on fixed positions (uf3_amd.forcefield.mc.MonteCarlo; kernels in uf3_mc.h): every frame its own
+ * Markov chain over WHICH species sits on which site -- canonical swaps or semi-grand-canonical transmutations.  The object owns
+ * positions, species (atomic numbers), a neighbour table and the per-frame counters in HBM.  A trial costs the energy terms that
+ * contain the one or two atoms it touches, not an evaluation of the frame.
+ *   uf3_mc_create         copies frames, positions [N][3], species, an optional per-atom mask swappable [N] (0 / 1; NULL: every
+ *                         atom) and the model (c1 / c2 / c3 as for uf3_eval), and builds the neighbour table: per atom the
+ *                         entries (real atom, image displacement) within the largest pair r_max and within the 3-body range, from
+ *                         the positions alone -- no species in it.  The table is built on the host, O(N^2 images) per frame, once
+ *                         per geometry.  UF3_EINVAL: a frame of more than 49 152 atoms (a frame's species sit in LDS, one byte
+ *                         each), an atom with more than 512 neighbours in the 3-body range (the affected centres of a trial sit
+ *                         in LDS; there is no global-memory fallback), non-finite positions or cells, a mask entry above 1, null
+ *                         pointers; UF3_ESPECIES: an element outside the basis.
+ *   uf3_mc_run            n_trials trials of every frame still running, in launches of at most 1024 trials (no launch is
+ *                         open-ended), one workgroup per frame.  Trial t (absolute: the counter lives in the object and goes on
+ *                         across runs) of frame f: Philox4x32-10 with counter (f, t lo, t hi, 0) and key (seed lo, seed hi) gives
+ *                         r0 .. r3.  mode 0 (swap): i = (r0 N) >> 32, j = (r1 N) >> 32 over the frame's N atoms; null trial
+ *                         (counted, never accepted) when i == j, z_i == z_j or either atom is not swappable.  mode 1 (transmute):
+ *                         i as above, new species the k-th of the allowed species other than z_i in the basis' species order,
+ *                         k = (r1 (S_allowed - 1)) >> 32; allowed: mu [S] finite (-inf excludes a species; mu is required in mode
+ *                         1 and refused in mode 0); null when i is not swappable, z_i is not allowed or nothing else is.  dE is
+ *                         the sum of every energy term of the evaluator that contains a touched atom, new species minus old, in a
+ *                         fixed order (no atomics); dE' = dE - (mu_new - mu_old).  Accepted when dE' <= 0 or
+ *                         u < exp(-dE' / k_B T_f), u = ((r2 << 32 | r3) >> 11) + 0.5) 2^-53; temperatures_K [n_frames] >= 0, 0
+ *                         accepts dE' <= 0 only.  An accepted trial writes the species and adds dE (not the mu term) to the
+ *                         frame's running energy, which starts from the evaluator's.  A non-finite dE freezes the frame (status
+ *                         2; the trial is not counted).  record_every > 0: records [n_trials / record_every][n_frames][3 + S]
+ *                         after every record_every-th trial of the run: energy, accepted so far, trials so far, atoms of each
+ *                         species; rows a frozen frame did not reach repeat its last row of the run (NULL when record_every is
+ *                         0).  run(a); run(b) equals run(a + b) bit for bit, and a frame's chain does not depend on the batch
+ *                         around it.  The context's MD skin and lists are not touched.
+ *   uf3_mc_delta          dE [n] of n caller-given proposals on the current species, nothing applied: frame, atom i within the
+ *                         frame, and the second atom j within the frame (mode 0) or the new atomic number (mode 1).  A swap of
+ *                         like atoms gives exactly 0.  UF3_EINVAL: an index outside its frame; UF3_ESPECIES: an unknown element.
+ *   uf3_mc_set_positions  new positions [N][3]: the table is rebuilt, the running energies are evaluated again on next need.
+ *   uf3_mc_get_state      host arrays out, NULL skips: species [N] (atomic numbers), running energies, accepted and counted
+ *                         trials, status (0 running, 2 frozen) [n_frames].
+ */
+typedef struct uf3_mc uf3_mc;
+int uf3_mc_create(uf3_basis *basis, const uf3_frames *frames, const double *pos, const int32_t *z, const uint8_t *swappable,
+                  const double *c1, const double *c2, const double *c3, uf3_mc **out);
+void uf3_mc_destroy(uf3_mc *mc);
+int uf3_mc_run(uf3_mc *mc, int64_t n_trials, int mode, const double *temperatures_K /*[n_frames]*/, const double *mu /*[S] or NULL*/,
+               uint64_t seed, int64_t record_every, double *records);
+int uf3_mc_delta(uf3_mc *mc, int64_t n, const int32_t *frame, const int32_t *i, const int32_t *j_or_species, int mode, double *dE);
+int uf3_mc_set_positions(uf3_mc *mc, const double *pos);
+int uf3_mc_get_state(uf3_mc *mc, int32_t *z, double *energies, int64_t *accepted, int64_t *trials, int32_t *status);
 
 /*
  * Analytic second derivatives of the energy uf3_eval computes, for ONE frame (uf3_hessian.h; the Gamma-point force constants

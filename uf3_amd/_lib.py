@@ -33,11 +33,12 @@ EXPORTS = ["uf3_ctx_create", "uf3_ctx_destroy", "uf3_ctx_set_stream", "uf3_ctx_s
            "uf3_md_info", "uf3_md_run_npt", "uf3_md_get_cells", "uf3_ctx_md_live", "uf3_philox_debug", "uf3_hessian", "uf3_hessian_dev",
            "uf3_relax_create", "uf3_relax_destroy", "uf3_relax_run", "uf3_relax_get_state",
            "uf3_neb_create", "uf3_neb_destroy", "uf3_neb_run", "uf3_neb_get_state",
+           "uf3_mc_create", "uf3_mc_destroy", "uf3_mc_run", "uf3_mc_delta", "uf3_mc_set_positions", "uf3_mc_get_state",
            "uf3_phonon_mesh", "uf3_phonon_mesh_dev", "uf3_phonon_dos", "uf3_phonon_dos_dev", "uf3_phonon_thermo",
            "uf3_phonon_thermo_dev"]
 
 
-SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_device.h", "uf3_md.h", "uf3_hessian.h", "uf3_relax.h", "uf3_phonon.h", "uf3_npt.h", "uf3_neb.h", os.path.join("..", "..", "include", "uf3_hip.h"))
+SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_device.h", "uf3_md.h", "uf3_hessian.h", "uf3_relax.h", "uf3_phonon.h", "uf3_npt.h", "uf3_neb.h", "uf3_mc.h", os.path.join("..", "..", "include", "uf3_hip.h"))
 
 
 def source_build_id(csrc_dir=None):
@@ -214,6 +215,13 @@ def load():
         lib.uf3_neb_destroy.restype = None
         lib.uf3_neb_run.argtypes = [vp, i64, dbl, dbl, dbl, dbl, dbl, C.c_int, i64, i64, vp]
         lib.uf3_neb_get_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.uf3_mc_create.argtypes = [vp, C.POINTER(Frames), vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
+        lib.uf3_mc_destroy.argtypes = [vp]
+        lib.uf3_mc_destroy.restype = None
+        lib.uf3_mc_run.argtypes = [vp, i64, C.c_int, vp, vp, C.c_uint64, i64, vp]
+        lib.uf3_mc_delta.argtypes = [vp, i64, vp, vp, vp, C.c_int, vp]
+        lib.uf3_mc_set_positions.argtypes = [vp, vp]
+        lib.uf3_mc_get_state.argtypes = [vp, vp, vp, vp, vp, vp]
         for name in ("uf3_phonon_mesh", "uf3_phonon_mesh_dev"):
             getattr(lib, name).argtypes = [vp, i32, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp]
         for name in ("uf3_phonon_dos", "uf3_phonon_dos_dev"):

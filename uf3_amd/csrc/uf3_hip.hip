@@ -23,6 +23,7 @@
 #include "uf3_hessian.h"
 #include "uf3_relax.h"
 #include "uf3_neb.h"
+#include "uf3_mc.h"
 #include "uf3_phonon.h"
 #include <chrono>
 #include <dlfcn.h>
@@ -4643,6 +4644,348 @@ extern "C" int uf3_neb_get_state(uf3_neb *r, double *pos, double *forces, double
         if (criterion) criterion[bd] = r->st_host[bd].crit_last;
         if (climbing) climbing[bd] = r->st_host[bd].climbing;
     }
+    return UF3_OK;
+}
+
+// ------------------------------------------------------------------------------ species-swap Monte Carlo (uf3_mc_*, uf3_mc.h)
+// A library-owned batch of lattice Monte Carlo chains on fixed positions: the species (atomic numbers) live in HBM and change there,
+// the neighbour table depends on the positions alone (built on the host at creation and by uf3_mc_set_positions, O(N^2 images)
+// per frame: once per geometry, not per trial), the running energies start from the evaluator's (eval_impl, energies only: the
+// context's MD lists and skin are not touched) and follow the accepted differences.
+struct uf3_mc {
+    uf3_basis *b = nullptr;
+    uf3_ctx *c = nullptr;
+    int32_t n_frames = 0;
+    int64_t natoms = 0;
+    int max_frame = 0;                          // atoms of the largest frame
+    bool has_mask = false, energy_valid = false;
+    uint64_t trial = 0;                         // absolute index of the next trial (Philox counter)
+    std::vector<int64_t> offsets;
+    std::vector<double> cells, pos_host;
+    std::vector<uint8_t> pbc;
+    uf3_frames fr{};
+    std::vector<double> c1, c2, c3;
+    int s2z[UF3_MAX_SPECIES] = {0};
+    Buf pos, z, swappable, energies, accepted, trials, status, offsets_dev, kT, off2, off3, ent2, ent3, c1d, c2d, c3d, ring, prop, dE;
+};
+
+extern "C" void uf3_mc_destroy(uf3_mc *m) {
+    if (!m) return;
+    hipSetDevice(m->c->device);
+    hipStreamSynchronize(m->c->stream);
+    for (Buf *p : {&m->pos, &m->z, &m->swappable, &m->energies, &m->accepted, &m->trials, &m->status, &m->offsets_dev, &m->kT, &m->off2,
+                   &m->off3, &m->ent2, &m->ent3, &m->c1d, &m->c2d, &m->c3d, &m->ring, &m->prop, &m->dE})
+        p->release();
+    delete m;
+}
+
+// the geometry-only neighbour table of the object's positions: the evaluator's candidate set (images -fac .. fac of every atom of
+// the frame, image_delta's arithmetic) cut at the largest pair range and at the 3-body range, entries in supercell index order
+static int mc_build_table(uf3_mc *m, const char *who) {
+    uf3_ctx *c = m->c;
+    const uf3_basis *b = m->b;
+    const BasisDev &H = b->host;
+    double s2_hi = 0.0;
+    for (int p = 0; p < H.P; p++) s2_hi = std::max(s2_hi, H.pairs[p].s_hi);
+    const bool has3 = H.T > 0;
+    std::vector<long long> off2(m->natoms + 1, 0), off3(m->natoms + 1, 0);
+    std::vector<McEnt2> ent2;
+    std::vector<McEnt3> ent3;
+    auto image_pos_h = [](int s) { return s == 0 ? 0 : (s > 0 ? 2 * s - 1 : -2 * s); };
+    for (int f = 0; f < m->n_frames; f++) {
+        const double *cell = m->cells.data() + 9 * (size_t)f;
+        const uint8_t *pbc = m->pbc.data() + 3 * (size_t)f;
+        const int64_t lo = m->offsets[f], n = m->offsets[f + 1] - lo;
+        int fac[3] = {0, 0, 0};
+        if (pbc[0] || pbc[1] || pbc[2]) {
+            reference_factors(cell, b->r_cut, fac);
+            for (int k = 0; k < 3; k++) if (!pbc[k]) fac[k] = 0;
+        }
+        for (int k = 0; k < 3; k++)
+            if (fac[k] > 400) return fail(c, UF3_EINVAL, std::string(who) + ": cell is too small relative to the cutoff");
+        const int cnt[3] = {2 * fac[0] + 1, 2 * fac[1] + 1, 2 * fac[2] + 1};
+        // the image shifts in the order of their rank in the reference supercell
+        struct Shift { int rank, s[3]; double off[3]; };
+        std::vector<Shift> shifts;
+        for (int s0 = -fac[0]; s0 <= fac[0]; s0++)
+            for (int s1 = -fac[1]; s1 <= fac[1]; s1++)
+                for (int s2 = -fac[2]; s2 <= fac[2]; s2++) {
+                    Shift sh;
+                    sh.rank = (image_pos_h(s1) * cnt[0] + image_pos_h(s0)) * cnt[2] + image_pos_h(s2);
+                    sh.s[0] = s0; sh.s[1] = s1; sh.s[2] = s2;
+                    for (int k = 0; k < 3; k++) sh.off[k] = s0 * cell[k] + s1 * cell[3 + k] + s2 * cell[6 + k];
+                    shifts.push_back(sh);
+                }
+        std::sort(shifts.begin(), shifts.end(), [](const Shift &a, const Shift &b2) { return a.rank < b2.rank; });
+        const double *P = m->pos_host.data() + 3 * (size_t)lo;
+        for (int64_t i = 0; i < n; i++) {
+            int n3_here = 0;
+            for (const Shift &sh : shifts)
+                for (int64_t j = 0; j < n; j++) {
+                    if (i == j && sh.rank == 0) continue;
+                    const double dx = (P[3 * j] + sh.off[0]) - P[3 * i], dy = (P[3 * j + 1] + sh.off[1]) - P[3 * i + 1],
+                                 dz = (P[3 * j + 2] + sh.off[2]) - P[3 * i + 2];
+                    const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
+                    const double s = (xx + yy) + zz;
+                    if (s < s2_hi) { McEnt2 e; e.s = s; e.atom = (int)j; e.pad = 0; ent2.push_back(e); }
+                    if (has3 && s > H.s3_lo && s <= H.s3_hi) {
+                        McEnt3 e;
+                        e.dx = dx; e.dy = dy; e.dz = dz; e.r = std::sqrt(s); e.atom = (int)j; e.pad[0] = e.pad[1] = e.pad[2] = 0;
+                        ent3.push_back(e);
+                        n3_here++;
+                    }
+                }
+            if (n3_here > UF3_MC_MAX_N3)
+                return fail(c, UF3_EINVAL, std::string(who) + ": an atom has " + std::to_string(n3_here) + " neighbours in the 3-body range, "
+                            "more than the " + std::to_string(UF3_MC_MAX_N3) + " the trial kernel's LDS list holds");
+            off2[lo + i + 1] = (long long)ent2.size();
+            off3[lo + i + 1] = (long long)ent3.size();
+        }
+    }
+    const size_t nn = (size_t)m->natoms + 1;
+    HIPCHK(c, m->off2.ensure(8 * nn));
+    HIPCHK(c, m->off3.ensure(8 * nn));
+    HIPCHK(c, m->ent2.ensure(sizeof(McEnt2) * std::max<size_t>(ent2.size(), 1)));
+    HIPCHK(c, m->ent3.ensure(sizeof(McEnt3) * std::max<size_t>(ent3.size(), 1)));
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(m->off2.p, off2.data(), 8 * nn, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(m->off3.p, off3.data(), 8 * nn, hipMemcpyHostToDevice, s));
+    if (!ent2.empty()) HIPCHK(c, hipMemcpyAsync(m->ent2.p, ent2.data(), sizeof(McEnt2) * ent2.size(), hipMemcpyHostToDevice, s));
+    if (!ent3.empty()) HIPCHK(c, hipMemcpyAsync(m->ent3.p, ent3.data(), sizeof(McEnt3) * ent3.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(m->pos.p, m->pos_host.data(), 24 * (size_t)m->natoms, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipStreamSynchronize(s));           // (the host vectors go out of scope)
+    m->energy_valid = false;
+    return UF3_OK;
+}
+
+extern "C" int uf3_mc_create(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const uint8_t *swappable,
+                             const double *c1, const double *c2, const double *c3, uf3_mc **out) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "uf3_mc_create: basis is NULL");
+    uf3_ctx *c = b->ctx;
+    if (!out) return fail(c, UF3_EINVAL, "uf3_mc_create: out is NULL");
+    if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, "uf3_mc_create: bad uf3_frames");
+    if (!pos) return fail(c, UF3_EINVAL, "uf3_mc_create: pos is NULL");
+    if (!z) return fail(c, UF3_EINVAL, "uf3_mc_create: z is NULL");
+    if (!c1 || (b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, "uf3_mc_create: missing coefficients (c1 / c2 / c3)");
+    const int nf = fr->n_frames;
+    if (fr->atom_offsets[0] != 0) return fail(c, UF3_EINVAL, "uf3_mc_create: atom_offsets[0] must be 0");
+    int max_frame = 0;
+    for (int f = 0; f < nf; f++) {
+        const int64_t nfr = fr->atom_offsets[f + 1] - fr->atom_offsets[f];
+        if (nfr < 1) return fail(c, UF3_EINVAL, "uf3_mc_create: every frame needs an atom");
+        if (nfr > UF3_MC_MAX_ATOMS)
+            return fail(c, UF3_EINVAL, "uf3_mc_create: a frame holds more than " + std::to_string(UF3_MC_MAX_ATOMS) + " atoms (its species sit in LDS)");
+        max_frame = std::max(max_frame, (int)nfr);
+    }
+    const int64_t n = fr->atom_offsets[nf];
+    if (n >= (1LL << 28)) return fail(c, UF3_EINVAL, "uf3_mc_create: batch must hold 1 .. 2^28 atoms");
+    if (!md_finite(pos, 3 * (size_t)n)) return fail(c, UF3_EINVAL, "uf3_mc_create: pos must be finite");
+    if (!md_finite(fr->cells, 9 * (size_t)nf)) return fail(c, UF3_EINVAL, "uf3_mc_create: cells must be finite");
+    for (int64_t i = 0; i < n; i++) {
+        if (z[i] < 0 || z[i] >= 120 || b->host.z2s[z[i]] < 0) return fail(c, UF3_ESPECIES, "uf3_mc_create: element outside the basis");
+        if (swappable && swappable[i] > 1) return fail(c, UF3_EINVAL, "uf3_mc_create: swappable must hold 0 or 1 per atom");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    uf3_mc *m = new uf3_mc();
+    m->b = b; m->c = c; m->n_frames = nf; m->natoms = n; m->max_frame = max_frame; m->has_mask = swappable != nullptr;
+    m->offsets.assign(fr->atom_offsets, fr->atom_offsets + nf + 1);
+    m->cells.assign(fr->cells, fr->cells + 9 * (size_t)nf);
+    m->pbc.assign(fr->pbc, fr->pbc + 3 * (size_t)nf);
+    m->pos_host.assign(pos, pos + 3 * (size_t)n);
+    m->fr.n_frames = nf; m->fr.atom_offsets = m->offsets.data(); m->fr.cells = m->cells.data(); m->fr.pbc = m->pbc.data();
+    const int S = b->host.S;
+    m->c1.assign(c1, c1 + S);
+    m->c2.assign(c2 ? c2 : c1, (c2 ? c2 : c1) + b->c2_len); m->c2.resize(b->c2_len + 8, 0.0);
+    m->c3.assign(c3 ? c3 : c1, (c3 ? c3 : c1) + b->c3_len); m->c3.resize(b->c3_len + 8, 0.0);
+    for (int zz = 0; zz < 120; zz++)
+        if (b->host.z2s[zz] >= 0 && b->host.z2s[zz] < UF3_MAX_SPECIES) m->s2z[b->host.z2s[zz]] = zz;
+    auto bail = [&](int rc) { const std::string msg = c->err; uf3_mc_destroy(m); return fail(c, rc, msg); };
+    if (m->pos.ensure(24 * (size_t)n) || m->z.ensure(4 * (size_t)n) || (swappable && m->swappable.ensure((size_t)n)) ||
+        m->energies.ensure(8 * (size_t)nf) || m->accepted.ensure(8 * (size_t)nf) || m->trials.ensure(8 * (size_t)nf) ||
+        m->status.ensure(4 * (size_t)nf) || m->offsets_dev.ensure(8 * (size_t)(nf + 1)) || m->kT.ensure(8 * (size_t)nf) ||
+        m->c1d.ensure(8 * m->c1.size()) || m->c2d.ensure(8 * m->c2.size()) || m->c3d.ensure(8 * m->c3.size())) {
+        fail(c, UF3_ENOMEM, "uf3_mc_create: out of device memory");
+        return bail(UF3_ENOMEM);
+    }
+    hipStream_t s = c->stream;
+    if (hipMemcpyAsync(m->z.p, z, 4 * (size_t)n, hipMemcpyHostToDevice, s) ||
+        (swappable && hipMemcpyAsync(m->swappable.p, swappable, (size_t)n, hipMemcpyHostToDevice, s)) ||
+        hipMemsetAsync(m->energies.p, 0, 8 * (size_t)nf, s) || hipMemsetAsync(m->accepted.p, 0, 8 * (size_t)nf, s) ||
+        hipMemsetAsync(m->trials.p, 0, 8 * (size_t)nf, s) || hipMemsetAsync(m->status.p, 0, 4 * (size_t)nf, s) ||
+        hipMemcpyAsync(m->offsets_dev.p, m->offsets.data(), 8 * (size_t)(nf + 1), hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(m->c1d.p, m->c1.data(), 8 * m->c1.size(), hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(m->c2d.p, m->c2.data(), 8 * m->c2.size(), hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(m->c3d.p, m->c3.data(), 8 * m->c3.size(), hipMemcpyHostToDevice, s) || hipStreamSynchronize(s)) {
+        fail(c, UF3_EHIP, "uf3_mc_create: upload failed");
+        return bail(UF3_EHIP);
+    }
+    const int rc = mc_build_table(m, "uf3_mc_create");
+    if (rc) return bail(rc);
+    *out = m;
+    return UF3_OK;
+}
+
+// the evaluator's energies of the current species at the current positions, when the running energies do not describe them
+static int mc_energies(uf3_mc *m) {
+    if (m->energy_valid) return UF3_OK;
+    const int rc = eval_impl(m->b, &m->fr, m->pos.as<double>(), m->z.as<int32_t>(), m->c1.data(), m->c2.data(), m->c3.data(),
+                             m->energies.as<double>(), nullptr, nullptr);
+    if (rc) return rc;
+    m->energy_valid = true;
+    return UF3_OK;
+}
+
+static McModel mc_model(const uf3_mc *m) {
+    McModel M;
+    M.B = m->b->dev; M.c1 = m->c1d.as<double>(); M.c2 = m->c2d.as<double>(); M.c3 = m->c3d.as<double>();
+    M.S = m->b->host.S; M.T = m->b->host.T;
+    return M;
+}
+
+static McTable mc_table(const uf3_mc *m) {
+    McTable t;
+    t.off2 = m->off2.as<long long>(); t.off3 = m->off3.as<long long>(); t.ent2 = m->ent2.as<McEnt2>(); t.ent3 = m->ent3.as<McEnt3>();
+    return t;
+}
+
+extern "C" int uf3_mc_set_positions(uf3_mc *m, const double *pos) {
+    if (!m) return fail(nullptr, UF3_EINVAL, "uf3_mc_set_positions: mc is NULL");
+    uf3_ctx *c = m->c;
+    if (!pos) return fail(c, UF3_EINVAL, "uf3_mc_set_positions: pos is NULL");
+    if (!md_finite(pos, 3 * (size_t)m->natoms)) return fail(c, UF3_EINVAL, "uf3_mc_set_positions: pos must be finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const std::vector<double> before = m->pos_host;
+    m->pos_host.assign(pos, pos + 3 * (size_t)m->natoms);
+    const int rc = mc_build_table(m, "uf3_mc_set_positions");
+    if (rc) {                                    // (refused: the object keeps its positions and its table)
+        const std::string msg = c->err;
+        m->pos_host = before;
+        mc_build_table(m, "uf3_mc_set_positions");
+        return fail(c, rc, msg);
+    }
+    return UF3_OK;
+}
+
+extern "C" int uf3_mc_run(uf3_mc *m, int64_t n_trials, int mode, const double *temperatures_K, const double *mu, uint64_t seed,
+                          int64_t record_every, double *records) {
+    if (!m) return fail(nullptr, UF3_EINVAL, "uf3_mc_run: mc is NULL");
+    uf3_ctx *c = m->c;
+    const int nf = m->n_frames, S = m->b->host.S;
+    if (n_trials < 0) return fail(c, UF3_EINVAL, "uf3_mc_run: n_trials must be >= 0");
+    if (mode != 0 && mode != 1) return fail(c, UF3_EINVAL, "uf3_mc_run: mode must be 0 (swap) or 1 (transmute)");
+    if (!temperatures_K) return fail(c, UF3_EINVAL, "uf3_mc_run: temperatures_K is NULL");
+    for (int f = 0; f < nf; f++)
+        if (!(temperatures_K[f] >= 0.0) || !std::isfinite(temperatures_K[f]))
+            return fail(c, UF3_EINVAL, "uf3_mc_run: temperatures must be finite and >= 0");
+    if ((mode == 1) != (mu != nullptr)) return fail(c, UF3_EINVAL, "uf3_mc_run: mu goes with mode 1 (transmute), and only with it");
+    if (mu)
+        for (int s = 0; s < S; s++)
+            if (std::isnan(mu[s]) || mu[s] == std::numeric_limits<double>::infinity())
+                return fail(c, UF3_EINVAL, "uf3_mc_run: a chemical potential must be finite or -inf (species not allowed)");
+    if (record_every < 0) return fail(c, UF3_EINVAL, "uf3_mc_run: record_every must be >= 0");
+    if ((record_every > 0) != (records != nullptr))
+        return fail(c, UF3_EINVAL, record_every ? "uf3_mc_run: records are due but the records buffer is NULL"
+                                                : "uf3_mc_run: a records buffer was given but no record is due");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = mc_energies(m);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    std::vector<double> kT(nf);
+    for (int f = 0; f < nf; f++) kT[f] = UF3_MD_KB * temperatures_K[f];
+    HIPCHK(c, hipMemcpyAsync(m->kT.p, kT.data(), 8 * (size_t)nf, hipMemcpyHostToDevice, s));
+    const int width = 3 + S;
+    const int64_t n_rec = record_every ? n_trials / record_every : 0;
+    if (n_rec) {
+        HIPCHK(c, m->ring.ensure(8 * (size_t)n_rec * nf * width));
+        HIPCHK(c, hipMemsetAsync(m->ring.p, 0, 8 * (size_t)n_rec * nf * width, s));
+    }
+    McTrialArgs A;
+    A.M = mc_model(m); A.tb = mc_table(m);
+    A.offsets = m->offsets_dev.as<long long>(); A.z = m->z.as<int32_t>();
+    A.swappable = m->has_mask ? m->swappable.as<uint8_t>() : nullptr;
+    A.energy = m->energies.as<double>(); A.accepted = m->accepted.as<long long>(); A.trials = m->trials.as<long long>();
+    A.status = m->status.as<int>(); A.kT = m->kT.as<double>();
+    for (int q = 0; q < UF3_MAX_SPECIES; q++) { A.mu[q] = (mu && q < S) ? mu[q] : 0.0; A.s2z[q] = m->s2z[q]; }
+    A.mode = mode; A.seed = seed; A.rec_every = record_every; A.records = n_rec ? m->ring.as<double>() : nullptr; A.n_frames = nf;
+    const size_t lds = ((size_t)m->max_frame + 15) & ~(size_t)15;
+    // a launch is a bounded block of trials; the blocks of a run queue up on the stream
+    for (int64_t done = 0; done < n_trials; done += UF3_MC_BLOCK_TRIALS) {
+        A.t0 = m->trial + (uint64_t)done; A.run_done = done;
+        A.n_trials = (int)std::min<int64_t>(UF3_MC_BLOCK_TRIALS, n_trials - done);
+        hipLaunchKernelGGL(k_mc_trials, dim3((unsigned)nf), dim3(UF3_MC_THREADS), lds, s, A);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (n_rec) HIPCHK(c, hipMemcpyAsync(records, m->ring.p, 8 * (size_t)n_rec * nf * width, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    m->trial += (uint64_t)n_trials;
+    if (n_rec) {
+        // a frame frozen inside the run wrote no later record: its rows repeat the last one written (trials > 0 marks a written row)
+        for (int f = 0; f < nf; f++)
+            for (int64_t k = 1; k < n_rec; k++) {
+                double *row = records + ((size_t)k * nf + f) * width;
+                if (row[2] == 0.0) memcpy(row, row - (size_t)nf * width, 8 * (size_t)width);
+            }
+    }
+    return UF3_OK;
+}
+
+extern "C" int uf3_mc_delta(uf3_mc *m, int64_t n, const int32_t *frame, const int32_t *i, const int32_t *j_or_species, int mode,
+                            double *dE) {
+    if (!m) return fail(nullptr, UF3_EINVAL, "uf3_mc_delta: mc is NULL");
+    uf3_ctx *c = m->c;
+    if (n < 0 || n >= (1LL << 30)) return fail(c, UF3_EINVAL, "uf3_mc_delta: n must lie in 0 .. 2^30");
+    if (mode != 0 && mode != 1) return fail(c, UF3_EINVAL, "uf3_mc_delta: mode must be 0 (swap) or 1 (transmute)");
+    if (n == 0) return UF3_OK;
+    if (!frame || !i || !j_or_species || !dE) return fail(c, UF3_EINVAL, "uf3_mc_delta: null argument");
+    std::vector<int32_t> prop(3 * (size_t)n);
+    for (int64_t q = 0; q < n; q++) {
+        if (frame[q] < 0 || frame[q] >= m->n_frames) return fail(c, UF3_EINVAL, "uf3_mc_delta: frame outside the batch");
+        const int64_t nfr = m->offsets[frame[q] + 1] - m->offsets[frame[q]];
+        if (i[q] < 0 || i[q] >= nfr) return fail(c, UF3_EINVAL, "uf3_mc_delta: atom i outside its frame");
+        int32_t second = j_or_species[q];
+        if (mode == 0) {
+            if (second < 0 || second >= nfr) return fail(c, UF3_EINVAL, "uf3_mc_delta: atom j outside its frame");
+        } else {
+            if (second < 0 || second >= 120 || m->b->host.z2s[second] < 0) return fail(c, UF3_ESPECIES, "uf3_mc_delta: element outside the basis");
+            second = m->b->host.z2s[second];
+        }
+        prop[q] = frame[q]; prop[n + q] = i[q]; prop[2 * n + q] = second;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, m->prop.ensure(12 * (size_t)n));
+    HIPCHK(c, m->dE.ensure(8 * (size_t)n));
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(m->prop.p, prop.data(), 12 * (size_t)n, hipMemcpyHostToDevice, s));
+    McDeltaArgs A;
+    A.M = mc_model(m); A.tb = mc_table(m);
+    A.offsets = m->offsets_dev.as<long long>(); A.z = m->z.as<int32_t>();
+    A.frame = m->prop.as<int32_t>(); A.i = A.frame + n; A.j = A.frame + 2 * n;
+    A.mode = mode; A.dE = m->dE.as<double>();
+    const size_t lds = ((size_t)m->max_frame + 15) & ~(size_t)15;
+    hipLaunchKernelGGL(k_mc_delta, dim3((unsigned)n), dim3(UF3_MC_THREADS), lds, s, A);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(dE, m->dE.p, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return UF3_OK;
+}
+
+extern "C" int uf3_mc_get_state(uf3_mc *m, int32_t *z, double *energies, int64_t *accepted, int64_t *trials, int32_t *status) {
+    if (!m) return fail(nullptr, UF3_EINVAL, "uf3_mc_get_state: mc is NULL");
+    uf3_ctx *c = m->c;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (energies) {
+        const int rc = mc_energies(m);
+        if (rc) return rc;
+    }
+    hipStream_t s = c->stream;
+    const size_t nf = (size_t)m->n_frames;
+    if (z) HIPCHK(c, hipMemcpyAsync(z, m->z.p, 4 * (size_t)m->natoms, hipMemcpyDeviceToHost, s));
+    if (energies) HIPCHK(c, hipMemcpyAsync(energies, m->energies.p, 8 * nf, hipMemcpyDeviceToHost, s));
+    if (accepted) HIPCHK(c, hipMemcpyAsync(accepted, m->accepted.p, 8 * nf, hipMemcpyDeviceToHost, s));
+    if (trials) HIPCHK(c, hipMemcpyAsync(trials, m->trials.p, 8 * nf, hipMemcpyDeviceToHost, s));
+    if (status) HIPCHK(c, hipMemcpyAsync(status, m->status.p, 4 * nf, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
     return UF3_OK;
 }
 

@@ -349,6 +349,25 @@ class UFCalculator(_Base):
                               f"{info['criterion'][k]:.3g} eV/A)", RuntimeWarning)
         return out, info
 
+    def monte_carlo(self, atoms_or_list, n_trials, temperature_K, **kw):
+        """
+        Species-swap Monte Carlo of a batch of frames at once on the device (``mc.MonteCarlo``: fixed positions, every frame
+        its own chain and temperature; canonical swaps, or with ``mode="transmute"`` and ``chemical_potentials``
+        semi-grand-canonical transmutations).  ``kw``: ``mode``, ``chemical_potentials``, ``swappable``, ``seed``, ``device``
+        (the object's) and ``record_every`` (``run``'s).  Returns (frames with their final species, info), info as
+        ``MonteCarlo.run`` returns it; warns (RuntimeWarning) for every frame a non-finite energy difference froze.
+        """
+        import warnings
+        from .mc import MonteCarlo
+        make = {k: kw.pop(k) for k in ("mode", "chemical_potentials", "swappable", "seed", "device") if k in kw}
+        with MonteCarlo(self, atoms_or_list, temperature_K, **make) as mc:
+            info = mc.run(n_trials, **kw)
+            out = mc.get_atoms()
+        for k, status in enumerate(info["status"]):
+            if status != "running":
+                warnings.warn(f"monte_carlo: frame {k} froze ({status} after {info['trials'][k]} trials)", RuntimeWarning)
+        return out, info
+
     def get_hessian(self, atoms, rows=None, strain=False):
         """Exact second derivatives of the energy on the device (``harmonic.hessian``): H [3N, 3N] (or the rows of ``rows``),
         with ``strain=True`` also the mixed position / strain derivatives, the clamped-ion strain term and the virial."""
