@@ -106,7 +106,7 @@ int uf3_ctx_use_own_stream(uf3_ctx *ctx);
 int uf3_ctx_synchronize(uf3_ctx *ctx);
 const char *uf3_last_error(const uf3_ctx *ctx);
 /* Which sources this binary was compiled from: the first 16 hex digits of the sha256 over uf3_hip.hip, uf3_kernels.h,
- * uf3_feat3.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h, uf3_npt.h, uf3_neb.h, uf3_mc.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
+ * uf3_feat3.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h, uf3_npt.h, uf3_neb.h, uf3_mc.h, uf3_flux.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
  * outside it).  __graft_entry__.build() rebuilds when it differs from the tree's, smoke() prints it. */
 const char *uf3_build_id(void);
 /* timing of the dominant kernel: (re)start / read accumulated HIP-event time in ms and launches */
@@ -451,6 +451,17 @@ int uf3_md_run_npt(uf3_md *md, int64_t n_steps, double dt_fs, double temperature
                    double skin, int64_t thermo_every, double *thermo);
 int uf3_md_get_cells(uf3_md *md, double *cells, double *scales, double *strain_rates);
 int uf3_ctx_md_live(uf3_ctx *ctx, int32_t *live);
+/* uf3_md_run with heat-current samples (uf3_flux.h; the definitions stand in front of uf3_site_terms below): what uf3_md_run does,
+ * and after every flux_every-th step of the run one record [n_frames][6] = J_conv (3), J_pot (3) (eV Angstrom / fs) of the closed
+ * state -- velocities at integer time, the positions the forces belong to.  flux must hold n_steps / flux_every records (NULL
+ * when none is due; flux_every = 0 is uf3_md_run call for call).  The launch that closes a sampled step does not open the next
+ * one, which is the split a run boundary makes anyway: the trajectory and the thermo records keep their bits, and run(a); run(b)
+ * gives the records of run(a + b).  The lists of the samples are the state's own (sized at its first sample with a quarter of
+ * headroom; a sample whose lists overflow is redone with a larger capacity); one stream synchronisation per sample.  There is
+ * no such entry for uf3_md_run_npt: the heat current is sampled at constant volume only (the Python layer refuses the pair with
+ * UF3_EINVAL). */
+int uf3_md_run_flux(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
+                    double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t flux_every, double *flux);
 int uf3_philox_debug(uf3_ctx *ctx, int64_t n, const uint32_t *counters, const uint32_t *keys, uint32_t *out);
 
 /*
@@ -569,6 +580,40 @@ int uf3_mc_run(uf3_mc *mc, int64_t n_trials, int mode, const double *temperature
 int uf3_mc_delta(uf3_mc *mc, int64_t n, const int32_t *frame, const int32_t *i, const int32_t *j_or_species, int mode, double *dE);
 int uf3_mc_set_positions(uf3_mc *mc, const double *pos);
 int uf3_mc_get_state(uf3_mc *mc, int32_t *z, double *energies, int64_t *accepted, int64_t *trials, int32_t *status);
+
+/*
+ * The energy uf3_eval computes, resolved per atom, for a batch of frames (uf3_flux.h).
+ *   Site energy   U_i: the evaluator's own partition, what uf3_eval_atoms(i, i + 1) returns as the share of atom i -- the
+ *                 one-body term of i's species, the directed pair terms phi(r_ij) of i over every image j in the pair range,
+ *                 and every triplet V(r_ij, r_ik, r_jk) with i as the centre, over unordered pairs {j, k} of its 3-body
+ *                 neighbours.  sum_i U_i = uf3_eval's frame energy.
+ *   Images        move with their parent atom and carry its velocity.
+ *   Site virial   W_i[a][b] = sum_terms sum_s d_s[a] (dU_i / dr_s)[b], s the slots of a term of U_i (neighbour images), d_s the
+ *                 vector from the centre to the image; [N][9] row-major.  sum_i W_i, symmetrised, in Voigt order = uf3_eval_virial's
+ *                 dE / d(strain).
+ *   Heat current  e_i = 1/2 m_i v_i^2 + U_i;  J = J_conv + J_pot, extensive, eV Angstrom / fs (velocities Angstrom / fs, masses amu):
+ *                 J_conv = sum_i e_i v_i,  J_pot = - sum_i sum_terms sum_s d_s (dU_i / dr_s . v_s)  (= d/dt sum_i r_i e_i with
+ *                 Newton's equations; exact in a cluster, term by term with image vectors in a periodic cell).  Pair:
+ *                 dU_i / dr_j = phi'(r_ij) u_ij; triplet with legs ij, ik, jk and leg gradient g: d / dr_j = g_ij u_ij - g_jk u_jk,
+ *                 d / dr_k = g_ik u_ik + g_jk u_jk (u_jk from j to k).
+ *   uf3_site_terms   site_energies [N] and / or site_virials [N][9] (NULL skips one).
+ *   uf3_heat_flux    flux [n_frames][6] = J_conv (3), J_pot (3); site_energies [N] or NULL.
+ * The neighbour lists are the call's own (every image in reach of every atom, O(N^2 images) per frame; skin 0): the context's MD
+ * lists and its evaluator state are left as they were.  No atomics: one wave per centre, a fixed reduction tree -- results repeat
+ * bit for bit and a frame's do not depend on the batch around it.  A 2-body-only basis is allowed.  Errors: bad frames, null
+ * pointers, masses not positive and finite or velocities not finite (host entries, nothing launched), atoms more than 500 cells
+ * apart along a periodic axis, a cell far thinner than the cut-off (UF3_EINVAL); an element outside the basis (UF3_ESPECIES).
+ * _dev: device pos, vel, z, masses and outputs (coefficients on the host, as uf3_eval_dev); the host entries stage both ways.
+ */
+int uf3_site_terms(uf3_basis *basis, const uf3_frames *frames, const double *pos, const int32_t *z, const double *c1,
+                   const double *c2, const double *c3, double *site_energies, double *site_virials);
+int uf3_site_terms_dev(uf3_basis *basis, const uf3_frames *frames, const double *d_pos, const int32_t *d_z, const double *c1,
+                       const double *c2, const double *c3, double *d_site_energies, double *d_site_virials);
+int uf3_heat_flux(uf3_basis *basis, const uf3_frames *frames, const double *pos, const double *vel, const int32_t *z,
+                  const double *masses, const double *c1, const double *c2, const double *c3, double *flux, double *site_energies);
+int uf3_heat_flux_dev(uf3_basis *basis, const uf3_frames *frames, const double *d_pos, const double *d_vel, const int32_t *d_z,
+                      const double *d_masses, const double *c1, const double *c2, const double *c3, double *d_flux,
+                      double *d_site_energies);
 
 /*
  * Analytic second derivatives of the energy uf3_eval computes, for ONE frame (uf3_hessian.h; the Gamma-point force constants

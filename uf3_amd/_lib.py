@@ -35,10 +35,11 @@ EXPORTS = ["uf3_ctx_create", "uf3_ctx_destroy", "uf3_ctx_set_stream", "uf3_ctx_s
            "uf3_neb_create", "uf3_neb_destroy", "uf3_neb_run", "uf3_neb_get_state",
            "uf3_mc_create", "uf3_mc_destroy", "uf3_mc_run", "uf3_mc_delta", "uf3_mc_set_positions", "uf3_mc_get_state",
            "uf3_phonon_mesh", "uf3_phonon_mesh_dev", "uf3_phonon_dos", "uf3_phonon_dos_dev", "uf3_phonon_thermo",
-           "uf3_phonon_thermo_dev"]
+           "uf3_phonon_thermo_dev",
+           "uf3_site_terms", "uf3_site_terms_dev", "uf3_heat_flux", "uf3_heat_flux_dev", "uf3_md_run_flux"]
 
 
-SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_device.h", "uf3_md.h", "uf3_hessian.h", "uf3_relax.h", "uf3_phonon.h", "uf3_npt.h", "uf3_neb.h", "uf3_mc.h", os.path.join("..", "..", "include", "uf3_hip.h"))
+SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_device.h", "uf3_md.h", "uf3_hessian.h", "uf3_relax.h", "uf3_phonon.h", "uf3_npt.h", "uf3_neb.h", "uf3_mc.h", "uf3_flux.h", os.path.join("..", "..", "include", "uf3_hip.h"))
 
 
 def source_build_id(csrc_dir=None):
@@ -228,6 +229,11 @@ def load():
             getattr(lib, name).argtypes = [vp, i32, i64, vp, vp, i32, vp, vp, i32, vp, dbl, vp]
         for name in ("uf3_phonon_thermo", "uf3_phonon_thermo_dev"):
             getattr(lib, name).argtypes = [vp, i32, i64, vp, vp, i32, vp, dbl, vp, vp, vp]
+        for name in ("uf3_site_terms", "uf3_site_terms_dev"):
+            getattr(lib, name).argtypes = [vp, C.POINTER(Frames), vp, vp, vp, vp, vp, vp, vp]
+        for name in ("uf3_heat_flux", "uf3_heat_flux_dev"):
+            getattr(lib, name).argtypes = [vp, C.POINTER(Frames), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.uf3_md_run_flux.argtypes = [vp, i64, dbl, dbl, dbl, C.c_uint64, dbl, i64, C.c_int, vp, i64, vp]
         _lib = lib
         return lib
 

@@ -67,11 +67,11 @@ __device__ __forceinline__ void bspline4_d2(const KnotRec &k, double x, double *
 }
 
 // ---- neighbour lists: one wave per atom, lanes over the other atoms, every image in reach of each -------------------------
-// WRITE = false: counts only.  Entries in (atom, image, lane) order: the same lists on every call.
-template <bool WRITE>
-__global__ void __launch_bounds__(64) k_hess_lists(HessArgs A) {
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (i >= A.natoms) return;
+// WRITE = false: counts only.  Entries in (atom, image, lane) order: the same lists on every call.  CHECK: flag image shifts
+// beyond pack3's range.  The body is a device function of one frame's arguments, so that a batch of frames (uf3_flux.h:
+// k_flux_lists, one HessArgs per frame put together on the device) walks the same code.
+template <bool WRITE, bool CHECK>
+__device__ __forceinline__ void hess_lists_atom(const HessArgs &A, int i, int lane) {
     const BasisDev *B = A.B;
     const double xi = A.pos[3 * (size_t)i], yi = A.pos[3 * (size_t)i + 1], zi = A.pos[3 * (size_t)i + 2];
     const int si = A.spec[i];
@@ -106,7 +106,7 @@ __global__ void __launch_bounds__(64) k_hess_lists(HessArgs A) {
                     const bool in3 = has3 && s > s3_lo && s <= s3_hi;
                     const bool ok = live && !self && (in2 || in3);
                     // (the reverse-shift lookup of k_hessian compares packed shifts: a shift beyond pack3's +-511 would alias)
-                    if (!WRITE && ok && (abs(S0) > 500 || abs(S1) > 500 || abs(S2) > 500)) *A.bad = 1;
+                    if (CHECK && ok && (abs(S0) > 500 || abs(S1) > 500 || abs(S2) > 500)) *A.bad = 1;
                     const unsigned long long mask = __ballot(ok);
                     if (WRITE && ok) {
                         const int slot = count + mbcnt(mask);
@@ -121,6 +121,12 @@ __global__ void __launch_bounds__(64) k_hess_lists(HessArgs A) {
                 }
     }
     if (lane == 0) A.cnt[i] = count;
+}
+
+template <bool WRITE>
+__global__ void __launch_bounds__(64) k_hess_lists(HessArgs A) {
+    if ((int)blockIdx.x >= A.natoms) return;
+    hess_lists_atom<WRITE, !WRITE>(A, blockIdx.x, threadIdx.x);
 }
 
 // ---- per-term derivatives -------------------------------------------------------------------------------------------------

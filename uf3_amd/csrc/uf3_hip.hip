@@ -25,6 +25,7 @@
 #include "uf3_neb.h"
 #include "uf3_mc.h"
 #include "uf3_phonon.h"
+#include "uf3_flux.h"
 #include <chrono>
 #include <dlfcn.h>
 
@@ -71,6 +72,12 @@ struct PinBuf {
     }
     void release() { if (p) hipHostFree(p); p = nullptr; cap = 0; }
 };
+// workspace of the site terms / heat current (uf3_flux.h): one per context for the stand-alone entries, one per MD state
+struct FluxWork {
+    Buf frames, offsets, spec, cnt, ent, coeff, flags, u, jp, io;
+    int cap = 0;                        // list capacity per atom (an MD state keeps it from sample to sample)
+    void release() { for (Buf *b : {&frames, &offsets, &spec, &cnt, &ent, &coeff, &flags, &u, &jp, &io}) b->release(); cap = 0; }
+};
 #define UF3_PIN_LIMIT (512 * 1024)   // bytes: larger transfers go straight from / to the caller's memory
 #define UF3_BAR_LIMIT (128 * 1024)   // bytes: largest block the host stores into device memory itself (beyond it the copy engine is quicker)
 
@@ -93,6 +100,7 @@ struct uf3_ctx {
         hist_edges, hist_noise,         // uf3_pair_histogram[_dev]: the caller's bin edges and supercell noise
         hs_spec, hs_cnt, hs_ent, hs_coeff, hs_part, hs_io,   // uf3_hessian[_dev]: its own lists, model copy, Born shares, host staging
         ph_ws, ph_part, ph_io;          // uf3_phonon_*: sorted terms and small inputs | smearing partials | host staging
+    FluxWork fx;                        // uf3_site_terms / uf3_heat_flux
     std::vector<char> ph_stage;         // host image of ph_ws (kept alive behind the asynchronous copy)
     int n3_cap = 0, cand_cap = 0;
     size_t bin_cnt_clean = 0;        // ints of bin_cnt known to be zero (k_bin_fill leaves the counts it used at zero)
@@ -329,6 +337,7 @@ extern "C" void uf3_ctx_destroy(uf3_ctx *c) {
                   &c->ph_ws, &c->ph_part, &c->ph_io};
     for (Buf *b : all) b->release();
     for (Buf &b : c->gram_tiles) b.release();
+    c->fx.release();
     if (c->comm) uf3_comm_destroy(c);
     { Buf *mdb[] = {&c->md.ent, &c->md.cnt, &c->md.pos_ref, &c->md.geo, &c->md.frame_of, &c->md.spec, &c->md.inbox, &c->md.surv, &c->md.mark}; for (Buf *b : mdb) b->release(); }
     c->stage_bar.release();
@@ -3616,6 +3625,9 @@ struct uf3_md {
     bool npt_ready = false;
     bool virials_valid = false;                 // virials describe pos and cells (with forces_valid)
     bool g_valid = false;                       // the pistons' g_close belongs to the current state
+    // heat-current samples (uf3_md_run_flux, uf3_flux.h): the masses as given, the lists' workspace, the records of a run
+    Buf mass, flux_ring;
+    FluxWork fx;
 };
 
 extern "C" void uf3_md_destroy(uf3_md *md) {
@@ -3626,6 +3638,7 @@ extern "C" void uf3_md_destroy(uf3_md *md) {
                    &md->blk_frame, &md->blk_lo, &md->blk_n, &md->frame_blk, &md->frame_of, &md->npt_st, &md->npt_coef, &md->npt_partial,
                    &md->cells_dev})
         p->release();
+    md->mass.release(); md->flux_ring.release(); md->fx.release();
     delete md;
 }
 
@@ -3680,9 +3693,10 @@ extern "C" int uf3_md_create(uf3_basis *b, const uf3_frames *fr, const double *p
     const size_t n3 = 3 * (size_t)n;
     if (md->pos.ensure(8 * n3) || md->vel.ensure(8 * n3) || md->frc.ensure(8 * n3) || md->inv_m.ensure(8 * (size_t)n) ||
         md->z.ensure(4 * (size_t)n) || md->offsets_dev.ensure(8 * (size_t)(nf + 1)) || md->energies.ensure(8 * (size_t)nf) ||
-        md->virials.ensure(48 * (size_t)nf))
+        md->virials.ensure(48 * (size_t)nf) || md->mass.ensure(8 * (size_t)n))
         return bail(fail(c, UF3_ENOMEM, "uf3_md_create: out of device memory"));
     if (hipMemcpyAsync(md->inv_m.p, inv.data(), 8 * (size_t)n, hipMemcpyHostToDevice, c->stream) ||
+        hipMemcpyAsync(md->mass.p, masses, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream) ||
         hipMemcpyAsync(md->z.p, z, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream) ||
         hipMemcpyAsync(md->offsets_dev.p, md->offsets.data(), 8 * (size_t)(nf + 1), hipMemcpyHostToDevice, c->stream) ||
         hipMemsetAsync(md->vel.p, 0, 8 * n3, c->stream))
@@ -3764,11 +3778,32 @@ static int md_launch(uf3_md *md, MdStepArgs &A, bool langevin, int64_t record, i
     return UF3_OK;
 }
 
+struct FluxArgs;
+static int flux_prepare(uf3_basis *b, const uf3_frames *fr, FluxWork &W, const int32_t *d_z, const double *c1, const double *c2,
+                        const double *c3, const char *who, FluxArgs &F);
+static int flux_sample(uf3_ctx *c, FluxWork &W, FluxArgs &F, bool headroom, const char *who);
+
+// one heat-current record of the closed state (velocities at integer time, the positions the forces belong to)
+static int md_flux_sample(uf3_md *md, FluxArgs &F, int64_t record) {
+    F.flux = md->flux_ring.as<double>() + (size_t)record * md->n_frames * 6;
+    return flux_sample(md->c, md->fx, F, true, "uf3_md_run_flux");
+}
+
+// flux_every > 0 (uf3_md_run_flux): the launch that closes a sampled step does not open the next one; the sample sits
+// between the two launches.  That is the split a run boundary makes anyway: the trajectory's bits do not change.
 static int md_run(uf3_md *md, int64_t n_steps, double dt, double T, double gamma, uint64_t seed, int64_t every, bool stress,
-                  double *thermo) {
+                  double *thermo, int64_t flux_every = 0, double *flux = nullptr) {
     uf3_ctx *c = md->c;
     const int width = stress ? 14 : 2;
     const int64_t n_rec = every ? n_steps / every : 0;
+    const int64_t n_flux = flux_every ? n_steps / flux_every : 0;
+    FluxArgs F;
+    if (n_flux) {
+        HIPCHK(c, md->flux_ring.ensure(48 * (size_t)n_flux * md->n_frames));
+        int rc = flux_prepare(md->b, &md->fr, md->fx, md->z.as<int32_t>(), md->c1.data(), md->c2.data(), md->c3.data(), "uf3_md_run_flux", F);
+        if (rc) return rc;
+        F.pos = md->pos.as<double>(); F.vel = md->vel.as<double>(); F.mass = md->mass.as<double>(); F.w = nullptr;
+    }
     if (n_rec) {
         HIPCHK(c, md->ring.ensure(8 * (size_t)n_rec * md->n_frames * width));
         HIPCHK(c, md->kin.ensure(56 * (size_t)md->natoms));
@@ -3787,7 +3822,20 @@ static int md_run(uf3_md *md, int64_t n_steps, double dt, double T, double gamma
         // closes step k - 1 of the run (its record, if due) and opens step k
         A.step = (unsigned long long)(t0 + k - 1); A.close = k > 1; A.open = 1;
         const bool rec = k > 1 && every && (k - 1) % every == 0;
-        int rc = md_launch(md, A, langevin, rec ? (k - 1) / every - 1 : -1, width);
+        int rc;
+        if (n_flux && k > 1 && (k - 1) % flux_every == 0) {
+            A.open = 0;
+            rc = md_launch(md, A, langevin, rec ? (k - 1) / every - 1 : -1, width);
+            // step k - 1 is closed and nothing has moved since its forces: an error below leaves the state of a run that
+            // ended here, which a later run goes on from
+            md->step = t0 + k - 1;
+            if (rc) return rc;
+            rc = md_flux_sample(md, F, (k - 1) / flux_every - 1);
+            if (rc) return rc;
+            A.close = 0; A.open = 1;
+            rc = md_launch(md, A, langevin, -1, width);
+        } else
+            rc = md_launch(md, A, langevin, rec ? (k - 1) / every - 1 : -1, width);
         md->forces_valid = false;
         md->step = t0 + k - 1;
         if (rc) return rc;
@@ -3800,15 +3848,38 @@ static int md_run(uf3_md *md, int64_t n_steps, double dt, double T, double gamma
     int rc = md_launch(md, A, langevin, rec ? n_steps / every - 1 : -1, width);
     if (rc) return rc;
     md->step = t0 + n_steps;
+    if (n_flux && n_steps % flux_every == 0) {
+        rc = md_flux_sample(md, F, n_steps / flux_every - 1);
+        if (rc) return rc;
+    }
+    if (n_flux) HIPCHK(c, hipMemcpyAsync(flux, md->flux_ring.p, 48 * (size_t)n_flux * md->n_frames, hipMemcpyDeviceToHost, c->stream));
     if (n_rec) HIPCHK(c, hipMemcpyAsync(thermo, md->ring.p, 8 * (size_t)n_rec * md->n_frames * width, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return UF3_OK;
 }
 
+static int md_run_entry(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
+                        double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t flux_every, double *flux);
+
 extern "C" int uf3_md_run(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
                           double skin, int64_t thermo_every, int with_stress, double *thermo) {
+    return md_run_entry(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, skin, thermo_every, with_stress, thermo, 0, nullptr);
+}
+
+extern "C" int uf3_md_run_flux(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
+                               double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t flux_every, double *flux) {
+    return md_run_entry(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, skin, thermo_every, with_stress, thermo, flux_every, flux);
+}
+
+static int md_run_entry(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
+                        double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t flux_every, double *flux) {
     if (!md) return fail(nullptr, UF3_EINVAL, "null md");
     uf3_ctx *c = md->c;
+    if (flux_every < 0) return fail(c, UF3_EINVAL, "uf3_md_run_flux: flux_every must be >= 0");
+    const int64_t n_flux = flux_every ? n_steps / flux_every : 0;
+    if ((n_flux > 0) != (flux != nullptr))
+        return fail(c, UF3_EINVAL, n_flux ? "uf3_md_run_flux: flux records are due but the flux buffer is NULL"
+                                          : "uf3_md_run_flux: a flux buffer was given but no record is due");
     if (n_steps < 0) return fail(c, UF3_EINVAL, "uf3_md_run: n_steps must be >= 0");
     if (!(dt_fs > 0.0) || !std::isfinite(dt_fs)) return fail(c, UF3_EINVAL, "uf3_md_run: dt must be positive and finite");
     if (!(temperature_K >= 0.0) || !std::isfinite(temperature_K)) return fail(c, UF3_EINVAL, "uf3_md_run: temperature must be finite and >= 0");
@@ -3826,7 +3897,7 @@ extern "C" int uf3_md_run(uf3_md *md, int64_t n_steps, double dt_fs, double temp
     const double caller_skin = c->md.skin;
     int rc = uf3_ctx_md_skin(c, skin);
     if (rc) return rc;
-    rc = md_run(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, thermo_every, with_stress != 0, thermo);
+    rc = md_run(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, thermo_every, with_stress != 0, thermo, flux_every, flux);
     if (rc) {
         const std::string msg = c->err;
         uf3_ctx_md_skin(c, caller_skin);
@@ -4990,33 +5061,16 @@ extern "C" int uf3_mc_get_state(uf3_mc *m, int32_t *z, double *energies, int64_t
 }
 
 // ------------------------------------------------------------------------------ analytic Hessian (uf3_hessian.h)
-static int hessian_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, const double *c1,
-                        const double *c2, const double *c3, int64_t row_begin, int64_t row_end, double *d_hess, double *d_mixed,
-                        double *d_born) {
-    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
-    uf3_ctx *c = b->ctx;
-    if (!fr || fr->n_frames != 1 || !fr->atom_offsets || !fr->cells || !fr->pbc)
-        return fail(c, UF3_EINVAL, "uf3_hessian: exactly one frame");
-    if (!d_pos || !d_z || !c1 || !d_hess) return fail(c, UF3_EINVAL, "uf3_hessian: null argument");
-    if ((b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, "uf3_hessian: missing coefficients");
-    const int64_t N = fr->atom_offsets[1] - fr->atom_offsets[0];
-    if (fr->atom_offsets[0] != 0 || N < 1 || N > (int64_t)1 << 30) return fail(c, UF3_EINVAL, "uf3_hessian: bad atom count");
-    if (row_begin < 0 || row_end > N || row_begin >= row_end)
-        return fail(c, UF3_EINVAL, "uf3_hessian: row span [" + std::to_string(row_begin) + ", " + std::to_string(row_end) +
-                                       ") empty or outside the frame's " + std::to_string(N) + " atoms");
-    if (d_born && (row_begin != 0 || row_end != N))
-        return fail(c, UF3_EINVAL, "uf3_hessian: born needs the whole frame's rows");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const int n = (int)N;
-    HessArgs A;
-    A.B = b->dev; A.pos = d_pos; A.natoms = n;
+// the list geometry of one frame (k_hess_lists; shared with the batched lists of uf3_flux.h): lattice rows (zero on a
+// non-periodic axis), the inverse of the completed cell, and the images tried per side around the nearest one
+static int hess_geometry(uf3_ctx *c, const uf3_basis *b, const double *cells, const uint8_t *pbc, const char *who, double *cell_out,
+                         double *inv_out, int *per_out, int *nimg_out) {
     // cell: the periodic rows as given; a non-periodic axis gets a unit vector orthogonal to what is there already, so that the
     // fractional coordinates along the periodic axes bound the image distance whatever the other rows hold
     double cell[9], comp[9];
-    for (int k = 0; k < 9; k++) cell[k] = fr->cells[k];
+    for (int k = 0; k < 9; k++) cell[k] = cells[k];
     int per[3];
-    for (int k = 0; k < 3; k++) per[k] = fr->pbc[k] ? 1 : 0;
+    for (int k = 0; k < 3; k++) per[k] = pbc[k] ? 1 : 0;
     {
         std::vector<std::array<double, 3>> basis_v;
         for (int k = 0; k < 3; k++) if (per[k]) basis_v.push_back({cell[3 * k], cell[3 * k + 1], cell[3 * k + 2]});
@@ -5043,16 +5097,42 @@ static int hessian_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos,
         }
     }
     double inv[9];
-    if (!invert3(comp, inv)) return fail(c, UF3_EINVAL, "uf3_hessian: singular cell");
+    if (!invert3(comp, inv)) return fail(c, UF3_EINVAL, std::string(who) + ": singular cell");
     const double reach = std::max(b->host.rmax2, b->host.T > 0 ? b->host.rmax3 : 0.0);
-    for (int k = 0; k < 9; k++) { A.cell[k] = per[k / 3] ? cell[k] : 0.0; A.inv[k] = inv[k]; }
+    for (int k = 0; k < 9; k++) { cell_out[k] = per[k / 3] ? cell[k] : 0.0; inv_out[k] = inv[k]; }
     for (int k = 0; k < 3; k++) {
-        A.per[k] = per[k];
+        per_out[k] = per[k];
         // |image distance| >= h_k |f_k + s_k| with h_k = 1 / |column k of inv|: |s_k| <= reach / h_k + 1/2 around the nearest image
         const double h = 1.0 / std::sqrt(inv[k] * inv[k] + inv[3 + k] * inv[3 + k] + inv[6 + k] * inv[6 + k]);
-        A.nimg[k] = per[k] ? (int)std::floor(reach / h + 0.5 + 1e-6) : 0;
-        if (A.nimg[k] > 64) return fail(c, UF3_EINVAL, "uf3_hessian: cell far thinner than the cut-off");
+        nimg_out[k] = per[k] ? (int)std::floor(reach / h + 0.5 + 1e-6) : 0;
+        if (nimg_out[k] > 64) return fail(c, UF3_EINVAL, std::string(who) + ": cell far thinner than the cut-off");
     }
+    return UF3_OK;
+}
+
+static int hessian_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, const double *c1,
+                        const double *c2, const double *c3, int64_t row_begin, int64_t row_end, double *d_hess, double *d_mixed,
+                        double *d_born) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    uf3_ctx *c = b->ctx;
+    if (!fr || fr->n_frames != 1 || !fr->atom_offsets || !fr->cells || !fr->pbc)
+        return fail(c, UF3_EINVAL, "uf3_hessian: exactly one frame");
+    if (!d_pos || !d_z || !c1 || !d_hess) return fail(c, UF3_EINVAL, "uf3_hessian: null argument");
+    if ((b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, "uf3_hessian: missing coefficients");
+    const int64_t N = fr->atom_offsets[1] - fr->atom_offsets[0];
+    if (fr->atom_offsets[0] != 0 || N < 1 || N > (int64_t)1 << 30) return fail(c, UF3_EINVAL, "uf3_hessian: bad atom count");
+    if (row_begin < 0 || row_end > N || row_begin >= row_end)
+        return fail(c, UF3_EINVAL, "uf3_hessian: row span [" + std::to_string(row_begin) + ", " + std::to_string(row_end) +
+                                       ") empty or outside the frame's " + std::to_string(N) + " atoms");
+    if (d_born && (row_begin != 0 || row_end != N))
+        return fail(c, UF3_EINVAL, "uf3_hessian: born needs the whole frame's rows");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int n = (int)N;
+    HessArgs A;
+    A.B = b->dev; A.pos = d_pos; A.natoms = n;
+    int rc_geo = hess_geometry(c, b, fr->cells, fr->pbc, "uf3_hessian", A.cell, A.inv, A.per, A.nimg);
+    if (rc_geo) return rc_geo;
     // species
     HIPCHK(c, c->hs_spec.ensure(sizeof(int) * ((size_t)n + 1)));
     int *d_spec = c->hs_spec.as<int>(), *d_bad = d_spec + n;
@@ -5136,6 +5216,197 @@ extern "C" int uf3_hessian(uf3_basis *b, const uf3_frames *fr, const double *pos
     if (born) HIPCHK(c, hipMemcpyAsync(born, d_b, b_b, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     if (c->hs_io.cap > ((size_t)1 << 30)) c->hs_io.release();      // (a large slab's staging is not kept for the context's lifetime)
+    return UF3_OK;
+}
+
+// ------------------------------------------------------------------------------ site terms and the heat current (uf3_flux.h)
+// flux_prepare: what does not change between the samples of one call (frame table, species, the model's copy);
+// flux_sample: lists, k_flux_site_terms, k_flux_frame on device positions (and velocities).
+static int flux_prepare(uf3_basis *b, const uf3_frames *fr, FluxWork &W, const int32_t *d_z, const double *c1, const double *c2,
+                        const double *c3, const char *who, FluxArgs &F) {
+    uf3_ctx *c = b->ctx;
+    const std::string me(who);
+    if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, me + ": bad uf3_frames");
+    if (!d_z || !c1) return fail(c, UF3_EINVAL, me + ": null argument");
+    if ((b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, me + ": missing coefficients");
+    const int nf = fr->n_frames;
+    if (fr->atom_offsets[0] != 0) return fail(c, UF3_EINVAL, me + ": atom_offsets[0] must be 0");
+    for (int f = 0; f < nf; f++)
+        if (fr->atom_offsets[f + 1] <= fr->atom_offsets[f]) return fail(c, UF3_EINVAL, me + ": every frame needs an atom");
+    const int64_t n = fr->atom_offsets[nf];
+    if (n > (int64_t)1 << 30) return fail(c, UF3_EINVAL, me + ": bad atom count");
+    std::vector<FluxFrame> tab((size_t)nf);
+    for (int f = 0; f < nf; f++) {
+        FluxFrame &g = tab[f];
+        int rc = hess_geometry(c, b, fr->cells + 9 * (size_t)f, fr->pbc + 3 * (size_t)f, who, g.cell, g.inv, g.per, g.nimg);
+        if (rc) return rc;
+        g.lo = fr->atom_offsets[f];
+        g.natoms = (int)(fr->atom_offsets[f + 1] - fr->atom_offsets[f]);
+        g.pad = 0;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    HIPCHK(c, W.frames.ensure(sizeof(FluxFrame) * (size_t)nf));
+    HIPCHK(c, W.offsets.ensure(8 * (size_t)(nf + 1)));
+    HIPCHK(c, W.spec.ensure(sizeof(int) * (size_t)n));
+    HIPCHK(c, W.cnt.ensure(sizeof(int) * (size_t)n));
+    HIPCHK(c, W.flags.ensure(sizeof(int) * 4));
+    HIPCHK(c, W.u.ensure(8 * (size_t)n));
+    HIPCHK(c, W.jp.ensure(24 * (size_t)n));
+    const size_t n1 = (size_t)b->host.S, n2 = b->c2_len, n3 = b->c3_len;
+    HIPCHK(c, W.coeff.ensure(8 * (n1 + n2 + n3 + 1)));
+    double *dc = W.coeff.as<double>();
+    // (pageable sources: each copy has left the host buffer when the call returns)
+    HIPCHK(c, hipMemcpyAsync(W.frames.p, tab.data(), sizeof(FluxFrame) * (size_t)nf, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(W.offsets.p, fr->atom_offsets, 8 * (size_t)(nf + 1), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(dc, c1, 8 * n1, hipMemcpyHostToDevice, st));
+    if (n2) HIPCHK(c, hipMemcpyAsync(dc + n1, c2, 8 * n2, hipMemcpyHostToDevice, st));
+    if (n3) HIPCHK(c, hipMemcpyAsync(dc + n1 + n2, c3, 8 * n3, hipMemcpyHostToDevice, st));
+    int *d_flags = W.flags.as<int>();
+    HIPCHK(c, hipMemsetAsync(d_flags, 0, sizeof(int) * 4, st));
+    hipLaunchKernelGGL(k_hess_species, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const BasisDev *)b->dev, d_z, (int)n,
+                       W.spec.as<int>(), d_flags + 2);
+    int bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, d_flags + 2, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (bad) return fail(c, UF3_ESPECIES, me + ": the batch contains an element outside the basis");
+    F = FluxArgs();
+    F.B = b->dev; F.frames = W.frames.as<FluxFrame>(); F.offsets = W.offsets.as<int64_t>(); F.n_frames = nf; F.n = n;
+    F.spec = W.spec.as<int>(); F.cnt = W.cnt.as<int>(); F.flags = d_flags;
+    F.c1 = dc; F.c2 = dc + n1; F.c3 = dc + n1 + n2;
+    F.u = W.u.as<double>(); F.jp = W.jp.as<double>();
+    return UF3_OK;
+}
+
+// F.pos, F.vel (null: no current), F.mass, F.u, F.w (null: no virials), F.flux set by the caller.  headroom: keep the
+// capacity between calls (an MD run: sized at the first sample, grown when a list overflows).
+static int flux_sample(uf3_ctx *c, FluxWork &W, FluxArgs &F, bool headroom, const char *who) {
+    hipStream_t st = c->stream;
+    const std::string me(who);
+    const unsigned n = (unsigned)F.n;
+    for (int attempt = 0; attempt < 3; attempt++) {
+        if (!headroom || W.cap == 0) {
+            F.cap = 0; F.ent = nullptr;
+            hipLaunchKernelGGL(k_flux_lists<false>, dim3(n), dim3(64), 0, st, F);
+            std::vector<int> cnt((size_t)n);
+            int flags[2] = {0, 0};
+            HIPCHK(c, hipMemcpyAsync(cnt.data(), F.cnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipMemcpyAsync(flags, F.flags, sizeof(flags), hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            if (flags[0]) return fail(c, UF3_EINVAL, me + ": atoms lie more than 500 cells apart along a periodic axis: wrap the positions");
+            const int longest = std::max(1, *std::max_element(cnt.begin(), cnt.end()));
+            W.cap = headroom ? longest + longest / 4 + 8 : longest;
+            if (W.cap > 12288) return fail(c, UF3_EINVAL, me + ": more than 12288 neighbours of one atom");
+        }
+        HIPCHK(c, W.ent.ensure(sizeof(HessNbr) * (size_t)n * (size_t)W.cap));
+        F.cap = W.cap; F.ent = W.ent.as<HessNbr>();
+        hipLaunchKernelGGL(k_flux_lists<true>, dim3(n), dim3(64), 0, st, F);
+        const size_t lds = sizeof(int) * (size_t)F.cap;
+        const bool want_w = F.w != nullptr, want_j = F.vel != nullptr;
+        if (want_w && want_j) hipLaunchKernelGGL((k_flux_site_terms<true, true>), dim3(n), dim3(64), lds, st, F);
+        else if (want_w) hipLaunchKernelGGL((k_flux_site_terms<true, false>), dim3(n), dim3(64), lds, st, F);
+        else if (want_j) hipLaunchKernelGGL((k_flux_site_terms<false, true>), dim3(n), dim3(64), lds, st, F);
+        else hipLaunchKernelGGL((k_flux_site_terms<false, false>), dim3(n), dim3(64), lds, st, F);
+        if (want_j) hipLaunchKernelGGL(k_flux_frame, dim3((unsigned)F.n_frames), dim3(UF3_MD_THREADS), 0, st, F);
+        HIPCHK(c, hipGetLastError());
+        if (!headroom) return UF3_OK;           // (sized for these very positions: nothing can overflow)
+        int flags[2] = {0, 0};
+        HIPCHK(c, hipMemcpyAsync(flags, F.flags, sizeof(flags), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (flags[0]) return fail(c, UF3_EINVAL, me + ": atoms lie more than 500 cells apart along a periodic axis: wrap the positions");
+        if (!flags[1]) return UF3_OK;
+        HIPCHK(c, hipMemsetAsync(F.flags, 0, sizeof(int) * 2, st));
+        W.cap = 0;                              // a list was cut: size again from these positions and redo the sample
+    }
+    return fail(c, UF3_EINVAL, me + ": the neighbour lists keep overflowing");
+}
+
+static int site_terms_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const double *d_vel, const int32_t *d_z,
+                           const double *d_mass, const double *c1, const double *c2, const double *c3, double *d_u, double *d_w,
+                           double *d_flux, const char *who) {
+    uf3_ctx *c = b->ctx;
+    if (!d_pos) return fail(c, UF3_EINVAL, std::string(who) + ": null argument");
+    FluxArgs F;
+    int rc = flux_prepare(b, fr, c->fx, d_z, c1, c2, c3, who, F);
+    if (rc) return rc;
+    F.pos = d_pos; F.vel = d_vel; F.mass = d_mass; F.w = d_w; F.flux = d_flux;
+    if (d_u) F.u = d_u;
+    return flux_sample(c, c->fx, F, false, who);
+}
+
+static bool flux_frames_ok(const uf3_frames *fr) {
+    if (!fr || fr->n_frames < 1 || !fr->atom_offsets) return false;
+    return fr->atom_offsets[fr->n_frames] >= 1 && fr->atom_offsets[fr->n_frames] <= (int64_t)1 << 30;
+}
+
+extern "C" int uf3_site_terms_dev(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, const double *c1,
+                                  const double *c2, const double *c3, double *d_site_energies, double *d_site_virials) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    if (!d_site_energies && !d_site_virials) return fail(b->ctx, UF3_EINVAL, "uf3_site_terms: nothing asked for");
+    return site_terms_impl(b, fr, d_pos, nullptr, d_z, nullptr, c1, c2, c3, d_site_energies, d_site_virials, nullptr, "uf3_site_terms");
+}
+
+extern "C" int uf3_site_terms(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1,
+                              const double *c2, const double *c3, double *site_energies, double *site_virials) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    uf3_ctx *c = b->ctx;
+    if (!flux_frames_ok(fr)) return fail(c, UF3_EINVAL, "uf3_site_terms: bad uf3_frames");
+    if (!pos || !z) return fail(c, UF3_EINVAL, "uf3_site_terms: null argument");
+    if (!site_energies && !site_virials) return fail(c, UF3_EINVAL, "uf3_site_terms: nothing asked for");
+    const size_t n = (size_t)fr->atom_offsets[fr->n_frames];
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t b_pos = 24 * n, b_z = (4 * n + 15) / 16 * 16, b_u = 8 * n, b_w = site_virials ? 72 * n : 0;
+    HIPCHK(c, c->fx.io.ensure(b_pos + b_z + b_u + b_w));
+    char *base = c->fx.io.as<char>();
+    double *d_pos = (double *)base, *d_u = (double *)(base + b_pos + b_z), *d_w = site_virials ? (double *)(base + b_pos + b_z + b_u) : nullptr;
+    int32_t *d_z = (int32_t *)(base + b_pos);
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(d_pos, pos, b_pos, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_z, z, 4 * n, hipMemcpyHostToDevice, st));
+    int rc = site_terms_impl(b, fr, d_pos, nullptr, d_z, nullptr, c1, c2, c3, d_u, d_w, nullptr, "uf3_site_terms");
+    if (rc) return rc;
+    if (site_energies) HIPCHK(c, hipMemcpyAsync(site_energies, d_u, b_u, hipMemcpyDeviceToHost, st));
+    if (site_virials) HIPCHK(c, hipMemcpyAsync(site_virials, d_w, b_w, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return UF3_OK;
+}
+
+extern "C" int uf3_heat_flux_dev(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const double *d_vel, const int32_t *d_z,
+                                 const double *d_masses, const double *c1, const double *c2, const double *c3, double *d_flux,
+                                 double *d_site_energies) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    if (!d_vel || !d_masses || !d_flux) return fail(b->ctx, UF3_EINVAL, "uf3_heat_flux: null argument");
+    return site_terms_impl(b, fr, d_pos, d_vel, d_z, d_masses, c1, c2, c3, d_site_energies, nullptr, d_flux, "uf3_heat_flux");
+}
+
+extern "C" int uf3_heat_flux(uf3_basis *b, const uf3_frames *fr, const double *pos, const double *vel, const int32_t *z,
+                             const double *masses, const double *c1, const double *c2, const double *c3, double *flux,
+                             double *site_energies) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    uf3_ctx *c = b->ctx;
+    if (!flux_frames_ok(fr)) return fail(c, UF3_EINVAL, "uf3_heat_flux: bad uf3_frames");
+    if (!pos || !vel || !z || !masses || !flux) return fail(c, UF3_EINVAL, "uf3_heat_flux: null argument");
+    const size_t n = (size_t)fr->atom_offsets[fr->n_frames], nf = (size_t)fr->n_frames;
+    for (size_t i = 0; i < n; i++)
+        if (!(masses[i] > 0.0) || !std::isfinite(masses[i])) return fail(c, UF3_EINVAL, "uf3_heat_flux: masses must be positive and finite");
+    if (!md_finite(vel, 3 * n)) return fail(c, UF3_EINVAL, "uf3_heat_flux: velocities must be finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t b_pos = 24 * n, b_z = (4 * n + 15) / 16 * 16, b_m = 8 * n, b_f = 48 * nf;
+    HIPCHK(c, c->fx.io.ensure(2 * b_pos + b_z + 2 * b_m + b_f));
+    char *base = c->fx.io.as<char>();
+    double *d_pos = (double *)base, *d_vel = (double *)(base + b_pos);
+    int32_t *d_z = (int32_t *)(base + 2 * b_pos);
+    double *d_m = (double *)(base + 2 * b_pos + b_z), *d_u = d_m + n, *d_f = d_u + n;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(d_pos, pos, b_pos, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_vel, vel, b_pos, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_z, z, 4 * n, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_m, masses, b_m, hipMemcpyHostToDevice, st));
+    int rc = site_terms_impl(b, fr, d_pos, d_vel, d_z, d_m, c1, c2, c3, d_u, nullptr, d_f, "uf3_heat_flux");
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(flux, d_f, b_f, hipMemcpyDeviceToHost, st));
+    if (site_energies) HIPCHK(c, hipMemcpyAsync(site_energies, d_u, b_m, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
     return UF3_OK;
 }
 

@@ -229,6 +229,71 @@ class UFCalculator(_Base):
         e = self.evaluate_frames(frames, forces=False)[0]
         return np.array([(e[2 * k] - e[2 * k + 1]) / (2 * d * vol) for k in range(6)])
 
+    # ---- per-atom resolution (uf3_site_terms / uf3_heat_flux) -------------------------------------------
+    def site_terms(self, atoms_list, virials=True):
+        """Site energies and site virials of a batch of frames: (U, W), lists with one array per frame, U[f] [N_f] (eV) and
+        W[f] [N_f, 3, 3] (eV; ``None`` in place of the list when ``virials`` is false).  U_i is the evaluator's own partition of
+        the energy (one-body term, the directed pair terms of i, the triplets with i as the centre): ``U[f].sum()`` is the
+        frame's energy.  W_i[a][b] = sum over the terms of U_i and their neighbour images s of d_s[a] (dU_i/dr_s)[b], d_s from
+        the centre to the image: the frame's sum, symmetrised, is ``evaluate_frames(..., virial=True)``'s dE/d(strain)."""
+        ctx = _lib.get_context(self.device)
+        db = _lib.device_basis(self.bspline_config, ctx)
+        batch = _lib.FrameBatch(list(atoms_list))
+        u = np.empty(batch.n_atoms)
+        w = np.empty((batch.n_atoms, 3, 3)) if virials else None
+        addr = _lib._addr
+        ctx.check(ctx.lib.uf3_site_terms(db.handle, C.byref(batch.struct), addr(batch.pos), addr(batch.z), self._pc[0], self._pc[1],
+                                         self._pc[2], addr(u), addr(w)))
+        off = batch.offsets
+        split = lambda a: [a[off[k]:off[k + 1]] for k in range(batch.n_frames)]     # noqa: E731
+        return split(u), (split(w) if virials else None)
+
+    def get_potential_energies(self, atoms=None):
+        """ASE's per-atom energies [N] (eV): the site energies U_i of ``site_terms``; their sum is ``get_potential_energy``."""
+        return self.site_terms([atoms], virials=False)[0][0]
+
+    def get_stresses(self, atoms=None):
+        """Per-atom stresses [N, 6], eV/A^3, in ``get_stress``'s convention -- Voigt order (xx, yy, zz, yz, xz, xy) and ASE's
+        sign (dE/d(strain) per volume: positive under tension) --, each atom given the volume V / N:
+        ``sym(W_i) / (V / N)`` with the site virials of ``site_terms``, so that their MEAN over the atoms is ``get_stress``
+        (no kinetic part).  The frame needs a cell with a volume."""
+        cell = np.array(atoms.get_cell(), dtype=float).reshape(3, 3)
+        vol = abs(np.linalg.det(cell))
+        if not vol > 0:
+            raise ValueError("get_stresses: the frame's cell has no volume")
+        w = self.site_terms([atoms])[1][0]
+        s = 0.5 * (w + w.transpose(0, 2, 1))
+        voigt = np.stack([s[:, 0, 0], s[:, 1, 1], s[:, 2, 2], s[:, 1, 2], s[:, 0, 2], s[:, 0, 1]], axis=1)
+        return voigt / (vol / len(w))
+
+    def heat_flux(self, atoms_list, velocities, masses=None, site_energies=False):
+        """The heat current of every frame, [n_frames, 2, 3] in eV A / fs: row 0 the convective part
+        sum_i (1/2 m_i v_i^2 + U_i) v_i, row 1 the potential part -sum_i sum_terms sum_s d_s (dU_i/dr_s . v_s) (images carry
+        their parent's velocity); J is their sum.  ``velocities`` [sum N, 3] in A / fs, frames concatenated; ``masses`` as
+        ``md.resolve_masses`` takes them (amu).  With ``site_energies`` also the U_i [sum N].  A velocities array of another
+        length, like a mass that is not positive and finite, is refused with the library's error (``UF3Error``, UF3_EINVAL)
+        before anything is launched."""
+        from .md import resolve_masses
+        frames = list(atoms_list)
+        ctx = _lib.get_context(self.device)
+        db = _lib.device_basis(self.bspline_config, ctx)
+        batch = _lib.FrameBatch(frames)
+        v = np.ascontiguousarray(np.asarray(velocities, dtype=float))
+        if v.shape != (batch.n_atoms, 3):
+            raise _lib.UF3Error(1, f"uf3_heat_flux: velocities must be [{batch.n_atoms}, 3], got {list(v.shape)}")
+        if masses is not None and not isinstance(masses, dict):
+            m = np.ascontiguousarray(np.asarray(masses, dtype=float).reshape(-1))
+            if m.shape != (batch.n_atoms,):
+                raise _lib.UF3Error(1, f"uf3_heat_flux: {m.size} masses for {batch.n_atoms} atoms")
+        else:
+            m = resolve_masses(frames, masses)
+        flux = np.empty((batch.n_frames, 2, 3))
+        u = np.empty(batch.n_atoms) if site_energies else None
+        addr = _lib._addr
+        ctx.check(ctx.lib.uf3_heat_flux(db.handle, C.byref(batch.struct), addr(batch.pos), addr(v), addr(batch.z), addr(m),
+                                        self._pc[0], self._pc[1], self._pc[2], addr(flux), addr(u)))
+        return (flux, u) if site_energies else flux
+
     def relax_fmax(self, geom, fmax=0.05, relax_cell=True, verbose=False, timeout=60.0, max_steps=2000, dt=0.1):
         """
         Minimise the maximum force (reference: calculator.py:406-436, which drives ASE's BFGSLineSearch on an

@@ -19,6 +19,12 @@ the device and ``dyn.cells`` / ``dyn.volumes`` follow them.
     npt = MolecularDynamics(calc, atoms_list, 1.0, masses=..., temperature_K=300, friction_per_fs=0.01, pressure_eV_A3=0.0,
                             barostat_time_fs=500.0, barostat_friction_per_fs=0.002)
 
+Heat current: ``run(n, flux_every=k)`` samples J = J_conv + J_pot of every frame on the device after
+every k-th step; ``heat_flux_autocorrelation`` and ``green_kubo`` turn the series into a thermal conductivity.
+
+    rec = md.run(200000, flux_every=10)
+    kappa = green_kubo(rec['heat_flux'][:, 0], 10 * md.timestep_fs, md.volumes[0], 300.0, max_lag=2000)
+
 Each ``run`` starts with one neighbour-list build (it sets the context's skin for its own duration and puts the caller's
 back).  A basis without 3-body terms never takes the evaluator's MD route and rebuilds its lists on every step: correct,
 only slower.
@@ -36,6 +42,44 @@ ACC = 0.009648533215665327       # eV / (Angstrom amu) -> Angstrom / fs^2
 KE_UNIT = 103.64269652680505     # amu Angstrom^2 / fs^2 -> eV
 KB = 8.617333262e-5              # eV / K
 ASE_TIME_FS = 10.180505          # one ASE time unit in fs (sqrt(KE_UNIT)): ASE velocities / ASE_TIME_FS = Angstrom / fs
+
+
+EV_PER_A_FS_K_TO_W_PER_M_K = 1.602176634e-19 / (1e-10 * 1e-15)       # eV / (Angstrom fs K) -> W / (m K)
+
+
+def heat_flux_autocorrelation(J, max_lag):
+    """<J(0) . J(t)> of a series J [n, ..., 3] sampled at equal spacing, lags 0 .. ``max_lag``: [max_lag + 1, ...].
+    C(k) = 1 / (n - k) sum_t J(t) . J(t + k): the unbiased normalisation, and the mean is NOT subtracted (the heat current
+    of an equilibrium run has zero mean; removing a sample mean would bias the Green-Kubo integral).  Computed through a
+    zero-padded FFT (NumPy, on the host), which gives the same sums as the direct double loop."""
+    J = np.asarray(J, dtype=float)
+    if J.ndim < 2 or J.shape[-1] != 3:
+        raise ValueError(f"heat_flux_autocorrelation: J must be [n, ..., 3], got {list(J.shape)}")
+    n = J.shape[0]
+    max_lag = _check_int("max_lag", max_lag, 0, max(n - 1, 0))
+    size = 1
+    while size < 2 * n:
+        size *= 2
+    spec = np.fft.rfft(J, n=size, axis=0)
+    corr = np.fft.irfft(spec * np.conj(spec), n=size, axis=0)[:max_lag + 1].sum(axis=-1)
+    norm = (n - np.arange(max_lag + 1)).astype(float)
+    return corr / norm.reshape((-1,) + (1,) * (corr.ndim - 1))
+
+
+def green_kubo(J, timestep_fs, volume_A3, temperature_K, max_lag):
+    """Running Green-Kubo integral kappa(tau) = 1 / (3 V k_B T^2) int_0^tau <J(0) . J(t)> dt in W / (m K), [max_lag + 1, ...]
+    for tau = 0, dt, ..., max_lag dt (trapezoidal rule).  ``J`` [n, ..., 3] in eV A / fs (``run``'s ``heat_flux`` of one
+    frame), ``timestep_fs`` the spacing of the SAMPLES (``flux_every`` times the integrator's step), ``volume_A3`` in A^3,
+    ``temperature_K`` in K.  Units: (eV A / fs)^2 fs / (A^3 (eV / K) K^2) = eV / (A fs K), times
+    1.602176634e-19 J/eV / (1e-10 m/A * 1e-15 s/fs) = 1.602176634e6 gives W / (m K).  The autocorrelation is
+    ``heat_flux_autocorrelation``'s (unbiased, mean not subtracted)."""
+    dt = _check_real("timestep_fs", timestep_fs, strict=True)
+    vol = _check_real("volume_A3", volume_A3, strict=True)
+    temp = _check_real("temperature_K", temperature_K, strict=True)
+    corr = heat_flux_autocorrelation(J, max_lag)
+    integral = np.zeros_like(corr)
+    integral[1:] = np.cumsum(0.5 * (corr[1:] + corr[:-1]), axis=0) * dt
+    return integral / (3.0 * vol * KB * temp * temp) * EV_PER_A_FS_K_TO_W_PER_M_K
 
 
 def kinetic_energy(velocities, masses):
@@ -341,12 +385,20 @@ class MolecularDynamics:
         s = self.seed if seed is None else _check_int("seed", seed, 0, (1 << 64) - 1)
         self.ctx.check(self.ctx.lib.uf3_md_init_velocities(self._live(), t, s, int(bool(exact))))
 
-    def run(self, n_steps, thermo_every=0, stress=False):
+    def run(self, n_steps, thermo_every=0, stress=False, flux_every=0):
         """``n_steps`` steps (Langevin when ``friction_per_fs`` > 0, else NVE; at a pressure NPT / NPH).  Returns the thermo
         records of every ``thermo_every``-th step (see ``thermo_records``; empty arrays when ``thermo_every`` is 0).  At a
-        pressure the records always carry stress and pressure (of that step's volume), volume, cell_scale and conserved."""
+        pressure the records always carry stress and pressure (of that step's volume), volume, cell_scale and conserved.
+        ``flux_every`` > 0: the heat current of every frame after every ``flux_every``-th step, sampled on the device from the
+        closed state (``uf3_md_run_flux``): ``heat_flux_convective``, ``heat_flux_potential`` and their sum ``heat_flux``
+        [n_records, n_frames, 3] in eV A / fs, and ``flux_step``.  The trajectory and the thermo records do not depend on it.
+        Not at a pressure: that raises ``UF3Error`` (UF3_EINVAL)."""
         n_steps = _check_int("n_steps", n_steps)
         every = _check_int("thermo_every", thermo_every)
+        flux_every = _check_int("flux_every", flux_every)
+        if flux_every and getattr(self, "pressure_eV_A3", None) is not None:
+            raise _lib.UF3Error(1, "uf3_md_run_flux: the heat current is sampled at constant volume only (flux_every with "
+                                   "pressure_eV_A3)")
         dt = _check_real("timestep_fs", self.timestep_fs, strict=True)
         temp = _check_real("temperature_K", self.temperature_K)
         gamma = _check_real("friction_per_fs", self.friction_per_fs)
@@ -367,6 +419,17 @@ class MolecularDynamics:
             return npt_records(raw, self.n_atoms, first, max(every, 1))
         width = 14 if stress else 2
         raw = np.zeros((n_rec, self._batch.n_frames, width))
+        if flux_every:
+            n_flux = n_steps // flux_every
+            fl = np.zeros((n_flux, self._batch.n_frames, 2, 3))
+            self.ctx.check(self.ctx.lib.uf3_md_run_flux(handle, n_steps, dt, temp, gamma, seed, skin, every, int(bool(stress)),
+                                                        _lib._p(raw) if n_rec else None, flux_every, _lib._p(fl) if n_flux else None))
+            out = thermo_records(raw, self.n_atoms, self.volumes, first, max(every, 1), stress)
+            out["heat_flux_convective"] = fl[:, :, 0].copy()
+            out["heat_flux_potential"] = fl[:, :, 1].copy()
+            out["heat_flux"] = fl[:, :, 0] + fl[:, :, 1]
+            out["flux_step"] = first + flux_every * np.arange(1, n_flux + 1, dtype=np.int64)
+            return out
         self.ctx.check(self.ctx.lib.uf3_md_run(handle, n_steps, dt, temp, gamma, seed, skin, every, int(bool(stress)),
                                                _lib._p(raw) if n_rec else None))
         return thermo_records(raw, self.n_atoms, self.volumes, first, max(every, 1), stress)
