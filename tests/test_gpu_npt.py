@@ -42,6 +42,9 @@ def _w128(seed):
 def _batches():
     # (frames of different size in one batch; all periodic: a cluster cannot be run at a pressure)
     return {"w_batch": (_unary, lambda: [_w128(1), synthetic.lattice_frame("bcc", (3, 3, 3), 3.165, [74], seed=7), _w128(2)]),
+            # 54 | 300 | 128 atoms: the middle frame spans two chunks of the chunk table (256 + 44) at non-zero offsets
+            "w300_two_chunks": (_unary, lambda: [synthetic.lattice_frame("bcc", (3, 3, 3), 3.165, [74], seed=7),
+                                                 synthetic.lattice_frame("bcc", (5, 5, 6), 3.165, [74], seed=17), _w128(2)]),
             "mow54": (_mow, lambda: [synthetic.lattice_frame("bcc", (3, 3, 3), 3.165, [42, 74], seed=84)])}
 
 
@@ -91,12 +94,12 @@ def _parity(name, n_steps, temperature_K, friction, p0, tau, gamma_p=0.0, t_pist
     return sr, builds
 
 
-@pytest.mark.parametrize("name", ["w_batch", "mow54"])
+@pytest.mark.parametrize("name", ["w_batch", "w300_two_chunks", "mow54"])
 def test_nph_parity(name):
     _parity(name, 30, 300.0, 0.0, 0.02, 1000.0)
 
 
-@pytest.mark.parametrize("name", ["w_batch", "mow54"])
+@pytest.mark.parametrize("name", ["w_batch", "w300_two_chunks", "mow54"])
 def test_npt_langevin_piston_parity(name):
     _parity(name, 30, 300.0, 0.05, 0.02, 1000.0, gamma_p=0.02)
 

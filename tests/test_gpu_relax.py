@@ -56,8 +56,14 @@ def _slab():
     return Atoms(numbers=a.get_atomic_numbers(), positions=a.get_positions(), cell=a.get_cell(), pbc=[True, True, False])
 
 
+def _w300():
+    # 300 atoms: two chunks of the drivers' chunk table (256 + 44), the second partly filled
+    return synthetic.lattice_frame("bcc", (5, 5, 6), A0_W, [74], seed=11, rattle=0.05, strain=0.0)
+
+
 def _batches():
     return {"w_vacancy_cluster": (_unary, lambda: [_vacancy(3), _cluster()]),
+            "w300_two_chunks": (_unary, lambda: [_cluster(), _w300(), _vacancy(8, reps=(3, 3, 3))]),
             "mow54_slab": (_mow, lambda: [_mow54(), _slab()]),
             "nexe_2body": (_binary, lambda: [load_case("case_nexe32")[2]])}
 
@@ -79,7 +85,7 @@ STATUS = {R.RUNNING: "running", R.CONVERGED: "converged", R.NONFINITE: "nonfinit
 
 
 @pytest.mark.parametrize("relax_cell", [False, True], ids=["positions", "cell"])
-@pytest.mark.parametrize("name", ["w_vacancy_cluster", "mow54_slab", "nexe_2body"])
+@pytest.mark.parametrize("name", ["w_vacancy_cluster", "w300_two_chunks", "mow54_slab", "nexe_2body"])
 def test_parity_with_the_restatement(name, relax_cell):
     make_calc, make_frames = _batches()[name]
     calc, frames = make_calc(), make_frames()

@@ -3602,50 +3602,162 @@ extern "C" int uf3_direction_cosines(uf3_ctx *c, const double *sup_pos, int64_t 
     return UF3_OK;
 }
 
-// ------------------------------------------------------------------------------ molecular dynamics (uf3_md_*, uf3_md.h)
-// A library-owned state: positions (unwrapped), velocities, forces, inverse masses and species in HBM, stepped by k_md_step
-// between calls of the evaluator (eval_impl, unchanged).  Between two launches the velocities are at integer time t and the
-// forces are F(t): a launch closes step t with a half-kick and opens step t + 1 (half-kick, drift; BAOAB's A-O-A with friction).
-struct uf3_md {
+// ------------------------------------------------------------------------------ what the library-owned drivers share
+// (uf3_md, uf3_relax, uf3_neb and uf3_mc below: a batch with its model and its buffers, stepped between calls of eval_impl)
+struct DevBuf : Buf {                           // a buffer that a driver owns: freed with its owner
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+};
+
+struct Batch {
     uf3_basis *b = nullptr;
     uf3_ctx *c = nullptr;
     int32_t n_frames = 0;
     int64_t natoms = 0;
     std::vector<int64_t> offsets;
-    std::vector<double> cells;
+    std::vector<double> cells;                  // the current cells (host: what eval_impl reads)
     std::vector<uint8_t> pbc;
     uf3_frames fr{};
     std::vector<double> c1, c2, c3;             // the model (host copies: eval_impl takes host coefficients)
-    Buf pos, vel, frc, inv_m, z, offsets_dev, energies, virials, kin, ring;
-    int64_t step = 0;                           // absolute step counter (feeds the random numbers)
-    bool forces_valid = false;                  // frc / energies describe pos
-    // constant-pressure runs (uf3_md_run_npt, uf3_npt.h): chunk table, pistons, the current cells on the device
-    Buf blk_frame, blk_lo, blk_n, frame_blk, frame_of, npt_st, npt_coef, npt_partial, cells_dev;
-    int n_blocks = 0;
-    bool npt_ready = false;
-    bool virials_valid = false;                 // virials describe pos and cells (with forces_valid)
-    bool g_valid = false;                       // the pistons' g_close belongs to the current state
-    // heat-current samples (uf3_md_run_flux, uf3_flux.h): the masses as given, the lists' workspace, the records of a run
-    Buf mass, flux_ring;
-    FluxWork fx;
+    DevBuf pos, z, energies, offsets_dev;
 };
-
-extern "C" void uf3_md_destroy(uf3_md *md) {
-    if (!md) return;
-    hipSetDevice(md->c->device);
-    hipStreamSynchronize(md->c->stream);
-    for (Buf *p : {&md->pos, &md->vel, &md->frc, &md->inv_m, &md->z, &md->offsets_dev, &md->energies, &md->virials, &md->kin, &md->ring,
-                   &md->blk_frame, &md->blk_lo, &md->blk_n, &md->frame_blk, &md->frame_of, &md->npt_st, &md->npt_coef, &md->npt_partial,
-                   &md->cells_dev})
-        p->release();
-    md->mass.release(); md->flux_ring.release(); md->fx.release();
-    delete md;
-}
 
 static bool md_finite(const double *a, size_t n) {
     for (size_t i = 0; i < n; i++) if (!std::isfinite(a[i])) return false;
     return true;
 }
+
+// what every *_create checks of its batch; *n: the atoms of the batch
+static int batch_check(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1, const double *c2,
+                       const double *c3, const void *out, const std::string &who, int64_t *n) {
+    if (!b) return fail(nullptr, UF3_EINVAL, who + ": basis is NULL");
+    uf3_ctx *c = b->ctx;
+    if (!out) return fail(c, UF3_EINVAL, who + ": out is NULL");
+    if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, who + ": bad uf3_frames");
+    if (!pos) return fail(c, UF3_EINVAL, who + ": pos is NULL");
+    if (!z) return fail(c, UF3_EINVAL, who + ": z is NULL");
+    if (!c1 || (b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, who + ": missing coefficients (c1 / c2 / c3)");
+    const int nf = fr->n_frames;
+    if (fr->atom_offsets[0] != 0) return fail(c, UF3_EINVAL, who + ": atom_offsets[0] must be 0");
+    for (int f = 0; f < nf; f++)
+        if (fr->atom_offsets[f + 1] <= fr->atom_offsets[f]) return fail(c, UF3_EINVAL, who + ": every frame needs an atom");
+    *n = fr->atom_offsets[nf];
+    if (*n >= (1LL << 28)) return fail(c, UF3_EINVAL, who + ": batch must hold 1 .. 2^28 atoms");
+    if (!md_finite(pos, 3 * (size_t)*n)) return fail(c, UF3_EINVAL, who + ": pos must be finite");
+    if (!md_finite(fr->cells, 9 * (size_t)nf)) return fail(c, UF3_EINVAL, who + ": cells must be finite");
+    return UF3_OK;
+}
+
+// the host copies of a checked batch (c2 / c3 followed by coeff_pad zeros), the four common buffers and their uploads, queued on
+// the stream: the caller's own uploads follow, then one wait.  pos == nullptr: the caller uploads the positions itself
+static int batch_init(Batch &B, uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1,
+                      const double *c2, const double *c3, size_t coeff_pad, const std::string &who) {
+    uf3_ctx *c = b->ctx;
+    const int nf = fr->n_frames;
+    const size_t n = (size_t)fr->atom_offsets[nf];
+    B.b = b; B.c = c; B.n_frames = nf; B.natoms = (int64_t)n;
+    B.offsets.assign(fr->atom_offsets, fr->atom_offsets + nf + 1);
+    B.cells.assign(fr->cells, fr->cells + 9 * (size_t)nf);
+    B.pbc.assign(fr->pbc, fr->pbc + 3 * (size_t)nf);
+    B.fr.n_frames = nf; B.fr.atom_offsets = B.offsets.data(); B.fr.cells = B.cells.data(); B.fr.pbc = B.pbc.data();
+    B.c1.assign(c1, c1 + b->host.S);
+    B.c2.assign(c2 ? c2 : c1, (c2 ? c2 : c1) + b->c2_len); B.c2.resize(b->c2_len + coeff_pad, 0.0);
+    B.c3.assign(c3 ? c3 : c1, (c3 ? c3 : c1) + b->c3_len); B.c3.resize(b->c3_len + coeff_pad, 0.0);
+    if (B.pos.ensure(24 * n) || B.z.ensure(4 * n) || B.energies.ensure(8 * (size_t)nf) || B.offsets_dev.ensure(8 * (size_t)(nf + 1)))
+        return fail(c, UF3_ENOMEM, who + ": out of device memory");
+    hipStream_t s = c->stream;
+    if ((pos && hipMemcpyAsync(B.pos.p, pos, 24 * n, hipMemcpyHostToDevice, s)) || hipMemcpyAsync(B.z.p, z, 4 * n, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(B.offsets_dev.p, B.offsets.data(), 8 * (size_t)(nf + 1), hipMemcpyHostToDevice, s))
+        return fail(c, UF3_EHIP, who + ": upload failed");
+    return UF3_OK;
+}
+
+// the evaluator on the batch's positions: energies, and forces / strain derivatives where asked for
+static int batch_eval(Batch &B, double *forces, double *virials) {
+    return eval_impl(B.b, &B.fr, B.pos.as<double>(), B.z.as<int32_t>(), B.c1.data(), B.c2.data(), B.c3.data(), B.energies.as<double>(),
+                     forces, virials);
+}
+
+// chunks of <= width atoms from each frame's first atom (a chunk never straddles frames): the workgroups of the drivers'
+// partial kernels, and each frame's chunks for the kernel that sums them
+struct ChunkTable {
+    DevBuf blk_frame, blk_lo, blk_n;            // [n_blocks]: the chunk's frame, its first atom, its atoms
+    DevBuf frame_blk, frame_of;                 // [n_frames + 1]: the frame's chunks; [N]: the atom's frame
+    int n_blocks = 0;
+};
+
+static int chunk_table_build(uf3_ctx *c, const std::vector<int64_t> &offsets, int n_frames, int width, ChunkTable &T,
+                             const std::string &who) {
+    const size_t n = (size_t)offsets[n_frames];
+    std::vector<int> blk_frame, blk_n, frame_blk(1, 0), frame_of(n);
+    std::vector<long long> blk_lo;
+    for (int f = 0; f < n_frames; f++) {
+        for (int64_t lo = offsets[f]; lo < offsets[f + 1]; lo += width) {
+            blk_frame.push_back(f);
+            blk_lo.push_back(lo);
+            blk_n.push_back((int)std::min<int64_t>(width, offsets[f + 1] - lo));
+        }
+        frame_blk.push_back((int)blk_frame.size());
+        for (int64_t i = offsets[f]; i < offsets[f + 1]; i++) frame_of[i] = f;
+    }
+    const size_t nb = blk_frame.size();
+    if (T.blk_frame.ensure(4 * nb) || T.blk_lo.ensure(8 * nb) || T.blk_n.ensure(4 * nb) || T.frame_blk.ensure(4 * (size_t)(n_frames + 1)) ||
+        T.frame_of.ensure(4 * n))
+        return fail(c, UF3_ENOMEM, who + ": out of device memory");
+    hipStream_t s = c->stream;
+    if (hipMemcpyAsync(T.blk_frame.p, blk_frame.data(), 4 * nb, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(T.blk_lo.p, blk_lo.data(), 8 * nb, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(T.blk_n.p, blk_n.data(), 4 * nb, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(T.frame_blk.p, frame_blk.data(), 4 * (size_t)(n_frames + 1), hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(T.frame_of.p, frame_of.data(), 4 * n, hipMemcpyHostToDevice, s) || hipStreamSynchronize(s))
+        return fail(c, UF3_EHIP, who + ": upload failed");      // (waited for: the host vectors go out of scope)
+    T.n_blocks = (int)nb;
+    return UF3_OK;
+}
+
+// uf3_*_destroy: waits for the driver's queued work, then frees it (its DevBufs with it)
+template <class Driver> static void driver_destroy(Driver *d) {
+    if (!d) return;
+    hipSetDevice(d->c->device);
+    hipStreamSynchronize(d->c->stream);
+    delete d;
+}
+
+// the run's skin for its own duration, the caller's back on every way out (a change of skin drops the lists: each run starts
+// with one list build); the run's error message outlives the restore
+template <class Run> static int with_run_skin(uf3_ctx *c, double skin, Run run) {
+    const double caller_skin = c->md.skin;
+    int rc = uf3_ctx_md_skin(c, skin);
+    if (rc) return rc;
+    rc = run();
+    const std::string msg = c->err;
+    const int rs = uf3_ctx_md_skin(c, caller_skin);
+    return rc ? fail(c, rc, msg) : rs;
+}
+
+// ------------------------------------------------------------------------------ molecular dynamics (uf3_md_*, uf3_md.h)
+// A library-owned state: positions (unwrapped), velocities, forces, inverse masses and species in HBM, stepped by k_md_step
+// between calls of the evaluator (eval_impl, unchanged).  Between two launches the velocities are at integer time t and the
+// forces are F(t): a launch closes step t with a half-kick and opens step t + 1 (half-kick, drift; BAOAB's A-O-A with friction).
+struct uf3_md : Batch {
+    DevBuf vel, frc, inv_m, virials, kin, ring;
+    int64_t step = 0;                           // absolute step counter (feeds the random numbers)
+    bool forces_valid = false;                  // frc / energies describe pos
+    // constant-pressure runs (uf3_md_run_npt, uf3_npt.h): chunk table, pistons, the current cells on the device
+    ChunkTable chunks;
+    DevBuf npt_st, npt_coef, npt_partial, cells_dev;
+    bool npt_ready = false;
+    bool virials_valid = false;                 // virials describe pos and cells (with forces_valid)
+    bool g_valid = false;                       // the pistons' g_close belongs to the current state
+    // heat-current samples (uf3_md_run_flux, uf3_flux.h): the masses as given, the lists' workspace, the records of a run
+    DevBuf mass, flux_ring;
+    FluxWork fx;
+    ~uf3_md() { fx.release(); }
+};
+
+extern "C" void uf3_md_destroy(uf3_md *md) { driver_destroy(md); }
 
 static int md_upload(uf3_md *md, const double *pos, const double *vel) {
     uf3_ctx *c = md->c;
@@ -3663,45 +3775,31 @@ static int md_upload(uf3_md *md, const double *pos, const double *vel) {
 
 extern "C" int uf3_md_create(uf3_basis *b, const uf3_frames *fr, const double *pos, const double *vel, const int32_t *z,
                              const double *masses, const double *c1, const double *c2, const double *c3, uf3_md **out) {
-    if (!b || !out) return fail(b ? b->ctx : nullptr, UF3_EINVAL, "uf3_md_create: null argument");
+    const char *who = "uf3_md_create";
+    int64_t n = 0;
+    int rc = batch_check(b, fr, pos, z, c1, c2, c3, out, who, &n);
+    if (rc) return rc;
     uf3_ctx *c = b->ctx;
-    if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, "uf3_md_create: bad uf3_frames");
-    if (!pos || !z || !masses || !c1 || (b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, "uf3_md_create: null argument");
-    const int nf = fr->n_frames;
-    if (fr->atom_offsets[0] != 0) return fail(c, UF3_EINVAL, "uf3_md_create: atom_offsets[0] must be 0");
-    for (int f = 0; f < nf; f++)
-        if (fr->atom_offsets[f + 1] <= fr->atom_offsets[f]) return fail(c, UF3_EINVAL, "uf3_md_create: every frame needs an atom");
-    const int64_t n = fr->atom_offsets[nf];
-    if (n >= (1LL << 28)) return fail(c, UF3_EINVAL, "uf3_md_create: batch must hold 1 .. 2^28 atoms");
+    if (!masses) return fail(c, UF3_EINVAL, "uf3_md_create: null argument");
     std::vector<double> inv(n);
     for (int64_t i = 0; i < n; i++) {
         if (!(masses[i] > 0.0) || !std::isfinite(masses[i])) return fail(c, UF3_EINVAL, "uf3_md_create: masses must be positive and finite");
         inv[i] = 1.0 / masses[i];
     }
-    if (!md_finite(fr->cells, 9 * (size_t)nf)) return fail(c, UF3_EINVAL, "uf3_md_create: cells must be finite");
     HIPCHK(c, hipSetDevice(c->device));
     uf3_md *md = new uf3_md();
-    md->b = b; md->c = c; md->n_frames = nf; md->natoms = n;
-    md->offsets.assign(fr->atom_offsets, fr->atom_offsets + nf + 1);
-    md->cells.assign(fr->cells, fr->cells + 9 * (size_t)nf);
-    md->pbc.assign(fr->pbc, fr->pbc + 3 * (size_t)nf);
-    md->fr.n_frames = nf; md->fr.atom_offsets = md->offsets.data(); md->fr.cells = md->cells.data(); md->fr.pbc = md->pbc.data();
-    md->c1.assign(c1, c1 + b->host.S);
-    md->c2.assign(c2 ? c2 : c1, (c2 ? c2 : c1) + b->c2_len); md->c2.push_back(0.0);
-    md->c3.assign(c3 ? c3 : c1, (c3 ? c3 : c1) + b->c3_len); md->c3.push_back(0.0);
     auto bail = [&](int rc) { uf3_md_destroy(md); return rc; };
+    rc = batch_init(*md, b, fr, pos, z, c1, c2, c3, 1, who);
+    if (rc) return bail(rc);
     const size_t n3 = 3 * (size_t)n;
-    if (md->pos.ensure(8 * n3) || md->vel.ensure(8 * n3) || md->frc.ensure(8 * n3) || md->inv_m.ensure(8 * (size_t)n) ||
-        md->z.ensure(4 * (size_t)n) || md->offsets_dev.ensure(8 * (size_t)(nf + 1)) || md->energies.ensure(8 * (size_t)nf) ||
-        md->virials.ensure(48 * (size_t)nf) || md->mass.ensure(8 * (size_t)n))
+    if (md->vel.ensure(8 * n3) || md->frc.ensure(8 * n3) || md->inv_m.ensure(8 * (size_t)n) || md->virials.ensure(48 * (size_t)md->n_frames) ||
+        md->mass.ensure(8 * (size_t)n))
         return bail(fail(c, UF3_ENOMEM, "uf3_md_create: out of device memory"));
     if (hipMemcpyAsync(md->inv_m.p, inv.data(), 8 * (size_t)n, hipMemcpyHostToDevice, c->stream) ||
         hipMemcpyAsync(md->mass.p, masses, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream) ||
-        hipMemcpyAsync(md->z.p, z, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream) ||
-        hipMemcpyAsync(md->offsets_dev.p, md->offsets.data(), 8 * (size_t)(nf + 1), hipMemcpyHostToDevice, c->stream) ||
         hipMemsetAsync(md->vel.p, 0, 8 * n3, c->stream))
         return bail(fail(c, UF3_EHIP, "uf3_md_create: upload failed"));
-    int rc = md_upload(md, pos, vel);
+    rc = md_upload(md, nullptr, vel);           // (waits for the uploads above)
     if (rc) return bail(rc);
     *out = md;
     return UF3_OK;
@@ -3714,8 +3812,7 @@ extern "C" int uf3_md_set_state(uf3_md *md, const double *pos, const double *vel
 
 // F(t) and the per-frame energies (and strain derivatives) of the current positions
 static int md_forces(uf3_md *md, bool virial) {
-    int rc = eval_impl(md->b, &md->fr, md->pos.as<double>(), md->z.as<int32_t>(), md->c1.data(), md->c2.data(), md->c3.data(),
-                       md->energies.as<double>(), md->frc.as<double>(), virial ? md->virials.as<double>() : nullptr);
+    int rc = batch_eval(*md, md->frc.as<double>(), virial ? md->virials.as<double>() : nullptr);
     md->forces_valid = rc == UF3_OK;
     md->virials_valid = md->forces_valid && virial;
     return rc;
@@ -3892,18 +3989,9 @@ static int md_run_entry(uf3_md *md, int64_t n_steps, double dt_fs, double temper
                                          : "uf3_md_run: a thermo buffer was given but no record is due");
     if (n_steps == 0) return UF3_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    // the run's skin for its own duration, the caller's back on every way out (a change of skin drops the lists: each run
-    // starts with one list build)
-    const double caller_skin = c->md.skin;
-    int rc = uf3_ctx_md_skin(c, skin);
-    if (rc) return rc;
-    rc = md_run(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, thermo_every, with_stress != 0, thermo, flux_every, flux);
-    if (rc) {
-        const std::string msg = c->err;
-        uf3_ctx_md_skin(c, caller_skin);
-        return fail(c, rc, msg);
-    }
-    return uf3_ctx_md_skin(c, caller_skin);
+    return with_run_skin(c, skin, [&] {
+        return md_run(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, thermo_every, with_stress != 0, thermo, flux_every, flux);
+    });
 }
 
 
@@ -3915,18 +4003,8 @@ static int npt_init(uf3_md *md) {
     if (md->npt_ready) return UF3_OK;
     uf3_ctx *c = md->c;
     const int nf = md->n_frames;
-    const int64_t n = md->natoms;
-    std::vector<int> blk_frame, blk_n, frame_blk(1, 0), frame_of(n);
-    std::vector<long long> blk_lo;
     std::vector<NptFrame> st(nf);
     for (int f = 0; f < nf; f++) {
-        for (int64_t lo = md->offsets[f]; lo < md->offsets[f + 1]; lo += UF3_NPT_THREADS) {
-            blk_frame.push_back(f);
-            blk_lo.push_back(lo);
-            blk_n.push_back((int)std::min<int64_t>(UF3_NPT_THREADS, md->offsets[f + 1] - lo));
-        }
-        frame_blk.push_back((int)blk_frame.size());
-        for (int64_t i = md->offsets[f]; i < md->offsets[f + 1]; i++) frame_of[i] = f;
         if (!(md->pbc[3 * f] && md->pbc[3 * f + 1] && md->pbc[3 * f + 2]))
             return fail(c, UF3_EINVAL, "uf3_md_run_npt: every frame must be periodic along all three axes");
         NptFrame &S = st[f];
@@ -3941,23 +4019,17 @@ static int npt_init(uf3_md *md) {
         S.vol0 = vol;
         for (int k = 0; k < 3; k++) S.hgt0[k] = vol / norm3(nrm[k]);
     }
-    const int nb = (int)blk_frame.size();
     HIPCHK(c, hipSetDevice(c->device));
-    if (md->blk_frame.ensure(4 * (size_t)nb) || md->blk_lo.ensure(8 * (size_t)nb) || md->blk_n.ensure(4 * (size_t)nb) ||
-        md->frame_blk.ensure(4 * (size_t)(nf + 1)) || md->frame_of.ensure(4 * (size_t)n) || md->npt_st.ensure(sizeof(NptFrame) * (size_t)nf) ||
-        md->npt_coef.ensure(sizeof(NptCoef) * (size_t)nf) || md->npt_partial.ensure(24 * (size_t)nb) || md->cells_dev.ensure(72 * (size_t)nf))
+    int rc = chunk_table_build(c, md->offsets, nf, UF3_NPT_THREADS, md->chunks, "uf3_md_run_npt");
+    if (rc) return rc;
+    if (md->npt_st.ensure(sizeof(NptFrame) * (size_t)nf) || md->npt_coef.ensure(sizeof(NptCoef) * (size_t)nf) ||
+        md->npt_partial.ensure(24 * (size_t)md->chunks.n_blocks) || md->cells_dev.ensure(72 * (size_t)nf))
         return fail(c, UF3_ENOMEM, "uf3_md_run_npt: out of device memory");
     hipStream_t s = c->stream;
-    if (hipMemcpyAsync(md->blk_frame.p, blk_frame.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(md->blk_lo.p, blk_lo.data(), 8 * (size_t)nb, hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(md->blk_n.p, blk_n.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(md->frame_blk.p, frame_blk.data(), 4 * (size_t)(nf + 1), hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(md->frame_of.p, frame_of.data(), 4 * (size_t)n, hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(md->npt_st.p, st.data(), sizeof(NptFrame) * (size_t)nf, hipMemcpyHostToDevice, s) ||
+    if (hipMemcpyAsync(md->npt_st.p, st.data(), sizeof(NptFrame) * (size_t)nf, hipMemcpyHostToDevice, s) ||
         hipMemsetAsync(md->npt_coef.p, 0, sizeof(NptCoef) * (size_t)nf, s) ||
         hipMemcpyAsync(md->cells_dev.p, md->cells.data(), 72 * (size_t)nf, hipMemcpyHostToDevice, s) || hipStreamSynchronize(s))
         return fail(c, UF3_EHIP, "uf3_md_run_npt: upload failed");
-    md->n_blocks = nb;
     md->npt_ready = true;
     return UF3_OK;
 }
@@ -3971,7 +4043,7 @@ static int npt_launch(uf3_md *md, NptArgs &A, int64_t record) {
     A.geo = lists ? c->md.geo.as<FrameGeom>() : nullptr;
     A.pos_ref = lists ? c->md.pos_ref.as<double>() : nullptr;
     A.thermo = record >= 0;
-    hipLaunchKernelGGL(k_npt_partial, dim3((unsigned)md->n_blocks), dim3(UF3_NPT_THREADS), 0, s, A);
+    hipLaunchKernelGGL(k_npt_partial, dim3((unsigned)md->chunks.n_blocks), dim3(UF3_NPT_THREADS), 0, s, A);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_npt_frame, dim3((unsigned)md->n_frames), dim3(UF3_NPT_THREADS), 0, s, A);
     HIPCHK(c, hipGetLastError());
@@ -4011,9 +4083,10 @@ static int npt_run(uf3_md *md, int64_t n_steps, double dt, double T, double gamm
     NptArgs A;
     memset(&A, 0, sizeof(A));
     A.pos = md->pos.as<double>(); A.vel = md->vel.as<double>(); A.frc = md->frc.as<double>(); A.inv_m = md->inv_m.as<double>();
-    A.kin = md->kin.as<double>(); A.frame_of = md->frame_of.as<int>(); A.n = md->natoms;
-    A.blk_frame = md->blk_frame.as<int>(); A.blk_n = md->blk_n.as<int>(); A.frame_blk = md->frame_blk.as<int>();
-    A.blk_lo = md->blk_lo.as<long long>(); A.partial = md->npt_partial.as<double>();
+    const ChunkTable &ct = md->chunks;
+    A.kin = md->kin.as<double>(); A.frame_of = ct.frame_of.as<int>(); A.n = md->natoms;
+    A.blk_frame = ct.blk_frame.as<int>(); A.blk_n = ct.blk_n.as<int>(); A.frame_blk = ct.frame_blk.as<int>();
+    A.blk_lo = ct.blk_lo.as<long long>(); A.partial = md->npt_partial.as<double>();
     A.offsets = md->offsets_dev.as<long long>(); A.virials = md->virials.as<double>();
     A.st = md->npt_st.as<NptFrame>(); A.coef = md->npt_coef.as<NptCoef>(); A.cells = md->cells_dev.as<double>();
     A.flags = c->flags.as<int>();
@@ -4076,29 +4149,27 @@ extern "C" int uf3_md_run_npt(uf3_md *md, int64_t n_steps, double dt_fs, double 
     if (rc) return rc;
     if (n_steps == 0) return UF3_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    // the run's skin and the "cells live" mode for its own duration; the caller's skin and mode back on every way out.  Lists
-    // from before the run are dropped on the way in (their cells are not compared any more), the run's own on the way out
-    const double caller_skin = c->md.skin;
-    const bool caller_live = c->md.live;
-    const double *caller_dev = c->md.live_dev;
-    double *caller_host = c->md.live_host;
-    rc = uf3_ctx_md_skin(c, skin);
-    if (rc) return rc;
-    c->md.valid = false;
-    c->md.live = true; c->md.live_dev = md->cells_dev.as<double>(); c->md.live_host = md->cells.data();
-    rc = npt_run(md, n_steps, dt_fs, temperature_K, friction_per_fs, pressure_eV_A3, barostat_time_fs, barostat_friction_per_fs,
-                 piston_temperature_K, seed, skin, thermo_every, thermo);
-    const std::string msg = c->err;
-    if (rc) {
-        // (the device's cells are the state: the host's copy follows them, whatever stopped the run)
-        hipMemcpyAsync(md->cells.data(), md->cells_dev.p, 72 * (size_t)md->n_frames, hipMemcpyDeviceToHost, c->stream);
-        hipStreamSynchronize(c->stream);
-        md->forces_valid = false; md->virials_valid = false; md->g_valid = false;
-    }
-    c->md.valid = false;
-    c->md.live = caller_live; c->md.live_dev = caller_dev; c->md.live_host = caller_host;
-    const int rs = uf3_ctx_md_skin(c, caller_skin);
-    return rc ? fail(c, rc, msg) : rs;
+    // the run's skin and the "cells live" mode for its own duration; the caller's mode, then the caller's skin, back on every
+    // way out.  Lists from before the run are dropped on the way in (their cells are not compared any more), the run's own on
+    // the way out
+    return with_run_skin(c, skin, [&] {
+        const bool caller_live = c->md.live;
+        const double *caller_dev = c->md.live_dev;
+        double *caller_host = c->md.live_host;
+        c->md.valid = false;
+        c->md.live = true; c->md.live_dev = md->cells_dev.as<double>(); c->md.live_host = md->cells.data();
+        const int rc = npt_run(md, n_steps, dt_fs, temperature_K, friction_per_fs, pressure_eV_A3, barostat_time_fs,
+                               barostat_friction_per_fs, piston_temperature_K, seed, skin, thermo_every, thermo);
+        if (rc) {
+            // (the device's cells are the state: the host's copy follows them, whatever stopped the run)
+            hipMemcpyAsync(md->cells.data(), md->cells_dev.p, 72 * (size_t)md->n_frames, hipMemcpyDeviceToHost, c->stream);
+            hipStreamSynchronize(c->stream);
+            md->forces_valid = false; md->virials_valid = false; md->g_valid = false;
+        }
+        c->md.valid = false;
+        c->md.live = caller_live; c->md.live_dev = caller_dev; c->md.live_host = caller_host;
+        return rc;
+    });
 }
 
 extern "C" int uf3_md_get_cells(uf3_md *md, double *cells, double *scales, double *strain_rates) {
@@ -4158,70 +4229,30 @@ extern "C" int uf3_philox_debug(uf3_ctx *c, int64_t n, const uint32_t *counters,
 // in cell runs, the scaled coordinates q (x = q D) in HBM.  Every step is one evaluator call (eval_impl, unchanged) and three
 // launches; positions-only runs wait for the device only every check_every steps.  Cell runs copy the new cells back every step
 // (the evaluator reads them from the host uf3_frames) and run on the rebuild route (skin 0: the MD route's key holds the cells).
-struct uf3_relax {
-    uf3_basis *b = nullptr;
-    uf3_ctx *c = nullptr;
-    int32_t n_frames = 0;
-    int64_t natoms = 0;
-    int n_blocks = 0;
+struct uf3_relax : Batch {
     bool cell_run = false;                      // some frame has the cell as a degree of freedom
     bool has_fixed = false;
-    std::vector<int64_t> offsets;
-    std::vector<double> cells;                  // the current cells (host: what eval_impl reads)
-    std::vector<uint8_t> pbc;
-    uf3_frames fr{};
-    std::vector<double> c1, c2, c3;
     std::vector<RelaxFrame> st_host;
-    Buf pos, q, vel, frc, z, fixed, energies, virials, offsets_dev, blk_frame, blk_lo, blk_n, frame_blk, frame_of, st, coef,
-        partial, cells_dev, ring;
+    ChunkTable chunks;
+    DevBuf q, vel, frc, fixed, virials, st, coef, partial, cells_dev, ring;
     bool forces_valid = false;                  // frc / energies (/ virials in a cell run) describe pos
 };
 
-extern "C" void uf3_relax_destroy(uf3_relax *r) {
-    if (!r) return;
-    hipSetDevice(r->c->device);
-    hipStreamSynchronize(r->c->stream);
-    for (Buf *p : {&r->pos, &r->q, &r->vel, &r->frc, &r->z, &r->fixed, &r->energies, &r->virials, &r->offsets_dev, &r->blk_frame,
-                   &r->blk_lo, &r->blk_n, &r->frame_blk, &r->frame_of, &r->st, &r->coef, &r->partial, &r->cells_dev, &r->ring})
-        p->release();
-    delete r;
-}
+extern "C" void uf3_relax_destroy(uf3_relax *r) { driver_destroy(r); }
 
 extern "C" int uf3_relax_create(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const uint8_t *fixed,
                                 const double *c1, const double *c2, const double *c3, int relax_cell, uf3_relax **out) {
-    if (!b) return fail(nullptr, UF3_EINVAL, "uf3_relax_create: basis is NULL");
+    const char *who = "uf3_relax_create";
+    int64_t n = 0;
+    int rc = batch_check(b, fr, pos, z, c1, c2, c3, out, who, &n);
+    if (rc) return rc;
     uf3_ctx *c = b->ctx;
-    if (!out) return fail(c, UF3_EINVAL, "uf3_relax_create: out is NULL");
-    if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, "uf3_relax_create: bad uf3_frames");
-    if (!pos) return fail(c, UF3_EINVAL, "uf3_relax_create: pos is NULL");
-    if (!z) return fail(c, UF3_EINVAL, "uf3_relax_create: z is NULL");
-    if (!c1 || (b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, "uf3_relax_create: missing coefficients (c1 / c2 / c3)");
     if (relax_cell != 0 && relax_cell != 1) return fail(c, UF3_EINVAL, "uf3_relax_create: relax_cell must be 0 or 1");
     if (relax_cell && fixed) return fail(c, UF3_EINVAL, "uf3_relax_create: fixed atoms together with relax_cell are not supported");
     const int nf = fr->n_frames;
-    if (fr->atom_offsets[0] != 0) return fail(c, UF3_EINVAL, "uf3_relax_create: atom_offsets[0] must be 0");
-    for (int f = 0; f < nf; f++)
-        if (fr->atom_offsets[f + 1] <= fr->atom_offsets[f]) return fail(c, UF3_EINVAL, "uf3_relax_create: every frame needs an atom");
-    const int64_t n = fr->atom_offsets[nf];
-    if (n >= (1LL << 28)) return fail(c, UF3_EINVAL, "uf3_relax_create: batch must hold 1 .. 2^28 atoms");
-    if (!md_finite(pos, 3 * (size_t)n)) return fail(c, UF3_EINVAL, "uf3_relax_create: pos must be finite");
-    if (!md_finite(fr->cells, 9 * (size_t)nf)) return fail(c, UF3_EINVAL, "uf3_relax_create: cells must be finite");
     if (fixed)
         for (int64_t i = 0; i < n; i++)
             if (fixed[i] > 1) return fail(c, UF3_EINVAL, "uf3_relax_create: fixed must hold 0 or 1 per atom");
-    // the chunk table: chunks of <= UF3_RELAX_THREADS atoms from each frame's first atom
-    std::vector<int> blk_frame, blk_n, frame_blk(1, 0), frame_of(n);
-    std::vector<long long> blk_lo;
-    for (int f = 0; f < nf; f++) {
-        for (int64_t lo = fr->atom_offsets[f]; lo < fr->atom_offsets[f + 1]; lo += UF3_RELAX_THREADS) {
-            blk_frame.push_back(f);
-            blk_lo.push_back(lo);
-            blk_n.push_back((int)std::min<int64_t>(UF3_RELAX_THREADS, fr->atom_offsets[f + 1] - lo));
-        }
-        frame_blk.push_back((int)blk_frame.size());
-        for (int64_t i = fr->atom_offsets[f]; i < fr->atom_offsets[f + 1]; i++) frame_of[i] = f;
-    }
-    const int nb = (int)blk_frame.size();
     std::vector<RelaxFrame> st(nf);
     bool cell_run = false;
     for (int f = 0; f < nf; f++) {
@@ -4241,35 +4272,20 @@ extern "C" int uf3_relax_create(uf3_basis *b, const uf3_frames *fr, const double
     }
     HIPCHK(c, hipSetDevice(c->device));
     uf3_relax *r = new uf3_relax();
-    r->b = b; r->c = c; r->n_frames = nf; r->natoms = n; r->n_blocks = nb; r->cell_run = cell_run; r->has_fixed = fixed != nullptr;
-    r->offsets.assign(fr->atom_offsets, fr->atom_offsets + nf + 1);
-    r->cells.assign(fr->cells, fr->cells + 9 * (size_t)nf);
-    r->pbc.assign(fr->pbc, fr->pbc + 3 * (size_t)nf);
-    r->fr.n_frames = nf; r->fr.atom_offsets = r->offsets.data(); r->fr.cells = r->cells.data(); r->fr.pbc = r->pbc.data();
-    r->c1.assign(c1, c1 + b->host.S);
-    r->c2.assign(c2 ? c2 : c1, (c2 ? c2 : c1) + b->c2_len); r->c2.push_back(0.0);
-    r->c3.assign(c3 ? c3 : c1, (c3 ? c3 : c1) + b->c3_len); r->c3.push_back(0.0);
+    r->cell_run = cell_run; r->has_fixed = fixed != nullptr;
     r->st_host = st;
     auto bail = [&](int rc) { uf3_relax_destroy(r); return rc; };
-    const size_t n3 = 3 * (size_t)n;
-    if (r->pos.ensure(8 * n3) || (cell_run && r->q.ensure(8 * n3)) || r->vel.ensure(8 * n3) || r->frc.ensure(8 * n3) ||
-        r->z.ensure(4 * (size_t)n) || (fixed && r->fixed.ensure((size_t)n)) || r->energies.ensure(8 * (size_t)nf) ||
-        r->virials.ensure(48 * (size_t)nf) || r->offsets_dev.ensure(8 * (size_t)(nf + 1)) || r->blk_frame.ensure(4 * (size_t)nb) ||
-        r->blk_lo.ensure(8 * (size_t)nb) || r->blk_n.ensure(4 * (size_t)nb) || r->frame_blk.ensure(4 * (size_t)(nf + 1)) ||
-        r->frame_of.ensure(4 * (size_t)n) || r->st.ensure(sizeof(RelaxFrame) * (size_t)nf) ||
-        r->coef.ensure(sizeof(RelaxCoef) * (size_t)nf) || r->partial.ensure(32 * (size_t)nb) || r->cells_dev.ensure(72 * (size_t)nf))
+    rc = batch_init(*r, b, fr, pos, z, c1, c2, c3, 1, who);
+    if (!rc) rc = chunk_table_build(c, r->offsets, nf, UF3_RELAX_THREADS, r->chunks, who);
+    if (rc) return bail(rc);
+    const size_t n3 = 3 * (size_t)n, nb = (size_t)r->chunks.n_blocks;
+    if ((cell_run && r->q.ensure(8 * n3)) || r->vel.ensure(8 * n3) || r->frc.ensure(8 * n3) || (fixed && r->fixed.ensure((size_t)n)) ||
+        r->virials.ensure(48 * (size_t)nf) || r->st.ensure(sizeof(RelaxFrame) * (size_t)nf) ||
+        r->coef.ensure(sizeof(RelaxCoef) * (size_t)nf) || r->partial.ensure(32 * nb) || r->cells_dev.ensure(72 * (size_t)nf))
         return bail(fail(c, UF3_ENOMEM, "uf3_relax_create: out of device memory"));
     hipStream_t s = c->stream;
-    if (hipMemcpyAsync(r->pos.p, pos, 8 * n3, hipMemcpyHostToDevice, s) ||
-        (cell_run && hipMemcpyAsync(r->q.p, pos, 8 * n3, hipMemcpyHostToDevice, s)) ||
-        hipMemsetAsync(r->vel.p, 0, 8 * n3, s) || hipMemcpyAsync(r->z.p, z, 4 * (size_t)n, hipMemcpyHostToDevice, s) ||
+    if ((cell_run && hipMemcpyAsync(r->q.p, pos, 8 * n3, hipMemcpyHostToDevice, s)) || hipMemsetAsync(r->vel.p, 0, 8 * n3, s) ||
         (fixed && hipMemcpyAsync(r->fixed.p, fixed, (size_t)n, hipMemcpyHostToDevice, s)) ||
-        hipMemcpyAsync(r->offsets_dev.p, r->offsets.data(), 8 * (size_t)(nf + 1), hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(r->blk_frame.p, blk_frame.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(r->blk_lo.p, blk_lo.data(), 8 * (size_t)nb, hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(r->blk_n.p, blk_n.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(r->frame_blk.p, frame_blk.data(), 4 * (size_t)(nf + 1), hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(r->frame_of.p, frame_of.data(), 4 * (size_t)n, hipMemcpyHostToDevice, s) ||
         hipMemcpyAsync(r->st.p, st.data(), sizeof(RelaxFrame) * (size_t)nf, hipMemcpyHostToDevice, s) ||
         hipMemsetAsync(r->coef.p, 0, sizeof(RelaxCoef) * (size_t)nf, s) ||
         hipMemcpyAsync(r->cells_dev.p, r->cells.data(), 72 * (size_t)nf, hipMemcpyHostToDevice, s) || hipStreamSynchronize(s))
@@ -4279,8 +4295,7 @@ extern "C" int uf3_relax_create(uf3_basis *b, const uf3_frames *fr, const double
 }
 
 static int relax_forces(uf3_relax *r) {
-    int rc = eval_impl(r->b, &r->fr, r->pos.as<double>(), r->z.as<int32_t>(), r->c1.data(), r->c2.data(), r->c3.data(),
-                       r->energies.as<double>(), r->frc.as<double>(), r->cell_run ? r->virials.as<double>() : nullptr);
+    int rc = batch_eval(*r, r->frc.as<double>(), r->cell_run ? r->virials.as<double>() : nullptr);
     r->forces_valid = rc == UF3_OK;
     return rc;
 }
@@ -4302,16 +4317,17 @@ static int relax_run(uf3_relax *r, int64_t max_steps, double fmax, double dt, do
     if (n_rec) HIPCHK(c, r->ring.ensure(16 * (size_t)n_rec * nf));
     RelaxPartialArgs P;
     P.frc = r->frc.as<double>(); P.vel = r->vel.as<double>(); P.fixed = r->has_fixed ? r->fixed.as<uint8_t>() : nullptr;
-    P.blk_frame = r->blk_frame.as<int>(); P.blk_lo = r->blk_lo.as<long long>(); P.blk_n = r->blk_n.as<int>();
+    const ChunkTable &T = r->chunks;
+    P.blk_frame = T.blk_frame.as<int>(); P.blk_lo = T.blk_lo.as<long long>(); P.blk_n = T.blk_n.as<int>();
     P.st = r->st.as<RelaxFrame>(); P.partial = r->partial.as<double>();
     RelaxFrameArgs F;
-    F.partial = r->partial.as<double>(); F.frame_blk = r->frame_blk.as<int>(); F.offsets = r->offsets_dev.as<long long>();
+    F.partial = r->partial.as<double>(); F.frame_blk = T.frame_blk.as<int>(); F.offsets = r->offsets_dev.as<long long>();
     F.energies = r->energies.as<double>(); F.virials = r->cell_run ? r->virials.as<double>() : nullptr;
     F.st = r->st.as<RelaxFrame>(); F.coef = r->coef.as<RelaxCoef>(); F.cells = r->cells_dev.as<double>();
     F.fmax = fmax; F.dt0 = dt; F.dt_max = dt_max; F.maxstep = maxstep;
     RelaxMoveArgs M;
     M.pos = r->pos.as<double>(); M.vel = r->vel.as<double>(); M.q = r->cell_run ? r->q.as<double>() : nullptr;
-    M.frc = r->frc.as<double>(); M.fixed = P.fixed; M.frame_of = r->frame_of.as<int>(); M.coef = r->coef.as<RelaxCoef>();
+    M.frc = r->frc.as<double>(); M.fixed = P.fixed; M.frame_of = T.frame_of.as<int>(); M.coef = r->coef.as<RelaxCoef>();
     M.n = r->natoms;
     int64_t last = max_steps;                   // the last evaluation made
     for (int64_t k = 0; k <= max_steps; k++) {
@@ -4319,7 +4335,7 @@ static int relax_run(uf3_relax *r, int64_t max_steps, double fmax, double dt, do
             int rc = relax_forces(r);
             if (rc) return rc;
         }
-        hipLaunchKernelGGL(k_relax_partial, dim3((unsigned)r->n_blocks), dim3(UF3_RELAX_THREADS), 0, s, P);
+        hipLaunchKernelGGL(k_relax_partial, dim3((unsigned)T.n_blocks), dim3(UF3_RELAX_THREADS), 0, s, P);
         HIPCHK(c, hipGetLastError());
         F.rec = (n_rec && k % rec_every == 0) ? r->ring.as<double>() + 2 * (size_t)nf * (size_t)(k / rec_every) : nullptr;
         F.can_move = k < max_steps;
@@ -4374,18 +4390,9 @@ extern "C" int uf3_relax_run(uf3_relax *r, int64_t max_steps, double fmax, doubl
         return fail(c, UF3_EINVAL, record_every ? "uf3_relax_run: records are due but the records buffer is NULL"
                                                 : "uf3_relax_run: a records buffer was given but no record is due");
     HIPCHK(c, hipSetDevice(c->device));
-    // the run's skin for its own duration (0 in a cell run: the MD route's list key holds the cells), the caller's back on
-    // every way out
-    const double caller_skin = c->md.skin;
-    int rc = uf3_ctx_md_skin(c, r->cell_run ? 0.0 : skin);
-    if (rc) return rc;
-    rc = relax_run(r, max_steps, fmax, dt, dt_max, maxstep, check_every, record_every, records);
-    if (rc) {
-        const std::string msg = c->err;
-        uf3_ctx_md_skin(c, caller_skin);
-        return fail(c, rc, msg);
-    }
-    return uf3_ctx_md_skin(c, caller_skin);
+    // (skin 0 in a cell run: the MD route's list key holds the cells)
+    return with_run_skin(c, r->cell_run ? 0.0 : skin,
+                         [&] { return relax_run(r, max_steps, fmax, dt, dt_max, maxstep, check_every, record_every, records); });
 }
 
 extern "C" int uf3_relax_get_state(uf3_relax *r, double *pos, double *cells, double *forces, double *energies, int32_t *status,
@@ -4416,57 +4423,30 @@ extern "C" int uf3_relax_get_state(uf3_relax *r, double *pos, double *cells, dou
 // A library-owned set of bands: positions (unwrapped), velocities, true forces, NEB forces, the per-band optimiser state in HBM.
 // Every step is one evaluator call over all frames (eval_impl, unchanged; the end points are evaluated with the rest because
 // their energies are needed) and four launches; the host waits for the device only every check_every steps.
-struct uf3_neb {
-    uf3_basis *b = nullptr;
-    uf3_ctx *c = nullptr;
-    int32_t n_frames = 0, n_bands = 0;
-    int64_t natoms = 0;
-    int n_blocks = 0;
+struct uf3_neb : Batch {
+    int32_t n_bands = 0;
     bool has_fixed = false;
-    std::vector<int64_t> offsets;
-    std::vector<double> cells;
-    std::vector<uint8_t> pbc;
-    uf3_frames fr{};
-    std::vector<double> c1, c2, c3;
     std::vector<NebBand> st_host;
     std::vector<double> e_last_host;
-    Buf pos, vel, frc, g, z, fixed, energies, e_last, offsets_dev, blk_frame, blk_lo, blk_n, frame_blk, frame_of, frame_band, st, coef,
-        img, partial, cmax, ring;
+    ChunkTable chunks;
+    DevBuf vel, frc, g, fixed, e_last, frame_band, st, coef, img, partial, cmax, ring;
     bool forces_valid = false;                  // frc / energies describe pos
     bool g_valid = false;                       // g describes pos (and the climb flag of the last run)
     int last_climb = 0;
 };
 
-extern "C" void uf3_neb_destroy(uf3_neb *r) {
-    if (!r) return;
-    hipSetDevice(r->c->device);
-    hipStreamSynchronize(r->c->stream);
-    for (Buf *p : {&r->pos, &r->vel, &r->frc, &r->g, &r->z, &r->fixed, &r->energies, &r->e_last, &r->offsets_dev, &r->blk_frame,
-                   &r->blk_lo, &r->blk_n, &r->frame_blk, &r->frame_of, &r->frame_band, &r->st, &r->coef, &r->img, &r->partial,
-                   &r->cmax, &r->ring})
-        p->release();
-    delete r;
-}
+extern "C" void uf3_neb_destroy(uf3_neb *r) { driver_destroy(r); }
 
 extern "C" int uf3_neb_create(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const uint8_t *fixed,
                               const double *c1, const double *c2, const double *c3, int32_t n_bands, const int32_t *band_first_frame,
                               const double *spring, uf3_neb **out) {
-    if (!b) return fail(nullptr, UF3_EINVAL, "uf3_neb_create: basis is NULL");
+    const char *who = "uf3_neb_create";
+    int64_t n = 0;
+    int rc = batch_check(b, fr, pos, z, c1, c2, c3, out, who, &n);
+    if (rc) return rc;
     uf3_ctx *c = b->ctx;
-    if (!out) return fail(c, UF3_EINVAL, "uf3_neb_create: out is NULL");
-    if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, "uf3_neb_create: bad uf3_frames");
-    if (!pos) return fail(c, UF3_EINVAL, "uf3_neb_create: pos is NULL");
-    if (!z) return fail(c, UF3_EINVAL, "uf3_neb_create: z is NULL");
-    if (!c1 || (b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, "uf3_neb_create: missing coefficients (c1 / c2 / c3)");
     if (n_bands < 1 || !band_first_frame || !spring) return fail(c, UF3_EINVAL, "uf3_neb_create: needs a band, band_first_frame and spring");
     const int nf = fr->n_frames;
-    if (fr->atom_offsets[0] != 0) return fail(c, UF3_EINVAL, "uf3_neb_create: atom_offsets[0] must be 0");
-    for (int f = 0; f < nf; f++)
-        if (fr->atom_offsets[f + 1] <= fr->atom_offsets[f]) return fail(c, UF3_EINVAL, "uf3_neb_create: every frame needs an atom");
-    const int64_t n = fr->atom_offsets[nf];
-    if (n >= (1LL << 28)) return fail(c, UF3_EINVAL, "uf3_neb_create: batch must hold 1 .. 2^28 atoms");
-    if (!md_finite(pos, 3 * (size_t)n)) return fail(c, UF3_EINVAL, "uf3_neb_create: pos must be finite");
-    if (!md_finite(fr->cells, 9 * (size_t)nf)) return fail(c, UF3_EINVAL, "uf3_neb_create: cells must be finite");
     if (fixed)
         for (int64_t i = 0; i < n; i++)
             if (fixed[i] > 1) return fail(c, UF3_EINVAL, "uf3_neb_create: fixed must hold 0 or 1 per atom");
@@ -4501,57 +4481,30 @@ extern "C" int uf3_neb_create(uf3_basis *b, const uf3_frames *fr, const double *
         S.first = 1; S.status = UF3_RELAX_RUNNING; S.climbing = -1; S.frame0 = f0; S.n_img = M;
         for (int j = 0; j < M; j++) frame_band[f0 + j] = bd;
     }
-    // the chunk table: chunks of <= UF3_RELAX_THREADS atoms from each frame's first atom
-    std::vector<int> blk_frame, blk_n, frame_blk(1, 0), frame_of(n);
-    std::vector<long long> blk_lo;
-    for (int f = 0; f < nf; f++) {
-        for (int64_t lo = fr->atom_offsets[f]; lo < fr->atom_offsets[f + 1]; lo += UF3_RELAX_THREADS) {
-            blk_frame.push_back(f);
-            blk_lo.push_back(lo);
-            blk_n.push_back((int)std::min<int64_t>(UF3_RELAX_THREADS, fr->atom_offsets[f + 1] - lo));
-        }
-        frame_blk.push_back((int)blk_frame.size());
-        for (int64_t i = fr->atom_offsets[f]; i < fr->atom_offsets[f + 1]; i++) frame_of[i] = f;
-    }
-    const int nb = (int)blk_frame.size();
     HIPCHK(c, hipSetDevice(c->device));
     uf3_neb *r = new uf3_neb();
-    r->b = b; r->c = c; r->n_frames = nf; r->n_bands = n_bands; r->natoms = n; r->n_blocks = nb; r->has_fixed = fixed != nullptr;
-    r->offsets.assign(fr->atom_offsets, fr->atom_offsets + nf + 1);
-    r->cells.assign(fr->cells, fr->cells + 9 * (size_t)nf);
-    r->pbc.assign(fr->pbc, fr->pbc + 3 * (size_t)nf);
-    r->fr.n_frames = nf; r->fr.atom_offsets = r->offsets.data(); r->fr.cells = r->cells.data(); r->fr.pbc = r->pbc.data();
-    r->c1.assign(c1, c1 + b->host.S);
-    r->c2.assign(c2 ? c2 : c1, (c2 ? c2 : c1) + b->c2_len); r->c2.push_back(0.0);
-    r->c3.assign(c3 ? c3 : c1, (c3 ? c3 : c1) + b->c3_len); r->c3.push_back(0.0);
+    r->n_bands = n_bands; r->has_fixed = fixed != nullptr;
     r->st_host = st;
     r->e_last_host.assign(nf, std::numeric_limits<double>::quiet_NaN());
     auto bail = [&](int rc) { uf3_neb_destroy(r); return rc; };
-    const size_t n3 = 3 * (size_t)n;
-    if (r->pos.ensure(8 * n3) || r->vel.ensure(8 * n3) || r->frc.ensure(8 * n3) || r->g.ensure(8 * n3) || r->z.ensure(4 * (size_t)n) ||
-        (fixed && r->fixed.ensure((size_t)n)) || r->energies.ensure(8 * (size_t)nf) || r->e_last.ensure(8 * (size_t)nf) ||
-        r->offsets_dev.ensure(8 * (size_t)(nf + 1)) || r->blk_frame.ensure(4 * (size_t)nb) || r->blk_lo.ensure(8 * (size_t)nb) ||
-        r->blk_n.ensure(4 * (size_t)nb) || r->frame_blk.ensure(4 * (size_t)(nf + 1)) || r->frame_of.ensure(4 * (size_t)n) ||
-        r->frame_band.ensure(4 * (size_t)nf) || r->st.ensure(sizeof(NebBand) * (size_t)n_bands) ||
+    rc = batch_init(*r, b, fr, pos, z, c1, c2, c3, 1, who);
+    if (!rc) rc = chunk_table_build(c, r->offsets, nf, UF3_RELAX_THREADS, r->chunks, who);
+    if (rc) return bail(rc);
+    const size_t n3 = 3 * (size_t)n, nb = (size_t)r->chunks.n_blocks;
+    if (r->vel.ensure(8 * n3) || r->frc.ensure(8 * n3) || r->g.ensure(8 * n3) || (fixed && r->fixed.ensure((size_t)n)) ||
+        r->e_last.ensure(8 * (size_t)nf) || r->frame_band.ensure(4 * (size_t)nf) || r->st.ensure(sizeof(NebBand) * (size_t)n_bands) ||
         r->coef.ensure(sizeof(NebCoef) * (size_t)n_bands) || r->img.ensure(sizeof(NebImage) * (size_t)nf) ||
-        r->partial.ensure(8 * UF3_NEB_NSUM * (size_t)nb) || r->cmax.ensure(8 * (size_t)nb))
+        r->partial.ensure(8 * UF3_NEB_NSUM * nb) || r->cmax.ensure(8 * nb))
         return bail(fail(c, UF3_ENOMEM, "uf3_neb_create: out of device memory"));
     hipStream_t s = c->stream;
-    if (hipMemcpyAsync(r->pos.p, pos, 8 * n3, hipMemcpyHostToDevice, s) || hipMemsetAsync(r->vel.p, 0, 8 * n3, s) ||
-        hipMemsetAsync(r->g.p, 0, 8 * n3, s) || hipMemcpyAsync(r->z.p, z, 4 * (size_t)n, hipMemcpyHostToDevice, s) ||
+    if (hipMemsetAsync(r->vel.p, 0, 8 * n3, s) || hipMemsetAsync(r->g.p, 0, 8 * n3, s) ||
         (fixed && hipMemcpyAsync(r->fixed.p, fixed, (size_t)n, hipMemcpyHostToDevice, s)) ||
         hipMemcpyAsync(r->e_last.p, r->e_last_host.data(), 8 * (size_t)nf, hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(r->offsets_dev.p, r->offsets.data(), 8 * (size_t)(nf + 1), hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(r->blk_frame.p, blk_frame.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(r->blk_lo.p, blk_lo.data(), 8 * (size_t)nb, hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(r->blk_n.p, blk_n.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(r->frame_blk.p, frame_blk.data(), 4 * (size_t)(nf + 1), hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(r->frame_of.p, frame_of.data(), 4 * (size_t)n, hipMemcpyHostToDevice, s) ||
         hipMemcpyAsync(r->frame_band.p, frame_band.data(), 4 * (size_t)nf, hipMemcpyHostToDevice, s) ||
         hipMemcpyAsync(r->st.p, st.data(), sizeof(NebBand) * (size_t)n_bands, hipMemcpyHostToDevice, s) ||
         hipMemsetAsync(r->coef.p, 0, sizeof(NebCoef) * (size_t)n_bands, s) ||
         hipMemsetAsync(r->img.p, 0, sizeof(NebImage) * (size_t)nf, s) ||
-        hipMemsetAsync(r->partial.p, 0, 8 * UF3_NEB_NSUM * (size_t)nb, s) || hipMemsetAsync(r->cmax.p, 0, 8 * (size_t)nb, s) ||
+        hipMemsetAsync(r->partial.p, 0, 8 * UF3_NEB_NSUM * nb, s) || hipMemsetAsync(r->cmax.p, 0, 8 * nb, s) ||
         hipStreamSynchronize(s))
         return bail(fail(c, UF3_EHIP, "uf3_neb_create: upload failed"));
     *out = r;
@@ -4559,8 +4512,7 @@ extern "C" int uf3_neb_create(uf3_basis *b, const uf3_frames *fr, const double *
 }
 
 static int neb_evaluate(uf3_neb *r) {
-    int rc = eval_impl(r->b, &r->fr, r->pos.as<double>(), r->z.as<int32_t>(), r->c1.data(), r->c2.data(), r->c3.data(),
-                       r->energies.as<double>(), r->frc.as<double>(), nullptr);
+    int rc = batch_eval(*r, r->frc.as<double>(), nullptr);
     r->forces_valid = rc == UF3_OK;
     r->g_valid = false;
     return rc;
@@ -4577,8 +4529,9 @@ static NebChunkArgs neb_chunk_args(uf3_neb *r, int climb, int all) {
     NebChunkArgs P;
     P.pos = r->pos.as<double>(); P.frc = r->frc.as<double>(); P.vel = r->vel.as<double>();
     P.fixed = r->has_fixed ? r->fixed.as<uint8_t>() : nullptr;
-    P.blk_frame = r->blk_frame.as<int>(); P.blk_lo = r->blk_lo.as<long long>(); P.blk_n = r->blk_n.as<int>();
-    P.frame_blk = r->frame_blk.as<int>(); P.frame_band = r->frame_band.as<int>(); P.offsets = r->offsets_dev.as<long long>();
+    const ChunkTable &T = r->chunks;
+    P.blk_frame = T.blk_frame.as<int>(); P.blk_lo = T.blk_lo.as<long long>(); P.blk_n = T.blk_n.as<int>();
+    P.frame_blk = T.frame_blk.as<int>(); P.frame_band = r->frame_band.as<int>(); P.offsets = r->offsets_dev.as<long long>();
     P.energies = r->energies.as<double>(); P.bands = r->st.as<NebBand>(); P.partial = r->partial.as<double>();
     P.g = r->g.as<double>(); P.cmax = r->cmax.as<double>(); P.img = r->img.as<NebImage>();
     P.climb = climb; P.all = all;
@@ -4596,12 +4549,12 @@ static int neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt, double
     if (n_rec) HIPCHK(c, r->ring.ensure(8 * (size_t)n_rec * row));
     const NebChunkArgs P = neb_chunk_args(r, climb, 0);
     NebBandArgs F;
-    F.cmax = r->cmax.as<double>(); F.frame_blk = r->frame_blk.as<int>(); F.energies = r->energies.as<double>();
+    F.cmax = r->cmax.as<double>(); F.frame_blk = r->chunks.frame_blk.as<int>(); F.energies = r->energies.as<double>();
     F.img = r->img.as<NebImage>(); F.bands = r->st.as<NebBand>(); F.coef = r->coef.as<NebCoef>(); F.e_last = r->e_last.as<double>();
     F.fmax = fmax; F.dt0 = dt; F.dt_max = dt_max; F.maxstep = maxstep; F.n_frames = nf; F.climb = climb;
     NebMoveArgs M;
     M.pos = r->pos.as<double>(); M.vel = r->vel.as<double>(); M.g = r->g.as<double>(); M.fixed = P.fixed;
-    M.frame_of = r->frame_of.as<int>(); M.frame_band = r->frame_band.as<int>(); M.bands = r->st.as<NebBand>();
+    M.frame_of = r->chunks.frame_of.as<int>(); M.frame_band = r->frame_band.as<int>(); M.bands = r->st.as<NebBand>();
     M.coef = r->coef.as<NebCoef>(); M.n = r->natoms;
     r->last_climb = climb;
     hipLaunchKernelGGL(k_neb_rearm, dim3((unsigned)((nbd + UF3_RELAX_THREADS - 1) / UF3_RELAX_THREADS)), dim3(UF3_RELAX_THREADS), 0, s,
@@ -4613,9 +4566,9 @@ static int neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt, double
             int rc = neb_evaluate(r);
             if (rc) return rc;
         }
-        hipLaunchKernelGGL(k_neb_partial, dim3((unsigned)r->n_blocks), dim3(UF3_RELAX_THREADS), 0, s, P);
+        hipLaunchKernelGGL(k_neb_partial, dim3((unsigned)r->chunks.n_blocks), dim3(UF3_RELAX_THREADS), 0, s, P);
         HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(k_neb_force, dim3((unsigned)r->n_blocks), dim3(UF3_RELAX_THREADS), 0, s, P);
+        hipLaunchKernelGGL(k_neb_force, dim3((unsigned)r->chunks.n_blocks), dim3(UF3_RELAX_THREADS), 0, s, P);
         HIPCHK(c, hipGetLastError());
         F.rec = (n_rec && k % rec_every == 0) ? r->ring.as<double>() + row * (size_t)(k / rec_every) : nullptr;
         F.can_move = k < max_steps;
@@ -4672,17 +4625,7 @@ extern "C" int uf3_neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt
         return fail(c, UF3_EINVAL, record_every ? "uf3_neb_run: records are due but the records buffer is NULL"
                                                 : "uf3_neb_run: a records buffer was given but no record is due");
     HIPCHK(c, hipSetDevice(c->device));
-    // the run's skin for its own duration, the caller's back on every way out
-    const double caller_skin = c->md.skin;
-    int rc = uf3_ctx_md_skin(c, skin);
-    if (rc) return rc;
-    rc = neb_run(r, max_steps, fmax, dt, dt_max, maxstep, climb, check_every, record_every, records);
-    if (rc) {
-        const std::string msg = c->err;
-        uf3_ctx_md_skin(c, caller_skin);
-        return fail(c, rc, msg);
-    }
-    return uf3_ctx_md_skin(c, caller_skin);
+    return with_run_skin(c, skin, [&] { return neb_run(r, max_steps, fmax, dt, dt_max, maxstep, climb, check_every, record_every, records); });
 }
 
 extern "C" int uf3_neb_get_state(uf3_neb *r, double *pos, double *forces, double *neb_forces, double *energies, int32_t *status,
@@ -4696,9 +4639,9 @@ extern "C" int uf3_neb_get_state(uf3_neb *r, double *pos, double *forces, double
     }
     if (neb_forces && !r->g_valid) {            // g of every band at these positions, frozen bands included; no state changes
         const NebChunkArgs P = neb_chunk_args(r, r->last_climb, 1);
-        hipLaunchKernelGGL(k_neb_partial, dim3((unsigned)r->n_blocks), dim3(UF3_RELAX_THREADS), 0, c->stream, P);
+        hipLaunchKernelGGL(k_neb_partial, dim3((unsigned)r->chunks.n_blocks), dim3(UF3_RELAX_THREADS), 0, c->stream, P);
         HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(k_neb_force, dim3((unsigned)r->n_blocks), dim3(UF3_RELAX_THREADS), 0, c->stream, P);
+        hipLaunchKernelGGL(k_neb_force, dim3((unsigned)r->chunks.n_blocks), dim3(UF3_RELAX_THREADS), 0, c->stream, P);
         HIPCHK(c, hipGetLastError());
         r->g_valid = true;
     }
@@ -4723,32 +4666,16 @@ extern "C" int uf3_neb_get_state(uf3_neb *r, double *pos, double *forces, double
 // the neighbour table depends on the positions alone (built on the host at creation and by uf3_mc_set_positions, O(N^2 images)
 // per frame: once per geometry, not per trial), the running energies start from the evaluator's (eval_impl, energies only: the
 // context's MD lists and skin are not touched) and follow the accepted differences.
-struct uf3_mc {
-    uf3_basis *b = nullptr;
-    uf3_ctx *c = nullptr;
-    int32_t n_frames = 0;
-    int64_t natoms = 0;
+struct uf3_mc : Batch {
     int max_frame = 0;                          // atoms of the largest frame
     bool has_mask = false, energy_valid = false;
     uint64_t trial = 0;                         // absolute index of the next trial (Philox counter)
-    std::vector<int64_t> offsets;
-    std::vector<double> cells, pos_host;
-    std::vector<uint8_t> pbc;
-    uf3_frames fr{};
-    std::vector<double> c1, c2, c3;
+    std::vector<double> pos_host;
     int s2z[UF3_MAX_SPECIES] = {0};
-    Buf pos, z, swappable, energies, accepted, trials, status, offsets_dev, kT, off2, off3, ent2, ent3, c1d, c2d, c3d, ring, prop, dE;
+    DevBuf swappable, accepted, trials, status, kT, off2, off3, ent2, ent3, c1d, c2d, c3d, ring, prop, dE;
 };
 
-extern "C" void uf3_mc_destroy(uf3_mc *m) {
-    if (!m) return;
-    hipSetDevice(m->c->device);
-    hipStreamSynchronize(m->c->stream);
-    for (Buf *p : {&m->pos, &m->z, &m->swappable, &m->energies, &m->accepted, &m->trials, &m->status, &m->offsets_dev, &m->kT, &m->off2,
-                   &m->off3, &m->ent2, &m->ent3, &m->c1d, &m->c2d, &m->c3d, &m->ring, &m->prop, &m->dE})
-        p->release();
-    delete m;
-}
+extern "C" void uf3_mc_destroy(uf3_mc *m) { driver_destroy(m); }
 
 // the geometry-only neighbour table of the object's positions: the evaluator's candidate set (images -fac .. fac of every atom of
 // the frame, image_delta's arithmetic) cut at the largest pair range and at the 3-body range, entries in supercell index order
@@ -4831,66 +4758,45 @@ static int mc_build_table(uf3_mc *m, const char *who) {
 
 extern "C" int uf3_mc_create(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const uint8_t *swappable,
                              const double *c1, const double *c2, const double *c3, uf3_mc **out) {
-    if (!b) return fail(nullptr, UF3_EINVAL, "uf3_mc_create: basis is NULL");
+    const char *who = "uf3_mc_create";
+    int64_t n = 0;
+    int rc = batch_check(b, fr, pos, z, c1, c2, c3, out, who, &n);
+    if (rc) return rc;
     uf3_ctx *c = b->ctx;
-    if (!out) return fail(c, UF3_EINVAL, "uf3_mc_create: out is NULL");
-    if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, "uf3_mc_create: bad uf3_frames");
-    if (!pos) return fail(c, UF3_EINVAL, "uf3_mc_create: pos is NULL");
-    if (!z) return fail(c, UF3_EINVAL, "uf3_mc_create: z is NULL");
-    if (!c1 || (b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, "uf3_mc_create: missing coefficients (c1 / c2 / c3)");
     const int nf = fr->n_frames;
-    if (fr->atom_offsets[0] != 0) return fail(c, UF3_EINVAL, "uf3_mc_create: atom_offsets[0] must be 0");
     int max_frame = 0;
     for (int f = 0; f < nf; f++) {
         const int64_t nfr = fr->atom_offsets[f + 1] - fr->atom_offsets[f];
-        if (nfr < 1) return fail(c, UF3_EINVAL, "uf3_mc_create: every frame needs an atom");
         if (nfr > UF3_MC_MAX_ATOMS)
             return fail(c, UF3_EINVAL, "uf3_mc_create: a frame holds more than " + std::to_string(UF3_MC_MAX_ATOMS) + " atoms (its species sit in LDS)");
         max_frame = std::max(max_frame, (int)nfr);
     }
-    const int64_t n = fr->atom_offsets[nf];
-    if (n >= (1LL << 28)) return fail(c, UF3_EINVAL, "uf3_mc_create: batch must hold 1 .. 2^28 atoms");
-    if (!md_finite(pos, 3 * (size_t)n)) return fail(c, UF3_EINVAL, "uf3_mc_create: pos must be finite");
-    if (!md_finite(fr->cells, 9 * (size_t)nf)) return fail(c, UF3_EINVAL, "uf3_mc_create: cells must be finite");
     for (int64_t i = 0; i < n; i++) {
         if (z[i] < 0 || z[i] >= 120 || b->host.z2s[z[i]] < 0) return fail(c, UF3_ESPECIES, "uf3_mc_create: element outside the basis");
         if (swappable && swappable[i] > 1) return fail(c, UF3_EINVAL, "uf3_mc_create: swappable must hold 0 or 1 per atom");
     }
     HIPCHK(c, hipSetDevice(c->device));
     uf3_mc *m = new uf3_mc();
-    m->b = b; m->c = c; m->n_frames = nf; m->natoms = n; m->max_frame = max_frame; m->has_mask = swappable != nullptr;
-    m->offsets.assign(fr->atom_offsets, fr->atom_offsets + nf + 1);
-    m->cells.assign(fr->cells, fr->cells + 9 * (size_t)nf);
-    m->pbc.assign(fr->pbc, fr->pbc + 3 * (size_t)nf);
+    m->max_frame = max_frame; m->has_mask = swappable != nullptr;
     m->pos_host.assign(pos, pos + 3 * (size_t)n);
-    m->fr.n_frames = nf; m->fr.atom_offsets = m->offsets.data(); m->fr.cells = m->cells.data(); m->fr.pbc = m->pbc.data();
-    const int S = b->host.S;
-    m->c1.assign(c1, c1 + S);
-    m->c2.assign(c2 ? c2 : c1, (c2 ? c2 : c1) + b->c2_len); m->c2.resize(b->c2_len + 8, 0.0);
-    m->c3.assign(c3 ? c3 : c1, (c3 ? c3 : c1) + b->c3_len); m->c3.resize(b->c3_len + 8, 0.0);
     for (int zz = 0; zz < 120; zz++)
         if (b->host.z2s[zz] >= 0 && b->host.z2s[zz] < UF3_MAX_SPECIES) m->s2z[b->host.z2s[zz]] = zz;
-    auto bail = [&](int rc) { const std::string msg = c->err; uf3_mc_destroy(m); return fail(c, rc, msg); };
-    if (m->pos.ensure(24 * (size_t)n) || m->z.ensure(4 * (size_t)n) || (swappable && m->swappable.ensure((size_t)n)) ||
-        m->energies.ensure(8 * (size_t)nf) || m->accepted.ensure(8 * (size_t)nf) || m->trials.ensure(8 * (size_t)nf) ||
-        m->status.ensure(4 * (size_t)nf) || m->offsets_dev.ensure(8 * (size_t)(nf + 1)) || m->kT.ensure(8 * (size_t)nf) ||
-        m->c1d.ensure(8 * m->c1.size()) || m->c2d.ensure(8 * m->c2.size()) || m->c3d.ensure(8 * m->c3.size())) {
-        fail(c, UF3_ENOMEM, "uf3_mc_create: out of device memory");
-        return bail(UF3_ENOMEM);
-    }
+    auto bail = [&](int rc) { uf3_mc_destroy(m); return rc; };
+    rc = batch_init(*m, b, fr, nullptr, z, c1, c2, c3, 8, who);     // (mc_build_table uploads the positions)
+    if (rc) return bail(rc);
+    if ((swappable && m->swappable.ensure((size_t)n)) || m->accepted.ensure(8 * (size_t)nf) || m->trials.ensure(8 * (size_t)nf) ||
+        m->status.ensure(4 * (size_t)nf) || m->kT.ensure(8 * (size_t)nf) || m->c1d.ensure(8 * m->c1.size()) ||
+        m->c2d.ensure(8 * m->c2.size()) || m->c3d.ensure(8 * m->c3.size()))
+        return bail(fail(c, UF3_ENOMEM, "uf3_mc_create: out of device memory"));
     hipStream_t s = c->stream;
-    if (hipMemcpyAsync(m->z.p, z, 4 * (size_t)n, hipMemcpyHostToDevice, s) ||
-        (swappable && hipMemcpyAsync(m->swappable.p, swappable, (size_t)n, hipMemcpyHostToDevice, s)) ||
+    if ((swappable && hipMemcpyAsync(m->swappable.p, swappable, (size_t)n, hipMemcpyHostToDevice, s)) ||
         hipMemsetAsync(m->energies.p, 0, 8 * (size_t)nf, s) || hipMemsetAsync(m->accepted.p, 0, 8 * (size_t)nf, s) ||
         hipMemsetAsync(m->trials.p, 0, 8 * (size_t)nf, s) || hipMemsetAsync(m->status.p, 0, 4 * (size_t)nf, s) ||
-        hipMemcpyAsync(m->offsets_dev.p, m->offsets.data(), 8 * (size_t)(nf + 1), hipMemcpyHostToDevice, s) ||
         hipMemcpyAsync(m->c1d.p, m->c1.data(), 8 * m->c1.size(), hipMemcpyHostToDevice, s) ||
         hipMemcpyAsync(m->c2d.p, m->c2.data(), 8 * m->c2.size(), hipMemcpyHostToDevice, s) ||
-        hipMemcpyAsync(m->c3d.p, m->c3.data(), 8 * m->c3.size(), hipMemcpyHostToDevice, s) || hipStreamSynchronize(s)) {
-        fail(c, UF3_EHIP, "uf3_mc_create: upload failed");
-        return bail(UF3_EHIP);
-    }
-    const int rc = mc_build_table(m, "uf3_mc_create");
+        hipMemcpyAsync(m->c3d.p, m->c3.data(), 8 * m->c3.size(), hipMemcpyHostToDevice, s) || hipStreamSynchronize(s))
+        return bail(fail(c, UF3_EHIP, "uf3_mc_create: upload failed"));
+    rc = mc_build_table(m, who);
     if (rc) return bail(rc);
     *out = m;
     return UF3_OK;
@@ -4899,8 +4805,7 @@ extern "C" int uf3_mc_create(uf3_basis *b, const uf3_frames *fr, const double *p
 // the evaluator's energies of the current species at the current positions, when the running energies do not describe them
 static int mc_energies(uf3_mc *m) {
     if (m->energy_valid) return UF3_OK;
-    const int rc = eval_impl(m->b, &m->fr, m->pos.as<double>(), m->z.as<int32_t>(), m->c1.data(), m->c2.data(), m->c3.data(),
-                             m->energies.as<double>(), nullptr, nullptr);
+    const int rc = batch_eval(*m, nullptr, nullptr);
     if (rc) return rc;
     m->energy_valid = true;
     return UF3_OK;

@@ -44,27 +44,6 @@ struct NebCoef {                            // what k_neb_move needs of its band
     int move, scale;
 };
 
-// NS - 1 sums and one NaN-sticky max (the last) over a 256-wide workgroup in a fixed order -> every lane's s[]
-template <int NS>
-__device__ __forceinline__ void neb_block_reduce(double (&s)[NS], double *lds) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < NS; k++) lds[k * UF3_RELAX_THREADS + t] = s[k];
-    __syncthreads();
-    for (int h = UF3_RELAX_THREADS / 2; h > 0; h >>= 1) {
-        if (t < h) {
-#pragma unroll
-            for (int k = 0; k < NS - 1; k++) lds[k * UF3_RELAX_THREADS + t] += lds[k * UF3_RELAX_THREADS + t + h];
-            lds[(NS - 1) * UF3_RELAX_THREADS + t] =
-                relax_nanmax(lds[(NS - 1) * UF3_RELAX_THREADS + t], lds[(NS - 1) * UF3_RELAX_THREADS + t + h]);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < NS; k++) s[k] = lds[k * UF3_RELAX_THREADS];
-    __syncthreads();                        // (the next reduction writes lds again)
-}
-
 struct NebChunkArgs {                       // k_neb_partial and k_neb_force
     const double *pos, *frc, *vel;         // [N][3]
     const uint8_t *fixed;                  // [N] or null
@@ -128,7 +107,7 @@ __global__ void __launch_bounds__(UF3_RELAX_THREADS) k_neb_partial(NebChunkArgs 
             s[9] = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
         }
     }
-    neb_block_reduce<UF3_NEB_NSUM>(s, lds);
+    relax_block_reduce<UF3_NEB_NSUM>(s, lds);
     if (t == 0) {
 #pragma unroll
         for (int k = 0; k < UF3_NEB_NSUM; k++) A.partial[UF3_NEB_NSUM * b + k] = s[k];
@@ -164,7 +143,7 @@ __global__ void __launch_bounds__(UF3_RELAX_THREADS) k_neb_force(NebChunkArgs A)
         for (int k = 0; k < UF3_NEB_NSUM - 1; k++) s[k] += A.partial[UF3_NEB_NSUM * c + k];
         s[10] = relax_nanmax(s[10], A.partial[UF3_NEB_NSUM * c + 10]);
     }
-    neb_block_reduce<UF3_NEB_NSUM>(s, lds);
+    relax_block_reduce<UF3_NEB_NSUM>(s, lds);
     int bad = (s[10] != s[10]) ? UF3_NEB_BAD_FORCE : 0;
     const long long i = A.blk_lo[b] + t;
     const bool mine = t < A.blk_n[b];
@@ -216,7 +195,7 @@ __global__ void __launch_bounds__(UF3_RELAX_THREADS) k_neb_force(NebChunkArgs A)
         for (int k = 0; k < 3; k++) A.g[3 * i + k] = g[k];
         m2[0] = g[0] * g[0] + g[1] * g[1] + g[2] * g[2];
     }
-    neb_block_reduce<1>(m2, lds);
+    relax_block_reduce<1>(m2, lds);
     if (t == 0) A.cmax[b] = m2[0];
 }
 
@@ -245,7 +224,7 @@ __global__ void __launch_bounds__(UF3_RELAX_THREADS) k_neb_band(NebBandArgs A) {
         double m2[1] = {0.0};
         for (int c = A.frame_blk[f0 + 1] + t; c < A.frame_blk[f0 + M - 1]; c += UF3_RELAX_THREADS)
             m2[0] = relax_nanmax(m2[0], A.cmax[c]);
-        neb_block_reduce<1>(m2, lds);
+        relax_block_reduce<1>(m2, lds);
         for (int j = t; j < M; j += UF3_RELAX_THREADS) A.e_last[f0 + j] = A.energies[f0 + j];
         if (t == 0) {
             double GV = 0.0, GG = 0.0, VV = 0.0;

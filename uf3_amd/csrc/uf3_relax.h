@@ -52,22 +52,25 @@ struct RelaxPartialArgs {
 
 __device__ __forceinline__ double relax_nanmax(double x, double y) { return (x != x || y != y) ? (x + y) : (x > y ? x : y); }
 
-// three sums and one NaN-sticky max over a 256-wide workgroup in a fixed order -> every lane's s[]
-__device__ __forceinline__ void relax_block_reduce(double (&s)[4], double *lds) {
+// NS - 1 sums and one NaN-sticky max (the last) over a 256-wide workgroup in a fixed order -> every lane's s[] (uf3_neb.h's too)
+template <int NS>
+__device__ __forceinline__ void relax_block_reduce(double (&s)[NS], double *lds) {
     const int t = threadIdx.x;
 #pragma unroll
-    for (int k = 0; k < 4; k++) lds[k * UF3_RELAX_THREADS + t] = s[k];
+    for (int k = 0; k < NS; k++) lds[k * UF3_RELAX_THREADS + t] = s[k];
     __syncthreads();
     for (int h = UF3_RELAX_THREADS / 2; h > 0; h >>= 1) {
         if (t < h) {
 #pragma unroll
-            for (int k = 0; k < 3; k++) lds[k * UF3_RELAX_THREADS + t] += lds[k * UF3_RELAX_THREADS + t + h];
-            lds[3 * UF3_RELAX_THREADS + t] = relax_nanmax(lds[3 * UF3_RELAX_THREADS + t], lds[3 * UF3_RELAX_THREADS + t + h]);
+            for (int k = 0; k < NS - 1; k++) lds[k * UF3_RELAX_THREADS + t] += lds[k * UF3_RELAX_THREADS + t + h];
+            lds[(NS - 1) * UF3_RELAX_THREADS + t] =
+                relax_nanmax(lds[(NS - 1) * UF3_RELAX_THREADS + t], lds[(NS - 1) * UF3_RELAX_THREADS + t + h]);
         }
         __syncthreads();
     }
 #pragma unroll
-    for (int k = 0; k < 4; k++) s[k] = lds[k * UF3_RELAX_THREADS];
+    for (int k = 0; k < NS; k++) s[k] = lds[k * UF3_RELAX_THREADS];
+    __syncthreads();                        // (the next reduction writes lds again)
 }
 
 // g = F D^T of a cell frame (row vector times D transposed), else F; zero for a fixed atom

@@ -18,35 +18,18 @@ Random numbers are counter-based (Philox4x32-10 on (frame, absolute trial), keye
 ``run(a + b)`` bit for bit, and a frame's chain does not depend on the batch around it.  Hybrid MC / MD: alternate with
 ``md.MolecularDynamics`` through ``set_positions`` (which rebuilds the neighbour table).
 """
-import ctypes as C
 import numbers
-import os
 
 import numpy as np
 
 from uf3_amd import _lib
+from uf3_amd.forcefield._driver import Driver, check_int, check_mask, frames_of
 from uf3_amd.data.composition import atomic_numbers, chemical_symbols
 
 KB = 8.617333262e-5              # eV / K
 MODES = {"swap": 0, "transmute": 1}
 STATUS = {0: "running", 2: "nonfinite"}
-
-
-def _frames_of(atoms_or_list):
-    frames = list(atoms_or_list) if isinstance(atoms_or_list, (list, tuple)) else [atoms_or_list]
-    if not frames:
-        raise ValueError("MonteCarlo: no frames")
-    for k, a in enumerate(frames):
-        if len(a) < 1:
-            raise ValueError(f"MonteCarlo: frame {k} has no atoms")
-    return frames
-
-
-def _check_int(name, value, lo=0, hi=None):
-    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or value < lo or (hi is not None and value > hi):
-        raise ValueError(f"MonteCarlo: {name} must be an integer >= {lo}" + (f" and <= {hi}" if hi is not None else "")
-                         + f", got {value!r}")
-    return int(value)
+WHO = "MonteCarlo"
 
 
 def _temperatures(temperature_K, n_frames):
@@ -97,18 +80,6 @@ def _chemical_potentials(mode, chemical_potentials, element_list):
     return np.ascontiguousarray(mu)
 
 
-def _swappable_mask(swappable, n_atoms):
-    if swappable is None:
-        return None
-    m = np.asarray(swappable)
-    if m.dtype != bool:
-        raise ValueError("MonteCarlo: swappable must be a boolean mask over the concatenated atoms")
-    m = m.reshape(-1)
-    if m.size != n_atoms:
-        raise ValueError(f"MonteCarlo: swappable holds {m.size} entries for {n_atoms} atoms")
-    return np.ascontiguousarray(m.astype(np.uint8))
-
-
 def run_records(raw, first_trial, every):
     """The dict ``run`` returns from raw records [n_rec, n_frames, 3 + S] ([E, accepted, trials, atoms of each species]):
     ``trial`` [n_rec] (absolute index of the object's trial counter after the record's trial), ``energy`` [n_rec, n_frames]
@@ -121,19 +92,20 @@ def run_records(raw, first_trial, every):
                 trials=np.rint(raw[..., 2]).astype(np.int64), composition=np.rint(raw[..., 3:]).astype(np.int64))
 
 
-class MonteCarlo:
+class MonteCarlo(Driver):
+    KIND, WHO = "mc", WHO
+
     def __init__(self, calculator, atoms_or_list, temperature_K, mode="swap", chemical_potentials=None, swappable=None, seed=0,
                  device=None):
         """``temperature_K``: a scalar or one value per frame.  ``swappable``: boolean mask [sum N] over the concatenated
         frames; atoms outside it keep their species.  ``chemical_potentials``: see the module text."""
-        self.handle = None
         # every argument is checked before the device is touched
         if mode not in MODES:
             raise ValueError(f"MonteCarlo: mode must be 'swap' or 'transmute', got {mode!r}")
         self.mode = mode
-        self.seed = _check_int("seed", seed, 0, (1 << 64) - 1)
+        self.seed = check_int(WHO, "seed", seed, 0, (1 << 64) - 1)
         self._list = isinstance(atoms_or_list, (list, tuple))
-        self.frames = _frames_of(atoms_or_list)
+        self.frames = frames_of(WHO, atoms_or_list)
         self.calculator = calculator
         self.element_list = list(calculator.bspline_config.element_list)
         self.temperature_K = _temperatures(temperature_K, len(self.frames))
@@ -148,52 +120,17 @@ class MonteCarlo:
         if foreign:
             raise ValueError("MonteCarlo: the frames hold elements outside the model: "
                              + ", ".join(chemical_symbols[q] if 0 < q < len(chemical_symbols) else str(q) for q in foreign))
-        self.swappable = _swappable_mask(swappable, self._batch.n_atoms)
+        self.swappable = check_mask(WHO, "swappable", swappable, self._batch.n_atoms)
         self.n_atoms = np.diff(self._batch.offsets).astype(np.int64)
         self.trial = 0
-        self.ctx = _lib.get_context(calculator.device if device is None else device)
-        self._dbasis = _lib.device_basis(calculator.bspline_config, self.ctx)
-        self._pid = os.getpid()
-        h = C.c_void_p()
-        self.ctx.check(self.ctx.lib.uf3_mc_create(self._dbasis.handle, C.byref(self._batch.struct), _lib._p(self._batch.pos),
-                                                  _lib._p(self._batch.z), _lib._p(self.swappable), _lib._p(calculator._c1),
-                                                  _lib._p(calculator._c2), _lib._p(calculator._c3), C.byref(h)))
-        self.handle = h
-
-    # ---- lifecycle --------------------------------------------------------------------------------------------------------
-    def _live(self):
-        if not self.handle:
-            raise RuntimeError("MonteCarlo: the object is closed")
-        return self.handle
-
-    def close(self):
-        if getattr(self, "handle", None):
-            if os.getpid() == self._pid and self.ctx.handle:
-                self.ctx.lib.uf3_mc_destroy(self.handle)
-            self.handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(calculator, device, [_lib._p(self._batch.pos), _lib._p(self._batch.z), _lib._p(self.swappable)])
 
     # ---- state ------------------------------------------------------------------------------------------------------------
     def _state(self, *which):
         nf, n = self._batch.n_frames, self._batch.n_atoms
         shapes = dict(z=((n,), np.int32), energies=((nf,), float), accepted=((nf,), np.int64), trials=((nf,), np.int64),
                       status=((nf,), np.int32))
-        out = {k: np.empty(*shapes[k]) for k in which}
-        args = [_lib._p(out[k]) if k in out else None for k in shapes]
-        self.ctx.check(self.ctx.lib.uf3_mc_get_state(self._live(), *args))
-        return out
+        return self._fetch(shapes, which)
 
     @property
     def numbers(self):
@@ -270,13 +207,13 @@ class MonteCarlo:
         ``trials`` [n_frames] (totals so far; null trials -- like species, the same atom twice, an atom outside ``swappable``
         -- are counted and never accepted), ``composition`` [n_frames, S] (atoms per species, element-list order), ``status``;
         with ``record_every`` > 0 also ``records`` (``run_records``) after every ``record_every``-th trial of this run."""
-        n_trials = _check_int("n_trials", n_trials)
-        every = _check_int("record_every", record_every)
+        n_trials = check_int(WHO, "n_trials", n_trials)
+        every = check_int(WHO, "record_every", record_every)
         temps = _temperatures(self.temperature_K, self._batch.n_frames)
         mu = self.chemical_potentials
         if (self.mode == "transmute") != (mu is not None):
             raise ValueError("MonteCarlo: chemical_potentials belong to mode='transmute', and that mode needs them")
-        seed = _check_int("seed", self.seed, 0, (1 << 64) - 1)
+        seed = check_int(WHO, "seed", self.seed, 0, (1 << 64) - 1)
         handle = self._live()
         n_rec = n_trials // every if every else 0
         raw = np.zeros((n_rec, self._batch.n_frames, 3 + len(self.element_list)))

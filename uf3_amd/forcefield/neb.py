@@ -21,32 +21,13 @@ status ``"nonfinite"``.
 ``run`` may be called again: the FIRE state carries over, and ``run(a); run(b)`` follows ``run(a + b)``.  A band that converged
 is tested again by the next run, whose ``fmax`` and ``climb`` may differ, and moves only if it fails that test.
 """
-import ctypes as C
-import numbers
-import os
-
 import numpy as np
 
 from uf3_amd import _lib
+from uf3_amd.forcefield._driver import Driver, check_int, check_mask, check_real
 from uf3_amd.forcefield.relax import STATUS
 
-
-def _check_real(name, value, lo=0.0, strict=False, hi=None):
-    try:
-        x = float(value)
-    except (TypeError, ValueError):
-        raise ValueError(f"NudgedElasticBand: {name} must be a number") from None
-    if not np.isfinite(x) or (x <= lo if strict else x < lo) or (hi is not None and x > hi):
-        bound = f"> {lo}" if strict else f">= {lo}"
-        raise ValueError(f"NudgedElasticBand: {name} must be finite and {bound}" + (f" and <= {hi}" if hi is not None else "")
-                         + f", got {value!r}")
-    return x
-
-
-def _check_int(name, value, lo=0):
-    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or value < lo:
-        raise ValueError(f"NudgedElasticBand: {name} must be an integer >= {lo}, got {value!r}")
-    return int(value)
+WHO = "NudgedElasticBand"
 
 
 def _axes(cell, pbc):
@@ -65,7 +46,7 @@ def interpolate(initial, final, n_images, mic=True):
     ``mic`` the displacement ``final - initial`` is wrapped to the minimum image along the periodic axes once, and the last
     image is ``initial + d``, unwrapped: neighbouring images then differ by d / (n_images - 1) as stored."""
     from uf3_amd.data.atoms import Atoms
-    n_images = _check_int("n_images", n_images, 2)
+    n_images = check_int(WHO, "n_images", n_images, 2)
     if len(initial) != len(final):
         raise ValueError(f"interpolate: the end points hold {len(initial)} and {len(final)} atoms")
     z = np.asarray(initial.get_atomic_numbers())
@@ -117,15 +98,16 @@ def _check_band(k, band):
             raise ValueError(f"NudgedElasticBand: band {k}, image {j}: positions identical to image {j - 1}")
 
 
-class NudgedElasticBand:
+class NudgedElasticBand(Driver):
+    KIND, WHO = "neb", WHO
+
     def __init__(self, calc, bands, spring=0.1, fixed=None, skin=0.5, device=None):
         """``bands``: one band (a list of ``Atoms``) or a list of bands.  ``spring`` (eV / Angstrom^2): a scalar or one value
         per band.  ``fixed``: boolean mask [sum N] over the concatenated images of all bands (ASE's FixAtoms), the same in
         every image of a band: those atoms feel no force, never move and do not enter tangents or spring lengths.  ``skin``
         (Angstrom): the evaluator's neighbour-list skin during runs."""
-        self.handle = None
         # every argument is checked before the device is touched
-        self.skin = _check_real("skin", skin, hi=4.0)
+        self.skin = check_real(WHO, "skin", skin, hi=4.0)
         self._single, self.bands = _bands_of(bands)
         for k, band in enumerate(self.bands):
             _check_band(k, band)
@@ -146,65 +128,24 @@ class NudgedElasticBand:
             raise ValueError("NudgedElasticBand: positions must be finite")
         if not np.all(np.isfinite(self._batch.cells)):
             raise ValueError("NudgedElasticBand: cells must be finite")
-        self.fixed = None
-        if fixed is not None:
-            m = np.asarray(fixed)
-            if m.dtype != bool:
-                raise ValueError("NudgedElasticBand: fixed must be a boolean mask over the concatenated atoms")
-            m = m.reshape(-1)
-            if m.size != self._batch.n_atoms:
-                raise ValueError(f"NudgedElasticBand: fixed holds {m.size} entries for {self._batch.n_atoms} atoms")
+        self.fixed = check_mask(WHO, "fixed", fixed, self._batch.n_atoms)
+        if self.fixed is not None:
+            m = self.fixed
             off = self._batch.offsets
             for k in range(nb):
                 f0, f1 = self.band_first[k], self.band_first[k + 1]
                 for f in range(f0 + 1, f1):
                     if not np.array_equal(m[off[f]:off[f + 1]], m[off[f0]:off[f0 + 1]]):
                         raise ValueError(f"NudgedElasticBand: band {k}, image {f - f0}: fixed mask differs from image 0")
-            self.fixed = np.ascontiguousarray(m.astype(np.uint8))
-        self.ctx = _lib.get_context(calc.device if device is None else device)
-        self._dbasis = _lib.device_basis(calc.bspline_config, self.ctx)
-        self._pid = os.getpid()
-        h = C.c_void_p()
-        self.ctx.check(self.ctx.lib.uf3_neb_create(self._dbasis.handle, C.byref(self._batch.struct), _lib._p(self._batch.pos),
-                                                   _lib._p(self._batch.z), _lib._p(self.fixed), _lib._p(calc._c1),
-                                                   _lib._p(calc._c2), _lib._p(calc._c3), nb, _lib._p(self.band_first),
-                                                   _lib._p(self.spring), C.byref(h)))
-        self.handle = h
-
-    # ---- lifecycle --------------------------------------------------------------------------------------------------------
-    def _live(self):
-        if not self.handle:
-            raise RuntimeError("NudgedElasticBand: the object is closed")
-        return self.handle
-
-    def close(self):
-        if getattr(self, "handle", None):
-            if os.getpid() == self._pid and self.ctx.handle:
-                self.ctx.lib.uf3_neb_destroy(self.handle)
-            self.handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(calc, device, [_lib._p(self._batch.pos), _lib._p(self._batch.z), _lib._p(self.fixed)],
+                     [nb, _lib._p(self.band_first), _lib._p(self.spring)])
 
     # ---- state ------------------------------------------------------------------------------------------------------------
     def _state(self, *which):
         nf, n, nb = self._batch.n_frames, self._batch.n_atoms, len(self.bands)
         shapes = dict(pos=((n, 3), float), forces=((n, 3), float), neb_forces=((n, 3), float), energies=((nf,), float),
                       status=((nb,), np.int32), steps=((nb,), np.int64), criterion=((nb,), float), climbing=((nb,), np.int32))
-        out = {k: np.empty(*shapes[k]) for k in which}
-        args = [_lib._p(out[k]) if k in out else None for k in shapes]
-        self.ctx.check(self.ctx.lib.uf3_neb_get_state(self._live(), *args))
-        return out
+        return self._fetch(shapes, which)
 
     def _per_band(self, x):
         return [x[self.band_first[k]:self.band_first[k + 1]].copy() for k in range(len(self.bands))]
@@ -245,16 +186,16 @@ class NudgedElasticBand:
         with ``record_every`` > 0 also ``records``: ``iteration`` [n_rec], ``energies`` [n_rec, n_frames], ``criterion`` and
         ``climbing_image`` [n_rec, n_bands] of evaluations 0, record_every, ... (after every band stopped, the final values
         repeat)."""
-        max_steps = _check_int("max_steps", max_steps)
-        fmax = _check_real("fmax", fmax, strict=True)
+        max_steps = check_int(WHO, "max_steps", max_steps)
+        fmax = check_real(WHO, "fmax", fmax, strict=True)
         if not isinstance(climb, (bool, np.bool_)):
             raise ValueError(f"NudgedElasticBand: climb must be True or False, got {climb!r}")
-        dt = _check_real("dt", dt, strict=True)
-        dt_max = _check_real("dt_max", dt_max, strict=True)
-        maxstep = _check_real("maxstep", maxstep, strict=True)
-        check_every = _check_int("check_every", check_every, 1)
-        record_every = _check_int("record_every", record_every)
-        skin = _check_real("skin", self.skin, hi=4.0)
+        dt = check_real(WHO, "dt", dt, strict=True)
+        dt_max = check_real(WHO, "dt_max", dt_max, strict=True)
+        maxstep = check_real(WHO, "maxstep", maxstep, strict=True)
+        check_every = check_int(WHO, "check_every", check_every, 1)
+        record_every = check_int(WHO, "record_every", record_every)
+        skin = check_real(WHO, "skin", self.skin, hi=4.0)
         handle = self._live()
         nf, nb = self._batch.n_frames, len(self.bands)
         n_rec = max_steps // record_every + 1 if record_every else 0

@@ -19,122 +19,46 @@ forces freeze a frame with status ``"nonfinite"``.
 unwrapped.  Cell runs wait for the device on every step (the evaluator reads the cells on the host) and rebuild their
 neighbour lists every step; positions-only runs look at the device every ``check_every`` steps.
 """
-import ctypes as C
-import numbers
-import os
-
 import numpy as np
 
 from uf3_amd import _lib
+from uf3_amd.forcefield._driver import Driver, check_int, check_mask, check_real, frames_of
 
 STATUS = {0: "running", 1: "converged", 2: "nonfinite"}
+WHO = "Relaxation"
 
 
-def _frames_of(atoms_or_list):
-    frames = list(atoms_or_list) if isinstance(atoms_or_list, (list, tuple)) else [atoms_or_list]
-    if not frames:
-        raise ValueError("Relaxation: no frames")
-    for k, a in enumerate(frames):
-        if len(a) < 1:
-            raise ValueError(f"Relaxation: frame {k} has no atoms")
-    return frames
+class Relaxation(Driver):
+    KIND, WHO = "relax", WHO
 
-
-def _check_real(name, value, lo=0.0, strict=False, hi=None):
-    try:
-        x = float(value)
-    except (TypeError, ValueError):
-        raise ValueError(f"Relaxation: {name} must be a number") from None
-    if not np.isfinite(x) or (x <= lo if strict else x < lo) or (hi is not None and x > hi):
-        bound = f"> {lo}" if strict else f">= {lo}"
-        raise ValueError(f"Relaxation: {name} must be finite and {bound}" + (f" and <= {hi}" if hi is not None else "")
-                         + f", got {value!r}")
-    return x
-
-
-def _check_int(name, value, lo=0):
-    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or value < lo:
-        raise ValueError(f"Relaxation: {name} must be an integer >= {lo}, got {value!r}")
-    return int(value)
-
-
-def _fixed_mask(fixed, n_atoms):
-    if fixed is None:
-        return None
-    m = np.asarray(fixed)
-    if m.dtype != bool:
-        raise ValueError("Relaxation: fixed must be a boolean mask over the concatenated atoms")
-    m = m.reshape(-1)
-    if m.size != n_atoms:
-        raise ValueError(f"Relaxation: fixed holds {m.size} entries for {n_atoms} atoms")
-    return np.ascontiguousarray(m.astype(np.uint8))
-
-
-class Relaxation:
     def __init__(self, calc, atoms_or_list, relax_cell=False, fixed=None, skin=0.5, device=None):
         """``fixed``: boolean mask [sum N] over the concatenated frames (ASE's FixAtoms): those atoms feel no force and never
         move; not together with ``relax_cell``.  ``skin`` (Angstrom): the evaluator's neighbour-list skin in positions-only
         runs (cell runs use 0)."""
-        self.handle = None
         # every argument is checked before the device is touched
         if not isinstance(relax_cell, (bool, np.bool_)):
             raise ValueError(f"Relaxation: relax_cell must be True or False, got {relax_cell!r}")
         self.relax_cell = bool(relax_cell)
-        self.skin = _check_real("skin", skin, hi=4.0)
+        self.skin = check_real(WHO, "skin", skin, hi=4.0)
         self._list = isinstance(atoms_or_list, (list, tuple))
-        self.frames = _frames_of(atoms_or_list)
+        self.frames = frames_of(WHO, atoms_or_list)
         self.calculator = calc
         self._batch = _lib.FrameBatch(self.frames)
         if not np.all(np.isfinite(self._batch.pos)):
             raise ValueError("Relaxation: positions must be finite")
         if not np.all(np.isfinite(self._batch.cells)):
             raise ValueError("Relaxation: cells must be finite")
-        self.fixed = _fixed_mask(fixed, self._batch.n_atoms)
+        self.fixed = check_mask(WHO, "fixed", fixed, self._batch.n_atoms)
         if self.fixed is not None and self.relax_cell:
             raise ValueError("Relaxation: fixed atoms together with relax_cell are not supported")
-        self.ctx = _lib.get_context(calc.device if device is None else device)
-        self._dbasis = _lib.device_basis(calc.bspline_config, self.ctx)
-        self._pid = os.getpid()
-        h = C.c_void_p()
-        self.ctx.check(self.ctx.lib.uf3_relax_create(self._dbasis.handle, C.byref(self._batch.struct), _lib._p(self._batch.pos),
-                                                     _lib._p(self._batch.z), _lib._p(self.fixed), _lib._p(calc._c1),
-                                                     _lib._p(calc._c2), _lib._p(calc._c3), int(self.relax_cell), C.byref(h)))
-        self.handle = h
-
-    # ---- lifecycle --------------------------------------------------------------------------------------------------------
-    def _live(self):
-        if not self.handle:
-            raise RuntimeError("Relaxation: the object is closed")
-        return self.handle
-
-    def close(self):
-        if getattr(self, "handle", None):
-            if os.getpid() == self._pid and self.ctx.handle:
-                self.ctx.lib.uf3_relax_destroy(self.handle)
-            self.handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(calc, device, [_lib._p(self._batch.pos), _lib._p(self._batch.z), _lib._p(self.fixed)], [int(self.relax_cell)])
 
     # ---- state ------------------------------------------------------------------------------------------------------------
     def _state(self, *which):
         nf, n = self._batch.n_frames, self._batch.n_atoms
         shapes = dict(pos=((n, 3), float), cells=((nf, 3, 3), float), forces=((n, 3), float), energies=((nf,), float),
                       status=((nf,), np.int32), steps=((nf,), np.int64), fmax=((nf,), float))
-        out = {k: np.empty(*shapes[k]) for k in which}
-        args = [_lib._p(out[k]) if k in out else None for k in shapes]
-        self.ctx.check(self.ctx.lib.uf3_relax_get_state(self._live(), *args))
-        return out
+        return self._fetch(shapes, which)
 
     def get_positions(self):
         """[N, 3] Angstrom, frames concatenated, unwrapped."""
@@ -168,14 +92,14 @@ class Relaxation:
         all runs so far), ``energy`` and ``fmax`` (the criterion) at the last evaluation; with ``record_every`` > 0 also
         ``records``: ``iteration`` [n_rec] and ``energy`` / ``fmax`` [n_rec, n_frames] of evaluations 0, record_every, ...
         (after every frame stopped, the final values repeat)."""
-        max_steps = _check_int("max_steps", max_steps)
-        fmax = _check_real("fmax", fmax, strict=True)
-        dt = _check_real("dt", dt, strict=True)
-        dt_max = _check_real("dt_max", dt_max, strict=True)
-        maxstep = _check_real("maxstep", maxstep, strict=True)
-        check_every = _check_int("check_every", check_every, 1)
-        record_every = _check_int("record_every", record_every)
-        skin = _check_real("skin", self.skin, hi=4.0)
+        max_steps = check_int(WHO, "max_steps", max_steps)
+        fmax = check_real(WHO, "fmax", fmax, strict=True)
+        dt = check_real(WHO, "dt", dt, strict=True)
+        dt_max = check_real(WHO, "dt_max", dt_max, strict=True)
+        maxstep = check_real(WHO, "maxstep", maxstep, strict=True)
+        check_every = check_int(WHO, "check_every", check_every, 1)
+        record_every = check_int(WHO, "record_every", record_every)
+        skin = check_real(WHO, "skin", self.skin, hi=4.0)
         handle = self._live()
         n_rec = max_steps // record_every + 1 if record_every else 0
         raw = np.zeros((n_rec, self._batch.n_frames, 2))
