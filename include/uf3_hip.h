@@ -106,7 +106,7 @@ int uf3_ctx_use_own_stream(uf3_ctx *ctx);
 int uf3_ctx_synchronize(uf3_ctx *ctx);
 const char *uf3_last_error(const uf3_ctx *ctx);
 /* Which sources this binary was compiled from: the first 16 hex digits of the sha256 over uf3_hip.hip, uf3_kernels.h,
- * uf3_feat3.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h, uf3_npt.h, uf3_neb.h, uf3_mc.h, uf3_flux.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
+ * uf3_feat3.h, uf3_virial_rows.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h, uf3_npt.h, uf3_neb.h, uf3_mc.h, uf3_flux.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
  * outside it).  __graft_entry__.build() rebuilds when it differs from the tree's, smoke() prints it. */
 const char *uf3_build_id(void);
 /* timing of the dominant kernel: (re)start / read accumulated HIP-event time in ms and launches */
@@ -204,6 +204,23 @@ int uf3_featurize(uf3_basis *basis, const uf3_frames *frames, const double *pos 
                   const int32_t *z /*[sumN]*/, double *x_e, double *x_f);
 int uf3_featurize_dev(uf3_basis *basis, const uf3_frames *frames, const double *d_pos,
                       const int32_t *d_z, double *d_x_e, double *d_x_f);
+/*
+ * Virial rows: the strain derivative of the (unnormalised) energy row, six more rows of the design matrix per frame
+ * (uf3_amd/csrc/uf3_virial_rows.h).
+ *   x_v [n_frames][6][F]   Voigt order xx, yy, zz, yz, xz, xy, the convention of uf3_eval_virial: d x_e / d t for the strain
+ *                          eps_aa = t, or eps_ab = eps_ba = t / 2 off the diagonal, applied to cell and positions alike;
+ *                          x_v[f] @ c is what uf3_eval_virial returns for the coefficients c.  One-body columns and every
+ *                          column the energy row leaves at zero are zero.
+ * x_e and x_f may be NULL; when given they are what uf3_featurize[_dev] writes, by the same launches.  A batch with an atom
+ * far outside its cell (the batches whose 3-body force rows take the reference's image-range rule) is refused with
+ * UF3_EINVAL: wrap the atoms first.  Capacity overflow as in uf3_featurize: the host entry grows and repeats, the device entry
+ * reports UF3_ERETRY at a later call once the context knows its capacities (and the refusal above likewise, then).
+ * With UF3_DEBUG_LDS set every launch reports "uf3 virial rows mode M: lds .. B, rows in lds|hbm ..." on stderr.
+ */
+int uf3_featurize_virial(uf3_basis *basis, const uf3_frames *frames, const double *pos, const int32_t *z,
+                         double *x_e, double *x_f, double *x_v /* [n_frames][6][F] */);
+int uf3_featurize_virial_dev(uf3_basis *basis, const uf3_frames *frames, const double *d_pos, const int32_t *d_z,
+                             double *d_x_e, double *d_x_f, double *d_x_v);
 /* The same with the force rows `ld` doubles apart (ld >= F; columns F .. ld of a row are left alone), the layout uf3_gram_dev
  * and uf3_gram_force_rows_dev read through their own `ld`: with ld a multiple of 16 every row starts on a 128-byte line --
  * rows of F = 434 or 1798 doubles do not, and the partial lines at the ends of a row's column segments are written twice

@@ -36,10 +36,11 @@ EXPORTS = ["uf3_ctx_create", "uf3_ctx_destroy", "uf3_ctx_set_stream", "uf3_ctx_s
            "uf3_mc_create", "uf3_mc_destroy", "uf3_mc_run", "uf3_mc_delta", "uf3_mc_set_positions", "uf3_mc_get_state",
            "uf3_phonon_mesh", "uf3_phonon_mesh_dev", "uf3_phonon_dos", "uf3_phonon_dos_dev", "uf3_phonon_thermo",
            "uf3_phonon_thermo_dev",
-           "uf3_site_terms", "uf3_site_terms_dev", "uf3_heat_flux", "uf3_heat_flux_dev", "uf3_md_run_flux"]
+           "uf3_site_terms", "uf3_site_terms_dev", "uf3_heat_flux", "uf3_heat_flux_dev", "uf3_md_run_flux",
+           "uf3_featurize_virial", "uf3_featurize_virial_dev"]
 
 
-SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_device.h", "uf3_md.h", "uf3_hessian.h", "uf3_relax.h", "uf3_phonon.h", "uf3_npt.h", "uf3_neb.h", "uf3_mc.h", "uf3_flux.h", os.path.join("..", "..", "include", "uf3_hip.h"))
+SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_virial_rows.h", "uf3_device.h", "uf3_md.h", "uf3_hessian.h", "uf3_relax.h", "uf3_phonon.h", "uf3_npt.h", "uf3_neb.h", "uf3_mc.h", "uf3_flux.h", os.path.join("..", "..", "include", "uf3_hip.h"))
 
 
 def source_build_id(csrc_dir=None):
@@ -173,6 +174,8 @@ def load():
         for name in ("uf3_featurize", "uf3_featurize_dev"):
             getattr(lib, name).argtypes = [vp, C.POINTER(Frames), vp, vp, vp, vp]
         lib.uf3_featurize_ld_dev.argtypes = [vp, C.POINTER(Frames), vp, vp, vp, vp, i64]
+        for name in ("uf3_featurize_virial", "uf3_featurize_virial_dev"):
+            getattr(lib, name).argtypes = [vp, C.POINTER(Frames), vp, vp, vp, vp, vp]
         for name in ("uf3_gram", "uf3_gram_dev"):
             getattr(lib, name).argtypes = [vp, vp, vp, i64, i32, i64, C.c_int, vp, vp]
         for name in ("uf3_eval", "uf3_eval_dev"):

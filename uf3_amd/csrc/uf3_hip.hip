@@ -18,6 +18,7 @@
 #include "../../include/uf3_hip.h"
 #include "uf3_kernels.h"
 #include "uf3_feat3.h"
+#include "uf3_virial_rows.h"
 #include "uf3_md.h"
 #include "uf3_npt.h"
 #include "uf3_hessian.h"
@@ -115,7 +116,9 @@ struct uf3_ctx {
     bool n3_tuned = false;           // capacity re-sized once to the lists actually seen
     bool cand_tuned = false;         // a featurizer call has completed with the current candidate capacity
     // status words of asynchronous featurizer calls: copied to pinned slots behind the launches, looked at later
-    struct Pending { hipEvent_t ev = nullptr; int cap = 0, cand = 0, xcap = 0; bool has3 = false, img = true, img_launch = false, live = false; };
+    struct Pending { hipEvent_t ev = nullptr; int cap = 0, cand = 0, xcap = 0; bool has3 = false, img = true, img_launch = false, live = false;
+                     bool virial = false;      // the call wrote virial rows (uf3_featurize_virial_dev): atoms far outside their cell are refused
+    };
     enum { N_PENDING = 16 };
     Pending pending_chk[N_PENDING];
     PinBuf pin_flags;                // [N_PENDING][8] ints
@@ -213,6 +216,7 @@ struct uf3_basis {
     bool dense_grouped[16] = {false}; // a trio of the mode stages grouped n windows (even-aligned groups: up to two padding records per pass)
     int dense_dump[16] = {0};        // ... smallest stage (doubles) the fold of its widest window needs
     int modes = 1;                   // bit m set: some trio block is handled by featurizer specialisation m
+    int vmodes = 0;                  // bit m set (1 .. 5): some trio block is handled by instance m of k_virial_rows
     double r_cut = 0;
     // k_featurize3 (3-body force rows by bond factorisation, uf3_feat3.h): eligibility and tables
     bool feat3_ok = false;
@@ -693,6 +697,7 @@ extern "C" int uf3_basis_create(uf3_ctx *c, const uf3_basis_spec *s, uf3_basis *
             if (i2 <= i_hi) td.thr2 = tn[i2];
         }
         b->modes |= 1 << (td.dense ? td.dense : td.nsrc == 1 ? (td.ncol > WAVE ? 2 : 1) : (td.nsrc == 2 ? (td.ncol > WAVE ? 4 : 3) : 5));
+        b->vmodes |= 1 << (td.nsrc == 1 ? (td.ncol > WAVE ? 2 : 1) : (td.nsrc == 2 ? (td.ncol > WAVE ? 4 : 3) : 5));
         for (auto &v : per_col) for (int k = 0; k < td.nsrc; k++) {
             int sp = k < (int)v.size() ? v[k] : -1;
             colsrc.push_back(sp);
@@ -1141,6 +1146,7 @@ struct Prepared {
     bool small_prepared = false; // ... by the one-workgroup kernel, which also zeroes md_build's list-length report
 };
 
+#define UF3_VIRIAL_OUTSIDE_MSG "uf3_featurize_virial: an atom lies far outside its cell; wrap the atoms into the cell first (virial rows follow the energy row, the image-range rule of the force rows has no strain analogue)"
 static int check_flags(uf3_ctx *c) {
     if (!c->flags.p) return UF3_OK;
     int fl[4] = {0, 0, 0, 0};
@@ -1168,6 +1174,7 @@ static int poll_pending(uf3_ctx *c, bool wait, bool remember) {
         if (p.has3 && fl[1] > p.cap) { c->n3_cap = std::max(c->n3_cap, (std::max(fl[1] + 8, p.cap + p.cap / 4) + 7) / 8 * 8); grown = true; }
         if (fl[2] > p.cand) { c->cand_cap = std::max(c->cand_cap, (std::max(fl[2] + 16, p.cand + p.cand / 4) + 7) / 8 * 8); grown = true; }
         if (fl[3] > p.xcap) { c->n3x_cap = std::max(c->n3x_cap, std::min(248, (fl[3] + 8 + 7) / 8 * 8)); grown = true; }
+        if (fl[4] && p.virial && !rc) rc = fail(c, UF3_EINVAL, UF3_VIRIAL_OUTSIDE_MSG " (earlier asynchronous call)");
         if (fl[4] && !p.img) { c->img_mode = true; grown = true; }      // (its 3-body launches left without writing rows)
         else if (!fl[4] && p.img_launch) c->img_mode = false;            // back to the ordinary launches
         if (grown && !rc)
@@ -1467,7 +1474,7 @@ static size_t feat3_lds_bytes(const uf3_basis *b, int cap, bool e_lds) {
 #define UF3_LDS_LIMIT ((size_t)160 * 1024 - 512)
 
 static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z,
-                              double *d_xe, double *d_xf, int64_t ld);
+                              double *d_xe, double *d_xf, int64_t ld, double *d_xv = nullptr);
 
 extern "C" int uf3_featurize_dev(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z,
                                  double *d_xe, double *d_xf) {
@@ -1484,18 +1491,43 @@ extern "C" int uf3_featurize_ld_dev(uf3_basis *b, const uf3_frames *fr, const do
     return featurize_dev_impl(b, fr, d_pos, d_z, d_xe, d_xf, ld);
 }
 
+// virial rows (uf3_virial_rows.h): x_v [n_frames][6][F] = the strain derivative of the energy row, by launches of their own
+// behind the featurizer's (whose instances, registers and LDS carve they leave alone)
+extern "C" int uf3_featurize_virial_dev(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z,
+                                        double *d_xe, double *d_xf, double *d_xv) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    if (!d_xv) return fail(b->ctx, UF3_EINVAL, "uf3_featurize_virial_dev: null x_v");
+    return featurize_dev_impl(b, fr, d_pos, d_z, d_xe, d_xf, b->host.F, d_xv);
+}
+
+// LDS bytes of one k_virial_rows workgroup WITHOUT its row set; must mirror the carve at the top of the kernel
+static size_t virial_lds_bytes(int cap, int n_pair_cols, int mode) {
+    const size_t list_d = mode == 0 ? 0 : 4 * (size_t)cap;
+    const size_t stage_d = mode == 0 ? 6 * (size_t)n_pair_cols : (size_t)VSTAGE * VREC_STRIDE;
+    const size_t per_wave_d = list_d + stage_d + ((list_d + stage_d) & 1);
+    const size_t per_wave_i = mode == 0 ? 0 : UF3_MAX_SPECIES + 2;
+    return WPB * per_wave_d * 8 + WPB * per_wave_i * 4 + 32;
+}
+// The six rows live in LDS while the whole carve leaves room for a second workgroup on the CU (half of the 160 KB less the
+// allocation granule, the target the featurizer's 3-body launches use): four waves alone would leave the walk's latency
+// uncovered.  Past that every add goes straight to HBM -- the e_direct rule (48 KB for the one energy row) with its threshold
+// moved to (this limit - the launch's other LDS) / 6 per row.
+#define UF3_VROWS_LDS (((size_t)160 * 1024 - 1024) / 2)
+
 static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z,
-                              double *d_xe, double *d_xf, int64_t ld) {
+                              double *d_xe, double *d_xf, int64_t ld, double *d_xv) {
     uf3_ctx *c = b->ctx;
     uf3_env_refresh();
     read_f3_env(c);
     if (!d_pos || !d_z) return fail(c, UF3_EINVAL, "null positions / species");
-    if (!d_xe && !d_xf) return UF3_OK;
+    if (!d_xe && !d_xf && !d_xv) return UF3_OK;
+    const bool want_v = d_xv != nullptr;
     // verdicts on earlier asynchronous calls that have arrived: returned to the asynchronous caller (their owner) HERE, so not
     // kept for uf3_ctx_synchronize as well -- a caller that redoes the work would meet the same verdict again after a clean redo
     { int rc0 = poll_pending(c, false, false); if (rc0) return rc0; }
     Prepared P;
-    const bool old_n3 = uf3_env("UF3_SEPARATE_N3") != nullptr;     // debugging: lists from k_build_n3 instead
+    // (lists from k_build_n3 instead: debugging, and virial rows alone -- no pair launch of the featurizer to build them)
+    const bool old_n3 = uf3_env("UF3_SEPARATE_N3") != nullptr || (want_v && !d_xe && !d_xf);
     int rc = prepare(b, fr, d_pos, d_z, old_n3, P);       // cell list only: MODE 0 builds the 3-body lists itself
     if (rc) return rc;
     hipStream_t st = c->stream;
@@ -1551,6 +1583,7 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
             if (rc) return rc;
         }
         if (want_e) HIPCHK(c, hipMemsetAsync(d_xe, 0, sizeof(double) * (size_t)P.n_frames * F, st));
+        if (want_v) HIPCHK(c, hipMemsetAsync(d_xv, 0, sizeof(double) * (size_t)P.n_frames * 6 * F, st));
         if (!P.flags_zeroed || attempt) HIPCHK(c, hipMemsetAsync(A.n3_need, 0, 2 * sizeof(int), st));       // n3_need, cand_need
         const bool img_launch = c->img_mode && has3 && want_f && A.outside;
         const bool ext_lists = img_launch;
@@ -1583,7 +1616,7 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
         {
             Timed tm(c, T_FEAT);
             for (int mode = 0; mode <= 9; mode++) {
-                if (!(b->modes & (1 << mode))) continue;
+                if (!(b->modes & (1 << mode)) || !(want_e || want_f)) continue;
                 if (feat3 && mode >= 1) continue;
                 const bool dense_mode = mode >= 6;
                 // knot records go to LDS when the block then still reaches the occupancy its registers allow
@@ -1797,6 +1830,49 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
 #undef UF3_F3_LAUNCH1
 #undef UF3_F3_ATTR
             }
+            if (want_v && !restart) {
+                const int S = b->host.S;
+                for (int vm = 0; vm <= 5; vm++) {
+                    if (vm && !((b->vmodes & (1 << vm)) && (has3 || old_n3) && b->host.T > 0)) continue;
+                    const int fe = vm == 0 ? A.n_pair_cols : F - S - A.n_pair_cols;
+                    const size_t other = virial_lds_bytes(vm == 0 ? 1 : A.n3.cap, A.n_pair_cols, vm);
+                    const size_t rows = 6 * ((size_t)fe + (fe & 1)) * 8;
+                    const int v_direct = rows + other > UF3_VROWS_LDS ? 1 : 0;
+                    const size_t lds = other + (v_direct ? 0 : rows);
+                    if (lds > UF3_LDS_LIMIT) return fail(c, UF3_EOVERFLOW, "virial rows: LDS footprint exceeds 160 KB (neighbour count too large)");
+                    const int per_cu = std::max(1, std::min(8, (int)((size_t)(160 * 1024) / lds)));
+                    int n_blocks = std::min((P.natoms + WPB - 1) / WPB, c->n_cu * per_cu * 24);
+                    const int apb = ((P.natoms + n_blocks - 1) / n_blocks + WPB - 1) / WPB * WPB;
+                    n_blocks = (P.natoms + apb - 1) / apb;
+                    A.atoms_per_block = apb;
+                    if (c->env_debug_lds)
+                        fprintf(stderr, "uf3 virial rows mode %d: lds %zu B, rows in %s (6 x %d columns = %zu B + %zu B other, limit %zu B), "
+                                "cap %d, blocks %d x %d atoms\n", vm, lds, v_direct ? "hbm" : "lds", fe, rows, other, (size_t)UF3_VROWS_LDS,
+                                A.n3.cap, n_blocks, apb);
+#define UF3_V_LAUNCH(M)                                                                                                    \
+    do {                                                                                                                   \
+        {                                                                                                                  \
+            static std::mutex mu; static size_t have[64] = {0};                                                            \
+            std::lock_guard<std::mutex> lk(mu);                                                                            \
+            size_t &hv = have[c->device & 63];                                                                             \
+            if (lds > hv) {                                                                                                \
+                HIPCHK(c, hipFuncSetAttribute((const void *)k_virial_rows<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+                hv = lds;                                                                                                  \
+            }                                                                                                              \
+        }                                                                                                                  \
+        hipLaunchKernelGGL((k_virial_rows<M>), dim3((n_blocks + 7) / 8 * 8), dim3(WPB * WAVE), lds, st, A, d_xv, v_direct);  \
+    } while (0)
+                    switch (vm) {
+                        case 0: UF3_V_LAUNCH(0); break;
+                        case 1: UF3_V_LAUNCH(1); break;
+                        case 2: UF3_V_LAUNCH(2); break;
+                        case 3: UF3_V_LAUNCH(3); break;
+                        case 4: UF3_V_LAUNCH(4); break;
+                        default: UF3_V_LAUNCH(5); break;
+                    }
+#undef UF3_V_LAUNCH
+                }
+            }
         }
         HIPCHK(c, hipGetLastError());
         if (restart) continue;
@@ -1816,6 +1892,7 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
             if (!pd.ev) HIPCHK(c, hipEventCreateWithFlags(&pd.ev, hipEventDisableTiming));
             HIPCHK(c, hipMemcpyAsync((int *)c->pin_flags.p + 8 * slot, c->flags.p, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
             HIPCHK(c, hipEventRecord(pd.ev, st));
+            pd.virial = want_v;
             pd.cap = cap; pd.cand = c->cand_cap; pd.has3 = has3; pd.xcap = ext_lists ? c->n3x_cap : (1 << 30); pd.img = img_launch || !(has3 && want_f && A.outside); pd.img_launch = img_launch; pd.live = true;
             c->pending_head = (slot + 1) % uf3_ctx::N_PENDING;
             return UF3_OK;
@@ -1824,6 +1901,7 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
         HIPCHK(c, hipMemcpyAsync(fl, c->flags.p, sizeof(fl), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         if (fl[0]) return check_flags(c);
+        if (want_v && fl[4]) return fail(c, UF3_EINVAL, UF3_VIRIAL_OUTSIDE_MSG);
         bool redo = false;
         if (has3 && want_f && A.outside && fl[4] && !c->img_mode) { c->img_mode = true; redo = true; }
         else if (img_launch && !fl[4]) c->img_mode = false;                 // (valid all the same) back to the ordinary launches
@@ -1835,7 +1913,7 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
         if (fl[2] > c->cand_cap) { c->cand_cap = (fl[2] + 16 + 7) / 8 * 8; redo = true; }
         if (redo) continue;
         if (has3 && !c->n3_tuned) { rc = n3_tune(c, A.n3, P.natoms); if (rc) return rc; }
-        c->cand_tuned = true;
+        if (want_e || want_f) c->cand_tuned = true;
         return UF3_OK;
     }
     return fail(c, UF3_EOVERFLOW, "neighbour capacities did not converge");
@@ -1962,6 +2040,34 @@ extern "C" int uf3_featurize(uf3_basis *b, const uf3_frames *fr, const double *p
         if (rc) return rc;
         if (be) HIPCHK(c, hipMemcpyAsync(xe, c->stage_out.p, be, hipMemcpyDeviceToHost, c->stream));
         if (bf) HIPCHK(c, hipMemcpyAsync(xf, c->stage_out2.p, bf, hipMemcpyDeviceToHost, c->stream));
+        rc = sync_own_call(c);
+        if (rc != UF3_ERETRY) return rc;     // the lists of this very call overflowed: repeat it with the raised capacities
+    }
+    return fail(c, UF3_EOVERFLOW, "neighbour capacities did not converge");
+}
+
+extern "C" int uf3_featurize_virial(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, double *xe,
+                                    double *xf, double *xv) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    uf3_ctx *c = b->ctx;
+    if (!xv) return fail(c, UF3_EINVAL, "uf3_featurize_virial: null x_v");
+    int natoms = 0;
+    poll_pending(c, true);
+    int rc = upload_frames(c, fr, pos, z, natoms);
+    if (rc) return rc;
+    const size_t F = (size_t)b->host.F;
+    const size_t be = xe ? 8 * F * fr->n_frames : 0, bf = xf ? 8 * F * 3 * (size_t)natoms : 0, bv = 8 * F * 6 * (size_t)fr->n_frames;
+    // (x_e and x_v share one block: stage_out2 belongs to the force rows)
+    HIPCHK(c, c->stage_out.ensure(be + bv));
+    if (bf) HIPCHK(c, c->stage_out2.ensure(bf));
+    double *d_xv = (double *)((char *)c->stage_out.p + be);
+    for (int attempt = 0; attempt < 6; attempt++) {
+        rc = uf3_featurize_virial_dev(b, fr, (const double *)c->stage_cur, c->d_stage_z,
+                                      be ? c->stage_out.as<double>() : nullptr, bf ? c->stage_out2.as<double>() : nullptr, d_xv);
+        if (rc) return rc;
+        if (be) HIPCHK(c, hipMemcpyAsync(xe, c->stage_out.p, be, hipMemcpyDeviceToHost, c->stream));
+        if (bf) HIPCHK(c, hipMemcpyAsync(xf, c->stage_out2.p, bf, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(xv, d_xv, bv, hipMemcpyDeviceToHost, c->stream));
         rc = sync_own_call(c);
         if (rc != UF3_ERETRY) return rc;     // the lists of this very call overflowed: repeat it with the raised capacities
     }

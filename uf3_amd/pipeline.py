@@ -14,6 +14,12 @@ over all F columns; the frozen columns are folded out on the device when the pie
 packed buffer of the unfrozen columns (2 F'^2 + 2 F' + 6 doubles) is what ``parallel.allreduce_packed`` sums
 over the ranks -- no host copy before the collective.
 
+Stress targets (``add_frames(..., stresses=...)``) go into a SECOND flat device buffer ``[ G_v (F x F) | o_v (F) | m_v (3) ]``:
+the virial rows of the frames that carry a stress are featurized on the device (``uf3_featurize_virial_dev``), divided by
+the frames' atom counts and multiplied by ``uf3_gram_dev``; the first buffer, its packed form and the library's own
+accumulation keep their layout.  The virial rows are exactly zero in the frozen columns, so the pieces of the frozen system
+are the unfrozen rows and columns of ``G_v`` and ``o_v`` as they stand.  One rank only.
+
 PyTorch is used only as the owner of the device buffers and of the stream: the arithmetic around the Gram kernels
 (normalisation, target moments, the fold of the frozen columns) is the library's (``uf3_fit_rows_dev``,
 ``uf3_fit_pack_dev``).
@@ -46,6 +52,10 @@ class DeviceFitAccumulator:
         self.ord_f = self.flat[o:o + F]; o += F
         self.m_e = self.flat[o:o + 3]; o += 3
         self.m_f = self.flat[o:o + 3]
+        self.flat_v = torch.zeros(F * F + F + 3, dtype=torch.float64, device=self.dev)
+        self.gram_v = self.flat_v[:F * F].view(F, F)
+        self.ord_v = self.flat_v[F * F:F * F + F]
+        self.m_v = self.flat_v[F * F + F:]
         self.max_atoms = int(max_atoms_per_chunk)
         self.first_fraction = float(first_chunk_fraction)     # (a call's chunks grow from this fraction of the limit, doubling: the GPU starts sooner)
         self.n_chunks = 0
@@ -57,6 +67,7 @@ class DeviceFitAccumulator:
 
     def reset(self):
         self.flat.zero_()
+        self.flat_v.zero_()
         self.n_chunks = 0
         self._counts = [0.0, 0.0]
         if getattr(self, "_fit", None):
@@ -97,8 +108,9 @@ class DeviceFitAccumulator:
         except Exception:  # noqa: BLE001 - interpreter shutdown
             pass
 
-    def add_frames(self, frames, energies, forces=None):
-        """frames: list of Atoms; energies [n]; forces: list of (N_i, 3) arrays (required when with_forces).
+    def add_frames(self, frames, energies, forces=None, stresses=None):
+        """frames: list of Atoms; energies [n]; forces: list of (N_i, 3) arrays (required when with_forces); stresses: one
+        ASE stress (Voigt 6-vector or 3 x 3, eV / A^3) or ``None`` per frame -- frames without one contribute no virial rows.
 
         Asynchronous: the host packs the next chunk into pinned staging while the GPU works on the current one (nothing
         is read back here; ``uf3_featurize_dev`` does not synchronise once the context knows its neighbour capacities).
@@ -118,6 +130,45 @@ class DeviceFitAccumulator:
         self.n_chunks += after[0] - before[0]
         self._counts[0] += after[1] - before[1]
         self._counts[1] += after[2] - before[2]
+        if stresses is not None:
+            self._add_virials(frames, stresses)
+
+    def _add_virials(self, frames, stresses):
+        """Virial rows of the frames that carry a stress: featurized on the device in chunks of at most ``max_atoms`` atoms,
+        divided by the atom counts, G_v / o_v by ``uf3_gram_dev``, the target moments beside them."""
+        from uf3_amd.regression import least_squares
+        torch = self.torch
+        if len(stresses) != len(frames):
+            raise ValueError("stresses: one entry (or None) per frame")
+        if self.ctx.comm_info()[0] > 1:
+            raise NotImplementedError("stress targets are accumulated on one rank only")
+        counts = [len(a) for a in frames]
+        volumes = [abs(float(np.linalg.det(np.asarray(a.get_cell(), dtype=float).reshape(3, 3)))) if s is not None else 0.0
+                   for a, s in zip(frames, stresses)]
+        y_all, kept = least_squares.virial_targets(stresses, volumes, counts, return_index=True)
+        F = self.n_feat
+        prev = self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
+        try:
+            start = 0
+            while start < len(kept):
+                stop, n_at = start, 0
+                while stop < len(kept) and (stop == start or n_at + counts[kept[stop]] <= self.max_atoms):
+                    n_at += counts[kept[stop]]
+                    stop += 1
+                batch = _lib.FrameBatch([frames[k] for k in kept[start:stop]])
+                d_pos = torch.from_numpy(batch.pos).to(self.dev)
+                d_z = torch.from_numpy(batch.z).to(self.dev)
+                x_v = torch.empty((stop - start, 6, F), dtype=torch.float64, device=self.dev)
+                self.fz.featurize_device(batch.struct, d_pos.data_ptr(), d_z.data_ptr(), None, None, d_x_v=x_v.data_ptr())
+                n = torch.tensor([counts[k] for k in kept[start:stop]], dtype=torch.float64).to(self.dev)
+                x_v /= n[:, None, None]
+                y = np.ascontiguousarray(y_all[start:stop]).reshape(-1)
+                d_y = torch.from_numpy(y).to(self.dev)
+                self._gram(x_v.view(-1, F), d_y, self.gram_v, self.ord_v)
+                self.m_v += torch.from_numpy(least_squares.moments(y)).to(self.dev)
+                start = stop
+        finally:
+            self.ctx.restore_stream(prev)
 
     def add_device_batch(self, frames_struct, n_frames, n_atoms, d_pos, d_z, d_counts, d_ye, d_yf=None, x_e=None, x_f=None):
         """One batch whose inputs already live in HBM (torch tensors; ``d_ye`` per-atom normalised, ``d_yf`` flat):
@@ -167,7 +218,19 @@ class DeviceFitAccumulator:
     def pieces(self):
         """Additive pieces of this rank as host arrays (what ``WeightedLinearModel.fit_from_pieces`` takes)."""
         from uf3_amd import parallel
-        return parallel.unpack_pieces(self.packed().cpu().numpy(), int(self._keep.numel()), with_forces=self.with_forces)
+        pieces = parallel.unpack_pieces(self.packed().cpu().numpy(), int(self._keep.numel()), with_forces=self.with_forces)
+        pieces.update(self.virial_pieces())
+        return pieces
+
+    def virial_pieces(self):
+        """``gram_v``, ``ord_v``, ``m_v`` on the unfrozen columns as host arrays; empty when no frame carried a stress."""
+        self.ctx.synchronize()
+        m_v = self.m_v.cpu().numpy()
+        if m_v[0] == 0:
+            return {}
+        keep = self._keep
+        return dict(gram_v=self.gram_v.index_select(0, keep).index_select(1, keep).cpu().numpy(),
+                    ord_v=self.ord_v.index_select(0, keep).cpu().numpy(), m_v=m_v)
 
 
 def _fit_counts(ctx, fit):
@@ -252,9 +315,11 @@ class NativeFitAccumulator:
         self.ctx.check(self.ctx.lib.uf3_fit_info(self.handle, C.byref(n), None, None))
         return n.value
 
-    def add_frames(self, frames, energies, forces=None):
+    def add_frames(self, frames, energies, forces=None, stresses=None):
         """frames: list of Atoms; energies [n]; forces: list of (N_i, 3) arrays (required when with_forces).  Returns once the
         last chunk is queued; a capacity overflow surfaces as ``_lib.RetryError`` later (``fit_frames`` starts over)."""
+        if stresses is not None:
+            raise NotImplementedError("stress targets are not built into the native accumulator: use DeviceFitAccumulator / fit_frames")
         if self.with_forces and forces is None and len(frames):
             raise ValueError("this accumulator was set up with forces: pass them")
         _fit_add(self.ctx, self.handle, frames, energies, forces, self.with_forces)
@@ -271,9 +336,11 @@ class NativeFitAccumulator:
 
 
 def fit_frames_native(model, featurizer, frames, energies, forces=None, weight=0.5, reduce=True, with_forces=None,
-                      max_atoms_per_chunk=320000):
+                      max_atoms_per_chunk=320000, stresses=None):
     """``fit_frames`` without PyTorch: accumulation in the library (``NativeFitAccumulator``), the ranks' pieces summed by the
     library's own RCCL communicator when the context has one (``parallel.native_comm``), solved on every rank."""
+    if stresses is not None:
+        raise NotImplementedError("stress targets are not built into the native accumulator: use fit_frames")
     if with_forces is None:
         with_forces = forces is not None
     acc = NativeFitAccumulator(model, featurizer, max_atoms_per_chunk=max_atoms_per_chunk, with_forces=with_forces)
@@ -296,22 +363,38 @@ def fit_frames_native(model, featurizer, frames, energies, forces=None, weight=0
     return pieces
 
 
+def _world_size():
+    """ranks of an initialised torch process group (1 without one; torch is not imported for the question)"""
+    import sys
+    dist = getattr(sys.modules.get("torch"), "distributed", None)
+    if dist is None or not (dist.is_available() and dist.is_initialized()):
+        return 1
+    return int(dist.get_world_size())
+
+
 def fit_frames(model, featurizer, frames, energies, forces=None, weight=0.5, reduce=True, with_forces=None,
-               max_atoms_per_chunk=320000):
+               max_atoms_per_chunk=320000, stresses=None, virial_weight=0.0):
     """
     Featurize + accumulate on this rank's GPU, sum-reduce the packed pieces across ranks on the device (if a
     process group is initialised), solve on every rank.  ``frames`` is THIS rank's shard; ``with_forces`` must be
     the same on every rank (default: whether forces were passed) -- a rank with an empty shard passes it explicitly.
+    ``stresses`` (one ASE stress or None per frame) with ``virial_weight`` in [0, 1): stress targets in the fit, see
+    ``WeightedLinearModel.fit_from_pieces``; one rank only.
     """
     from uf3_amd import parallel
+    from uf3_amd.regression import least_squares
+    least_squares.check_virial_weight(virial_weight)
+    if stresses is not None and _world_size() > 1:
+        raise NotImplementedError("stress targets with more than one rank are not built: fit the stresses on one rank")
     if with_forces is None:
         with_forces = forces is not None
     acc = DeviceFitAccumulator(model, featurizer, with_forces=with_forces, max_atoms_per_chunk=max_atoms_per_chunk)
     attempt = 0
     while True:
         try:
-            acc.add_frames(frames, energies, forces)
+            acc.add_frames(frames, energies, forces, stresses=stresses)
             flat = acc.packed()
+            virial = acc.virial_pieces() if stresses is not None else {}
             break
         except _lib.UF3Error as exc:
             # Chunks queued before the verdict arrived are still in flight with the old capacities: wait for them and
@@ -331,5 +414,6 @@ def fit_frames(model, featurizer, frames, energies, forces=None, weight=0.5, red
     if reduce:
         flat = parallel.allreduce_packed(flat, ctx=acc.ctx)          # (the library's own communicator when the context has one)
     pieces = parallel.unpack_pieces(flat.cpu().numpy(), n_cols, with_forces=with_forces)
-    model.fit_from_pieces(pieces, weight=weight)
+    pieces.update(virial)
+    model.fit_from_pieces(pieces, weight=weight, virial_weight=virial_weight)
     return pieces

@@ -123,6 +123,54 @@ def calc_E_F_weights(n_e, n_f, std_e, std_f):
     return 1 / np.sqrt(n_e) / std_e, 1 / np.sqrt(n_f) / std_f
 
 
+VOIGT = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))
+
+
+def virial_targets(stresses, volumes, atom_counts, return_index=False):
+    """
+    Targets of the virial rows from ASE stresses: ``y_v = stress * V / N`` per frame, shape ``[n_kept, 6]``.
+
+    ``stresses``: one entry per frame -- a Voigt 6-vector (xx, yy, zz, yz, xz, xy) or a symmetric 3 x 3 tensor, in
+    eV / A^3 with ``stress = (1 / V) dE / d eps`` (what ``UFCalculator.get_stress`` and ASE calculators return) -- or
+    ``None`` for a frame without one, which contributes no rows.  ``volumes`` [A^3] and ``atom_counts`` per frame.  The
+    rows that go with these targets are ``x_v / N``: per-atom normalisation, as for the energy rows, so that a large
+    cell does not outweigh a small one.  ``return_index=True`` also returns the indices of the frames kept.
+    """
+    if not (len(stresses) == len(volumes) == len(atom_counts)):
+        raise ValueError("virial_targets: one stress, one volume and one atom count per frame")
+    rows, kept = [], []
+    for k, s in enumerate(stresses):
+        if s is None:
+            continue
+        s = np.asarray(s, dtype=float)
+        if s.shape == (3, 3):
+            s = np.array([0.5 * (s[a, b] + s[b, a]) for a, b in VOIGT])
+        elif s.shape != (6,):
+            raise ValueError(f"virial_targets: stress {k} is neither a Voigt 6-vector nor a 3 x 3 tensor")
+        if not (float(volumes[k]) > 0 and int(atom_counts[k]) > 0):
+            raise ValueError(f"virial_targets: frame {k} carries a stress but no volume or no atoms")
+        rows.append(s * (float(volumes[k]) / int(atom_counts[k])))
+        kept.append(k)
+    y_v = np.array(rows, dtype=float).reshape(len(rows), 6)
+    return (y_v, np.array(kept, dtype=np.int64)) if return_index else y_v
+
+
+def virial_row_weight(m_v):
+    """``w_v = 1 / (sqrt(n_v) std(y_v))`` from the target moments (1 / sqrt(n_v) when the std is 0, as
+    ``calc_E_F_weights`` does for energies)."""
+    n, std = m_v[0], std_from_moments(m_v)
+    if n == 0:
+        return 0.0
+    return 1 / np.sqrt(n) if std == 0 else 1 / np.sqrt(n) / std
+
+
+def check_virial_weight(virial_weight):
+    lam = float(virial_weight)
+    if not (0.0 <= lam < 1.0):
+        raise ValueError(f"virial_weight must lie in [0, 1): {virial_weight}")
+    return lam
+
+
 def rmse_metric(predicted, actual):
     return np.sqrt(np.mean(np.subtract(predicted, actual) ** 2))
 
@@ -234,8 +282,9 @@ class WeightedLinearModel(BasicLinearModel):
         self.coefficients = revert_frozen_coefficients(solution, self.n_feats, self.mask, self.frozen_c,
                                                        self.col_idx)
 
-    def gram_pieces(self, x_e, y_e, x_f=None, y_f=None):
-        """Additive pieces of one shard: Gram/ordinate of the frozen system + target moments."""
+    def gram_pieces(self, x_e, y_e, x_f=None, y_f=None, x_v=None, y_v=None):
+        """Additive pieces of one shard: Gram/ordinate of the frozen system + target moments.  ``x_v`` [n, 6, F] (or
+        [6 n, F]): virial rows ALREADY divided by the frames' atom counts, ``y_v`` [n, 6]: ``virial_targets``."""
         x_e, y_e = np.asarray(x_e, dtype=float), np.asarray(y_e, dtype=float)
         xe, ye = freeze_columns(x_e, y_e, self.mask, self.frozen_c, self.col_idx)
         # the energy weight comes from the FROZEN targets, the force weight from the raw ones (least_squares.py:296-304)
@@ -246,20 +295,51 @@ class WeightedLinearModel(BasicLinearModel):
             pieces["m_f"] = moments(y_f)
             xf, yf = freeze_columns(x_f, y_f, self.mask, self.frozen_c, self.col_idx)
             pieces["gram_f"], pieces["ord_f"] = gram_device(xf, yf, self.device)
+        if x_v is not None:
+            x_v = np.asarray(x_v, dtype=float).reshape(-1, np.shape(x_v)[-1])
+            y_v = np.asarray(y_v, dtype=float).reshape(-1)
+            if len(x_v) != len(y_v):
+                raise ValueError(f"gram_pieces: {len(x_v)} virial rows, {len(y_v)} targets")
+            if len(y_v):
+                xv, yv = freeze_columns(x_v, y_v, self.mask, self.frozen_c, self.col_idx)
+                pieces["m_v"] = moments(yv)
+                pieces["gram_v"], pieces["ord_v"] = gram_device(xv, yv, self.device)
         return pieces
 
-    def fit_from_pieces(self, pieces, weight=0.5):
+    def fit_from_pieces(self, pieces, weight=0.5, virial_weight=0.0):
+        """Solve from additive pieces.  ``virial_weight`` = lambda in [0, 1): with virial pieces present the system is
+        ``(1 - lambda) [kappa w_e^2 G_e + (1 - kappa) w_f^2 G_f] + lambda w_v^2 G_v`` (ordinate alike); with lambda = 0
+        or no virial pieces the arithmetic is exactly that of a fit without them.  Without force pieces the bracket is
+        ``w_e^2 G_e`` (the energy pieces alone carry no weight of their own otherwise)."""
+        lam = check_virial_weight(virial_weight)
+        use_v = lam > 0.0 and "gram_v" in pieces and pieces["m_v"][0] > 0
         if "gram_f" in pieces:
             w_e, w_f = calc_E_F_weights(pieces["m_e"][0], pieces["m_f"][0], std_from_moments(pieces["m_e"]),
                                         std_from_moments(pieces["m_f"]))
             gram, ordinate = self.combine_weighted_gram(pieces["gram_e"], pieces["gram_f"], pieces["ord_e"],
                                                         pieces["ord_f"], w_e, w_f, weight)
+        elif use_v:
+            w_e = virial_row_weight(pieces["m_e"])
+            gram, ordinate = w_e ** 2 * pieces["gram_e"], w_e ** 2 * pieces["ord_e"]
         else:
             gram, ordinate = pieces["gram_e"], pieces["ord_e"]
+        if use_v:
+            gram, ordinate = self.combine_virial_gram(gram, pieces["gram_v"], ordinate, pieces["ord_v"],
+                                                      virial_row_weight(pieces["m_v"]), lam)
         self.fit_with_gram(gram, ordinate)
 
-    def fit(self, x_e, y_e, x_f=None, y_f=None, weight=0.5, batch_size=2500):
-        """Energies (+ forces) -> coefficients (least_squares.py:274-321)."""
+    def combine_virial_gram(self, gram, gram_v, ordinate, ord_v, virial_row_w, virial_weight):
+        gram = ((1 - virial_weight) * gram) + (virial_weight * virial_row_w ** 2 * gram_v)
+        ordinate = ((1 - virial_weight) * ordinate) + (virial_weight * virial_row_w ** 2 * ord_v)
+        return gram, ordinate
+
+    def fit(self, x_e, y_e, x_f=None, y_f=None, weight=0.5, batch_size=2500, x_v=None, y_v=None, virial_weight=0.0):
+        """Energies (+ forces) -> coefficients (least_squares.py:274-321).  With virial rows (``x_v`` divided by the
+        frames' atom counts, ``y_v`` from ``virial_targets``) and ``virial_weight`` > 0: through the pieces."""
+        if x_v is not None and check_virial_weight(virial_weight) > 0.0:
+            return self.fit_from_pieces(self.gram_pieces(x_e, y_e, x_f, y_f, x_v=x_v, y_v=y_v), weight=weight,
+                                        virial_weight=virial_weight)
+        check_virial_weight(virial_weight)
         x_e, y_e = np.asarray(x_e, dtype=float), np.asarray(y_e, dtype=float)
         xe, ye = freeze_columns(x_e, y_e, self.mask, self.frozen_c, self.col_idx)
         gram, ordinate = gram_device(xe, ye, self.device)

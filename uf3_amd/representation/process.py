@@ -106,13 +106,35 @@ class BasisFeaturizer:
             start = stop
         return x_e, x_f, offsets
 
-    def featurize_device(self, frames_struct, d_pos, d_z, d_x_e=None, d_x_f=None, ld=None):
-        """Device-resident entry: raw HBM pointers (ints), asynchronous on the context stream.  ``ld``: doubles between
-        consecutive force rows (default: the number of features, dense rows; a multiple of 16 puts every row on a cache
-        line of its own, ``aligned_ld``)."""
+    def featurize_virials(self, atoms_list, energy=False, periodic=None):
+        """
+        Virial rows of a batch of frames: ``x_v [n_frames, 6, F]``, the strain derivative of the (unnormalised) energy row
+        in Voigt order xx, yy, zz, yz, xz, xy -- the convention of ``UFCalculator.get_stress`` times the volume, so that
+        ``x_v[f] @ coefficients`` is the frame's ``dE / d eps``.  ``energy=True`` returns ``(x_e, x_v)``, both from one call.
+        Frames with atoms far outside their cell are refused (wrap them first).
+        """
         import ctypes as C
         ctx, db = self._dev()
-        if ld is None or int(ld) == db.n_feat:
+        F = db.n_feat
+        x_v = np.empty((len(atoms_list), 6, F))
+        x_e = np.empty((len(atoms_list), F)) if energy else None
+        batch = _lib.FrameBatch(atoms_list, periodic=periodic)
+        ctx.check(ctx.lib.uf3_featurize_virial(db.handle, C.byref(batch.struct), _lib._p(batch.pos), _lib._p(batch.z),
+                                               _lib._p(x_e), None, _lib._p(x_v)))
+        return (x_e, x_v) if energy else x_v
+
+    def featurize_device(self, frames_struct, d_pos, d_z, d_x_e=None, d_x_f=None, ld=None, d_x_v=None):
+        """Device-resident entry: raw HBM pointers (ints), asynchronous on the context stream.  ``ld``: doubles between
+        consecutive force rows (default: the number of features, dense rows; a multiple of 16 puts every row on a cache
+        line of its own, ``aligned_ld``).  ``d_x_v``: where the virial rows ``[n_frames][6][F]`` go (dense force rows only)."""
+        import ctypes as C
+        ctx, db = self._dev()
+        if d_x_v:
+            if not (ld is None or int(ld) == db.n_feat):
+                raise ValueError("featurize_device: virial rows come with dense force rows (ld = n_feat) only")
+            ctx.check(ctx.lib.uf3_featurize_virial_dev(db.handle, C.byref(frames_struct), C.c_void_p(d_pos), C.c_void_p(d_z),
+                                                       C.c_void_p(d_x_e or 0), C.c_void_p(d_x_f or 0), C.c_void_p(d_x_v)))
+        elif ld is None or int(ld) == db.n_feat:
             ctx.check(ctx.lib.uf3_featurize_dev(db.handle, C.byref(frames_struct), C.c_void_p(d_pos), C.c_void_p(d_z),
                                                 C.c_void_p(d_x_e or 0), C.c_void_p(d_x_f or 0)))
         else:
