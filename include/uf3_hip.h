@@ -249,6 +249,31 @@ int uf3_gram_force_rows_dev(uf3_basis *basis, const double *d_x_f, const double 
                             int64_t n_atoms, int64_t ld, int accumulate, double *d_gram, double *d_ord);
 
 /*
+ * Leverage of feature rows against the system a linear fit solved (uf3_amd/csrc/uf3_leverage.h):
+ *   q[g] = sum over the rows r of group g, over k, of ( sum_{j <= k} W[k][j] X[r][j] )^2  =  sum_r x_r^T (G + R^T R)^-1 x_r
+ * for W = inv(cholesky(G + R^T R)).
+ *   X      [n_rows][ld] row-major fp64; the first n_feat columns are used, columns n_feat .. ld never reach the result
+ *          (they may hold anything, NaN included).
+ *   W      [n_feat][n_feat] row-major, lower triangular with EXACT zeros above the diagonal (the caller's promise: the kernel
+ *          skips every 16 x 4 matrix-core step that lies wholly above the diagonal and does not mask the others); frozen
+ *          columns are whole zero rows and zero columns.
+ *   group  1 or 3: how many consecutive rows are summed into one output (3: one number per atom from its three force rows).
+ *          Any other value, or n_rows % group != 0, is UF3_EINVAL.
+ *   q      [n_rows / group], written with plain stores by the one workgroup that owns the rows: no atomics, no Z = X W^T in
+ *          memory, no scratch proportional to n_rows.  The same call twice gives bit-identical q; q >= 0, and exactly 0.0 for
+ *          an all-zero row.
+ * n_rows == 0 is allowed and launches nothing (q is left alone).  The _dev entry takes device pointers, runs on the context's
+ * stream and does not synchronise -- after the context's first matrix-core call: that one (this entry's or uf3_gram_dev's) probes
+ * the accumulator layout and waits for the answer, so make it before capturing a graph.  The host entry stages x and w, runs
+ * and copies q back.
+ * With UF3_DEBUG_LDS set every launch reports its configuration on stderr ("uf3: leverage kernel=k_leverage rows=.. ...").
+ */
+int uf3_leverage(uf3_ctx *ctx, const double *x, int64_t n_rows, int32_t n_feat, int64_t ld,
+                 const double *w, int32_t group, double *q /* [n_rows / group] */);
+int uf3_leverage_dev(uf3_ctx *ctx, const double *d_x, int64_t n_rows, int32_t n_feat, int64_t ld,
+                     const double *d_w, int32_t group, double *d_q);
+
+/*
  * The bookkeeping around the Gram pieces of a device-resident fit (what the reference does on the host in
  * dataframe_to_tuples, least_squares.py:666-713, freeze_columns / VarianceRecorder, :19-67, :296-304, :817-890), on the
  * context's stream, nothing synchronises:

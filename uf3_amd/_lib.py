@@ -37,10 +37,11 @@ EXPORTS = ["uf3_ctx_create", "uf3_ctx_destroy", "uf3_ctx_set_stream", "uf3_ctx_s
            "uf3_phonon_mesh", "uf3_phonon_mesh_dev", "uf3_phonon_dos", "uf3_phonon_dos_dev", "uf3_phonon_thermo",
            "uf3_phonon_thermo_dev",
            "uf3_site_terms", "uf3_site_terms_dev", "uf3_heat_flux", "uf3_heat_flux_dev", "uf3_md_run_flux",
-           "uf3_featurize_virial", "uf3_featurize_virial_dev"]
+           "uf3_featurize_virial", "uf3_featurize_virial_dev",
+           "uf3_leverage", "uf3_leverage_dev"]
 
 
-SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_virial_rows.h", "uf3_device.h", "uf3_md.h", "uf3_hessian.h", "uf3_relax.h", "uf3_phonon.h", "uf3_npt.h", "uf3_neb.h", "uf3_mc.h", "uf3_flux.h", os.path.join("..", "..", "include", "uf3_hip.h"))
+SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_virial_rows.h", "uf3_leverage.h", "uf3_device.h", "uf3_md.h", "uf3_hessian.h", "uf3_relax.h", "uf3_phonon.h", "uf3_npt.h", "uf3_neb.h", "uf3_mc.h", "uf3_flux.h", os.path.join("..", "..", "include", "uf3_hip.h"))
 
 
 def source_build_id(csrc_dir=None):
@@ -178,6 +179,8 @@ def load():
             getattr(lib, name).argtypes = [vp, C.POINTER(Frames), vp, vp, vp, vp, vp]
         for name in ("uf3_gram", "uf3_gram_dev"):
             getattr(lib, name).argtypes = [vp, vp, vp, i64, i32, i64, C.c_int, vp, vp]
+        for name in ("uf3_leverage", "uf3_leverage_dev"):
+            getattr(lib, name).argtypes = [vp, vp, i64, i32, i64, vp, i32, vp]
         for name in ("uf3_eval", "uf3_eval_dev"):
             getattr(lib, name).argtypes = [vp, C.POINTER(Frames), vp, vp, vp, vp, vp, vp, vp]
         for name in ("uf3_eval_virial", "uf3_eval_virial_dev"):

@@ -19,6 +19,7 @@
 #include "uf3_kernels.h"
 #include "uf3_feat3.h"
 #include "uf3_virial_rows.h"
+#include "uf3_leverage.h"
 #include "uf3_md.h"
 #include "uf3_npt.h"
 #include "uf3_hessian.h"
@@ -3384,6 +3385,49 @@ extern "C" int uf3_gram(uf3_ctx *c, const double *x, const double *y, int64_t n_
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(gram, dg, bg, hipMemcpyDeviceToHost, c->stream));
     if (ord && y) HIPCHK(c, hipMemcpyAsync(ord, dord, bo, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return UF3_OK;
+}
+
+// ------------------------------------------------------------------------------ leverage (uf3_leverage.h)
+extern "C" int uf3_leverage_dev(uf3_ctx *c, const double *d_x, int64_t n_rows, int32_t n_feat, int64_t ld, const double *d_w,
+                                int32_t group, double *d_q) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "null ctx");
+    if (n_rows < 0 || n_feat < 1 || ld < n_feat || (group != 1 && group != 3) || n_rows % group != 0 ||
+        n_rows / LV_ROWS >= INT32_MAX || (n_rows && (!d_x || !d_w || !d_q)))
+        return fail(c, UF3_EINVAL, "uf3_leverage: bad argument (group is 1 or 3 and divides n_rows, ld >= n_feat >= 1)");
+    if (n_rows == 0) return UF3_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ensure_frag(c);
+    if (rc) return rc;
+    const unsigned blocks = (unsigned)((n_rows + LV_ROWS - 1) / LV_ROWS);
+    hipLaunchKernelGGL(k_leverage, dim3(blocks), dim3(256), 0, c->stream, d_x, n_rows, n_feat, ld, d_w, group, c->frag.as<int>(), d_q);
+    HIPCHK(c, hipGetLastError());
+    if (c->env_debug_lds) {
+        const int nt = (n_feat + 15) / 16;
+        fprintf(stderr, "uf3: leverage kernel=k_leverage rows=%lld feat=%d ld=%lld group=%d blocks=%u rows_per_block=%d lds=%zu B "
+                "slab=%d passes=%d\n", (long long)n_rows, n_feat, (long long)ld, group, blocks, LV_ROWS,
+                sizeof(double) * (LV_ROWS * LV_LDW + 128), LV_SLAB, (nt + 4 * LV_KT - 1) / (4 * LV_KT));
+    }
+    return UF3_OK;
+}
+
+extern "C" int uf3_leverage(uf3_ctx *c, const double *x, int64_t n_rows, int32_t n_feat, int64_t ld, const double *w, int32_t group,
+                            double *q) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "null ctx");
+    if (n_rows < 0 || n_feat < 1 || ld < n_feat || (group != 1 && group != 3) || n_rows % group != 0 || (n_rows && (!x || !w || !q)))
+        return fail(c, UF3_EINVAL, "uf3_leverage: bad argument (group is 1 or 3 and divides n_rows, ld >= n_feat >= 1)");
+    if (n_rows == 0) return UF3_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bx = 8 * (size_t)n_rows * ld, bw = 8 * (size_t)n_feat * n_feat, bq = 8 * (size_t)(n_rows / group);
+    HIPCHK(c, c->stage_out2.ensure(bx + 64));
+    HIPCHK(c, c->stage_out.ensure(bw + bq + 64));
+    double *dx = c->stage_out2.as<double>(), *dw = c->stage_out.as<double>(), *dq = dw + (size_t)n_feat * n_feat;
+    HIPCHK(c, hipMemcpyAsync(dx, x, bx, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dw, w, bw, hipMemcpyHostToDevice, c->stream));
+    int rc = uf3_leverage_dev(c, dx, n_rows, n_feat, ld, dw, group, dq);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(q, dq, bq, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return UF3_OK;
 }

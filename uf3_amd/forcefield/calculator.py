@@ -252,6 +252,23 @@ class UFCalculator(_Base):
         """ASE's per-atom energies [N] (eV): the site energies U_i of ``site_terms``; their sum is ``get_potential_energy``."""
         return self.site_terms([atoms], virials=False)[0][0]
 
+    def get_leverages(self, atoms_or_list, forces=True, max_atoms_per_chunk=320000):
+        """Leverages of one frame or a list of frames against the system this calculator's model was fitted on
+        (``pipeline.DeviceLeverage``): ``dict(energy, force, offsets)``; for a single ``Atoms`` ``energy`` is a scalar and
+        ``force`` has shape [N].  A model without a posterior (read from a file, no ``load_posterior``) raises ``ValueError``."""
+        from uf3_amd import pipeline
+        from uf3_amd.representation import process
+        lev = getattr(self, "_leverage", None)
+        w = self.model.whitening()                                # (the ValueError, before anything touches the device)
+        if lev is None or lev.max_atoms != int(max_atoms_per_chunk) or lev._w_host is not w:
+            fz = process.BasisFeaturizer(self.bspline_config, device=self.device)
+            lev = self._leverage = pipeline.DeviceLeverage(self.model, fz, max_atoms_per_chunk=max_atoms_per_chunk)
+        single = not isinstance(atoms_or_list, (list, tuple))
+        out = lev.frames([atoms_or_list] if single else list(atoms_or_list), forces=forces)
+        if single:
+            out["energy"] = float(out["energy"][0])
+        return out
+
     def get_stresses(self, atoms=None):
         """Per-atom stresses [N, 6], eV/A^3, in ``get_stress``'s convention -- Voigt order (xx, yy, zz, yz, xz, xy) and ASE's
         sign (dE/d(strain) per volume: positive under tension) --, each atom given the volume V / N:

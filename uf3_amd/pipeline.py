@@ -233,6 +233,102 @@ class DeviceFitAccumulator:
                     ord_v=self.ord_v.index_select(0, keep).cpu().numpy(), m_v=m_v)
 
 
+class DeviceLeverage:
+    """
+    Leverages of frames against the system a fitted model solved, without the feature rows leaving the GPU:
+    ``h = x^T (G + R^T R)^-1 x`` per frame (energy row divided by the atom count, as the fit does) and per atom (its three
+    force rows summed) -- how far a geometry lies from what the fit saw; see ``WeightedLinearModel.leverage`` for what
+    the number means.  The whitening matrix of the model (``model.whitening()``) is uploaded once per object; frames are
+    featurized chunk by chunk (``featurize_device``) into device buffers that are reused, ``uf3_leverage_dev`` runs on
+    them, and only the leverages come back.
+    """
+
+    def __init__(self, model, featurizer, max_atoms_per_chunk=320000):
+        import torch
+        self.torch = torch
+        self.model, self.fz = model, featurizer
+        w = model.whitening()                                 # (ValueError when the model carries no posterior)
+        self.ctx, self.db = featurizer._dev()
+        self.dev = torch.device("cuda", self.ctx.device)     # (the featurizer's device: buffers and launches on one GPU)
+        self.n_feat = self.db.n_feat
+        if w.shape != (self.n_feat, self.n_feat):
+            raise ValueError("DeviceLeverage: the model's basis is not the featurizer's")
+        self.max_atoms = int(max_atoms_per_chunk)
+        self._w_host = w                                      # (what the upload was made from: a refit makes a new one)
+        self._w = torch.from_numpy(np.ascontiguousarray(w)).to(self.dev)
+        self._x_e = self._x_f = None
+
+    def _buffers(self, n_frames, n_atoms, forces):
+        torch, F = self.torch, self.n_feat
+        if self._x_e is None or self._x_e.shape[0] < n_frames:
+            self._x_e = torch.empty((n_frames, F), dtype=torch.float64, device=self.dev)
+        if forces and (self._x_f is None or self._x_f.shape[0] < 3 * n_atoms):
+            self._x_f = None                                  # (released before the larger one is asked for)
+            self._x_f = torch.empty((3 * n_atoms, F), dtype=torch.float64, device=self.dev)
+        return self._x_e[:n_frames], (self._x_f[:3 * n_atoms] if forces else None)
+
+    def _leverage(self, x, group, q):
+        self.ctx.check(self.ctx.lib.uf3_leverage_dev(self.ctx.handle, C.c_void_p(x.data_ptr()), x.shape[0], self.n_feat, self.n_feat,
+                                                     C.c_void_p(self._w.data_ptr()), group, C.c_void_p(q.data_ptr())))
+
+    def _frames(self, frames, forces):
+        torch = self.torch
+        counts = [len(a) for a in frames]
+        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        q_e = np.empty(len(frames))
+        q_f = np.empty(int(offsets[-1])) if forces else None
+        prev = self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
+        try:
+            start = 0
+            while start < len(frames):
+                stop, n_at = start, 0
+                while stop < len(frames) and (stop == start or n_at + counts[stop] <= self.max_atoms):
+                    n_at += counts[stop]
+                    stop += 1
+                batch = _lib.FrameBatch(frames[start:stop])
+                d_pos = torch.from_numpy(batch.pos).to(self.dev)
+                d_z = torch.from_numpy(batch.z).to(self.dev)
+                x_e, x_f = self._buffers(stop - start, n_at, forces)
+                self.fz.featurize_device(batch.struct, d_pos.data_ptr(), d_z.data_ptr(), x_e.data_ptr(),
+                                         x_f.data_ptr() if forces else None)
+                n = torch.tensor(counts[start:stop], dtype=torch.float64).to(self.dev)
+                x_e /= n[:, None]
+                d_q = torch.empty(stop - start + (n_at if forces else 0), dtype=torch.float64, device=self.dev)
+                self._leverage(x_e, 1, d_q[:stop - start])
+                if forces and n_at:
+                    self._leverage(x_f, 3, d_q[stop - start:])
+                self.ctx.synchronize()                        # verdict on the asynchronous featurizer call (RetryError)
+                q = d_q.cpu().numpy()
+                q_e[start:stop] = q[:stop - start]
+                if forces:
+                    q_f[offsets[start]:offsets[stop]] = q[stop - start:]
+                start = stop
+        finally:
+            self.ctx.restore_stream(prev)
+        out = dict(energy=q_e, offsets=offsets)
+        if forces:
+            out["force"] = q_f
+        return out
+
+    def frames(self, frames, forces=True):
+        """``dict(energy=[n_frames], force=[sum N], offsets=[n_frames + 1])`` (no ``force`` with ``forces=False``): the leverage
+        of every frame's per-atom energy row and of every atom's three force rows; atom ``i`` of frame ``f`` is entry
+        ``offsets[f] + i``.  Frames are batched under the atom limit (a frame larger than the limit is a chunk of its own)."""
+        frames = list(frames)
+        if any(len(a) < 1 for a in frames):
+            raise ValueError("DeviceLeverage.frames: a frame without atoms has no per-atom energy row")
+        try:
+            return self._frames(frames, bool(forces))
+        except _lib.RetryError:
+            # the asynchronous featurizer overflowed its capacities and the context has adapted (as in fit_frames): wait for
+            # what is in flight, drop its verdicts, start the call over once
+            try:
+                self.ctx.synchronize()
+            except _lib.UF3Error:
+                pass
+            return self._frames(frames, bool(forces))
+
+
 def _fit_counts(ctx, fit):
     n, e, f = C.c_int64(), C.c_double(), C.c_double()
     ctx.check(ctx.lib.uf3_fit_info(fit, C.byref(n), C.byref(e), C.byref(f)))

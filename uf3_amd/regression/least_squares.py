@@ -83,6 +83,47 @@ def gram_device(x, y, device=None):
     return gram, ordinate
 
 
+def _leverage_rows(x, n_feat, group):
+    """Rows [n, F] (group 1 or 3) or [n, 3, F] (group 3) -> contiguous [n_rows, F]."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 3:
+        if x.shape[1] != 3 or group != 3:
+            raise ValueError("leverage: rows of shape [n, 3, F] go with group=3")
+        x = x.reshape(-1, x.shape[-1])
+    if x.ndim != 2 or x.shape[1] != n_feat:
+        raise ValueError(f"leverage: rows must be [n, {n_feat}] or [n, 3, {n_feat}], not {x.shape}")
+    if group not in (1, 3) or len(x) % group:
+        raise ValueError("leverage: group is 1 or 3 and divides the number of rows")
+    return np.ascontiguousarray(x)
+
+
+def leverage_reference(x, w, group=1):
+    """NumPy statement of ``uf3_leverage``: ``((x @ w.T) ** 2).sum(1)``, summed over groups of ``group`` rows."""
+    w = np.asarray(w, dtype=np.float64)
+    x = _leverage_rows(x, len(w), group)
+    return ((x @ w.T) ** 2).sum(1).reshape(-1, group).sum(1)
+
+
+def leverage_bound(x, w, group=1):
+    """``4 F 2^-53 sum_k (sum_j |x_j| |w_kj|)^2`` per output: the first-order rounding bound of ANY summation order of
+    the same products (``z_k`` is off by at most ``F eps (|x| |w|)_k``, so ``q = sum z_k^2`` by ``2 |z_k|`` times that,
+    and ``|z_k| <= (|x| |w|)_k``; the factor 4 leaves room for two such results being compared)."""
+    w = np.asarray(w, dtype=np.float64)
+    x = _leverage_rows(x, len(w), group)
+    return 4.0 * len(w) * 2.0 ** -53 * ((np.abs(x) @ np.abs(w).T) ** 2).sum(1).reshape(-1, group).sum(1)
+
+
+def leverage_device(x, w, group=1, device=None):
+    """``uf3_leverage`` on host rows: [n / group] of ``sum_k (sum_{j <= k} w[k, j] x[r, j])^2`` (fp64 MFMA).  ``w`` is lower
+    triangular with exact zeros above the diagonal."""
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    x = _leverage_rows(x, len(w), group)
+    ctx = _lib.get_context(device)
+    q = np.empty(len(x) // group)
+    ctx.check(ctx.lib.uf3_leverage(ctx.handle, _lib._p(x), len(x), len(w), len(w), _lib._p(w), group, _lib._p(q)))
+    return q
+
+
 def moore_penrose_components(x, y):
     return gram_device(x, y)
 
@@ -212,6 +253,9 @@ class BasicLinearModel:
 
 
 class WeightedLinearModel(BasicLinearModel):
+    system_matrix = None   # gram + reg^T reg of the last fit_with_gram on the unfrozen columns (load_posterior restores it)
+    _whitening = None
+
     def __init__(self, bspline_config, regularizer=None, data_coverage=None, **params):
         super().__init__(regularizer)
         self.bspline_config = bspline_config
@@ -278,9 +322,67 @@ class WeightedLinearModel(BasicLinearModel):
                                               self.frozen_c, self.col_idx)
         self.data_coverage = np.logical_or(self.data_coverage, coverage)
         reg = freeze_regularizer(self.regularizer, self.mask)
-        solution = lu_factorization(gram + np.dot(reg.T, reg), ordinate)
+        system = gram + np.dot(reg.T, reg)
+        solution = lu_factorization(system, ordinate)
         self.coefficients = revert_frozen_coefficients(solution, self.n_feats, self.mask, self.frozen_c,
                                                        self.col_idx)
+        self.system_matrix, self._whitening = system, None
+
+    # -- leverage: how far a row lies from what the fit saw ---------------------------------
+    def whitening(self):
+        """``W = inv(cholesky(system_matrix))`` embedded at the unfrozen indices of the full column range, [F, F] fp64,
+        lower triangular (``mask`` is ascending) with zero rows and columns at the frozen indices: ``|W x|^2`` is
+        ``x^T (G + R^T R)^-1 x`` on the unfrozen columns.  Computed once on the host and cached."""
+        if self._whitening is not None:
+            return self._whitening
+        if self.system_matrix is None:
+            raise ValueError("this model carries no system matrix (a model read from a file has none): fit it first, "
+                             "or call load_posterior")
+        try:
+            chol = np.linalg.cholesky(self.system_matrix)
+        except np.linalg.LinAlgError:
+            raise ValueError("the system matrix gram + reg^T reg is not positive definite: raise the ridge penalties of "
+                             "the regulariser (ridge_1b / ridge_2b / ridge_3b)") from None
+        n = len(chol)
+        # a triangular solve against the identity; the strict upper triangle is set to exact zeros (the kernel's contract)
+        w_small = np.tril(np.linalg.solve(chol, np.eye(n)))
+        mask = np.asarray(self.mask)
+        w = np.zeros((self.n_feats, self.n_feats))
+        w[np.ix_(mask, mask)] = w_small
+        self._whitening = w
+        return w
+
+    def save_posterior(self, path):
+        """The system matrix of the fit and the unfrozen column indices it lives on, as an ``.npz``."""
+        if self.system_matrix is None:
+            raise ValueError("this model carries no system matrix: fit it first, or call load_posterior")
+        with open(path, "wb") as f:
+            np.savez(f, system_matrix=self.system_matrix, indices=np.asarray(self.mask, dtype=np.int64),
+                     n_feats=np.int64(self.n_feats))
+
+    def load_posterior(self, path):
+        """Restore what ``save_posterior`` wrote; a file whose indices are not this model's unfrozen columns is refused."""
+        with np.load(path) as d:
+            system, idx, n_feats = np.array(d["system_matrix"], dtype=np.float64), np.array(d["indices"]), int(d["n_feats"])
+        mask = np.asarray(self.mask)
+        if n_feats != self.n_feats or idx.shape != mask.shape or np.any(idx != mask):
+            raise ValueError("load_posterior: the file's column indices do not match this model's basis")
+        if system.shape != (len(mask), len(mask)):
+            raise ValueError("load_posterior: the system matrix does not have one row and column per index")
+        self.system_matrix, self._whitening = system, None
+
+    def leverage(self, x, group=1):
+        """
+        Leverage ``h = x^T (G + R^T R)^-1 x`` of host rows ``x`` [n, F] (or [n, 3, F] with ``group=3``) on the GPU
+        (``uf3_leverage``): [n / group], ``group`` consecutive rows summed into one number (3: one per atom from its
+        three force rows).
+
+        It is the leverage of the row AS GIVEN against the WEIGHTED system the fit solved -- up to the noise scale the
+        posterior variance of the prediction ``x . c``.  Pass energy rows divided by the atom count, as the fit does.
+        Leverages of training rows in the statistical sense (they sum to the effective number of parameters) carry the
+        row's weight: ``kappa w_e^2 h`` for an energy row, ``(1 - kappa) w_f^2 h`` for a force row.
+        """
+        return leverage_device(x, self.whitening(), group=group, device=self.device)
 
     def gram_pieces(self, x_e, y_e, x_f=None, y_f=None, x_v=None, y_v=None):
         """Additive pieces of one shard: Gram/ordinate of the frozen system + target moments.  ``x_v`` [n, 6, F] (or
@@ -460,6 +562,7 @@ class WeightedLinearModel(BasicLinearModel):
             solution = json_io.load_interaction_map(filename)
         elif solution is None:
             raise ValueError("Neither solution nor filename were provided.")
+        self.system_matrix, self._whitening = None, None   # (the posterior of an earlier fit does not go with these coefficients)
         if "coefficients" in solution:
             solution = solution["coefficients"]
         elif "solution" in solution:
