@@ -300,6 +300,23 @@ int uf3_fit_pack_dev(uf3_ctx *ctx, int32_t n_feat, const double *d_flat, const i
  *   c1 [S]; c2 concatenated pair coefficient vectors (nk-4 each, all basis functions);
  *   c3 concatenated full L*M*N grids per trio (BSplineBasis.decompress_3B output).
  *   energies [n_frames]; forces [sum N][3] (NULL: energies only).
+ *
+ * The leg rule of the whole evaluator family (uf3_eval*, uf3_eval_atoms, uf3_eval_centres, the MD / relax / NEB / NPT drivers,
+ * uf3_hessian, uf3_site_terms, uf3_heat_flux, uf3_mc_*):
+ *   - The energy of a triplet is the reference's.  Leg l takes the neighbour of lower atomic number; of two neighbours of one
+ *     species, the one with the lower reference supercell index AS SEEN FROM THE REAL COPY OF THE CENTRE (image rank with b
+ *     slowest, a middle, c fastest, each axis in the order 0, +1, -1, +2, ...; then the atom's index in the frame).
+ *     The tie-break decides a number only where the two legs differ (a symmetry-1 trio); on equal l and m legs either
+ *     assignment is the same function, and every kernel keeps the order it always had there (and with it its bits).
+ *   - Every other quantity is the exact derivative or partition of that energy: forces, virials, site energies and site
+ *     virials, the heat current, the Hessian with its mixed rows and Born term, the MC energy differences.
+ * Two properties of a basis with a symmetry-1 trio (two neighbours of one species on UNEQUAL l and m legs) follow:
+ *   1. The forces are not the reference calculator's.  Its force loop numbers ghost-centred triplets differently from its
+ *      energy loop, so its forces are not the gradient of its energy there; the evaluator's are.  (The featurizer's force rows
+ *      stay the reference's.)
+ *   2. The energy depends on the numbering of the atoms and on which cell image holds an atom (wrap a frame and it may change).
+ *      That is the reference's property; nothing here is invariant under renumbering or lattice translations of single atoms
+ *      on such a basis.
  */
 int uf3_eval(uf3_basis *basis, const uf3_frames *frames, const double *pos, const int32_t *z,
              const double *c1, const double *c2, const double *c3, double *energies, double *forces);
@@ -608,7 +625,9 @@ int uf3_neb_get_state(uf3_neb *neb, double *pos, double *forces, double *neb_for
  *                         around it.  The context's MD skin and lists are not touched.
  *   uf3_mc_delta          dE [n] of n caller-given proposals on the current species, nothing applied: frame, atom i within the
  *                         frame, and the second atom j within the frame (mode 0) or the new atomic number (mode 1).  A swap of
- *                         like atoms gives exactly 0.  UF3_EINVAL: an index outside its frame; UF3_ESPECIES: an unknown element.
+ *                         like atoms gives exactly 0.  A triplet's legs follow the evaluator's rule (above uf3_eval) for the
+ *                         species it has before and after the move: a change of species can move a neighbour onto the other leg
+ *                         and a triplet in or out of its trio's ranges.  UF3_EINVAL: an index outside its frame; UF3_ESPECIES: an unknown element.
  *   uf3_mc_set_positions  new positions [N][3]: the table is rebuilt, the running energies are evaluated again on next need.
  *   uf3_mc_get_state      host arrays out, NULL skips: species [N] (atomic numbers), running energies, accepted and counted
  *                         trials, status (0 running, 2 frozen) [n_frames].
@@ -638,6 +657,9 @@ int uf3_mc_get_state(uf3_mc *mc, int32_t *z, double *energies, int64_t *accepted
  *                 Newton's equations; exact in a cluster, term by term with image vectors in a periodic cell).  Pair:
  *                 dU_i / dr_j = phi'(r_ij) u_ij; triplet with legs ij, ik, jk and leg gradient g: d / dr_j = g_ij u_ij - g_jk u_jk,
  *                 d / dr_k = g_ik u_ik + g_jk u_jk (u_jk from j to k).
+ *   Legs          the evaluator's rule (above uf3_eval): of two neighbours of one species the lower reference supercell index
+ *                 as seen from the centre takes leg l.  The order in which a centre's terms are ADDED is another matter (by image
+ *                 vector: see below) and does not decide any term.
  *   uf3_site_terms   site_energies [N] and / or site_virials [N][9] (NULL skips one).
  *   uf3_heat_flux    flux [n_frames][6] = J_conv (3), J_pot (3); site_energies [N] or NULL.
  * The neighbour lists are the call's own (every image in reach of every atom, O(N^2 images) per frame; skin 0): the context's MD
@@ -664,6 +686,8 @@ int uf3_heat_flux_dev(uf3_basis *basis, const uf3_frames *frames, const double *
  *   mixed [3R][6]   d2E / dx_{m,a} dt_v (NULL: not formed): t_v the strain of uf3_eval_virial (Voigt xx, yy, zz, yz, xz, xy;
  *                   eps_ab = eps_ba = t / 2 off the diagonal; cell and positions map through I + eps); = -dF_{m,a} / dt_v
  *   born  [6][6]    d2E / dt_u dt_v at fixed fractional coordinates (clamped ions; NULL: not formed; whole frame only)
+ * Every triplet's legs follow the evaluator's rule (above uf3_eval), also where the row atom is a neighbour of the triplet: H,
+ * mixed and born are the second derivatives of uf3_eval's energy on every basis, symmetry-1 trios included.
  * The neighbour lists are the call's own (skin 0): the context's MD lists and its evaluator state are left as they were.
  * Every row is written by one thread in a fixed order: the results are bitwise repeatable, and the rows of a slab are the
  * rows of the whole call.  Errors: more than one frame, an empty or out-of-range row span, born with a partial span

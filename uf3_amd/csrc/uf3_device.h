@@ -161,6 +161,21 @@ __device__ __forceinline__ int supercell_index(const FrameGeom &g, int s0, int s
     return rank * (g.atom_hi - g.atom_lo) + local_atom;
 }
 
+// The order of reference supercell indices without the image range: the rank of an image goes by (b, a, c), b slowest, each
+// axis in the order 0, +1, -1, +2, ..., so which of two images comes first does not depend on how many images an axis holds.
+// a, b: (packed image shift as seen from the real copy of the centre, atom within the frame) of two neighbours.  Decides which
+// of two neighbours of ONE species takes leg l of their triplet (the lower index) wherever no FrameGeom
+// is at hand (uf3_hessian.h, uf3_flux.h).
+__device__ __forceinline__ bool supercell_before(int shift_a, int atom_a, int shift_b, int atom_b) {
+    int a0, a1, a2, b0, b1, b2;
+    unpack3(shift_a, a0, a1, a2);
+    unpack3(shift_b, b0, b1, b2);
+    if (a1 != b1) return image_pos(a1) < image_pos(b1);
+    if (a0 != b0) return image_pos(a0) < image_pos(b0);
+    if (a2 != b2) return image_pos(a2) < image_pos(b2);
+    return atom_a < atom_b;
+}
+
 // ---- cubic B-spline: interval search + de Boor-Cox triangle ---------------------
 // interval i with t_i < x <= t_{i+1}, 3 <= i <= nk-5.  Caller guarantees t0 < x <= tlast.
 __device__ __forceinline__ int find_interval(const KnotRec *recs, const LegDev &leg, double x) {

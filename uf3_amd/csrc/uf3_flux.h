@@ -27,6 +27,8 @@
 // No atomics: every record has one writer and every sum a fixed order that depends on the centre's entries alone, taken in a
 // canonical order (by image vector), so the results repeat bit for bit, do not depend on the batch around a frame, and do not
 // depend on the numbering of the atoms or on the choice of the periodic cell where that leaves the image vectors' bits alone.
+// (Except on a symmetry-1 trio: there the reference's energy itself depends on both, through which of two neighbours of one
+// species takes leg l -- supercell_before, uf3_device.h; DESIGN.md section 7.  The ORDER of the sums stays canonical.)
 #pragma once
 #include "uf3_hessian.h"
 #include "uf3_md.h"
@@ -166,7 +168,9 @@ __global__ void __launch_bounds__(64) k_flux_site_terms(FluxArgs F) {
         }
     }
     __syncthreads();
-    // triplets with m as the centre: legs in the evaluator's order (lower species on leg l; equal species in canonical order)
+    // triplets with m as the centre, walked in canonical order; legs in the evaluator's order: lower species on leg l; equal
+    // species on the unequal legs of a symmetry-1 trio by the reference supercell index as seen from m, which decides the number;
+    // equal species on equal legs in canonical order, which keeps the bits independent of numbering and cell (test_tiling)
     if (B->T > 0) {
         const int npair = n3 * (n3 - 1) / 2;
         for (int p0 = 0; p0 < npair; p0 += WAVE) {
@@ -175,9 +179,11 @@ __global__ void __launch_bounds__(64) k_flux_site_terms(FluxArgs F) {
             int a, b;
             flux_pair_of(p, a, b);
             const HessNbr ea = L[idx3[a]], eb = L[idx3[b]];
-            const bool swap = ea.spec > eb.spec;
+            const int lo_spec = min(ea.spec, eb.spec), hi_spec = max(ea.spec, eb.spec);
+            const int trio = B->trio_of[(sm * UF3_MAX_SPECIES + lo_spec) * UF3_MAX_SPECIES + hi_spec];
+            const bool swap = ea.spec > eb.spec || (ea.spec == eb.spec && trio >= 0 && B->trios[trio].nsrc == 1 &&
+                                                    supercell_before(eb.shp, eb.j, ea.shp, ea.j));
             const HessNbr &ej = swap ? eb : ea, &ek = swap ? ea : eb;
-            const int trio = B->trio_of[(sm * UF3_MAX_SPECIES + ej.spec) * UF3_MAX_SPECIES + ek.spec];
             const double dj[3] = {ej.dx, ej.dy, ej.dz}, dk[3] = {ek.dx, ek.dy, ek.dz};
             const double djk[3] = {dk[0] - dj[0], dk[1] - dj[1], dk[2] - dj[2]};
             const double rn = norm3_rn(djk[0], djk[1], djk[2]);

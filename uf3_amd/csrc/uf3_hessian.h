@@ -252,12 +252,19 @@ __device__ __forceinline__ bool trio_d2(const BasisDev *B, const double *c3, int
     return true;
 }
 
-// the triplet of centre c with list entries ea, eb (eb != ea): legs in the evaluator's order (lower species on leg l; equal
-// species in list order), slot of row atom m = the slot of entry `mine` (0: the centre itself)
+// the triplet of centre c with list entries ea, eb (positions ia != ib in c's list): legs in the evaluator's order -- lower
+// species on leg l; equal species on the unequal legs of a symmetry-1 trio by the reference supercell index as seen from c (NOT
+// by list position: the lists are in (atom, image offset around the nearest image) order); equal species on
+// equal legs, where the order decides nothing, by list position as ever.  Slot of row atom m = the slot of entry `mine` (0: the
+// centre itself)
 __device__ __forceinline__ void hess_triplet(const HessArgs &A, double *Hm, double *mix, double *bo, int c, const HessNbr &ea, int ia,
                                              const HessNbr &eb, int ib, int mine) {
     const BasisDev *B = A.B;
-    const bool swap = ea.spec > eb.spec || (ea.spec == eb.spec && ia > ib);
+    bool swap = ea.spec > eb.spec;
+    if (ea.spec == eb.spec) {
+        const int t = B->trio_of[(A.spec[c] * UF3_MAX_SPECIES + ea.spec) * UF3_MAX_SPECIES + ea.spec];
+        swap = (t >= 0 && B->trios[t].nsrc == 1) ? supercell_before(eb.shp, eb.j, ea.shp, ea.j) : ia > ib;
+    }
     const HessNbr &ej = swap ? eb : ea, &ek = swap ? ea : eb;
     const int trio = B->trio_of[(A.spec[c] * UF3_MAX_SPECIES + ej.spec) * UF3_MAX_SPECIES + ek.spec];
     if (trio < 0) return;

@@ -638,7 +638,8 @@ __global__ void k_max_count(const int *cnt, int n, int *out) {
 //   centre real (shift 0)      -> compare the supercell indices seen from the centre;
 //   centre ghost, k real       -> compare the two real indices;
 //   centre ghost, k ghost      -> m (real) is always j.
-// Only matters for symmetry-1 trios with equal neighbour species; reproduced for parity.
+// Only matters for symmetry-1 trios with equal neighbour species; reproduced for parity by the FEATURIZER, whose force rows are
+// the reference's.  The evaluator does not follow it where it decides a number: trio_legs_differ below.
 __device__ __forceinline__ bool neighbour_is_first(const FrameGeom &g, int sm, int ksp, int s0, int s1, int s2,
                                                    int m_local, int msidx, int ksidx, int kshift, int k_local) {
     (void)g; (void)msidx;
@@ -649,6 +650,15 @@ __device__ __forceinline__ bool neighbour_is_first(const FrameGeom &g, int sm, i
     bool k_real = (k0 + s0 == 0) && (k1 + s1 == 0) && (k2 + s2 == 0);
     return k_real ? (m_local < k_local) : true;
 }
+
+// The evaluator's answer to the same question (the gather role of k_eval: uf3_eval_atoms, UF3_EVAL_GATHER, calls without
+// forces) where the answer decides a number -- two neighbours of one species on the UNEQUAL legs of a symmetry-1 trio: the
+// energy's assignment, whatever copy of the centre the reference's force loop would number from.  The lower supercell index as
+// seen from the REAL copy of the centre takes leg l (msidx: m numbered from c; ksidx: the entry's own): the order of the centre's
+// list, which the centre pass walks.  The gathered forces are then minus the gradient of the energy, as the centre pass's are,
+// and not the reference's.  On a trio with equal l and m legs either assignment is the same function;
+// there the caller keeps neighbour_is_first, and with it the bits it has always produced.
+__device__ __forceinline__ bool trio_legs_differ(const BasisDev *B, int trio) { return trio >= 0 && B->trios[trio].nsrc == 1; }
 
 // ---------------------------------------------------------------------------------
 // featurizer
@@ -3267,9 +3277,10 @@ k_eval(EvalArgs A) {
                 double vx = ke.dx, vy = ke.dy, vz = ke.dz, rk = ke.r;
                 double ex = ox[q] + vx, ey = oy[q] + vy, ez = oz[q] + vz;
                 double rn = norm3_leg(vx - (-ox[q]), vy - (-oy[q]), vz - (-oz[q]));
-                bool m_first = neighbour_is_first(g, sm, ksp, s0, s1, s2, m_local, msidx, ksidx, ke.shiftc,
-                                                  ke.parent - g.atom_lo);
                 int sc = ospec[q];
+                bool m_first = (sm == ksp && trio_legs_differ(B, B->trio_of[(sc * UF3_MAX_SPECIES + sm) * UF3_MAX_SPECIES + sm]))
+                                   ? msidx < ksidx
+                                   : neighbour_is_first(g, sm, ksp, s0, s1, s2, m_local, msidx, ksidx, ke.shiftc, ke.parent - g.atom_lo);
                 double val, gr[3];
                 int trio; double rl, rm;
                 if (m_first) { rl = orr[q]; rm = rk; trio = B->trio_of[(sc * UF3_MAX_SPECIES + sm) * UF3_MAX_SPECIES + ksp]; }
