@@ -450,9 +450,16 @@ int uf3_scan_solve_dev(uf3_ctx *ctx, int32_t n_cols, int32_t n_folds, const doub
 
 /*
  * Molecular dynamics on the device (uf3_amd.forcefield.md.MolecularDynamics; kernels in uf3_md.h).  The object owns positions
- * (kept UNWRAPPED: the evaluator bins wrapped copies itself), velocities, forces, inverse masses and species of a batch of frames
+ * (kept UNWRAPPED), velocities, forces, inverse masses and species of a batch of frames
  * in HBM and steps them with velocity Verlet (friction 0) or BAOAB Langevin dynamics; the forces come from the evaluator
  * (uf3_eval[_virial]_dev's code path) between two fused integrator launches.  Units: Angstrom, fs, amu, eV, K.
+ * Atoms outside the cell: the evaluator bins wrapped copies for its cell lists, but it takes the reference's finite image range
+ * (-fac .. fac cells per axis) around the positions AS GIVEN, as uf3_eval does on the same frame.  An atom that has drifted out of
+ * its cell loses the interactions that range no longer reaches from where it is: the energy and forces of every step are uf3_eval's
+ * of the unwrapped positions the object holds, which are the wrapped frame's only while every atom is inside its cell.  Nothing in
+ * the object wraps.  A run in which atoms may cross a cell face (diffusion, a melt) is to be stopped and continued from wrapped
+ * positions (uf3_md_set_state) before that happens.  The same holds for uf3_relax_* and uf3_neb_*, which keep positions
+ * unwrapped for the same reason (tests/test_gpu_redescribed.py holds the rule).
  *   uf3_md_create          copies frames, positions [N][3], velocities [N][3] (NULL: zero), species, masses [N] and the model
  *                          (c1 / c2 / c3 as for uf3_eval) into the object; no evaluation yet.  Masses positive and finite.
  *   uf3_md_set_state       host arrays in; NULL keeps that part.  New positions invalidate the forces.
@@ -604,7 +611,10 @@ int uf3_neb_get_state(uf3_neb *neb, double *pos, double *forces, double *neb_for
  *                         per geometry.  UF3_EINVAL: a frame of more than 49 152 atoms (a frame's species sit in LDS, one byte
  *                         each), an atom with more than 512 neighbours in the 3-body range (the affected centres of a trial sit
  *                         in LDS; there is no global-memory fallback), non-finite positions or cells, a mask entry above 1, null
- *                         pointers; UF3_ESPECIES: an element outside the basis.
+ *                         pointers; UF3_ESPECIES: an element outside the basis.  Atoms outside the cell: the table holds the
+ *                         evaluator's candidate set, the images -fac .. fac of the reference's range around the positions AS
+ *                         GIVEN.  Every dE and running energy is uf3_eval's on those positions; like uf3_eval's it lacks the terms
+ *                         of an atom outside its cell that the range no longer reaches.  Wrap first for the wrapped frame's.
  *   uf3_mc_run            n_trials trials of every frame still running, in launches of at most 1024 trials (no launch is
  *                         open-ended), one workgroup per frame.  Trial t (absolute: the counter lives in the object and goes on
  *                         across runs) of frame f: Philox4x32-10 with counter (f, t lo, t hi, 0) and key (seed lo, seed hi) gives
@@ -647,7 +657,11 @@ int uf3_mc_get_state(uf3_mc *mc, int32_t *z, double *energies, int64_t *accepted
  *   Site energy   U_i: the evaluator's own partition, what uf3_eval_atoms(i, i + 1) returns as the share of atom i -- the
  *                 one-body term of i's species, the directed pair terms phi(r_ij) of i over every image j in the pair range,
  *                 and every triplet V(r_ij, r_ik, r_jk) with i as the centre, over unordered pairs {j, k} of its 3-body
- *                 neighbours.  sum_i U_i = uf3_eval's frame energy.
+ *                 neighbours.  sum_i U_i = uf3_eval's energy of the WRAPPED frame: the lists take every image in reach around
+ *                 the nearest one, so U, W and J do not change when an atom is moved by a lattice vector, whereas uf3_eval
+ *                 takes the reference's finite image range around the positions as given and loses terms of an atom outside its
+ *                 cell.  The two agree when every atom lies inside its cell (wrap first); uf3_md_run_flux samples on the
+ *                 object's unwrapped positions and so keeps describing the wrapped frame after uf3_md_run's forces no longer do.
  *   Images        move with their parent atom and carry its velocity.
  *   Site virial   W_i[a][b] = sum_terms sum_s d_s[a] (dU_i / dr_s)[b], s the slots of a term of U_i (neighbour images), d_s the
  *                 vector from the centre to the image; [N][9] row-major.  sum_i W_i, symmetrised, in Voigt order = uf3_eval_virial's
@@ -680,14 +694,17 @@ int uf3_heat_flux_dev(uf3_basis *basis, const uf3_frames *frames, const double *
                       double *d_site_energies);
 
 /*
- * Analytic second derivatives of the energy uf3_eval computes, for ONE frame (uf3_hessian.h; the Gamma-point force constants
- * of the frame, periodic images folded onto their parent atom).  Rows m in [row_begin, row_end) (R rows), all N atoms as columns.
+ * Analytic second derivatives of the energy uf3_eval computes on the WRAPPED frame, for ONE frame (uf3_hessian.h; the Gamma-point
+ * force constants of the frame, periodic images folded onto their parent atom).  The lists take every image in reach around the
+ * nearest one: H, mixed and born do not change when an atom is moved by a lattice vector, whereas uf3_eval takes the reference's
+ * finite image range around the positions as given -- with an atom outside its cell they are the derivatives of the wrapped
+ * frame's energy, not of what uf3_eval returns for the positions passed in.  Rows m in [row_begin, row_end) (R rows), all N atoms as columns.
  *   hess  [3R][3N]  d2E / dx_{m,a} dx_{p,b}
  *   mixed [3R][6]   d2E / dx_{m,a} dt_v (NULL: not formed): t_v the strain of uf3_eval_virial (Voigt xx, yy, zz, yz, xz, xy;
  *                   eps_ab = eps_ba = t / 2 off the diagonal; cell and positions map through I + eps); = -dF_{m,a} / dt_v
  *   born  [6][6]    d2E / dt_u dt_v at fixed fractional coordinates (clamped ions; NULL: not formed; whole frame only)
  * Every triplet's legs follow the evaluator's rule (above uf3_eval), also where the row atom is a neighbour of the triplet: H,
- * mixed and born are the second derivatives of uf3_eval's energy on every basis, symmetry-1 trios included.
+ * mixed and born are the second derivatives of uf3_eval's energy (of the wrapped frame) on every basis, symmetry-1 trios included.
  * The neighbour lists are the call's own (skin 0): the context's MD lists and its evaluator state are left as they were.
  * Every row is written by one thread in a fixed order: the results are bitwise repeatable, and the rows of a slab are the
  * rows of the whole call.  Errors: more than one frame, an empty or out-of-range row span, born with a partial span

@@ -165,6 +165,13 @@ def npt_records(raw, n_atoms, first_step, every):
 
 
 class MolecularDynamics(Driver):
+    """Velocity Verlet / Langevin / constant-pressure dynamics of a batch of frames on the device (module text above).
+
+    Atoms outside the cell: positions are kept unwrapped and go to the evaluator as they are, and the evaluator takes the
+    reference's finite image range around the positions as given (``include/uf3_hip.h``, above ``uf3_md_create``; DESIGN.md
+    section 7).  An atom that leaves its cell during a run (diffusion, a melt) loses the interactions that range no longer reaches from where it
+    is: energies and forces are then ``evaluate_frames``' of the unwrapped positions, not the wrapped crystal's.  Start from
+    wrapped frames, and before atoms can cross a cell face stop, ``set_positions(get_positions(wrap=True))`` and go on."""
     KIND, WHO = "md", WHO
 
     def __init__(self, calculator, atoms_or_list, timestep_fs, masses=None, temperature_K=0.0, friction_per_fs=0.0, seed=0,

@@ -99,6 +99,13 @@ def _check_band(k, band):
 
 
 class NudgedElasticBand(Driver):
+    """Batched nudged-elastic-band relaxation of one or more bands on the device (module text above).
+
+    Atoms outside the cell: positions are kept unwrapped and go to the evaluator as they are, and the evaluator takes the
+    reference's finite image range around the positions as given (``include/uf3_hip.h``, above ``uf3_md_create``; DESIGN.md
+    section 7).  An atom that leaves its cell along a band or while it relaxes loses the interactions that range no longer reaches from where it
+    is: energies and forces are then ``evaluate_frames``' of the unwrapped positions, not the wrapped crystal's.  Start from
+    wrapped frames, and describe a path that crosses a cell face in a cell (or with an origin) in which every image stays inside."""
     KIND, WHO = "neb", WHO
 
     def __init__(self, calc, bands, spring=0.1, fixed=None, skin=0.5, device=None):

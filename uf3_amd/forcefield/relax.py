@@ -29,6 +29,13 @@ WHO = "Relaxation"
 
 
 class Relaxation(Driver):
+    """Batched FIRE relaxation of positions, optionally with the cell, on the device (module text above).
+
+    Atoms outside the cell: positions are kept unwrapped and go to the evaluator as they are, and the evaluator takes the
+    reference's finite image range around the positions as given (``include/uf3_hip.h``, above ``uf3_md_create``; DESIGN.md
+    section 7).  An atom that leaves its cell during a relaxation loses the interactions that range no longer reaches from where it
+    is: energies and forces are then ``evaluate_frames``' of the unwrapped positions, not the wrapped crystal's.  Start from
+    wrapped frames, and wrap the positions again before continuing a relaxation that moved atoms across a cell face."""
     KIND, WHO = "relax", WHO
 
     def __init__(self, calc, atoms_or_list, relax_cell=False, fixed=None, skin=0.5, device=None):
