@@ -282,3 +282,27 @@ def test_refusals():
     with pytest.raises(_lib.UF3Error, match="constant volume"):
         dyn.run(4, flux_every=2)
     dyn.close()
+
+
+@pytest.mark.parametrize("label", ["w2", "nexe4"])
+def test_optional_outputs_do_not_move_the_others(label):
+    """The host entries' staging blocks hold an optional output only when it is asked for: the site energies have the same bits
+    with and without the virials, the virials alone are the virials, and the current is the same with and without the site
+    energies."""
+    import ctypes as C
+    model, make, seed = FRAMES[label]
+    calc, atoms = _calc(model), make()
+    U, W = calc.site_terms([atoms])
+    assert np.array_equal(calc.site_terms([atoms], virials=False)[0][0], U[0])
+    ctx = _lib.get_context(calc.device)
+    db = _lib.device_basis(calc.bspline_config, ctx)
+    batch = _lib.FrameBatch([atoms])
+    w_only = np.full((batch.n_atoms, 3, 3), -7.0)
+    addr = _lib._addr
+    ctx.check(ctx.lib.uf3_site_terms(db.handle, C.byref(batch.struct), addr(batch.pos), addr(batch.z), calc._pc[0], calc._pc[1],
+                                     calc._pc[2], None, addr(w_only)))
+    assert np.array_equal(w_only, W[0])
+    vel, m = _vel(atoms, seed), _masses(atoms)
+    flux, Uf = calc.heat_flux([atoms], vel, m, site_energies=True)
+    assert np.array_equal(calc.heat_flux([atoms], vel, m), flux) and np.array_equal(Uf, U[0])
+    assert np.abs(flux).max() > 0

@@ -334,3 +334,106 @@ def test_abi_refusals():
         harmonic.hessian(calc, atoms, rows=(5, 5))
     with pytest.raises(ValueError, match="whole frame"):
         harmonic.hessian(calc, atoms, rows=(0, 4), strain=True)
+
+
+def _abi(calc):
+    from uf3_amd import _lib
+    ctx = _lib.get_context(calc.device)
+    return _lib, ctx, _lib.device_basis(calc.bspline_config, ctx)
+
+
+def _w16():
+    return synthetic.lattice_frame("bcc", (2, 2, 2), 3.165, [74], seed=3)
+
+
+def _w2():
+    return synthetic.lattice_frame("bcc", (1, 1, 1), 3.165, [74], seed=4)
+
+
+def _cluster13():
+    pos = np.asarray(synthetic.lattice_frame("bcc", (2, 2, 2), 3.165, [74], seed=7).get_positions(), dtype=float)
+    keep = np.sort(np.argsort(np.linalg.norm(pos - pos.mean(axis=0), axis=1))[:13])
+    return Atoms(numbers=np.full(13, 74), positions=pos[keep], cell=np.zeros((3, 3)), pbc=False)
+
+
+def test_hessian_and_site_term_workspaces_stay_apart():
+    """The Hessian's lists and the site terms' lists are two workspaces of one type: a site-term call on a batch of other sizes
+    and another capacity between two Hessian calls changes no bit, on the host entries and with both device entries queued on
+    one stream before anything waits (uf3_hessian_dev returns with k_hessian still to run on its lists)."""
+    import ctypes as C
+    import torch
+    calc = _calc(_unary_model())
+    _lib, ctx, db = _abi(calc)
+    w16, others = _w16(), [_w2(), _cluster13()]
+    H = harmonic.hessian(calc, w16)
+    U, W = calc.site_terms(others)
+    assert np.array_equal(harmonic.hessian(calc, w16), H)
+    U2, W2 = calc.site_terms(others)
+    assert all(np.array_equal(a, b) for a, b in zip(U + W, U2 + W2))
+    # device entries, back to back on one stream
+    dev = torch.device("cuda", calc.device if isinstance(calc.device, int) else 0)
+    hb, sb = _lib.FrameBatch([w16]), _lib.FrameBatch(others)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    ptr = lambda t: C.c_void_p(t.data_ptr())                              # noqa: E731
+    h_pos, h_z, s_pos, s_z = up(hb.pos), up(hb.z), up(sb.pos), up(sb.z)
+    d_h = up(np.full(H.shape, -7.0))
+    d_u, d_w = up(np.full(sb.n_atoms, -7.0)), up(np.full((sb.n_atoms, 9), -7.0))
+    torch.cuda.synchronize(dev)
+    stream = torch.cuda.Stream(dev)
+    prev = ctx.set_stream(stream.cuda_stream)
+    try:
+        with torch.cuda.stream(stream):
+            ctx.check(ctx.lib.uf3_hessian_dev(db.handle, C.byref(hb.struct), ptr(h_pos), ptr(h_z), calc._pc[0], calc._pc[1],
+                                              calc._pc[2], 0, 16, ptr(d_h), None, None))
+            ctx.check(ctx.lib.uf3_site_terms_dev(db.handle, C.byref(sb.struct), ptr(s_pos), ptr(s_z), calc._pc[0], calc._pc[1],
+                                                 calc._pc[2], ptr(d_u), ptr(d_w)))
+            stream.synchronize()
+    finally:
+        ctx.restore_stream(prev)
+    assert np.array_equal(d_h.cpu().numpy(), H)
+    assert np.array_equal(d_u.cpu().numpy(), np.concatenate(U))
+    assert np.array_equal(d_w.cpu().numpy().reshape(-1, 3, 3), np.concatenate(W))
+
+
+@pytest.mark.parametrize("label", ["w2", "nexe4"])
+def test_optional_outputs_do_not_move_the_hessian(label):
+    """uf3_hessian's staging block holds mixed and born only when they are asked for: hess has the same bits with and without
+    either, and each optional output the same bits whatever else is asked for."""
+    import ctypes as C
+    if label == "w2":
+        calc, atoms = _calc(_unary_model()), _w2()
+    else:
+        calc = _calc(ls.WeightedLinearModel.from_json(os.path.join(GOLDEN, "model_binary.json")))
+        atoms = synthetic.lattice_frame("fcc", (1, 1, 1), 4.6, [10, 54], seed=5)
+    _lib, ctx, db = _abi(calc)
+    batch = _lib.FrameBatch([atoms])
+    n = batch.n_atoms
+    assert n == (2 if label == "w2" else 4)
+    addr = _lib._addr
+    got = {}
+    for want_m in (False, True):
+        for want_b in (False, True):
+            H, M, B = np.full((3 * n, 3 * n), -7.0), np.full((3 * n, 6), -7.0), np.full((6, 6), -7.0)
+            ctx.check(ctx.lib.uf3_hessian(db.handle, C.byref(batch.struct), addr(batch.pos), addr(batch.z), calc._pc[0], calc._pc[1],
+                                          calc._pc[2], 0, n, addr(H), addr(M) if want_m else None, addr(B) if want_b else None))
+            assert want_m or np.all(M == -7.0)
+            assert want_b or np.all(B == -7.0)
+            got[want_m, want_b] = (H, M, B)
+    H0 = got[False, False][0]
+    assert np.abs(H0).max() > 0 and np.all(H0 != -7.0)
+    assert all(np.array_equal(g[0], H0) for g in got.values())
+    assert np.array_equal(got[True, False][1], got[True, True][1]) and np.all(got[True, True][1] != -7.0)
+    assert np.array_equal(got[False, True][2], got[True, True][2]) and np.all(got[True, True][2] != -7.0)
+
+
+def test_the_site_term_kernel_s_neighbour_limit_is_not_the_hessian_s():
+    """12 288 neighbours of one atom is the size of k_flux_site_terms' LDS index array, not a property of the lists both entries
+    build: one Xe atom in a 0.5 A cell has some 16 000 images inside the pair range (3 A < r < 8 A, 16 images tried per side),
+    uf3_site_terms refuses it by that name, and uf3_hessian, whose kernel walks the list from global memory, takes it."""
+    from uf3_amd import _lib
+    calc = _calc(ls.WeightedLinearModel.from_json(os.path.join(GOLDEN, "model_binary.json")))
+    atoms = Atoms(numbers=[54], positions=[[0.1, 0.2, 0.3]], cell=np.eye(3) * 0.5, pbc=True)
+    with pytest.raises(_lib.UF3Error, match="more than 12288 neighbours"):
+        calc.site_terms([atoms])
+    H = harmonic.hessian(calc, atoms)
+    assert H.shape == (3, 3) and np.all(np.isfinite(H))

@@ -65,19 +65,25 @@ def _skew3():
     return Atoms(numbers=[42, 74, 74], positions=frac @ cell, cell=cell, pbc=True)
 
 
+def _conv4(a=A0_W):
+    return Atoms(numbers=[74] * 4, positions=[[0, 0, 0], [a / 2] * 3, [a, 0, 0], [1.5 * a, a / 2, a / 2]],
+                 cell=np.diag([2 * a, a, a]), pbc=True)
+
+
 CASES = {
     "w_prim": (_unary_model, _prim, W_MASS, 5),
     "w_conv": (_unary_model, _conv, W_MASS, 5),
     "mow16": (_mow_model, _mow16, MOW_MASS, 2),
     "mow_skew3": (_mow_model, _skew3, MOW_MASS, 3),
 }
+EXTRA = {"w_conv4": (_unary_model, _conv4, W_MASS, 5)}      # (not among the cases every test runs over)
 _cache = {}
 
 
 def _case(name):
     """(calc, atoms, masses [N], n_super, fc_rows) of a case, the force constants computed once."""
     if name not in _cache:
-        model, atoms, masses, n_super = CASES[name]
+        model, atoms, masses, n_super = CASES.get(name) or EXTRA[name]
         calc, atoms = _calc(model()), atoms()
         m = harmonic._masses(atoms, masses)
         _cache[name] = (calc, atoms, m, n_super, harmonic._supercell_rows(calc, atoms, n_super))
@@ -406,3 +412,25 @@ def test_calculator_surface():
         assert res["n_imaginary"] > 0 and res["n_excluded"] >= res["n_imaginary"]
         with pytest.warns(RuntimeWarning, match="imaginary"):
             assert calc2.get_phonon_dos(atoms, mesh=(2, 2, 2), n_super=2, masses=MOW_MASS)["n_imaginary"] == res["n_imaginary"]
+
+
+@pytest.mark.parametrize("name", ["w_conv", "w_conv4"])
+def test_dos_outputs_and_weights_are_independent_sections(name):
+    """uf3_phonon_dos stages the q-weights, the counts and the smeared DOS only when they are passed: counts alone, the DOS alone
+    and both give the same arrays, with the weights and without."""
+    q, w = harmonic.qmesh((4, 4, 4))
+    lam, _ = _dev_lam(name, q)
+    f = harmonic.eigenvalues_to_frequencies(lam)
+    assert f.shape[1] == (6 if name == "w_conv" else 12)
+    edges = _guarded_edges(f)
+    s = np.linspace(f.min() - 1.0, f.max() + 1.0, 41)
+    for wq in (w, None):
+        c_only, no_d = harmonic.dos_from_eigenvalues(lam, wq, edges=edges)
+        no_c, d_only = harmonic.dos_from_eigenvalues(lam, wq, samples=s, sigma=0.15)
+        c_both, d_both = harmonic.dos_from_eigenvalues(lam, wq, edges=edges, samples=s, sigma=0.15)
+        assert no_d is None and no_c is None
+        assert np.array_equal(c_only, c_both) and np.array_equal(d_only, d_both)
+        assert c_both.sum() == f.shape[1] * (len(q) if wq is None else w.sum())
+        assert d_both.max() > 0
+        if wq is None:
+            assert np.array_equal(c_both, np.histogram(f.ravel(), bins=edges)[0])

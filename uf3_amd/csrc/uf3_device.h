@@ -176,6 +176,21 @@ __device__ __forceinline__ bool supercell_before(int shift_a, int atom_a, int sh
     return atom_a < atom_b;
 }
 
+// A symmetry-1 trio: its l and m legs are different functions, so which of two neighbours of ONE species takes leg l decides
+// a number there, and only there (k_eval's gather role asks this too: uf3_kernels.h, neighbour_is_first).
+__device__ __forceinline__ bool trio_legs_differ(const BasisDev *B, int trio) { return trio >= 0 && B->trios[trio].nsrc == 1; }
+
+// Leg assignment of the triplet of a centre of species sc with list entries a, b (HessNbr): true when b takes leg l (the
+// caller swaps).  The lower species takes leg l; equal species on a symmetry-1 trio: the lower reference supercell index as
+// seen from the centre (the energy's assignment); equal species on equal legs, where the order decides no
+// number: the caller's own tie-break (list position in k_hessian, canonical order = no swap in k_flux_site_terms, on purpose).
+template <class Entry>
+__device__ __forceinline__ bool trio_swap_legs(const BasisDev *B, int sc, const Entry &a, const Entry &b, bool equal_legs_swap) {
+    if (a.spec != b.spec) return a.spec > b.spec;
+    const int t = B->trio_of[(sc * UF3_MAX_SPECIES + a.spec) * UF3_MAX_SPECIES + a.spec];
+    return trio_legs_differ(B, t) ? supercell_before(b.shp, b.j, a.shp, a.j) : equal_legs_swap;
+}
+
 // ---- cubic B-spline: interval search + de Boor-Cox triangle ---------------------
 // interval i with t_i < x <= t_{i+1}, 3 <= i <= nk-5.  Caller guarantees t0 < x <= tlast.
 __device__ __forceinline__ int find_interval(const KnotRec *recs, const LegDev &leg, double x) {

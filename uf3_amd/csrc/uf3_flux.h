@@ -16,8 +16,9 @@
 // Derivatives   pair: dU_i / dr_j = phi'(r_ij) u_ij.  Triplet with legs ij, ik, jk and leg gradient g:
 //               d / dr_j = g_ij u_ij - g_jk u_jk,   d / dr_k = g_ik u_ik + g_jk u_jk   (u_jk the unit vector from j to k).
 //
-//   k_flux_lists   the lists of k_hess_lists (uf3_hessian.h: the same device function) for a batch: one wave per atom, its
-//                  frame's arguments put together from a per-frame table.  O(N^2 images) per frame.
+//   k_flux_lists   the per-atom image lists (hess_lists_atom, uf3_hessian.h) of a batch: one wave per atom, its frame's
+//                  arguments put together from a per-frame table.  O(N^2 images) per frame.  The one list kernel: the
+//                  Hessian's frame is a batch of one.
 //   k_flux_site_terms  one wave per centre: lanes over its pair entries, then over the (j, k) pairs of its 3-body
 //                  neighbours, in strides of 64; U (1), J_pot (3) and W (9) in registers, combined by the evaluator's DPP tree (wave_sum),
 //                  lane 0 writes the record.  Values and leg gradients come from trio_value and the evaluator's pair code
@@ -33,7 +34,7 @@
 #include "uf3_hessian.h"
 #include "uf3_md.h"
 
-// one frame of a batch for k_flux_lists (what hessian_impl puts into HessArgs for its single frame)
+// one frame of a batch for k_flux_lists: the geometry of its HessArgs (hess_geometry) and where its atoms start
 struct FluxFrame {
     double cell[9], inv[9];
     int per[3], nimg[3];
@@ -168,8 +169,7 @@ __global__ void __launch_bounds__(64) k_flux_site_terms(FluxArgs F) {
         }
     }
     __syncthreads();
-    // triplets with m as the centre, walked in canonical order; legs in the evaluator's order: lower species on leg l; equal
-    // species on the unequal legs of a symmetry-1 trio by the reference supercell index as seen from m, which decides the number;
+    // triplets with m as the centre, walked in canonical order; legs in the evaluator's order (trio_swap_legs, uf3_device.h),
     // equal species on equal legs in canonical order, which keeps the bits independent of numbering and cell (test_tiling)
     if (B->T > 0) {
         const int npair = n3 * (n3 - 1) / 2;
@@ -179,11 +179,9 @@ __global__ void __launch_bounds__(64) k_flux_site_terms(FluxArgs F) {
             int a, b;
             flux_pair_of(p, a, b);
             const HessNbr ea = L[idx3[a]], eb = L[idx3[b]];
-            const int lo_spec = min(ea.spec, eb.spec), hi_spec = max(ea.spec, eb.spec);
-            const int trio = B->trio_of[(sm * UF3_MAX_SPECIES + lo_spec) * UF3_MAX_SPECIES + hi_spec];
-            const bool swap = ea.spec > eb.spec || (ea.spec == eb.spec && trio >= 0 && B->trios[trio].nsrc == 1 &&
-                                                    supercell_before(eb.shp, eb.j, ea.shp, ea.j));
+            const bool swap = trio_swap_legs(B, sm, ea, eb, false);
             const HessNbr &ej = swap ? eb : ea, &ek = swap ? ea : eb;
+            const int trio = B->trio_of[(sm * UF3_MAX_SPECIES + ej.spec) * UF3_MAX_SPECIES + ek.spec];
             const double dj[3] = {ej.dx, ej.dy, ej.dz}, dk[3] = {ek.dx, ek.dy, ek.dz};
             const double djk[3] = {dk[0] - dj[0], dk[1] - dj[1], dk[2] - dj[2]};
             const double rn = norm3_rn(djk[0], djk[1], djk[2]);

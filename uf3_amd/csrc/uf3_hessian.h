@@ -68,8 +68,8 @@ __device__ __forceinline__ void bspline4_d2(const KnotRec &k, double x, double *
 
 // ---- neighbour lists: one wave per atom, lanes over the other atoms, every image in reach of each -------------------------
 // WRITE = false: counts only.  Entries in (atom, image, lane) order: the same lists on every call.  CHECK: flag image shifts
-// beyond pack3's range.  The body is a device function of one frame's arguments, so that a batch of frames (uf3_flux.h:
-// k_flux_lists, one HessArgs per frame put together on the device) walks the same code.
+// beyond pack3's range.  A device function of one frame's arguments; its one kernel is k_flux_lists (uf3_flux.h), which puts a
+// HessArgs together per frame of a batch on the device.  The Hessian's frame is a batch of one.
 template <bool WRITE, bool CHECK>
 __device__ __forceinline__ void hess_lists_atom(const HessArgs &A, int i, int lane) {
     const BasisDev *B = A.B;
@@ -121,12 +121,6 @@ __device__ __forceinline__ void hess_lists_atom(const HessArgs &A, int i, int la
                 }
     }
     if (lane == 0) A.cnt[i] = count;
-}
-
-template <bool WRITE>
-__global__ void __launch_bounds__(64) k_hess_lists(HessArgs A) {
-    if ((int)blockIdx.x >= A.natoms) return;
-    hess_lists_atom<WRITE, !WRITE>(A, blockIdx.x, threadIdx.x);
 }
 
 // ---- per-term derivatives -------------------------------------------------------------------------------------------------
@@ -252,19 +246,14 @@ __device__ __forceinline__ bool trio_d2(const BasisDev *B, const double *c3, int
     return true;
 }
 
-// the triplet of centre c with list entries ea, eb (positions ia != ib in c's list): legs in the evaluator's order -- lower
-// species on leg l; equal species on the unequal legs of a symmetry-1 trio by the reference supercell index as seen from c (NOT
-// by list position: the lists are in (atom, image offset around the nearest image) order); equal species on
-// equal legs, where the order decides nothing, by list position as ever.  Slot of row atom m = the slot of entry `mine` (0: the
-// centre itself)
+// the triplet of centre c with list entries ea, eb (positions ia != ib in c's list): legs in the evaluator's order
+// (trio_swap_legs, uf3_device.h; NOT by list position where the order decides a number: the lists are in (atom, image offset
+// around the nearest image) order), equal species on equal legs by list position as ever.  Slot of row atom m = the slot of
+// entry `mine` (0: the centre itself)
 __device__ __forceinline__ void hess_triplet(const HessArgs &A, double *Hm, double *mix, double *bo, int c, const HessNbr &ea, int ia,
                                              const HessNbr &eb, int ib, int mine) {
     const BasisDev *B = A.B;
-    bool swap = ea.spec > eb.spec;
-    if (ea.spec == eb.spec) {
-        const int t = B->trio_of[(A.spec[c] * UF3_MAX_SPECIES + ea.spec) * UF3_MAX_SPECIES + ea.spec];
-        swap = (t >= 0 && B->trios[t].nsrc == 1) ? supercell_before(eb.shp, eb.j, ea.shp, ea.j) : ia > ib;
-    }
+    const bool swap = trio_swap_legs(B, A.spec[c], ea, eb, ia > ib);
     const HessNbr &ej = swap ? eb : ea, &ek = swap ? ea : eb;
     const int trio = B->trio_of[(A.spec[c] * UF3_MAX_SPECIES + ej.spec) * UF3_MAX_SPECIES + ek.spec];
     if (trio < 0) return;

@@ -74,11 +74,51 @@ struct PinBuf {
     }
     void release() { if (p) hipHostFree(p); p = nullptr; cap = 0; }
 };
-// workspace of the site terms / heat current (uf3_flux.h): one per context for the stand-alone entries, one per MD state
-struct FluxWork {
+// workspace of the per-atom image lists (k_flux_lists): frame table, species, the model's copy, counts and entries; the site
+// records (u, jp: site terms and heat current only) and the host entries' staging block.  One per user -- the context's
+// Hessian entries, its site-term entries, each MD state -- and nothing in it shared.
+struct ListWork {
     Buf frames, offsets, spec, cnt, ent, coeff, flags, u, jp, io;
     int cap = 0;                        // list capacity per atom (an MD state keeps it from sample to sample)
     void release() { for (Buf *b : {&frames, &offsets, &spec, &cnt, &ent, &coeff, &flags, &u, &jp, &io}) b->release(); cap = 0; }
+};
+
+// One device block of a synchronous host entry (uf3_hessian, uf3_site_terms, uf3_heat_flux, uf3_phonon_mesh / _dos / _thermo,
+// uf3_gram, uf3_leverage), cut into sections in the order they are declared.  add() every section (present = false: an optional
+// the caller did not pass), alloc(), then at<T>() is a section's device pointer (null when absent), in() queues uploads, and
+// out() queues the downloads of the outputs that were asked for and is the call's one hipStreamSynchronize.  Offsets and the
+// 16-byte alignment of the sections are computed here and nowhere else.
+// Not for upload_frames and the entries built on it (uf3_featurize*, uf3_eval*, uf3_pair_histogram): their BAR / pinned /
+// deferred staging is what bench.py measures and has invariants of its own (pin_in_busy, staged_in_dev).  Not for the drivers'
+// *_get_state either: those copy out of the state's own buffers.
+struct Stage {
+    enum { MAX_SECTIONS = 8 };
+    Buf &buf;
+    hipStream_t st;
+    size_t off[MAX_SECTIONS], len[MAX_SECTIONS], total = 0;
+    bool here[MAX_SECTIONS];
+    int n = 0;
+    Stage(Buf &b, hipStream_t s) : buf(b), st(s) {}
+    int add(size_t bytes, bool present = true) {
+        if (n == MAX_SECTIONS) { fprintf(stderr, "uf3: Stage: more than %d sections\n", (int)MAX_SECTIONS); abort(); }
+        off[n] = total; len[n] = present ? bytes : 0; here[n] = present;
+        total += (len[n] + 15) / 16 * 16;
+        return n++;
+    }
+    hipError_t alloc() { return buf.ensure(total); }
+    template <class T> T *at(int s) const { return here[s] ? (T *)((char *)buf.p + off[s]) : nullptr; }
+    struct Copy { int s; const void *host; };
+    hipError_t copy(std::initializer_list<Copy> l, bool up) const {
+        for (const Copy &k : l) {
+            if (!k.host || !len[k.s]) continue;
+            void *d = at<char>(k.s), *h = (void *)k.host;
+            hipError_t e = up ? hipMemcpyAsync(d, h, len[k.s], hipMemcpyHostToDevice, st) : hipMemcpyAsync(h, d, len[k.s], hipMemcpyDeviceToHost, st);
+            if (e != hipSuccess) return e;
+        }
+        return up ? hipSuccess : hipStreamSynchronize(st);
+    }
+    hipError_t in(std::initializer_list<Copy> l) const { return copy(l, true); }
+    hipError_t out(std::initializer_list<Copy> l) const { return copy(l, false); }
 };
 #define UF3_PIN_LIMIT (512 * 1024)   // bytes: larger transfers go straight from / to the caller's memory
 #define UF3_BAR_LIMIT (128 * 1024)   // bytes: largest block the host stores into device memory itself (beyond it the copy engine is quicker)
@@ -100,9 +140,11 @@ struct uf3_ctx {
         bin_cnt,                        // atoms per cell-list bin (counting sort)
         part_sums,                      // per-workgroup energy / strain-derivative sums of the MD collection pass (see EvalArgs)
         hist_edges, hist_noise,         // uf3_pair_histogram[_dev]: the caller's bin edges and supercell noise
-        hs_spec, hs_cnt, hs_ent, hs_coeff, hs_part, hs_io,   // uf3_hessian[_dev]: its own lists, model copy, Born shares, host staging
+        hs_part, hs_io,                 // uf3_hessian[_dev]: the row atoms' Born shares | host staging
         ph_ws, ph_part, ph_io;          // uf3_phonon_*: sorted terms and small inputs | smearing partials | host staging
-    FluxWork fx;                        // uf3_site_terms / uf3_heat_flux
+    ListWork hs,                        // uf3_hessian[_dev]: its frame's lists and model copy (a call returns with work queued on them;
+                                        // its u, jp and io stay empty: the Hessian has no site records and stages in hs_io)
+             fx;                        // uf3_site_terms / uf3_heat_flux: theirs, the site records and the host staging
     std::vector<char> ph_stage;         // host image of ph_ws (kept alive behind the asynchronous copy)
     int n3_cap = 0, cand_cap = 0;
     size_t bin_cnt_clean = 0;        // ints of bin_cnt known to be zero (k_bin_fill leaves the counts it used at zero)
@@ -338,11 +380,11 @@ extern "C" void uf3_ctx_destroy(uf3_ctx *c) {
                   &c->key_out, &c->val_in, &c->val_out, &c->sort_tmp, &c->bin_start, &c->slots, &c->flags, &c->n3_cnt, &c->n3_int, &c->n3_dbl, &c->e_atom, &c->nbr_f, &c->coeff,
                   &c->stage_pos, &c->stage_z, &c->stage_out, &c->stage_out2, &c->sp_rows, &c->sp_seg, &c->gram_tij, &c->frag, &c->dbg, &c->halo, &c->n3x_ent, &c->n3x_off,
                   &c->bin_cnt, &c->coeff_cw, &c->part_sums,
-                  &c->hs_spec, &c->hs_cnt, &c->hs_ent, &c->hs_coeff, &c->hs_part, &c->hs_io,
+                  &c->hs_part, &c->hs_io,
                   &c->ph_ws, &c->ph_part, &c->ph_io};
     for (Buf *b : all) b->release();
     for (Buf &b : c->gram_tiles) b.release();
-    c->fx.release();
+    c->hs.release(); c->fx.release();
     if (c->comm) uf3_comm_destroy(c);
     { Buf *mdb[] = {&c->md.ent, &c->md.cnt, &c->md.pos_ref, &c->md.geo, &c->md.frame_of, &c->md.spec, &c->md.inbox, &c->md.surv, &c->md.mark}; for (Buf *b : mdb) b->release(); }
     c->stage_bar.release();
@@ -3370,22 +3412,19 @@ extern "C" int uf3_gram(uf3_ctx *c, const double *x, const double *y, int64_t n_
     if (!c) return fail(nullptr, UF3_EINVAL, "null ctx");
     if (!x || !gram || n_feat < 1 || ld < n_feat || n_rows < 0) return fail(c, UF3_EINVAL, "uf3_gram: bad argument");
     HIPCHK(c, hipSetDevice(c->device));
-    size_t bx = 8 * (size_t)n_rows * ld, bg = 8 * (size_t)n_feat * n_feat, bo = 8 * (size_t)n_feat;
-    HIPCHK(c, c->stage_out2.ensure(bx + 8 * (size_t)n_rows + 64));
-    HIPCHK(c, c->stage_out.ensure(bg + bo));
-    double *dxp = c->stage_out2.as<double>(), *dyp = dxp + (size_t)n_rows * ld;
-    double *dg = c->stage_out.as<double>(), *dord = dg + (size_t)n_feat * n_feat;
-    if (n_rows) HIPCHK(c, hipMemcpyAsync(dxp, x, bx, hipMemcpyHostToDevice, c->stream));
-    if (y && n_rows) HIPCHK(c, hipMemcpyAsync(dyp, y, 8 * (size_t)n_rows, hipMemcpyHostToDevice, c->stream));
-    if (accumulate) {
-        HIPCHK(c, hipMemcpyAsync(dg, gram, bg, hipMemcpyHostToDevice, c->stream));
-        if (ord) HIPCHK(c, hipMemcpyAsync(dord, ord, bo, hipMemcpyHostToDevice, c->stream));
-    }
-    int rc = uf3_gram_dev(c, dxp, y ? dyp : nullptr, n_rows, n_feat, ld, accumulate, dg, (ord && y) ? dord : nullptr);
+    // the rows in stage_out2 (with the 64 bytes of slack behind them that the block has always had), the sums in stage_out
+    Stage I(c->stage_out2, c->stream), O(c->stage_out, c->stream);
+    const int s_x = I.add(8 * (size_t)n_rows * ld), s_y = I.add(8 * (size_t)n_rows, y != nullptr);
+    I.add(64);
+    const int s_g = O.add(8 * (size_t)n_feat * n_feat), s_o = O.add(8 * (size_t)n_feat, ord != nullptr);
+    HIPCHK(c, I.alloc());
+    HIPCHK(c, O.alloc());
+    HIPCHK(c, I.in({{s_x, x}, {s_y, y}}));
+    if (accumulate) HIPCHK(c, O.in({{s_g, gram}, {s_o, ord}}));
+    int rc = uf3_gram_dev(c, I.at<double>(s_x), I.at<double>(s_y), n_rows, n_feat, ld, accumulate, O.at<double>(s_g),
+                          y ? O.at<double>(s_o) : nullptr);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(gram, dg, bg, hipMemcpyDeviceToHost, c->stream));
-    if (ord && y) HIPCHK(c, hipMemcpyAsync(ord, dord, bo, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, O.out({{s_g, gram}, {s_o, y ? ord : nullptr}}));
     return UF3_OK;
 }
 
@@ -3419,16 +3458,19 @@ extern "C" int uf3_leverage(uf3_ctx *c, const double *x, int64_t n_rows, int32_t
         return fail(c, UF3_EINVAL, "uf3_leverage: bad argument (group is 1 or 3 and divides n_rows, ld >= n_feat >= 1)");
     if (n_rows == 0) return UF3_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t bx = 8 * (size_t)n_rows * ld, bw = 8 * (size_t)n_feat * n_feat, bq = 8 * (size_t)(n_rows / group);
-    HIPCHK(c, c->stage_out2.ensure(bx + 64));
-    HIPCHK(c, c->stage_out.ensure(bw + bq + 64));
-    double *dx = c->stage_out2.as<double>(), *dw = c->stage_out.as<double>(), *dq = dw + (size_t)n_feat * n_feat;
-    HIPCHK(c, hipMemcpyAsync(dx, x, bx, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dw, w, bw, hipMemcpyHostToDevice, c->stream));
-    int rc = uf3_leverage_dev(c, dx, n_rows, n_feat, ld, dw, group, dq);
+    // the rows in stage_out2, [w | q] in stage_out, each with the 64 bytes of slack behind it that the block has always had
+    Stage I(c->stage_out2, c->stream), O(c->stage_out, c->stream);
+    const int s_x = I.add(8 * (size_t)n_rows * ld);
+    I.add(64);
+    const int s_w = O.add(8 * (size_t)n_feat * n_feat), s_q = O.add(8 * (size_t)(n_rows / group));
+    O.add(64);
+    HIPCHK(c, I.alloc());
+    HIPCHK(c, O.alloc());
+    HIPCHK(c, I.in({{s_x, x}}));
+    HIPCHK(c, O.in({{s_w, w}}));
+    int rc = uf3_leverage_dev(c, I.at<double>(s_x), n_rows, n_feat, ld, O.at<double>(s_w), group, O.at<double>(s_q));
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(q, dq, bq, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, O.out({{s_q, q}}));
     return UF3_OK;
 }
 
@@ -3903,7 +3945,7 @@ struct uf3_md : Batch {
     bool g_valid = false;                       // the pistons' g_close belongs to the current state
     // heat-current samples (uf3_md_run_flux, uf3_flux.h): the masses as given, the lists' workspace, the records of a run
     DevBuf mass, flux_ring;
-    FluxWork fx;
+    ListWork fx;
     ~uf3_md() { fx.release(); }
 };
 
@@ -4026,9 +4068,9 @@ static int md_launch(uf3_md *md, MdStepArgs &A, bool langevin, int64_t record, i
 }
 
 struct FluxArgs;
-static int flux_prepare(uf3_basis *b, const uf3_frames *fr, FluxWork &W, const int32_t *d_z, const double *c1, const double *c2,
-                        const double *c3, const char *who, FluxArgs &F);
-static int flux_sample(uf3_ctx *c, FluxWork &W, FluxArgs &F, bool headroom, const char *who);
+static int lists_prepare(uf3_basis *b, const uf3_frames *fr, ListWork &W, const int32_t *d_z, const double *c1, const double *c2,
+                         const double *c3, const char *who, const char *what, FluxArgs &F);
+static int flux_sample(uf3_ctx *c, ListWork &W, FluxArgs &F, bool headroom, const char *who);
 
 // one heat-current record of the closed state (velocities at integer time, the positions the forces belong to)
 static int md_flux_sample(uf3_md *md, FluxArgs &F, int64_t record) {
@@ -4047,7 +4089,7 @@ static int md_run(uf3_md *md, int64_t n_steps, double dt, double T, double gamma
     FluxArgs F;
     if (n_flux) {
         HIPCHK(c, md->flux_ring.ensure(48 * (size_t)n_flux * md->n_frames));
-        int rc = flux_prepare(md->b, &md->fr, md->fx, md->z.as<int32_t>(), md->c1.data(), md->c2.data(), md->c3.data(), "uf3_md_run_flux", F);
+        int rc = lists_prepare(md->b, &md->fr, md->fx, md->z.as<int32_t>(), md->c1.data(), md->c2.data(), md->c3.data(), "uf3_md_run_flux", "batch", F);
         if (rc) return rc;
         F.pos = md->pos.as<double>(); F.vel = md->vel.as<double>(); F.mass = md->mass.as<double>(); F.w = nullptr;
     }
@@ -5115,9 +5157,12 @@ extern "C" int uf3_mc_get_state(uf3_mc *m, int32_t *z, double *energies, int64_t
     return UF3_OK;
 }
 
-// ------------------------------------------------------------------------------ analytic Hessian (uf3_hessian.h)
-// the list geometry of one frame (k_hess_lists; shared with the batched lists of uf3_flux.h): lattice rows (zero on a
-// non-periodic axis), the inverse of the completed cell, and the images tried per side around the nearest one
+// ------------------------------------------------------------------------------ per-atom image lists (hess_lists_atom, k_flux_lists)
+// What the Hessian, the site terms / heat current and an MD state's flux samples are computed from.  lists_prepare: what does
+// not change while the atoms move (frame table, species, the model's copy); lists_longest: the count pass; lists_fill: the
+// entries at the workspace's capacity, which the caller derives from the longest list.
+// the list geometry of one frame: lattice rows (zero on a non-periodic axis), the inverse of the completed cell, and the
+// images tried per side around the nearest one
 static int hess_geometry(uf3_ctx *c, const uf3_basis *b, const double *cells, const uint8_t *pbc, const char *who, double *cell_out,
                          double *inv_out, int *per_out, int *nimg_out) {
     // cell: the periodic rows as given; a non-periodic axis gets a unit vector orthogonal to what is there already, so that the
@@ -5165,120 +5210,9 @@ static int hess_geometry(uf3_ctx *c, const uf3_basis *b, const double *cells, co
     return UF3_OK;
 }
 
-static int hessian_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, const double *c1,
-                        const double *c2, const double *c3, int64_t row_begin, int64_t row_end, double *d_hess, double *d_mixed,
-                        double *d_born) {
-    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
-    uf3_ctx *c = b->ctx;
-    if (!fr || fr->n_frames != 1 || !fr->atom_offsets || !fr->cells || !fr->pbc)
-        return fail(c, UF3_EINVAL, "uf3_hessian: exactly one frame");
-    if (!d_pos || !d_z || !c1 || !d_hess) return fail(c, UF3_EINVAL, "uf3_hessian: null argument");
-    if ((b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, "uf3_hessian: missing coefficients");
-    const int64_t N = fr->atom_offsets[1] - fr->atom_offsets[0];
-    if (fr->atom_offsets[0] != 0 || N < 1 || N > (int64_t)1 << 30) return fail(c, UF3_EINVAL, "uf3_hessian: bad atom count");
-    if (row_begin < 0 || row_end > N || row_begin >= row_end)
-        return fail(c, UF3_EINVAL, "uf3_hessian: row span [" + std::to_string(row_begin) + ", " + std::to_string(row_end) +
-                                       ") empty or outside the frame's " + std::to_string(N) + " atoms");
-    if (d_born && (row_begin != 0 || row_end != N))
-        return fail(c, UF3_EINVAL, "uf3_hessian: born needs the whole frame's rows");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const int n = (int)N;
-    HessArgs A;
-    A.B = b->dev; A.pos = d_pos; A.natoms = n;
-    int rc_geo = hess_geometry(c, b, fr->cells, fr->pbc, "uf3_hessian", A.cell, A.inv, A.per, A.nimg);
-    if (rc_geo) return rc_geo;
-    // species
-    HIPCHK(c, c->hs_spec.ensure(sizeof(int) * ((size_t)n + 1)));
-    int *d_spec = c->hs_spec.as<int>(), *d_bad = d_spec + n;
-    HIPCHK(c, hipMemsetAsync(d_bad, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_hess_species, dim3((n + 255) / 256), dim3(256), 0, st, (const BasisDev *)b->dev, d_z, n, d_spec, d_bad);
-    int bad = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (bad) return fail(c, UF3_ESPECIES, "uf3_hessian: the frame contains an element outside the basis");
-    A.spec = d_spec;
-    // model: the library's own copy (the evaluator's model cache is left alone)
-    const size_t n2 = b->c2_len, n3 = b->c3_len;
-    HIPCHK(c, c->hs_coeff.ensure(8 * (n2 + n3 + 1)));
-    double *dc = c->hs_coeff.as<double>();
-    if (n2) HIPCHK(c, hipMemcpyAsync(dc, c2, 8 * n2, hipMemcpyHostToDevice, st));
-    if (n3) HIPCHK(c, hipMemcpyAsync(dc + n2, c3, 8 * n3, hipMemcpyHostToDevice, st));
-    A.c2 = dc; A.c3 = dc + n2;
-    // lists: count, size, fill (every atom: the centres of the rows' triplets may lie anywhere in the frame)
-    HIPCHK(c, c->hs_cnt.ensure(sizeof(int) * (size_t)n));
-    A.cnt = c->hs_cnt.as<int>(); A.cap = 0; A.ent = nullptr; A.bad = d_bad;      // (d_bad is 0: the species check passed)
-    hipLaunchKernelGGL(k_hess_lists<false>, dim3(n), dim3(64), 0, st, A);
-    std::vector<int> cnt((size_t)n);
-    HIPCHK(c, hipMemcpyAsync(cnt.data(), A.cnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (bad) return fail(c, UF3_EINVAL, "uf3_hessian: atoms lie more than 500 cells apart along a periodic axis: wrap the positions");
-    const int cap = std::max(1, *std::max_element(cnt.begin(), cnt.end()));
-    HIPCHK(c, c->hs_ent.ensure(sizeof(HessNbr) * (size_t)n * cap));
-    A.cap = cap; A.ent = c->hs_ent.as<HessNbr>();
-    hipLaunchKernelGGL(k_hess_lists<true>, dim3(n), dim3(64), 0, st, A);
-    // rows
-    const int64_t R = row_end - row_begin;
-    A.row_begin = row_begin; A.row_end = row_end; A.ld = 3 * N;
-    A.hess = d_hess; A.mixed = d_mixed;
-    HIPCHK(c, hipMemsetAsync(d_hess, 0, sizeof(double) * 9 * (size_t)R * (size_t)N, st));
-    if (d_mixed) HIPCHK(c, hipMemsetAsync(d_mixed, 0, sizeof(double) * 18 * (size_t)R, st));
-    A.born_part = nullptr;
-    if (d_born) {
-        HIPCHK(c, c->hs_part.ensure(sizeof(double) * 36 * (size_t)R));
-        A.born_part = c->hs_part.as<double>();
-        HIPCHK(c, hipMemsetAsync(A.born_part, 0, sizeof(double) * 36 * (size_t)R, st));
-    }
-    hipLaunchKernelGGL(k_hessian, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, st, A);
-    if (d_born) hipLaunchKernelGGL(k_hess_born_sum, dim3(36), dim3(256), 0, st, (const double *)A.born_part, (long long)R, d_born);
-    HIPCHK(c, hipGetLastError());
-    return UF3_OK;
-}
-
-extern "C" int uf3_hessian_dev(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, const double *c1,
-                               const double *c2, const double *c3, int64_t row_begin, int64_t row_end, double *d_hess,
-                               double *d_mixed, double *d_born) {
-    return hessian_impl(b, fr, d_pos, d_z, c1, c2, c3, row_begin, row_end, d_hess, d_mixed, d_born);
-}
-
-extern "C" int uf3_hessian(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1,
-                           const double *c2, const double *c3, int64_t row_begin, int64_t row_end, double *hess, double *mixed,
-                           double *born) {
-    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
-    uf3_ctx *c = b->ctx;
-    if (!fr || fr->n_frames != 1 || !fr->atom_offsets) return fail(c, UF3_EINVAL, "uf3_hessian: exactly one frame");
-    if (!pos || !z || !hess) return fail(c, UF3_EINVAL, "uf3_hessian: null argument");
-    const int64_t N = fr->atom_offsets[1] - fr->atom_offsets[0];
-    if (N < 1 || row_begin < 0 || row_end > N || row_begin >= row_end) return hessian_impl(b, fr, pos, z, c1, c2, c3, row_begin, row_end, hess, mixed, born);
-    const int64_t R = row_end - row_begin;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t b_pos = 24 * (size_t)N, b_z = (4 * (size_t)N + 15) / 16 * 16, b_h = 72 * (size_t)R * (size_t)N,
-                 b_m = mixed ? 144 * (size_t)R : 0, b_b = born ? 36 * 8 : 0;
-    HIPCHK(c, c->hs_io.ensure(b_pos + b_z + b_h + b_m + b_b));
-    char *base = c->hs_io.as<char>();
-    double *d_pos = (double *)base;
-    int32_t *d_z = (int32_t *)(base + b_pos);
-    double *d_h = (double *)(base + b_pos + b_z), *d_m = mixed ? (double *)(base + b_pos + b_z + b_h) : nullptr,
-           *d_b = born ? (double *)(base + b_pos + b_z + b_h + b_m) : nullptr;
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_pos, pos, b_pos, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_z, z, 4 * (size_t)N, hipMemcpyHostToDevice, st));
-    int rc = hessian_impl(b, fr, d_pos, d_z, c1, c2, c3, row_begin, row_end, d_h, d_m, d_b);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(hess, d_h, b_h, hipMemcpyDeviceToHost, st));
-    if (mixed) HIPCHK(c, hipMemcpyAsync(mixed, d_m, b_m, hipMemcpyDeviceToHost, st));
-    if (born) HIPCHK(c, hipMemcpyAsync(born, d_b, b_b, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (c->hs_io.cap > ((size_t)1 << 30)) c->hs_io.release();      // (a large slab's staging is not kept for the context's lifetime)
-    return UF3_OK;
-}
-
-// ------------------------------------------------------------------------------ site terms and the heat current (uf3_flux.h)
-// flux_prepare: what does not change between the samples of one call (frame table, species, the model's copy);
-// flux_sample: lists, k_flux_site_terms, k_flux_frame on device positions (and velocities).
-static int flux_prepare(uf3_basis *b, const uf3_frames *fr, FluxWork &W, const int32_t *d_z, const double *c1, const double *c2,
-                        const double *c3, const char *who, FluxArgs &F) {
+// Fills F with everything but the positions and the outputs.  what: "frame" or "batch", for the species message.
+static int lists_prepare(uf3_basis *b, const uf3_frames *fr, ListWork &W, const int32_t *d_z, const double *c1, const double *c2,
+                         const double *c3, const char *who, const char *what, FluxArgs &F) {
     uf3_ctx *c = b->ctx;
     const std::string me(who);
     if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, me + ": bad uf3_frames");
@@ -5306,8 +5240,7 @@ static int flux_prepare(uf3_basis *b, const uf3_frames *fr, FluxWork &W, const i
     HIPCHK(c, W.spec.ensure(sizeof(int) * (size_t)n));
     HIPCHK(c, W.cnt.ensure(sizeof(int) * (size_t)n));
     HIPCHK(c, W.flags.ensure(sizeof(int) * 4));
-    HIPCHK(c, W.u.ensure(8 * (size_t)n));
-    HIPCHK(c, W.jp.ensure(24 * (size_t)n));
+    // the model: the library's own copy (the evaluator's model cache is left alone)
     const size_t n1 = (size_t)b->host.S, n2 = b->c2_len, n3 = b->c3_len;
     HIPCHK(c, W.coeff.ensure(8 * (n1 + n2 + n3 + 1)));
     double *dc = W.coeff.as<double>();
@@ -5324,38 +5257,141 @@ static int flux_prepare(uf3_basis *b, const uf3_frames *fr, FluxWork &W, const i
     int bad = 0;
     HIPCHK(c, hipMemcpyAsync(&bad, d_flags + 2, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    if (bad) return fail(c, UF3_ESPECIES, me + ": the batch contains an element outside the basis");
+    if (bad) return fail(c, UF3_ESPECIES, me + ": the " + what + " contains an element outside the basis");
     F = FluxArgs();
     F.B = b->dev; F.frames = W.frames.as<FluxFrame>(); F.offsets = W.offsets.as<int64_t>(); F.n_frames = nf; F.n = n;
     F.spec = W.spec.as<int>(); F.cnt = W.cnt.as<int>(); F.flags = d_flags;
     F.c1 = dc; F.c2 = dc + n1; F.c3 = dc + n1 + n2;
-    F.u = W.u.as<double>(); F.jp = W.jp.as<double>();
     return UF3_OK;
 }
 
-// F.pos, F.vel (null: no current), F.mass, F.u, F.w (null: no virials), F.flux set by the caller.  headroom: keep the
-// capacity between calls (an MD run: sized at the first sample, grown when a list overflows).
-static int flux_sample(uf3_ctx *c, FluxWork &W, FluxArgs &F, bool headroom, const char *who) {
+// the count pass on F.pos: the longest list of the batch (at least 1)
+static int lists_longest(uf3_ctx *c, FluxArgs &F, const char *who, int &longest) {
+    hipStream_t st = c->stream;
+    const size_t n = (size_t)F.n;
+    F.cap = 0; F.ent = nullptr;
+    hipLaunchKernelGGL(k_flux_lists<false>, dim3((unsigned)n), dim3(64), 0, st, F);
+    std::vector<int> cnt(n);
+    int flags[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(cnt.data(), F.cnt, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(flags, F.flags, sizeof(flags), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (flags[0]) return fail(c, UF3_EINVAL, std::string(who) + ": atoms lie more than 500 cells apart along a periodic axis: wrap the positions");
+    longest = std::max(1, *std::max_element(cnt.begin(), cnt.end()));
+    return UF3_OK;
+}
+
+// the fill pass on F.pos at capacity W.cap (every atom: the centres of a row's triplets may lie anywhere in its frame)
+static int lists_fill(uf3_ctx *c, ListWork &W, FluxArgs &F) {
+    HIPCHK(c, W.ent.ensure(sizeof(HessNbr) * (size_t)F.n * (size_t)W.cap));
+    F.cap = W.cap; F.ent = W.ent.as<HessNbr>();
+    hipLaunchKernelGGL(k_flux_lists<true>, dim3((unsigned)F.n), dim3(64), 0, c->stream, F);
+    return UF3_OK;
+}
+
+// ------------------------------------------------------------------------------ analytic Hessian (uf3_hessian.h)
+// The one-frame case of the batched lists, sized exactly; the lists live in the context's own workspace (hs), which no other
+// entry touches: uf3_hessian_dev returns with k_hessian queued on them.
+static int hessian_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, const double *c1,
+                        const double *c2, const double *c3, int64_t row_begin, int64_t row_end, double *d_hess, double *d_mixed,
+                        double *d_born) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    uf3_ctx *c = b->ctx;
+    if (!fr || fr->n_frames != 1 || !fr->atom_offsets || !fr->cells || !fr->pbc)
+        return fail(c, UF3_EINVAL, "uf3_hessian: exactly one frame");
+    if (!d_pos || !d_z || !c1 || !d_hess) return fail(c, UF3_EINVAL, "uf3_hessian: null argument");
+    if ((b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, "uf3_hessian: missing coefficients");
+    const int64_t N = fr->atom_offsets[1] - fr->atom_offsets[0];
+    if (fr->atom_offsets[0] != 0 || N < 1 || N > (int64_t)1 << 30) return fail(c, UF3_EINVAL, "uf3_hessian: bad atom count");
+    if (row_begin < 0 || row_end > N || row_begin >= row_end)
+        return fail(c, UF3_EINVAL, "uf3_hessian: row span [" + std::to_string(row_begin) + ", " + std::to_string(row_end) +
+                                       ") empty or outside the frame's " + std::to_string(N) + " atoms");
+    if (d_born && (row_begin != 0 || row_end != N))
+        return fail(c, UF3_EINVAL, "uf3_hessian: born needs the whole frame's rows");
+    ListWork &W = c->hs;
+    FluxArgs F;
+    // (the argument checks of lists_prepare cannot fire here: every case was refused above, in the Hessian's own words)
+    int rc = lists_prepare(b, fr, W, d_z, c1, c2, c3, "uf3_hessian", "frame", F);
+    if (rc) return rc;
+    F.pos = d_pos;
+    rc = lists_longest(c, F, "uf3_hessian", W.cap);
+    if (rc) return rc;
+    rc = lists_fill(c, W, F);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    HessArgs A = {};      // (geometry and bad stay zero: the list build's, filled per frame by k_flux_lists; k_hessian reads none)
+    A.B = b->dev; A.pos = d_pos; A.spec = F.spec; A.natoms = (int)N;
+    A.cap = F.cap; A.cnt = F.cnt; A.ent = F.ent; A.c2 = F.c2; A.c3 = F.c3;
+    const int64_t R = row_end - row_begin;
+    A.row_begin = row_begin; A.row_end = row_end; A.ld = 3 * N;
+    A.hess = d_hess; A.mixed = d_mixed;
+    HIPCHK(c, hipMemsetAsync(d_hess, 0, sizeof(double) * 9 * (size_t)R * (size_t)N, st));
+    if (d_mixed) HIPCHK(c, hipMemsetAsync(d_mixed, 0, sizeof(double) * 18 * (size_t)R, st));
+    if (d_born) {
+        HIPCHK(c, c->hs_part.ensure(sizeof(double) * 36 * (size_t)R));
+        A.born_part = c->hs_part.as<double>();
+        HIPCHK(c, hipMemsetAsync(A.born_part, 0, sizeof(double) * 36 * (size_t)R, st));
+    }
+    hipLaunchKernelGGL(k_hessian, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, st, A);
+    if (d_born) hipLaunchKernelGGL(k_hess_born_sum, dim3(36), dim3(256), 0, st, (const double *)A.born_part, (long long)R, d_born);
+    HIPCHK(c, hipGetLastError());
+    return UF3_OK;
+}
+
+extern "C" int uf3_hessian_dev(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, const double *c1,
+                               const double *c2, const double *c3, int64_t row_begin, int64_t row_end, double *d_hess,
+                               double *d_mixed, double *d_born) {
+    return hessian_impl(b, fr, d_pos, d_z, c1, c2, c3, row_begin, row_end, d_hess, d_mixed, d_born);
+}
+
+extern "C" int uf3_hessian(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1,
+                           const double *c2, const double *c3, int64_t row_begin, int64_t row_end, double *hess, double *mixed,
+                           double *born) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    uf3_ctx *c = b->ctx;
+    if (!fr || fr->n_frames != 1 || !fr->atom_offsets) return fail(c, UF3_EINVAL, "uf3_hessian: exactly one frame");
+    if (!pos || !z || !hess) return fail(c, UF3_EINVAL, "uf3_hessian: null argument");
+    const int64_t N = fr->atom_offsets[1] - fr->atom_offsets[0];
+    if (N < 1 || row_begin < 0 || row_end > N || row_begin >= row_end) return hessian_impl(b, fr, pos, z, c1, c2, c3, row_begin, row_end, hess, mixed, born);
+    const size_t R = (size_t)(row_end - row_begin), n = (size_t)N;
+    HIPCHK(c, hipSetDevice(c->device));
+    Stage S(c->hs_io, c->stream);
+    const int s_pos = S.add(24 * n), s_z = S.add(4 * n), s_h = S.add(72 * R * n), s_m = S.add(144 * R, mixed != nullptr),
+              s_b = S.add(36 * 8, born != nullptr);
+    HIPCHK(c, S.alloc());
+    HIPCHK(c, S.in({{s_pos, pos}, {s_z, z}}));
+    int rc = hessian_impl(b, fr, S.at<double>(s_pos), S.at<int32_t>(s_z), c1, c2, c3, row_begin, row_end, S.at<double>(s_h),
+                          S.at<double>(s_m), S.at<double>(s_b));
+    if (rc) return rc;
+    HIPCHK(c, S.out({{s_h, hess}, {s_m, mixed}, {s_b, born}}));
+    if (c->hs_io.cap > ((size_t)1 << 30)) c->hs_io.release();      // (a large slab's staging is not kept for the context's lifetime)
+    return UF3_OK;
+}
+
+// ------------------------------------------------------------------------------ site terms and the heat current (uf3_flux.h)
+// lists, k_flux_site_terms, k_flux_frame on device positions (and velocities).  F from lists_prepare, and F.pos, F.vel
+// (null: no current), F.mass, F.u (null: the workspace's), F.w (null: no virials), F.flux set by the caller.  headroom: keep
+// the capacity between calls (an MD run: sized at the first sample with room to move, grown when a list overflows); without
+// it the lists are sized exactly for these positions.
+static int flux_sample(uf3_ctx *c, ListWork &W, FluxArgs &F, bool headroom, const char *who) {
     hipStream_t st = c->stream;
     const std::string me(who);
     const unsigned n = (unsigned)F.n;
+    HIPCHK(c, W.u.ensure(8 * (size_t)n));
+    HIPCHK(c, W.jp.ensure(24 * (size_t)n));
+    if (!F.u) F.u = W.u.as<double>();
+    F.jp = W.jp.as<double>();
     for (int attempt = 0; attempt < 3; attempt++) {
         if (!headroom || W.cap == 0) {
-            F.cap = 0; F.ent = nullptr;
-            hipLaunchKernelGGL(k_flux_lists<false>, dim3(n), dim3(64), 0, st, F);
-            std::vector<int> cnt((size_t)n);
-            int flags[2] = {0, 0};
-            HIPCHK(c, hipMemcpyAsync(cnt.data(), F.cnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipMemcpyAsync(flags, F.flags, sizeof(flags), hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            if (flags[0]) return fail(c, UF3_EINVAL, me + ": atoms lie more than 500 cells apart along a periodic axis: wrap the positions");
-            const int longest = std::max(1, *std::max_element(cnt.begin(), cnt.end()));
+            int longest;
+            int rc = lists_longest(c, F, who, longest);
+            if (rc) return rc;
             W.cap = headroom ? longest + longest / 4 + 8 : longest;
+            // (k_flux_site_terms' index array, [cap] ints of LDS: its limit, not the lists')
             if (W.cap > 12288) return fail(c, UF3_EINVAL, me + ": more than 12288 neighbours of one atom");
         }
-        HIPCHK(c, W.ent.ensure(sizeof(HessNbr) * (size_t)n * (size_t)W.cap));
-        F.cap = W.cap; F.ent = W.ent.as<HessNbr>();
-        hipLaunchKernelGGL(k_flux_lists<true>, dim3(n), dim3(64), 0, st, F);
+        int rc = lists_fill(c, W, F);
+        if (rc) return rc;
         const size_t lds = sizeof(int) * (size_t)F.cap;
         const bool want_w = F.w != nullptr, want_j = F.vel != nullptr;
         if (want_w && want_j) hipLaunchKernelGGL((k_flux_site_terms<true, true>), dim3(n), dim3(64), lds, st, F);
@@ -5382,10 +5418,9 @@ static int site_terms_impl(uf3_basis *b, const uf3_frames *fr, const double *d_p
     uf3_ctx *c = b->ctx;
     if (!d_pos) return fail(c, UF3_EINVAL, std::string(who) + ": null argument");
     FluxArgs F;
-    int rc = flux_prepare(b, fr, c->fx, d_z, c1, c2, c3, who, F);
+    int rc = lists_prepare(b, fr, c->fx, d_z, c1, c2, c3, who, "batch", F);
     if (rc) return rc;
-    F.pos = d_pos; F.vel = d_vel; F.mass = d_mass; F.w = d_w; F.flux = d_flux;
-    if (d_u) F.u = d_u;
+    F.pos = d_pos; F.vel = d_vel; F.mass = d_mass; F.u = d_u; F.w = d_w; F.flux = d_flux;
     return flux_sample(c, c->fx, F, false, who);
 }
 
@@ -5410,19 +5445,15 @@ extern "C" int uf3_site_terms(uf3_basis *b, const uf3_frames *fr, const double *
     if (!site_energies && !site_virials) return fail(c, UF3_EINVAL, "uf3_site_terms: nothing asked for");
     const size_t n = (size_t)fr->atom_offsets[fr->n_frames];
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t b_pos = 24 * n, b_z = (4 * n + 15) / 16 * 16, b_u = 8 * n, b_w = site_virials ? 72 * n : 0;
-    HIPCHK(c, c->fx.io.ensure(b_pos + b_z + b_u + b_w));
-    char *base = c->fx.io.as<char>();
-    double *d_pos = (double *)base, *d_u = (double *)(base + b_pos + b_z), *d_w = site_virials ? (double *)(base + b_pos + b_z + b_u) : nullptr;
-    int32_t *d_z = (int32_t *)(base + b_pos);
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_pos, pos, b_pos, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_z, z, 4 * n, hipMemcpyHostToDevice, st));
-    int rc = site_terms_impl(b, fr, d_pos, nullptr, d_z, nullptr, c1, c2, c3, d_u, d_w, nullptr, "uf3_site_terms");
+    Stage S(c->fx.io, c->stream);
+    // (the energies' section is there whether or not they are asked for: the kernel writes them either way)
+    const int s_pos = S.add(24 * n), s_z = S.add(4 * n), s_u = S.add(8 * n), s_w = S.add(72 * n, site_virials != nullptr);
+    HIPCHK(c, S.alloc());
+    HIPCHK(c, S.in({{s_pos, pos}, {s_z, z}}));
+    int rc = site_terms_impl(b, fr, S.at<double>(s_pos), nullptr, S.at<int32_t>(s_z), nullptr, c1, c2, c3, S.at<double>(s_u),
+                             S.at<double>(s_w), nullptr, "uf3_site_terms");
     if (rc) return rc;
-    if (site_energies) HIPCHK(c, hipMemcpyAsync(site_energies, d_u, b_u, hipMemcpyDeviceToHost, st));
-    if (site_virials) HIPCHK(c, hipMemcpyAsync(site_virials, d_w, b_w, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, S.out({{s_u, site_energies}, {s_w, site_virials}}));
     return UF3_OK;
 }
 
@@ -5446,22 +5477,15 @@ extern "C" int uf3_heat_flux(uf3_basis *b, const uf3_frames *fr, const double *p
         if (!(masses[i] > 0.0) || !std::isfinite(masses[i])) return fail(c, UF3_EINVAL, "uf3_heat_flux: masses must be positive and finite");
     if (!md_finite(vel, 3 * n)) return fail(c, UF3_EINVAL, "uf3_heat_flux: velocities must be finite");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t b_pos = 24 * n, b_z = (4 * n + 15) / 16 * 16, b_m = 8 * n, b_f = 48 * nf;
-    HIPCHK(c, c->fx.io.ensure(2 * b_pos + b_z + 2 * b_m + b_f));
-    char *base = c->fx.io.as<char>();
-    double *d_pos = (double *)base, *d_vel = (double *)(base + b_pos);
-    int32_t *d_z = (int32_t *)(base + 2 * b_pos);
-    double *d_m = (double *)(base + 2 * b_pos + b_z), *d_u = d_m + n, *d_f = d_u + n;
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_pos, pos, b_pos, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_vel, vel, b_pos, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_z, z, 4 * n, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_m, masses, b_m, hipMemcpyHostToDevice, st));
-    int rc = site_terms_impl(b, fr, d_pos, d_vel, d_z, d_m, c1, c2, c3, d_u, nullptr, d_f, "uf3_heat_flux");
+    Stage S(c->fx.io, c->stream);
+    const int s_pos = S.add(24 * n), s_vel = S.add(24 * n), s_z = S.add(4 * n), s_m = S.add(8 * n), s_u = S.add(8 * n),
+              s_f = S.add(48 * nf);
+    HIPCHK(c, S.alloc());
+    HIPCHK(c, S.in({{s_pos, pos}, {s_vel, vel}, {s_z, z}, {s_m, masses}}));
+    int rc = site_terms_impl(b, fr, S.at<double>(s_pos), S.at<double>(s_vel), S.at<int32_t>(s_z), S.at<double>(s_m), c1, c2, c3,
+                             S.at<double>(s_u), nullptr, S.at<double>(s_f), "uf3_heat_flux");
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(flux, d_f, b_f, hipMemcpyDeviceToHost, st));
-    if (site_energies) HIPCHK(c, hipMemcpyAsync(site_energies, d_u, b_m, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, S.out({{s_f, flux}, {s_u, site_energies}}));
     return UF3_OK;
 }
 
@@ -5555,22 +5579,15 @@ extern "C" int uf3_phonon_mesh(uf3_ctx *c, int32_t n_atoms, int64_t n_sc_atoms, 
         return phonon_mesh_impl(c, n_atoms, n_sc_atoms, fc, inv_sqrt_mass, n_terms, terms, term_w, nq, q, lam, status);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n3 = 3 * (size_t)n_atoms;
-    const size_t b_fc = 8 * n3 * 3 * (size_t)n_sc_atoms, b_m = (8 * (size_t)n_atoms + 15) / 16 * 16, b_q = 24 * (size_t)nq,
-                 b_l = 8 * n3 * (size_t)nq, b_s = 4 * (size_t)nq;
-    HIPCHK(c, c->ph_io.ensure(b_fc + b_m + b_q + b_l + b_s));
-    char *base = c->ph_io.as<char>();
-    double *d_fc = (double *)base, *d_m = (double *)(base + b_fc), *d_q = (double *)(base + b_fc + b_m),
-           *d_l = (double *)(base + b_fc + b_m + b_q);
-    int32_t *d_s = (int32_t *)(base + b_fc + b_m + b_q + b_l);
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_fc, fc, b_fc, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_m, inv_sqrt_mass, 8 * (size_t)n_atoms, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_q, q, b_q, hipMemcpyHostToDevice, st));
-    int rc = phonon_mesh_impl(c, n_atoms, n_sc_atoms, d_fc, d_m, n_terms, terms, term_w, nq, d_q, d_l, d_s);
+    Stage S(c->ph_io, c->stream);
+    const int s_fc = S.add(8 * n3 * 3 * (size_t)n_sc_atoms), s_m = S.add(8 * (size_t)n_atoms), s_q = S.add(24 * (size_t)nq),
+              s_l = S.add(8 * n3 * (size_t)nq), s_s = S.add(4 * (size_t)nq);
+    HIPCHK(c, S.alloc());
+    HIPCHK(c, S.in({{s_fc, fc}, {s_m, inv_sqrt_mass}, {s_q, q}}));
+    int rc = phonon_mesh_impl(c, n_atoms, n_sc_atoms, S.at<double>(s_fc), S.at<double>(s_m), n_terms, terms, term_w, nq,
+                              S.at<double>(s_q), S.at<double>(s_l), S.at<int32_t>(s_s));
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(lam, d_l, b_l, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(status, d_s, b_s, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, S.out({{s_l, lam}, {s_s, status}}));
     return UF3_OK;
 }
 
@@ -5647,18 +5664,6 @@ extern "C" int uf3_phonon_dos_dev(uf3_ctx *c, int32_t n_modes, int64_t nq, const
     return phonon_dos_impl(c, n_modes, nq, d_lam, d_wq, n_bins, edges, d_counts, n_samples, samples, sigma, d_dos);
 }
 
-// lam | wq of a host entry into ph_io; *d_wq NULL when wq is
-static int phonon_stage_modes(uf3_ctx *c, int32_t n_modes, int64_t nq, const double *lam, const int64_t *wq, size_t extra, double **d_lam,
-                              int64_t **d_wq, char **d_extra) {
-    const size_t b_l = 8 * (size_t)n_modes * (size_t)nq, b_w = wq ? 8 * (size_t)nq : 0;
-    HIPCHK(c, c->ph_io.ensure(b_l + b_w + extra));
-    char *base = c->ph_io.as<char>();
-    *d_lam = (double *)base; *d_wq = wq ? (int64_t *)(base + b_l) : nullptr; *d_extra = base + b_l + b_w;
-    HIPCHK(c, hipMemcpyAsync(*d_lam, lam, b_l, hipMemcpyHostToDevice, c->stream));
-    if (wq) HIPCHK(c, hipMemcpyAsync(*d_wq, wq, b_w, hipMemcpyHostToDevice, c->stream));
-    return UF3_OK;
-}
-
 extern "C" int uf3_phonon_dos(uf3_ctx *c, int32_t n_modes, int64_t nq, const double *lam, const int64_t *wq, int32_t n_bins,
                               const double *edges, int64_t *counts, int32_t n_samples, const double *samples, double sigma, double *dos) {
     if (!c) return fail(nullptr, UF3_EINVAL, "uf3_phonon_dos: ctx is NULL");
@@ -5666,18 +5671,15 @@ extern "C" int uf3_phonon_dos(uf3_ctx *c, int32_t n_modes, int64_t nq, const dou
         (counts && (n_bins < 1 || n_bins > (1 << 24))) || (dos && (n_samples < 1 || n_samples > (1 << 24))))
         return phonon_dos_impl(c, n_modes, nq, lam, wq, n_bins, edges, counts, n_samples, samples, sigma, dos);
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t b_c = counts ? 8 * (size_t)n_bins : 0, b_d = dos ? 8 * (size_t)n_samples : 0;
-    double *d_lam; int64_t *d_wq; char *d_out;
-    int rc = phonon_stage_modes(c, n_modes, nq, lam, wq, b_c + b_d, &d_lam, &d_wq, &d_out);
+    Stage S(c->ph_io, c->stream);
+    const int s_l = S.add(8 * (size_t)n_modes * (size_t)nq), s_w = S.add(8 * (size_t)nq, wq != nullptr),
+              s_c = S.add(8 * (size_t)n_bins, counts != nullptr), s_d = S.add(8 * (size_t)n_samples, dos != nullptr);
+    HIPCHK(c, S.alloc());
+    HIPCHK(c, S.in({{s_l, lam}, {s_w, wq}}));
+    int rc = phonon_dos_impl(c, n_modes, nq, S.at<double>(s_l), S.at<int64_t>(s_w), n_bins, edges, S.at<int64_t>(s_c), n_samples,
+                             samples, sigma, S.at<double>(s_d));
     if (rc) return rc;
-    int64_t *d_c = counts ? (int64_t *)d_out : nullptr;
-    double *d_d = dos ? (double *)(d_out + b_c) : nullptr;
-    rc = phonon_dos_impl(c, n_modes, nq, d_lam, d_wq, n_bins, edges, d_c, n_samples, samples, sigma, d_d);
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    if (counts) HIPCHK(c, hipMemcpyAsync(counts, d_c, b_c, hipMemcpyDeviceToHost, st));
-    if (dos) HIPCHK(c, hipMemcpyAsync(dos, d_d, b_d, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, S.out({{s_c, counts}, {s_d, dos}}));
     return UF3_OK;
 }
 
@@ -5715,19 +5717,15 @@ extern "C" int uf3_phonon_thermo(uf3_ctx *c, int32_t n_modes, int64_t nq, const 
         n_temps > 65535)
         return phonon_thermo_impl(c, n_modes, nq, lam, wq, n_temps, temps, cutoff_thz, out, zpe, excluded);
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t b_o = 32 * (size_t)n_temps;
-    double *d_lam; int64_t *d_wq; char *d_x;
-    int rc = phonon_stage_modes(c, n_modes, nq, lam, wq, b_o + 16, &d_lam, &d_wq, &d_x);
+    Stage S(c->ph_io, c->stream);
+    const int s_l = S.add(8 * (size_t)n_modes * (size_t)nq), s_w = S.add(8 * (size_t)nq, wq != nullptr),
+              s_o = S.add(32 * (size_t)n_temps), s_z = S.add(8), s_e = S.add(8);
+    HIPCHK(c, S.alloc());
+    HIPCHK(c, S.in({{s_l, lam}, {s_w, wq}}));
+    int rc = phonon_thermo_impl(c, n_modes, nq, S.at<double>(s_l), S.at<int64_t>(s_w), n_temps, temps, cutoff_thz, S.at<double>(s_o),
+                                S.at<double>(s_z), S.at<int64_t>(s_e));
     if (rc) return rc;
-    double *d_o = (double *)d_x, *d_z = (double *)(d_x + b_o);
-    int64_t *d_e = (int64_t *)(d_x + b_o + 8);
-    rc = phonon_thermo_impl(c, n_modes, nq, d_lam, d_wq, n_temps, temps, cutoff_thz, d_o, d_z, d_e);
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(out, d_o, b_o, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(zpe, d_z, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(excluded, d_e, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, S.out({{s_o, out}, {s_z, zpe}, {s_e, excluded}}));
     return UF3_OK;
 }
 

@@ -639,7 +639,7 @@ __global__ void k_max_count(const int *cnt, int n, int *out) {
 //   centre ghost, k real       -> compare the two real indices;
 //   centre ghost, k ghost      -> m (real) is always j.
 // Only matters for symmetry-1 trios with equal neighbour species; reproduced for parity by the FEATURIZER, whose force rows are
-// the reference's.  The evaluator does not follow it where it decides a number: trio_legs_differ below.
+// the reference's.  The evaluator does not follow it where it decides a number: trio_legs_differ (uf3_device.h).
 __device__ __forceinline__ bool neighbour_is_first(const FrameGeom &g, int sm, int ksp, int s0, int s1, int s2,
                                                    int m_local, int msidx, int ksidx, int kshift, int k_local) {
     (void)g; (void)msidx;
@@ -657,8 +657,7 @@ __device__ __forceinline__ bool neighbour_is_first(const FrameGeom &g, int sm, i
 // seen from the REAL copy of the centre takes leg l (msidx: m numbered from c; ksidx: the entry's own): the order of the centre's
 // list, which the centre pass walks.  The gathered forces are then minus the gradient of the energy, as the centre pass's are,
 // and not the reference's.  On a trio with equal l and m legs either assignment is the same function;
-// there the caller keeps neighbour_is_first, and with it the bits it has always produced.
-__device__ __forceinline__ bool trio_legs_differ(const BasisDev *B, int trio) { return trio >= 0 && B->trios[trio].nsrc == 1; }
+// there the caller keeps neighbour_is_first, and with it the bits it has always produced.  (trio_legs_differ: uf3_device.h.)
 
 // ---------------------------------------------------------------------------------
 // featurizer
