@@ -528,6 +528,20 @@ int uf3_ctx_md_live(uf3_ctx *ctx, int32_t *live);
  * UF3_EINVAL). */
 int uf3_md_run_flux(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
                     double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t flux_every, double *flux);
+/* uf3_md_run with grade samples (uf3_site_rows.h; the definitions stand in front of uf3_site_rows below): what uf3_md_run does,
+ * and after every grade_every-th step of the run one record [n_frames][2] = (the frame's largest site grade, the frame-local
+ * index of its atom as a double) of the closed state, placed exactly as uf3_md_run_flux places a heat-current sample: the
+ * trajectory and the thermo records keep their bits, and run(a); run(b) gives the records of run(a + b).  d_w: uf3_leverage's W
+ * [n_feat][n_feat] ON THE DEVICE.  grades must hold n_steps / grade_every records (NULL when none is due).  grade_stop > 0: the
+ * run ends after the first sample in which any frame's maximum exceeds grade_stop; *steps_done is the number of completed steps of
+ * this call, the state is that of a run of *steps_done steps bit for bit (a later run continues from it), and only the thermo and
+ * grade records due up to that sample are filled.  grade_stop <= 0: never.  The whole batch stops, not the one frame.  The
+ * samples' lists are the state's own, as for the flux; one stream synchronisation per sample.  The grades describe the WRAPPED
+ * frame, as uf3_site_terms does.  No constant-pressure variant, and no entry that samples grades and the heat current in one run
+ * (the Python layer refuses both pairs). */
+int uf3_md_run_grade(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
+                     double skin, int64_t thermo_every, int with_stress, double *thermo, const double *d_w, int64_t grade_every,
+                     double grade_stop, double *grades, int64_t *steps_done);
 int uf3_philox_debug(uf3_ctx *ctx, int64_t n, const uint32_t *counters, const uint32_t *keys, uint32_t *out);
 
 /*
@@ -692,6 +706,37 @@ int uf3_heat_flux(uf3_basis *basis, const uf3_frames *frames, const double *pos,
 int uf3_heat_flux_dev(uf3_basis *basis, const uf3_frames *frames, const double *d_pos, const double *d_vel, const int32_t *d_z,
                       const double *d_masses, const double *c1, const double *c2, const double *c3, double *d_flux,
                       double *d_site_energies);
+
+/*
+ * Site rows and extrapolation grades (uf3_site_rows.h): how far an ATOM lies from the fit.
+ *   Site row   rows[i][0 .. F) . c == U_i, uf3_site_terms' site energy, for EVERY flat coefficient vector c (the featurizer's
+ *              column order, length n_feat, frozen columns included: what the calculator expands into c1 / c2 / c3).  The same
+ *              partition, the same leg rule (on a symmetry-1 trio the supercell-index tie-break decides which column a product
+ *              lands in), the same nearest-image lists; the fold from (trio, bin triple) to column is the table the
+ *              featurizer's energy row uses.  The sum of a frame's rows is uf3_featurize's energy row of the wrapped frame.
+ *   Grade      grade[i] = |W b_i|^2 = b_i^T (G + R^T R)^-1 b_i with uf3_leverage's W (lower triangular with exact zeros above
+ *              the diagonal, frozen columns as zero rows and columns): the predictive variance of the site energy up to the
+ *              noise scale.
+ *   uf3_site_rows    rows [N][ld], ld >= n_feat; columns n_feat .. ld are not written.  Takes no coefficients.  The grades
+ *                    describe the WRAPPED frame, as uf3_site_terms does: an atom outside its cell counts as its image inside.
+ *   uf3_site_grade   grade [N]; frame_max / frame_argmax [n_frames] (either may be NULL): the largest grade of each frame and
+ *                    the frame-local index of its atom, the lowest index on ties, from a fixed reduction tree.  Here, and
+ *                    here only, a frame may be empty: it gives 0 and -1.  The grades describe the WRAPPED frame, as
+ *                    uf3_site_terms does.  A tile of 16 rows is built in LDS and multiplied by W on the fp64 matrix cores;
+ *                    where 16 rows of this basis and the lists' index arrays do not fit 80 KB of LDS (n_feat above about 600)
+ *                    the entry goes through chunks of site rows in a context-owned scratch of at most 64 MB and uf3_leverage's
+ *                    kernel instead: the same numbers within uf3_leverage's summation-order bound.
+ * One wave per centre, the row accumulated in LDS, plain stores, no global atomics: results repeat bit for bit and a frame's do
+ * not depend on the batch around it.  A 2-body-only basis is allowed.  Errors as uf3_site_terms: bad frames, null pointers, atoms
+ * more than 500 cells apart along a periodic axis, a cell far thinner than the cut-off, a list or a row too long for LDS
+ * (UF3_EINVAL); an element outside the basis (UF3_ESPECIES).  _dev: device pos, z, w and outputs.
+ */
+int uf3_site_rows(uf3_basis *basis, const uf3_frames *frames, const double *pos, const int32_t *z, double *rows, int64_t ld);
+int uf3_site_rows_dev(uf3_basis *basis, const uf3_frames *frames, const double *d_pos, const int32_t *d_z, double *d_rows, int64_t ld);
+int uf3_site_grade(uf3_basis *basis, const uf3_frames *frames, const double *pos, const int32_t *z, const double *w, double *grade,
+                   double *frame_max, int32_t *frame_argmax);
+int uf3_site_grade_dev(uf3_basis *basis, const uf3_frames *frames, const double *d_pos, const int32_t *d_z, const double *d_w,
+                       double *d_grade, double *d_frame_max, int32_t *d_frame_argmax);
 
 /*
  * Analytic second derivatives of the energy uf3_eval computes on the WRAPPED frame, for ONE frame (uf3_hessian.h; the Gamma-point

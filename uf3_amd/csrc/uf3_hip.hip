@@ -2,6 +2,7 @@
 // contexts, device-resident basis tables, per-call frame geometry, kernel launches.
 #include <algorithm>
 #include <array>
+#include <functional>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -28,6 +29,7 @@
 #include "uf3_mc.h"
 #include "uf3_phonon.h"
 #include "uf3_flux.h"
+#include "uf3_site_rows.h"
 #include <chrono>
 #include <dlfcn.h>
 
@@ -144,7 +146,10 @@ struct uf3_ctx {
         ph_ws, ph_part, ph_io;          // uf3_phonon_*: sorted terms and small inputs | smearing partials | host staging
     ListWork hs,                        // uf3_hessian[_dev]: its frame's lists and model copy (a call returns with work queued on them;
                                         // its u, jp and io stay empty: the Hessian has no site records and stages in hs_io)
-             fx;                        // uf3_site_terms / uf3_heat_flux: theirs, the site records and the host staging
+             fx;                        // uf3_site_terms / uf3_heat_flux / uf3_site_rows / uf3_site_grade: theirs, the site records
+                                        // and the host staging
+    Buf site_rows_ws, site_off;         // uf3_site_grade: the fall-back's chunk of rows (bounded) | the caller's frame offsets
+    bool site_grade_lds_set = false;    // k_site_grade may take SG_LDS_BUDGET of dynamic LDS
     std::vector<char> ph_stage;         // host image of ph_ws (kept alive behind the asynchronous copy)
     int n3_cap = 0, cand_cap = 0;
     size_t bin_cnt_clean = 0;        // ints of bin_cnt known to be zero (k_bin_fill leaves the counts it used at zero)
@@ -3945,6 +3950,8 @@ struct uf3_md : Batch {
     bool g_valid = false;                       // the pistons' g_close belongs to the current state
     // heat-current samples (uf3_md_run_flux, uf3_flux.h): the masses as given, the lists' workspace, the records of a run
     DevBuf mass, flux_ring;
+    // grade samples (uf3_md_run_grade, uf3_site_rows.h): the atoms' grades of one sample, the records of a run
+    DevBuf grade, grade_ring;
     ListWork fx;
     ~uf3_md() { fx.release(); }
 };
@@ -4069,8 +4076,21 @@ static int md_launch(uf3_md *md, MdStepArgs &A, bool langevin, int64_t record, i
 
 struct FluxArgs;
 static int lists_prepare(uf3_basis *b, const uf3_frames *fr, ListWork &W, const int32_t *d_z, const double *c1, const double *c2,
-                         const double *c3, const char *who, const char *what, FluxArgs &F);
+                         const double *c3, const char *who, const char *what, FluxArgs &F, bool model = true);
 static int flux_sample(uf3_ctx *c, ListWork &W, FluxArgs &F, bool headroom, const char *who);
+static int site_grade_sample(uf3_basis *b, ListWork &W, FluxArgs &F, bool headroom, const char *who, const double *d_w,
+                             double *d_grade, const int64_t *d_offsets, int n_out, double *d_fmax, int32_t *d_fargmax,
+                             double *d_pair, const std::function<int()> &after);
+
+// the grade sampler of a run (uf3_md_run_grade): W on the device, the period, the stop threshold (<= 0: none), the caller's
+// records [n_samples][n_frames][2] and where the number of completed steps goes
+struct MdGrade {
+    const double *d_w;
+    int64_t every;
+    double stop;
+    double *out;
+    int64_t *steps_done;
+};
 
 // one heat-current record of the closed state (velocities at integer time, the positions the forces belong to)
 static int md_flux_sample(uf3_md *md, FluxArgs &F, int64_t record) {
@@ -4080,13 +4100,48 @@ static int md_flux_sample(uf3_md *md, FluxArgs &F, int64_t record) {
 
 // flux_every > 0 (uf3_md_run_flux): the launch that closes a sampled step does not open the next one; the sample sits
 // between the two launches.  That is the split a run boundary makes anyway: the trajectory's bits do not change.
+// G (uf3_md_run_grade; never together with flux_every): grade samples at the same place.  A sample whose largest grade exceeds
+// G->stop ends the run there: the state is the closed one the sample saw, the records due so far are copied out.
 static int md_run(uf3_md *md, int64_t n_steps, double dt, double T, double gamma, uint64_t seed, int64_t every, bool stress,
-                  double *thermo, int64_t flux_every = 0, double *flux = nullptr) {
+                  double *thermo, int64_t flux_every = 0, double *flux = nullptr, const MdGrade *G = nullptr) {
     uf3_ctx *c = md->c;
     const int width = stress ? 14 : 2;
     const int64_t n_rec = every ? n_steps / every : 0;
     const int64_t n_flux = flux_every ? n_steps / flux_every : 0;
+    const int64_t n_grade = G && G->every ? n_steps / G->every : 0;
+    if (G) *G->steps_done = 0;
     FluxArgs F;
+    if (n_grade) {
+        HIPCHK(c, md->grade.ensure(8 * (size_t)md->natoms));
+        HIPCHK(c, md->grade_ring.ensure(16 * (size_t)n_grade * md->n_frames));
+        int rc = lists_prepare(md->b, &md->fr, md->fx, md->z.as<int32_t>(), nullptr, nullptr, nullptr, "uf3_md_run_grade", "batch", F, false);
+        if (rc) return rc;
+        F.pos = md->pos.as<double>();
+    }
+    // sample s (0-based) of the closed state; true in `stop` when it ends the run.  Its record is in the caller's array when
+    // this returns (the copy is queued in front of the sample's own synchronisation).
+    auto grade_sample = [&](int64_t s, bool &stop) {
+        const size_t rec = 2 * (size_t)md->n_frames;
+        double *d_rec = md->grade_ring.as<double>() + (size_t)s * rec, *h_rec = G->out + (size_t)s * rec;
+        int rc = site_grade_sample(md->b, md->fx, F, true, "uf3_md_run_grade", G->d_w, md->grade.as<double>(),
+                                   md->offsets_dev.as<int64_t>(), md->n_frames, nullptr, nullptr, d_rec, [&] {
+            HIPCHK(c, hipMemcpyAsync(h_rec, d_rec, 8 * rec, hipMemcpyDeviceToHost, c->stream));
+            return (int)UF3_OK;
+        });
+        if (rc) return rc;
+        stop = false;
+        if (G->stop > 0.0)
+            for (int f = 0; f < md->n_frames; f++) stop = stop || h_rec[2 * (size_t)f] > G->stop;
+        return (int)UF3_OK;
+    };
+    // the end of a run that a sample stopped after `done` steps: the thermo records due so far
+    auto stopped = [&](int64_t done) {
+        *G->steps_done = done;
+        const int64_t due = every ? done / every : 0;
+        if (due) HIPCHK(c, hipMemcpyAsync(thermo, md->ring.p, 8 * (size_t)due * md->n_frames * width, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return (int)UF3_OK;
+    };
     if (n_flux) {
         HIPCHK(c, md->flux_ring.ensure(48 * (size_t)n_flux * md->n_frames));
         int rc = lists_prepare(md->b, &md->fr, md->fx, md->z.as<int32_t>(), md->c1.data(), md->c2.data(), md->c3.data(), "uf3_md_run_flux", "batch", F);
@@ -4123,6 +4178,18 @@ static int md_run(uf3_md *md, int64_t n_steps, double dt, double T, double gamma
             if (rc) return rc;
             A.close = 0; A.open = 1;
             rc = md_launch(md, A, langevin, -1, width);
+        } else if (n_grade && k > 1 && (k - 1) % G->every == 0) {
+            A.open = 0;
+            rc = md_launch(md, A, langevin, rec ? (k - 1) / every - 1 : -1, width);
+            md->step = t0 + k - 1;              // (as above: a closed state, whatever happens below)
+            if (rc) return rc;
+            *G->steps_done = k - 1;
+            bool stop;
+            rc = grade_sample((k - 1) / G->every - 1, stop);
+            if (rc) return rc;
+            if (stop) return stopped(k - 1);
+            A.close = 0; A.open = 1;
+            rc = md_launch(md, A, langevin, -1, width);
         } else
             rc = md_launch(md, A, langevin, rec ? (k - 1) / every - 1 : -1, width);
         md->forces_valid = false;
@@ -4141,6 +4208,12 @@ static int md_run(uf3_md *md, int64_t n_steps, double dt, double T, double gamma
         rc = md_flux_sample(md, F, n_steps / flux_every - 1);
         if (rc) return rc;
     }
+    if (G) *G->steps_done = n_steps;
+    if (n_grade && n_steps % G->every == 0) {
+        bool stop;
+        rc = grade_sample(n_steps / G->every - 1, stop);
+        if (rc) return rc;
+    }
     if (n_flux) HIPCHK(c, hipMemcpyAsync(flux, md->flux_ring.p, 48 * (size_t)n_flux * md->n_frames, hipMemcpyDeviceToHost, c->stream));
     if (n_rec) HIPCHK(c, hipMemcpyAsync(thermo, md->ring.p, 8 * (size_t)n_rec * md->n_frames * width, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -4148,7 +4221,8 @@ static int md_run(uf3_md *md, int64_t n_steps, double dt, double T, double gamma
 }
 
 static int md_run_entry(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
-                        double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t flux_every, double *flux);
+                        double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t flux_every, double *flux,
+                        const MdGrade *G = nullptr);
 
 extern "C" int uf3_md_run(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
                           double skin, int64_t thermo_every, int with_stress, double *thermo) {
@@ -4160,8 +4234,27 @@ extern "C" int uf3_md_run_flux(uf3_md *md, int64_t n_steps, double dt_fs, double
     return md_run_entry(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, skin, thermo_every, with_stress, thermo, flux_every, flux);
 }
 
+extern "C" int uf3_md_run_grade(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
+                                double skin, int64_t thermo_every, int with_stress, double *thermo, const double *d_w,
+                                int64_t grade_every, double grade_stop, double *grades, int64_t *steps_done) {
+    if (!md) return fail(nullptr, UF3_EINVAL, "null md");
+    uf3_ctx *c = md->c;
+    if (!steps_done) return fail(c, UF3_EINVAL, "uf3_md_run_grade: null argument (steps_done)");
+    *steps_done = 0;
+    if (grade_every < 0) return fail(c, UF3_EINVAL, "uf3_md_run_grade: grade_every must be >= 0");
+    if (std::isnan(grade_stop)) return fail(c, UF3_EINVAL, "uf3_md_run_grade: grade_stop is not a number");
+    const int64_t n_grade = grade_every && n_steps > 0 ? n_steps / grade_every : 0;
+    if ((n_grade > 0) != (grades != nullptr))
+        return fail(c, UF3_EINVAL, n_grade ? "uf3_md_run_grade: grade records are due but the grades buffer is NULL"
+                                           : "uf3_md_run_grade: a grades buffer was given but no record is due");
+    if (n_grade && !d_w) return fail(c, UF3_EINVAL, "uf3_md_run_grade: null argument (w)");
+    const MdGrade G = {d_w, grade_every, grade_stop, grades, steps_done};
+    return md_run_entry(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, skin, thermo_every, with_stress, thermo, 0, nullptr, &G);
+}
+
 static int md_run_entry(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
-                        double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t flux_every, double *flux) {
+                        double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t flux_every, double *flux,
+                        const MdGrade *G) {
     if (!md) return fail(nullptr, UF3_EINVAL, "null md");
     uf3_ctx *c = md->c;
     if (flux_every < 0) return fail(c, UF3_EINVAL, "uf3_md_run_flux: flux_every must be >= 0");
@@ -4182,7 +4275,7 @@ static int md_run_entry(uf3_md *md, int64_t n_steps, double dt_fs, double temper
     if (n_steps == 0) return UF3_OK;
     HIPCHK(c, hipSetDevice(c->device));
     return with_run_skin(c, skin, [&] {
-        return md_run(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, thermo_every, with_stress != 0, thermo, flux_every, flux);
+        return md_run(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, thermo_every, with_stress != 0, thermo, flux_every, flux, G);
     });
 }
 
@@ -5210,14 +5303,15 @@ static int hess_geometry(uf3_ctx *c, const uf3_basis *b, const double *cells, co
     return UF3_OK;
 }
 
-// Fills F with everything but the positions and the outputs.  what: "frame" or "batch", for the species message.
+// Fills F with everything but the positions and the outputs.  what: "frame" or "batch", for the species message.  model = false
+// (site rows and grades: they take no coefficients): c1 / c2 / c3 are not looked at and F's stay null.
 static int lists_prepare(uf3_basis *b, const uf3_frames *fr, ListWork &W, const int32_t *d_z, const double *c1, const double *c2,
-                         const double *c3, const char *who, const char *what, FluxArgs &F) {
+                         const double *c3, const char *who, const char *what, FluxArgs &F, bool model) {
     uf3_ctx *c = b->ctx;
     const std::string me(who);
     if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, me + ": bad uf3_frames");
-    if (!d_z || !c1) return fail(c, UF3_EINVAL, me + ": null argument");
-    if ((b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, me + ": missing coefficients");
+    if (!d_z || (model && !c1)) return fail(c, UF3_EINVAL, me + ": null argument");
+    if (model && ((b->c2_len && !c2) || (b->c3_len && !c3))) return fail(c, UF3_EINVAL, me + ": missing coefficients");
     const int nf = fr->n_frames;
     if (fr->atom_offsets[0] != 0) return fail(c, UF3_EINVAL, me + ": atom_offsets[0] must be 0");
     for (int f = 0; f < nf; f++)
@@ -5241,13 +5335,13 @@ static int lists_prepare(uf3_basis *b, const uf3_frames *fr, ListWork &W, const 
     HIPCHK(c, W.cnt.ensure(sizeof(int) * (size_t)n));
     HIPCHK(c, W.flags.ensure(sizeof(int) * 4));
     // the model: the library's own copy (the evaluator's model cache is left alone)
-    const size_t n1 = (size_t)b->host.S, n2 = b->c2_len, n3 = b->c3_len;
+    const size_t n1 = model ? (size_t)b->host.S : 0, n2 = model ? b->c2_len : 0, n3 = model ? b->c3_len : 0;
     HIPCHK(c, W.coeff.ensure(8 * (n1 + n2 + n3 + 1)));
     double *dc = W.coeff.as<double>();
     // (pageable sources: each copy has left the host buffer when the call returns)
     HIPCHK(c, hipMemcpyAsync(W.frames.p, tab.data(), sizeof(FluxFrame) * (size_t)nf, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(W.offsets.p, fr->atom_offsets, 8 * (size_t)(nf + 1), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(dc, c1, 8 * n1, hipMemcpyHostToDevice, st));
+    if (n1) HIPCHK(c, hipMemcpyAsync(dc, c1, 8 * n1, hipMemcpyHostToDevice, st));
     if (n2) HIPCHK(c, hipMemcpyAsync(dc + n1, c2, 8 * n2, hipMemcpyHostToDevice, st));
     if (n3) HIPCHK(c, hipMemcpyAsync(dc + n1 + n2, c3, 8 * n3, hipMemcpyHostToDevice, st));
     int *d_flags = W.flags.as<int>();
@@ -5261,7 +5355,7 @@ static int lists_prepare(uf3_basis *b, const uf3_frames *fr, ListWork &W, const 
     F = FluxArgs();
     F.B = b->dev; F.frames = W.frames.as<FluxFrame>(); F.offsets = W.offsets.as<int64_t>(); F.n_frames = nf; F.n = n;
     F.spec = W.spec.as<int>(); F.cnt = W.cnt.as<int>(); F.flags = d_flags;
-    F.c1 = dc; F.c2 = dc + n1; F.c3 = dc + n1 + n2;
+    if (model) { F.c1 = dc; F.c2 = dc + n1; F.c3 = dc + n1 + n2; }
     return UF3_OK;
 }
 
@@ -5373,32 +5467,25 @@ extern "C" int uf3_hessian(uf3_basis *b, const uf3_frames *fr, const double *pos
 // (null: no current), F.mass, F.u (null: the workspace's), F.w (null: no virials), F.flux set by the caller.  headroom: keep
 // the capacity between calls (an MD run: sized at the first sample with room to move, grown when a list overflows); without
 // it the lists are sized exactly for these positions.
-static int flux_sample(uf3_ctx *c, ListWork &W, FluxArgs &F, bool headroom, const char *who) {
+// The lists of F.pos at the workspace's capacity, then launch() (the kernels that walk them; a walk that meets a cut list sets
+// flags[1]).  headroom: see flux_sample.  cap_limit / what: the walk's own limit on the capacity and its words for it.
+template <class Launch>
+static int lists_sample(uf3_ctx *c, ListWork &W, FluxArgs &F, bool headroom, const char *who, int cap_limit, const char *what,
+                        Launch launch) {
     hipStream_t st = c->stream;
     const std::string me(who);
-    const unsigned n = (unsigned)F.n;
-    HIPCHK(c, W.u.ensure(8 * (size_t)n));
-    HIPCHK(c, W.jp.ensure(24 * (size_t)n));
-    if (!F.u) F.u = W.u.as<double>();
-    F.jp = W.jp.as<double>();
     for (int attempt = 0; attempt < 3; attempt++) {
         if (!headroom || W.cap == 0) {
             int longest;
             int rc = lists_longest(c, F, who, longest);
             if (rc) return rc;
             W.cap = headroom ? longest + longest / 4 + 8 : longest;
-            // (k_flux_site_terms' index array, [cap] ints of LDS: its limit, not the lists')
-            if (W.cap > 12288) return fail(c, UF3_EINVAL, me + ": more than 12288 neighbours of one atom");
+            if (W.cap > cap_limit) { W.cap = 0; return fail(c, UF3_EINVAL, me + what); }
         }
         int rc = lists_fill(c, W, F);
         if (rc) return rc;
-        const size_t lds = sizeof(int) * (size_t)F.cap;
-        const bool want_w = F.w != nullptr, want_j = F.vel != nullptr;
-        if (want_w && want_j) hipLaunchKernelGGL((k_flux_site_terms<true, true>), dim3(n), dim3(64), lds, st, F);
-        else if (want_w) hipLaunchKernelGGL((k_flux_site_terms<true, false>), dim3(n), dim3(64), lds, st, F);
-        else if (want_j) hipLaunchKernelGGL((k_flux_site_terms<false, true>), dim3(n), dim3(64), lds, st, F);
-        else hipLaunchKernelGGL((k_flux_site_terms<false, false>), dim3(n), dim3(64), lds, st, F);
-        if (want_j) hipLaunchKernelGGL(k_flux_frame, dim3((unsigned)F.n_frames), dim3(UF3_MD_THREADS), 0, st, F);
+        rc = launch();
+        if (rc) return rc;
         HIPCHK(c, hipGetLastError());
         if (!headroom) return UF3_OK;           // (sized for these very positions: nothing can overflow)
         int flags[2] = {0, 0};
@@ -5410,6 +5497,26 @@ static int flux_sample(uf3_ctx *c, ListWork &W, FluxArgs &F, bool headroom, cons
         W.cap = 0;                              // a list was cut: size again from these positions and redo the sample
     }
     return fail(c, UF3_EINVAL, me + ": the neighbour lists keep overflowing");
+}
+
+static int flux_sample(uf3_ctx *c, ListWork &W, FluxArgs &F, bool headroom, const char *who) {
+    hipStream_t st = c->stream;
+    const unsigned n = (unsigned)F.n;
+    HIPCHK(c, W.u.ensure(8 * (size_t)n));
+    HIPCHK(c, W.jp.ensure(24 * (size_t)n));
+    if (!F.u) F.u = W.u.as<double>();
+    F.jp = W.jp.as<double>();
+    // (k_flux_site_terms' index array, [cap] ints of LDS: its limit, not the lists')
+    return lists_sample(c, W, F, headroom, who, 12288, ": more than 12288 neighbours of one atom", [&] {
+        const size_t lds = sizeof(int) * (size_t)F.cap;
+        const bool want_w = F.w != nullptr, want_j = F.vel != nullptr;
+        if (want_w && want_j) hipLaunchKernelGGL((k_flux_site_terms<true, true>), dim3(n), dim3(64), lds, st, F);
+        else if (want_w) hipLaunchKernelGGL((k_flux_site_terms<true, false>), dim3(n), dim3(64), lds, st, F);
+        else if (want_j) hipLaunchKernelGGL((k_flux_site_terms<false, true>), dim3(n), dim3(64), lds, st, F);
+        else hipLaunchKernelGGL((k_flux_site_terms<false, false>), dim3(n), dim3(64), lds, st, F);
+        if (want_j) hipLaunchKernelGGL(k_flux_frame, dim3((unsigned)F.n_frames), dim3(UF3_MD_THREADS), 0, st, F);
+        return (int)UF3_OK;
+    });
 }
 
 static int site_terms_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const double *d_vel, const int32_t *d_z,
@@ -5486,6 +5593,177 @@ extern "C" int uf3_heat_flux(uf3_basis *b, const uf3_frames *fr, const double *p
                              S.at<double>(s_u), nullptr, S.at<double>(s_f), "uf3_heat_flux");
     if (rc) return rc;
     HIPCHK(c, S.out({{s_f, flux}, {s_u, site_energies}}));
+    return UF3_OK;
+}
+
+// ------------------------------------------------------------------------------ site rows and grades (uf3_site_rows.h)
+#define SITE_ROWS_LDS 65536                        // k_site_rows: row + index array
+#define SITE_CHUNK_BYTES ((size_t)64 << 20)        // the fall-back's chunk of rows
+
+// k_site_rows on centres [m0, m1) of the lists in F
+static void site_rows_launch(uf3_ctx *c, const FluxArgs &F, int n_feat, long long m0, long long m1, double *d_rows, int64_t ld) {
+    SiteArgs A = {};
+    A.F = F; A.m0 = m0; A.m1 = m1; A.n_feat = n_feat; A.rows = d_rows; A.ld = ld;
+    const size_t lds = 8 * (size_t)site_row_stride(n_feat) + 4 * (size_t)F.cap;
+    hipLaunchKernelGGL(k_site_rows, dim3((unsigned)(m1 - m0)), dim3(64), lds, c->stream, A);
+}
+static int site_rows_cap_limit(int n_feat) { return (SITE_ROWS_LDS - 8 * site_row_stride(n_feat)) / 4; }
+
+static int site_rows_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, double *d_rows, int64_t ld) {
+    uf3_ctx *c = b->ctx;
+    const int n_feat = b->host.F;
+    if (!d_pos || !d_rows) return fail(c, UF3_EINVAL, "uf3_site_rows: null argument");
+    if (ld < n_feat) return fail(c, UF3_EINVAL, "uf3_site_rows: ld must be >= n_feat");
+    if (site_rows_cap_limit(n_feat) < 1) return fail(c, UF3_EINVAL, "uf3_site_rows: a row of this basis does not fit in LDS");
+    FluxArgs F;
+    int rc = lists_prepare(b, fr, c->fx, d_z, nullptr, nullptr, nullptr, "uf3_site_rows", "batch", F, false);
+    if (rc) return rc;
+    F.pos = d_pos;
+    return lists_sample(c, c->fx, F, false, "uf3_site_rows", site_rows_cap_limit(n_feat),
+                        ": an atom has more neighbours than fit in LDS beside its row", [&] {
+        site_rows_launch(c, F, n_feat, 0, F.n, d_rows, ld);
+        return (int)UF3_OK;
+    });
+}
+
+extern "C" int uf3_site_rows_dev(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, double *d_rows, int64_t ld) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    return site_rows_impl(b, fr, d_pos, d_z, d_rows, ld);
+}
+
+extern "C" int uf3_site_rows(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, double *rows, int64_t ld) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    uf3_ctx *c = b->ctx;
+    if (!flux_frames_ok(fr)) return fail(c, UF3_EINVAL, "uf3_site_rows: bad uf3_frames");
+    if (!pos || !z || !rows) return fail(c, UF3_EINVAL, "uf3_site_rows: null argument");
+    if (ld < b->host.F) return fail(c, UF3_EINVAL, "uf3_site_rows: ld must be >= n_feat");
+    const size_t n = (size_t)fr->atom_offsets[fr->n_frames], F = (size_t)b->host.F;
+    HIPCHK(c, hipSetDevice(c->device));
+    Stage S(c->fx.io, c->stream);
+    const int s_pos = S.add(24 * n), s_z = S.add(4 * n), s_r = S.add(8 * n * F);
+    HIPCHK(c, S.alloc());
+    HIPCHK(c, S.in({{s_pos, pos}, {s_z, z}}));
+    int rc = site_rows_impl(b, fr, S.at<double>(s_pos), S.at<int32_t>(s_z), S.at<double>(s_r), (int64_t)F);
+    if (rc) return rc;
+    // (the caller's padding columns F .. ld are not written: a strided copy of the F used ones)
+    HIPCHK(c, hipMemcpy2DAsync(rows, 8 * (size_t)ld, S.at<double>(s_r), 8 * F, 8 * F, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->fx.io.cap > ((size_t)1 << 30)) c->fx.io.release();
+    return UF3_OK;
+}
+
+// The grades of the lists' batch: F from lists_prepare with F.pos set.  d_offsets: the frames the maxima are taken over
+// ([n_out + 1] on the device); the other outputs as k_site_frame_max's.  Fused (k_site_grade) where the tile and the four index
+// arrays fit SG_LDS_BUDGET at the lists' capacity; otherwise chunks of k_site_rows into the context's scratch + k_leverage.
+// after(): queued behind the sample's kernels and in front of the sample's one synchronisation (headroom), or nullptr.
+static int site_grade_sample(uf3_basis *b, ListWork &W, FluxArgs &F, bool headroom, const char *who, const double *d_w,
+                             double *d_grade, const int64_t *d_offsets, int n_out, double *d_fmax, int32_t *d_fargmax,
+                             double *d_pair, const std::function<int()> &after) {
+    uf3_ctx *c = b->ctx;
+    const int n_feat = b->host.F;
+    int rc = ensure_frag(c);
+    if (rc) return rc;
+    if (!c->site_grade_lds_set) {
+        HIPCHK(c, hipFuncSetAttribute((const void *)k_site_grade, hipFuncAttributeMaxDynamicSharedMemorySize, SG_LDS_BUDGET));
+        c->site_grade_lds_set = true;
+    }
+    if (site_rows_cap_limit(n_feat) < 1) return fail(c, UF3_EINVAL, std::string(who) + ": a row of this basis does not fit in LDS");
+    hipStream_t st = c->stream;
+    return lists_sample(c, W, F, headroom, who, site_rows_cap_limit(n_feat), ": an atom has more neighbours than fit in LDS beside its row", [&] {
+        const size_t lds = site_grade_lds(n_feat, F.cap);
+        const bool fused = lds <= SG_LDS_BUDGET;
+        if (fused) {
+            SiteArgs A = {};
+            A.F = F; A.m0 = 0; A.m1 = F.n; A.n_feat = n_feat; A.w = d_w; A.frag = c->frag.as<int>(); A.grade = d_grade;
+            hipLaunchKernelGGL(k_site_grade, dim3((unsigned)((F.n + SG_TILE - 1) / SG_TILE)), dim3(256), lds, st, A);
+        } else {
+            // whole leverage tiles per chunk; the scratch does not grow with the batch
+            long long chunk = (long long)(SITE_CHUNK_BYTES / (8 * (size_t)n_feat)) / LV_ROWS * LV_ROWS;
+            chunk = std::max<long long>(LV_ROWS, std::min<long long>(chunk, (F.n + LV_ROWS - 1) / LV_ROWS * LV_ROWS));
+            HIPCHK(c, c->site_rows_ws.ensure(8 * (size_t)chunk * n_feat));
+            for (long long m0 = 0; m0 < F.n; m0 += chunk) {
+                const long long m1 = std::min<long long>(F.n, m0 + chunk);
+                site_rows_launch(c, F, n_feat, m0, m1, c->site_rows_ws.as<double>(), n_feat);
+                int rl = uf3_leverage_dev(c, c->site_rows_ws.as<double>(), m1 - m0, n_feat, n_feat, d_w, 1, d_grade + m0);
+                if (rl) return rl;
+            }
+        }
+        if (c->env_debug_lds)
+            fprintf(stderr, "uf3: site grade kernel=%s atoms=%lld feat=%d cap=%d tile=%d lds=%zu B budget=%d B\n",
+                    fused ? "k_site_grade" : "k_site_rows+k_leverage", (long long)F.n, n_feat, F.cap, SG_TILE, lds, (int)SG_LDS_BUDGET);
+        if (d_fmax || d_fargmax || d_pair)
+            hipLaunchKernelGGL(k_site_frame_max, dim3((unsigned)n_out), dim3(256), 0, st, (const double *)d_grade, d_offsets, d_fmax,
+                               d_fargmax, d_pair);
+        return after ? after() : (int)UF3_OK;
+    });
+}
+
+// The caller's frames may hold empty ones (0 and -1 for them): the lists are built for the others.
+static int site_grade_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, const double *d_w,
+                           double *d_grade, double *d_fmax, int32_t *d_fargmax) {
+    uf3_ctx *c = b->ctx;
+    const char *who = "uf3_site_grade";
+    if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, "uf3_site_grade: bad uf3_frames");
+    if (!d_w) return fail(c, UF3_EINVAL, "uf3_site_grade: null argument (w)");
+    const int nf = fr->n_frames;
+    if (fr->atom_offsets[0] != 0) return fail(c, UF3_EINVAL, "uf3_site_grade: atom_offsets[0] must be 0");
+    for (int f = 0; f < nf; f++)
+        if (fr->atom_offsets[f + 1] < fr->atom_offsets[f]) return fail(c, UF3_EINVAL, "uf3_site_grade: atom_offsets must not decrease");
+    const int64_t n = fr->atom_offsets[nf];
+    if (n && (!d_pos || !d_z || !d_grade)) return fail(c, UF3_EINVAL, "uf3_site_grade: null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->site_off.ensure(8 * (size_t)(nf + 1)));
+    HIPCHK(c, hipMemcpyAsync(c->site_off.p, fr->atom_offsets, 8 * (size_t)(nf + 1), hipMemcpyHostToDevice, c->stream));
+    if (n == 0) {
+        if (d_fmax || d_fargmax)
+            hipLaunchKernelGGL(k_site_frame_max, dim3((unsigned)nf), dim3(256), 0, c->stream, (const double *)nullptr,
+                               (const int64_t *)c->site_off.as<int64_t>(), d_fmax, d_fargmax, (double *)nullptr);
+        HIPCHK(c, hipStreamSynchronize(c->stream));        // (the offsets' pageable source)
+        return UF3_OK;
+    }
+    std::vector<int64_t> off(1, 0);
+    std::vector<double> cells;
+    std::vector<uint8_t> pbc;
+    for (int f = 0; f < nf; f++) {
+        if (fr->atom_offsets[f + 1] == fr->atom_offsets[f]) continue;
+        off.push_back(fr->atom_offsets[f + 1]);
+        cells.insert(cells.end(), fr->cells + 9 * (size_t)f, fr->cells + 9 * (size_t)f + 9);
+        pbc.insert(pbc.end(), fr->pbc + 3 * (size_t)f, fr->pbc + 3 * (size_t)f + 3);
+    }
+    uf3_frames live = *fr;
+    live.n_frames = (int)off.size() - 1; live.atom_offsets = off.data(); live.cells = cells.data(); live.pbc = pbc.data();
+    FluxArgs F;
+    int rc = lists_prepare(b, &live, c->fx, d_z, nullptr, nullptr, nullptr, who, "batch", F, false);   // (synchronises: the offsets have left)
+    if (rc) return rc;
+    F.pos = d_pos;
+    return site_grade_sample(b, c->fx, F, false, who, d_w, d_grade, c->site_off.as<int64_t>(), nf, d_fmax, d_fargmax, nullptr, nullptr);
+}
+
+extern "C" int uf3_site_grade_dev(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, const double *d_w,
+                                  double *d_grade, double *d_frame_max, int32_t *d_frame_argmax) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    return site_grade_impl(b, fr, d_pos, d_z, d_w, d_grade, d_frame_max, d_frame_argmax);
+}
+
+extern "C" int uf3_site_grade(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *w, double *grade,
+                              double *frame_max, int32_t *frame_argmax) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
+    uf3_ctx *c = b->ctx;
+    if (!fr || fr->n_frames < 1 || !fr->atom_offsets || fr->atom_offsets[fr->n_frames] < 0 || fr->atom_offsets[fr->n_frames] > (int64_t)1 << 30)
+        return fail(c, UF3_EINVAL, "uf3_site_grade: bad uf3_frames");
+    if (!w) return fail(c, UF3_EINVAL, "uf3_site_grade: null argument (w)");
+    const size_t n = (size_t)fr->atom_offsets[fr->n_frames], nf = (size_t)fr->n_frames, F = (size_t)b->host.F;
+    if (n && (!pos || !z || !grade)) return fail(c, UF3_EINVAL, "uf3_site_grade: null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    Stage S(c->fx.io, c->stream);
+    const int s_pos = S.add(24 * n), s_z = S.add(4 * n), s_w = S.add(8 * F * F), s_g = S.add(8 * n), s_m = S.add(8 * nf, frame_max != nullptr),
+              s_a = S.add(4 * nf, frame_argmax != nullptr);
+    HIPCHK(c, S.alloc());
+    HIPCHK(c, S.in({{s_pos, pos}, {s_z, z}, {s_w, w}}));
+    int rc = site_grade_impl(b, fr, S.at<double>(s_pos), S.at<int32_t>(s_z), S.at<double>(s_w), S.at<double>(s_g), S.at<double>(s_m),
+                             S.at<int32_t>(s_a));
+    if (rc) return rc;
+    HIPCHK(c, S.out({{s_g, grade}, {s_m, frame_max}, {s_a, frame_argmax}}));
     return UF3_OK;
 }
 

@@ -252,10 +252,8 @@ class UFCalculator(_Base):
         """ASE's per-atom energies [N] (eV): the site energies U_i of ``site_terms``; their sum is ``get_potential_energy``."""
         return self.site_terms([atoms], virials=False)[0][0]
 
-    def get_leverages(self, atoms_or_list, forces=True, max_atoms_per_chunk=320000):
-        """Leverages of one frame or a list of frames against the system this calculator's model was fitted on
-        (``pipeline.DeviceLeverage``): ``dict(energy, force, offsets)``; for a single ``Atoms`` ``energy`` is a scalar and
-        ``force`` has shape [N].  A model without a posterior (read from a file, no ``load_posterior``) raises ``ValueError``."""
+    def _device_leverage(self, max_atoms_per_chunk):
+        """The calculator's ``pipeline.DeviceLeverage``, made again when the chunk limit or the model's posterior changed."""
         from uf3_amd import pipeline
         from uf3_amd.representation import process
         lev = getattr(self, "_leverage", None)
@@ -263,10 +261,29 @@ class UFCalculator(_Base):
         if lev is None or lev.max_atoms != int(max_atoms_per_chunk) or lev._w_host is not w:
             fz = process.BasisFeaturizer(self.bspline_config, device=self.device)
             lev = self._leverage = pipeline.DeviceLeverage(self.model, fz, max_atoms_per_chunk=max_atoms_per_chunk)
+        return lev
+
+    def get_leverages(self, atoms_or_list, forces=True, max_atoms_per_chunk=320000):
+        """Leverages of one frame or a list of frames against the system this calculator's model was fitted on
+        (``pipeline.DeviceLeverage``): ``dict(energy, force, offsets)``; for a single ``Atoms`` ``energy`` is a scalar and
+        ``force`` has shape [N].  A model without a posterior (read from a file, no ``load_posterior``) raises ``ValueError``."""
+        lev = self._device_leverage(max_atoms_per_chunk)
         single = not isinstance(atoms_or_list, (list, tuple))
         out = lev.frames([atoms_or_list] if single else list(atoms_or_list), forces=forces)
         if single:
             out["energy"] = float(out["energy"][0])
+        return out
+
+    def get_site_grades(self, atoms_or_list, max_atoms_per_chunk=320000):
+        """Per-atom extrapolation grades of one frame or a list of frames against the system this calculator's model was
+        fitted on (``pipeline.DeviceLeverage.sites``): ``dict(grade, frame_max, frame_argmax, offsets)``; for a single
+        ``Atoms`` ``frame_max`` and ``frame_argmax`` are scalars.  The grades describe the wrapped frame, as ``site_terms``
+        does.  A model without a posterior raises ``ValueError``."""
+        lev = self._device_leverage(max_atoms_per_chunk)
+        single = not isinstance(atoms_or_list, (list, tuple))
+        out = lev.sites([atoms_or_list] if single else list(atoms_or_list))
+        if single:
+            out["frame_max"], out["frame_argmax"] = float(out["frame_max"][0]), int(out["frame_argmax"][0])
         return out
 
     def get_stresses(self, atoms=None):

@@ -330,20 +330,36 @@ class MolecularDynamics(Driver):
         s = self.seed if seed is None else check_int(WHO, "seed", seed, 0, (1 << 64) - 1)
         self.ctx.check(self.ctx.lib.uf3_md_init_velocities(self._live(), t, s, int(bool(exact))))
 
-    def run(self, n_steps, thermo_every=0, stress=False, flux_every=0):
+    def run(self, n_steps, thermo_every=0, stress=False, flux_every=0, grade_every=0, grade_stop=None):
         """``n_steps`` steps (Langevin when ``friction_per_fs`` > 0, else NVE; at a pressure NPT / NPH).  Returns the thermo
         records of every ``thermo_every``-th step (see ``thermo_records``; empty arrays when ``thermo_every`` is 0).  At a
         pressure the records always carry stress and pressure (of that step's volume), volume, cell_scale and conserved.
         ``flux_every`` > 0: the heat current of every frame after every ``flux_every``-th step, sampled on the device from the
         closed state (``uf3_md_run_flux``): ``heat_flux_convective``, ``heat_flux_potential`` and their sum ``heat_flux``
         [n_records, n_frames, 3] in eV A / fs, and ``flux_step``.  The trajectory and the thermo records do not depend on it.
-        Not at a pressure: that raises ``UF3Error`` (UF3_EINVAL)."""
+        Not at a pressure: that raises ``UF3Error`` (UF3_EINVAL).
+        ``grade_every`` > 0: after every ``grade_every``-th step the extrapolation grades of the closed state
+        (``uf3_md_run_grade``; ``UFCalculator.get_site_grades`` for what they are, of the WRAPPED frame): ``grade``
+        [n_samples, n_frames] the largest site grade of each frame, ``grade_atom`` the frame-local index of its atom,
+        ``grade_step``, and ``steps_done``.  ``grade_stop`` > 0: the run ends after the first sample in which any frame's
+        ``grade`` exceeds it -- the whole batch stops; ``steps_done`` steps were made, every record is cut to them, the state is
+        that of ``run(steps_done)`` and a later ``run`` goes on from it.  The trajectory and the thermo records do not depend on
+        the sampling.  W is the calculator's ``model.whitening()`` (``ValueError`` without a posterior), uploaded once per
+        object.  Not at a pressure and not together with ``flux_every``: ``UF3Error`` (UF3_EINVAL)."""
         n_steps = check_int(WHO, "n_steps", n_steps)
         every = check_int(WHO, "thermo_every", thermo_every)
         flux_every = check_int(WHO, "flux_every", flux_every)
+        grade_every = check_int(WHO, "grade_every", grade_every)
+        grade_stop = 0.0 if grade_stop is None else check_real(WHO, "grade_stop", grade_stop, lo=None)
         if flux_every and getattr(self, "pressure_eV_A3", None) is not None:
             raise _lib.UF3Error(1, "uf3_md_run_flux: the heat current is sampled at constant volume only (flux_every with "
                                    "pressure_eV_A3)")
+        if grade_every and getattr(self, "pressure_eV_A3", None) is not None:
+            raise _lib.UF3Error(1, "uf3_md_run_grade: grades are sampled at constant volume only (grade_every with "
+                                   "pressure_eV_A3)")
+        if grade_every and flux_every:
+            raise _lib.UF3Error(1, "uf3_md_run_grade: grade_every and flux_every do not go into one run")
+        w_host = self.calculator.model.whitening() if grade_every else None    # (the ValueError, before anything touches the device)
         dt = check_real(WHO, "timestep_fs", self.timestep_fs, strict=True)
         temp = check_real(WHO, "temperature_K", self.temperature_K)
         gamma = check_real(WHO, "friction_per_fs", self.friction_per_fs)
@@ -375,6 +391,33 @@ class MolecularDynamics(Driver):
             out["heat_flux"] = fl[:, :, 0] + fl[:, :, 1]
             out["flux_step"] = first + flux_every * np.arange(1, n_flux + 1, dtype=np.int64)
             return out
+        if grade_every:
+            n_grade = n_steps // grade_every
+            gr = np.zeros((n_grade, self._batch.n_frames, 2))
+            done = C.c_int64(0)
+            self.ctx.check(self.ctx.lib.uf3_md_run_grade(handle, n_steps, dt, temp, gamma, seed, skin, every, int(bool(stress)),
+                                                         _lib._p(raw) if n_rec else None, self._grade_w(w_host), grade_every,
+                                                         grade_stop, _lib._p(gr) if n_grade else None, C.byref(done)))
+            done = done.value
+            out = thermo_records(raw[:done // every if every else 0], self.n_atoms, self.volumes, first, max(every, 1), stress)
+            gr = gr[:done // grade_every]
+            out["grade"] = gr[:, :, 0].copy()
+            out["grade_atom"] = gr[:, :, 1].astype(np.int64)
+            out["grade_step"] = first + grade_every * np.arange(1, len(gr) + 1, dtype=np.int64)
+            out["steps_done"] = done
+            return out
         self.ctx.check(self.ctx.lib.uf3_md_run(handle, n_steps, dt, temp, gamma, seed, skin, every, int(bool(stress)),
                                                _lib._p(raw) if n_rec else None))
         return thermo_records(raw, self.n_atoms, self.volumes, first, max(every, 1), stress)
+
+    def _grade_w(self, w_host):
+        """Device address of the whitening matrix: uploaded once per object (again after a refit made a new one)."""
+        if getattr(self, "_grade_w_host", None) is not w_host:
+            import torch
+            n_feat = _lib.device_basis(self.calculator.bspline_config, self.ctx).n_feat
+            if w_host.shape != (n_feat, n_feat):
+                raise ValueError("MolecularDynamics: the model's whitening matrix is not of the calculator's basis")
+            self._grade_w_dev = torch.from_numpy(np.ascontiguousarray(w_host, dtype=np.float64)).to(torch.device("cuda", self.ctx.device))
+            torch.cuda.synchronize(self._grade_w_dev.device)
+            self._grade_w_host = w_host
+        return C.c_void_p(self._grade_w_dev.data_ptr())

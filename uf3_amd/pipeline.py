@@ -328,6 +328,47 @@ class DeviceLeverage:
                 pass
             return self._frames(frames, bool(forces))
 
+    def sites(self, frames):
+        """Extrapolation grades of every atom, ``gamma_i = b_i^T (G + R^T R)^-1 b_i`` with ``b_i`` the atom's site row
+        (``uf3_site_grade_dev``: the rows are built in LDS and never reach memory):
+        ``dict(grade=[sum N], frame_max=[n_frames], frame_argmax=[n_frames], offsets=[n_frames + 1])`` -- the largest grade of
+        each frame and the frame-local index of its atom (lowest on ties; 0 and -1 for a frame without atoms).  Up to the noise
+        scale ``grade`` is the predictive variance of the atom's site energy.  The grades describe the wrapped frame, as
+        ``UFCalculator.site_terms`` does.  Frames are batched under the atom limit."""
+        torch = self.torch
+        frames = list(frames)
+        counts = [len(a) for a in frames]
+        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        grade = np.empty(int(offsets[-1]))
+        fmax, farg = np.zeros(len(frames)), -np.ones(len(frames), dtype=np.int32)
+        live = [k for k, n in enumerate(counts) if n]         # (a frame without atoms has no cell worth passing on)
+        prev = self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
+        try:
+            start = 0
+            while start < len(live):
+                stop, n_at = start, 0
+                while stop < len(live) and (stop == start or n_at + counts[live[stop]] <= self.max_atoms):
+                    n_at += counts[live[stop]]
+                    stop += 1
+                idx = live[start:stop]
+                batch = _lib.FrameBatch([frames[k] for k in idx])
+                d_pos = torch.from_numpy(batch.pos).to(self.dev)
+                d_z = torch.from_numpy(batch.z).to(self.dev)
+                d_g = torch.empty(n_at + len(idx), dtype=torch.float64, device=self.dev)
+                d_a = torch.empty(len(idx), dtype=torch.int32, device=self.dev)
+                self.ctx.check(self.ctx.lib.uf3_site_grade_dev(self.db.handle, C.byref(batch.struct), C.c_void_p(d_pos.data_ptr()),
+                                                               C.c_void_p(d_z.data_ptr()), C.c_void_p(self._w.data_ptr()),
+                                                               C.c_void_p(d_g.data_ptr()), C.c_void_p(d_g[n_at:].data_ptr()),
+                                                               C.c_void_p(d_a.data_ptr())))
+                g = d_g.cpu().numpy()
+                fmax[idx], farg[idx] = g[n_at:], d_a.cpu().numpy()
+                for j, k in enumerate(idx):
+                    grade[offsets[k]:offsets[k + 1]] = g[batch.offsets[j]:batch.offsets[j + 1]]
+                start = stop
+        finally:
+            self.ctx.restore_stream(prev)
+        return dict(grade=grade, frame_max=fmax, frame_argmax=farg, offsets=offsets)
+
 
 def _fit_counts(ctx, fit):
     n, e, f = C.c_int64(), C.c_double(), C.c_double()

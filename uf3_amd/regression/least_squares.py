@@ -384,6 +384,14 @@ class WeightedLinearModel(BasicLinearModel):
         """
         return leverage_device(x, self.whitening(), group=group, device=self.device)
 
+    def site_leverage(self, site_rows):
+        """
+        Extrapolation grades ``b_i^T (G + R^T R)^-1 b_i`` of host site rows [N, F] (``BasisFeaturizer.site_rows``):
+        ``leverage(site_rows, group=1)``, up to the noise scale the predictive variance of each atom's site energy.  The
+        fused device route that builds no rows is ``pipeline.DeviceLeverage.sites``.
+        """
+        return self.leverage(site_rows, group=1)
+
     def gram_pieces(self, x_e, y_e, x_f=None, y_f=None, x_v=None, y_v=None):
         """Additive pieces of one shard: Gram/ordinate of the frozen system + target moments.  ``x_v`` [n, 6, F] (or
         [6 n, F]): virial rows ALREADY divided by the frames' atom counts, ``y_v`` [n, 6]: ``virial_targets``."""

@@ -123,6 +123,20 @@ class BasisFeaturizer:
                                                _lib._p(x_e), None, _lib._p(x_v)))
         return (x_e, x_v) if energy else x_v
 
+    def site_rows(self, atoms_list):
+        """
+        Site rows of a batch of frames: ``(rows [sum N, F], offsets [n_frames + 1])`` with ``rows[i] @ coefficients`` the
+        site energy ``U_i`` of ``UFCalculator.site_terms`` for every coefficient vector (``uf3_site_rows``); a frame's rows
+        sum to its energy row.  The rows describe the wrapped frame, as ``site_terms`` does.
+        """
+        import ctypes as C
+        ctx, db = self._dev()
+        batch = _lib.FrameBatch(list(atoms_list))
+        rows = np.empty((batch.n_atoms, db.n_feat))
+        ctx.check(ctx.lib.uf3_site_rows(db.handle, C.byref(batch.struct), _lib._p(batch.pos), _lib._p(batch.z), _lib._p(rows),
+                                        db.n_feat))
+        return rows, np.asarray(batch.offsets, dtype=np.int64).copy()
+
     def featurize_device(self, frames_struct, d_pos, d_z, d_x_e=None, d_x_f=None, ld=None, d_x_v=None):
         """Device-resident entry: raw HBM pointers (ints), asynchronous on the context stream.  ``ld``: doubles between
         consecutive force rows (default: the number of features, dense rows; a multiple of 16 puts every row on a cache
