@@ -310,10 +310,18 @@ __device__ __forceinline__ double norm3_rn(double dx, double dy, double dz) {
     return sqrt(norm3_sq_rn(dx, dy, dz));
 }
 
-// |d| for the THIRD leg of a triplet (r_jk): not part of any neighbour-index decision -- it selects knot intervals, where a
-// cubic B-spline is continuous, and is compared with the leg's ends, where the basis functions vanish -- so the last bit does
-// not matter and the root comes from the hardware estimate + one Newton step + one correction (8 instructions; the IEEE
-// library root with its scaling for subnormal arguments is 20, and the walk takes one per triplet role).
+// |d| for the THIRD leg of a triplet (r_jk): not part of any neighbour-index decision.  It selects knot intervals, where a cubic
+// B-spline is continuous to the second derivative, and is compared with the leg's ends.  At the last knot, and at the first one
+// under a leading trim of 3, the kept basis functions vanish and the last bit does not matter.  With leading trim 0 it does: the
+// first function is 1 just above t0, so rn > t0 decides a whole term, and a root that is exactly representable must come out
+// exact.  Relied on, and measured rather than proven: s is the correctly rounded radicand wherever norm3_rn's is (one non-zero
+// component, or squares that add without rounding), and the residual step g + (s - g * g) * h rounds the root to nearest unless
+// it lies within a few 2^-50 ulp of the midpoint of two doubles, which a representable root of a representable radicand does not.
+// tests/test_gpu_on_knots.py holds every kernel that calls this to distances on, and 1 and 2 x 2^-42 A either side of, every
+// knot and leg end (with the result taken one ulp high, every test of a basis with leading trim 0 fails there).  Where r_jk is
+// no double the fused radicand may put a distance within rounding of t0 on the other side than cdist's
+// sum: accepted, not tested.  The root comes from the hardware estimate + one Newton step + one correction (8 instructions; the
+// IEEE library root with its scaling for subnormal arguments is 20, and the walk takes one per triplet role).
 __device__ __forceinline__ double norm3_leg(double dx, double dy, double dz) {
     const double s = fma(dz, dz, fma(dy, dy, dx * dx));
     const double y = __builtin_amdgcn_rsq(s);
