@@ -50,6 +50,7 @@ class Band:
         self._forces = None
         self.margins = []            # per evaluation: the smallest margin of the comparisons of the bands that ran
         self.max_dr = 0.0            # the largest |dr| over a band's DOF in any step (tests: <= maxstep)
+        self.power = []              # g.v / (|g| |v|) of every power test made: how far from 0 the branch was decided
 
     def _span(self, b):
         f0, f1 = self.bands[b], self.bands[b + 1]
@@ -114,6 +115,8 @@ class Band:
         v = self.v[ilo:ihi]
         dt = dt0 if self.first[b] else self.dt[b]
         if not self.first[b]:
+            scale = np.sqrt(np.vdot(g, g) * np.vdot(v, v))
+            self.power.append(np.vdot(g, v) / scale if scale > 0 else 0.0)
             if np.vdot(g, v) > 0:
                 v = (1 - self.alpha[b]) * v + self.alpha[b] * np.sqrt(np.vdot(v, v)) / np.sqrt(np.vdot(g, g)) * g
                 if self.n_pos[b] > N_MIN:

@@ -47,6 +47,7 @@ class Fire:
         self._forces = None
         self.max_dr = 0.0            # the largest |dr| over a frame's DOF in any step (tests: <= maxstep)
         self.first_dt = []           # (frame, dt of its first move)
+        self.power = []              # P / (|g| |v|) of every power test made: how far from 0 the branch was decided
 
     def _eval(self):
         self._forces = self.evaluate(self.x, self.cells)
@@ -84,6 +85,8 @@ class Fire:
             self.first_dt.append((f, dt))
         else:
             P = np.vdot(g, v) + np.vdot(G, vc)
+            scale = np.sqrt((np.vdot(g, g) + np.vdot(G, G)) * (np.vdot(v, v) + np.vdot(vc, vc)))
+            self.power.append(P / scale if scale > 0 else 0.0)
             if P > 0:
                 vn = np.sqrt(np.vdot(v, v) + np.vdot(vc, vc))
                 gn = np.sqrt(np.vdot(g, g) + np.vdot(G, G))
