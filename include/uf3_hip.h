@@ -718,7 +718,8 @@ int uf3_heat_flux_dev(uf3_basis *basis, const uf3_frames *frames, const double *
  *              the diagonal, frozen columns as zero rows and columns): the predictive variance of the site energy up to the
  *              noise scale.
  *   uf3_site_rows    rows [N][ld], ld >= n_feat; columns n_feat .. ld are not written.  Takes no coefficients.  The grades
- *                    describe the WRAPPED frame, as uf3_site_terms does: an atom outside its cell counts as its image inside.
+ *                    describe the WRAPPED frame, as uf3_site_terms does: an atom outside its cell counts as its image inside,
+ *                    also in the symmetry-1 tie-break (the wrapped image's place in the reference supercell decides the column).
  *   uf3_site_grade   grade [N]; frame_max / frame_argmax [n_frames] (either may be NULL): the largest grade of each frame and
  *                    the frame-local index of its atom, the lowest index on ties, from a fixed reduction tree.  Here, and
  *                    here only, a frame may be empty: it gives 0 and -1.  The grades describe the WRAPPED frame, as

@@ -14,7 +14,11 @@
 #include "uf3_device.h"
 
 // one neighbour image of an atom: vector from the atom to the image, its length, the parent atom, the packed integer image
-// shift (relative to the raw positions) and flags (bit 0: inside the pair range of the two species, bit 1: 3-body neighbour)
+// shift and flags (bit 0: inside the pair range of the two species, bit 1: 3-body neighbour).  The shift is that of the WRAPPED
+// frame: with both atoms folded into the cell (hess_home_cell), the image of j that this entry is lies at wrapped(j) + shift .
+// cell as seen from wrapped(i).  On a frame whose atoms lie inside their cell that is the shift applied to the positions as
+// given; an atom outside its cell counts as its image inside, also where the shift decides a number (supercell_before on a
+// symmetry-1 trio).  Reverse entries carry the negated shift either way (k_hessian's lookup).
 struct __attribute__((aligned(16))) HessNbr {
     double dx, dy, dz, r;
     int j, shp, spec, flags;
@@ -66,6 +70,18 @@ __device__ __forceinline__ void bspline4_d2(const KnotRec &k, double x, double *
     dd[0] = -a2; dd[1] = a2 - b2; dd[2] = b2 - c2; dd[3] = c2;
 }
 
+// The cell an atom lies in, per periodic axis: floor of its fractional coordinate.  An atom inside its cell or within
+// HESS_FACE_EPS (fractional) of one of its faces stays where it is given, as the reference takes it: a coordinate that is 0 or 1
+// up to rounding (an atom on a face of a skewed cell) must not hop to the neighbouring cell.
+#define HESS_FACE_EPS 1e-9
+__device__ __forceinline__ void hess_home_cell(const HessArgs &A, double x, double y, double z, int *w) {
+    for (int k = 0; k < 3; k++) {
+        const double f = x * A.inv[k] + y * A.inv[3 + k] + z * A.inv[6 + k];
+        const bool stays = !A.per[k] || (f >= -HESS_FACE_EPS && f < 1.0 + HESS_FACE_EPS);
+        w[k] = stays ? 0 : (int)fmin(fmax(floor(f), -1.0e6), 1.0e6);
+    }
+}
+
 // ---- neighbour lists: one wave per atom, lanes over the other atoms, every image in reach of each -------------------------
 // WRITE = false: counts only.  Entries in (atom, image, lane) order: the same lists on every call.  CHECK: flag image shifts
 // beyond pack3's range.  A device function of one frame's arguments; its one kernel is k_flux_lists (uf3_flux.h), which puts a
@@ -75,6 +91,8 @@ __device__ __forceinline__ void hess_lists_atom(const HessArgs &A, int i, int la
     const BasisDev *B = A.B;
     const double xi = A.pos[3 * (size_t)i], yi = A.pos[3 * (size_t)i + 1], zi = A.pos[3 * (size_t)i + 2];
     const int si = A.spec[i];
+    int wi[3];
+    hess_home_cell(A, xi, yi, zi, wi);
     const double s3_lo = B->s3_lo, s3_hi = B->s3_hi;
     const bool has3 = B->T > 0;
     const int n0 = A.per[0] ? A.nimg[0] : 0, n1 = A.per[1] ? A.nimg[1] : 0, n2 = A.per[2] ? A.nimg[2] : 0;
@@ -86,10 +104,12 @@ __device__ __forceinline__ void hess_lists_atom(const HessArgs &A, int i, int la
         const int jj = live ? j : i;
         const double ex = A.pos[3 * (size_t)jj] - xi, ey = A.pos[3 * (size_t)jj + 1] - yi, ez = A.pos[3 * (size_t)jj + 2] - zi;
         const int sj = A.spec[jj];
-        int base[3];
+        int base[3], wj[3];
+        hess_home_cell(A, A.pos[3 * (size_t)jj], A.pos[3 * (size_t)jj + 1], A.pos[3 * (size_t)jj + 2], wj);
         for (int k = 0; k < 3; k++) {
             const double f = ex * A.inv[k] + ey * A.inv[3 + k] + ez * A.inv[6 + k];
             base[k] = A.per[k] ? -(int)rint(f) : 0;
+            wj[k] -= wi[k];                                   // what the wrapped frame's shift has over the one applied here
         }
         const int p = B->pair_of[si * UF3_MAX_SPECIES + sj];
         const double p_lo = p >= 0 ? B->pairs[p].s_lo : 0.0, p_hi = p >= 0 ? B->pairs[p].s_hi : -1.0;
@@ -106,14 +126,16 @@ __device__ __forceinline__ void hess_lists_atom(const HessArgs &A, int i, int la
                     const bool in3 = has3 && s > s3_lo && s <= s3_hi;
                     const bool ok = live && !self && (in2 || in3);
                     // (the reverse-shift lookup of k_hessian compares packed shifts: a shift beyond pack3's +-511 would alias)
-                    if (CHECK && ok && (abs(S0) > 500 || abs(S1) > 500 || abs(S2) > 500)) *A.bad = 1;
+                    const int T0 = S0 + wj[0], T1 = S1 + wj[1], T2 = S2 + wj[2];
+                    if (CHECK && ok && (abs(S0) > 500 || abs(S1) > 500 || abs(S2) > 500 || abs(T0) > 500 || abs(T1) > 500 || abs(T2) > 500))
+                        *A.bad = 1;
                     const unsigned long long mask = __ballot(ok);
                     if (WRITE && ok) {
                         const int slot = count + mbcnt(mask);
                         if (slot < A.cap) {
                             HessNbr e;
                             e.dx = dx; e.dy = dy; e.dz = dz; e.r = sqrt(s);
-                            e.j = j; e.shp = pack3(S0, S1, S2); e.spec = sj; e.flags = (in2 ? 1 : 0) | (in3 ? 2 : 0);
+                            e.j = j; e.shp = pack3(T0, T1, T2); e.spec = sj; e.flags = (in2 ? 1 : 0) | (in3 ? 2 : 0);
                             out[slot] = e;
                         }
                     }

@@ -150,6 +150,7 @@ struct uf3_ctx {
                                         // and the host staging
     Buf site_rows_ws, site_off;         // uf3_site_grade: the fall-back's chunk of rows (bounded) | the caller's frame offsets
     bool site_grade_lds_set = false;    // k_site_grade may take SG_LDS_BUDGET of dynamic LDS
+    bool site_rows_lds_set = false;     // k_site_rows likewise (SITE_ROWS_LDS)
     std::vector<char> ph_stage;         // host image of ph_ws (kept alive behind the asynchronous copy)
     int n3_cap = 0, cand_cap = 0;
     size_t bin_cnt_clean = 0;        // ints of bin_cnt known to be zero (k_bin_fill leaves the counts it used at zero)
@@ -5597,7 +5598,8 @@ extern "C" int uf3_heat_flux(uf3_basis *b, const uf3_frames *fr, const double *p
 }
 
 // ------------------------------------------------------------------------------ site rows and grades (uf3_site_rows.h)
-#define SITE_ROWS_LDS 65536                        // k_site_rows: row + index array
+#define SITE_ROWS_LDS SG_LDS_BUDGET                // k_site_rows: row + index array; as k_site_grade, two workgroups per CU (a row of
+                                                   // eight species' notebook basis, F = 8164, takes 65 552 bytes)
 #define SITE_CHUNK_BYTES ((size_t)64 << 20)        // the fall-back's chunk of rows
 
 // k_site_rows on centres [m0, m1) of the lists in F
@@ -5607,6 +5609,14 @@ static void site_rows_launch(uf3_ctx *c, const FluxArgs &F, int n_feat, long lon
     const size_t lds = 8 * (size_t)site_row_stride(n_feat) + 4 * (size_t)F.cap;
     hipLaunchKernelGGL(k_site_rows, dim3((unsigned)(m1 - m0)), dim3(64), lds, c->stream, A);
 }
+// more than the default 64 KB of dynamic LDS has to be asked for, once per context (before the first launch)
+static int site_rows_lds_attr(uf3_ctx *c) {
+    if (!c->site_rows_lds_set) {
+        HIPCHK(c, hipFuncSetAttribute((const void *)k_site_rows, hipFuncAttributeMaxDynamicSharedMemorySize, SITE_ROWS_LDS));
+        c->site_rows_lds_set = true;
+    }
+    return UF3_OK;
+}
 static int site_rows_cap_limit(int n_feat) { return (SITE_ROWS_LDS - 8 * site_row_stride(n_feat)) / 4; }
 
 static int site_rows_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, double *d_rows, int64_t ld) {
@@ -5615,6 +5625,7 @@ static int site_rows_impl(uf3_basis *b, const uf3_frames *fr, const double *d_po
     if (!d_pos || !d_rows) return fail(c, UF3_EINVAL, "uf3_site_rows: null argument");
     if (ld < n_feat) return fail(c, UF3_EINVAL, "uf3_site_rows: ld must be >= n_feat");
     if (site_rows_cap_limit(n_feat) < 1) return fail(c, UF3_EINVAL, "uf3_site_rows: a row of this basis does not fit in LDS");
+    if (int ra = site_rows_lds_attr(c)) return ra;
     FluxArgs F;
     int rc = lists_prepare(b, fr, c->fx, d_z, nullptr, nullptr, nullptr, "uf3_site_rows", "batch", F, false);
     if (rc) return rc;
@@ -5667,6 +5678,7 @@ static int site_grade_sample(uf3_basis *b, ListWork &W, FluxArgs &F, bool headro
         HIPCHK(c, hipFuncSetAttribute((const void *)k_site_grade, hipFuncAttributeMaxDynamicSharedMemorySize, SG_LDS_BUDGET));
         c->site_grade_lds_set = true;
     }
+    if (int ra = site_rows_lds_attr(c)) return ra;
     if (site_rows_cap_limit(n_feat) < 1) return fail(c, UF3_EINVAL, std::string(who) + ": a row of this basis does not fit in LDS");
     hipStream_t st = c->stream;
     return lists_sample(c, W, F, headroom, who, site_rows_cap_limit(n_feat), ": an atom has more neighbours than fit in LDS beside its row", [&] {
