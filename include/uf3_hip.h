@@ -106,7 +106,7 @@ int uf3_ctx_use_own_stream(uf3_ctx *ctx);
 int uf3_ctx_synchronize(uf3_ctx *ctx);
 const char *uf3_last_error(const uf3_ctx *ctx);
 /* Which sources this binary was compiled from: the first 16 hex digits of the sha256 over uf3_hip.hip, uf3_kernels.h,
- * uf3_feat3.h, uf3_virial_rows.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h, uf3_npt.h, uf3_neb.h, uf3_mc.h, uf3_flux.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
+ * uf3_feat3.h, uf3_virial_rows.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h, uf3_npt.h, uf3_neb.h, uf3_idpp.h, uf3_mc.h, uf3_flux.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
  * outside it).  __graft_entry__.build() rebuilds when it differs from the tree's, smoke() prints it. */
 const char *uf3_build_id(void);
 /* timing of the dominant kernel: (re)start / read accumulated HIP-event time in ms and launches */
@@ -612,6 +612,29 @@ int uf3_neb_run(uf3_neb *neb, int64_t max_steps, double fmax, double dt, double 
                 int64_t check_every, int64_t record_every, double *records);
 int uf3_neb_get_state(uf3_neb *neb, double *pos, double *forces, double *neb_forces, double *energies, int32_t *status,
                       int64_t *steps, double *criterion, int32_t *climbing /*[n_bands]*/);
+
+/*
+ * IDPP band initialisation on the device (uf3_amd.forcefield.neb.IDPP / idpp_interpolate; kernels in uf3_idpp.h): bands relaxed on
+ * the image dependent pair potential (Smidstrup et al., J. Chem. Phys. 140, 214106; ASE's idpp_interpolate), an artificial surface
+ * built from interpolated pair distances that keeps atoms of a band apart where a linear band drives them through each other.
+ * Image k of a band of M images, lambda = k / (M - 1), over all pairs with one image each (no cut-off):
+ *     d_ij = |D_ij|, D_ij the nearest-image vector x_j - x_i;   t_ij = (1 - lambda) d_ij(R^0) + lambda d_ij(R^{M-1});
+ *     S = sum_{i<j} (t_ij - d_ij)^2 / d_ij^4  (1 / A^2);   F_i = -dS/dx_i = sum_{j != i} c_ij D_ij / d_ij,
+ *     c_ij = -2 (t - d) (d + 2 (t - d)) / d^5.
+ * Nearest-image vector: the fractional difference along the periodic axes (the cell completed by unit vectors orthogonal to its
+ * periodic rows for the other axes) has its rounding subtracted; among the 3^p shifts in {-1, 0, 1} on the p periodic axes around
+ * that result the shortest vector is taken, ties to the first in a fixed order.  Exact for every cell whose true nearest image
+ * lies within one cell of the rounded one; where the periodic cell rows are mutually orthogonal rounding alone is exact and the
+ * search is skipped.  A pair at exactly half a cell is a kink of S.
+ *   uf3_idpp_create    uf3_neb_create's arguments and refusals without a basis and a model (spring: 1 / A^4).  The handle is a
+ *                      uf3_neb whose energies are S and whose forces are F; uf3_neb_run (skin is accepted and unused: no lists
+ *                      are built and the context's MD skin is not touched; climb = 1 is UF3_EINVAL), uf3_neb_get_state and
+ *                      uf3_neb_destroy serve it.  Fixed atoms count in every sum and feel no force.  Coincident atoms make S
+ *                      non-finite: that band ends with status 2.
+ */
+int uf3_idpp_create(uf3_ctx *ctx, const uf3_frames *frames, const double *pos, const int32_t *z, const uint8_t *fixed,
+                    int32_t n_bands, const int32_t *band_first_frame /*[n_bands + 1]*/, const double *spring /*[n_bands]*/,
+                    uf3_neb **out);
 
 /*
  * Batched species-swap Monte Carlo on fixed positions (uf3_amd.forcefield.mc.MonteCarlo; kernels in uf3_mc.h): every frame its own

@@ -26,6 +26,7 @@
 #include "uf3_hessian.h"
 #include "uf3_relax.h"
 #include "uf3_neb.h"
+#include "uf3_idpp.h"
 #include "uf3_mc.h"
 #include "uf3_phonon.h"
 #include "uf3_flux.h"
@@ -3828,15 +3829,14 @@ static bool md_finite(const double *a, size_t n) {
 }
 
 // what every *_create checks of its batch; *n: the atoms of the batch
-static int batch_check(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1, const double *c2,
-                       const double *c3, const void *out, const std::string &who, int64_t *n) {
-    if (!b) return fail(nullptr, UF3_EINVAL, who + ": basis is NULL");
-    uf3_ctx *c = b->ctx;
+// (b null: a batch without a model -- uf3_idpp_create -- on context c)
+static int batch_check(uf3_ctx *c, uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1,
+                       const double *c2, const double *c3, const void *out, const std::string &who, int64_t *n) {
     if (!out) return fail(c, UF3_EINVAL, who + ": out is NULL");
     if (!fr || fr->n_frames < 1 || !fr->atom_offsets || !fr->cells || !fr->pbc) return fail(c, UF3_EINVAL, who + ": bad uf3_frames");
     if (!pos) return fail(c, UF3_EINVAL, who + ": pos is NULL");
     if (!z) return fail(c, UF3_EINVAL, who + ": z is NULL");
-    if (!c1 || (b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, who + ": missing coefficients (c1 / c2 / c3)");
+    if (b && (!c1 || (b->c2_len && !c2) || (b->c3_len && !c3))) return fail(c, UF3_EINVAL, who + ": missing coefficients (c1 / c2 / c3)");
     const int nf = fr->n_frames;
     if (fr->atom_offsets[0] != 0) return fail(c, UF3_EINVAL, who + ": atom_offsets[0] must be 0");
     for (int f = 0; f < nf; f++)
@@ -3848,11 +3848,17 @@ static int batch_check(uf3_basis *b, const uf3_frames *fr, const double *pos, co
     return UF3_OK;
 }
 
+static int batch_check(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1, const double *c2,
+                       const double *c3, const void *out, const std::string &who, int64_t *n) {
+    if (!b) return fail(nullptr, UF3_EINVAL, who + ": basis is NULL");
+    return batch_check(b->ctx, b, fr, pos, z, c1, c2, c3, out, who, n);
+}
+
 // the host copies of a checked batch (c2 / c3 followed by coeff_pad zeros), the four common buffers and their uploads, queued on
 // the stream: the caller's own uploads follow, then one wait.  pos == nullptr: the caller uploads the positions itself
-static int batch_init(Batch &B, uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1,
+// (b null: no model is kept, c is the context)
+static int batch_init(Batch &B, uf3_ctx *c, uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1,
                       const double *c2, const double *c3, size_t coeff_pad, const std::string &who) {
-    uf3_ctx *c = b->ctx;
     const int nf = fr->n_frames;
     const size_t n = (size_t)fr->atom_offsets[nf];
     B.b = b; B.c = c; B.n_frames = nf; B.natoms = (int64_t)n;
@@ -3860,9 +3866,11 @@ static int batch_init(Batch &B, uf3_basis *b, const uf3_frames *fr, const double
     B.cells.assign(fr->cells, fr->cells + 9 * (size_t)nf);
     B.pbc.assign(fr->pbc, fr->pbc + 3 * (size_t)nf);
     B.fr.n_frames = nf; B.fr.atom_offsets = B.offsets.data(); B.fr.cells = B.cells.data(); B.fr.pbc = B.pbc.data();
-    B.c1.assign(c1, c1 + b->host.S);
-    B.c2.assign(c2 ? c2 : c1, (c2 ? c2 : c1) + b->c2_len); B.c2.resize(b->c2_len + coeff_pad, 0.0);
-    B.c3.assign(c3 ? c3 : c1, (c3 ? c3 : c1) + b->c3_len); B.c3.resize(b->c3_len + coeff_pad, 0.0);
+    if (b) {
+        B.c1.assign(c1, c1 + b->host.S);
+        B.c2.assign(c2 ? c2 : c1, (c2 ? c2 : c1) + b->c2_len); B.c2.resize(b->c2_len + coeff_pad, 0.0);
+        B.c3.assign(c3 ? c3 : c1, (c3 ? c3 : c1) + b->c3_len); B.c3.resize(b->c3_len + coeff_pad, 0.0);
+    }
     if (B.pos.ensure(24 * n) || B.z.ensure(4 * n) || B.energies.ensure(8 * (size_t)nf) || B.offsets_dev.ensure(8 * (size_t)(nf + 1)))
         return fail(c, UF3_ENOMEM, who + ": out of device memory");
     hipStream_t s = c->stream;
@@ -3870,6 +3878,11 @@ static int batch_init(Batch &B, uf3_basis *b, const uf3_frames *fr, const double
         hipMemcpyAsync(B.offsets_dev.p, B.offsets.data(), 8 * (size_t)(nf + 1), hipMemcpyHostToDevice, s))
         return fail(c, UF3_EHIP, who + ": upload failed");
     return UF3_OK;
+}
+
+static int batch_init(Batch &B, uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1,
+                      const double *c2, const double *c3, size_t coeff_pad, const std::string &who) {
+    return batch_init(B, b->ctx, b, fr, pos, z, c1, c2, c3, coeff_pad, who);
 }
 
 // the evaluator on the batch's positions: energies, and forces / strain derivatives where asked for
@@ -4719,30 +4732,33 @@ struct uf3_neb : Batch {
     bool forces_valid = false;                  // frc / energies describe pos
     bool g_valid = false;                       // g describes pos (and the climb flag of the last run)
     int last_climb = 0;
+    bool idpp = false;                          // made by uf3_idpp_create: energies and forces are k_idpp's, not the evaluator's
+    DevBuf idpp_cells, idpp_partial;
 };
 
 extern "C" void uf3_neb_destroy(uf3_neb *r) { driver_destroy(r); }
 
-extern "C" int uf3_neb_create(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const uint8_t *fixed,
-                              const double *c1, const double *c2, const double *c3, int32_t n_bands, const int32_t *band_first_frame,
-                              const double *spring, uf3_neb **out) {
-    const char *who = "uf3_neb_create";
+static int idpp_setup(uf3_neb *r, const std::string &who);
+
+// uf3_neb_create (b: the basis of the model c1 / c2 / c3) and uf3_idpp_create (b null: no model, the handle evaluates k_idpp)
+static int neb_create(uf3_ctx *c, uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const uint8_t *fixed,
+                      const double *c1, const double *c2, const double *c3, int32_t n_bands, const int32_t *band_first_frame,
+                      const double *spring, uf3_neb **out, const std::string &me) {
     int64_t n = 0;
-    int rc = batch_check(b, fr, pos, z, c1, c2, c3, out, who, &n);
+    int rc = batch_check(c, b, fr, pos, z, c1, c2, c3, out, me, &n);
     if (rc) return rc;
-    uf3_ctx *c = b->ctx;
-    if (n_bands < 1 || !band_first_frame || !spring) return fail(c, UF3_EINVAL, "uf3_neb_create: needs a band, band_first_frame and spring");
+    if (n_bands < 1 || !band_first_frame || !spring) return fail(c, UF3_EINVAL, me + ": needs a band, band_first_frame and spring");
     const int nf = fr->n_frames;
     if (fixed)
         for (int64_t i = 0; i < n; i++)
-            if (fixed[i] > 1) return fail(c, UF3_EINVAL, "uf3_neb_create: fixed must hold 0 or 1 per atom");
+            if (fixed[i] > 1) return fail(c, UF3_EINVAL, me + ": fixed must hold 0 or 1 per atom");
     if (band_first_frame[0] != 0 || band_first_frame[n_bands] != nf)
-        return fail(c, UF3_EINVAL, "uf3_neb_create: band_first_frame must run from 0 to n_frames");
+        return fail(c, UF3_EINVAL, me + ": band_first_frame must run from 0 to n_frames");
     std::vector<NebBand> st(n_bands);
     std::vector<int> frame_band(nf);
     for (int bd = 0; bd < n_bands; bd++) {
         const int f0 = band_first_frame[bd], M = band_first_frame[bd + 1] - f0;
-        const std::string who = "uf3_neb_create: band " + std::to_string(bd);
+        const std::string who = me + ": band " + std::to_string(bd);
         if (M < 3) return fail(c, UF3_EINVAL, who + " has " + std::to_string(M) + " images; a band needs at least 3");
         if (!(spring[bd] > 0.0) || !std::isfinite(spring[bd])) return fail(c, UF3_EINVAL, who + ": spring must be positive and finite");
         const int64_t lo0 = fr->atom_offsets[f0], na = fr->atom_offsets[f0 + 1] - lo0;
@@ -4773,15 +4789,15 @@ extern "C" int uf3_neb_create(uf3_basis *b, const uf3_frames *fr, const double *
     r->st_host = st;
     r->e_last_host.assign(nf, std::numeric_limits<double>::quiet_NaN());
     auto bail = [&](int rc) { uf3_neb_destroy(r); return rc; };
-    rc = batch_init(*r, b, fr, pos, z, c1, c2, c3, 1, who);
-    if (!rc) rc = chunk_table_build(c, r->offsets, nf, UF3_RELAX_THREADS, r->chunks, who);
+    rc = batch_init(*r, c, b, fr, pos, z, c1, c2, c3, 1, me);
+    if (!rc) rc = chunk_table_build(c, r->offsets, nf, UF3_RELAX_THREADS, r->chunks, me);
     if (rc) return bail(rc);
     const size_t n3 = 3 * (size_t)n, nb = (size_t)r->chunks.n_blocks;
     if (r->vel.ensure(8 * n3) || r->frc.ensure(8 * n3) || r->g.ensure(8 * n3) || (fixed && r->fixed.ensure((size_t)n)) ||
         r->e_last.ensure(8 * (size_t)nf) || r->frame_band.ensure(4 * (size_t)nf) || r->st.ensure(sizeof(NebBand) * (size_t)n_bands) ||
         r->coef.ensure(sizeof(NebCoef) * (size_t)n_bands) || r->img.ensure(sizeof(NebImage) * (size_t)nf) ||
         r->partial.ensure(8 * UF3_NEB_NSUM * nb) || r->cmax.ensure(8 * nb))
-        return bail(fail(c, UF3_ENOMEM, "uf3_neb_create: out of device memory"));
+        return bail(fail(c, UF3_ENOMEM, me + ": out of device memory"));
     hipStream_t s = c->stream;
     if (hipMemsetAsync(r->vel.p, 0, 8 * n3, s) || hipMemsetAsync(r->g.p, 0, 8 * n3, s) ||
         (fixed && hipMemcpyAsync(r->fixed.p, fixed, (size_t)n, hipMemcpyHostToDevice, s)) ||
@@ -4792,13 +4808,115 @@ extern "C" int uf3_neb_create(uf3_basis *b, const uf3_frames *fr, const double *
         hipMemsetAsync(r->img.p, 0, sizeof(NebImage) * (size_t)nf, s) ||
         hipMemsetAsync(r->partial.p, 0, 8 * UF3_NEB_NSUM * nb, s) || hipMemsetAsync(r->cmax.p, 0, 8 * nb, s) ||
         hipStreamSynchronize(s))
-        return bail(fail(c, UF3_EHIP, "uf3_neb_create: upload failed"));
+        return bail(fail(c, UF3_EHIP, me + ": upload failed"));
+    if (!b) {
+        rc = idpp_setup(r, me);
+        if (rc) return bail(rc);
+    }
     *out = r;
     return UF3_OK;
 }
 
+extern "C" int uf3_neb_create(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const uint8_t *fixed,
+                              const double *c1, const double *c2, const double *c3, int32_t n_bands, const int32_t *band_first_frame,
+                              const double *spring, uf3_neb **out) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "uf3_neb_create: basis is NULL");
+    return neb_create(b->ctx, b, fr, pos, z, fixed, c1, c2, c3, n_bands, band_first_frame, spring, out, "uf3_neb_create");
+}
+
+// one frame's cell for k_idpp: the inverse of the cell completed as neb._axes does (the rows of non-periodic axes replaced by unit
+// vectors orthogonal to the rows there) and the flags.  False: the periodic rows span nothing
+static bool idpp_cell(const double *cell, const uint8_t *pbc, IdppCell &C) {
+    double h[3][3];
+    int np = 0;
+    for (int k = 0; k < 3; k++) {
+        C.per[k] = pbc[k] != 0;
+        np += C.per[k];
+        for (int q = 0; q < 3; q++) h[k][q] = C.per[k] ? cell[3 * k + q] : 0.0;
+    }
+    auto cross = [](const double *u, const double *v, double *w) {
+        w[0] = u[1] * v[2] - u[2] * v[1]; w[1] = u[2] * v[0] - u[0] * v[2]; w[2] = u[0] * v[1] - u[1] * v[0];
+    };
+    auto unit = [](double *w) {
+        const double l = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+        if (!(l > 0.0) || !std::isfinite(l)) return false;
+        for (int q = 0; q < 3; q++) w[q] /= l;
+        return true;
+    };
+    if (np == 2) {
+        const int k = !C.per[0] ? 0 : (!C.per[1] ? 1 : 2);
+        cross(h[(k + 1) % 3], h[(k + 2) % 3], h[k]);
+        if (!unit(h[k])) return false;
+    } else if (np == 1) {
+        const int k = C.per[0] ? 0 : (C.per[1] ? 1 : 2);
+        int m = 0;                                  // the Cartesian axis least along the row
+        for (int q = 1; q < 3; q++) if (std::fabs(h[k][q]) < std::fabs(h[k][m])) m = q;
+        double e[3] = {0.0, 0.0, 0.0};
+        e[m] = 1.0;
+        cross(h[k], e, h[(k + 1) % 3]);
+        if (!unit(h[(k + 1) % 3])) return false;
+        cross(h[k], h[(k + 1) % 3], h[(k + 2) % 3]);
+        if (!unit(h[(k + 2) % 3])) return false;
+    } else if (np == 0) {
+        for (int k = 0; k < 3; k++) h[k][k] = 1.0;
+    }
+    double co[3][3];
+    cross(h[1], h[2], co[0]); cross(h[2], h[0], co[1]); cross(h[0], h[1], co[2]);
+    const double det = h[0][0] * co[0][0] + h[0][1] * co[0][1] + h[0][2] * co[0][2];
+    if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return false;
+    bool ortho = true;
+    for (int k = 0; k < 3; k++) {
+        for (int q = 0; q < 3; q++) {
+            C.h[3 * k + q] = C.per[k] ? cell[3 * k + q] : 0.0;
+            C.g[3 * k + q] = co[k][q] / det;        // the fraction along axis k of D: D . (h_l x h_m) / det
+        }
+        for (int l = k + 1; l < 3; l++)
+            if (C.per[k] && C.per[l] && h[k][0] * h[l][0] + h[k][1] * h[l][1] + h[k][2] * h[l][2] != 0.0) ortho = false;
+    }
+    C.search = (np > 0 && !ortho) ? 1 : 0;          // mutually orthogonal periodic rows (exact zeros): rounding alone is exact
+    return true;
+}
+
+static int idpp_setup(uf3_neb *r, const std::string &who) {
+    uf3_ctx *c = r->c;
+    r->idpp = true;
+    std::vector<IdppCell> cells(r->n_frames);
+    for (int f = 0; f < r->n_frames; f++)
+        if (!idpp_cell(r->cells.data() + 9 * (size_t)f, r->pbc.data() + 3 * (size_t)f, cells[f]))
+            return fail(c, UF3_EINVAL, who + ": frame " + std::to_string(f) + ": the periodic cell rows span no volume");
+    if (r->idpp_cells.ensure(sizeof(IdppCell) * cells.size()) || r->idpp_partial.ensure(8 * (size_t)r->chunks.n_blocks))
+        return fail(c, UF3_ENOMEM, who + ": out of device memory");
+    if (hipMemcpyAsync(r->idpp_cells.p, cells.data(), sizeof(IdppCell) * cells.size(), hipMemcpyHostToDevice, c->stream) ||
+        hipStreamSynchronize(c->stream))
+        return fail(c, UF3_EHIP, who + ": upload failed");
+    return UF3_OK;
+}
+
+extern "C" int uf3_idpp_create(uf3_ctx *c, const uf3_frames *fr, const double *pos, const int32_t *z, const uint8_t *fixed,
+                               int32_t n_bands, const int32_t *band_first_frame, const double *spring, uf3_neb **out) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "uf3_idpp_create: ctx is NULL");
+    return neb_create(c, nullptr, fr, pos, z, fixed, nullptr, nullptr, nullptr, n_bands, band_first_frame, spring, out, "uf3_idpp_create");
+}
+
+// S and F of every image of a handle of uf3_idpp_create (k_idpp, k_idpp_sum): no lists, no model, nothing of the context's MD state
+static int idpp_evaluate(uf3_neb *r) {
+    uf3_ctx *c = r->c;
+    const ChunkTable &T = r->chunks;
+    IdppArgs P;
+    P.pos = r->pos.as<double>(); P.blk_frame = T.blk_frame.as<int>(); P.blk_lo = T.blk_lo.as<long long>(); P.blk_n = T.blk_n.as<int>();
+    P.frame_blk = T.frame_blk.as<int>(); P.frame_band = r->frame_band.as<int>(); P.offsets = r->offsets_dev.as<long long>();
+    P.bands = r->st.as<NebBand>(); P.cells = r->idpp_cells.as<IdppCell>(); P.frc = r->frc.as<double>();
+    P.partial = r->idpp_partial.as<double>(); P.energies = r->energies.as<double>(); P.n_frames = r->n_frames;
+    hipLaunchKernelGGL(k_idpp, dim3((unsigned)T.n_blocks), dim3(UF3_RELAX_THREADS), 0, c->stream, P);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_idpp_sum, dim3((unsigned)((r->n_frames + UF3_RELAX_THREADS - 1) / UF3_RELAX_THREADS)), dim3(UF3_RELAX_THREADS), 0,
+                       c->stream, P);
+    HIPCHK(c, hipGetLastError());
+    return UF3_OK;
+}
+
 static int neb_evaluate(uf3_neb *r) {
-    int rc = batch_eval(*r, r->frc.as<double>(), nullptr);
+    int rc = r->idpp ? idpp_evaluate(r) : batch_eval(*r, r->frc.as<double>(), nullptr);
     r->forces_valid = rc == UF3_OK;
     r->g_valid = false;
     return rc;
@@ -4911,6 +5029,10 @@ extern "C" int uf3_neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt
         return fail(c, UF3_EINVAL, record_every ? "uf3_neb_run: records are due but the records buffer is NULL"
                                                 : "uf3_neb_run: a records buffer was given but no record is due");
     HIPCHK(c, hipSetDevice(c->device));
+    if (r->idpp) {                              // no lists are built: the context's MD skin is not touched
+        if (climb) return fail(c, UF3_EINVAL, "uf3_neb_run: a handle of uf3_idpp_create takes no climbing image");
+        return neb_run(r, max_steps, fmax, dt, dt_max, maxstep, 0, check_every, record_every, records);
+    }
     return with_run_skin(c, skin, [&] { return neb_run(r, max_steps, fmax, dt, dt_max, maxstep, climb, check_every, record_every, records); });
 }
 

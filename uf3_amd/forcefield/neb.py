@@ -20,7 +20,18 @@ status ``"nonfinite"``.
 
 ``run`` may be called again: the FIRE state carries over, and ``run(a); run(b)`` follows ``run(a + b)``.  A band that converged
 is tested again by the next run, whose ``fmax`` and ``climb`` may differ, and moves only if it fails that test.
+
+``interpolate`` builds a band by linear interpolation of the positions, which drives atoms through each other on any path that
+turns (an exchange, a dumbbell rotation, a ring).  ``idpp_interpolate`` relaxes that band on the image dependent pair potential
+(``IDPP``; Smidstrup et al., J. Chem. Phys. 140, 214106; what ASE calls ``idpp_interpolate``), which needs no model, on the device
+(``uf3_idpp_create``, ``uf3_amd/csrc/uf3_idpp.h``):
+
+    images, info = neb.idpp_interpolate(initial, final, 7)
 """
+import ctypes as C
+import os
+import warnings
+
 import numpy as np
 
 from uf3_amd import _lib
@@ -68,74 +79,64 @@ def interpolate(initial, final, n_images, mic=True):
     return [Atoms(numbers=z, positions=x0 + d * (k / (n_images - 1)), cell=cell, pbc=pbc) for k in range(n_images)]
 
 
-def _bands_of(bands):
+def _bands_of(bands, who=WHO):
     if isinstance(bands, (list, tuple)) and bands and isinstance(bands[0], (list, tuple)):
         return False, [list(b) for b in bands]
     if not isinstance(bands, (list, tuple)):
-        raise ValueError("NudgedElasticBand: bands must be a list of Atoms or a list of such lists")
+        raise ValueError(f"{who}: bands must be a list of Atoms or a list of such lists")
     return True, [list(bands)]
 
 
-def _check_band(k, band):
+def _check_band(k, band, who=WHO):
     if len(band) < 3:
-        raise ValueError(f"NudgedElasticBand: band {k} has {len(band)} images; a band needs at least 3")
+        raise ValueError(f"{who}: band {k} has {len(band)} images; a band needs at least 3")
     a0 = band[0]
     if len(a0) < 1:
-        raise ValueError(f"NudgedElasticBand: band {k} has no atoms")
+        raise ValueError(f"{who}: band {k} has no atoms")
     z0 = np.asarray(a0.get_atomic_numbers())
     c0 = np.array(a0.get_cell(), dtype=float).reshape(3, 3)
     p0 = np.asarray(a0.get_pbc(), dtype=bool).reshape(3)
     for j, a in enumerate(band[1:], 1):
         if len(a) != len(a0):
-            raise ValueError(f"NudgedElasticBand: band {k}, image {j}: atom count differs from image 0")
+            raise ValueError(f"{who}: band {k}, image {j}: atom count differs from image 0")
         if not np.array_equal(np.asarray(a.get_atomic_numbers()), z0):
-            raise ValueError(f"NudgedElasticBand: band {k}, image {j}: species differ from image 0")
+            raise ValueError(f"{who}: band {k}, image {j}: species differ from image 0")
         if not np.array_equal(np.array(a.get_cell(), dtype=float).reshape(3, 3), c0):
-            raise ValueError(f"NudgedElasticBand: band {k}, image {j}: cell differs from image 0")
+            raise ValueError(f"{who}: band {k}, image {j}: cell differs from image 0")
         if not np.array_equal(np.asarray(a.get_pbc(), dtype=bool).reshape(3), p0):
-            raise ValueError(f"NudgedElasticBand: band {k}, image {j}: pbc differs from image 0")
+            raise ValueError(f"{who}: band {k}, image {j}: pbc differs from image 0")
         if np.array_equal(np.asarray(a.get_positions(), dtype=float), np.asarray(band[j - 1].get_positions(), dtype=float)):
-            raise ValueError(f"NudgedElasticBand: band {k}, image {j}: positions identical to image {j - 1}")
+            raise ValueError(f"{who}: band {k}, image {j}: positions identical to image {j - 1}")
 
 
-class NudgedElasticBand(Driver):
-    """Batched nudged-elastic-band relaxation of one or more bands on the device (module text above).
+class _Bands(Driver):
+    """What ``NudgedElasticBand`` and ``IDPP`` share: the checks of the bands, the state getters and the run on a ``uf3_neb``
+    handle."""
+    KIND = "neb"
 
-    Atoms outside the cell: positions are kept unwrapped and go to the evaluator as they are, and the evaluator takes the
-    reference's finite image range around the positions as given (``include/uf3_hip.h``, above ``uf3_md_create``; DESIGN.md
-    section 7).  An atom that leaves its cell along a band or while it relaxes loses the interactions that range no longer reaches from where it
-    is: energies and forces are then ``evaluate_frames``' of the unwrapped positions, not the wrapped crystal's.  Start from
-    wrapped frames, and describe a path that crosses a cell face in a cell (or with an origin) in which every image stays inside."""
-    KIND, WHO = "neb", WHO
-
-    def __init__(self, calc, bands, spring=0.1, fixed=None, skin=0.5, device=None):
-        """``bands``: one band (a list of ``Atoms``) or a list of bands.  ``spring`` (eV / Angstrom^2): a scalar or one value
-        per band.  ``fixed``: boolean mask [sum N] over the concatenated images of all bands (ASE's FixAtoms), the same in
-        every image of a band: those atoms feel no force, never move and do not enter tangents or spring lengths.  ``skin``
-        (Angstrom): the evaluator's neighbour-list skin during runs."""
-        # every argument is checked before the device is touched
-        self.skin = check_real(WHO, "skin", skin, hi=4.0)
-        self._single, self.bands = _bands_of(bands)
+    def _setup(self, bands, spring, fixed):
+        """Every check of ``bands``, ``spring`` and ``fixed``, and ``self._batch``: nothing here touches the device."""
+        who = self.WHO
+        self._single, self.bands = _bands_of(bands, who)
         for k, band in enumerate(self.bands):
-            _check_band(k, band)
+            _check_band(k, band, who)
         nb = len(self.bands)
         sp = np.asarray(spring, dtype=float)
         if sp.ndim == 0:
             sp = np.full(nb, float(sp))
         if sp.shape != (nb,):
-            raise ValueError(f"NudgedElasticBand: spring must be a scalar or hold one value per band ({nb}), got shape {sp.shape}")
+            raise ValueError(f"{who}: spring must be a scalar or hold one value per band ({nb}), got shape {sp.shape}")
         if not np.all(np.isfinite(sp)) or np.any(sp <= 0.0):
-            raise ValueError("NudgedElasticBand: spring must be positive and finite")
+            raise ValueError(f"{who}: spring must be positive and finite")
         self.spring = np.ascontiguousarray(sp)
         self.frames = [a for band in self.bands for a in band]
         self.band_first = np.ascontiguousarray(np.cumsum([0] + [len(b) for b in self.bands]), dtype=np.int32)
-        self.calculator = calc
         self._batch = _lib.FrameBatch(self.frames)
         if not np.all(np.isfinite(self._batch.pos)):
-            raise ValueError("NudgedElasticBand: positions must be finite")
+            raise ValueError(f"{who}: positions must be finite")
         if not np.all(np.isfinite(self._batch.cells)):
-            raise ValueError("NudgedElasticBand: cells must be finite")
-        self.fixed = check_mask(WHO, "fixed", fixed, self._batch.n_atoms)
+            raise ValueError(f"{who}: cells must be finite")
+        self.fixed = check_mask(who, "fixed", fixed, self._batch.n_atoms)
         if self.fixed is not None:
             m = self.fixed
             off = self._batch.offsets
@@ -143,9 +144,7 @@ class NudgedElasticBand(Driver):
                 f0, f1 = self.band_first[k], self.band_first[k + 1]
                 for f in range(f0 + 1, f1):
                     if not np.array_equal(m[off[f]:off[f + 1]], m[off[f0]:off[f0 + 1]]):
-                        raise ValueError(f"NudgedElasticBand: band {k}, image {f - f0}: fixed mask differs from image 0")
-        self._create(calc, device, [_lib._p(self._batch.pos), _lib._p(self._batch.z), _lib._p(self.fixed)],
-                     [nb, _lib._p(self.band_first), _lib._p(self.spring)])
+                        raise ValueError(f"{who}: band {k}, image {f - f0}: fixed mask differs from image 0")
 
     # ---- state ------------------------------------------------------------------------------------------------------------
     def _state(self, *which):
@@ -162,16 +161,16 @@ class NudgedElasticBand(Driver):
         return self._state("pos")["pos"]
 
     def get_forces(self):
-        """[N, 3] eV / Angstrom: the true forces at the current positions."""
+        """[N, 3]: the true forces at the current positions (eV / Angstrom; ``IDPP``: F = -dS/dx, 1 / Angstrom^3)."""
         return self._state("forces")["forces"]
 
     def get_neb_forces(self):
-        """[N, 3] eV / Angstrom: the NEB forces g at the current positions (0 on end points and fixed atoms; climbing as in
-        the last run)."""
+        """[N, 3], the forces' unit: the NEB forces g at the current positions (0 on end points and fixed atoms; climbing as
+        in the last run)."""
         return self._state("neb_forces")["neb_forces"]
 
     def get_potential_energies(self):
-        """One array [M] per band, eV, at the current positions."""
+        """One array [M] per band at the current positions (eV; ``IDPP``: S, 1 / Angstrom^2)."""
         return self._per_band(self._state("energies")["energies"])
 
     def get_images(self):
@@ -185,24 +184,18 @@ class NudgedElasticBand(Driver):
         return out[0] if self._single else out
 
     # ---- optimisation -----------------------------------------------------------------------------------------------------
-    def run(self, max_steps, fmax=0.05, climb=False, dt=0.1, dt_max=1.0, maxstep=0.2, check_every=10, record_every=0):
-        """Up to ``max_steps`` FIRE steps of every band still running (evaluations 0 .. max_steps).  Returns per band:
-        ``status`` ("running" | "converged" | "nonfinite"), ``converged`` (bool), ``steps`` (moves made in all runs so far),
-        ``criterion`` (the largest per-atom |g|), ``energies`` (a list of arrays [M]), ``barrier`` (max E - E_0),
-        ``reverse_barrier`` (max E - E_{M-1}) and ``climbing_image`` (index within the band, -1: none) at the last evaluation;
-        with ``record_every`` > 0 also ``records``: ``iteration`` [n_rec], ``energies`` [n_rec, n_frames], ``criterion`` and
-        ``climbing_image`` [n_rec, n_bands] of evaluations 0, record_every, ... (after every band stopped, the final values
-        repeat)."""
-        max_steps = check_int(WHO, "max_steps", max_steps)
-        fmax = check_real(WHO, "fmax", fmax, strict=True)
+    def _run(self, max_steps, fmax, climb, dt, dt_max, maxstep, check_every, record_every, skin):
+        who = self.WHO
+        max_steps = check_int(who, "max_steps", max_steps)
+        fmax = check_real(who, "fmax", fmax, strict=True)
         if not isinstance(climb, (bool, np.bool_)):
-            raise ValueError(f"NudgedElasticBand: climb must be True or False, got {climb!r}")
-        dt = check_real(WHO, "dt", dt, strict=True)
-        dt_max = check_real(WHO, "dt_max", dt_max, strict=True)
-        maxstep = check_real(WHO, "maxstep", maxstep, strict=True)
-        check_every = check_int(WHO, "check_every", check_every, 1)
-        record_every = check_int(WHO, "record_every", record_every)
-        skin = check_real(WHO, "skin", self.skin, hi=4.0)
+            raise ValueError(f"{who}: climb must be True or False, got {climb!r}")
+        dt = check_real(who, "dt", dt, strict=True)
+        dt_max = check_real(who, "dt_max", dt_max, strict=True)
+        maxstep = check_real(who, "maxstep", maxstep, strict=True)
+        check_every = check_int(who, "check_every", check_every, 1)
+        record_every = check_int(who, "record_every", record_every)
+        skin = check_real(who, "skin", skin, hi=4.0)
         handle = self._live()
         nf, nb = self._batch.n_frames, len(self.bands)
         n_rec = max_steps // record_every + 1 if record_every else 0
@@ -219,3 +212,102 @@ class NudgedElasticBand(Driver):
             out["records"] = dict(iteration=record_every * np.arange(n_rec, dtype=np.int64), energies=raw[:, :nf].copy(),
                                   criterion=tail[..., 0].copy(), climbing_image=tail[..., 1].astype(np.int32))
         return out
+
+
+class NudgedElasticBand(_Bands):
+    """Batched nudged-elastic-band relaxation of one or more bands on the device (module text above).
+
+    Atoms outside the cell: positions are kept unwrapped and go to the evaluator as they are, and the evaluator takes the
+    reference's finite image range around the positions as given (``include/uf3_hip.h``, above ``uf3_md_create``; DESIGN.md
+    section 7).  An atom that leaves its cell along a band or while it relaxes loses the interactions that range no longer reaches from where it
+    is: energies and forces are then ``evaluate_frames``' of the unwrapped positions, not the wrapped crystal's.  Start from
+    wrapped frames, and describe a path that crosses a cell face in a cell (or with an origin) in which every image stays inside."""
+    WHO = WHO
+
+    def __init__(self, calc, bands, spring=0.1, fixed=None, skin=0.5, device=None):
+        """``bands``: one band (a list of ``Atoms``) or a list of bands.  ``spring`` (eV / Angstrom^2): a scalar or one value
+        per band.  ``fixed``: boolean mask [sum N] over the concatenated images of all bands (ASE's FixAtoms), the same in
+        every image of a band: those atoms feel no force, never move and do not enter tangents or spring lengths.  ``skin``
+        (Angstrom): the evaluator's neighbour-list skin during runs."""
+        # every argument is checked before the device is touched
+        self.skin = check_real(WHO, "skin", skin, hi=4.0)
+        self._setup(bands, spring, fixed)
+        self.calculator = calc
+        self._create(calc, device, [_lib._p(self._batch.pos), _lib._p(self._batch.z), _lib._p(self.fixed)],
+                     [len(self.bands), _lib._p(self.band_first), _lib._p(self.spring)])
+
+    def run(self, max_steps, fmax=0.05, climb=False, dt=0.1, dt_max=1.0, maxstep=0.2, check_every=10, record_every=0):
+        """Up to ``max_steps`` FIRE steps of every band still running (evaluations 0 .. max_steps).  Returns per band:
+        ``status`` ("running" | "converged" | "nonfinite"), ``converged`` (bool), ``steps`` (moves made in all runs so far),
+        ``criterion`` (the largest per-atom |g|), ``energies`` (a list of arrays [M]), ``barrier`` (max E - E_0),
+        ``reverse_barrier`` (max E - E_{M-1}) and ``climbing_image`` (index within the band, -1: none) at the last evaluation;
+        with ``record_every`` > 0 also ``records``: ``iteration`` [n_rec], ``energies`` [n_rec, n_frames], ``criterion`` and
+        ``climbing_image`` [n_rec, n_bands] of evaluations 0, record_every, ... (after every band stopped, the final values
+        repeat)."""
+        return self._run(max_steps, fmax, climb, dt, dt_max, maxstep, check_every, record_every, self.skin)
+
+
+class IDPP(_Bands):
+    """Bands relaxed on the image dependent pair potential on the device (``uf3_idpp_create``): for image k of a band of M
+    images, lambda = k / (M - 1), over all pairs with one image each,
+
+        S = sum_{i<j} (t_ij - d_ij)^2 / d_ij^4,    t_ij = (1 - lambda) d_ij(first image) + lambda d_ij(last image),
+
+    with d_ij the nearest-image distance (``include/uf3_hip.h`` above ``uf3_idpp_create``: exact for every cell whose nearest
+    image lies within one cell of the rounded fractional difference; a pair at exactly half a cell is a kink of S).  The band
+    mechanics are ``NudgedElasticBand``'s (improved tangent, springs, one FIRE per band, the same statuses) with S as the
+    energy (1 / Angstrom^2) and F = -dS/dx as the force (1 / Angstrom^3); there is no climbing image, no neighbour list and no
+    calculator.  Fixed atoms count in every sum and feel no force.  Two atoms of an image at one position make S non-finite:
+    that band ends ``"nonfinite"``."""
+    WHO = "IDPP"
+
+    def __init__(self, bands, spring=0.1, fixed=None, device=None):
+        """``bands``, ``fixed``: as on ``NudgedElasticBand``.  ``spring`` (1 / Angstrom^4): a scalar or one value per band."""
+        # every argument is checked before the device is touched
+        if device is not None:
+            device = check_int(self.WHO, "device", device)
+        self._setup(bands, spring, fixed)
+        self.ctx = _lib.get_context(device)
+        self._pid = os.getpid()
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.uf3_idpp_create(self.ctx.handle, C.byref(self._batch.struct), _lib._p(self._batch.pos),
+                                                    _lib._p(self._batch.z), _lib._p(self.fixed), len(self.bands),
+                                                    _lib._p(self.band_first), _lib._p(self.spring), C.byref(h)))
+        self.handle = h
+
+    def run(self, max_steps, fmax=0.1, dt=0.1, dt_max=1.0, maxstep=0.2, check_every=10, record_every=0):
+        """``NudgedElasticBand.run`` without ``climb``: ``criterion`` and ``fmax`` in 1 / Angstrom^3, ``energies`` S per image;
+        ``climbing_image`` is -1 throughout."""
+        return self._run(max_steps, fmax, False, dt, dt_max, maxstep, check_every, record_every, 0.0)
+
+
+def idpp_interpolate(initial, final, n_images, mic=True, fmax=0.1, max_steps=1000, **kw):
+    """``interpolate(initial, final, n_images, mic)``, then that band relaxed by ``IDPP`` until every atom of every interior
+    image has |g_i| < ``fmax`` (1 / Angstrom^3; 0.1 is ASE's default) or for ``max_steps`` steps.  ``initial`` and ``final`` may
+    be lists of equal length: one band each, relaxed in one batch.  ``kw``: ``spring``, ``fixed``, ``device`` of ``IDPP`` and
+    ``dt``, ``dt_max``, ``maxstep``, ``check_every`` of its ``run``.  Returns (images, info): the band (a list of bands for
+    lists), unwrapped like ``interpolate``'s, and ``IDPP.run``'s result.  Warns (``RuntimeWarning``) for each band that did
+    not converge."""
+    who = "idpp_interpolate"
+    many = isinstance(initial, (list, tuple))
+    if many != isinstance(final, (list, tuple)):
+        raise ValueError(f"{who}: initial and final must both be Atoms or both be lists")
+    ini, fin = (list(initial), list(final)) if many else ([initial], [final])
+    if len(ini) != len(fin) or not ini:
+        raise ValueError(f"{who}: initial and final hold {len(ini)} and {len(fin)} frames")
+    n_images = check_int(who, "n_images", n_images, 3)
+    fmax = check_real(who, "fmax", fmax, strict=True)
+    max_steps = check_int(who, "max_steps", max_steps)
+    make = {k: kw.pop(k) for k in ("spring", "fixed", "device") if k in kw}
+    run = {k: kw.pop(k) for k in ("dt", "dt_max", "maxstep", "check_every") if k in kw}
+    if kw:
+        raise ValueError(f"{who}: unknown arguments {sorted(kw)}")
+    bands = [interpolate(a, b, n_images, mic=mic) for a, b in zip(ini, fin)]
+    with IDPP(bands, **make) as band:
+        info = band.run(max_steps, fmax=fmax, **run)
+        images = band.get_images()
+    for k, status in enumerate(info["status"]):
+        if status != "converged":
+            warnings.warn(f"{who}: band {k} did not converge ({status}): criterion {info['criterion'][k]:.3g} 1 / Angstrom^3 "
+                          f"after {int(info['steps'][k])} steps", RuntimeWarning, stacklevel=2)
+    return (images if many else images[0]), info
