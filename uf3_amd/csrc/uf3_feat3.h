@@ -67,7 +67,9 @@ struct F3Cfg {
     static constexpr int PS = 32 * NR;                           // positions per fixed-leg row in the fold's dump
     static constexpr int EFP = (EF + 1) & ~1;                    // dense bond values of a neighbour-role record, padded
     static constexpr int RS_N = EFP + 16 + (NR == 1 ? 2 : 0);    // doubles per neighbour-role record: B(r_ek)[ext_p] | (a3 B_n', B_n) x 4 (| pad: 44 dwords apart, the
-                                                                 // eight lanes of a 16-byte store group hit different banks)
+                                                                 // eight lanes of a 16-byte store group hit different banks -- and the quad of zeros, kept
+                                                                 // zero, that stage 1 reads for an n slot outside the record's four functions.  The wide
+                                                                 // windows have no LDS to spare for a pad: they select the address of `zq` instead)
     static constexpr int RS_C = NR == 1 ? 10 : (NR == 2 ? 12 : 14);   // ... per centre-role record: B_n over the n window (ext_n < RS_C), zero-padded
     static constexpr int NREC = NR == 1 ? 29 : 32;               // neighbour-role records per engine pass
     static constexpr int DUMP = NR == 1 ? 4 * EF * 32 : 2 * (EF * PS + 2);   // the fold's dump: pairs of all four rows | one component per half at a time
@@ -86,25 +88,26 @@ typedef const __attribute__((address_space(3))) double *F3LdsDoubles;
 #define F3_ROWS_GLOBAL 0
 #endif
 typedef const __attribute__((address_space(1))) F3Pair *F3GlobalPairs;
-template <bool DERIV>
+// (NF: how many of the four the caller uses, from the first on -- the rest of the row is not fetched and v, d keep what they held)
+template <bool DERIV, int NF = 4>
 __device__ __forceinline__ int f3_eval(const double *rows, const Feat3Leg &lg, double x, double (&v)[4], double (&d)[4]) {
     const int hi = lg.nk - 5;
     int iv = 3 + (int)((x - lg.t0) * lg.inv_h);
     iv = iv < 3 ? 3 : (iv > hi ? hi : iv);
-    F3Pair kn, cf[8];
+    F3Pair kn, cf[2 * NF];
     auto load_row = [&](int i) {
 #if F3_ROWS_GLOBAL
         F3GlobalPairs q = (F3GlobalPairs)(const F3Pair *)(rows + (size_t)(lg.row0 + i - 3) * 18);
 #else
         F3LdsPairs q = (F3LdsPairs)(const F3Pair *)(rows + (size_t)(lg.row0 + i - 3) * 18);
 #endif
-        F3Pair t0 = q[0], t[8];
+        F3Pair t0 = q[0], t[2 * NF];
 #pragma unroll
-        for (int e = 0; e < 8; e++) t[e] = q[1 + e];
+        for (int e = 0; e < 2 * NF; e++) t[e] = q[1 + e];
         kn = t0;
 #pragma unroll
-        for (int e = 0; e < 8; e++) cf[e] = t[e];
-        __builtin_amdgcn_sched_group_barrier(F3_ROWS_GLOBAL ? 0x020 : 0x100, 9, 0);
+        for (int e = 0; e < 2 * NF; e++) cf[e] = t[e];
+        __builtin_amdgcn_sched_group_barrier(F3_ROWS_GLOBAL ? 0x020 : 0x100, 1 + 2 * NF, 0);
     };
     load_row(iv);
     if (__builtin_expect(x > kn.y && iv < hi, 0)) {
@@ -114,7 +117,7 @@ __device__ __forceinline__ int f3_eval(const double *rows, const Feat3Leg &lg, d
     }
     const double u = x - kn.x;
 #pragma unroll
-    for (int fq = 0; fq < 4; fq++) {
+    for (int fq = 0; fq < NF; fq++) {
         const double c0 = cf[2 * fq].x, c1 = cf[2 * fq].y, c2 = cf[2 * fq + 1].x, c3 = cf[2 * fq + 1].y;
         double pv = fma(c3, u, c2), pd = fma(c3, u, pv);
         pv = fma(pv, u, c1); pd = fma(pd, u, pv);
@@ -136,6 +139,9 @@ __global__ void __launch_bounds__(WPB * WAVE, (NR == 1 ? 4 : F3_WIDE_MINW))
 k_featurize3(Feat3Args A) {
     typedef F3Cfg<EF, NR> Cfg;
     constexpr int RS_C = Cfg::RS_C, RS_N = Cfg::RS_N, NREC = Cfg::NREC, PS = Cfg::PS, EFP = Cfg::EFP;
+    // functions of a centre-leg evaluation that anything reads: a three-row window has no place for the fourth (the T table
+    // stops at EF rows, stage 1 reads a record's bond values at p_lane < EF)
+    constexpr int NFP = EF == 3 ? 3 : 4;
     extern __shared__ __align__(16) unsigned char smem[];
     const BasisDev *B = A.B;
     // (cap: what the LDS arrays are laid out for -- the longest list this instance serves; ent_stride: entries per atom in the
@@ -164,7 +170,7 @@ k_featurize3(Feat3Args A) {
     double *ox = wd, *oy = ox + cap, *oz = oy + cap, *orr = oz + cap, *oir = orr + cap;
     double *tq = wd + list_d;                                         // [cap][EF][4]: T_f = (Tx Ty Tz T3) of every own bond
     double *stage = tq + tq_d;
-    double *zq = stage + (Cfg::STAGE - 4);                            // a quad of zeros
+    double *zq = stage + (Cfg::STAGE - 4);                            // a quad of zeros (read by the wide windows only)
     int *oparent = wi, *oshift = wi + cap, *noff = wi + 2 * cap, *nbase = noff + cap + 1, *so = nbase + cap + 1;
     int *osbp = so + (UF3_MAX_SPECIES + 2);                           // first window row of every own bond
     int *ospoff = osbp + cap;                     // [cap][S + 1] (last: the only array whose place depends on S)
@@ -182,7 +188,7 @@ k_featurize3(Feat3Args A) {
     // serves NR positions, 32 apart --------------------------------------------------------------------------------------
     const int ext_p = A.ext_p, ext_n = A.ext_n, lo_n = A.lo_n, lo_p = A.lo_p, npos = ext_p * ext_n;
     const int half = lane >> 5;
-    int p_lane[NR], n_lane[NR], qn_lane[NR], n32_lane[NR];
+    int p_lane[NR], n_lane[NR], qn_lane[NR], n32_lane[NR], n32h_lane[NR];
     const int pr_rows = A.pr_rows;
 #pragma unroll
     for (int r = 0; r < NR; r++) {
@@ -193,6 +199,7 @@ k_featurize3(Feat3Args A) {
         n_lane[r] = on ? (lane & 31) - pl * ext_n : -(1 << 20);            // (idle positions always read zeros)
         qn_lane[r] = on ? n_lane[r] : RS_C - 1;                            // (... a centre-role record's zero padding)
         n32_lane[r] = n_lane[r] * 32;
+        n32h_lane[r] = n32_lane[r] + 16 * half;
     }
     (void)npos;
     const int sbn_max = ext_n > 4 ? ext_n - 4 : 0, sbp_max = ext_p > 4 ? ext_p - 4 : 0;
@@ -253,7 +260,7 @@ k_featurize3(Feat3Args A) {
             double v[4] = {0, 0, 0, 0}, d[4] = {0, 0, 0, 0};
             int sbp = 0;
             if (r > leg_p.t0 && r < leg_p.tlast && !UF3_SKIP(32)) {
-                const int iv = f3_eval<true>(rows, leg_p, r, v, d);
+                const int iv = f3_eval<true, NFP>(rows, leg_p, r, v, d);
                 sbp = max(0, min(sbp_max, iv - 3 - lo_p));
             }
             if (EF > 4) osbp[e] = sbp;
@@ -434,6 +441,16 @@ k_featurize3(Feat3Args A) {
                 }
                 total_n = __builtin_amdgcn_readfirstlane(total_n);
                 if (lane == 0) noff[ncen] = total_n;
+                if (NR == 1) {
+                    // the records' pads, which stage 1 reads as zeros: the centre role's records and the fold's dump lie over them,
+                    // the record stores below never touch them -- once per role
+                    static_assert(NR != 1 || RS_N - EFP - 16 == 2, "a neighbour-role record ends in one 16-byte pad");
+                    static_assert(NR != 1 || EFP * 8 + 128 + 16 <= RS_N * 8, "the clamped offset (128) must stay inside the record");
+                    // (the zero is made here: as a loop invariant the compiler kept four registers of zeros and spilled them)
+                    double z;
+                    asm volatile("v_mov_b64 %0, 0" : "=v"(z));
+                    if (lane < NREC) *(double2 *)(stage + (size_t)lane * RS_N + EFP + 16) = double2{z, z};
+                }
                 wave_sync();
                 for (int p0 = 0; p0 < total_n; p0 += WAVE) {
                     const int q = p0 + lane;
@@ -456,7 +473,7 @@ k_featurize3(Feat3Args A) {
                         if (valid && !UF3_SKIP(64)) {
                             const double in = fast_rcp(rn);
                             a3[0] = ex * in; a3[1] = ey * in; a3[2] = ez * in;
-                            const int ivp = f3_eval<false>(rows, leg_p, rk, pv, dum);
+                            const int ivp = f3_eval<false, NFP>(rows, leg_p, rk, pv, dum);
                             sbp = max(0, min(sbp_max, ivp - 3 - lo_p));
                             const int iv = f3_eval<true>(rows, leg_n, rn, bn, bd);
                             sbn = max(0, min(sbn_max, iv - 3 - lo_n));
@@ -527,9 +544,17 @@ k_featurize3(Feat3Args A) {
                                     F3Pair tt[CNT];
 #pragma unroll
                                     for (int i = 0; i < CNT; i++) {
-                                        const unsigned off_n = (unsigned)(n32_lane[r] - sb[i]);        // 32 (n - first slot)
-                                        const char *qa = (const char *)(rp + i * RS_N + EFP + 2 * half) + off_n;
-                                        qa = off_n < 128u ? qa : (const char *)zq;
+                                        const char *qa;
+                                        if (NR == 1) {
+                                            // 32 (n - first slot) + 16 half inside the record's four quads; everything else -- below the
+                                            // window (wraps), above it, idle positions -- lands on the record's own pad of zeros
+                                            const unsigned off = min((unsigned)(n32h_lane[r] - sb[i]), 128u);
+                                            qa = (const char *)(rp + i * RS_N + EFP) + off;
+                                        } else {
+                                            const unsigned off_n = (unsigned)(n32_lane[r] - sb[i]);    // 32 (n - first slot)
+                                            qa = (const char *)(rp + i * RS_N + EFP + 2 * half) + off_n;
+                                            qa = off_n < 128u ? qa : (const char *)zq;
+                                        }
                                         bq[i] = ((F3LdsDoubles)rp)[i * RS_N + p_lane[r]];
                                         tt[i] = *(F3LdsPairs)(const F3Pair *)qa;
                                     }
