@@ -2,6 +2,7 @@
 // contexts, device-resident basis tables, per-call frame geometry, kernel launches.
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <functional>
 #include <cmath>
 #include <cstdio>
@@ -10,6 +11,8 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 #include <thread>
 
@@ -150,8 +153,6 @@ struct uf3_ctx {
              fx;                        // uf3_site_terms / uf3_heat_flux / uf3_site_rows / uf3_site_grade: theirs, the site records
                                         // and the host staging
     Buf site_rows_ws, site_off;         // uf3_site_grade: the fall-back's chunk of rows (bounded) | the caller's frame offsets
-    bool site_grade_lds_set = false;    // k_site_grade may take SG_LDS_BUDGET of dynamic LDS
-    bool site_rows_lds_set = false;     // k_site_rows likewise (SITE_ROWS_LDS)
     std::vector<char> ph_stage;         // host image of ph_ws (kept alive behind the asynchronous copy)
     int n3_cap = 0, cand_cap = 0;
     size_t bin_cnt_clean = 0;        // ints of bin_cnt known to be zero (k_bin_fill leaves the counts it used at zero)
@@ -340,6 +341,58 @@ extern "C" const char *uf3_last_error(const uf3_ctx *ctx) { return ctx ? ctx->er
 #define UF3_BUILD_ID "unknown"
 #endif
 extern "C" const char *uf3_build_id(void) { return UF3_BUILD_ID; }
+
+// ------------------------------------------------------------------------------ launch helpers
+// More than the default 64 KB of dynamic LDS has to be asked for, and the answer belongs to the kernel instance on a device, not
+// to a context or a thread: one process-wide high-water mark per instance and device that only grows -- ADVICE round 5.  Every
+// launch whose dynamic LDS can pass 64 KB asks here, nowhere else.  Within the mark no lock is taken; raising it takes a mutex.
+template <auto Kernel>
+static hipError_t lds_opt_in(int device, size_t lds) {
+    static std::mutex mu;
+    static std::atomic<size_t> have[64];
+    std::atomic<size_t> &hv = have[device & 63];
+    if (lds <= hv.load(std::memory_order_acquire)) return hipSuccess;
+    std::lock_guard<std::mutex> lk(mu);
+    if (lds > hv.load(std::memory_order_relaxed)) {
+        hipError_t e = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        hv.store(lds, std::memory_order_release);
+    }
+    return hipSuccess;
+}
+// ... and the launch behind it, on the context's stream
+template <auto Kernel, typename... Args>
+static hipError_t launch_lds(const uf3_ctx *c, dim3 grid, dim3 block, size_t lds, const Args &...args) {
+    hipError_t e = lds_opt_in<Kernel>(c->device, lds);
+    if (e == hipSuccess) hipLaunchKernelGGL(Kernel, grid, block, lds, c->stream, args...);
+    return e;
+}
+
+// Run-time values as template arguments: f is a generic lambda that takes the value as a std::integral_constant and returns a
+// status.  f is instantiated for every value offered, so a caller offers only the values that have a kernel instance (or
+// discards the others with `if constexpr`): the library holds the instances the dispatch names and no others.
+template <typename F>
+static int with_bool(bool v, F &&f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+template <int... Is, typename F>
+static int with_int(int v, std::integer_sequence<int, Is...>, F &&f) {      // (the last value is the default arm, as in a switch)
+    constexpr int vals[] = {Is...}, last = vals[sizeof...(Is) - 1];
+    int rc = UF3_OK;
+    (void)(((v == Is || Is == last) && ((rc = f(std::integral_constant<int, Is>{})), true)) || ...);
+    return rc;
+}
+
+// The shape the featurizer's three stages (k_featurize, k_featurize3, k_virial_rows) share: workgroups of WPB waves, each walking a
+// contiguous run of atoms (keeps the shared energy row on one frame); many more workgroups than resident slots -- 24 per slot
+// (measured: 2 per slot 3400 frames/s, 16-48 per slot 3640, finer again slower): the tail of the launch is short and concurrent
+// workgroups work on nearby atoms
+struct AtomGrid { int atoms_per_block, n_blocks; unsigned grid; };      // grid: n_blocks in whole rounds over the 8 XCDs
+static AtomGrid atom_grid(int natoms, size_t lds, int n_cu) {
+    const int per_cu = std::max(1, std::min(8, (int)((size_t)(160 * 1024) / lds)));
+    int n_blocks = std::min((natoms + WPB - 1) / WPB, n_cu * per_cu * 24);
+    const int apb = ((natoms + n_blocks - 1) / n_blocks + WPB - 1) / WPB * WPB;
+    n_blocks = (natoms + apb - 1) / apb;
+    return {apb, n_blocks, (unsigned)((n_blocks + 7) / 8 * 8)};      // (surplus workgroups find no atoms)
+}
 
 // the featurizer's switches, re-read on every call (uf3_env is a look-up in the cached UF3_* entries; tests and A/B runs flip
 // them between calls on one shared context -- ADVICE round 5)
@@ -1481,12 +1534,15 @@ static int prepare(uf3_basis *b, const uf3_frames *fr, const double *d_pos, cons
 static int ensure_frag(uf3_ctx *c);
 
 // LDS bytes of one featurizer workgroup; must mirror the carve at the top of k_featurize
-static size_t feat_lds_bytes(int F, int S, int cap, int cand_cap, bool want_e, size_t n_recs, int mode, int dense_stage,
-                             int dense_nrec, int n_pair_cols) {
+// (FeatShape: what a call's launches have in common -- features, species, list and candidate capacities, the energy row in LDS,
+// pair columns; the knot records in LDS, the mode and its staging area differ from launch to launch)
+struct FeatShape { int F, S, cap, cand_cap; bool e_lds; int n_pair_cols; };
+static size_t feat_lds_bytes(const FeatShape &sh, size_t n_recs, int mode, int dense_stage) {
     const bool dense = mode >= 6;
-    if (mode == 0) F = S + n_pair_cols;            // (the pair launch's energy row: one-body + pair columns)
-    size_t e_d = want_e ? (size_t)F + (F & 1) : 0;
-    size_t cand_d = (size_t)cand_cap * CAND_STRIDE;
+    const int S = sh.S, cap = sh.cap, n_pair_cols = sh.n_pair_cols;
+    const int F = mode == 0 ? S + n_pair_cols : sh.F;            // (the pair launch's energy row: one-body + pair columns)
+    size_t e_d = sh.e_lds ? (size_t)F + (F & 1) : 0;
+    size_t cand_d = (size_t)sh.cand_cap * CAND_STRIDE;
     size_t pair_buf_d = std::max(4 * (size_t)n_pair_cols, (3 * (size_t)cap + 1) / 2 + 2);
     size_t stage_d = mode == 0 ? cand_d + pair_buf_d
                      : (dense ? (size_t)dense_stage : (size_t)NSTAGE * ITEM_STRIDE);
@@ -1501,19 +1557,18 @@ static size_t feat_lds_bytes(int F, int S, int cap, int cand_cap, bool want_e, s
 
 // LDS footprint of k_featurize3 at list capacity cap (uf3_feat3.h): grows by ~168 B (3-row windows) to ~264 B (6-row windows)
 // per list entry and wave -- faster than the launches it replaces, so uf3_featurize_dev asks BEFORE it chooses the launch
-static void feat3_shape(const uf3_basis *b, int &ep, int &stage, int &nrec) {
+static void feat3_shape(const uf3_basis *b, int &ep, int &stage) {      // (the records' headers travel in registers: uf3_feat3.h)
     ep = std::max(3, b->f3_ext_p);
     switch (ep) {
-        case 3: stage = F3Cfg<3, 1>::STAGE; nrec = F3Cfg<3, 1>::NREC; break;
-        case 4: stage = F3Cfg<4, 2>::STAGE; nrec = F3Cfg<4, 2>::NREC; break;
-        case 5: stage = F3Cfg<5, 3>::STAGE; nrec = F3Cfg<5, 3>::NREC; break;
-        default: stage = F3Cfg<6, 3>::STAGE; nrec = F3Cfg<6, 3>::NREC; break;
+        case 3: stage = F3Cfg<3, 1>::STAGE; break;
+        case 4: stage = F3Cfg<4, 2>::STAGE; break;
+        case 5: stage = F3Cfg<5, 3>::STAGE; break;
+        default: stage = F3Cfg<6, 3>::STAGE; break;
     }
 }
 static size_t feat3_lds_bytes(const uf3_basis *b, int cap, bool e_lds) {
-    int ep, stage, nrec;
-    feat3_shape(b, ep, stage, nrec);
-    (void)nrec;                  // (the records' headers travel in registers: uf3_feat3.h)
+    int ep, stage;
+    feat3_shape(b, ep, stage);
     const int F = b->host.F, S = b->host.S;
     const size_t e_d = e_lds ? (size_t)F + (F & 1) : 0, rows_d = (size_t)b->n_f3rows * 18;
     const size_t list_d = 5 * (size_t)cap + ((5 * cap) & 1), tq_d = (size_t)cap * ep * 4, stage_d = (size_t)stage;
@@ -1563,6 +1618,224 @@ static size_t virial_lds_bytes(int cap, int n_pair_cols, int mode) {
 // uncovered.  Past that every add goes straight to HBM -- the e_direct rule (48 KB for the one energy row) with its threshold
 // moved to (this limit - the launch's other LDS) / 6 per row.
 #define UF3_VROWS_LDS (((size_t)160 * 1024 - 1024) / 2)
+
+// Which instances of the featurizer's and the evaluator's kernels the library holds -- the dispatch below (launch_featurize,
+// feat3_stage, virial_rows_stage, eval_impl) names exactly these:
+//   k_featurize<WANT_E, WANT_F, RECS_LDS, MODE, IMG>  WANT_E or WANT_F, modes 0 .. 9; modes 10 and 11 (mode 7 with grouped windows
+//       only, mode 9 banded only) for force launches only.  IMG launches (the image-range rule) are force launches of modes
+//       1 .. 9 and carry the knot records in HBM only
+//   k_featurize3<WANT_E, EF, NR, CAP>  (EF, NR) = (3, 1), (4, 2), (5, 3), (6, 3); the list capacity at run time (CAP 0) or 16 as a
+//       constant, 24 and 32 for EF = 3 only
+//   k_virial_rows<MODE>  modes 0 .. 5
+//   k_eval<false, VIR, CAP, MD, TAB, CW, WIN>  CAP 0 or 16; CW and WIN are TAB instances, and CW exists on the MD route only
+static int launch_featurize(uf3_ctx *c, bool want_e, bool want_f, bool recs_lds, int launch_mode, bool img, unsigned grid,
+                            size_t lds, const FeatArgs &A) {
+    auto go = [&](auto E, auto Fo, auto R, auto M, auto I) {
+        HIPCHK(c, (launch_lds<k_featurize<E, Fo, R, M, I>>(c, dim3(grid), dim3(WPB * WAVE), lds, A)));
+        return (int)UF3_OK;
+    };
+    constexpr std::true_type yes{}; constexpr std::false_type no{};
+    if (img && launch_mode != 0)         // (the pair launch has no image-range variant)
+        return with_int(launch_mode, std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9>{}, [&](auto M) {
+            return with_bool(want_e, [&](auto E) { return go(E, yes, no, M, yes); }); });
+    if (launch_mode >= 10)
+        return with_int(launch_mode, std::integer_sequence<int, 10, 11>{}, [&](auto M) {
+            return with_bool(want_e, [&](auto E) { return with_bool(recs_lds, [&](auto R) { return go(E, yes, R, M, no); }); }); });
+    return with_int(launch_mode, std::make_integer_sequence<int, 10>{}, [&](auto M) {
+        return with_bool(recs_lds, [&](auto R) {
+            if (!want_f) return go(yes, no, R, M, no);
+            return with_bool(want_e, [&](auto E) { return go(E, yes, R, M, no); }); }); });
+}
+
+// The plan of one k_featurize launch: the instance, what of the tables goes to LDS, the bytes.  Modes that are not dense leave
+// the dense fields and dsrc_lds as the launch before left them in A (their kernels do not read them).
+struct FeatPlan {
+    int launch_mode;                    // the instance's MODE
+    int trio_rec_lo;                    // first knot record (window row) the launch reads ...
+    size_t n_rec_mode;                  // ... and how many of them
+    bool recs_lds;                      // those in LDS
+    size_t lds, lds_plain, lds_recs;    // dynamic LDS of the launch | without and with the records, where both were looked at
+    size_t lds_extra;                   // the source tables' part of it
+    int dense_nrec, dense_stage, dsrc_lds, gsrc_lds;      // FeatArgs' fields of these names
+};
+static FeatPlan feat_plan(const uf3_basis *b, const FeatShape &sh, const FeatArgs &A, int mode, bool want_f, bool img_launch,
+                          bool dsrc_ok) {
+    FeatPlan p = {};
+    const bool dense_mode = mode >= 6;
+    // knot records go to LDS when the block then still reaches the occupancy its registers allow
+    // (10: mode 7 with grouped windows only -- the force launches of a basis whose mode-7 blocks are all grouped)
+    p.launch_mode = (mode == 7 && want_f && b->all_grouped7 && !img_launch) ? 10
+                    : ((mode == 9 && want_f && b->all_banded9 && !img_launch) ? 11 : mode);
+    // (a grouped-only launch reads the window rows, not the knot records of the legs)
+    p.trio_rec_lo = (int)(p.launch_mode == 10 ? b->wrow_lo : b->trio_rec_lo);
+    p.n_rec_mode = mode == 0 ? b->n_pair_recs : b->n_recs - (size_t)p.trio_rec_lo;
+    p.dense_nrec = A.dense_nrec; p.dense_stage = A.dense_stage;
+    p.dsrc_lds = dense_mode ? (dsrc_ok && !(mode == 7 && want_f && b->all_grouped7)) : A.dsrc_lds;
+    const bool gsrc_wanted = mode == 7 && want_f && b->dense_grouped[7] && b->n_gsrc > 0 && b->n_gsrc * 2 <= 4096;
+    const size_t gsrc_bytes = gsrc_wanted ? b->n_gsrc * 2 : 0;
+    p.gsrc_lds = gsrc_wanted;
+    p.lds_extra = ((dense_mode && p.dsrc_lds) ? sizeof(int) * b->n_dsrc : 0) + gsrc_bytes;
+    const bool recs_allowed = !(img_launch && mode != 0);
+    bool found = false;
+    if (dense_mode) {
+        const int stride = want_f ? b->dense_stride_f[mode] : b->dense_stride[mode];
+        // (grouped windows fold from three 16 x 16 tiles side by side: 768 doubles)
+        const int dump = want_f && b->dense_grouped[mode] ? std::max(768, b->dense_dump[mode]) : b->dense_dump[mode];
+        const bool grouped = want_f && b->dense_grouped[mode];
+        const int nrec_max = std::max(4, std::min(DENSE_NREC, 1200 / stride));
+        // (+ the padding record of an odd pass; grouped windows: one per odd group, at most 2 + (nr odd))
+        auto stage_for = [&](int nr) { return std::max(dump, (nr + (nr & 1) + (grouped ? 2 : 0)) * stride); };
+        // (21 records = 63 staging lanes = one walk step: a block of <= 63 items is one step and three passes)
+        p.dense_nrec = nrec_max; p.dense_stage = stage_for(nrec_max);
+        if (mode <= 7) {
+            // records per staging pass: as many as the stage allows; fewer (smaller stage) if that lets a third
+            // workgroup onto the CU -- the kernel is latency-bound.  Three workgroups per CU need <= 52 KB each
+            // (LDS is granted in coarse granules: 53 KB did not fit).  Candidates in order of preference: the
+            // knot records / window rows in LDS first, then more records per pass
+            const int tries[3] = {nrec_max, std::min(nrec_max, 20), std::min(nrec_max, 15)};
+            const size_t budget = (WPB == 4 ? 52 : 13 * WPB) * 1024;      // (12 waves per CU: 3 x 4 or 2 x 6)
+            const bool dsrc_allowed = p.dsrc_lds;
+            for (int q = 0; q < 12 && !found; q++) {
+                // (the records / window rows in LDS first: a staging lane reads eleven 16-byte pieces of them per pass)
+                const int nr = tries[(q % 6) / 2];
+                const bool with_recs = q < 6, with_dsrc = (q & 1) == 0;
+                if ((with_recs && !recs_allowed) || (with_dsrc && !dsrc_allowed)) continue;
+                size_t need = feat_lds_bytes(sh, with_recs ? p.n_rec_mode : 0, mode, stage_for(nr)) +
+                              (with_dsrc ? sizeof(int) * b->n_dsrc : 0) + gsrc_bytes;
+                if (need <= budget) {
+                    found = true; p.recs_lds = with_recs; p.lds = p.lds_recs = need;
+                    p.dense_nrec = nr; p.dense_stage = stage_for(nr); p.dsrc_lds = with_dsrc;
+                }
+            }
+        }
+    }
+    if (!found) {
+        p.lds_plain = feat_lds_bytes(sh, 0, mode, p.dense_stage) + p.lds_extra;
+        p.lds_recs = feat_lds_bytes(sh, p.n_rec_mode, mode, p.dense_stage) + p.lds_extra;
+        const size_t lds_target = (160 * 1024 - 1024) / (mode == 0 ? 4 : 2);
+        p.recs_lds = p.lds_recs <= lds_target && recs_allowed;
+        p.lds = p.recs_lds ? p.lds_recs : p.lds_plain;
+    }
+    return p;
+}
+
+// Stage 2, 3-body force rows by bond factorisation: one k_featurize3 launch (or two, of which one leaves at once) for all trio
+// blocks, behind the pair launch that built the lists of A at capacity `cap`
+static int feat3_stage(uf3_basis *b, const FeatArgs &A, int cap) {
+    uf3_ctx *c = b->ctx;
+    const bool e_lds = A.x_e && !A.e_direct;
+    Feat3Args G;
+    G.B = b->dev; G.trios = b->d_trios; G.rows = b->d_f3rows; G.n_rows = b->n_f3rows;
+    G.fsrc = b->d_f3src; G.trio_fsrc = b->d_f3off; G.n_fsrc = b->n_f3src;
+    G.leg_p = b->f3_leg_p; G.leg_n = b->f3_leg_n;
+    G.lo_p = b->f3_lo_p; G.ext_p = b->f3_ext_p; G.lo_n = b->f3_lo_n; G.ext_n = b->f3_ext_n;
+    G.pr_rows = std::min(b->f3_ext_p, 32 / b->f3_ext_n);
+    G.geoms = A.geoms; G.frame_of = A.frame_of; G.n3 = A.n3; G.pos = A.pos; G.spec = A.spec;
+    G.x_e = A.x_e; G.x_f = A.x_f; G.ld = A.ld; G.natoms = A.natoms; G.e_direct = A.e_direct; G.skip = A.skip;
+    G.sel = A.n3_seen; G.sel_mode = 0; G.sel_cap = 16;
+    const int ep = std::max(3, b->f3_ext_p);                    // (the window's rows, as feat3_shape has them)
+    // one launch laid out for lists of up to `lcap` entries (the batch's list array keeps the context's capacity as
+    // its stride); sel_mode: see Feat3Args
+    auto launch_f3 = [&](int lcap, int sel_mode) -> int {
+        G.sel_mode = sel_mode;
+        const size_t lds = feat3_lds_bytes(b, lcap, e_lds);      // (<= UF3_LDS_LIMIT: checked where feat3 was decided)
+        const AtomGrid g = atom_grid(G.natoms, lds, c->n_cu);
+        G.atoms_per_block = g.atoms_per_block;
+        if (c->env_debug_lds)
+            fprintf(stderr, "uf3 featurize3: lds %zu B, cap %d (lists %d apart), selection %d, blocks %u x %d atoms, window %d x %d, %d round(s)\n",
+                    lds, lcap, cap, sel_mode, g.grid, G.atoms_per_block, G.ext_p, G.ext_n, b->f3_nr);
+        return with_bool(A.x_e != nullptr, [&](auto E) {
+        return with_int(ep, std::integer_sequence<int, 3, 4, 5, 6>{}, [&](auto EF) {
+        return with_int(lcap, std::integer_sequence<int, 16, 24, 32, 0>{}, [&](auto LC) {
+            // the list capacity as a constant where an instance has it: 16, and (the default trims) 24 and 32 -- fcc and denser
+            // cells; at run time (0) otherwise
+            constexpr int NR = EF == 3 ? 1 : (EF == 4 ? 2 : 3), CAP = (LC == 16 || EF == 3) ? LC : 0;
+            HIPCHK(c, (launch_lds<k_featurize3<E, EF, NR, CAP>>(c, dim3(g.grid), dim3(WPB * WAVE), lds, G)));
+            return (int)UF3_OK;
+        }); }); });
+    };
+    // The lists of this batch were built just now at the context's capacity -- an estimate on a context's first call,
+    // what the densest batch so far needed later on -- but the instance that serves most cells is the one laid out for 16
+    // entries (4 workgroups per CU, LDS offsets as immediates).  Which one applies is known on the device only: the list
+    // build leaves the batch's longest list in flags[7], and two launches follow of which one leaves at once.
+    if (A.n3_seen && cap > 16) {
+        const int r1 = launch_f3(16, 1);
+        return r1 ? r1 : launch_f3(cap, 2);
+    }
+    return launch_f3(cap, 0);
+}
+
+// Stage 3, virial rows: a k_virial_rows launch per mode of the basis (3-body modes: where lists exist) into d_xv
+static int virial_rows_stage(uf3_basis *b, FeatArgs &A, double *d_xv, bool lists) {
+    uf3_ctx *c = b->ctx;
+    const int F = b->host.F, S = b->host.S;
+    for (int vm = 0; vm <= 5; vm++) {
+        if (vm && !((b->vmodes & (1 << vm)) && lists && b->host.T > 0)) continue;
+        const int fe = vm == 0 ? A.n_pair_cols : F - S - A.n_pair_cols;
+        const size_t other = virial_lds_bytes(vm == 0 ? 1 : A.n3.cap, A.n_pair_cols, vm);
+        const size_t rows = 6 * ((size_t)fe + (fe & 1)) * 8;
+        const int v_direct = rows + other > UF3_VROWS_LDS ? 1 : 0;
+        const size_t lds = other + (v_direct ? 0 : rows);
+        if (lds > UF3_LDS_LIMIT) return fail(c, UF3_EOVERFLOW, "virial rows: LDS footprint exceeds 160 KB (neighbour count too large)");
+        const AtomGrid g = atom_grid(A.natoms, lds, c->n_cu);
+        A.atoms_per_block = g.atoms_per_block;
+        if (c->env_debug_lds)
+            fprintf(stderr, "uf3 virial rows mode %d: lds %zu B, rows in %s (6 x %d columns = %zu B + %zu B other, limit %zu B), "
+                    "cap %d, blocks %d x %d atoms\n", vm, lds, v_direct ? "hbm" : "lds", fe, rows, other, (size_t)UF3_VROWS_LDS,
+                    A.n3.cap, g.n_blocks, g.atoms_per_block);
+        int rc = with_int(vm, std::make_integer_sequence<int, 6>{}, [&](auto M) {
+            HIPCHK(c, (launch_lds<k_virial_rows<M>>(c, dim3(g.grid), dim3(WPB * WAVE), lds, A, d_xv, v_direct)));
+            return (int)UF3_OK;
+        });
+        if (rc) return rc;
+    }
+    return UF3_OK;
+}
+
+// The verdict deferred (capacities known from earlier calls: do not wait): the status words follow the launches into a pinned
+// slot beside `what`, the call's capacities and routes; the context's next call / uf3_ctx_synchronize looks (UF3_ERETRY on overflow)
+static int featurize_defer(uf3_ctx *c, uf3_ctx::Pending what) {
+    int slot = -1;
+    for (int q = 0; q < uf3_ctx::N_PENDING && slot < 0; q++)
+        if (!c->pending_chk[(c->pending_head + q) % uf3_ctx::N_PENDING].live) slot = (c->pending_head + q) % uf3_ctx::N_PENDING;
+    if (slot < 0) {        // all slots in flight: wait for the oldest
+        int rcw = poll_pending(c, true);
+        if (rcw) return rcw;
+        slot = c->pending_head;
+    }
+    HIPCHK(c, c->pin_flags.ensure(sizeof(int) * 8 * uf3_ctx::N_PENDING));
+    uf3_ctx::Pending &pd = c->pending_chk[slot];
+    if (!pd.ev) HIPCHK(c, hipEventCreateWithFlags(&pd.ev, hipEventDisableTiming));
+    HIPCHK(c, hipMemcpyAsync((int *)c->pin_flags.p + 8 * slot, c->flags.p, 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(pd.ev, c->stream));
+    what.ev = pd.ev; what.live = true;
+    pd = what;
+    c->pending_head = (slot + 1) % uf3_ctx::N_PENDING;
+    return UF3_OK;
+}
+
+// The verdict at once: wait for the status words and adapt the context's capacities and routes to them.  redo (false on entry)
+// becomes true where the call's launches have to be repeated with what the context has learnt
+static int featurize_adapt(uf3_ctx *c, const FeatArgs &A, bool has3, bool want_v, bool img_launch, int cap, bool &redo) {
+    const bool want_e = A.x_e != nullptr, want_f = A.x_f != nullptr;
+    int fl[8] = {0, 0, 0, 0, 0, 0, 0, 0};            // error flag, n3 need, candidate need, extension need, atoms far outside
+    HIPCHK(c, hipMemcpyAsync(fl, c->flags.p, sizeof(fl), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (fl[0]) return check_flags(c);
+    if (want_v && fl[4]) return fail(c, UF3_EINVAL, UF3_VIRIAL_OUTSIDE_MSG);
+    if (has3 && want_f && A.outside && fl[4] && !c->img_mode) { c->img_mode = true; redo = true; }
+    else if (img_launch && !fl[4]) c->img_mode = false;                 // (valid all the same) back to the ordinary launches
+    if (img_launch && fl[3] > c->n3x_cap) {              // (the extension lists of the image-range launches)
+        if (fl[3] > 248) return fail(c, UF3_EOVERFLOW, "extension neighbour lists of atoms far outside their cell exceed 248 entries");
+        c->n3x_cap = (fl[3] + 8 + 7) / 8 * 8; redo = true;
+    }
+    if (has3 && fl[1] > cap) { c->n3_cap = (fl[1] + 8 + 7) / 8 * 8; c->n3_tuned = true; redo = true; }
+    if (fl[2] > c->cand_cap) { c->cand_cap = (fl[2] + 16 + 7) / 8 * 8; redo = true; }
+    if (redo) return UF3_OK;
+    if (has3 && !c->n3_tuned) { int rc = n3_tune(c, A.n3, A.natoms); if (rc) return rc; }
+    if (want_e || want_f) c->cand_tuned = true;
+    return UF3_OK;
+}
 
 static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z,
                               double *d_xe, double *d_xf, int64_t ld, double *d_xv) {
@@ -1636,8 +1909,7 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
         if (want_v) HIPCHK(c, hipMemsetAsync(d_xv, 0, sizeof(double) * (size_t)P.n_frames * 6 * F, st));
         if (!P.flags_zeroed || attempt) HIPCHK(c, hipMemsetAsync(A.n3_need, 0, 2 * sizeof(int), st));       // n3_need, cand_need
         const bool img_launch = c->img_mode && has3 && want_f && A.outside;
-        const bool ext_lists = img_launch;
-        if (ext_lists) {
+        if (img_launch) {
             // extension lists for batches with atoms outside their cell (the kernel leaves at once otherwise); storage only
             // once a batch has asked for it (flags[3], through the same retry path as the other capacities)
             const int xcap = c->n3x_cap;
@@ -1654,8 +1926,9 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
         // behind the pair launch that builds the lists
         // (dense or long-range lists, past ~200 entries at the default trims and ~100 on the 6 x 12 windows, do not fit its
         // LDS layout: those calls keep the matrix-core / generic launches, which handled them before k_featurize3 existed)
+        FeatShape sh = {F, b->host.S, cap, A.cand_cap, want_e && !A.e_direct, A.n_pair_cols};
         const bool feat3 = b->feat3_ok && want_f && (has3 || old_n3) && !img_launch && cap <= 255 && !c->env_no_feat3 &&
-                           feat3_lds_bytes(b, cap, want_e && !A.e_direct) <= UF3_LDS_LIMIT;
+                           feat3_lds_bytes(b, cap, sh.e_lds) <= UF3_LDS_LIMIT;
         // (the pair launch below leaves the batch's longest 3-body list in flags[7] when k_featurize3 can use it: see there)
         A.n3_seen = nullptr;
         if (feat3 && has3 && cap > 16) {
@@ -1668,74 +1941,19 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
             for (int mode = 0; mode <= 9; mode++) {
                 if (!(b->modes & (1 << mode)) || !(want_e || want_f)) continue;
                 if (feat3 && mode >= 1) continue;
-                const bool dense_mode = mode >= 6;
-                // knot records go to LDS when the block then still reaches the occupancy its registers allow
-                // (10: mode 7 with grouped windows only -- the force launches of a basis whose mode-7 blocks are all grouped)
-                const int launch_mode = (mode == 7 && want_f && b->all_grouped7 && !img_launch) ? 10
-                                        : ((mode == 9 && want_f && b->all_banded9 && !img_launch) ? 11 : mode);
-                // (a grouped-only launch reads the window rows, not the knot records of the legs)
-                A.trio_rec_lo = (int)(launch_mode == 10 ? b->wrow_lo : b->trio_rec_lo);
-                size_t n_rec_mode = mode == 0 ? b->n_pair_recs : b->n_recs - (size_t)A.trio_rec_lo;
-                const int S = b->host.S;
-                const size_t cu_lds = 160 * 1024 - 1024;
-                if (dense_mode) A.dsrc_lds = dsrc_ok && !(mode == 7 && want_f && b->all_grouped7);
-                const bool gsrc_wanted = mode == 7 && want_f && b->dense_grouped[7] && b->n_gsrc > 0 && b->n_gsrc * 2 <= 4096;
-                const size_t gsrc_bytes = gsrc_wanted ? b->n_gsrc * 2 : 0;
-                A.gsrc_lds = gsrc_wanted;
-                size_t lds_extra = ((dense_mode && A.dsrc_lds) ? sizeof(int) * b->n_dsrc : 0) + gsrc_bytes;
-                bool recs_lds = false;
-                size_t lds = 0, lds_plain = 0, lds_recs = 0;
-                bool found = false;
-                if (dense_mode) {
-                    const int stride = want_f ? b->dense_stride_f[mode] : b->dense_stride[mode];
-                    // (grouped windows fold from three 16 x 16 tiles side by side: 768 doubles)
-                    const int dump = want_f && b->dense_grouped[mode] ? std::max(768, b->dense_dump[mode]) : b->dense_dump[mode];
-                    const bool grouped = want_f && b->dense_grouped[mode];
-                    const int nrec_max = std::max(4, std::min(DENSE_NREC, 1200 / stride));
-                    // (+ the padding record of an odd pass; grouped windows: one per odd group, at most 2 + (nr odd))
-                    auto stage_for = [&](int nr) { return std::max(dump, (nr + (nr & 1) + (grouped ? 2 : 0)) * stride); };
-                    // (21 records = 63 staging lanes = one walk step: a block of <= 63 items is one step and three passes)
-                    A.dense_nrec = nrec_max; A.dense_stage = stage_for(nrec_max);
-                    if (mode <= 7) {
-                        // records per staging pass: as many as the stage allows; fewer (smaller stage) if that lets a third
-                        // workgroup onto the CU -- the kernel is latency-bound.  Three workgroups per CU need <= 52 KB each
-                        // (LDS is granted in coarse granules: 53 KB did not fit).  Candidates in order of preference: the
-                        // knot records / window rows in LDS first, then more records per pass
-                        const int tries[3] = {nrec_max, std::min(nrec_max, 20), std::min(nrec_max, 15)};
-                        const size_t budget = (WPB == 4 ? 52 : 13 * WPB) * 1024;      // (12 waves per CU: 3 x 4 or 2 x 6)
-                        const bool dsrc_allowed = A.dsrc_lds, recs_allowed = !(img_launch && mode != 0);
-                        for (int q = 0; q < 12 && !found; q++) {
-                            // (the records / window rows in LDS first: a staging lane reads eleven 16-byte pieces of them per pass)
-                            const int nr = tries[(q % 6) / 2];
-                            const bool with_recs = q < 6, with_dsrc = (q & 1) == 0;
-                            if ((with_recs && !recs_allowed) || (with_dsrc && !dsrc_allowed)) continue;
-                            size_t need = feat_lds_bytes(F, S, cap, A.cand_cap, want_e && !A.e_direct, with_recs ? n_rec_mode : 0, mode,
-                                                         stage_for(nr), nr, A.n_pair_cols) + (with_dsrc ? sizeof(int) * b->n_dsrc : 0) + gsrc_bytes;
-                            if (need <= budget) {
-                                found = true; recs_lds = with_recs; lds = lds_recs = need;
-                                A.dense_nrec = nr; A.dense_stage = stage_for(nr); A.dsrc_lds = with_dsrc;
-                            }
-                        }
-                    }
-                }
-                if (!found) {
-                    lds_plain = feat_lds_bytes(F, S, cap, A.cand_cap, want_e && !A.e_direct, 0, mode, A.dense_stage, A.dense_nrec, A.n_pair_cols) + lds_extra;
-                    lds_recs = feat_lds_bytes(F, S, cap, A.cand_cap, want_e && !A.e_direct, n_rec_mode, mode, A.dense_stage, A.dense_nrec, A.n_pair_cols) + lds_extra;
-                    const size_t lds_target = cu_lds / (mode == 0 ? 4 : 2);
-                    recs_lds = lds_recs <= lds_target && !(img_launch && mode != 0);
-                    lds = recs_lds ? lds_recs : lds_plain;
-                }
-                if (lds > UF3_LDS_LIMIT && mode == 0 && !c->cand_tuned && c->cand_cap > 64) {
+                FeatPlan pl = feat_plan(b, sh, A, mode, want_f, img_launch, dsrc_ok);
+                A.trio_rec_lo = pl.trio_rec_lo;
+                A.dense_nrec = pl.dense_nrec; A.dense_stage = pl.dense_stage; A.dsrc_lds = pl.dsrc_lds; A.gsrc_lds = pl.gsrc_lds;
+                if (pl.lds > UF3_LDS_LIMIT && mode == 0 && !c->cand_tuned && c->cand_cap > 64) {
                     // the candidate capacity is still the density ESTIMATE (60 % headroom): a dense frame must not fail on the
                     // guess -- take what fits, the overflow flag reports the true need and the call is repeated with it
-                    while (c->cand_cap > 64 && feat_lds_bytes(F, S, cap, c->cand_cap, want_e && !A.e_direct, recs_lds ? n_rec_mode : 0, 0,
-                                                              A.dense_stage, A.dense_nrec, A.n_pair_cols) + lds_extra > UF3_LDS_LIMIT)
-                        c->cand_cap = (c->cand_cap * 7 / 8 + 7) / 8 * 8;
+                    while (c->cand_cap > 64 && pl.lds > UF3_LDS_LIMIT) {
+                        sh.cand_cap = c->cand_cap = (c->cand_cap * 7 / 8 + 7) / 8 * 8;
+                        pl.lds = feat_lds_bytes(sh, pl.recs_lds ? pl.n_rec_mode : 0, 0, pl.dense_stage) + pl.lds_extra;
+                    }
                     A.cand_cap = c->cand_cap;
-                    lds = feat_lds_bytes(F, S, cap, A.cand_cap, want_e && !A.e_direct, recs_lds ? n_rec_mode : 0, 0, A.dense_stage,
-                                         A.dense_nrec, A.n_pair_cols) + lds_extra;
                 }
-                if (lds > UF3_LDS_LIMIT && !caps_reset) {
+                if (pl.lds > UF3_LDS_LIMIT && !caps_reset) {
                     // the capacities are grow-only memories of the densest batch this context has seen: a sparser batch on a wider
                     // basis must not fail on them -- back to this batch's own estimates, once, and the call starts over
                     const int est3 = has3 ? n3_cap_estimate(b, P.max_density) : 0, estc = cand_estimate();
@@ -1746,225 +1964,30 @@ static int featurize_dev_impl(uf3_basis *b, const uf3_frames *fr, const double *
                         break;
                     }
                 }
-                if (lds > UF3_LDS_LIMIT) return fail(c, UF3_EOVERFLOW, "featurizer LDS footprint exceeds 160 KB (F or neighbour count too large)");
-                // blocks of WPB waves, each walking a contiguous run of atoms (keeps the shared energy row on
-                // one frame); many more blocks than resident slots (measured: 2 per slot 3400 frames/s, 16-48 per slot
-                // 3640, finer again slower): the tail of the launch is short and concurrent blocks work on nearby atoms
-                int per_cu = std::max(1, std::min(8, (int)((size_t)(160 * 1024) / lds)));
-                int n_blocks = std::min((P.natoms + WPB - 1) / WPB, c->n_cu * per_cu * 24);
-                int apb = ((P.natoms + n_blocks - 1) / n_blocks + WPB - 1) / WPB * WPB;
-                n_blocks = (P.natoms + apb - 1) / apb;
-                A.atoms_per_block = apb;
+                if (pl.lds > UF3_LDS_LIMIT) return fail(c, UF3_EOVERFLOW, "featurizer LDS footprint exceeds 160 KB (F or neighbour count too large)");
+                const AtomGrid g = atom_grid(P.natoms, pl.lds, c->n_cu);
+                A.atoms_per_block = g.atoms_per_block;
                 if (uf3_env("UF3_DEBUG_LDS"))
                     fprintf(stderr, "uf3 featurize mode %d: lds %zu B (plain %zu, with recs %zu), recs_lds %d, cap %d, cand_cap %d, "
-                            "blocks %d x %d atoms, n_recs %zu, dense nrec %d stage %d\n", launch_mode, lds, lds_plain, lds_recs,
-                            (int)recs_lds, cap, A.cand_cap, n_blocks, apb, n_rec_mode, A.dense_nrec, A.dense_stage);
-#define UF3_GRID(n) (((n) + 7) / 8 * 8)      /* whole rounds over the XCDs (surplus workgroups find no atoms) */
-/* (the dynamic-LDS attribute belongs to the kernel instance on a device, not to a context or a thread: one process-wide, \
-   mutex-protected high-water mark per instance and device that only grows -- ADVICE round 5) */ \
-#define UF3_LAUNCH1(E, Fo, R, M, I)                                                                                   \
-    do {                                                                                                            \
-        {                                                                                                           \
-            static std::mutex mu; static size_t have[64] = {0};                                                     \
-            std::lock_guard<std::mutex> lk(mu);                                                                     \
-            size_t &hv = have[c->device & 63];                                                                      \
-            if (lds > hv) {                                                                                         \
-                HIPCHK(c, hipFuncSetAttribute((const void *)k_featurize<E, Fo, R, M, I>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-                hv = lds;                                                                                           \
-            }                                                                                                       \
-        }                                                                                                           \
-        hipLaunchKernelGGL((k_featurize<E, Fo, R, M, I>), dim3(UF3_GRID(n_blocks)), dim3(WPB * WAVE), lds, st, A);   \
-    } while (0)
-#define UF3_LAUNCH(M)                                                                                               \
-    do {                                                                                                            \
-        if (img_launch && M != 0) {   /* (the image-range variants exist with the knot records in HBM only) */       \
-            if (want_e) UF3_LAUNCH1(true, true, false, (M == 0 ? 1 : M), true); else UF3_LAUNCH1(false, true, false, (M == 0 ? 1 : M), true); \
-        }                                                                                                           \
-        else if (want_e && want_f) { if (recs_lds) UF3_LAUNCH1(true, true, true, M, false); else UF3_LAUNCH1(true, true, false, M, false); }   \
-        else if (want_f) { if (recs_lds) UF3_LAUNCH1(false, true, true, M, false); else UF3_LAUNCH1(false, true, false, M, false); }    \
-        else { if (recs_lds) UF3_LAUNCH1(true, false, true, M, false); else UF3_LAUNCH1(true, false, false, M, false); }               \
-    } while (0)
-                switch (launch_mode) {
-                    case 0: UF3_LAUNCH(0); break;
-                    case 1: UF3_LAUNCH(1); break;
-                    case 2: UF3_LAUNCH(2); break;
-                    case 3: UF3_LAUNCH(3); break;
-                    case 4: UF3_LAUNCH(4); break;
-                    case 5: UF3_LAUNCH(5); break;
-                    case 6: UF3_LAUNCH(6); break;
-                    case 7: UF3_LAUNCH(7); break;
-                    case 8: UF3_LAUNCH(8); break;
-                    case 10: if (want_e) { if (recs_lds) UF3_LAUNCH1(true, true, true, 10, false); else UF3_LAUNCH1(true, true, false, 10, false); }
-                             else { if (recs_lds) UF3_LAUNCH1(false, true, true, 10, false); else UF3_LAUNCH1(false, true, false, 10, false); }
-                             break;
-                    case 11: if (want_e) { if (recs_lds) UF3_LAUNCH1(true, true, true, 11, false); else UF3_LAUNCH1(true, true, false, 11, false); }
-                             else { if (recs_lds) UF3_LAUNCH1(false, true, true, 11, false); else UF3_LAUNCH1(false, true, false, 11, false); }
-                             break;
-                    default: UF3_LAUNCH(9); break;
-                }
-#undef UF3_LAUNCH
-#undef UF3_LAUNCH1
+                            "blocks %d x %d atoms, n_recs %zu, dense nrec %d stage %d\n", pl.launch_mode, pl.lds, pl.lds_plain, pl.lds_recs,
+                            (int)pl.recs_lds, cap, A.cand_cap, g.n_blocks, g.atoms_per_block, pl.n_rec_mode, A.dense_nrec, A.dense_stage);
+                rc = launch_featurize(c, want_e, want_f, pl.recs_lds, pl.launch_mode, img_launch, g.grid, pl.lds, A);
+                if (rc) return rc;
             }
-            if (feat3 && !restart) {
-                Feat3Args G;
-                G.B = b->dev; G.trios = b->d_trios; G.rows = b->d_f3rows; G.n_rows = b->n_f3rows;
-                G.fsrc = b->d_f3src; G.trio_fsrc = b->d_f3off; G.n_fsrc = b->n_f3src;
-                G.leg_p = b->f3_leg_p; G.leg_n = b->f3_leg_n;
-                G.lo_p = b->f3_lo_p; G.ext_p = b->f3_ext_p; G.lo_n = b->f3_lo_n; G.ext_n = b->f3_ext_n;
-                G.pr_rows = std::min(b->f3_ext_p, 32 / b->f3_ext_n);
-                G.geoms = P.geoms; G.frame_of = P.frame_of; G.n3 = A.n3; G.pos = d_pos; G.spec = P.spec;
-                G.x_e = d_xe; G.x_f = d_xf; G.ld = (int)ld; G.natoms = P.natoms; G.e_direct = A.e_direct; G.skip = A.skip;
-                G.sel = A.n3_seen; G.sel_mode = 0; G.sel_cap = 16;
-                int ep, stage, nrec;
-                feat3_shape(b, ep, stage, nrec);
-                (void)stage; (void)nrec;
-                const int nr = b->f3_nr;
-        /* (the dynamic-LDS attribute belongs to the kernel instance on a device: one process-wide high-water mark each) */   \
-#define UF3_F3_ATTR(KERNEL, lds)                                                                                           \
-    do {                                                                                                                   \
-        static std::mutex mu; static size_t have[64] = {0};                                                                \
-        std::lock_guard<std::mutex> lk(mu);                                                                                \
-        size_t &hv = have[c->device & 63];                                                                                 \
-        if ((lds) > hv) {                                                                                                  \
-            HIPCHK(c, hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds)));  \
-            hv = (lds);                                                                                                    \
-        }                                                                                                                  \
-    } while (0)
-#define UF3_F3_LAUNCH1(E, EFv, NRv, CAPv)                                                                                   \
-    do {                                                                                                                   \
-        UF3_F3_ATTR((k_featurize3<E, EFv, NRv, CAPv>), lds);                                                               \
-        hipLaunchKernelGGL((k_featurize3<E, EFv, NRv, CAPv>), dim3(grid), dim3(WPB * WAVE), lds, st, G);                    \
-    } while (0)
-#define UF3_F3_LAUNCH(E, EFv, NRv)                                                                                          \
-    do { if (lcap == 16) UF3_F3_LAUNCH1(E, EFv, NRv, 16); else UF3_F3_LAUNCH1(E, EFv, NRv, 0); } while (0)
-                // one launch laid out for lists of up to `lcap` entries (the batch's list array keeps the context's capacity as
-                // its stride); sel_mode: see Feat3Args
-                auto launch_f3 = [&](int lcap, int sel_mode) -> int {
-                    G.sel_mode = sel_mode;
-                    const size_t lds = feat3_lds_bytes(b, lcap, want_e && !A.e_direct);      // (<= UF3_LDS_LIMIT: checked where feat3 was decided)
-                    // the grid over all atoms: 24 workgroups per resident slot
-                    const int per_cu = std::max(1, std::min(8, (int)((size_t)(160 * 1024) / lds)));
-                    int n_blocks = std::min((G.natoms + WPB - 1) / WPB, c->n_cu * per_cu * 24);
-                    const int apb = ((G.natoms + n_blocks - 1) / n_blocks + WPB - 1) / WPB * WPB;
-                    n_blocks = (G.natoms + apb - 1) / apb;
-                    G.atoms_per_block = apb;
-                    const unsigned grid = (unsigned)((n_blocks + 7) / 8 * 8);
-                    if (c->env_debug_lds)
-                        fprintf(stderr, "uf3 featurize3: lds %zu B, cap %d (lists %d apart), selection %d, blocks %u x %d atoms, window %d x %d, %d round(s)\n",
-                                lds, lcap, cap, sel_mode, grid, G.atoms_per_block, G.ext_p, G.ext_n, nr);
-                    switch (ep) {
-                        case 3:      // (the default trims: the list capacity as a constant also at 24 and 32 -- fcc and denser cells)
-                            if (lcap == 24) { if (want_e) UF3_F3_LAUNCH1(true, 3, 1, 24); else UF3_F3_LAUNCH1(false, 3, 1, 24); }
-                            else if (lcap == 32) { if (want_e) UF3_F3_LAUNCH1(true, 3, 1, 32); else UF3_F3_LAUNCH1(false, 3, 1, 32); }
-                            else if (want_e) UF3_F3_LAUNCH(true, 3, 1); else UF3_F3_LAUNCH(false, 3, 1);
-                            break;
-                        case 4: if (want_e) UF3_F3_LAUNCH(true, 4, 2); else UF3_F3_LAUNCH(false, 4, 2); break;
-                        case 5: if (want_e) UF3_F3_LAUNCH(true, 5, 3); else UF3_F3_LAUNCH(false, 5, 3); break;
-                        default: if (want_e) UF3_F3_LAUNCH(true, 6, 3); else UF3_F3_LAUNCH(false, 6, 3); break;
-                    }
-                    return UF3_OK;
-                };
-                // The lists of this batch were built just now at the context's capacity -- an estimate on a context's first call,
-                // what the densest batch so far needed later on -- but the instance that serves most cells is the one laid out for 16
-                // entries (4 workgroups per CU, LDS offsets as immediates).  Which one applies is known on the device only: the list
-                // build leaves the batch's longest list in flags[7], and two launches follow of which one leaves at once.
-                if (A.n3_seen && cap > 16) {
-                    int r1 = launch_f3(16, 1);
-                    if (!r1) r1 = launch_f3(cap, 2);
-                    if (r1) return r1;
-                } else {
-                    int r1 = launch_f3(cap, 0);
-                    if (r1) return r1;
-                }
-#undef UF3_F3_LAUNCH
-#undef UF3_F3_LAUNCH1
-#undef UF3_F3_ATTR
-            }
-            if (want_v && !restart) {
-                const int S = b->host.S;
-                for (int vm = 0; vm <= 5; vm++) {
-                    if (vm && !((b->vmodes & (1 << vm)) && (has3 || old_n3) && b->host.T > 0)) continue;
-                    const int fe = vm == 0 ? A.n_pair_cols : F - S - A.n_pair_cols;
-                    const size_t other = virial_lds_bytes(vm == 0 ? 1 : A.n3.cap, A.n_pair_cols, vm);
-                    const size_t rows = 6 * ((size_t)fe + (fe & 1)) * 8;
-                    const int v_direct = rows + other > UF3_VROWS_LDS ? 1 : 0;
-                    const size_t lds = other + (v_direct ? 0 : rows);
-                    if (lds > UF3_LDS_LIMIT) return fail(c, UF3_EOVERFLOW, "virial rows: LDS footprint exceeds 160 KB (neighbour count too large)");
-                    const int per_cu = std::max(1, std::min(8, (int)((size_t)(160 * 1024) / lds)));
-                    int n_blocks = std::min((P.natoms + WPB - 1) / WPB, c->n_cu * per_cu * 24);
-                    const int apb = ((P.natoms + n_blocks - 1) / n_blocks + WPB - 1) / WPB * WPB;
-                    n_blocks = (P.natoms + apb - 1) / apb;
-                    A.atoms_per_block = apb;
-                    if (c->env_debug_lds)
-                        fprintf(stderr, "uf3 virial rows mode %d: lds %zu B, rows in %s (6 x %d columns = %zu B + %zu B other, limit %zu B), "
-                                "cap %d, blocks %d x %d atoms\n", vm, lds, v_direct ? "hbm" : "lds", fe, rows, other, (size_t)UF3_VROWS_LDS,
-                                A.n3.cap, n_blocks, apb);
-#define UF3_V_LAUNCH(M)                                                                                                    \
-    do {                                                                                                                   \
-        {                                                                                                                  \
-            static std::mutex mu; static size_t have[64] = {0};                                                            \
-            std::lock_guard<std::mutex> lk(mu);                                                                            \
-            size_t &hv = have[c->device & 63];                                                                             \
-            if (lds > hv) {                                                                                                \
-                HIPCHK(c, hipFuncSetAttribute((const void *)k_virial_rows<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-                hv = lds;                                                                                                  \
-            }                                                                                                              \
-        }                                                                                                                  \
-        hipLaunchKernelGGL((k_virial_rows<M>), dim3((n_blocks + 7) / 8 * 8), dim3(WPB * WAVE), lds, st, A, d_xv, v_direct);  \
-    } while (0)
-                    switch (vm) {
-                        case 0: UF3_V_LAUNCH(0); break;
-                        case 1: UF3_V_LAUNCH(1); break;
-                        case 2: UF3_V_LAUNCH(2); break;
-                        case 3: UF3_V_LAUNCH(3); break;
-                        case 4: UF3_V_LAUNCH(4); break;
-                        default: UF3_V_LAUNCH(5); break;
-                    }
-#undef UF3_V_LAUNCH
-                }
-            }
+            if (feat3 && !restart) { rc = feat3_stage(b, A, cap); if (rc) return rc; }
+            if (want_v && !restart) { rc = virial_rows_stage(b, A, d_xv, has3 || old_n3); if (rc) return rc; }
         }
         HIPCHK(c, hipGetLastError());
         if (restart) continue;
         if ((!has3 || c->n3_tuned) && c->cand_tuned && !old_n3) {
-            // capacities known from earlier calls: do not wait.  The status words follow the launches into a pinned
-            // slot; the next call on this context / uf3_ctx_synchronize looks at them (UF3_ERETRY if they overflowed)
-            int slot = -1;
-            for (int q = 0; q < uf3_ctx::N_PENDING && slot < 0; q++)
-                if (!c->pending_chk[(c->pending_head + q) % uf3_ctx::N_PENDING].live) slot = (c->pending_head + q) % uf3_ctx::N_PENDING;
-            if (slot < 0) {        // all slots in flight: wait for the oldest
-                int rcw = poll_pending(c, true);
-                if (rcw) return rcw;
-                slot = c->pending_head;
-            }
-            HIPCHK(c, c->pin_flags.ensure(sizeof(int) * 8 * uf3_ctx::N_PENDING));
-            uf3_ctx::Pending &pd = c->pending_chk[slot];
-            if (!pd.ev) HIPCHK(c, hipEventCreateWithFlags(&pd.ev, hipEventDisableTiming));
-            HIPCHK(c, hipMemcpyAsync((int *)c->pin_flags.p + 8 * slot, c->flags.p, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipEventRecord(pd.ev, st));
-            pd.virial = want_v;
-            pd.cap = cap; pd.cand = c->cand_cap; pd.has3 = has3; pd.xcap = ext_lists ? c->n3x_cap : (1 << 30); pd.img = img_launch || !(has3 && want_f && A.outside); pd.img_launch = img_launch; pd.live = true;
-            c->pending_head = (slot + 1) % uf3_ctx::N_PENDING;
-            return UF3_OK;
+            uf3_ctx::Pending pd;
+            pd.virial = want_v; pd.cap = cap; pd.cand = c->cand_cap; pd.has3 = has3; pd.xcap = img_launch ? c->n3x_cap : (1 << 30);
+            pd.img = img_launch || !(has3 && want_f && A.outside); pd.img_launch = img_launch;
+            return featurize_defer(c, pd);
         }
-        int fl[8] = {0, 0, 0, 0, 0, 0, 0, 0};            // error flag, n3 need, candidate need, extension need, atoms far outside
-        HIPCHK(c, hipMemcpyAsync(fl, c->flags.p, sizeof(fl), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        if (fl[0]) return check_flags(c);
-        if (want_v && fl[4]) return fail(c, UF3_EINVAL, UF3_VIRIAL_OUTSIDE_MSG);
         bool redo = false;
-        if (has3 && want_f && A.outside && fl[4] && !c->img_mode) { c->img_mode = true; redo = true; }
-        else if (img_launch && !fl[4]) c->img_mode = false;                 // (valid all the same) back to the ordinary launches
-        if (ext_lists && fl[3] > c->n3x_cap) {
-            if (fl[3] > 248) return fail(c, UF3_EOVERFLOW, "extension neighbour lists of atoms far outside their cell exceed 248 entries");
-            c->n3x_cap = (fl[3] + 8 + 7) / 8 * 8; redo = true;
-        }
-        if (has3 && fl[1] > cap) { c->n3_cap = (fl[1] + 8 + 7) / 8 * 8; c->n3_tuned = true; redo = true; }
-        if (fl[2] > c->cand_cap) { c->cand_cap = (fl[2] + 16 + 7) / 8 * 8; redo = true; }
-        if (redo) continue;
-        if (has3 && !c->n3_tuned) { rc = n3_tune(c, A.n3, P.natoms); if (rc) return rc; }
-        if (want_e || want_f) c->cand_tuned = true;
-        return UF3_OK;
+        rc = featurize_adapt(c, A, has3, want_v, img_launch, cap, redo);
+        if (rc || !redo) return rc;
     }
     return fail(c, UF3_EOVERFLOW, "neighbour capacities did not converge");
 }
@@ -2461,35 +2484,27 @@ static int eval_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, co
                 {
                     // instance: strain derivative | list capacity 16 as a constant | candidates from the persistent lists | centre
                     // legs from per-bond tables (one set of 3-body legs, T <= 64, short lists: the usual case)
+                    // (which of the combinations exist: the comment block "Which instances ... the library holds")
                     cap16 = cap == 16 && !uf3_env("UF3_EVAL_NO_CAP16");
-                    const int inst = (A.virial ? 1 : 0) | (cap16 ? 2 : 0) | (md_step ? 4 : 0) | (tab ? 8 : 0);
-#define UF3_EVAL_CW_CASE(I) case I: {                                                                                                  \
-        static std::mutex mu; static size_t have[64] = {0};                                                                           \
-        { std::lock_guard<std::mutex> lk(mu); size_t &hv = have[c->device & 63];                                                      \
-          if (lds > hv) { HIPCHK(c, hipFuncSetAttribute((const void *)k_eval<false, ((I) & 1) != 0, ((I) & 2) ? 16 : 0, ((I) & 4) != 0, true, true>, \
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); hv = lds; } }         \
-        hipLaunchKernelGGL((k_eval<false, ((I) & 1) != 0, ((I) & 2) ? 16 : 0, ((I) & 4) != 0, true, true>), eg_cw, dim3(64 * EVAL_CW_WAVES), lds, st, A); } break;
                     const dim3 eg_cw((unsigned)(((n_centres + EVAL_CW_WAVES - 1) / EVAL_CW_WAVES + 7) / 8 * 8));
-                    if (cw) switch (inst & 7) {
-                        // (MD route only: with the walk-order arrays of the fused list build the waves' own LDS is 7.1 KB each, and two
-                        // 8-wave workgroups + two copies of the tables do not fit a CU -- 168 of 160 KB; not instantiated)
-                        UF3_EVAL_CW_CASE(4) UF3_EVAL_CW_CASE(5) UF3_EVAL_CW_CASE(6) UF3_EVAL_CW_CASE(7)
-                        default: return fail(c, UF3_EINVAL, "k_eval<CW> outside the MD route");
-                    }
-#undef UF3_EVAL_CW_CASE
-#define UF3_EVAL_WIN_CASE(I) case I: hipLaunchKernelGGL((k_eval<false, ((I) & 1) != 0, ((I) & 2) ? 16 : 0, ((I) & 4) != 0, true, false, true>), eg, dim3(64), lds, st, A); break;
-                    else if (win) switch (inst & 7) {
-                        UF3_EVAL_WIN_CASE(0) UF3_EVAL_WIN_CASE(1) UF3_EVAL_WIN_CASE(2) UF3_EVAL_WIN_CASE(3)
-                        UF3_EVAL_WIN_CASE(4) UF3_EVAL_WIN_CASE(5) UF3_EVAL_WIN_CASE(6) UF3_EVAL_WIN_CASE(7)
-                    }
-#undef UF3_EVAL_WIN_CASE
-#define UF3_EVAL_CASE(I) case I: hipLaunchKernelGGL((k_eval<false, ((I) & 1) != 0, ((I) & 2) ? 16 : 0, ((I) & 4) != 0, ((I) & 8) != 0>), eg, dim3(64), lds, st, A); break;
-                    else switch (inst) {
-                        UF3_EVAL_CASE(0) UF3_EVAL_CASE(1) UF3_EVAL_CASE(2) UF3_EVAL_CASE(3) UF3_EVAL_CASE(4) UF3_EVAL_CASE(5)
-                        UF3_EVAL_CASE(6) UF3_EVAL_CASE(7) UF3_EVAL_CASE(8) UF3_EVAL_CASE(9) UF3_EVAL_CASE(10) UF3_EVAL_CASE(11)
-                        UF3_EVAL_CASE(12) UF3_EVAL_CASE(13) UF3_EVAL_CASE(14) UF3_EVAL_CASE(15)
-                    }
-#undef UF3_EVAL_CASE
+                    const int rl = with_bool(A.virial != 0, [&](auto VIR) {
+                    return with_bool(cap16, [&](auto C16) {
+                    return with_bool(md_step, [&](auto MD) {
+                        constexpr int CAP = C16 ? 16 : 0;
+                        if (cw) {
+                            // (MD route only: with the walk-order arrays of the fused list build the waves' own LDS is 7.1 KB each, and two
+                            // 8-wave workgroups + two copies of the tables do not fit a CU -- 168 of 160 KB; not instantiated)
+                            if constexpr (MD)
+                                HIPCHK(c, (launch_lds<k_eval<false, VIR, CAP, true, true, true>>(c, eg_cw, dim3(64 * EVAL_CW_WAVES), lds, A)));
+                            else
+                                return fail(c, UF3_EINVAL, "k_eval<CW> outside the MD route");
+                        }
+                        else if (win) hipLaunchKernelGGL((k_eval<false, VIR, CAP, MD, true, false, true>), eg, dim3(64), lds, st, A);
+                        else if (tab) hipLaunchKernelGGL((k_eval<false, VIR, CAP, MD, true>), eg, dim3(64), lds, st, A);
+                        else hipLaunchKernelGGL((k_eval<false, VIR, CAP, MD, false>), eg, dim3(64), lds, st, A);
+                        return (int)UF3_OK;
+                    }); }); });
+                    if (rl) return rl;
                 }
                 if (fuse && deferred_cap) *deferred_cap = (int)cap;
                 if (centres && !md_step) {
@@ -5731,14 +5746,6 @@ static void site_rows_launch(uf3_ctx *c, const FluxArgs &F, int n_feat, long lon
     const size_t lds = 8 * (size_t)site_row_stride(n_feat) + 4 * (size_t)F.cap;
     hipLaunchKernelGGL(k_site_rows, dim3((unsigned)(m1 - m0)), dim3(64), lds, c->stream, A);
 }
-// more than the default 64 KB of dynamic LDS has to be asked for, once per context (before the first launch)
-static int site_rows_lds_attr(uf3_ctx *c) {
-    if (!c->site_rows_lds_set) {
-        HIPCHK(c, hipFuncSetAttribute((const void *)k_site_rows, hipFuncAttributeMaxDynamicSharedMemorySize, SITE_ROWS_LDS));
-        c->site_rows_lds_set = true;
-    }
-    return UF3_OK;
-}
 static int site_rows_cap_limit(int n_feat) { return (SITE_ROWS_LDS - 8 * site_row_stride(n_feat)) / 4; }
 
 static int site_rows_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, double *d_rows, int64_t ld) {
@@ -5747,7 +5754,7 @@ static int site_rows_impl(uf3_basis *b, const uf3_frames *fr, const double *d_po
     if (!d_pos || !d_rows) return fail(c, UF3_EINVAL, "uf3_site_rows: null argument");
     if (ld < n_feat) return fail(c, UF3_EINVAL, "uf3_site_rows: ld must be >= n_feat");
     if (site_rows_cap_limit(n_feat) < 1) return fail(c, UF3_EINVAL, "uf3_site_rows: a row of this basis does not fit in LDS");
-    if (int ra = site_rows_lds_attr(c)) return ra;
+    HIPCHK(c, lds_opt_in<k_site_rows>(c->device, SITE_ROWS_LDS));       // (its whole budget, before the first launch)
     FluxArgs F;
     int rc = lists_prepare(b, fr, c->fx, d_z, nullptr, nullptr, nullptr, "uf3_site_rows", "batch", F, false);
     if (rc) return rc;
@@ -5796,11 +5803,8 @@ static int site_grade_sample(uf3_basis *b, ListWork &W, FluxArgs &F, bool headro
     const int n_feat = b->host.F;
     int rc = ensure_frag(c);
     if (rc) return rc;
-    if (!c->site_grade_lds_set) {
-        HIPCHK(c, hipFuncSetAttribute((const void *)k_site_grade, hipFuncAttributeMaxDynamicSharedMemorySize, SG_LDS_BUDGET));
-        c->site_grade_lds_set = true;
-    }
-    if (int ra = site_rows_lds_attr(c)) return ra;
+    HIPCHK(c, lds_opt_in<k_site_grade>(c->device, SG_LDS_BUDGET));      // (the kernels' whole budgets, before their first launches)
+    HIPCHK(c, lds_opt_in<k_site_rows>(c->device, SITE_ROWS_LDS));
     if (site_rows_cap_limit(n_feat) < 1) return fail(c, UF3_EINVAL, std::string(who) + ": a row of this basis does not fit in LDS");
     hipStream_t st = c->stream;
     return lists_sample(c, W, F, headroom, who, site_rows_cap_limit(n_feat), ": an atom has more neighbours than fit in LDS beside its row", [&] {
@@ -5961,15 +5965,7 @@ static int phonon_mesh_impl(uf3_ctx *c, int32_t n_atoms, int64_t n_sc, const dou
         else hipLaunchKernelGGL(k_ph_mesh_lane<2>, dim3(g), dim3(64), 0, st, A);
     } else {
         const size_t lds = ph_wave_lds(3 * N);
-        if (lds > 65536) {      // (more than 64 KB of dynamic LDS is an opt-in per kernel and device: one high-water mark each)
-            static std::mutex mu; static size_t have[64] = {0};
-            std::lock_guard<std::mutex> lk(mu);
-            size_t &hv = have[c->device & 63];
-            if (lds > hv) {
-                HIPCHK(c, hipFuncSetAttribute((const void *)k_ph_mesh_wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hv = lds;
-            }
-        }
+        if (lds > 65536) HIPCHK(c, lds_opt_in<k_ph_mesh_wave>(c->device, lds));
         hipLaunchKernelGGL(k_ph_mesh_wave, dim3((unsigned)nq), dim3(64), lds, st, A);
     }
     HIPCHK(c, hipGetLastError());
