@@ -81,6 +81,15 @@ struct F3Cfg {
 typedef double __attribute__((ext_vector_type(2))) F3Pair;
 typedef const __attribute__((address_space(3))) F3Pair *F3LdsPairs;
 typedef const __attribute__((address_space(3))) double *F3LdsDoubles;
+// the LDS byte address of p as a scalar the compiler takes as it is: a stage-1 trip adds its per-lane offset to it in ONE vector
+// instruction and advances it on the scalar unit (left to itself the compiler splits the constant part of the address off into a
+// vector add of its own, or keeps vector induction variables per pointer)
+__device__ __forceinline__ unsigned f3_lds_addr(const double *p) { return (unsigned)(size_t)(F3LdsDoubles)p; }
+__device__ __forceinline__ unsigned f3_lds_base(unsigned a) {
+    a = __builtin_amdgcn_readfirstlane(a);
+    asm("" : "+s"(a));
+    return a;
+}
 
 // four consecutive window functions of a leg at x (t0 < x < tlast): values v, derivatives d; returns the knot interval.
 // The row of the guessed interval is fetched whole and again only when the guess was off (non-uniform knots, x on a knot).
@@ -171,6 +180,7 @@ k_featurize3(Feat3Args A) {
     double *tq = wd + list_d;                                         // [cap][EF][4]: T_f = (Tx Ty Tz T3) of every own bond
     double *stage = tq + tq_d;
     double *zq = stage + (Cfg::STAGE - 4);                            // a quad of zeros (read by the wide windows only)
+    const unsigned stage_a = f3_lds_addr(stage), tq_a = f3_lds_addr(tq), zq_a = f3_lds_addr(zq);
     int *oparent = wi, *oshift = wi + cap, *noff = wi + 2 * cap, *nbase = noff + cap + 1, *so = nbase + cap + 1;
     int *osbp = so + (UF3_MAX_SPECIES + 2);                           // first window row of every own bond
     int *ospoff = osbp + cap;                     // [cap][S + 1] (last: the only array whose place depends on S)
@@ -188,7 +198,7 @@ k_featurize3(Feat3Args A) {
     // serves NR positions, 32 apart --------------------------------------------------------------------------------------
     const int ext_p = A.ext_p, ext_n = A.ext_n, lo_n = A.lo_n, lo_p = A.lo_p, npos = ext_p * ext_n;
     const int half = lane >> 5;
-    int p_lane[NR], n_lane[NR], qn_lane[NR], n32_lane[NR], n32h_lane[NR];
+    int p_lane[NR], n_lane[NR], qn_lane[NR], n32_lane[NR], n32h_lane[NR], p8_lane[NR], qn8_lane[NR], tp_lane[NR];
     const int pr_rows = A.pr_rows;
 #pragma unroll
     for (int r = 0; r < NR; r++) {
@@ -200,6 +210,9 @@ k_featurize3(Feat3Args A) {
         qn_lane[r] = on ? n_lane[r] : RS_C - 1;                            // (... a centre-role record's zero padding)
         n32_lane[r] = n_lane[r] * 32;
         n32h_lane[r] = n32_lane[r] + 16 * half;
+        p8_lane[r] = 8 * p_lane[r];                                        // byte offsets of stage 1's reads: a record's bond value,
+        qn8_lane[r] = 8 * qn_lane[r];                                      // its n-leg value, the partner's T pair of this half
+        tp_lane[r] = 32 * p_lane[r] + 16 * half;
     }
     (void)npos;
     const int sbn_max = ext_n > 4 ? ext_n - 4 : 0, sbp_max = ext_p > 4 ? ext_p - 4 : 0;
@@ -300,7 +313,8 @@ k_featurize3(Feat3Args A) {
             // stage 2: the open bond's W into the rows of the window.  Lower half: rows (x, y) += (Tx, Ty) W_plain + T3 (W_x, W_y);
             // upper half: rows (z, energy) += (Tz, T3) W_plain + T3 (W_z, 0) -- the energy row from the centre role only.
             int wmask = 0;                                          // rounds that took records since the last flush
-            auto flush = [&](bool is_c) {
+            auto flush = [&](auto role) {
+                constexpr bool IS_C = decltype(role)::value;        // the centre role's flush: the energy row takes part
                 if (cur < 0 || UF3_SKIP(2)) return;
                 const double *tc = tq + (size_t)cur * EF * 4;
                 // (wide windows: only the rounds that were summed into)
@@ -317,11 +331,24 @@ k_featurize3(Feat3Args A) {
                     const auto r0 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
                     const auto r1 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
                     const double wpl = __hiloint2double(r1[1], r0[1]);        // W_plain (the upper half's second sum) in every lane
-                    const double wpl1 = (half && !is_c) ? 0.0 : wpl, ws1 = half ? 0.0 : ws[r][1];
+                    // (the swap's other result keeps the lower half's own second sum in the lower half: ws[r][1] itself is dead from
+                    // here on -- it is zeroed below -- and the swap takes one copy per dword instead of two)
+                    const double wlo = __hiloint2double(r1[0], r0[0]);
 #pragma unroll
-                    for (int q = 0; q < EF; q++) {
-                        xacc[r][q][0] = fma(tv[q].x, wpl, fma(t3[q], ws[r][0], xacc[r][q][0]));
-                        xacc[r][q][1] = fma(tv[q].y, wpl1, fma(t3[q], ws1, xacc[r][q][1]));
+                    for (int q = 0; q < EF; q++) xacc[r][q][0] = fma(tv[q].x, wpl, fma(t3[q], ws[r][0], xacc[r][q][0]));
+                    // the second chain by halves, as exec masks instead of selected zeros: T3 (W_y) belongs to the lower half only (the
+                    // upper half's second sum IS W_plain), T W_plain to both halves in the centre role (Ty | the energy row) and to the
+                    // lower half only in the neighbour role.  Inner term first, as ever.
+                    if (!half) {
+#pragma unroll
+                        for (int q = 0; q < EF; q++) {
+                            xacc[r][q][1] = fma(t3[q], wlo, xacc[r][q][1]);
+                            if (!IS_C) xacc[r][q][1] = fma(tv[q].y, wpl, xacc[r][q][1]);
+                        }
+                    }
+                    if (IS_C) {
+#pragma unroll
+                        for (int q = 0; q < EF; q++) xacc[r][q][1] = fma(tv[q].y, wpl, xacc[r][q][1]);
                     }
                     ws[r][0] = ws[r][1] = 0.0;
                 }
@@ -386,10 +413,10 @@ k_featurize3(Feat3Args A) {
                         if (same) s0 = max(s0, pr + fi_s + 1);
                         if (s0 >= s1) continue;
                         const int key = f_los + fi_s;
-                        if (key != cur) { flush(true); cur = key; }
+                        if (key != cur) { flush(std::true_type{}); cur = key; }
                         wmask |= smask;
-                        const double *qp = stage + (size_t)(s0 - p0) * RS_C;
-                        const double *tp = tq + (size_t)(g_los + (s0 - pr)) * EF * 4 + 2 * half;
+                        unsigned qp = f3_lds_base(stage_a + (s0 - p0) * (RS_C * 8));
+                        unsigned tp = f3_lds_base(tq_a + (g_los + (s0 - pr)) * (EF * 32));
                         int cnt = s1 - s0;
                         auto body = [&](auto tag) {
                             constexpr int CNT = decltype(tag)::value;
@@ -400,22 +427,24 @@ k_featurize3(Feat3Args A) {
                                 F3Pair tt[CNT];
 #pragma unroll
                                 for (int i = 0; i < CNT; i++) {
-                                    bq[i] = ((F3LdsDoubles)qp)[i * RS_C + qn_lane[r]];
-                                    tt[i] = *(F3LdsPairs)(const F3Pair *)(tp + (size_t)i * EF * 4 + 4 * p_lane[r]);
+                                    bq[i] = *(F3LdsDoubles)(qp + qn8_lane[r] + i * RS_C * 8);
+                                    tt[i] = *(F3LdsPairs)(tp + tp_lane[r] + i * EF * 32);
                                 }
 #pragma unroll
                                 for (int i = 0; i < CNT; i++) { ws[r][0] = fma(tt[i].x, bq[i], ws[r][0]); ws[r][1] = fma(tt[i].y, bq[i], ws[r][1]); }
                             }
-                            qp += CNT * RS_C; tp += (size_t)CNT * EF * 4; cnt -= CNT;
+                            qp += CNT * RS_C * 8; tp += CNT * EF * 32; cnt -= CNT;
+                            asm("" : "+s"(qp), "+s"(tp));
                         };
                         while (cnt >= 4) body(std::integral_constant<int, 4>{});
+                        // (three plain ifs, no else: a body leaves cnt at 0, and the sums stay in the registers of the trip)
                         if (cnt == 3) body(std::integral_constant<int, 3>{});
-                        else if (cnt == 2) body(std::integral_constant<int, 2>{});
-                        else if (cnt == 1) body(std::integral_constant<int, 1>{});
+                        if (cnt == 2) body(std::integral_constant<int, 2>{});
+                        if (cnt == 1) body(std::integral_constant<int, 1>{});
                     }
                     wave_sync();
                 }
-                flush(true);
+                flush(std::true_type{});
                 cur = -1;
             }
             // ---- neighbour role: m is a neighbour of the centre e (fixed bond (m, e)); k runs over e's list.  The valid items of
@@ -524,9 +553,9 @@ k_featurize3(Feat3Args A) {
                             gm &= gm - 1;
                             const int g1 = gm ? __builtin_ctzll(gm) : end;
                             const int key = __builtin_amdgcn_readlane(v_key, g0);
-                            if (key != cur) { flush(false); cur = key; }
+                            if (key != cur) { flush(std::false_type{}); cur = key; }
                             wmask |= smask;
-                            const double *rp = stage + (size_t)g0 * RS_N;
+                            unsigned rp = f3_lds_base(stage_a + g0 * (RS_N * 8));
                             int gi = g0, cnt = g1 - g0;
                             auto body = [&](auto tag) {
                                 constexpr int CNT = decltype(tag)::value;
@@ -544,34 +573,35 @@ k_featurize3(Feat3Args A) {
                                     F3Pair tt[CNT];
 #pragma unroll
                                     for (int i = 0; i < CNT; i++) {
-                                        const char *qa;
+                                        unsigned qa;
                                         if (NR == 1) {
                                             // 32 (n - first slot) + 16 half inside the record's four quads; everything else -- below the
                                             // window (wraps), above it, idle positions -- lands on the record's own pad of zeros
                                             const unsigned off = min((unsigned)(n32h_lane[r] - sb[i]), 128u);
-                                            qa = (const char *)(rp + i * RS_N + EFP) + off;
+                                            qa = rp + off + (i * RS_N + EFP) * 8;
                                         } else {
                                             const unsigned off_n = (unsigned)(n32_lane[r] - sb[i]);    // 32 (n - first slot)
-                                            qa = (const char *)(rp + i * RS_N + EFP + 2 * half) + off_n;
-                                            qa = off_n < 128u ? qa : (const char *)zq;
+                                            qa = rp + off_n + (i * RS_N + EFP) * 8 + 16 * half;
+                                            qa = off_n < 128u ? qa : zq_a;
                                         }
-                                        bq[i] = ((F3LdsDoubles)rp)[i * RS_N + p_lane[r]];
-                                        tt[i] = *(F3LdsPairs)(const F3Pair *)qa;
+                                        bq[i] = *(F3LdsDoubles)(rp + p8_lane[r] + i * RS_N * 8);
+                                        tt[i] = *(F3LdsPairs)qa;
                                     }
 #pragma unroll
                                     for (int i = 0; i < CNT; i++) { ws[r][0] = fma(bq[i], tt[i].x, ws[r][0]); ws[r][1] = fma(bq[i], tt[i].y, ws[r][1]); }
                                 }
-                                rp += CNT * RS_N; gi += CNT; cnt -= CNT;
+                                rp += CNT * RS_N * 8; gi += CNT; cnt -= CNT;
+                                asm("" : "+s"(rp));
                             };
                             while (cnt >= 4) body(std::integral_constant<int, 4>{});
                             if (cnt == 3) body(std::integral_constant<int, 3>{});
-                            else if (cnt == 2) body(std::integral_constant<int, 2>{});
-                            else if (cnt == 1) body(std::integral_constant<int, 1>{});
+                            if (cnt == 2) body(std::integral_constant<int, 2>{});
+                            if (cnt == 1) body(std::integral_constant<int, 1>{});
                         }
                         wave_sync();
                     }
                 }
-                flush(false);
+                flush(std::false_type{});
                 cur = -1;
             }
             if (UF3_SKIP(16)) continue;
