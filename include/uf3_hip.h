@@ -106,7 +106,7 @@ int uf3_ctx_use_own_stream(uf3_ctx *ctx);
 int uf3_ctx_synchronize(uf3_ctx *ctx);
 const char *uf3_last_error(const uf3_ctx *ctx);
 /* Which sources this binary was compiled from: the first 16 hex digits of the sha256 over uf3_hip.hip, uf3_kernels.h,
- * uf3_feat3.h, uf3_virial_rows.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h, uf3_npt.h, uf3_neb.h, uf3_idpp.h, uf3_mc.h, uf3_flux.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
+ * uf3_feat3.h, uf3_virial_rows.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h, uf3_npt.h, uf3_neb.h, uf3_ssneb.h, uf3_idpp.h, uf3_mc.h, uf3_flux.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
  * outside it).  __graft_entry__.build() rebuilds when it differs from the tree's, smoke() prints it. */
 const char *uf3_build_id(void);
 /* timing of the dominant kernel: (re)start / read accumulated HIP-event time in ms and launches */
@@ -635,6 +635,34 @@ int uf3_neb_get_state(uf3_neb *neb, double *pos, double *forces, double *neb_for
 int uf3_idpp_create(uf3_ctx *ctx, const uf3_frames *frames, const double *pos, const int32_t *z, const uint8_t *fixed,
                     int32_t n_bands, const int32_t *band_first_frame /*[n_bands + 1]*/, const double *spring /*[n_bands]*/,
                     uf3_neb **out);
+
+/*
+ * Nudged elastic bands whose images differ in cell (solid-state NEB; uf3_amd.forcefield.neb.CellNudgedElasticBand; kernels in
+ * uf3_ssneb.h): the band of uf3_neb_create in uf3_relax_create's generalised coordinates.  C0 is the cell of a band's image 0;
+ * image i has D_i = C0^-1 C_i, q_i = x_i D_i^-1 and the vector u_i = (q_i [n][3], Y_i = kappa D_i [3][3]) of 3 n + 9 numbers; its
+ * true force is (F D_i^T, G_i = -D_i^-T W_i / kappa), W the strain derivative of uf3_eval_virial.  t+ = u_{i+1} - u_i and
+ * t- = u_i - u_{i-1} as stored over all 3 n + 9 entries (no minimum image); tangent, spring term, climbing image, the one FIRE
+ * per band (its velocity has a 3 x 3 cell part per image; maxstep over the band's whole vector) and the statuses are
+ * uf3_neb_run's.  Criterion: the largest row norm of g over every atom row and the three cell rows of every interior image.
+ * A move: q += dr_q, D += dr_Y / kappa, x = q D, C = C0 D; end images never move and their cells are never written.
+ *   uf3_ssneb_create        uf3_neb_create's arguments without a fixed mask, and cell_factor [n_bands] (kappa; NULL: the atom
+ *                           count of an image, uf3_relax_run's convention).  UF3_EINVAL: uf3_neb_create's refusals except that
+ *                           the cells of a band's images may differ; a frame that is not periodic along all three axes; a
+ *                           cell without volume (|det| <= 1e-12 of the product of its row lengths); a cell_factor that is not positive and finite.  The handle is a uf3_neb:
+ *                           uf3_neb_run, uf3_neb_get_state and uf3_neb_destroy serve it.  uf3_neb_run freezes a band (status 2)
+ *                           also on a non-finite strain derivative and on a singular or non-finite D; its skin is accepted and
+ *                           unused: the context's MD skin is 0 during the run (every step rebuilds the lists: the cells change)
+ *                           and the caller's again on return; the new cells are waited for after every step.
+ *                           uf3_neb_get_state's forces and neb_forces are the atom rows F D^T and those of g.
+ *   uf3_neb_get_cell_state  host arrays out, NULL skips: the current cells [n_frames][9], the strain derivatives
+ *                           [n_frames][6] (xx, yy, zz, yz, xz, xy), the cell forces G and the cell part of g [n_frames][9]
+ *                           (0 on end points; tangents as in the last run) of the current state (evaluated first if it moved
+ *                           since).  UF3_EINVAL on a handle that uf3_ssneb_create did not make.
+ */
+int uf3_ssneb_create(uf3_basis *basis, const uf3_frames *frames, const double *pos, const int32_t *z, const double *c1,
+                     const double *c2, const double *c3, int32_t n_bands, const int32_t *band_first_frame /*[n_bands + 1]*/,
+                     const double *spring /*[n_bands]*/, const double *cell_factor /*[n_bands] or NULL*/, uf3_neb **out);
+int uf3_neb_get_cell_state(uf3_neb *neb, double *cells, double *virials, double *cell_forces, double *neb_cell_forces);
 
 /*
  * Batched species-swap Monte Carlo on fixed positions (uf3_amd.forcefield.mc.MonteCarlo; kernels in uf3_mc.h): every frame its own

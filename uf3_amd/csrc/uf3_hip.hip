@@ -29,6 +29,7 @@
 #include "uf3_hessian.h"
 #include "uf3_relax.h"
 #include "uf3_neb.h"
+#include "uf3_ssneb.h"
 #include "uf3_idpp.h"
 #include "uf3_mc.h"
 #include "uf3_phonon.h"
@@ -4749,16 +4750,21 @@ struct uf3_neb : Batch {
     int last_climb = 0;
     bool idpp = false;                          // made by uf3_idpp_create: energies and forces are k_idpp's, not the evaluator's
     DevBuf idpp_cells, idpp_partial;
+    // made by uf3_ssneb_create (uf3_ssneb.h): the cell is part of every image's vector
+    bool cellb = false;
+    DevBuf q, fq, D, vc, G, gc, D_ev, vc_ev, kappa, virials, cells_dev;
 };
 
 extern "C" void uf3_neb_destroy(uf3_neb *r) { driver_destroy(r); }
 
 static int idpp_setup(uf3_neb *r, const std::string &who);
+static int ssneb_setup(uf3_neb *r, const double *pos, const int32_t *band_first_frame, const double *cell_factor, const std::string &who);
 
 // uf3_neb_create (b: the basis of the model c1 / c2 / c3) and uf3_idpp_create (b null: no model, the handle evaluates k_idpp)
 static int neb_create(uf3_ctx *c, uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const uint8_t *fixed,
                       const double *c1, const double *c2, const double *c3, int32_t n_bands, const int32_t *band_first_frame,
-                      const double *spring, uf3_neb **out, const std::string &me) {
+                      const double *spring, uf3_neb **out, const std::string &me, bool cellb = false,
+                      const double *cell_factor = nullptr) {
     int64_t n = 0;
     int rc = batch_check(c, b, fr, pos, z, c1, c2, c3, out, me, &n);
     if (rc) return rc;
@@ -4783,13 +4789,30 @@ static int neb_create(uf3_ctx *c, uf3_basis *b, const uf3_frames *fr, const doub
             const std::string img = who + ", image " + std::to_string(j);
             if (fr->atom_offsets[f + 1] - lo != na) return fail(c, UF3_EINVAL, img + ": atom count differs from image 0");
             if (memcmp(z + lo, z + lo0, 4 * (size_t)na)) return fail(c, UF3_EINVAL, img + ": species differ from image 0");
-            if (memcmp(fr->cells + 9 * (size_t)f, fr->cells + 9 * (size_t)f0, 72)) return fail(c, UF3_EINVAL, img + ": cell differs from image 0");
+            if (!cellb && memcmp(fr->cells + 9 * (size_t)f, fr->cells + 9 * (size_t)f0, 72))
+                return fail(c, UF3_EINVAL, img + ": cell differs from image 0");
             for (int k = 0; k < 3; k++)
                 if ((fr->pbc[3 * f + k] != 0) != (fr->pbc[3 * f0 + k] != 0)) return fail(c, UF3_EINVAL, img + ": pbc differs from image 0");
             if (fixed && memcmp(fixed + lo, fixed + lo0, (size_t)na)) return fail(c, UF3_EINVAL, img + ": fixed mask differs from image 0");
             bool same = true;
             for (int64_t q = 0; q < 3 * na && same; q++) same = pos[3 * lo + q] == pos[3 * (lo - na) + q];
             if (same) return fail(c, UF3_EINVAL, img + ": positions identical to image " + std::to_string(j - 1));
+        }
+        if (cellb) {
+            if (cell_factor && (!(cell_factor[bd] > 0.0) || !std::isfinite(cell_factor[bd])))
+                return fail(c, UF3_EINVAL, who + ": cell_factor must be positive and finite");
+            for (int j = 0; j < M; j++) {
+                const int f = f0 + j;
+                const std::string img = who + ", image " + std::to_string(j);
+                if (!(fr->pbc[3 * f] && fr->pbc[3 * f + 1] && fr->pbc[3 * f + 2]))
+                    return fail(c, UF3_EINVAL, img + ": a cell band needs frames periodic along all three axes");
+                const double *cl = fr->cells + 9 * (size_t)f;
+                const double det = cl[0] * (cl[4] * cl[8] - cl[5] * cl[7]) - cl[1] * (cl[3] * cl[8] - cl[5] * cl[6]) +
+                                   cl[2] * (cl[3] * cl[7] - cl[4] * cl[6]);
+                // (singular to rounding: the volume against the product of the row lengths)
+                if (!(std::fabs(det) > 1e-12 * norm3(cl) * norm3(cl + 3) * norm3(cl + 6)))
+                    return fail(c, UF3_EINVAL, img + ": the cell is singular");
+            }
         }
         NebBand &S = st[bd];
         memset(&S, 0, sizeof(S));
@@ -4828,6 +4851,10 @@ static int neb_create(uf3_ctx *c, uf3_basis *b, const uf3_frames *fr, const doub
         rc = idpp_setup(r, me);
         if (rc) return bail(rc);
     }
+    if (cellb) {
+        rc = ssneb_setup(r, pos, band_first_frame, cell_factor, me);
+        if (rc) return bail(rc);
+    }
     *out = r;
     return UF3_OK;
 }
@@ -4837,6 +4864,67 @@ extern "C" int uf3_neb_create(uf3_basis *b, const uf3_frames *fr, const double *
                               const double *spring, uf3_neb **out) {
     if (!b) return fail(nullptr, UF3_EINVAL, "uf3_neb_create: basis is NULL");
     return neb_create(b->ctx, b, fr, pos, z, fixed, c1, c2, c3, n_bands, band_first_frame, spring, out, "uf3_neb_create");
+}
+
+// the cell band's own state: D_i = C0^-1 C_i and q_i = x_i D_i^-1 per image (host, once), zero cell velocities, kappa per band
+// (cell_factor null: the band's atom count per image, uf3_relax.h's convention)
+static void ssneb_inv3(const double *m, double *r) {
+    const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
+    const double id = 1.0 / (m[0] * c00 + m[1] * c01 + m[2] * c02);
+    r[0] = c00 * id; r[1] = (m[2] * m[7] - m[1] * m[8]) * id; r[2] = (m[1] * m[5] - m[2] * m[4]) * id;
+    r[3] = c01 * id; r[4] = (m[0] * m[8] - m[2] * m[6]) * id; r[5] = (m[2] * m[3] - m[0] * m[5]) * id;
+    r[6] = c02 * id; r[7] = (m[1] * m[6] - m[0] * m[7]) * id; r[8] = (m[0] * m[4] - m[1] * m[3]) * id;
+}
+
+static int ssneb_setup(uf3_neb *r, const double *pos, const int32_t *band_first_frame, const double *cell_factor, const std::string &who) {
+    uf3_ctx *c = r->c;
+    r->cellb = true;
+    const int nf = r->n_frames, nbd = r->n_bands;
+    const size_t n3 = 3 * (size_t)r->natoms;
+    std::vector<double> D(9 * (size_t)nf), q(n3), kappa(nbd);
+    for (int bd = 0; bd < nbd; bd++) {
+        const int f0 = band_first_frame[bd], M = band_first_frame[bd + 1] - f0;
+        kappa[bd] = cell_factor ? cell_factor[bd] : (double)(r->offsets[f0 + 1] - r->offsets[f0]);
+        double C0i[9];
+        ssneb_inv3(r->cells.data() + 9 * (size_t)f0, C0i);
+        for (int j = 0; j < M; j++) {
+            const int f = f0 + j;
+            const double *C = r->cells.data() + 9 * (size_t)f;
+            double *Df = D.data() + 9 * (size_t)f, Di[9];
+            for (int a = 0; a < 3; a++)
+                for (int k = 0; k < 3; k++)
+                    Df[3 * a + k] = j == 0 ? (a == k ? 1.0 : 0.0) : C0i[3 * a] * C[k] + C0i[3 * a + 1] * C[3 + k] + C0i[3 * a + 2] * C[6 + k];
+            ssneb_inv3(Df, Di);
+            for (int64_t i = r->offsets[f]; i < r->offsets[f + 1]; i++)
+                for (int k = 0; k < 3; k++)
+                    q[3 * i + k] = pos[3 * i] * Di[k] + pos[3 * i + 1] * Di[3 + k] + pos[3 * i + 2] * Di[6 + k];
+        }
+    }
+    if (!md_finite(D.data(), D.size()) || !md_finite(q.data(), q.size()))
+        return fail(c, UF3_EINVAL, who + ": the images' cells do not give finite deformations of image 0's cell");
+    const size_t f9 = 72 * (size_t)nf;
+    if (r->q.ensure(8 * n3) || r->fq.ensure(8 * n3) || r->D.ensure(f9) || r->vc.ensure(f9) || r->G.ensure(f9) || r->gc.ensure(f9) ||
+        r->D_ev.ensure(f9) || r->vc_ev.ensure(f9) || r->kappa.ensure(8 * (size_t)nbd) || r->virials.ensure(48 * (size_t)nf) ||
+        r->cells_dev.ensure(f9))
+        return fail(c, UF3_ENOMEM, who + ": out of device memory");
+    hipStream_t s = c->stream;
+    if (hipMemcpyAsync(r->q.p, q.data(), 8 * n3, hipMemcpyHostToDevice, s) || hipMemsetAsync(r->fq.p, 0, 8 * n3, s) ||
+        hipMemcpyAsync(r->D.p, D.data(), f9, hipMemcpyHostToDevice, s) || hipMemsetAsync(r->vc.p, 0, f9, s) ||
+        hipMemsetAsync(r->G.p, 0, f9, s) || hipMemsetAsync(r->gc.p, 0, f9, s) ||
+        hipMemcpyAsync(r->D_ev.p, D.data(), f9, hipMemcpyHostToDevice, s) || hipMemsetAsync(r->vc_ev.p, 0, f9, s) ||
+        hipMemcpyAsync(r->kappa.p, kappa.data(), 8 * (size_t)nbd, hipMemcpyHostToDevice, s) ||
+        hipMemsetAsync(r->virials.p, 0, 48 * (size_t)nf, s) ||
+        hipMemcpyAsync(r->cells_dev.p, r->cells.data(), f9, hipMemcpyHostToDevice, s) || hipStreamSynchronize(s))
+        return fail(c, UF3_EHIP, who + ": upload failed");      // (waited for: the host vectors go out of scope)
+    return UF3_OK;
+}
+
+extern "C" int uf3_ssneb_create(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1,
+                                const double *c2, const double *c3, int32_t n_bands, const int32_t *band_first_frame,
+                                const double *spring, const double *cell_factor, uf3_neb **out) {
+    if (!b) return fail(nullptr, UF3_EINVAL, "uf3_ssneb_create: basis is NULL");
+    return neb_create(b->ctx, b, fr, pos, z, nullptr, c1, c2, c3, n_bands, band_first_frame, spring, out, "uf3_ssneb_create", true,
+                      cell_factor);
 }
 
 // one frame's cell for k_idpp: the inverse of the cell completed as neb._axes does (the rows of non-periodic axes replaced by unit
@@ -4931,7 +5019,7 @@ static int idpp_evaluate(uf3_neb *r) {
 }
 
 static int neb_evaluate(uf3_neb *r) {
-    int rc = r->idpp ? idpp_evaluate(r) : batch_eval(*r, r->frc.as<double>(), nullptr);
+    int rc = r->idpp ? idpp_evaluate(r) : batch_eval(*r, r->frc.as<double>(), r->cellb ? r->virials.as<double>() : nullptr);
     r->forces_valid = rc == UF3_OK;
     r->g_valid = false;
     return rc;
@@ -4957,6 +5045,38 @@ static NebChunkArgs neb_chunk_args(uf3_neb *r, int climb, int all) {
     return P;
 }
 
+static SsChunkArgs ssneb_chunk_args(uf3_neb *r, int climb, int all) {
+    SsChunkArgs P;
+    P.q = r->q.as<double>(); P.frc = r->frc.as<double>(); P.vel = r->vel.as<double>(); P.virials = r->virials.as<double>();
+    P.D = r->D.as<double>(); P.vc = r->vc.as<double>(); P.kappa = r->kappa.as<double>();
+    const ChunkTable &T = r->chunks;
+    P.blk_frame = T.blk_frame.as<int>(); P.blk_lo = T.blk_lo.as<long long>(); P.blk_n = T.blk_n.as<int>();
+    P.frame_blk = T.frame_blk.as<int>(); P.frame_band = r->frame_band.as<int>(); P.offsets = r->offsets_dev.as<long long>();
+    P.energies = r->energies.as<double>(); P.bands = r->st.as<NebBand>();
+    P.fq = r->fq.as<double>(); P.G = r->G.as<double>(); P.D_ev = r->D_ev.as<double>(); P.vc_ev = r->vc_ev.as<double>();
+    P.partial = r->partial.as<double>(); P.g = r->g.as<double>(); P.gc = r->gc.as<double>(); P.cmax = r->cmax.as<double>();
+    P.img = r->img.as<NebImage>();
+    P.climb = climb; P.all = all;
+    return P;
+}
+
+// the partial and the force launch of an evaluation: k_neb_* or, on a handle of uf3_ssneb_create, k_ssneb_*
+static int neb_launch_forces(uf3_neb *r, const NebChunkArgs &P, const SsChunkArgs &S) {
+    uf3_ctx *c = r->c;
+    const dim3 grid((unsigned)r->chunks.n_blocks), blk(UF3_RELAX_THREADS);
+    if (r->cellb) {
+        hipLaunchKernelGGL(k_ssneb_partial, grid, blk, 0, c->stream, S);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k_ssneb_force, grid, blk, 0, c->stream, S);
+    } else {
+        hipLaunchKernelGGL(k_neb_partial, grid, blk, 0, c->stream, P);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k_neb_force, grid, blk, 0, c->stream, P);
+    }
+    HIPCHK(c, hipGetLastError());
+    return UF3_OK;
+}
+
 // evaluations k = 0 .. max_steps; each but the last may move the bands still running
 static int neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt, double dt_max, double maxstep, int climb, int64_t every,
                    int64_t rec_every, double *records) {
@@ -4967,6 +5087,7 @@ static int neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt, double
     const int64_t n_rec = rec_every ? max_steps / rec_every + 1 : 0;
     if (n_rec) HIPCHK(c, r->ring.ensure(8 * (size_t)n_rec * row));
     const NebChunkArgs P = neb_chunk_args(r, climb, 0);
+    const SsChunkArgs SP = r->cellb ? ssneb_chunk_args(r, climb, 0) : SsChunkArgs();
     NebBandArgs F;
     F.cmax = r->cmax.as<double>(); F.frame_blk = r->chunks.frame_blk.as<int>(); F.energies = r->energies.as<double>();
     F.img = r->img.as<NebImage>(); F.bands = r->st.as<NebBand>(); F.coef = r->coef.as<NebCoef>(); F.e_last = r->e_last.as<double>();
@@ -4975,6 +5096,13 @@ static int neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt, double
     M.pos = r->pos.as<double>(); M.vel = r->vel.as<double>(); M.g = r->g.as<double>(); M.fixed = P.fixed;
     M.frame_of = r->chunks.frame_of.as<int>(); M.frame_band = r->frame_band.as<int>(); M.bands = r->st.as<NebBand>();
     M.coef = r->coef.as<NebCoef>(); M.n = r->natoms;
+    SsMoveArgs SM;
+    if (r->cellb) {
+        SM.pos = M.pos; SM.q = r->q.as<double>(); SM.vel = M.vel; SM.D = r->D.as<double>(); SM.vc = r->vc.as<double>();
+        SM.cells = r->cells_dev.as<double>(); SM.g = M.g; SM.gc = r->gc.as<double>(); SM.D_ev = r->D_ev.as<double>();
+        SM.vc_ev = r->vc_ev.as<double>(); SM.kappa = r->kappa.as<double>(); SM.frame_of = M.frame_of; SM.frame_band = M.frame_band;
+        SM.offsets = r->offsets_dev.as<long long>(); SM.bands = M.bands; SM.coef = M.coef; SM.n = M.n;
+    }
     r->last_climb = climb;
     hipLaunchKernelGGL(k_neb_rearm, dim3((unsigned)((nbd + UF3_RELAX_THREADS - 1) / UF3_RELAX_THREADS)), dim3(UF3_RELAX_THREADS), 0, s,
                        r->st.as<NebBand>(), nbd);
@@ -4985,20 +5113,23 @@ static int neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt, double
             int rc = neb_evaluate(r);
             if (rc) return rc;
         }
-        hipLaunchKernelGGL(k_neb_partial, dim3((unsigned)r->chunks.n_blocks), dim3(UF3_RELAX_THREADS), 0, s, P);
-        HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(k_neb_force, dim3((unsigned)r->chunks.n_blocks), dim3(UF3_RELAX_THREADS), 0, s, P);
-        HIPCHK(c, hipGetLastError());
+        int rl = neb_launch_forces(r, P, SP);
+        if (rl) return rl;
         F.rec = (n_rec && k % rec_every == 0) ? r->ring.as<double>() + row * (size_t)(k / rec_every) : nullptr;
         F.can_move = k < max_steps;
         hipLaunchKernelGGL(k_neb_band, dim3((unsigned)nbd), dim3(UF3_RELAX_THREADS), 0, s, F);
         HIPCHK(c, hipGetLastError());
         r->g_valid = false;                     // (frozen bands' rows are older than this evaluation: get_state forms them all)
         if (k == max_steps) break;
-        hipLaunchKernelGGL(k_neb_move, dim3((unsigned)((r->natoms + UF3_RELAX_THREADS - 1) / UF3_RELAX_THREADS)),
-                           dim3(UF3_RELAX_THREADS), 0, s, M);
+        const dim3 mgrid((unsigned)((r->natoms + UF3_RELAX_THREADS - 1) / UF3_RELAX_THREADS));
+        if (r->cellb) hipLaunchKernelGGL(k_ssneb_move, mgrid, dim3(UF3_RELAX_THREADS), 0, s, SM);
+        else hipLaunchKernelGGL(k_neb_move, mgrid, dim3(UF3_RELAX_THREADS), 0, s, M);
         HIPCHK(c, hipGetLastError());
         r->forces_valid = false;
+        if (r->cellb) {                         // (the evaluator and its list build read the cells on the host)
+            HIPCHK(c, hipMemcpyAsync(r->cells.data(), r->cells_dev.p, 72 * (size_t)nf, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+        }
         if ((k + 1) % every == 0) {             // poll: stop once no band runs (nothing moved in this step then)
             int rc = neb_fetch_state(r);
             if (rc) return rc;
@@ -5048,7 +5179,17 @@ extern "C" int uf3_neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt
         if (climb) return fail(c, UF3_EINVAL, "uf3_neb_run: a handle of uf3_idpp_create takes no climbing image");
         return neb_run(r, max_steps, fmax, dt, dt_max, maxstep, 0, check_every, record_every, records);
     }
-    return with_run_skin(c, skin, [&] { return neb_run(r, max_steps, fmax, dt, dt_max, maxstep, climb, check_every, record_every, records); });
+    // (skin 0 on a handle of uf3_ssneb_create: the MD route's list key holds the cells)
+    return with_run_skin(c, r->cellb ? 0.0 : skin,
+                         [&] { return neb_run(r, max_steps, fmax, dt, dt_max, maxstep, climb, check_every, record_every, records); });
+}
+
+static int neb_all_forces(uf3_neb *r) {
+    const NebChunkArgs P = neb_chunk_args(r, r->last_climb, 1);
+    const SsChunkArgs SP = r->cellb ? ssneb_chunk_args(r, r->last_climb, 1) : SsChunkArgs();
+    int rc = neb_launch_forces(r, P, SP);
+    r->g_valid = rc == UF3_OK;
+    return rc;
 }
 
 extern "C" int uf3_neb_get_state(uf3_neb *r, double *pos, double *forces, double *neb_forces, double *energies, int32_t *status,
@@ -5060,17 +5201,14 @@ extern "C" int uf3_neb_get_state(uf3_neb *r, double *pos, double *forces, double
         int rc = neb_evaluate(r);
         if (rc) return rc;
     }
-    if (neb_forces && !r->g_valid) {            // g of every band at these positions, frozen bands included; no state changes
-        const NebChunkArgs P = neb_chunk_args(r, r->last_climb, 1);
-        hipLaunchKernelGGL(k_neb_partial, dim3((unsigned)r->chunks.n_blocks), dim3(UF3_RELAX_THREADS), 0, c->stream, P);
-        HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(k_neb_force, dim3((unsigned)r->chunks.n_blocks), dim3(UF3_RELAX_THREADS), 0, c->stream, P);
-        HIPCHK(c, hipGetLastError());
-        r->g_valid = true;
+    // g of every band at these positions, frozen bands included; no state changes (a cell band's forces are F D^T: k_ssneb_partial's)
+    if ((neb_forces || (forces && r->cellb)) && !r->g_valid) {
+        int rc = neb_all_forces(r);
+        if (rc) return rc;
     }
     const size_t n3 = 3 * (size_t)r->natoms;
     if (pos) HIPCHK(c, hipMemcpyAsync(pos, r->pos.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
-    if (forces) HIPCHK(c, hipMemcpyAsync(forces, r->frc.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
+    if (forces) HIPCHK(c, hipMemcpyAsync(forces, r->cellb ? r->fq.p : r->frc.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
     if (neb_forces) HIPCHK(c, hipMemcpyAsync(neb_forces, r->g.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
     if (energies) HIPCHK(c, hipMemcpyAsync(energies, r->energies.p, 8 * (size_t)r->n_frames, hipMemcpyDeviceToHost, c->stream));
     int rc = neb_fetch_state(r);
@@ -5081,6 +5219,28 @@ extern "C" int uf3_neb_get_state(uf3_neb *r, double *pos, double *forces, double
         if (criterion) criterion[bd] = r->st_host[bd].crit_last;
         if (climbing) climbing[bd] = r->st_host[bd].climbing;
     }
+    return UF3_OK;
+}
+
+extern "C" int uf3_neb_get_cell_state(uf3_neb *r, double *cells, double *virials, double *cell_forces, double *neb_cell_forces) {
+    if (!r) return fail(nullptr, UF3_EINVAL, "uf3_neb_get_cell_state: neb is NULL");
+    uf3_ctx *c = r->c;
+    if (!r->cellb) return fail(c, UF3_EINVAL, "uf3_neb_get_cell_state: the handle is not a cell band (uf3_ssneb_create)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((virials || cell_forces || neb_cell_forces) && !r->forces_valid) {
+        int rc = neb_evaluate(r);
+        if (rc) return rc;
+    }
+    if ((cell_forces || neb_cell_forces) && !r->g_valid) {
+        int rc = neb_all_forces(r);
+        if (rc) return rc;
+    }
+    const size_t nf = (size_t)r->n_frames;
+    if (virials) HIPCHK(c, hipMemcpyAsync(virials, r->virials.p, 48 * nf, hipMemcpyDeviceToHost, c->stream));
+    if (cell_forces) HIPCHK(c, hipMemcpyAsync(cell_forces, r->G.p, 72 * nf, hipMemcpyDeviceToHost, c->stream));
+    if (neb_cell_forces) HIPCHK(c, hipMemcpyAsync(neb_cell_forces, r->gc.p, 72 * nf, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (cells) memcpy(cells, r->cells.data(), 72 * nf);
     return UF3_OK;
 }
 

@@ -424,19 +424,33 @@ class UFCalculator(_Base):
                           f"{', ...' if len(bad) > 10 else ''})", RuntimeWarning)
         return out, info
 
-    def neb_bands(self, bands, fmax=0.05, climb=True, max_steps=2000, **kw):
+    def neb_bands(self, bands, fmax=0.05, climb=True, max_steps=2000, relax_cell=False, cell_factor=None, **kw):
         """
         Nudged elastic bands at once on the device (``neb.NudgedElasticBand``: improved tangents, one FIRE per band).  ``bands``:
         one band (a list of frames, end points included; ``neb.interpolate`` makes one) or a list of bands.  With ``climb`` the
         bands first run to ``fmax`` without a climbing image, then with one; both phases share ``max_steps``.  ``kw``:
         ``spring``, ``fixed``, ``skin``, ``device`` (the object's) and ``dt``, ``dt_max``, ``maxstep``, ``check_every``
         (``run``'s).  Returns (bands, info), info as ``NudgedElasticBand.run`` returns it (``barrier``, ``energies``, ...);
-        warns (RuntimeWarning) for every band that did not converge.
+        warns (RuntimeWarning) for every band that did not converge.  ``relax_cell=True``: the images of a band may differ in
+        cell and the cells of the interior images move with the atoms (``neb.CellNudgedElasticBand``; ``cell_factor`` is its
+        argument, ``fixed`` and ``skin`` are not taken); the returned images carry their cells.
         """
         import warnings
-        from .neb import NudgedElasticBand
-        make = {k: kw.pop(k) for k in ("spring", "fixed", "skin", "device") if k in kw}
-        with NudgedElasticBand(self, bands, **make) as band:
+        from .neb import CellNudgedElasticBand, NudgedElasticBand
+        if not isinstance(relax_cell, (bool, np.bool_)):
+            raise ValueError(f"neb_bands: relax_cell must be True or False, got {relax_cell!r}")
+        if relax_cell:
+            for k in ("fixed", "skin"):
+                if k in kw:
+                    raise ValueError(f"neb_bands: {k} is not supported together with relax_cell")
+            make = {k: kw.pop(k) for k in ("spring", "device") if k in kw}
+            opt = CellNudgedElasticBand(self, bands, cell_factor=cell_factor, **make)
+        else:
+            if cell_factor is not None:
+                raise ValueError("neb_bands: cell_factor needs relax_cell=True")
+            make = {k: kw.pop(k) for k in ("spring", "fixed", "skin", "device") if k in kw}
+            opt = NudgedElasticBand(self, bands, **make)
+        with opt as band:
             info = band.run(max_steps, fmax=fmax, climb=False, **kw)
             if climb:
                 left = max_steps - int(info["steps"].max())

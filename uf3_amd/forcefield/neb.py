@@ -27,6 +27,22 @@ turns (an exchange, a dumbbell rotation, a ring).  ``idpp_interpolate`` relaxes 
 (``uf3_idpp_create``, ``uf3_amd/csrc/uf3_idpp.h``):
 
     images, info = neb.idpp_interpolate(initial, final, 7)
+
+``CellNudgedElasticBand`` is the band whose images differ in cell (solid-state NEB: solid-solid transformations, ideal shear,
+any path whose saddle wants another cell than its ends; ``uf3_ssneb_create``, ``uf3_amd/csrc/uf3_ssneb.h``).  It works in
+``Relaxation(relax_cell=True)``'s generalised coordinates: with C0 the cell of a band's first image, image i has
+D_i = C0^-1 C_i, q_i = x_i D_i^-1 and the vector u_i = (q_i, Y_i = kappa D_i) of 3 N + 9 numbers, kappa the band's
+``cell_factor`` (default N, the relaxer's; Sheppard et al.'s Jacobian is volume^(1/3) N^(1/6)); its true force is
+(F D_i^T, -D_i^-T W_i / kappa), W the strain derivative.  Tangents, springs, the climbing image and the one FIRE per band are the
+rules above on these longer vectors, differences as stored; a band has converged when every atom row and every cell row of g
+of every interior image is shorter than ``fmax``.  Every axis must be periodic, ``fixed`` is not supported, end images and their
+cells never move.  Not done here: minimum-image tangents, IDPP on changing cells, an external pressure.
+
+    final = neb.remove_cell_rotation(initial, final)                      # no rigid rotation along the band
+    images = neb.interpolate(initial, final, 7, interpolate_cell=True)
+    with CellNudgedElasticBand(calc, images) as band:
+        out = band.run(1500, fmax=0.05, climb=True)
+        cells = band.get_cells()
 """
 import ctypes as C
 import os
@@ -52,10 +68,19 @@ def _axes(cell, pbc):
     return full
 
 
-def interpolate(initial, final, n_images, mic=True):
+def _singular(cell):
+    """True for a cell without volume to rounding (against the product of its row lengths), as ``uf3_ssneb_create`` tests it."""
+    return not abs(np.linalg.det(cell)) > 1e-12 * np.prod(np.sqrt((cell * cell).sum(1)))
+
+
+def interpolate(initial, final, n_images, mic=True, interpolate_cell=False):
     """``n_images`` frames from ``initial`` to ``final``, end points included, by linear interpolation of the positions.  With
     ``mic`` the displacement ``final - initial`` is wrapped to the minimum image along the periodic axes once, and the last
-    image is ``initial + d``, unwrapped: neighbouring images then differ by d / (n_images - 1) as stored."""
+    image is ``initial + d``, unwrapped: neighbouring images then differ by d / (n_images - 1) as stored.
+
+    ``interpolate_cell``: the end points may differ in cell (all axes periodic).  The cells are interpolated linearly and the
+    positions in fractional coordinates, each image's taken in its own cell; with ``mic`` the fractional displacement is wrapped
+    once.  Neighbouring images then differ by equal steps in the scaled coordinates ``CellNudgedElasticBand`` works in."""
     from uf3_amd.data.atoms import Atoms
     n_images = check_int(WHO, "n_images", n_images, 2)
     if len(initial) != len(final):
@@ -63,12 +88,30 @@ def interpolate(initial, final, n_images, mic=True):
     z = np.asarray(initial.get_atomic_numbers())
     if not np.array_equal(z, np.asarray(final.get_atomic_numbers())):
         raise ValueError("interpolate: the end points differ in species")
+    if not isinstance(interpolate_cell, (bool, np.bool_)):
+        raise ValueError(f"interpolate: interpolate_cell must be True or False, got {interpolate_cell!r}")
     cell = np.array(initial.get_cell(), dtype=float).reshape(3, 3)
-    if not np.array_equal(cell, np.array(final.get_cell(), dtype=float).reshape(3, 3)):
+    cell1 = np.array(final.get_cell(), dtype=float).reshape(3, 3)
+    if not interpolate_cell and not np.array_equal(cell, cell1):
         raise ValueError("interpolate: the end points differ in cell")
     pbc = np.asarray(initial.get_pbc(), dtype=bool).reshape(3)
     if not np.array_equal(pbc, np.asarray(final.get_pbc(), dtype=bool).reshape(3)):
         raise ValueError("interpolate: the end points differ in pbc")
+    if interpolate_cell:
+        if not pbc.all():
+            raise ValueError("interpolate: interpolate_cell needs end points periodic along all three axes")
+        if not (np.all(np.isfinite(cell)) and np.all(np.isfinite(cell1))) or _singular(cell) or _singular(cell1):
+            raise ValueError("interpolate: interpolate_cell needs end points with finite cells that are not singular")
+        s0 = np.asarray(initial.get_positions(), dtype=float) @ np.linalg.inv(cell)
+        ds = np.asarray(final.get_positions(), dtype=float) @ np.linalg.inv(cell1) - s0
+        if mic:
+            ds -= np.round(ds)
+        out = []
+        for k in range(n_images):
+            t = k / (n_images - 1)
+            ck = cell + (cell1 - cell) * t
+            out.append(Atoms(numbers=z, positions=(s0 + ds * t) @ ck, cell=ck, pbc=pbc))
+        return out
     x0 = np.asarray(initial.get_positions(), dtype=float)
     d = np.asarray(final.get_positions(), dtype=float) - x0
     if mic and pbc.any():
@@ -79,6 +122,24 @@ def interpolate(initial, final, n_images, mic=True):
     return [Atoms(numbers=z, positions=x0 + d * (k / (n_images - 1)), cell=cell, pbc=pbc) for k in range(n_images)]
 
 
+def remove_cell_rotation(initial, final):
+    """``final`` turned rigidly (cell and positions; the energy does not change) so that C0^-1 C_final, C0 the cell of
+    ``initial``, is symmetric positive definite: the polar decomposition of the deformation between the two cells.  A band
+    between ``initial`` and the result holds no rigid rotation, which no force would ever remove.  Host only."""
+    from uf3_amd.data.atoms import Atoms
+    c0 = np.array(initial.get_cell(), dtype=float).reshape(3, 3)
+    c1 = np.array(final.get_cell(), dtype=float).reshape(3, 3)
+    if not (np.all(np.isfinite(c0)) and np.all(np.isfinite(c1))) or _singular(c0) or _singular(c1):
+        raise ValueError("remove_cell_rotation: both cells must be finite and not singular")
+    d = np.linalg.inv(c0) @ c1
+    if np.linalg.det(d) < 0:
+        raise ValueError("remove_cell_rotation: the two cells differ in handedness")
+    u, _, vt = np.linalg.svd(d)
+    rot = u @ vt                                         # d = p rot with p symmetric positive definite; d rot^T = p
+    return Atoms(numbers=final.get_atomic_numbers(), positions=np.asarray(final.get_positions(), dtype=float) @ rot.T,
+                 cell=c1 @ rot.T, pbc=final.get_pbc())
+
+
 def _bands_of(bands, who=WHO):
     if isinstance(bands, (list, tuple)) and bands and isinstance(bands[0], (list, tuple)):
         return False, [list(b) for b in bands]
@@ -87,7 +148,7 @@ def _bands_of(bands, who=WHO):
     return True, [list(bands)]
 
 
-def _check_band(k, band, who=WHO):
+def _check_band(k, band, who=WHO, cells_differ=False):
     if len(band) < 3:
         raise ValueError(f"{who}: band {k} has {len(band)} images; a band needs at least 3")
     a0 = band[0]
@@ -101,7 +162,7 @@ def _check_band(k, band, who=WHO):
             raise ValueError(f"{who}: band {k}, image {j}: atom count differs from image 0")
         if not np.array_equal(np.asarray(a.get_atomic_numbers()), z0):
             raise ValueError(f"{who}: band {k}, image {j}: species differ from image 0")
-        if not np.array_equal(np.array(a.get_cell(), dtype=float).reshape(3, 3), c0):
+        if not cells_differ and not np.array_equal(np.array(a.get_cell(), dtype=float).reshape(3, 3), c0):
             raise ValueError(f"{who}: band {k}, image {j}: cell differs from image 0")
         if not np.array_equal(np.asarray(a.get_pbc(), dtype=bool).reshape(3), p0):
             raise ValueError(f"{who}: band {k}, image {j}: pbc differs from image 0")
@@ -113,13 +174,14 @@ class _Bands(Driver):
     """What ``NudgedElasticBand`` and ``IDPP`` share: the checks of the bands, the state getters and the run on a ``uf3_neb``
     handle."""
     KIND = "neb"
+    CELLS_DIFFER = False
 
     def _setup(self, bands, spring, fixed):
         """Every check of ``bands``, ``spring`` and ``fixed``, and ``self._batch``: nothing here touches the device."""
         who = self.WHO
         self._single, self.bands = _bands_of(bands, who)
         for k, band in enumerate(self.bands):
-            _check_band(k, band, who)
+            _check_band(k, band, who, self.CELLS_DIFFER)
         nb = len(self.bands)
         sp = np.asarray(spring, dtype=float)
         if sp.ndim == 0:
@@ -245,6 +307,94 @@ class NudgedElasticBand(_Bands):
         ``climbing_image`` [n_rec, n_bands] of evaluations 0, record_every, ... (after every band stopped, the final values
         repeat)."""
         return self._run(max_steps, fmax, climb, dt, dt_max, maxstep, check_every, record_every, self.skin)
+
+
+class CellNudgedElasticBand(_Bands):
+    """Batched nudged elastic bands whose images differ in cell, on the device (module text above; ``uf3_ssneb_create``).
+    What ``NudgedElasticBand`` says about atoms outside the cell holds here too."""
+    WHO = "CellNudgedElasticBand"
+    CELLS_DIFFER = True
+
+    def __init__(self, calc, bands, spring=0.1, cell_factor=None, device=None):
+        """``bands``: one band (a list of ``Atoms``; ``interpolate(..., interpolate_cell=True)`` makes one) or a list of bands,
+        every frame periodic along all three axes with a cell that is not singular.  ``spring`` (eV / Angstrom^2): a scalar or
+        one value per band.  ``cell_factor`` (kappa): None (each band's atom count per image), a scalar or one value per band,
+        positive and finite."""
+        # every argument is checked before the device is touched
+        who = self.WHO
+        if device is not None:
+            device = check_int(who, "device", device)
+        self._setup(bands, spring, None)
+        nb = len(self.bands)
+        for k, band in enumerate(self.bands):
+            for j, a in enumerate(band):
+                if not np.all(np.asarray(a.get_pbc(), dtype=bool).reshape(3)):
+                    raise ValueError(f"{who}: band {k}, image {j}: a cell band needs frames periodic along all three axes")
+                if _singular(np.array(a.get_cell(), dtype=float).reshape(3, 3)):
+                    raise ValueError(f"{who}: band {k}, image {j}: the cell is singular")
+        if cell_factor is None:
+            cf = np.array([float(len(b[0])) for b in self.bands])
+        else:
+            try:
+                cf = np.asarray(cell_factor, dtype=float)
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: cell_factor must be None, a number or one number per band") from None
+            if cf.ndim == 0:
+                cf = np.full(nb, float(cf))
+            if cf.shape != (nb,):
+                raise ValueError(f"{who}: cell_factor must be a scalar or hold one value per band ({nb}), got shape {cf.shape}")
+            if not np.all(np.isfinite(cf)) or np.any(cf <= 0.0):
+                raise ValueError(f"{who}: cell_factor must be positive and finite")
+        self.cell_factor = np.ascontiguousarray(cf)
+        self.calculator = calc
+        self.ctx = _lib.get_context(calc.device if device is None else device)
+        self._dbasis = _lib.device_basis(calc.bspline_config, self.ctx)
+        self._pid = os.getpid()
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.uf3_ssneb_create(self._dbasis.handle, C.byref(self._batch.struct), _lib._p(self._batch.pos),
+                                                     _lib._p(self._batch.z), _lib._p(calc._c1), _lib._p(calc._c2),
+                                                     _lib._p(calc._c3), nb, _lib._p(self.band_first), _lib._p(self.spring),
+                                                     _lib._p(self.cell_factor), C.byref(h)))
+        self.handle = h
+
+    def run(self, max_steps, fmax=0.05, climb=False, dt=0.1, dt_max=1.0, maxstep=0.2, check_every=10, record_every=0):
+        """``NudgedElasticBand.run`` (no skin: the cells change, every step builds its lists anew).  ``criterion``: the largest
+        row norm of g over the atom rows (eV / Angstrom, in scaled coordinates) and the cell rows of every interior image;
+        ``maxstep`` bounds the band's whole step over atoms and cells."""
+        return self._run(max_steps, fmax, climb, dt, dt_max, maxstep, check_every, record_every, 0.0)
+
+    def _cell_state(self, *which):
+        nf = self._batch.n_frames
+        shapes = dict(cells=(nf, 3, 3), virials=(nf, 6), cell_forces=(nf, 3, 3), neb_cell_forces=(nf, 3, 3))
+        out = {k: np.empty(shapes[k]) for k in which}
+        self.ctx.check(self.ctx.lib.uf3_neb_get_cell_state(self._live(), *[_lib._p(out[k]) if k in out else None for k in shapes]))
+        return out
+
+    def get_cells(self):
+        """[n_frames, 3, 3] Angstrom: the current cell of every image of every band."""
+        return self._cell_state("cells")["cells"]
+
+    def get_virials(self):
+        """[n_frames, 6]: dE/d(strain) (xx, yy, zz, yz, xz, xy; eV) at the current state."""
+        return self._cell_state("virials")["virials"]
+
+    def get_cell_forces(self):
+        """[n_frames, 3, 3]: the true force on Y = kappa D of every image, -D^-T W / kappa.  (``get_forces``: F D^T.)"""
+        return self._cell_state("cell_forces")["cell_forces"]
+
+    def get_neb_cell_forces(self):
+        """[n_frames, 3, 3]: the cell part of the NEB force g (0 on end points; climbing as in the last run)."""
+        return self._cell_state("neb_cell_forces")["neb_cell_forces"]
+
+    def get_images(self):
+        """The bands at the current positions, each image with its own current cell."""
+        from uf3_amd.data.atoms import Atoms
+        x, cells = self._state("pos")["pos"], self.get_cells()
+        off = self._batch.offsets
+        flat = [Atoms(numbers=a.get_atomic_numbers(), positions=x[off[k]:off[k + 1]], cell=cells[k], pbc=a.get_pbc())
+                for k, a in enumerate(self.frames)]
+        out = [flat[self.band_first[k]:self.band_first[k + 1]] for k in range(len(self.bands))]
+        return out[0] if self._single else out
 
 
 class IDPP(_Bands):
