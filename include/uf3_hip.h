@@ -106,7 +106,7 @@ int uf3_ctx_use_own_stream(uf3_ctx *ctx);
 int uf3_ctx_synchronize(uf3_ctx *ctx);
 const char *uf3_last_error(const uf3_ctx *ctx);
 /* Which sources this binary was compiled from: the first 16 hex digits of the sha256 over uf3_hip.hip, uf3_kernels.h,
- * uf3_feat3.h, uf3_virial_rows.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h, uf3_npt.h, uf3_neb.h, uf3_ssneb.h, uf3_idpp.h, uf3_mc.h, uf3_flux.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
+ * uf3_feat3.h, uf3_virial_rows.h, uf3_device.h, uf3_md.h, uf3_hessian.h, uf3_relax.h, uf3_phonon.h, uf3_npt.h, uf3_neb.h, uf3_idpp.h, uf3_mc.h, uf3_flux.h and this header, concatenated in that order (the Makefile passes it in; "unknown" for a build
  * outside it).  __graft_entry__.build() rebuilds when it differs from the tree's, smoke() prints it. */
 const char *uf3_build_id(void);
 /* timing of the dominant kernel: (re)start / read accumulated HIP-event time in ms and launches */
@@ -637,8 +637,8 @@ int uf3_idpp_create(uf3_ctx *ctx, const uf3_frames *frames, const double *pos, c
                     uf3_neb **out);
 
 /*
- * Nudged elastic bands whose images differ in cell (solid-state NEB; uf3_amd.forcefield.neb.CellNudgedElasticBand; kernels in
- * uf3_ssneb.h): the band of uf3_neb_create in uf3_relax_create's generalised coordinates.  C0 is the cell of a band's image 0;
+ * Nudged elastic bands whose images differ in cell (solid-state NEB; uf3_amd.forcefield.neb.CellNudgedElasticBand; the <true>
+ * instances of uf3_neb.h's kernels): the band of uf3_neb_create in uf3_relax_create's generalised coordinates.  C0 is the cell of a band's image 0;
  * image i has D_i = C0^-1 C_i, q_i = x_i D_i^-1 and the vector u_i = (q_i [n][3], Y_i = kappa D_i [3][3]) of 3 n + 9 numbers; its
  * true force is (F D_i^T, G_i = -D_i^-T W_i / kappa), W the strain derivative of uf3_eval_virial.  t+ = u_{i+1} - u_i and
  * t- = u_i - u_{i-1} as stored over all 3 n + 9 entries (no minimum image); tangent, spring term, climbing image, the one FIRE

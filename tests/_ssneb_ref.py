@@ -1,4 +1,4 @@
-"""NumPy restatement of the device nudged elastic band with changing cells (uf3_amd/csrc/uf3_ssneb.h): tests/_neb_ref.py's band
+"""NumPy restatement of the device nudged elastic band with changing cells (uf3_amd/csrc/uf3_neb.h, the cell instances): tests/_neb_ref.py's band
 in tests/_relax_ref.py's generalised coordinates.  With C0 the cell of a band's first image, image i has D_i = C0^-1 C_i,
 q_i = x_i D_i^-1 and the vector u_i = (q_i, Y_i = kappa D_i); its true force is (F D_i^T, -D_i^-T W_i / kappa).  Differences
 between images as stored over all 3 n + 9 entries, the improved tangent, an optional climbing image, one FIRE per band, the

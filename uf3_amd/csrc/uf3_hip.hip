@@ -29,7 +29,6 @@
 #include "uf3_hessian.h"
 #include "uf3_relax.h"
 #include "uf3_neb.h"
-#include "uf3_ssneb.h"
 #include "uf3_idpp.h"
 #include "uf3_mc.h"
 #include "uf3_phonon.h"
@@ -4555,6 +4554,29 @@ struct uf3_relax : Batch {
 
 extern "C" void uf3_relax_destroy(uf3_relax *r) { driver_destroy(r); }
 
+static double det3(const double *m) {
+    return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
+}
+
+// what uf3_relax_run and uf3_neb_run (who) ask of their arguments, in the order of the parameter list (climb sits in the middle
+// of it, so its test does too: uf3_relax_run has none and passes 0)
+static int fire_run_check(uf3_ctx *c, const std::string &who, int64_t max_steps, double fmax, double dt, double dt_max, double maxstep,
+                          double skin, int climb, int64_t check_every, int64_t record_every, const double *records) {
+    if (max_steps < 0) return fail(c, UF3_EINVAL, who + ": max_steps must be >= 0");
+    if (!(fmax > 0.0) || !std::isfinite(fmax)) return fail(c, UF3_EINVAL, who + ": fmax must be positive and finite");
+    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, UF3_EINVAL, who + ": dt must be positive and finite");
+    if (!(dt_max > 0.0) || !std::isfinite(dt_max)) return fail(c, UF3_EINVAL, who + ": dt_max must be positive and finite");
+    if (!(maxstep > 0.0) || !std::isfinite(maxstep)) return fail(c, UF3_EINVAL, who + ": maxstep must be positive and finite");
+    if (!(skin >= 0.0) || skin > 4.0) return fail(c, UF3_EINVAL, who + ": skin must lie in [0, 4] Angstrom");
+    if (climb != 0 && climb != 1) return fail(c, UF3_EINVAL, who + ": climb must be 0 or 1");
+    if (check_every < 1) return fail(c, UF3_EINVAL, who + ": check_every must be >= 1");
+    if (record_every < 0) return fail(c, UF3_EINVAL, who + ": record_every must be >= 0");
+    if ((record_every > 0) != (records != nullptr))
+        return fail(c, UF3_EINVAL, who + (record_every ? ": records are due but the records buffer is NULL"
+                                                       : ": a records buffer was given but no record is due"));
+    return UF3_OK;
+}
+
 extern "C" int uf3_relax_create(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const uint8_t *fixed,
                                 const double *c1, const double *c2, const double *c3, int relax_cell, uf3_relax **out) {
     const char *who = "uf3_relax_create";
@@ -4574,16 +4596,14 @@ extern "C" int uf3_relax_create(uf3_basis *b, const uf3_frames *fr, const double
         RelaxFrame &S = st[f];
         memset(&S, 0, sizeof(S));
         const double *cl = fr->cells + 9 * (size_t)f;
-        const double det = cl[0] * (cl[4] * cl[8] - cl[5] * cl[7]) - cl[1] * (cl[3] * cl[8] - cl[5] * cl[6]) +
-                           cl[2] * (cl[3] * cl[7] - cl[4] * cl[6]);
         const bool periodic = fr->pbc[3 * f] && fr->pbc[3 * f + 1] && fr->pbc[3 * f + 2];
-        if (relax_cell && periodic && det == 0.0) return fail(c, UF3_EINVAL, "uf3_relax_create: a periodic frame's cell is singular");
+        if (relax_cell && periodic && det3(cl) == 0.0) return fail(c, UF3_EINVAL, "uf3_relax_create: a periodic frame's cell is singular");
         S.cellf = relax_cell && periodic;
         cell_run = cell_run || S.cellf;
-        S.dt = 0.0; S.alpha = UF3_FIRE_ASTART;
+        S.fire.alpha = UF3_FIRE_ASTART; S.fire.first = 1;
         S.e_last = S.fmax_last = std::numeric_limits<double>::quiet_NaN();
         for (int k = 0; k < 9; k++) { S.D[k] = (k % 4 == 0) ? 1.0 : 0.0; S.cell0[k] = cl[k]; }
-        S.first = 1; S.status = UF3_RELAX_RUNNING;
+        S.status = UF3_RELAX_RUNNING;
     }
     HIPCHK(c, hipSetDevice(c->device));
     uf3_relax *r = new uf3_relax();
@@ -4693,17 +4713,8 @@ extern "C" int uf3_relax_run(uf3_relax *r, int64_t max_steps, double fmax, doubl
                              int64_t check_every, int64_t record_every, double *records) {
     if (!r) return fail(nullptr, UF3_EINVAL, "uf3_relax_run: relax is NULL");
     uf3_ctx *c = r->c;
-    if (max_steps < 0) return fail(c, UF3_EINVAL, "uf3_relax_run: max_steps must be >= 0");
-    if (!(fmax > 0.0) || !std::isfinite(fmax)) return fail(c, UF3_EINVAL, "uf3_relax_run: fmax must be positive and finite");
-    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, UF3_EINVAL, "uf3_relax_run: dt must be positive and finite");
-    if (!(dt_max > 0.0) || !std::isfinite(dt_max)) return fail(c, UF3_EINVAL, "uf3_relax_run: dt_max must be positive and finite");
-    if (!(maxstep > 0.0) || !std::isfinite(maxstep)) return fail(c, UF3_EINVAL, "uf3_relax_run: maxstep must be positive and finite");
-    if (!(skin >= 0.0) || skin > 4.0) return fail(c, UF3_EINVAL, "uf3_relax_run: skin must lie in [0, 4] Angstrom");
-    if (check_every < 1) return fail(c, UF3_EINVAL, "uf3_relax_run: check_every must be >= 1");
-    if (record_every < 0) return fail(c, UF3_EINVAL, "uf3_relax_run: record_every must be >= 0");
-    if ((record_every > 0) != (records != nullptr))
-        return fail(c, UF3_EINVAL, record_every ? "uf3_relax_run: records are due but the records buffer is NULL"
-                                                : "uf3_relax_run: a records buffer was given but no record is due");
+    int rc = fire_run_check(c, "uf3_relax_run", max_steps, fmax, dt, dt_max, maxstep, skin, 0, check_every, record_every, records);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     // (skin 0 in a cell run: the MD route's list key holds the cells)
     return with_run_skin(c, r->cell_run ? 0.0 : skin,
@@ -4728,7 +4739,7 @@ extern "C" int uf3_relax_get_state(uf3_relax *r, double *pos, double *cells, dou
     if (cells) memcpy(cells, r->cells.data(), 72 * (size_t)r->n_frames);
     for (int f = 0; f < r->n_frames; f++) {
         if (status) status[f] = r->st_host[f].status;
-        if (steps) steps[f] = r->st_host[f].steps;
+        if (steps) steps[f] = r->st_host[f].fire.steps;
         if (fmax) fmax[f] = r->st_host[f].fmax_last;
     }
     return UF3_OK;
@@ -4750,7 +4761,7 @@ struct uf3_neb : Batch {
     int last_climb = 0;
     bool idpp = false;                          // made by uf3_idpp_create: energies and forces are k_idpp's, not the evaluator's
     DevBuf idpp_cells, idpp_partial;
-    // made by uf3_ssneb_create (uf3_ssneb.h): the cell is part of every image's vector
+    // made by uf3_ssneb_create (k_neb_*<true>): the cell is part of every image's vector
     bool cellb = false;
     DevBuf q, fq, D, vc, G, gc, D_ev, vc_ev, kappa, virials, cells_dev;
 };
@@ -4807,18 +4818,16 @@ static int neb_create(uf3_ctx *c, uf3_basis *b, const uf3_frames *fr, const doub
                 if (!(fr->pbc[3 * f] && fr->pbc[3 * f + 1] && fr->pbc[3 * f + 2]))
                     return fail(c, UF3_EINVAL, img + ": a cell band needs frames periodic along all three axes");
                 const double *cl = fr->cells + 9 * (size_t)f;
-                const double det = cl[0] * (cl[4] * cl[8] - cl[5] * cl[7]) - cl[1] * (cl[3] * cl[8] - cl[5] * cl[6]) +
-                                   cl[2] * (cl[3] * cl[7] - cl[4] * cl[6]);
                 // (singular to rounding: the volume against the product of the row lengths)
-                if (!(std::fabs(det) > 1e-12 * norm3(cl) * norm3(cl + 3) * norm3(cl + 6)))
+                if (!(std::fabs(det3(cl)) > 1e-12 * norm3(cl) * norm3(cl + 3) * norm3(cl + 6)))
                     return fail(c, UF3_EINVAL, img + ": the cell is singular");
             }
         }
         NebBand &S = st[bd];
         memset(&S, 0, sizeof(S));
-        S.dt = 0.0; S.alpha = UF3_FIRE_ASTART; S.spring = spring[bd];
+        S.fire.alpha = UF3_FIRE_ASTART; S.fire.first = 1; S.spring = spring[bd];
         S.crit_last = std::numeric_limits<double>::quiet_NaN();
-        S.first = 1; S.status = UF3_RELAX_RUNNING; S.climbing = -1; S.frame0 = f0; S.n_img = M;
+        S.status = UF3_RELAX_RUNNING; S.climbing = -1; S.frame0 = f0; S.n_img = M;
         for (int j = 0; j < M; j++) frame_band[f0 + j] = bd;
     }
     HIPCHK(c, hipSetDevice(c->device));
@@ -4868,14 +4877,6 @@ extern "C" int uf3_neb_create(uf3_basis *b, const uf3_frames *fr, const double *
 
 // the cell band's own state: D_i = C0^-1 C_i and q_i = x_i D_i^-1 per image (host, once), zero cell velocities, kappa per band
 // (cell_factor null: the band's atom count per image, uf3_relax.h's convention)
-static void ssneb_inv3(const double *m, double *r) {
-    const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
-    const double id = 1.0 / (m[0] * c00 + m[1] * c01 + m[2] * c02);
-    r[0] = c00 * id; r[1] = (m[2] * m[7] - m[1] * m[8]) * id; r[2] = (m[1] * m[5] - m[2] * m[4]) * id;
-    r[3] = c01 * id; r[4] = (m[0] * m[8] - m[2] * m[6]) * id; r[5] = (m[2] * m[3] - m[0] * m[5]) * id;
-    r[6] = c02 * id; r[7] = (m[1] * m[6] - m[0] * m[7]) * id; r[8] = (m[0] * m[4] - m[1] * m[3]) * id;
-}
-
 static int ssneb_setup(uf3_neb *r, const double *pos, const int32_t *band_first_frame, const double *cell_factor, const std::string &who) {
     uf3_ctx *c = r->c;
     r->cellb = true;
@@ -4886,7 +4887,7 @@ static int ssneb_setup(uf3_neb *r, const double *pos, const int32_t *band_first_
         const int f0 = band_first_frame[bd], M = band_first_frame[bd + 1] - f0;
         kappa[bd] = cell_factor ? cell_factor[bd] : (double)(r->offsets[f0 + 1] - r->offsets[f0]);
         double C0i[9];
-        ssneb_inv3(r->cells.data() + 9 * (size_t)f0, C0i);
+        relax_inv3(r->cells.data() + 9 * (size_t)f0, C0i);
         for (int j = 0; j < M; j++) {
             const int f = f0 + j;
             const double *C = r->cells.data() + 9 * (size_t)f;
@@ -4894,7 +4895,7 @@ static int ssneb_setup(uf3_neb *r, const double *pos, const int32_t *band_first_
             for (int a = 0; a < 3; a++)
                 for (int k = 0; k < 3; k++)
                     Df[3 * a + k] = j == 0 ? (a == k ? 1.0 : 0.0) : C0i[3 * a] * C[k] + C0i[3 * a + 1] * C[3 + k] + C0i[3 * a + 2] * C[6 + k];
-            ssneb_inv3(Df, Di);
+            relax_inv3(Df, Di);
             for (int64_t i = r->offsets[f]; i < r->offsets[f + 1]; i++)
                 for (int k = 0; k < 3; k++)
                     q[3 * i + k] = pos[3 * i] * Di[k] + pos[3 * i + 1] * Di[3 + k] + pos[3 * i + 2] * Di[6 + k];
@@ -5034,7 +5035,7 @@ static int neb_fetch_state(uf3_neb *r) {
 
 static NebChunkArgs neb_chunk_args(uf3_neb *r, int climb, int all) {
     NebChunkArgs P;
-    P.pos = r->pos.as<double>(); P.frc = r->frc.as<double>(); P.vel = r->vel.as<double>();
+    P.pos = r->cellb ? r->q.as<double>() : r->pos.as<double>(); P.frc = r->frc.as<double>(); P.vel = r->vel.as<double>();
     P.fixed = r->has_fixed ? r->fixed.as<uint8_t>() : nullptr;
     const ChunkTable &T = r->chunks;
     P.blk_frame = T.blk_frame.as<int>(); P.blk_lo = T.blk_lo.as<long long>(); P.blk_n = T.blk_n.as<int>();
@@ -5042,39 +5043,24 @@ static NebChunkArgs neb_chunk_args(uf3_neb *r, int climb, int all) {
     P.energies = r->energies.as<double>(); P.bands = r->st.as<NebBand>(); P.partial = r->partial.as<double>();
     P.g = r->g.as<double>(); P.cmax = r->cmax.as<double>(); P.img = r->img.as<NebImage>();
     P.climb = climb; P.all = all;
-    return P;
-}
-
-static SsChunkArgs ssneb_chunk_args(uf3_neb *r, int climb, int all) {
-    SsChunkArgs P;
-    P.q = r->q.as<double>(); P.frc = r->frc.as<double>(); P.vel = r->vel.as<double>(); P.virials = r->virials.as<double>();
-    P.D = r->D.as<double>(); P.vc = r->vc.as<double>(); P.kappa = r->kappa.as<double>();
-    const ChunkTable &T = r->chunks;
-    P.blk_frame = T.blk_frame.as<int>(); P.blk_lo = T.blk_lo.as<long long>(); P.blk_n = T.blk_n.as<int>();
-    P.frame_blk = T.frame_blk.as<int>(); P.frame_band = r->frame_band.as<int>(); P.offsets = r->offsets_dev.as<long long>();
-    P.energies = r->energies.as<double>(); P.bands = r->st.as<NebBand>();
+    // (null pointers on a handle without cells)
+    P.virials = r->virials.as<double>(); P.D = r->D.as<double>(); P.vc = r->vc.as<double>(); P.kappa = r->kappa.as<double>();
     P.fq = r->fq.as<double>(); P.G = r->G.as<double>(); P.D_ev = r->D_ev.as<double>(); P.vc_ev = r->vc_ev.as<double>();
-    P.partial = r->partial.as<double>(); P.g = r->g.as<double>(); P.gc = r->gc.as<double>(); P.cmax = r->cmax.as<double>();
-    P.img = r->img.as<NebImage>();
-    P.climb = climb; P.all = all;
+    P.gc = r->gc.as<double>();
     return P;
 }
 
-// the partial and the force launch of an evaluation: k_neb_* or, on a handle of uf3_ssneb_create, k_ssneb_*
-static int neb_launch_forces(uf3_neb *r, const NebChunkArgs &P, const SsChunkArgs &S) {
+// the partial and the force launch of an evaluation (the <true> instances on a handle of uf3_ssneb_create)
+static int neb_launch_forces(uf3_neb *r, const NebChunkArgs &P) {
     uf3_ctx *c = r->c;
     const dim3 grid((unsigned)r->chunks.n_blocks), blk(UF3_RELAX_THREADS);
-    if (r->cellb) {
-        hipLaunchKernelGGL(k_ssneb_partial, grid, blk, 0, c->stream, S);
+    return with_bool(r->cellb, [&](auto CELL) {
+        hipLaunchKernelGGL(k_neb_partial<CELL>, grid, blk, 0, c->stream, P);
         HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(k_ssneb_force, grid, blk, 0, c->stream, S);
-    } else {
-        hipLaunchKernelGGL(k_neb_partial, grid, blk, 0, c->stream, P);
+        hipLaunchKernelGGL(k_neb_force<CELL>, grid, blk, 0, c->stream, P);
         HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(k_neb_force, grid, blk, 0, c->stream, P);
-    }
-    HIPCHK(c, hipGetLastError());
-    return UF3_OK;
+        return (int)UF3_OK;
+    });
 }
 
 // evaluations k = 0 .. max_steps; each but the last may move the bands still running
@@ -5087,7 +5073,6 @@ static int neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt, double
     const int64_t n_rec = rec_every ? max_steps / rec_every + 1 : 0;
     if (n_rec) HIPCHK(c, r->ring.ensure(8 * (size_t)n_rec * row));
     const NebChunkArgs P = neb_chunk_args(r, climb, 0);
-    const SsChunkArgs SP = r->cellb ? ssneb_chunk_args(r, climb, 0) : SsChunkArgs();
     NebBandArgs F;
     F.cmax = r->cmax.as<double>(); F.frame_blk = r->chunks.frame_blk.as<int>(); F.energies = r->energies.as<double>();
     F.img = r->img.as<NebImage>(); F.bands = r->st.as<NebBand>(); F.coef = r->coef.as<NebCoef>(); F.e_last = r->e_last.as<double>();
@@ -5096,13 +5081,10 @@ static int neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt, double
     M.pos = r->pos.as<double>(); M.vel = r->vel.as<double>(); M.g = r->g.as<double>(); M.fixed = P.fixed;
     M.frame_of = r->chunks.frame_of.as<int>(); M.frame_band = r->frame_band.as<int>(); M.bands = r->st.as<NebBand>();
     M.coef = r->coef.as<NebCoef>(); M.n = r->natoms;
-    SsMoveArgs SM;
-    if (r->cellb) {
-        SM.pos = M.pos; SM.q = r->q.as<double>(); SM.vel = M.vel; SM.D = r->D.as<double>(); SM.vc = r->vc.as<double>();
-        SM.cells = r->cells_dev.as<double>(); SM.g = M.g; SM.gc = r->gc.as<double>(); SM.D_ev = r->D_ev.as<double>();
-        SM.vc_ev = r->vc_ev.as<double>(); SM.kappa = r->kappa.as<double>(); SM.frame_of = M.frame_of; SM.frame_band = M.frame_band;
-        SM.offsets = r->offsets_dev.as<long long>(); SM.bands = M.bands; SM.coef = M.coef; SM.n = M.n;
-    }
+    // (null pointers on a handle without cells)
+    M.q = r->q.as<double>(); M.D = r->D.as<double>(); M.vc = r->vc.as<double>(); M.cells = r->cells_dev.as<double>();
+    M.gc = r->gc.as<double>(); M.D_ev = r->D_ev.as<double>(); M.vc_ev = r->vc_ev.as<double>(); M.kappa = r->kappa.as<double>();
+    M.offsets = r->offsets_dev.as<long long>();
     r->last_climb = climb;
     hipLaunchKernelGGL(k_neb_rearm, dim3((unsigned)((nbd + UF3_RELAX_THREADS - 1) / UF3_RELAX_THREADS)), dim3(UF3_RELAX_THREADS), 0, s,
                        r->st.as<NebBand>(), nbd);
@@ -5113,7 +5095,7 @@ static int neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt, double
             int rc = neb_evaluate(r);
             if (rc) return rc;
         }
-        int rl = neb_launch_forces(r, P, SP);
+        int rl = neb_launch_forces(r, P);
         if (rl) return rl;
         F.rec = (n_rec && k % rec_every == 0) ? r->ring.as<double>() + row * (size_t)(k / rec_every) : nullptr;
         F.can_move = k < max_steps;
@@ -5122,9 +5104,12 @@ static int neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt, double
         r->g_valid = false;                     // (frozen bands' rows are older than this evaluation: get_state forms them all)
         if (k == max_steps) break;
         const dim3 mgrid((unsigned)((r->natoms + UF3_RELAX_THREADS - 1) / UF3_RELAX_THREADS));
-        if (r->cellb) hipLaunchKernelGGL(k_ssneb_move, mgrid, dim3(UF3_RELAX_THREADS), 0, s, SM);
-        else hipLaunchKernelGGL(k_neb_move, mgrid, dim3(UF3_RELAX_THREADS), 0, s, M);
-        HIPCHK(c, hipGetLastError());
+        rl = with_bool(r->cellb, [&](auto CELL) {
+            hipLaunchKernelGGL(k_neb_move<CELL>, mgrid, dim3(UF3_RELAX_THREADS), 0, s, M);
+            HIPCHK(c, hipGetLastError());
+            return (int)UF3_OK;
+        });
+        if (rl) return rl;
         r->forces_valid = false;
         if (r->cellb) {                         // (the evaluator and its list build read the cells on the host)
             HIPCHK(c, hipMemcpyAsync(r->cells.data(), r->cells_dev.p, 72 * (size_t)nf, hipMemcpyDeviceToHost, s));
@@ -5162,18 +5147,8 @@ extern "C" int uf3_neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt
                            int climb, int64_t check_every, int64_t record_every, double *records) {
     if (!r) return fail(nullptr, UF3_EINVAL, "uf3_neb_run: neb is NULL");
     uf3_ctx *c = r->c;
-    if (max_steps < 0) return fail(c, UF3_EINVAL, "uf3_neb_run: max_steps must be >= 0");
-    if (!(fmax > 0.0) || !std::isfinite(fmax)) return fail(c, UF3_EINVAL, "uf3_neb_run: fmax must be positive and finite");
-    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, UF3_EINVAL, "uf3_neb_run: dt must be positive and finite");
-    if (!(dt_max > 0.0) || !std::isfinite(dt_max)) return fail(c, UF3_EINVAL, "uf3_neb_run: dt_max must be positive and finite");
-    if (!(maxstep > 0.0) || !std::isfinite(maxstep)) return fail(c, UF3_EINVAL, "uf3_neb_run: maxstep must be positive and finite");
-    if (!(skin >= 0.0) || skin > 4.0) return fail(c, UF3_EINVAL, "uf3_neb_run: skin must lie in [0, 4] Angstrom");
-    if (climb != 0 && climb != 1) return fail(c, UF3_EINVAL, "uf3_neb_run: climb must be 0 or 1");
-    if (check_every < 1) return fail(c, UF3_EINVAL, "uf3_neb_run: check_every must be >= 1");
-    if (record_every < 0) return fail(c, UF3_EINVAL, "uf3_neb_run: record_every must be >= 0");
-    if ((record_every > 0) != (records != nullptr))
-        return fail(c, UF3_EINVAL, record_every ? "uf3_neb_run: records are due but the records buffer is NULL"
-                                                : "uf3_neb_run: a records buffer was given but no record is due");
+    int rc = fire_run_check(c, "uf3_neb_run", max_steps, fmax, dt, dt_max, maxstep, skin, climb, check_every, record_every, records);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (r->idpp) {                              // no lists are built: the context's MD skin is not touched
         if (climb) return fail(c, UF3_EINVAL, "uf3_neb_run: a handle of uf3_idpp_create takes no climbing image");
@@ -5185,9 +5160,7 @@ extern "C" int uf3_neb_run(uf3_neb *r, int64_t max_steps, double fmax, double dt
 }
 
 static int neb_all_forces(uf3_neb *r) {
-    const NebChunkArgs P = neb_chunk_args(r, r->last_climb, 1);
-    const SsChunkArgs SP = r->cellb ? ssneb_chunk_args(r, r->last_climb, 1) : SsChunkArgs();
-    int rc = neb_launch_forces(r, P, SP);
+    int rc = neb_launch_forces(r, neb_chunk_args(r, r->last_climb, 1));
     r->g_valid = rc == UF3_OK;
     return rc;
 }
@@ -5201,7 +5174,7 @@ extern "C" int uf3_neb_get_state(uf3_neb *r, double *pos, double *forces, double
         int rc = neb_evaluate(r);
         if (rc) return rc;
     }
-    // g of every band at these positions, frozen bands included; no state changes (a cell band's forces are F D^T: k_ssneb_partial's)
+    // g of every band at these positions, frozen bands included; no state changes (a cell band's forces are F D^T: k_neb_partial's)
     if ((neb_forces || (forces && r->cellb)) && !r->g_valid) {
         int rc = neb_all_forces(r);
         if (rc) return rc;
@@ -5215,7 +5188,7 @@ extern "C" int uf3_neb_get_state(uf3_neb *r, double *pos, double *forces, double
     if (rc) return rc;
     for (int bd = 0; bd < r->n_bands; bd++) {
         if (status) status[bd] = r->st_host[bd].status;
-        if (steps) steps[bd] = r->st_host[bd].steps;
+        if (steps) steps[bd] = r->st_host[bd].fire.steps;
         if (criterion) criterion[bd] = r->st_host[bd].crit_last;
         if (climbing) climbing[bd] = r->st_host[bd].climbing;
     }

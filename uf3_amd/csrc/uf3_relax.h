@@ -27,17 +27,62 @@
 #define UF3_FIRE_ASTART 0.1
 #define UF3_FIRE_FA 0.99
 
-struct RelaxFrame {                         // one frame's optimiser state (device)
-    double dt, alpha, e_last, fmax_last;   // e_last / fmax_last: energy and criterion at the last evaluation while running
-    double D[9], cell0[9], vc[9];          // deformation (cell = cell0 D), reference cell, velocity of Y = n D
+struct FireState {                          // one optimiser's FIRE state: a frame here, a band in uf3_neb.h
+    double dt, alpha;
     long long steps;
-    int n_pos, first, status, cellf;       // cellf: the cell is a degree of freedom (relax_cell, periodic along all axes)
+    int n_pos, first;
+};
+
+struct FireStep {                           // one move as FIRE decided it: v' = (a v + b g) + dt g; dr = dt v' (* s when the trust
+    double a, b, dt, s;                    // radius cuts: scale)
+    int scale, pad;
+};
+
+// FIRE's state machine, the only copy: the decision for one optimiser's whole vector from its g.v, |g|^2 and |v|^2; S advances
+__device__ __forceinline__ FireStep fire_step(FireState &S, double GV, double GG, double VV, double dt0, double dt_max,
+                                              double maxstep) {
+    double a = 1.0, b = 0.0, dt = S.first ? dt0 : S.dt, alpha = S.alpha;
+    int n_pos = S.n_pos;
+    if (!S.first) {
+        if (GV > 0.0) {
+            a = 1.0 - alpha;
+            b = alpha * sqrt(VV) / sqrt(GG);
+            if (n_pos > UF3_FIRE_NMIN) { dt = fmin(dt * UF3_FIRE_FINC, dt_max); alpha *= UF3_FIRE_FA; }
+            n_pos += 1;
+        } else {
+            a = 0.0; b = 0.0;
+            alpha = UF3_FIRE_ASTART; dt *= UF3_FIRE_FDEC; n_pos = 0;
+        }
+    }
+    // |v'|^2 of v' = a v + (b + dt) g from the sums
+    const double c = b + dt;
+    const double v2 = fmax(a * a * VV + 2.0 * a * c * GV + c * c * GG, 0.0);
+    const double drn = dt * sqrt(v2);
+    const int scale = drn > maxstep;
+    S.dt = dt; S.alpha = alpha; S.n_pos = n_pos; S.first = 0; S.steps += 1;
+    const FireStep K = {a, b, dt, scale ? maxstep / drn : 1.0, scale, 0};
+    return K;
+}
+
+// the kick of one degree of freedom, the only copy: its new velocity, and in dr its move
+__device__ __forceinline__ double fire_kick(const FireStep &K, double v, double g, double &dr) {
+    const double vn = (K.a * v + K.b * g) + K.dt * g;
+    dr = K.dt * vn;
+    if (K.scale) dr *= K.s;
+    return vn;
+}
+
+struct RelaxFrame {                         // one frame's optimiser state (device)
+    FireState fire;
+    double e_last, fmax_last;              // energy and criterion at the last evaluation while running
+    double D[9], cell0[9], vc[9];          // deformation (cell = cell0 D), reference cell, velocity of Y = n D
+    int status, cellf;                     // cellf: the cell is a degree of freedom (relax_cell, periodic along all axes)
 };
 
 struct RelaxCoef {                          // what k_relax_move needs of its frame's decision in this step
-    double a, b, dt, s;                    // v' = (a v + b g) + dt g; dr = dt v' (* s when the trust radius cuts)
+    FireStep k;
     double Dold[9], Dnew[9];               // D at the evaluation (g = F Dold^T) and after the step (x = q Dnew)
-    int move, scale, cellf, pad;
+    int move, cellf;
 };
 
 struct RelaxPartialArgs {
@@ -119,12 +164,22 @@ struct RelaxFrameArgs {
     int can_move;                          // 0 on the run's last evaluation: the convergence test only
 };
 
-__device__ __forceinline__ void relax_inv3(const double *m, double *r) {
+__host__ __device__ __forceinline__ void relax_inv3(const double *m, double *r) {
     const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
     const double id = 1.0 / (m[0] * c00 + m[1] * c01 + m[2] * c02);
     r[0] = c00 * id; r[1] = (m[2] * m[7] - m[1] * m[8]) * id; r[2] = (m[1] * m[5] - m[2] * m[4]) * id;
     r[3] = c01 * id; r[4] = (m[0] * m[8] - m[2] * m[6]) * id; r[5] = (m[2] * m[3] - m[0] * m[5]) * id;
     r[6] = c02 * id; r[7] = (m[1] * m[6] - m[0] * m[7]) * id; r[8] = (m[0] * m[4] - m[1] * m[3]) * id;
+}
+
+// the force on the cell coordinates Y = kappa D: G = -D^-T W / kappa, W the strain derivative as uf3_eval_virial's six numbers
+// (not finite for a singular D)
+__device__ __forceinline__ void relax_cell_force(const double *D, const double *v, double kappa, double G[9]) {
+    const double W[9] = {v[0], v[5], v[4], v[5], v[1], v[3], v[4], v[3], v[2]};
+    double Di[9];
+    relax_inv3(D, Di);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) G[3 * i + j] = -(Di[i] * W[j] + Di[3 + i] * W[3 + j] + Di[6 + i] * W[6 + j]) / kappa;
 }
 
 __global__ void __launch_bounds__(UF3_RELAX_THREADS) k_relax_frame(RelaxFrameArgs A) {
@@ -150,15 +205,8 @@ __global__ void __launch_bounds__(UF3_RELAX_THREADS) k_relax_frame(RelaxFrameArg
 #pragma unroll
             for (int k = 0; k < 9; k++) D[k] = S->D[k];
             if (cellf) {
-                const double *v = A.virials + 6 * f;
-                const double W[9] = {v[0], v[5], v[4], v[5], v[1], v[3], v[4], v[3], v[2]};
-                double Di[9];
-                relax_inv3(D, Di);
-                for (int i = 0; i < 3; i++)
-                    for (int j = 0; j < 3; j++) {
-                        G[3 * i + j] = -(Di[i] * W[j] + Di[3 + i] * W[3 + j] + Di[6 + i] * W[6 + j]) / n;
-                        finite = finite && isfinite(G[3 * i + j]);
-                    }
+                relax_cell_force(D, A.virials + 6 * f, n, G);
+                for (int k = 0; k < 9; k++) finite = finite && isfinite(G[k]);
             }
             double crit = sqrt(s[3]);
             for (int i = 0; i < 3; i++) crit = fmax(crit, sqrt(G[3 * i] * G[3 * i] + G[3 * i + 1] * G[3 * i + 1] + G[3 * i + 2] * G[3 * i + 2]));
@@ -172,31 +220,11 @@ __global__ void __launch_bounds__(UF3_RELAX_THREADS) k_relax_frame(RelaxFrameArg
             } else if (A.can_move) {
                 double GV = s[0], GG = s[1], VV = s[2];
                 for (int k = 0; k < 9; k++) { GV += G[k] * S->vc[k]; GG += G[k] * G[k]; VV += S->vc[k] * S->vc[k]; }
-                double a = 1.0, b = 0.0, dt = S->first ? A.dt0 : S->dt, alpha = S->alpha;
-                int n_pos = S->n_pos;
-                if (!S->first) {
-                    if (GV > 0.0) {
-                        a = 1.0 - alpha;
-                        b = alpha * sqrt(VV) / sqrt(GG);
-                        if (n_pos > UF3_FIRE_NMIN) { dt = fmin(dt * UF3_FIRE_FINC, A.dt_max); alpha *= UF3_FIRE_FA; }
-                        n_pos += 1;
-                    } else {
-                        a = 0.0; b = 0.0;
-                        alpha = UF3_FIRE_ASTART; dt *= UF3_FIRE_FDEC; n_pos = 0;
-                    }
-                }
-                // |v'|^2 of v' = a v + (b + dt) g from the frame's sums
-                const double c = b + dt;
-                const double v2 = fmax(a * a * VV + 2.0 * a * c * GV + c * c * GG, 0.0);
-                const double drn = dt * sqrt(v2);
-                const int scale = drn > A.maxstep;
-                const double sc = scale ? A.maxstep / drn : 1.0;
+                const FireStep step = fire_step(S->fire, GV, GG, VV, A.dt0, A.dt_max, A.maxstep);
                 if (cellf) {
                     for (int k = 0; k < 9; k++) {
-                        const double vk = (a * S->vc[k] + b * G[k]) + dt * G[k];
-                        S->vc[k] = vk;
-                        double dr = dt * vk;
-                        if (scale) dr *= sc;
+                        double dr;
+                        S->vc[k] = fire_kick(step, S->vc[k], G[k], dr);
                         S->D[k] = D[k] + dr / n;
                     }
                     for (int i = 0; i < 3; i++)
@@ -204,8 +232,7 @@ __global__ void __launch_bounds__(UF3_RELAX_THREADS) k_relax_frame(RelaxFrameArg
                             A.cells[9 * f + 3 * i + j] = S->cell0[3 * i] * S->D[j] + S->cell0[3 * i + 1] * S->D[3 + j] +
                                                          S->cell0[3 * i + 2] * S->D[6 + j];
                 }
-                S->dt = dt; S->alpha = alpha; S->n_pos = n_pos; S->first = 0; S->steps += 1;
-                K->a = a; K->b = b; K->dt = dt; K->s = sc; K->scale = scale;
+                K->k = step;
                 for (int k = 0; k < 9; k++) { K->Dold[k] = D[k]; K->Dnew[k] = S->D[k]; }
                 move = 1;
             }
@@ -236,18 +263,13 @@ __global__ void __launch_bounds__(UF3_RELAX_THREADS) k_relax_move(RelaxMoveArgs 
     const RelaxCoef *K = A.coef + A.frame_of[i];
     if (!K->move || (A.fixed && A.fixed[i])) return;
     const bool cellf = K->cellf != 0;
-    double F[3], g[3], v[3], dr[3];
+    double F[3], g[3], dr[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) F[k] = A.frc[3 * i + k];
     relax_g(F, K->Dold, cellf, false, g);
-    const double a = K->a, b = K->b, dt = K->dt, s = K->s;
+    const FireStep step = K->k;
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        v[k] = (a * A.vel[3 * i + k] + b * g[k]) + dt * g[k];
-        A.vel[3 * i + k] = v[k];
-        dr[k] = dt * v[k];
-        if (K->scale) dr[k] *= s;
-    }
+    for (int k = 0; k < 3; k++) A.vel[3 * i + k] = fire_kick(step, A.vel[3 * i + k], g[k], dr[k]);
     if (cellf) {
         double q[3];
 #pragma unroll

@@ -29,7 +29,7 @@ turns (an exchange, a dumbbell rotation, a ring).  ``idpp_interpolate`` relaxes 
     images, info = neb.idpp_interpolate(initial, final, 7)
 
 ``CellNudgedElasticBand`` is the band whose images differ in cell (solid-state NEB: solid-solid transformations, ideal shear,
-any path whose saddle wants another cell than its ends; ``uf3_ssneb_create``, ``uf3_amd/csrc/uf3_ssneb.h``).  It works in
+any path whose saddle wants another cell than its ends; ``uf3_ssneb_create``, the cell instances of ``uf3_amd/csrc/uf3_neb.h``).  It works in
 ``Relaxation(relax_cell=True)``'s generalised coordinates: with C0 the cell of a band's first image, image i has
 D_i = C0^-1 C_i, q_i = x_i D_i^-1 and the vector u_i = (q_i, Y_i = kappa D_i) of 3 N + 9 numbers, kappa the band's
 ``cell_factor`` (default N, the relaxer's; Sheppard et al.'s Jacobian is volume^(1/3) N^(1/6)); its true force is
