@@ -229,3 +229,48 @@ def test_run_rejects_a_thermo_buffer_that_does_not_match():
         assert lib.uf3_md_run(h, 10, -1.0, 0.0, 0.0, 0, 0.5, 0, 0, None) == 1
         assert "dt" in lib.uf3_last_error(dyn.ctx.handle).decode()
         assert dyn.step == 0
+
+
+def test_run_arguments_are_checked_in_one_order_under_each_entry_s_name():
+    """Two bad arguments at once: the message is that of the one checked first, under the prefix of the entry whose check it is."""
+    calc = _unary()
+    w16 = synthetic.lattice_frame("bcc", (2, 2, 2), 3.165, [74], seed=3)
+    with md.MolecularDynamics(calc, [w16], 1.0, masses=MASSES) as dyn:
+        lib, h = dyn.ctx.lib, dyn.handle
+        buf, done = _lib._p(np.zeros((4, 1, 6))), C.c_int64(-1)
+
+        def said(rc):
+            assert rc == 1
+            return lib.uf3_last_error(dyn.ctx.handle).decode()
+
+        def run(n=4, dt=1.0, temp=0.0, gamma=0.0, skin=0.5, every=0, thermo=None):
+            return said(lib.uf3_md_run(h, n, dt, temp, gamma, 0, skin, every, 0, thermo))
+
+        def flux(n=4, dt=1.0, every=0, flux_every=0, out=None):
+            return said(lib.uf3_md_run_flux(h, n, dt, 0.0, 0.0, 0, 0.5, every, 0, None, flux_every, out))
+
+        def grade(n=4, dt=1.0, every=0, grade_every=0, stop=0.0, out=None):
+            return said(lib.uf3_md_run_grade(h, n, dt, 0.0, 0.0, 0, 0.5, every, 0, None, None, grade_every, stop, out, C.byref(done)))
+
+        # the sampler's own checks come first, under its entry's name
+        assert flux(n=-1, flux_every=-2) == "uf3_md_run_flux: flux_every must be >= 0"
+        assert flux(n=-1, flux_every=2, out=buf) == "uf3_md_run_flux: a flux buffer was given but no record is due"
+        assert flux(n=4, dt=-1.0, flux_every=2) == "uf3_md_run_flux: flux records are due but the flux buffer is NULL"
+        assert grade(n=-1, grade_every=-2) == "uf3_md_run_grade: grade_every must be >= 0"
+        assert grade(dt=-1.0, stop=float("nan")) == "uf3_md_run_grade: grade_stop is not a number"
+        assert grade(n=4, dt=-1.0, grade_every=2) == "uf3_md_run_grade: grade records are due but the grades buffer is NULL"
+        assert grade(n=1, dt=-1.0, grade_every=2, out=buf) == "uf3_md_run_grade: a grades buffer was given but no record is due"
+        assert grade(n=4, dt=-1.0, grade_every=2, out=buf) == "uf3_md_run_grade: null argument (w)"
+        # the shared checks, in the order of the parameter list, under uf3_md_run's name from all three entries
+        for entry in (run, flux, grade):
+            assert entry(n=-1, dt=-1.0) == "uf3_md_run: n_steps must be >= 0"
+            assert entry(dt=-1.0, every=-1) == "uf3_md_run: dt must be positive and finite"
+            assert entry(every=-1) == "uf3_md_run: thermo_every must be >= 0"
+            assert entry(every=2) == "uf3_md_run: thermo records are due but the thermo buffer is NULL"
+        assert run(dt=-1.0, temp=-5.0) == "uf3_md_run: dt must be positive and finite"
+        assert run(temp=-5.0, gamma=-1.0) == "uf3_md_run: temperature must be finite and >= 0"
+        assert run(gamma=-1.0, every=-1) == "uf3_md_run: friction must be finite and >= 0"
+        assert run(every=-1, skin=9.0) == "uf3_md_run: thermo_every must be >= 0"
+        assert run(skin=9.0, every=2) == "uf3_md_run: skin must lie in [0, 4] Angstrom"
+        assert run(every=5, thermo=buf) == "uf3_md_run: a thermo buffer was given but no record is due"
+        assert dyn.step == 0 and done.value == 0

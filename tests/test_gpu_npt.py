@@ -292,3 +292,29 @@ def test_atoms_and_wrapped_positions_use_the_current_cell():
         tr_k = md.KE_UNIT * float(np.sum(m * np.sum(v * v, axis=1)))
         assert rec["pressure"][-1, 0] == pytest.approx((tr_k - w[0][:3].sum()) / (3 * dyn.volumes[0]), rel=1e-8, abs=1e-10)
         assert rec["cell_scale"][-1, 0] == s
+
+
+def test_run_arguments_are_checked_in_the_order_of_the_parameter_list():
+    """Two bad arguments at once: the message is that of the one checked first -- the barostat's four between friction and
+    thermo_every -- under uf3_md_run_npt's name."""
+    calc = _unary()
+    with _npt(calc, [synthetic.lattice_frame("bcc", (2, 2, 2), 3.165, [74], seed=3)]) as dyn:
+        lib, h = dyn.ctx.lib, dyn.handle
+
+        def run(n=4, dt=1.0, temp=300.0, gamma=0.0, p0=0.0, tau=500.0, gamma_p=0.0, t_piston=300.0, skin=0.5, every=0, thermo=None):
+            assert lib.uf3_md_run_npt(h, n, dt, temp, gamma, p0, tau, gamma_p, t_piston, 0, skin, every, thermo) == 1
+            return lib.uf3_last_error(dyn.ctx.handle).decode()
+
+        assert run(n=-1, dt=-1.0) == "uf3_md_run_npt: n_steps must be >= 0"
+        assert run(dt=-1.0, temp=-5.0) == "uf3_md_run_npt: dt must be positive and finite"
+        assert run(temp=-5.0, gamma=-1.0) == "uf3_md_run_npt: temperature must be finite and >= 0"
+        assert run(gamma=-1.0, p0=float("nan")) == "uf3_md_run_npt: friction must be finite and >= 0"
+        assert run(p0=float("nan"), tau=0.0) == "uf3_md_run_npt: pressure must be finite"
+        assert run(tau=0.0, gamma_p=-1.0) == "uf3_md_run_npt: barostat time must be positive and finite"
+        assert run(gamma_p=-1.0, t_piston=0.0) == "uf3_md_run_npt: barostat friction must be finite and >= 0"
+        assert run(t_piston=0.0, every=-1) == "uf3_md_run_npt: piston temperature must be positive and finite"
+        assert run(every=-1, skin=9.0) == "uf3_md_run_npt: thermo_every must be >= 0"
+        assert run(skin=9.0, every=2) == "uf3_md_run_npt: skin must lie in [0, 4] Angstrom"
+        assert run(every=2) == "uf3_md_run_npt: thermo records are due but the thermo buffer is NULL"
+        assert run(every=5, thermo=_lib._p(np.zeros((4, 1, 17)))) == "uf3_md_run_npt: a thermo buffer was given but no record is due"
+        assert dyn.step == 0

@@ -4081,29 +4081,143 @@ extern "C" int uf3_md_init_velocities(uf3_md *md, double temperature_K, uint64_t
     return UF3_OK;
 }
 
-// one k_md_step launch (+ the frame sums of a thermo record when `record` >= 0)
-static int md_launch(uf3_md *md, MdStepArgs &A, bool langevin, int64_t record, int width) {
-    uf3_ctx *c = md->c;
-    const bool thermo = record >= 0;
-    const dim3 g((unsigned)((md->natoms + 255) / 256)), blk(256);
-    if (langevin) {
-        if (thermo) hipLaunchKernelGGL((k_md_step<true, true>), g, blk, 0, c->stream, A);
-        else hipLaunchKernelGGL((k_md_step<true, false>), g, blk, 0, c->stream, A);
-    } else {
-        if (thermo) hipLaunchKernelGGL((k_md_step<false, true>), g, blk, 0, c->stream, A);
-        else hipLaunchKernelGGL((k_md_step<false, false>), g, blk, 0, c->stream, A);
-    }
-    HIPCHK(c, hipGetLastError());
-    if (thermo) {
-        hipLaunchKernelGGL(k_md_thermo, dim3((unsigned)md->n_frames), dim3(UF3_MD_THREADS), 0, c->stream, (const double *)md->kin.as<double>(),
-                           (long long)md->natoms, (const int64_t *)md->offsets_dev.as<int64_t>(), (const double *)md->energies.as<double>(),
-                           (const double *)md->virials.as<double>(), md->ring.as<double>() + (size_t)record * md->n_frames * width, width);
-        HIPCHK(c, hipGetLastError());
-    }
-    return UF3_OK;
+// ---- the run loop of uf3_md_run, uf3_md_run_flux, uf3_md_run_grade and uf3_md_run_npt ----------------------
+// what a run asks of each of its record buffers (thermo, flux, grade): given exactly when records are due
+static int md_records_check(uf3_ctx *c, const std::string &who, const char *what, const char *buffer, int64_t due, const void *given) {
+    if ((due > 0) == (given != nullptr)) return UF3_OK;
+    return fail(c, UF3_EINVAL, due > 0 ? who + ": " + what + " records are due but the " + buffer + " buffer is NULL"
+                                       : who + ": a " + buffer + " buffer was given but no record is due");
 }
 
-struct FluxArgs;
+struct NptBaro { double p0, tau, gamma_p, Tp; };        // pressure, barostat time and friction, piston temperature
+
+// what the four entries (who) ask of a run's arguments, in the order of uf3_md_run_npt's parameter list: the barostat's four sit
+// in the middle of it, so their tests do too (baro null: a constant-volume run has none)
+static int md_run_check(uf3_ctx *c, const std::string &who, int64_t n_steps, double dt, double T, double gamma, const NptBaro *baro,
+                        int64_t every, double skin, const double *thermo) {
+    if (n_steps < 0) return fail(c, UF3_EINVAL, who + ": n_steps must be >= 0");
+    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, UF3_EINVAL, who + ": dt must be positive and finite");
+    if (!(T >= 0.0) || !std::isfinite(T)) return fail(c, UF3_EINVAL, who + ": temperature must be finite and >= 0");
+    if (!(gamma >= 0.0) || !std::isfinite(gamma)) return fail(c, UF3_EINVAL, who + ": friction must be finite and >= 0");
+    if (baro) {
+        if (!std::isfinite(baro->p0)) return fail(c, UF3_EINVAL, who + ": pressure must be finite");
+        if (!(baro->tau > 0.0) || !std::isfinite(baro->tau)) return fail(c, UF3_EINVAL, who + ": barostat time must be positive and finite");
+        if (!(baro->gamma_p >= 0.0) || !std::isfinite(baro->gamma_p)) return fail(c, UF3_EINVAL, who + ": barostat friction must be finite and >= 0");
+        if (!(baro->Tp > 0.0) || !std::isfinite(baro->Tp)) return fail(c, UF3_EINVAL, who + ": piston temperature must be positive and finite");
+    }
+    if (every < 0) return fail(c, UF3_EINVAL, who + ": thermo_every must be >= 0");
+    if (!(skin >= 0.0) || skin > 4.0) return fail(c, UF3_EINVAL, who + ": skin must lie in [0, 4] Angstrom");
+    return md_records_check(c, who, "thermo", "thermo", every ? n_steps / every : 0, thermo);
+}
+
+// A run without samples (uf3_md_run, uf3_md_run_npt), and what a sampler is: a period, and what the loop calls
+struct MdSampler {
+    int64_t every = 0;                          // a sample of the closed state after every every-th step (0: none)
+    int64_t *steps_done = nullptr;              // where the number of completed steps goes (uf3_md_run_grade)
+    int prepare() { return UF3_OK; }            // the ring of the run's records, the lists' workspace
+    int sample(int64_t, bool &) { return UF3_OK; }      // record s (0-based); true in `stop` when it ends the run
+    int copy_out() { return UF3_OK; }           // queues the records' way to the caller
+};
+
+// The loop every run is.  E, the ensemble: prepare(n_rec) (its buffers, and F(t) of the state the run starts from), launch(close,
+// open, step, record) (what lies between two force calls, + the frame sums of thermo record `record` >= 0), forces(k) (the
+// evaluator for step k), moved() (the validity flags an opening launch drops) and copy_out() (what else the caller gets back).
+// S, the sampler (above): the launch that closes a sampled step does not open the next one, and the sample sits between the
+// two launches.  That is the split a run boundary makes anyway: the trajectory's bits do not change.  A sample that stops the run
+// ends it there: the state is the closed one the sample saw, the thermo records due so far are copied out.
+template <class Ensemble, class Sampler>
+static int md_steps(uf3_md *md, int64_t n_steps, int64_t every, int width, double *thermo, Ensemble &E, Sampler &S) {
+    uf3_ctx *c = md->c;
+    const int64_t n_rec = every ? n_steps / every : 0, t0 = md->step;
+    int rc = S.prepare();
+    if (rc) return rc;
+    if (n_rec) HIPCHK(c, md->ring.ensure(8 * (size_t)n_rec * md->n_frames * width));
+    rc = E.prepare(n_rec);
+    if (rc) return rc;
+    // after `done` steps of the run: the thermo record its close fills (-1: none), whether a sample is due, and the run's end
+    auto record = [&](int64_t done) { return done && every && done % every == 0 ? done / every - 1 : -1; };
+    auto sampled = [&](int64_t done) { return done && S.every && done % S.every == 0; };
+    auto finish = [&](int64_t done) {
+        const int64_t due = every ? done / every : 0;
+        int rc = S.copy_out();
+        if (rc) return rc;
+        if (due) HIPCHK(c, hipMemcpyAsync(thermo, md->ring.p, 8 * (size_t)due * md->n_frames * width, hipMemcpyDeviceToHost, c->stream));
+        rc = E.copy_out();
+        if (rc) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return (int)UF3_OK;
+    };
+    for (int64_t k = 1; k <= n_steps; k++) {
+        // closes step k - 1 of the run (its record, if due) and opens step k
+        const int64_t step = t0 + k - 1;
+        if (sampled(k - 1)) {
+            rc = E.launch(1, 0, step, record(k - 1));
+            // step k - 1 is closed and nothing has moved since its forces: a closed state, whatever happens below -- an error
+            // leaves the state of a run that ended here, which a later run goes on from
+            md->step = step;
+            if (rc) return rc;
+            if (S.steps_done) *S.steps_done = k - 1;
+            bool stop = false;
+            rc = S.sample((k - 1) / S.every - 1, stop);
+            if (rc) return rc;
+            if (stop) return finish(k - 1);
+            rc = E.launch(0, 1, step, -1);
+        } else
+            rc = E.launch(k > 1, 1, step, record(k - 1));
+        E.moved();
+        md->step = step;
+        if (rc) return rc;
+        rc = E.forces(k);
+        if (rc) return rc;
+    }
+    // the closing half of the last step
+    rc = E.launch(1, 0, t0 + n_steps - 1, record(n_steps));
+    if (rc) return rc;
+    md->step = t0 + n_steps;
+    if (S.steps_done) *S.steps_done = n_steps;
+    if (sampled(n_steps)) {
+        bool stop;
+        rc = S.sample(n_steps / S.every - 1, stop);
+        if (rc) return rc;
+    }
+    return finish(n_steps);
+}
+
+// NVE / Langevin: one k_md_step launch between two force calls
+struct MdVerlet {
+    uf3_md *md; MdStepArgs A; bool langevin, stress; int64_t every; int width;
+    MdVerlet(uf3_md *md, double dt, double T, double gamma, uint64_t seed, int64_t every, bool stress)
+        : md(md), langevin(gamma > 0.0), stress(stress), every(every), width(stress ? 14 : 2) {
+        A.pos = md->pos.as<double>(); A.vel = md->vel.as<double>(); A.frc = md->frc.as<double>(); A.inv_m = md->inv_m.as<double>();
+        A.n = md->natoms; A.dt = dt;
+        A.c = std::exp(-gamma * dt); A.kT = UF3_MD_KB * T; A.seed = (unsigned long long)seed;
+    }
+    int prepare(int64_t n_rec) {
+        if (n_rec) HIPCHK(md->c, md->kin.ensure(56 * (size_t)md->natoms));
+        A.kin = md->kin.as<double>();
+        return md->forces_valid ? (int)UF3_OK : md_forces(md, false);
+    }
+    int launch(int close, int open, int64_t step, int64_t record) {
+        uf3_ctx *c = md->c;
+        A.step = (unsigned long long)step; A.close = close; A.open = open;
+        const dim3 g((unsigned)((md->natoms + 255) / 256)), blk(256);
+        with_bool(langevin, [&](auto L) { return with_bool(record >= 0, [&](auto T) {
+            hipLaunchKernelGGL((k_md_step<L, T>), g, blk, 0, c->stream, A);
+            return (int)UF3_OK; }); });
+        HIPCHK(c, hipGetLastError());
+        if (record >= 0) {
+            hipLaunchKernelGGL(k_md_thermo, dim3((unsigned)md->n_frames), dim3(UF3_MD_THREADS), 0, c->stream, (const double *)md->kin.as<double>(),
+                               (long long)md->natoms, (const int64_t *)md->offsets_dev.as<int64_t>(), (const double *)md->energies.as<double>(),
+                               (const double *)md->virials.as<double>(), md->ring.as<double>() + (size_t)record * md->n_frames * width, width);
+            HIPCHK(c, hipGetLastError());
+        }
+        return UF3_OK;
+    }
+    int forces(int64_t k) { return md_forces(md, stress && every && k % every == 0); }
+    void moved() { md->forces_valid = false; }
+    int copy_out() { return UF3_OK; }
+};
+
 static int lists_prepare(uf3_basis *b, const uf3_frames *fr, ListWork &W, const int32_t *d_z, const double *c1, const double *c2,
                          const double *c3, const char *who, const char *what, FluxArgs &F, bool model = true);
 static int flux_sample(uf3_ctx *c, ListWork &W, FluxArgs &F, bool headroom, const char *who);
@@ -4111,156 +4225,93 @@ static int site_grade_sample(uf3_basis *b, ListWork &W, FluxArgs &F, bool headro
                              double *d_grade, const int64_t *d_offsets, int n_out, double *d_fmax, int32_t *d_fargmax,
                              double *d_pair, const std::function<int()> &after);
 
-// the grade sampler of a run (uf3_md_run_grade): W on the device, the period, the stop threshold (<= 0: none), the caller's
-// records [n_samples][n_frames][2] and where the number of completed steps goes
-struct MdGrade {
-    const double *d_w;
-    int64_t every;
-    double stop;
-    double *out;
-    int64_t *steps_done;
+// uf3_md_run_flux: one heat-current record [n_frames][6] per sample (velocities at integer time, the positions the forces belong
+// to), copied out at the end of the run
+struct MdFluxSampler : MdSampler {
+    uf3_md *md; int64_t n_flux; double *out; FluxArgs F;
+    MdFluxSampler(uf3_md *md, int64_t n_steps, int64_t flux_every, double *flux)
+        : md(md), n_flux(flux_every ? n_steps / flux_every : 0), out(flux) { every = flux_every; }
+    int prepare() {
+        if (!n_flux) return UF3_OK;
+        HIPCHK(md->c, md->flux_ring.ensure(48 * (size_t)n_flux * md->n_frames));
+        int rc = lists_prepare(md->b, &md->fr, md->fx, md->z.as<int32_t>(), md->c1.data(), md->c2.data(), md->c3.data(), "uf3_md_run_flux", "batch", F);
+        F.pos = md->pos.as<double>(); F.vel = md->vel.as<double>(); F.mass = md->mass.as<double>(); F.w = nullptr;
+        return rc;
+    }
+    int sample(int64_t s, bool &) {
+        F.flux = md->flux_ring.as<double>() + (size_t)s * md->n_frames * 6;
+        return flux_sample(md->c, md->fx, F, true, "uf3_md_run_flux");
+    }
+    int copy_out() {
+        uf3_ctx *c = md->c;
+        if (n_flux) HIPCHK(c, hipMemcpyAsync(out, md->flux_ring.p, 48 * (size_t)n_flux * md->n_frames, hipMemcpyDeviceToHost, c->stream));
+        return UF3_OK;
+    }
 };
 
-// one heat-current record of the closed state (velocities at integer time, the positions the forces belong to)
-static int md_flux_sample(uf3_md *md, FluxArgs &F, int64_t record) {
-    F.flux = md->flux_ring.as<double>() + (size_t)record * md->n_frames * 6;
-    return flux_sample(md->c, md->fx, F, true, "uf3_md_run_flux");
-}
-
-// flux_every > 0 (uf3_md_run_flux): the launch that closes a sampled step does not open the next one; the sample sits
-// between the two launches.  That is the split a run boundary makes anyway: the trajectory's bits do not change.
-// G (uf3_md_run_grade; never together with flux_every): grade samples at the same place.  A sample whose largest grade exceeds
-// G->stop ends the run there: the state is the closed one the sample saw, the records due so far are copied out.
-static int md_run(uf3_md *md, int64_t n_steps, double dt, double T, double gamma, uint64_t seed, int64_t every, bool stress,
-                  double *thermo, int64_t flux_every = 0, double *flux = nullptr, const MdGrade *G = nullptr) {
-    uf3_ctx *c = md->c;
-    const int width = stress ? 14 : 2;
-    const int64_t n_rec = every ? n_steps / every : 0;
-    const int64_t n_flux = flux_every ? n_steps / flux_every : 0;
-    const int64_t n_grade = G && G->every ? n_steps / G->every : 0;
-    if (G) *G->steps_done = 0;
-    FluxArgs F;
-    if (n_grade) {
-        HIPCHK(c, md->grade.ensure(8 * (size_t)md->natoms));
-        HIPCHK(c, md->grade_ring.ensure(16 * (size_t)n_grade * md->n_frames));
-        int rc = lists_prepare(md->b, &md->fr, md->fx, md->z.as<int32_t>(), nullptr, nullptr, nullptr, "uf3_md_run_grade", "batch", F, false);
-        if (rc) return rc;
-        F.pos = md->pos.as<double>();
+// uf3_md_run_grade: W on the device, the stop threshold (<= 0: none) and the caller's records [n_samples][n_frames][2].  A
+// sample's record is in the caller's array when sample() returns (the copy is queued in front of the sample's own synchronisation)
+struct MdGradeSampler : MdSampler {
+    uf3_md *md; int64_t n_grade; const double *d_w; double stop_above, *out; FluxArgs F;
+    MdGradeSampler(uf3_md *md, int64_t n_steps, const double *d_w, int64_t grade_every, double grade_stop, double *grades, int64_t *done)
+        : md(md), n_grade(grade_every ? n_steps / grade_every : 0), d_w(d_w), stop_above(grade_stop), out(grades) {
+        every = grade_every; steps_done = done;
     }
-    // sample s (0-based) of the closed state; true in `stop` when it ends the run.  Its record is in the caller's array when
-    // this returns (the copy is queued in front of the sample's own synchronisation).
-    auto grade_sample = [&](int64_t s, bool &stop) {
+    int prepare() {
+        if (!n_grade) return UF3_OK;
+        HIPCHK(md->c, md->grade.ensure(8 * (size_t)md->natoms));
+        HIPCHK(md->c, md->grade_ring.ensure(16 * (size_t)n_grade * md->n_frames));
+        int rc = lists_prepare(md->b, &md->fr, md->fx, md->z.as<int32_t>(), nullptr, nullptr, nullptr, "uf3_md_run_grade", "batch", F, false);
+        F.pos = md->pos.as<double>();
+        return rc;
+    }
+    int sample(int64_t s, bool &stop) {
+        uf3_ctx *c = md->c;
         const size_t rec = 2 * (size_t)md->n_frames;
-        double *d_rec = md->grade_ring.as<double>() + (size_t)s * rec, *h_rec = G->out + (size_t)s * rec;
-        int rc = site_grade_sample(md->b, md->fx, F, true, "uf3_md_run_grade", G->d_w, md->grade.as<double>(),
+        double *d_rec = md->grade_ring.as<double>() + (size_t)s * rec, *h_rec = out + (size_t)s * rec;
+        int rc = site_grade_sample(md->b, md->fx, F, true, "uf3_md_run_grade", d_w, md->grade.as<double>(),
                                    md->offsets_dev.as<int64_t>(), md->n_frames, nullptr, nullptr, d_rec, [&] {
             HIPCHK(c, hipMemcpyAsync(h_rec, d_rec, 8 * rec, hipMemcpyDeviceToHost, c->stream));
             return (int)UF3_OK;
         });
         if (rc) return rc;
         stop = false;
-        if (G->stop > 0.0)
-            for (int f = 0; f < md->n_frames; f++) stop = stop || h_rec[2 * (size_t)f] > G->stop;
-        return (int)UF3_OK;
-    };
-    // the end of a run that a sample stopped after `done` steps: the thermo records due so far
-    auto stopped = [&](int64_t done) {
-        *G->steps_done = done;
-        const int64_t due = every ? done / every : 0;
-        if (due) HIPCHK(c, hipMemcpyAsync(thermo, md->ring.p, 8 * (size_t)due * md->n_frames * width, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return (int)UF3_OK;
-    };
-    if (n_flux) {
-        HIPCHK(c, md->flux_ring.ensure(48 * (size_t)n_flux * md->n_frames));
-        int rc = lists_prepare(md->b, &md->fr, md->fx, md->z.as<int32_t>(), md->c1.data(), md->c2.data(), md->c3.data(), "uf3_md_run_flux", "batch", F);
-        if (rc) return rc;
-        F.pos = md->pos.as<double>(); F.vel = md->vel.as<double>(); F.mass = md->mass.as<double>(); F.w = nullptr;
+        if (stop_above > 0.0)
+            for (int f = 0; f < md->n_frames; f++) stop = stop || h_rec[2 * (size_t)f] > stop_above;
+        return UF3_OK;
     }
-    if (n_rec) {
-        HIPCHK(c, md->ring.ensure(8 * (size_t)n_rec * md->n_frames * width));
-        HIPCHK(c, md->kin.ensure(56 * (size_t)md->natoms));
-    }
-    if (!md->forces_valid) {
-        int rc = md_forces(md, false);
-        if (rc) return rc;
-    }
-    const bool langevin = gamma > 0.0;
-    MdStepArgs A;
-    A.pos = md->pos.as<double>(); A.vel = md->vel.as<double>(); A.frc = md->frc.as<double>(); A.inv_m = md->inv_m.as<double>();
-    A.kin = md->kin.as<double>(); A.n = md->natoms; A.dt = dt;
-    A.c = std::exp(-gamma * dt); A.kT = UF3_MD_KB * T; A.seed = (unsigned long long)seed;
-    const int64_t t0 = md->step;
-    for (int64_t k = 1; k <= n_steps; k++) {
-        // closes step k - 1 of the run (its record, if due) and opens step k
-        A.step = (unsigned long long)(t0 + k - 1); A.close = k > 1; A.open = 1;
-        const bool rec = k > 1 && every && (k - 1) % every == 0;
-        int rc;
-        if (n_flux && k > 1 && (k - 1) % flux_every == 0) {
-            A.open = 0;
-            rc = md_launch(md, A, langevin, rec ? (k - 1) / every - 1 : -1, width);
-            // step k - 1 is closed and nothing has moved since its forces: an error below leaves the state of a run that
-            // ended here, which a later run goes on from
-            md->step = t0 + k - 1;
-            if (rc) return rc;
-            rc = md_flux_sample(md, F, (k - 1) / flux_every - 1);
-            if (rc) return rc;
-            A.close = 0; A.open = 1;
-            rc = md_launch(md, A, langevin, -1, width);
-        } else if (n_grade && k > 1 && (k - 1) % G->every == 0) {
-            A.open = 0;
-            rc = md_launch(md, A, langevin, rec ? (k - 1) / every - 1 : -1, width);
-            md->step = t0 + k - 1;              // (as above: a closed state, whatever happens below)
-            if (rc) return rc;
-            *G->steps_done = k - 1;
-            bool stop;
-            rc = grade_sample((k - 1) / G->every - 1, stop);
-            if (rc) return rc;
-            if (stop) return stopped(k - 1);
-            A.close = 0; A.open = 1;
-            rc = md_launch(md, A, langevin, -1, width);
-        } else
-            rc = md_launch(md, A, langevin, rec ? (k - 1) / every - 1 : -1, width);
-        md->forces_valid = false;
-        md->step = t0 + k - 1;
-        if (rc) return rc;
-        rc = md_forces(md, stress && every && k % every == 0);
-        if (rc) return rc;
-    }
-    // the closing half-kick of the last step
-    A.step = (unsigned long long)(t0 + n_steps - 1); A.close = 1; A.open = 0;
-    const bool rec = every && n_steps % every == 0;
-    int rc = md_launch(md, A, langevin, rec ? n_steps / every - 1 : -1, width);
-    if (rc) return rc;
-    md->step = t0 + n_steps;
-    if (n_flux && n_steps % flux_every == 0) {
-        rc = md_flux_sample(md, F, n_steps / flux_every - 1);
-        if (rc) return rc;
-    }
-    if (G) *G->steps_done = n_steps;
-    if (n_grade && n_steps % G->every == 0) {
-        bool stop;
-        rc = grade_sample(n_steps / G->every - 1, stop);
-        if (rc) return rc;
-    }
-    if (n_flux) HIPCHK(c, hipMemcpyAsync(flux, md->flux_ring.p, 48 * (size_t)n_flux * md->n_frames, hipMemcpyDeviceToHost, c->stream));
-    if (n_rec) HIPCHK(c, hipMemcpyAsync(thermo, md->ring.p, 8 * (size_t)n_rec * md->n_frames * width, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return UF3_OK;
-}
+};
 
+// what the three constant-volume entries share, behind the checks of their own sampler
+template <class Sampler>
 static int md_run_entry(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
-                        double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t flux_every, double *flux,
-                        const MdGrade *G = nullptr);
+                        double skin, int64_t thermo_every, int with_stress, double *thermo, Sampler &&S) {
+    uf3_ctx *c = md->c;
+    int rc = md_run_check(c, "uf3_md_run", n_steps, dt_fs, temperature_K, friction_per_fs, nullptr, thermo_every, skin, thermo);
+    if (rc) return rc;
+    if (n_steps == 0) return UF3_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return with_run_skin(c, skin, [&] {
+        MdVerlet E(md, dt_fs, temperature_K, friction_per_fs, seed, thermo_every, with_stress != 0);
+        return md_steps(md, n_steps, thermo_every, E.width, thermo, E, S);
+    });
+}
 
 extern "C" int uf3_md_run(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
                           double skin, int64_t thermo_every, int with_stress, double *thermo) {
-    return md_run_entry(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, skin, thermo_every, with_stress, thermo, 0, nullptr);
+    if (!md) return fail(nullptr, UF3_EINVAL, "null md");
+    return md_run_entry(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, skin, thermo_every, with_stress, thermo, MdSampler());
 }
 
 extern "C" int uf3_md_run_flux(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
                                double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t flux_every, double *flux) {
-    return md_run_entry(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, skin, thermo_every, with_stress, thermo, flux_every, flux);
+    if (!md) return fail(nullptr, UF3_EINVAL, "null md");
+    uf3_ctx *c = md->c;
+    if (flux_every < 0) return fail(c, UF3_EINVAL, "uf3_md_run_flux: flux_every must be >= 0");
+    int rc = md_records_check(c, "uf3_md_run_flux", "flux", "flux", flux_every ? n_steps / flux_every : 0, flux);
+    if (rc) return rc;
+    return md_run_entry(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, skin, thermo_every, with_stress, thermo,
+                        MdFluxSampler(md, n_steps, flux_every, flux));
 }
 
 extern "C" int uf3_md_run_grade(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
@@ -4273,41 +4324,12 @@ extern "C" int uf3_md_run_grade(uf3_md *md, int64_t n_steps, double dt_fs, doubl
     if (grade_every < 0) return fail(c, UF3_EINVAL, "uf3_md_run_grade: grade_every must be >= 0");
     if (std::isnan(grade_stop)) return fail(c, UF3_EINVAL, "uf3_md_run_grade: grade_stop is not a number");
     const int64_t n_grade = grade_every && n_steps > 0 ? n_steps / grade_every : 0;
-    if ((n_grade > 0) != (grades != nullptr))
-        return fail(c, UF3_EINVAL, n_grade ? "uf3_md_run_grade: grade records are due but the grades buffer is NULL"
-                                           : "uf3_md_run_grade: a grades buffer was given but no record is due");
+    int rc = md_records_check(c, "uf3_md_run_grade", "grade", "grades", n_grade, grades);
+    if (rc) return rc;
     if (n_grade && !d_w) return fail(c, UF3_EINVAL, "uf3_md_run_grade: null argument (w)");
-    const MdGrade G = {d_w, grade_every, grade_stop, grades, steps_done};
-    return md_run_entry(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, skin, thermo_every, with_stress, thermo, 0, nullptr, &G);
+    return md_run_entry(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, skin, thermo_every, with_stress, thermo,
+                        MdGradeSampler(md, n_steps, d_w, grade_every, grade_stop, grades, steps_done));
 }
-
-static int md_run_entry(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
-                        double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t flux_every, double *flux,
-                        const MdGrade *G) {
-    if (!md) return fail(nullptr, UF3_EINVAL, "null md");
-    uf3_ctx *c = md->c;
-    if (flux_every < 0) return fail(c, UF3_EINVAL, "uf3_md_run_flux: flux_every must be >= 0");
-    const int64_t n_flux = flux_every ? n_steps / flux_every : 0;
-    if ((n_flux > 0) != (flux != nullptr))
-        return fail(c, UF3_EINVAL, n_flux ? "uf3_md_run_flux: flux records are due but the flux buffer is NULL"
-                                          : "uf3_md_run_flux: a flux buffer was given but no record is due");
-    if (n_steps < 0) return fail(c, UF3_EINVAL, "uf3_md_run: n_steps must be >= 0");
-    if (!(dt_fs > 0.0) || !std::isfinite(dt_fs)) return fail(c, UF3_EINVAL, "uf3_md_run: dt must be positive and finite");
-    if (!(temperature_K >= 0.0) || !std::isfinite(temperature_K)) return fail(c, UF3_EINVAL, "uf3_md_run: temperature must be finite and >= 0");
-    if (!(friction_per_fs >= 0.0) || !std::isfinite(friction_per_fs)) return fail(c, UF3_EINVAL, "uf3_md_run: friction must be finite and >= 0");
-    if (thermo_every < 0) return fail(c, UF3_EINVAL, "uf3_md_run: thermo_every must be >= 0");
-    if (!(skin >= 0.0) || skin > 4.0) return fail(c, UF3_EINVAL, "uf3_md_run: skin must lie in [0, 4] Angstrom");
-    const int64_t n_rec = thermo_every ? n_steps / thermo_every : 0;
-    if ((n_rec > 0) != (thermo != nullptr))
-        return fail(c, UF3_EINVAL, n_rec ? "uf3_md_run: thermo records are due but the thermo buffer is NULL"
-                                         : "uf3_md_run: a thermo buffer was given but no record is due");
-    if (n_steps == 0) return UF3_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    return with_run_skin(c, skin, [&] {
-        return md_run(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, thermo_every, with_stress != 0, thermo, flux_every, flux, G);
-    });
-}
-
 
 // ------------------------------------------------------------------------------ constant pressure (uf3_md_run_npt, uf3_npt.h)
 // The same state as above plus one piston per frame.  Between two force calls: k_npt_partial, k_npt_frame, k_npt_move.  The
@@ -4348,118 +4370,85 @@ static int npt_init(uf3_md *md) {
     return UF3_OK;
 }
 
-// the three launches between two force calls (+ the frame sums of a thermo record when `record` >= 0)
-static int npt_launch(uf3_md *md, NptArgs &A, int64_t record) {
-    uf3_ctx *c = md->c;
-    hipStream_t s = c->stream;
-    // the evaluator's persistent copies, while its lists are this run's
-    const bool lists = c->md.live && c->md.valid && c->md.natoms == md->natoms && c->md.n_frames == md->n_frames;
-    A.geo = lists ? c->md.geo.as<FrameGeom>() : nullptr;
-    A.pos_ref = lists ? c->md.pos_ref.as<double>() : nullptr;
-    A.thermo = record >= 0;
-    hipLaunchKernelGGL(k_npt_partial, dim3((unsigned)md->chunks.n_blocks), dim3(UF3_NPT_THREADS), 0, s, A);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_npt_frame, dim3((unsigned)md->n_frames), dim3(UF3_NPT_THREADS), 0, s, A);
-    HIPCHK(c, hipGetLastError());
-    const dim3 g((unsigned)((md->natoms + UF3_NPT_THREADS - 1) / UF3_NPT_THREADS)), blk(UF3_NPT_THREADS);
-    if (A.langevin) {
-        if (A.thermo) hipLaunchKernelGGL((k_npt_move<true, true>), g, blk, 0, s, A);
-        else hipLaunchKernelGGL((k_npt_move<true, false>), g, blk, 0, s, A);
-    } else {
-        if (A.thermo) hipLaunchKernelGGL((k_npt_move<false, true>), g, blk, 0, s, A);
-        else hipLaunchKernelGGL((k_npt_move<false, false>), g, blk, 0, s, A);
+// NPH / NPT: three launches between two force calls, the cells on the device
+struct MdPiston {
+    uf3_md *md; NptArgs A;
+    MdPiston(uf3_md *md, double dt, double T, double gamma, const NptBaro &B, uint64_t seed, double skin) : md(md) {
+        memset(&A, 0, sizeof(A));
+        A.pos = md->pos.as<double>(); A.vel = md->vel.as<double>(); A.frc = md->frc.as<double>(); A.inv_m = md->inv_m.as<double>();
+        const ChunkTable &ct = md->chunks;
+        A.frame_of = ct.frame_of.as<int>(); A.n = md->natoms;
+        A.blk_frame = ct.blk_frame.as<int>(); A.blk_n = ct.blk_n.as<int>(); A.frame_blk = ct.frame_blk.as<int>();
+        A.blk_lo = ct.blk_lo.as<long long>(); A.partial = md->npt_partial.as<double>();
+        A.offsets = md->offsets_dev.as<long long>(); A.virials = md->virials.as<double>();
+        A.st = md->npt_st.as<NptFrame>(); A.coef = md->npt_coef.as<NptCoef>(); A.cells = md->cells_dev.as<double>();
+        A.dt = dt; A.p0 = B.p0; A.tau2_kTp = B.tau * B.tau * UF3_MD_KB * B.Tp; A.kT = UF3_MD_KB * T;
+        A.c = std::exp(-gamma * dt); A.cp = std::exp(-B.gamma_p * dt);
+        A.r_cut = md->b->host.rsearch; A.skin = skin;
+        A.seed = (unsigned long long)seed;
+        A.langevin = gamma > 0.0 || B.gamma_p > 0.0;
     }
-    HIPCHK(c, hipGetLastError());
-    if (A.thermo) {
-        hipLaunchKernelGGL(k_npt_thermo, dim3((unsigned)md->n_frames), dim3(UF3_MD_THREADS), 0, s, A, (const double *)md->energies.as<double>(),
-                           md->ring.as<double>() + (size_t)record * md->n_frames * UF3_NPT_REC);
-        HIPCHK(c, hipGetLastError());
-    }
-    A.rebuilt = 0;
-    return UF3_OK;
-}
-
-// forces, energies and strain derivatives of the current positions and cells; *rebuilt: the evaluator built its lists on the way
-static int npt_forces(uf3_md *md, NptArgs &A) {
-    const long long before = md->c->md.builds;
-    int rc = md_forces(md, true);
-    if (md->c->md.builds != before) A.rebuilt = 1;
-    return rc;
-}
-
-static int npt_run(uf3_md *md, int64_t n_steps, double dt, double T, double gamma, double p0, double tau, double gamma_p, double Tp,
-                   uint64_t seed, double skin, int64_t every, double *thermo) {
-    uf3_ctx *c = md->c;
-    const int64_t n_rec = every ? n_steps / every : 0;
-    if (n_rec) HIPCHK(c, md->ring.ensure(8 * (size_t)n_rec * md->n_frames * UF3_NPT_REC));
-    HIPCHK(c, md->kin.ensure(56 * (size_t)md->natoms));
-    if (!c->flags.p) { HIPCHK(c, c->flags.ensure(64)); HIPCHK(c, hipMemsetAsync(c->flags.p, 0, 64, c->stream)); }
-    NptArgs A;
-    memset(&A, 0, sizeof(A));
-    A.pos = md->pos.as<double>(); A.vel = md->vel.as<double>(); A.frc = md->frc.as<double>(); A.inv_m = md->inv_m.as<double>();
-    const ChunkTable &ct = md->chunks;
-    A.kin = md->kin.as<double>(); A.frame_of = ct.frame_of.as<int>(); A.n = md->natoms;
-    A.blk_frame = ct.blk_frame.as<int>(); A.blk_n = ct.blk_n.as<int>(); A.frame_blk = ct.frame_blk.as<int>();
-    A.blk_lo = ct.blk_lo.as<long long>(); A.partial = md->npt_partial.as<double>();
-    A.offsets = md->offsets_dev.as<long long>(); A.virials = md->virials.as<double>();
-    A.st = md->npt_st.as<NptFrame>(); A.coef = md->npt_coef.as<NptCoef>(); A.cells = md->cells_dev.as<double>();
-    A.flags = c->flags.as<int>();
-    A.dt = dt; A.p0 = p0; A.tau2_kTp = tau * tau * UF3_MD_KB * Tp; A.kT = UF3_MD_KB * T;
-    A.c = std::exp(-gamma * dt); A.cp = std::exp(-gamma_p * dt);
-    A.r_cut = md->b->host.rsearch; A.skin = skin;
-    A.seed = (unsigned long long)seed;
-    A.langevin = gamma > 0.0 || gamma_p > 0.0;
-    if (!(md->forces_valid && md->virials_valid)) {
+    int prepare(int64_t) {
+        uf3_ctx *c = md->c;
+        HIPCHK(c, md->kin.ensure(56 * (size_t)md->natoms));
+        if (!c->flags.p) { HIPCHK(c, c->flags.ensure(64)); HIPCHK(c, hipMemsetAsync(c->flags.p, 0, 64, c->stream)); }
+        A.kin = md->kin.as<double>(); A.flags = c->flags.as<int>();
+        if (md->forces_valid && md->virials_valid) return UF3_OK;
         md->g_valid = false;
-        int rc = npt_forces(md, A);
-        if (rc) return rc;
+        return forces(0);
     }
-    const int64_t t0 = md->step;
-    for (int64_t k = 1; k <= n_steps; k++) {
-        // closes step k - 1 of the run (its record, if due) and opens step k
-        A.step = (unsigned long long)(t0 + k - 1); A.close = k > 1; A.open = 1; A.use_g = md->g_valid;
-        const bool rec = k > 1 && every && (k - 1) % every == 0;
-        int rc = npt_launch(md, A, rec ? (k - 1) / every - 1 : -1);
-        md->forces_valid = false; md->virials_valid = false; md->g_valid = false;
-        md->step = t0 + k - 1;
-        if (rc) return rc;
-        rc = npt_forces(md, A);
-        if (rc) return rc;
+    // use_g: the opening half takes G from the last closing half (nothing changed since)
+    int launch(int close, int open, int64_t step, int64_t record) {
+        uf3_ctx *c = md->c;
+        hipStream_t s = c->stream;
+        A.step = (unsigned long long)step; A.close = close; A.open = open; A.use_g = open && md->g_valid;
+        // the evaluator's persistent copies, while its lists are this run's
+        const bool lists = c->md.live && c->md.valid && c->md.natoms == md->natoms && c->md.n_frames == md->n_frames;
+        A.geo = lists ? c->md.geo.as<FrameGeom>() : nullptr;
+        A.pos_ref = lists ? c->md.pos_ref.as<double>() : nullptr;
+        A.thermo = record >= 0;
+        hipLaunchKernelGGL(k_npt_partial, dim3((unsigned)md->chunks.n_blocks), dim3(UF3_NPT_THREADS), 0, s, A);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k_npt_frame, dim3((unsigned)md->n_frames), dim3(UF3_NPT_THREADS), 0, s, A);
+        HIPCHK(c, hipGetLastError());
+        const dim3 g((unsigned)((md->natoms + UF3_NPT_THREADS - 1) / UF3_NPT_THREADS)), blk(UF3_NPT_THREADS);
+        with_bool(A.langevin, [&](auto L) { return with_bool(A.thermo, [&](auto T) {
+            hipLaunchKernelGGL((k_npt_move<L, T>), g, blk, 0, s, A);
+            return (int)UF3_OK; }); });
+        HIPCHK(c, hipGetLastError());
+        if (A.thermo) {
+            hipLaunchKernelGGL(k_npt_thermo, dim3((unsigned)md->n_frames), dim3(UF3_MD_THREADS), 0, s, A, (const double *)md->energies.as<double>(),
+                               md->ring.as<double>() + (size_t)record * md->n_frames * UF3_NPT_REC);
+            HIPCHK(c, hipGetLastError());
+        }
+        A.rebuilt = 0;
+        if (!open) md->g_valid = true;           // (the pistons' g_close belongs to the closed state)
+        return UF3_OK;
     }
-    A.step = (unsigned long long)(t0 + n_steps - 1); A.close = 1; A.open = 0; A.use_g = 0;
-    const bool rec = every && n_steps % every == 0;
-    int rc = npt_launch(md, A, rec ? n_steps / every - 1 : -1);
-    if (rc) return rc;
-    md->step = t0 + n_steps;
-    md->g_valid = true;
-    if (n_rec) HIPCHK(c, hipMemcpyAsync(thermo, md->ring.p, 8 * (size_t)n_rec * md->n_frames * UF3_NPT_REC, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(md->cells.data(), md->cells_dev.p, 72 * (size_t)md->n_frames, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return UF3_OK;
-}
+    // forces, energies and strain derivatives of the current positions and cells; rebuilt: the evaluator built its lists on the way
+    int forces(int64_t) {
+        const long long before = md->c->md.builds;
+        int rc = md_forces(md, true);
+        if (md->c->md.builds != before) A.rebuilt = 1;
+        return rc;
+    }
+    void moved() { md->forces_valid = false; md->virials_valid = false; md->g_valid = false; }
+    int copy_out() {
+        uf3_ctx *c = md->c;
+        HIPCHK(c, hipMemcpyAsync(md->cells.data(), md->cells_dev.p, 72 * (size_t)md->n_frames, hipMemcpyDeviceToHost, c->stream));
+        return UF3_OK;
+    }
+};
 
 extern "C" int uf3_md_run_npt(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs,
                               double pressure_eV_A3, double barostat_time_fs, double barostat_friction_per_fs,
                               double piston_temperature_K, uint64_t seed, double skin, int64_t thermo_every, double *thermo) {
     if (!md) return fail(nullptr, UF3_EINVAL, "null md");
     uf3_ctx *c = md->c;
-    if (n_steps < 0) return fail(c, UF3_EINVAL, "uf3_md_run_npt: n_steps must be >= 0");
-    if (!(dt_fs > 0.0) || !std::isfinite(dt_fs)) return fail(c, UF3_EINVAL, "uf3_md_run_npt: dt must be positive and finite");
-    if (!(temperature_K >= 0.0) || !std::isfinite(temperature_K)) return fail(c, UF3_EINVAL, "uf3_md_run_npt: temperature must be finite and >= 0");
-    if (!(friction_per_fs >= 0.0) || !std::isfinite(friction_per_fs)) return fail(c, UF3_EINVAL, "uf3_md_run_npt: friction must be finite and >= 0");
-    if (!std::isfinite(pressure_eV_A3)) return fail(c, UF3_EINVAL, "uf3_md_run_npt: pressure must be finite");
-    if (!(barostat_time_fs > 0.0) || !std::isfinite(barostat_time_fs)) return fail(c, UF3_EINVAL, "uf3_md_run_npt: barostat time must be positive and finite");
-    if (!(barostat_friction_per_fs >= 0.0) || !std::isfinite(barostat_friction_per_fs))
-        return fail(c, UF3_EINVAL, "uf3_md_run_npt: barostat friction must be finite and >= 0");
-    if (!(piston_temperature_K > 0.0) || !std::isfinite(piston_temperature_K))
-        return fail(c, UF3_EINVAL, "uf3_md_run_npt: piston temperature must be positive and finite");
-    if (thermo_every < 0) return fail(c, UF3_EINVAL, "uf3_md_run_npt: thermo_every must be >= 0");
-    if (!(skin >= 0.0) || skin > 4.0) return fail(c, UF3_EINVAL, "uf3_md_run_npt: skin must lie in [0, 4] Angstrom");
-    const int64_t n_rec = thermo_every ? n_steps / thermo_every : 0;
-    if ((n_rec > 0) != (thermo != nullptr))
-        return fail(c, UF3_EINVAL, n_rec ? "uf3_md_run_npt: thermo records are due but the thermo buffer is NULL"
-                                         : "uf3_md_run_npt: a thermo buffer was given but no record is due");
-    int rc = npt_init(md);
+    const NptBaro B = {pressure_eV_A3, barostat_time_fs, barostat_friction_per_fs, piston_temperature_K};
+    int rc = md_run_check(c, "uf3_md_run_npt", n_steps, dt_fs, temperature_K, friction_per_fs, &B, thermo_every, skin, thermo);
+    if (rc) return rc;
+    rc = npt_init(md);
     if (rc) return rc;
     if (n_steps == 0) return UF3_OK;
     HIPCHK(c, hipSetDevice(c->device));
@@ -4472,8 +4461,9 @@ extern "C" int uf3_md_run_npt(uf3_md *md, int64_t n_steps, double dt_fs, double 
         double *caller_host = c->md.live_host;
         c->md.valid = false;
         c->md.live = true; c->md.live_dev = md->cells_dev.as<double>(); c->md.live_host = md->cells.data();
-        const int rc = npt_run(md, n_steps, dt_fs, temperature_K, friction_per_fs, pressure_eV_A3, barostat_time_fs,
-                               barostat_friction_per_fs, piston_temperature_K, seed, skin, thermo_every, thermo);
+        MdPiston E(md, dt_fs, temperature_K, friction_per_fs, B, seed, skin);
+        MdSampler none;
+        const int rc = md_steps(md, n_steps, thermo_every, UF3_NPT_REC, thermo, E, none);
         if (rc) {
             // (the device's cells are the state: the host's copy follows them, whatever stopped the run)
             hipMemcpyAsync(md->cells.data(), md->cells_dev.p, 72 * (size_t)md->n_frames, hipMemcpyDeviceToHost, c->stream);
@@ -5781,10 +5771,9 @@ static int flux_sample(uf3_ctx *c, ListWork &W, FluxArgs &F, bool headroom, cons
     return lists_sample(c, W, F, headroom, who, 12288, ": more than 12288 neighbours of one atom", [&] {
         const size_t lds = sizeof(int) * (size_t)F.cap;
         const bool want_w = F.w != nullptr, want_j = F.vel != nullptr;
-        if (want_w && want_j) hipLaunchKernelGGL((k_flux_site_terms<true, true>), dim3(n), dim3(64), lds, st, F);
-        else if (want_w) hipLaunchKernelGGL((k_flux_site_terms<true, false>), dim3(n), dim3(64), lds, st, F);
-        else if (want_j) hipLaunchKernelGGL((k_flux_site_terms<false, true>), dim3(n), dim3(64), lds, st, F);
-        else hipLaunchKernelGGL((k_flux_site_terms<false, false>), dim3(n), dim3(64), lds, st, F);
+        with_bool(want_w, [&](auto WANT_W) { return with_bool(want_j, [&](auto WANT_J) {
+            hipLaunchKernelGGL((k_flux_site_terms<WANT_W, WANT_J>), dim3(n), dim3(64), lds, st, F);
+            return (int)UF3_OK; }); });
         if (want_j) hipLaunchKernelGGL(k_flux_frame, dim3((unsigned)F.n_frames), dim3(UF3_MD_THREADS), 0, st, F);
         return (int)UF3_OK;
     });

@@ -3,8 +3,9 @@
 //
 //   md_philox        Philox4x32-10 (Salmon et al., SC'11): counter (atom, step lo, step hi, draw), key (seed lo, seed hi)
 //   k_md_step        one fused launch between two force calls: closing half-kick of step t (+ the atom's kinetic terms on a
-//                    thermo step), opening half-kick of step t + 1, drift; with LANGEVIN the drift is BAOAB's A-O-A
-//   k_md_thermo      one workgroup per frame: the per-atom kinetic terms summed in a fixed order, one thermo record
+//                    thermo step: md_store_kin), opening half-kick of step t + 1, drift; with LANGEVIN the drift is BAOAB's A-O-A
+//   k_md_thermo      one workgroup per frame: the per-atom kinetic terms summed in a fixed order (md_kin_sum), one thermo record
+//                    (md_store_kin and md_kin_sum are k_npt_move's and k_npt_thermo's too, uf3_npt.h: one copy of each)
 //   k_md_init_velocities   Maxwell-Boltzmann draws, one thread per atom
 //   k_md_init_com    one workgroup per frame: centre-of-mass velocity removed, optional rescale to the exact temperature (3N
 //                    degrees of freedom)
@@ -66,6 +67,19 @@ struct MdStepArgs {
     int close, open;                   // half-kick that closes step t | opening half-kick + drift of step t + 1
 };
 
+// the atom's kinetic terms of a thermo step, k_md_step's and k_npt_move's (uf3_npt.h): kin[7][n] = 1/2 m v^2 | m v (x) v (Voigt),
+// eV.  The products stay (m * v_a) * v_b as written: the thermo records' bits follow the operand order.
+__device__ __forceinline__ void md_store_kin(double *kin, long long n, long long i, double im, const double v[3]) {
+    const double m = UF3_MD_KE / im;
+    kin[i] = 0.5 * m * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    kin[n + i] = m * v[0] * v[0];
+    kin[2 * n + i] = m * v[1] * v[1];
+    kin[3 * n + i] = m * v[2] * v[2];
+    kin[4 * n + i] = m * v[1] * v[2];
+    kin[5 * n + i] = m * v[0] * v[2];
+    kin[6 * n + i] = m * v[0] * v[1];
+}
+
 template <bool LANGEVIN, bool THERMO>
 __global__ void __launch_bounds__(256) k_md_step(MdStepArgs A) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -78,16 +92,7 @@ __global__ void __launch_bounds__(256) k_md_step(MdStepArgs A) {
 #pragma unroll
         for (int k = 0; k < 3; k++) v[k] += h * a[k];
     }
-    if (THERMO) {
-        const double m = UF3_MD_KE / im;
-        A.kin[i] = 0.5 * m * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-        A.kin[A.n + i] = m * v[0] * v[0];
-        A.kin[2 * A.n + i] = m * v[1] * v[1];
-        A.kin[3 * A.n + i] = m * v[2] * v[2];
-        A.kin[4 * A.n + i] = m * v[1] * v[2];
-        A.kin[5 * A.n + i] = m * v[0] * v[2];
-        A.kin[6 * A.n + i] = m * v[0] * v[1];
-    }
+    if (THERMO) md_store_kin(A.kin, A.n, i, im, v);
     if (A.open) {
         double x[3];
 #pragma unroll
@@ -132,18 +137,23 @@ __device__ __forceinline__ void md_block_sum(double (&x)[K], double *lds) {
     __syncthreads();
 }
 
+// what k_md_thermo and k_npt_thermo (uf3_npt.h) start with: the kinetic terms a record of `width` doubles holds (1 of 7 when it
+// is 2) summed over the atoms [lo, hi) of the workgroup's frame, in lane 0's s[]
+__device__ __forceinline__ void md_kin_sum(const double *kin, long long n, long long lo, long long hi, int width, double (&s)[7]) {
+    __shared__ double lds[7 * UF3_MD_THREADS];
+    const int nk = width == 2 ? 1 : 7;
+    for (long long i = lo + threadIdx.x; i < hi; i += UF3_MD_THREADS)
+        for (int k = 0; k < nk; k++) s[k] += kin[k * n + i];
+    md_block_sum<7>(s, lds);
+}
+
 // one record per frame: [PE, KE] or [PE, KE, W (6), K (6)]; rec = thermo + (record * n_frames + frame) * width
 __global__ void __launch_bounds__(UF3_MD_THREADS) k_md_thermo(const double *kin, long long n, const int64_t *offsets,
                                                               const double *energies, const double *virials, double *rec_base,
                                                               int width) {
-    __shared__ double lds[7 * UF3_MD_THREADS];
     const int f = blockIdx.x;
-    const long long lo = offsets[f], hi = offsets[f + 1];
-    const int nk = width == 2 ? 1 : 7;
     double s[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (long long i = lo + threadIdx.x; i < hi; i += UF3_MD_THREADS)
-        for (int k = 0; k < nk; k++) s[k] += kin[k * n + i];
-    md_block_sum<7>(s, lds);
+    md_kin_sum(kin, n, offsets[f], offsets[f + 1], width, s);
     if (threadIdx.x == 0) {
         double *r = rec_base + (size_t)f * width;
         r[0] = energies[f];

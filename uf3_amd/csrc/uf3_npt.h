@@ -21,10 +21,11 @@
 //                   closing kick follows from the three sums: v' = a v + b F/m), writes the frame's coefficients and its new
 //                   cell rows into device memory -- the integrator's own copy and, when the evaluator's persistent lists
 //                   are live, the FrameGeom its kernels read -- and the limits of the list test below
-//   k_npt_move      one thread per atom: kick, kinetic terms of a thermo step, kick, drift, draws; then the list test: the
+//   k_npt_move      one thread per atom: kick, kinetic terms of a thermo step (uf3_md.h's md_store_kin), kick, drift, draws -- k_md_step
+//                   with the frame's coefficients in its kick and drift expressions, which stay its own; then the list test: the
 //                   reference positions of the evaluator's lists are carried along with the cell (x_ref *= e), and the atom
 //                   raises the evaluator's status words when |x - x_ref| has passed the frame's limit
-//   k_npt_thermo    one workgroup per frame: the record [PE, KE, W (6), K (6), V, s, H]
+//   k_npt_thermo    one workgroup per frame: uf3_md.h's md_kin_sum, then the record [PE, KE, W (6), K (6), V, s, H]
 //
 // The list test.  Lists built at r_cut + skin from positions X in a cell C stay complete for positions x in the cell s C
 // (s relative to the build) while 2 |x / s - X| <= skin - r_cut (1 / s - 1) for every atom: a pair within r_cut now,
@@ -203,16 +204,7 @@ __global__ void __launch_bounds__(UF3_NPT_THREADS) k_npt_move(NptArgs A) {
 #pragma unroll
         for (int k = 0; k < 3; k++) v[k] = a1 * v[k] + b1 * a[k];
     }
-    if (THERMO) {
-        const double m = UF3_MD_KE / im;
-        A.kin[i] = 0.5 * m * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-        A.kin[A.n + i] = m * v[0] * v[0];
-        A.kin[2 * A.n + i] = m * v[1] * v[1];
-        A.kin[3 * A.n + i] = m * v[2] * v[2];
-        A.kin[4 * A.n + i] = m * v[1] * v[2];
-        A.kin[5 * A.n + i] = m * v[0] * v[2];
-        A.kin[6 * A.n + i] = m * v[0] * v[1];
-    }
+    if (THERMO) md_store_kin(A.kin, A.n, i, im, v);
     if (A.open) {
         const double a2 = K->a2, b2 = K->b2, e1 = K->e1, d1 = K->d1;
         double x[3];
@@ -253,13 +245,10 @@ __global__ void __launch_bounds__(UF3_NPT_THREADS) k_npt_move(NptArgs A) {
 
 // one record per frame: [PE, KE, W (6), K (6), V, s, H = KE + PE + P0 V + W_p v_eps^2 / 2] at the integer time just closed
 __global__ void __launch_bounds__(UF3_MD_THREADS) k_npt_thermo(NptArgs A, const double *energies, double *rec_base) {
-    __shared__ double lds[7 * UF3_MD_THREADS];
     const int f = blockIdx.x;
     const long long lo = A.offsets[f], hi = A.offsets[f + 1];
     double s[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (long long i = lo + threadIdx.x; i < hi; i += UF3_MD_THREADS)
-        for (int k = 0; k < 7; k++) s[k] += A.kin[k * A.n + i];
-    md_block_sum<7>(s, lds);
+    md_kin_sum(A.kin, A.n, lo, hi, UF3_NPT_REC, s);
     if (threadIdx.x == 0) {
         const NptFrame *S = A.st + f;
         double *r = rec_base + (size_t)f * UF3_NPT_REC;

@@ -207,6 +207,7 @@ class MolecularDynamics(Driver):
             raise ValueError("MolecularDynamics: positions must be finite")
         self.n_atoms = np.diff(self._batch.offsets).astype(np.int64)
         self._cell_scale = np.ones(self._batch.n_frames)
+        self._grade_w_host = self._grade_w_dev = None
         vel = None if vel is None else np.ascontiguousarray(vel)
         self._create(calculator, device, [_lib._p(self._batch.pos), _lib._p(vel), _lib._p(self._batch.z), _lib._p(self.masses)])
 
@@ -351,10 +352,11 @@ class MolecularDynamics(Driver):
         flux_every = check_int(WHO, "flux_every", flux_every)
         grade_every = check_int(WHO, "grade_every", grade_every)
         grade_stop = 0.0 if grade_stop is None else check_real(WHO, "grade_stop", grade_stop, lo=None)
-        if flux_every and getattr(self, "pressure_eV_A3", None) is not None:
+        pressure = getattr(self, "pressure_eV_A3", None)        # (a bare object, as tests/test_md_host.py makes, has no barostat)
+        if flux_every and pressure is not None:
             raise _lib.UF3Error(1, "uf3_md_run_flux: the heat current is sampled at constant volume only (flux_every with "
                                    "pressure_eV_A3)")
-        if grade_every and getattr(self, "pressure_eV_A3", None) is not None:
+        if grade_every and pressure is not None:
             raise _lib.UF3Error(1, "uf3_md_run_grade: grades are sampled at constant volume only (grade_every with "
                                    "pressure_eV_A3)")
         if grade_every and flux_every:
@@ -365,54 +367,47 @@ class MolecularDynamics(Driver):
         gamma = check_real(WHO, "friction_per_fs", self.friction_per_fs)
         skin = check_real(WHO, "skin", self.skin, hi=4.0)
         seed = check_int(WHO, "seed", self.seed, 0, (1 << 64) - 1)
-        baro = self._check_barostat(getattr(self, "pressure_eV_A3", None), getattr(self, "barostat_time_fs", None),
-                                    getattr(self, "barostat_friction_per_fs", 0.0), getattr(self, "piston_temperature_K", None))
-        handle = self._live()
-        first = self.step
-        n_rec = n_steps // every if every else 0
+        baro = self._check_barostat(pressure, getattr(self, "barostat_time_fs", None), getattr(self, "barostat_friction_per_fs", 0.0),
+                                    getattr(self, "piston_temperature_K", None))
+        handle, lib, first = self._live(), self.ctx.lib, self.step
+        n_frames, n_rec = self._batch.n_frames, n_steps // every if every else 0
+        ring = lambda a: _lib._p(a) if len(a) else None                             # noqa: E731 (no record due: no buffer)
         if baro is not None:
-            raw = np.zeros((n_rec, self._batch.n_frames, 17))
+            raw = np.zeros((n_rec, n_frames, 17))
             try:
-                self.ctx.check(self.ctx.lib.uf3_md_run_npt(handle, n_steps, dt, temp, gamma, baro[0], baro[1], baro[2], baro[3], seed,
-                                                           skin, every, _lib._p(raw) if n_rec else None))
+                self.ctx.check(lib.uf3_md_run_npt(handle, n_steps, dt, temp, gamma, *baro, seed, skin, every, ring(raw)))
             finally:
                 self._fetch_cells()
             return npt_records(raw, self.n_atoms, first, max(every, 1))
-        width = 14 if stress else 2
-        raw = np.zeros((n_rec, self._batch.n_frames, width))
+        raw = np.zeros((n_rec, n_frames, 14 if stress else 2))
+        args = (handle, n_steps, dt, temp, gamma, seed, skin, every, int(bool(stress)), ring(raw))
+        done = C.c_int64(n_steps)
         if flux_every:
-            n_flux = n_steps // flux_every
-            fl = np.zeros((n_flux, self._batch.n_frames, 2, 3))
-            self.ctx.check(self.ctx.lib.uf3_md_run_flux(handle, n_steps, dt, temp, gamma, seed, skin, every, int(bool(stress)),
-                                                        _lib._p(raw) if n_rec else None, flux_every, _lib._p(fl) if n_flux else None))
-            out = thermo_records(raw, self.n_atoms, self.volumes, first, max(every, 1), stress)
+            fl = np.zeros((n_steps // flux_every, n_frames, 2, 3))
+            self.ctx.check(lib.uf3_md_run_flux(*args, flux_every, ring(fl)))
+        elif grade_every:
+            gr = np.zeros((n_steps // grade_every, n_frames, 2))
+            self.ctx.check(lib.uf3_md_run_grade(*args, self._grade_w(w_host), grade_every, grade_stop, ring(gr), C.byref(done)))
+        else:
+            self.ctx.check(lib.uf3_md_run(*args))
+        done = done.value                   # (fewer than asked only when a grade sample stopped the run: every record is cut to them)
+        out = thermo_records(raw[:done // every if every else 0], self.n_atoms, self.volumes, first, max(every, 1), stress)
+        if flux_every:
             out["heat_flux_convective"] = fl[:, :, 0].copy()
             out["heat_flux_potential"] = fl[:, :, 1].copy()
             out["heat_flux"] = fl[:, :, 0] + fl[:, :, 1]
-            out["flux_step"] = first + flux_every * np.arange(1, n_flux + 1, dtype=np.int64)
-            return out
-        if grade_every:
-            n_grade = n_steps // grade_every
-            gr = np.zeros((n_grade, self._batch.n_frames, 2))
-            done = C.c_int64(0)
-            self.ctx.check(self.ctx.lib.uf3_md_run_grade(handle, n_steps, dt, temp, gamma, seed, skin, every, int(bool(stress)),
-                                                         _lib._p(raw) if n_rec else None, self._grade_w(w_host), grade_every,
-                                                         grade_stop, _lib._p(gr) if n_grade else None, C.byref(done)))
-            done = done.value
-            out = thermo_records(raw[:done // every if every else 0], self.n_atoms, self.volumes, first, max(every, 1), stress)
+            out["flux_step"] = first + flux_every * np.arange(1, len(fl) + 1, dtype=np.int64)
+        elif grade_every:
             gr = gr[:done // grade_every]
             out["grade"] = gr[:, :, 0].copy()
             out["grade_atom"] = gr[:, :, 1].astype(np.int64)
             out["grade_step"] = first + grade_every * np.arange(1, len(gr) + 1, dtype=np.int64)
             out["steps_done"] = done
-            return out
-        self.ctx.check(self.ctx.lib.uf3_md_run(handle, n_steps, dt, temp, gamma, seed, skin, every, int(bool(stress)),
-                                               _lib._p(raw) if n_rec else None))
-        return thermo_records(raw, self.n_atoms, self.volumes, first, max(every, 1), stress)
+        return out
 
     def _grade_w(self, w_host):
         """Device address of the whitening matrix: uploaded once per object (again after a refit made a new one)."""
-        if getattr(self, "_grade_w_host", None) is not w_host:
+        if self._grade_w_host is not w_host:
             import torch
             n_feat = _lib.device_basis(self.calculator.bspline_config, self.ctx).n_feat
             if w_host.shape != (n_feat, n_feat):
