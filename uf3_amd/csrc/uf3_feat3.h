@@ -81,6 +81,14 @@ struct F3Cfg {
 typedef double __attribute__((ext_vector_type(2))) F3Pair;
 typedef const __attribute__((address_space(3))) F3Pair *F3LdsPairs;
 typedef const __attribute__((address_space(3))) double *F3LdsDoubles;
+// an 8-byte LDS read the compiler may not merge with its neighbour: two reads off one base register become ONE two-address
+// ds_read2_b64, which takes 8.3 cycles of the CU's LDS where two ds_read_b64 take 4.9 (tools/experiments/lds_read_bench.hip,
+// DESIGN.md section 3.6).  The read stays the compiler's own -- it places and counts the waits -- and nothing else about it is
+// volatile: the memory it reads is written before the wave_sync in front of it.
+typedef const volatile __attribute__((address_space(3))) double *F3LdsSingles;
+// entry i of a per-wave list array, read singly where the instance says so (LIST1 in the kernel) and as the plain expression
+// otherwise: behind a function the wide instances allocate differently and spill two more scalar registers
+#define F3_LIST(a, i) (LIST1 ? *(F3LdsSingles)((a) + (i)) : (a)[i])
 // the LDS byte address of p as a scalar the compiler takes as it is: a stage-1 trip adds its per-lane offset to it in ONE vector
 // instruction and advances it on the scalar unit (left to itself the compiler splits the constant part of the address off into a
 // vector add of its own, or keeps vector induction variables per pointer)
@@ -151,6 +159,12 @@ k_featurize3(Feat3Args A) {
     // functions of a centre-leg evaluation that anything reads: a three-row window has no place for the fourth (the T table
     // stops at EF rows, stage 1 reads a record's bond values at p_lane < EF)
     constexpr int NFP = EF == 3 ? 3 : 4;
+    // Which 8-byte reads are kept single (F3LdsSingles): the trips' and the flush's at one and three rounds -- the two-round
+    // instances keep the compiler's pairs, their generic-capacity ones spill two to five more scalar registers with any of the
+    // three read singly; the list entries of the walks and the T-table prologue at one round only (at two and three rounds they
+    // cost two scalar spills each in two instances).  DESIGN.md section 3.6.
+    constexpr bool TRIP1 = NR != 2, LIST1 = NR == 1;
+    typedef std::conditional_t<TRIP1, F3LdsSingles, F3LdsDoubles> F3TripReads;
     extern __shared__ __align__(16) unsigned char smem[];
     const BasisDev *B = A.B;
     // (cap: what the LDS arrays are laid out for -- the longest list this instance serves; ent_stride: entries per atom in the
@@ -269,7 +283,7 @@ k_featurize3(Feat3Args A) {
         // ---- T_f of every own bond: rows over the whole window of the centre legs, zero where the bond's four functions are
         // not (and all zero when the bond is outside the legs' range) -------------------------------------------------------
         for (int e = lane; e < n_own; e += WAVE) {
-            const double r = orr[e];
+            const double r = F3_LIST(orr, e);
             double v[4] = {0, 0, 0, 0}, d[4] = {0, 0, 0, 0};
             int sbp = 0;
             if (r > leg_p.t0 && r < leg_p.tlast && !UF3_SKIP(32)) {
@@ -277,7 +291,7 @@ k_featurize3(Feat3Args A) {
                 sbp = max(0, min(sbp_max, iv - 3 - lo_p));
             }
             if (EF > 4) osbp[e] = sbp;
-            const double ir = oir[e], ux = ox[e] * ir, uy = oy[e] * ir, uz = oz[e] * ir;
+            const double ir = F3_LIST(oir, e), ux = F3_LIST(ox, e) * ir, uy = F3_LIST(oy, e) * ir, uz = F3_LIST(oz, e) * ir;
             double *dst = tq + (size_t)e * EF * 4;
             if (EF > 4) {
 #pragma unroll
@@ -322,7 +336,7 @@ k_featurize3(Feat3Args A) {
                 double t3[EF];
 #pragma unroll
                 for (int q = 0; q < EF; q++) {
-                    tv[q] = *(F3LdsPairs)(const F3Pair *)(tc + 4 * q + 2 * half); t3[q] = ((F3LdsDoubles)tc)[4 * q + 3];
+                    tv[q] = *(F3LdsPairs)(const F3Pair *)(tc + 4 * q + 2 * half); t3[q] = ((F3TripReads)tc)[4 * q + 3];
                 }
 #pragma unroll
                 for (int r = 0; r < NR; r++) {
@@ -378,8 +392,9 @@ k_featurize3(Feat3Args A) {
                     double bn[4] = {0, 0, 0, 0}, dum[4];
                     int sbn = 0;
                     if (valid) {
-                        const double rf = orr[f], rg = orr[gg];
-                        const double ex = ox[gg] - ox[f], ey = oy[gg] - oy[f], ez = oz[gg] - oz[f];
+                        const double rf = F3_LIST(orr, f), rg = F3_LIST(orr, gg);
+                        const double ex = F3_LIST(ox, gg) - F3_LIST(ox, f), ey = F3_LIST(oy, gg) - F3_LIST(oy, f),
+                                     ez = F3_LIST(oz, gg) - F3_LIST(oz, f);
                         const double rn = norm3_leg(ex, ey, ez);
                         valid = (rf > leg_p.t0) & (rf < leg_p.tlast) & (rg > leg_p.t0) & (rg < leg_p.tlast) &
                                 (rn > leg_n.t0) & (rn < leg_n.tlast);
@@ -427,7 +442,7 @@ k_featurize3(Feat3Args A) {
                                 F3Pair tt[CNT];
 #pragma unroll
                                 for (int i = 0; i < CNT; i++) {
-                                    bq[i] = *(F3LdsDoubles)(qp + qn8_lane[r] + i * RS_C * 8);
+                                    bq[i] = *(F3TripReads)(qp + qn8_lane[r] + i * RS_C * 8);
                                     tt[i] = *(F3LdsPairs)(tp + tp_lane[r] + i * EF * 32);
                                 }
 #pragma unroll
@@ -492,7 +507,7 @@ k_featurize3(Feat3Args A) {
                         e = rc_lo + lo;
                         const int kk = nbase[lo] + (q - noff[lo]);
                         const int pc = oparent[e];
-                        const double oex = ox[e], oey = oy[e], oez = oz[e], oer = orr[e];
+                        const double oex = F3_LIST(ox, e), oey = F3_LIST(oy, e), oez = F3_LIST(oz, e), oer = F3_LIST(orr, e);
                         const N3Entry ke = A.n3.ent[(size_t)pc * ent_stride + kk];
                         valid = !(ke.parent == m && ke.shiftc == oshift[e]);                  // k is m itself
                         const double ex = oex + ke.dx, ey = oey + ke.dy, ez = oez + ke.dz;   // m -> k
@@ -529,7 +544,9 @@ k_featurize3(Feat3Args A) {
                                 for (int u = 0; u < 4; u++) rp[sbp + u] = pv[u];
                             } else {
                                 *(double2 *)rp = double2{pv[0], pv[1]};
-                                *(double2 *)(rp + 2) = double2{pv[2], pv[3]};
+                                // (a three-row window: stage 1 reads a record's bond values at p_lane < 3, pv[3] was never evaluated)
+                                if (EF == 3) rp[2] = pv[2];
+                                else *(double2 *)(rp + 2) = double2{pv[2], pv[3]};
                             }
 #pragma unroll
                             for (int u = 0; u < 4; u++) {
@@ -584,7 +601,7 @@ k_featurize3(Feat3Args A) {
                                             qa = rp + off_n + (i * RS_N + EFP) * 8 + 16 * half;
                                             qa = off_n < 128u ? qa : zq_a;
                                         }
-                                        bq[i] = *(F3LdsDoubles)(rp + p8_lane[r] + i * RS_N * 8);
+                                        bq[i] = *(F3TripReads)(rp + p8_lane[r] + i * RS_N * 8);
                                         tt[i] = *(F3LdsPairs)qa;
                                     }
 #pragma unroll
@@ -661,3 +678,4 @@ k_featurize3(Feat3Args A) {
             }
     }
 }
+#undef F3_LIST
