@@ -457,8 +457,9 @@ int uf3_scan_solve_dev(uf3_ctx *ctx, int32_t n_cols, int32_t n_folds, const doub
  * (-fac .. fac cells per axis) around the positions AS GIVEN, as uf3_eval does on the same frame.  An atom that has drifted out of
  * its cell loses the interactions that range no longer reaches from where it is: the energy and forces of every step are uf3_eval's
  * of the unwrapped positions the object holds, which are the wrapped frame's only while every atom is inside its cell.  Nothing in
- * the object wraps.  A run in which atoms may cross a cell face (diffusion, a melt) is to be stopped and continued from wrapped
- * positions (uf3_md_set_state) before that happens.  The same holds for uf3_relax_* and uf3_neb_*, which keep positions
+ * the object wraps unless uf3_md_set_wrap (below) has turned wrapping on, which is the repair for runs in which atoms may cross
+ * a cell face (diffusion, a melt); without it such a run is to be stopped and continued from wrapped positions
+ * (uf3_md_set_state) before that happens.  The same holds for uf3_relax_* and uf3_neb_*, which keep positions
  * unwrapped for the same reason (tests/test_gpu_redescribed.py holds the rule).
  *   uf3_md_create          copies frames, positions [N][3], velocities [N][3] (NULL: zero), species, masses [N] and the model
  *                          (c1 / c2 / c3 as for uf3_eval) into the object; no evaluation yet.  Masses positive and finite.
@@ -542,6 +543,38 @@ int uf3_md_run_flux(uf3_md *md, int64_t n_steps, double dt_fs, double temperatur
 int uf3_md_run_grade(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
                      double skin, int64_t thermo_every, int with_stress, double *thermo, const double *d_w, int64_t grade_every,
                      double grade_stop, double *grades, int64_t *steps_done);
+/* Periodic wrapping with image counts, opt-in (k_md_wrap, uf3_md.h).  Off -- the default -- nothing above
+ * changes: no launch, no buffer, no bit.  On, the object stores pos and int32 img [N][3] and its position is pos + img . cell
+ * with the frame's CURRENT cell (rows are lattice vectors; under uf3_md_run_npt the cell the integrator has just written).
+ * k_md_wrap takes n = floor(fractional coordinate) on periodic axes, pos -= n . cell, img += n; axes that are not periodic and
+ * frames without a periodic axis are left alone bit for bit.  It runs in front of every neighbour-list build made for the
+ * object (the first of a run, the early-warning rebuild, the "lists outrun" repeat) and in front of every evaluation on the
+ * rebuild-everything route (skin 0, 2-body bases), never between a list build and the steps on its lists.  Invariant: an
+ * evaluation of a wrapping object never sees an atom farther outside its cell than that atom has moved since the last wrap
+ * (at most skin / 2, or the constant-pressure limit), so the evaluator's image-range rule and the samplers' nearest-image rule
+ * describe the same crystal and the hazard above does not arise.  A wrap rounds (pos - n . cell is not exact): with wrapping
+ * on, the last bits of a trajectory depend on where the lists were built (the skin, the run boundaries); it stays deterministic
+ * for a given sequence of calls, and run(a); run(b) agrees with run(a + b) to rounding, not bit for bit.
+ *   uf3_md_set_wrap     on: wraps now and from then on as described; off: folds img into pos and zeroes it.  Either drops
+ *                       the evaluator's lists and the object's forces only if a position changed.
+ *   uf3_md_get_state    keeps its meaning: positions UNWRAPPED, pos + img . cell formed on the device.
+ *   uf3_md_get_wrapped  the stored pair: pos [N][3] and img [N][3] (zeros while wrapping has never been on); NULL skips.
+ *   uf3_md_set_state    positions are taken as given and img becomes zero.
+ * Mean-squared displacement (k_md_msd_partial, k_md_msd_frame):
+ *   uf3_md_msd_origin   the origin [N][3] of the displacements; NULL: the current unwrapped positions.  A run that samples
+ *                       without one takes the positions it starts from.
+ *   uf3_md_run_msd      what uf3_md_run does, and after every msd_every-th step one record [n_frames][4 S + 4] of the closed
+ *                       state, S the basis' species count: per species sum |dr|^2, sum dx, sum dy, sum dz over its atoms with
+ *                       dr = pos + img . cell - origin, then sum m dr (3) and sum m over the frame.  Placed as uf3_md_run_flux
+ *                       places its samples: the trajectory and the thermo records keep their bits.  No atomics: the order of
+ *                       the sums depends on the atom counts alone and records repeat bit for bit.  msd must hold
+ *                       n_steps / msd_every records (NULL when none is due).  Constant volume only, and one sampler per run
+ *                       (the Python layer refuses msd_every at a pressure or next to flux_every / grade_every). */
+int uf3_md_set_wrap(uf3_md *md, int on);
+int uf3_md_get_wrapped(uf3_md *md, double *pos, int32_t *images);
+int uf3_md_msd_origin(uf3_md *md, const double *origin);
+int uf3_md_run_msd(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
+                   double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t msd_every, double *msd);
 int uf3_philox_debug(uf3_ctx *ctx, int64_t n, const uint32_t *counters, const uint32_t *keys, uint32_t *out);
 
 /*

@@ -39,7 +39,8 @@ EXPORTS = ["uf3_ctx_create", "uf3_ctx_destroy", "uf3_ctx_set_stream", "uf3_ctx_s
            "uf3_site_terms", "uf3_site_terms_dev", "uf3_heat_flux", "uf3_heat_flux_dev", "uf3_md_run_flux",
            "uf3_featurize_virial", "uf3_featurize_virial_dev",
            "uf3_leverage", "uf3_leverage_dev",
-           "uf3_site_rows", "uf3_site_rows_dev", "uf3_site_grade", "uf3_site_grade_dev", "uf3_md_run_grade"]
+           "uf3_site_rows", "uf3_site_rows_dev", "uf3_site_grade", "uf3_site_grade_dev", "uf3_md_run_grade",
+           "uf3_md_set_wrap", "uf3_md_get_wrapped", "uf3_md_msd_origin", "uf3_md_run_msd"]
 
 
 SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_virial_rows.h", "uf3_leverage.h", "uf3_site_rows.h", "uf3_device.h", "uf3_md.h", "uf3_hessian.h", "uf3_relax.h", "uf3_phonon.h", "uf3_npt.h", "uf3_neb.h", "uf3_idpp.h", "uf3_mc.h", "uf3_flux.h", os.path.join("..", "..", "include", "uf3_hip.h"))
@@ -249,6 +250,10 @@ def load():
         for name in ("uf3_site_grade", "uf3_site_grade_dev"):
             getattr(lib, name).argtypes = [vp, C.POINTER(Frames), vp, vp, vp, vp, vp, vp]
         lib.uf3_md_run_grade.argtypes = [vp, i64, dbl, dbl, dbl, C.c_uint64, dbl, i64, C.c_int, vp, vp, i64, dbl, vp, vp]
+        lib.uf3_md_set_wrap.argtypes = [vp, C.c_int]
+        lib.uf3_md_get_wrapped.argtypes = [vp, vp, vp]
+        lib.uf3_md_msd_origin.argtypes = [vp, vp]
+        lib.uf3_md_run_msd.argtypes = [vp, i64, dbl, dbl, dbl, C.c_uint64, dbl, i64, C.c_int, vp, i64, vp]
         _lib = lib
         return lib
 

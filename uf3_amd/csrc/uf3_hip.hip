@@ -227,6 +227,10 @@ struct uf3_ctx {
         bool live = false;
         const double *live_dev = nullptr;
         double *live_host = nullptr;
+        // a wrapping MD object (uf3_md_set_wrap) arms this for each of its evaluations: called with the positions in front of
+        // every list build (md_build) and in front of every evaluation on the rebuild-everything route, it folds them into the
+        // cell (k_md_wrap) -- never between a build and the steps on its lists.  Empty: nothing wraps
+        std::function<int(const double *)> wrap;
     } md;
     // RCCL communicator of this rank (uf3_comm_init): the library is opened at run time (no link dependency), see rccl_api()
     void *comm = nullptr;
@@ -2178,7 +2182,9 @@ static int md_build(uf3_basis *b, const uf3_frames *fr, const double *d_pos, con
     uf3_ctx::MdState &md = c->md;
     md.valid = false; md.stale = false;
     const bool defer = may_defer && md.cap_tuned && !md.verify_next && md.basis == b && md.cap > 0;
-    int rc = prepare(b, fr, d_pos, d_z, false, P, false, 0, -1, md.skin);      // cell list at r_cut + skin
+    int rc = md.wrap ? md.wrap(d_pos) : (int)UF3_OK;       // (k_md_snapshot below then sees the wrapped positions)
+    if (rc) return rc;
+    rc = prepare(b, fr, d_pos, d_z, false, P, false, 0, -1, md.skin);      // cell list at r_cut + skin
     if (rc) return rc;
     hipStream_t st = c->stream;
     const int natoms = P.natoms, nf = P.n_frames;
@@ -2338,6 +2344,10 @@ static int eval_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, co
             HIPCHK(c, hipMemsetAsync(c->flags.as<int>() + 1, 0, 4 * sizeof(int), st));
         md_prepared(c, P);
     } else {
+        if (c->md.wrap) {                           // (the rebuild-everything route: every evaluation builds its lists)
+            rc = c->md.wrap(d_pos);
+            if (rc) return rc;
+        }
         rc = prepare(b, fr, d_pos, d_z, !fuse, P, deferred_cap != nullptr, atom_begin, whole ? -1 : atom_end);
         if (rc) return rc;
     }
@@ -3981,11 +3991,129 @@ struct uf3_md : Batch {
     DevBuf mass, flux_ring;
     // grade samples (uf3_md_run_grade, uf3_site_rows.h): the atoms' grades of one sample, the records of a run
     DevBuf grade, grade_ring;
+    // periodic wrapping (uf3_md_set_wrap, k_md_wrap): off, img is zero and no run reads it.  On, the object's position is
+    // pos + img . cell with the current cell; cells_now() is that cell on the device
+    bool wrap = false;
+    bool chunks_ready = false;                  // `chunks` is built (npt_init, md_wrap_buffers, the MSD sampler)
+    DevBuf img, wrap_cells, wrap_pbc, wrap_flag, unwrapped;
+    // mean-squared-displacement samples (uf3_md_run_msd): species of every atom (host: from uf3_md_create), the origin
+    std::vector<signed char> spec;
+    DevBuf msd_spec, msd_origin, msd_partial, msd_ring;
+    bool msd_origin_set = false;
     ListWork fx;
     ~uf3_md() { fx.release(); }
+    const double *cells_now() const { return npt_ready ? cells_dev.as<double>() : wrap_cells.as<double>(); }
 };
 
 extern "C" void uf3_md_destroy(uf3_md *md) { driver_destroy(md); }
+
+static int md_chunks(uf3_md *md, const std::string &who) {
+    if (md->chunks_ready) return UF3_OK;
+    int rc = chunk_table_build(md->c, md->offsets, md->n_frames, UF3_NPT_THREADS, md->chunks, who);
+    md->chunks_ready = rc == UF3_OK;
+    return rc;
+}
+
+// what the wrap kernels read besides pos: image counts (zero when first made), the frames' cells and boundary flags, the chunk
+// table's frame of every atom.  Outside a constant-pressure object the cells never change: one upload
+static int md_wrap_buffers(uf3_md *md, const std::string &who) {
+    uf3_ctx *c = md->c;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = md_chunks(md, who);
+    if (rc) return rc;
+    if (md->img.p) return UF3_OK;
+    const size_t nf = (size_t)md->n_frames;
+    if (md->wrap_cells.ensure(72 * nf) || md->wrap_pbc.ensure(3 * nf) || md->wrap_flag.ensure(4) || md->img.ensure(12 * (size_t)md->natoms))
+        return fail(c, UF3_ENOMEM, who + ": out of device memory");
+    hipStream_t s = c->stream;
+    if (hipMemcpyAsync(md->wrap_cells.p, md->cells.data(), 72 * nf, hipMemcpyHostToDevice, s) ||
+        hipMemcpyAsync(md->wrap_pbc.p, md->pbc.data(), 3 * nf, hipMemcpyHostToDevice, s) ||
+        hipMemsetAsync(md->img.p, 0, 12 * (size_t)md->natoms, s) || hipStreamSynchronize(s)) {
+        md->img.release();
+        return fail(c, UF3_EHIP, who + ": upload failed");
+    }
+    return UF3_OK;
+}
+
+static MdWrapArgs md_wrap_args(uf3_md *md, int *changed) {
+    MdWrapArgs A;
+    A.pos = md->pos.as<double>(); A.img = md->img.as<int>(); A.cells = md->cells_now();
+    A.pbc = md->wrap_pbc.as<unsigned char>(); A.frame_of = md->chunks.frame_of.as<int>(); A.n = md->natoms; A.changed = changed;
+    return A;
+}
+
+// the hook of uf3_ctx::MdState::wrap: queued in front of the list build (or the evaluation) that called it
+static int md_wrap_launch(uf3_md *md, const double *d_pos, int *changed = nullptr) {
+    uf3_ctx *c = md->c;
+    if (d_pos != md->pos.as<double>()) return UF3_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_md_wrap, dim3((unsigned)((md->natoms + 255) / 256)), dim3(256), 0, c->stream, md_wrap_args(md, changed));
+    HIPCHK(c, hipGetLastError());
+    return UF3_OK;
+}
+
+// pos + img . cell into `out` (fold: into pos itself, img zeroed); *moved: some atom had a nonzero image count
+static int md_unwrap(uf3_md *md, double *out, bool fold, bool *moved) {
+    uf3_ctx *c = md->c;
+    int *flag = moved ? md->wrap_flag.as<int>() : nullptr;
+    if (flag) HIPCHK(c, hipMemsetAsync(flag, 0, 4, c->stream));
+    hipLaunchKernelGGL(k_md_unwrap, dim3((unsigned)((md->natoms + 255) / 256)), dim3(256), 0, c->stream, md_wrap_args(md, flag), out,
+                       fold ? 1 : 0);
+    HIPCHK(c, hipGetLastError());
+    if (flag) {
+        int h = 0;
+        HIPCHK(c, hipMemcpyAsync(&h, flag, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        *moved = h != 0;
+    }
+    return UF3_OK;
+}
+
+// positions changed under the evaluator's feet: its lists and everything evaluated go
+static void md_positions_changed(uf3_md *md) {
+    md->c->md.valid = false;
+    md->forces_valid = false; md->virials_valid = false; md->g_valid = false;
+}
+
+extern "C" int uf3_md_set_wrap(uf3_md *md, int on) {
+    if (!md) return fail(nullptr, UF3_EINVAL, "uf3_md_set_wrap: null md");
+    uf3_ctx *c = md->c;
+    if ((on != 0) == md->wrap) return UF3_OK;
+    if (on) {
+        int rc = md_wrap_buffers(md, "uf3_md_set_wrap");
+        if (rc) return rc;
+        int *flag = md->wrap_flag.as<int>(), h = 0;
+        HIPCHK(c, hipMemsetAsync(flag, 0, 4, c->stream));
+        rc = md_wrap_launch(md, md->pos.as<double>(), flag);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(&h, flag, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        md->wrap = true;
+        if (h) md_positions_changed(md);
+        return UF3_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    bool moved = false;
+    int rc = md_unwrap(md, md->pos.as<double>(), true, &moved);
+    if (rc) return rc;
+    md->wrap = false;
+    if (moved) md_positions_changed(md);
+    return UF3_OK;
+}
+
+extern "C" int uf3_md_get_wrapped(uf3_md *md, double *pos, int32_t *images) {
+    if (!md) return fail(nullptr, UF3_EINVAL, "uf3_md_get_wrapped: null md");
+    uf3_ctx *c = md->c;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n3 = 3 * (size_t)md->natoms;
+    if (pos) HIPCHK(c, hipMemcpyAsync(pos, md->pos.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
+    if (images) {
+        if (md->img.p) HIPCHK(c, hipMemcpyAsync(images, md->img.p, 4 * n3, hipMemcpyDeviceToHost, c->stream));
+        else memset(images, 0, 4 * n3);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return UF3_OK;
+}
 
 static int md_upload(uf3_md *md, const double *pos, const double *vel) {
     uf3_ctx *c = md->c;
@@ -3994,6 +4122,7 @@ static int md_upload(uf3_md *md, const double *pos, const double *vel) {
     if (vel && !md_finite(vel, n3)) return fail(c, UF3_EINVAL, "uf3_md: velocities must be finite");
     HIPCHK(c, hipSetDevice(c->device));
     if (pos) HIPCHK(c, hipMemcpyAsync(md->pos.p, pos, 8 * n3, hipMemcpyHostToDevice, c->stream));
+    if (pos && md->img.p) HIPCHK(c, hipMemsetAsync(md->img.p, 0, 4 * n3, c->stream));      // (positions are taken as given)
     if (vel) HIPCHK(c, hipMemcpyAsync(md->vel.p, vel, 8 * n3, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (pos) md->forces_valid = false;
@@ -4016,6 +4145,8 @@ extern "C" int uf3_md_create(uf3_basis *b, const uf3_frames *fr, const double *p
     }
     HIPCHK(c, hipSetDevice(c->device));
     uf3_md *md = new uf3_md();
+    md->spec.resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) md->spec[i] = z[i] >= 0 && z[i] < 120 ? b->host.z2s[z[i]] : (signed char)-1;
     auto bail = [&](int rc) { uf3_md_destroy(md); return rc; };
     rc = batch_init(*md, b, fr, pos, z, c1, c2, c3, 1, who);
     if (rc) return bail(rc);
@@ -4035,12 +4166,15 @@ extern "C" int uf3_md_create(uf3_basis *b, const uf3_frames *fr, const double *p
 
 extern "C" int uf3_md_set_state(uf3_md *md, const double *pos, const double *vel) {
     if (!md) return fail(nullptr, UF3_EINVAL, "null md");
+    if (pos && md->wrap) md->c->md.valid = false;           // (as given, possibly outside the cell: the next evaluation builds, and wraps)
     return md_upload(md, pos, vel);
 }
 
 // F(t) and the per-frame energies (and strain derivatives) of the current positions
 static int md_forces(uf3_md *md, bool virial) {
+    if (md->wrap) md->c->md.wrap = [md](const double *d_pos) { return md_wrap_launch(md, d_pos); };
     int rc = batch_eval(*md, md->frc.as<double>(), virial ? md->virials.as<double>() : nullptr);
+    if (md->wrap) md->c->md.wrap = nullptr;
     md->forces_valid = rc == UF3_OK;
     md->virials_valid = md->forces_valid && virial;
     return rc;
@@ -4055,7 +4189,14 @@ extern "C" int uf3_md_get_state(uf3_md *md, double *pos, double *vel, double *fo
         if (rc) return rc;
     }
     const size_t n3 = 3 * (size_t)md->natoms;
-    if (pos) HIPCHK(c, hipMemcpyAsync(pos, md->pos.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
+    const void *d_pos = md->pos.p;
+    if (pos && md->wrap) {                                  // (unwrapped, as always: pos + img . cell, formed on the device)
+        HIPCHK(c, md->unwrapped.ensure(8 * n3));
+        int rc = md_unwrap(md, md->unwrapped.as<double>(), false, nullptr);
+        if (rc) return rc;
+        d_pos = md->unwrapped.p;
+    }
+    if (pos) HIPCHK(c, hipMemcpyAsync(pos, d_pos, 8 * n3, hipMemcpyDeviceToHost, c->stream));
     if (vel) HIPCHK(c, hipMemcpyAsync(vel, md->vel.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
     if (forces) HIPCHK(c, hipMemcpyAsync(forces, md->frc.p, 8 * n3, hipMemcpyDeviceToHost, c->stream));
     if (energies) HIPCHK(c, hipMemcpyAsync(energies, md->energies.p, 8 * (size_t)md->n_frames, hipMemcpyDeviceToHost, c->stream));
@@ -4285,9 +4426,9 @@ struct MdGradeSampler : MdSampler {
 // what the three constant-volume entries share, behind the checks of their own sampler
 template <class Sampler>
 static int md_run_entry(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
-                        double skin, int64_t thermo_every, int with_stress, double *thermo, Sampler &&S) {
+                        double skin, int64_t thermo_every, int with_stress, double *thermo, Sampler &&S, const char *who = "uf3_md_run") {
     uf3_ctx *c = md->c;
-    int rc = md_run_check(c, "uf3_md_run", n_steps, dt_fs, temperature_K, friction_per_fs, nullptr, thermo_every, skin, thermo);
+    int rc = md_run_check(c, who, n_steps, dt_fs, temperature_K, friction_per_fs, nullptr, thermo_every, skin, thermo);
     if (rc) return rc;
     if (n_steps == 0) return UF3_OK;
     HIPCHK(c, hipSetDevice(c->device));
@@ -4331,6 +4472,83 @@ extern "C" int uf3_md_run_grade(uf3_md *md, int64_t n_steps, double dt_fs, doubl
                         MdGradeSampler(md, n_steps, d_w, grade_every, grade_stop, grades, steps_done));
 }
 
+// uf3_md_run_msd: one record [n_frames][4 S + 4] per sample (k_md_msd_partial, k_md_msd_frame: uf3_md.h) of the closed state,
+// copied out at the end of the run.  The sample only reads: the trajectory and the thermo records do not depend on it
+static int md_msd_origin(uf3_md *md, const double *origin, const std::string &who) {
+    uf3_ctx *c = md->c;
+    const size_t n3 = 3 * (size_t)md->natoms;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (origin && !md_finite(origin, n3)) return fail(c, UF3_EINVAL, who + ": origin must be finite");
+    if (md->msd_origin.ensure(8 * n3)) return fail(c, UF3_ENOMEM, who + ": out of device memory");
+    if (origin) HIPCHK(c, hipMemcpyAsync(md->msd_origin.p, origin, 8 * n3, hipMemcpyHostToDevice, c->stream));
+    else if (md->wrap) {
+        int rc = md_unwrap(md, md->msd_origin.as<double>(), false, nullptr);
+        if (rc) return rc;
+    } else
+        HIPCHK(c, hipMemcpyAsync(md->msd_origin.p, md->pos.p, 8 * n3, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    md->msd_origin_set = true;
+    return UF3_OK;
+}
+
+extern "C" int uf3_md_msd_origin(uf3_md *md, const double *origin) {
+    if (!md) return fail(nullptr, UF3_EINVAL, "uf3_md_msd_origin: null md");
+    return md_msd_origin(md, origin, "uf3_md_msd_origin");
+}
+
+struct MdMsdSampler : MdSampler {
+    uf3_md *md; int64_t n_msd; double *out; MdMsdArgs A; int width;
+    MdMsdSampler(uf3_md *md, int64_t n_steps, int64_t msd_every, double *msd)
+        : md(md), n_msd(msd_every ? n_steps / msd_every : 0), out(msd), width(4 * md->b->host.S + 4) { every = msd_every; }
+    int prepare() {
+        if (!n_msd) return UF3_OK;
+        uf3_ctx *c = md->c;
+        const char *who = "uf3_md_run_msd";
+        int rc = md_chunks(md, who);
+        if (rc) return rc;
+        if (!md->msd_origin_set) { rc = md_msd_origin(md, nullptr, who); if (rc) return rc; }    // (no origin yet: where the run starts)
+        if (!md->msd_spec.p) {
+            if (md->msd_spec.ensure((size_t)md->natoms)) return fail(c, UF3_ENOMEM, "uf3_md_run_msd: out of device memory");
+            HIPCHK(c, hipMemcpyAsync(md->msd_spec.p, md->spec.data(), (size_t)md->natoms, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        if (md->msd_partial.ensure(8 * (size_t)md->chunks.n_blocks * width) || md->msd_ring.ensure(8 * (size_t)n_msd * md->n_frames * width))
+            return fail(c, UF3_ENOMEM, "uf3_md_run_msd: out of device memory");
+        const ChunkTable &ct = md->chunks;
+        A.pos = md->pos.as<double>(); A.origin = md->msd_origin.as<double>(); A.mass = md->mass.as<double>();
+        A.img = md->wrap ? md->img.as<int>() : nullptr; A.cells = md->wrap ? md->cells_now() : nullptr;
+        A.spec = md->msd_spec.as<signed char>(); A.frame_of = ct.frame_of.as<int>(); A.blk_n = ct.blk_n.as<int>();
+        A.frame_blk = ct.frame_blk.as<int>(); A.blk_lo = ct.blk_lo.as<long long>();
+        A.partial = md->msd_partial.as<double>(); A.rec = nullptr; A.S = md->b->host.S;
+        return UF3_OK;
+    }
+    int sample(int64_t s, bool &) {
+        uf3_ctx *c = md->c;
+        A.rec = md->msd_ring.as<double>() + (size_t)s * md->n_frames * width;
+        hipLaunchKernelGGL(k_md_msd_partial, dim3((unsigned)md->chunks.n_blocks), dim3(UF3_MD_THREADS), 0, c->stream, A);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k_md_msd_frame, dim3((unsigned)md->n_frames), dim3(64), 0, c->stream, A);
+        HIPCHK(c, hipGetLastError());
+        return UF3_OK;
+    }
+    int copy_out() {
+        uf3_ctx *c = md->c;
+        if (n_msd) HIPCHK(c, hipMemcpyAsync(out, md->msd_ring.p, 8 * (size_t)n_msd * md->n_frames * width, hipMemcpyDeviceToHost, c->stream));
+        return UF3_OK;
+    }
+};
+
+extern "C" int uf3_md_run_msd(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
+                              double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t msd_every, double *msd) {
+    if (!md) return fail(nullptr, UF3_EINVAL, "uf3_md_run_msd: null md");
+    uf3_ctx *c = md->c;
+    if (msd_every < 0) return fail(c, UF3_EINVAL, "uf3_md_run_msd: msd_every must be >= 0");
+    int rc = md_records_check(c, "uf3_md_run_msd", "msd", "msd", msd_every && n_steps > 0 ? n_steps / msd_every : 0, msd);
+    if (rc) return rc;
+    return md_run_entry(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, skin, thermo_every, with_stress, thermo,
+                        MdMsdSampler(md, n_steps, msd_every, msd), "uf3_md_run_msd");
+}
+
 // ------------------------------------------------------------------------------ constant pressure (uf3_md_run_npt, uf3_npt.h)
 // The same state as above plus one piston per frame.  Between two force calls: k_npt_partial, k_npt_frame, k_npt_move.  The
 // cells change on every step and stay on the device: the evaluator runs on its persistent lists in the "cells live" mode of
@@ -4356,7 +4574,7 @@ static int npt_init(uf3_md *md) {
         for (int k = 0; k < 3; k++) S.hgt0[k] = vol / norm3(nrm[k]);
     }
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = chunk_table_build(c, md->offsets, nf, UF3_NPT_THREADS, md->chunks, "uf3_md_run_npt");
+    int rc = md_chunks(md, "uf3_md_run_npt");
     if (rc) return rc;
     if (md->npt_st.ensure(sizeof(NptFrame) * (size_t)nf) || md->npt_coef.ensure(sizeof(NptCoef) * (size_t)nf) ||
         md->npt_partial.ensure(24 * (size_t)md->chunks.n_blocks) || md->cells_dev.ensure(72 * (size_t)nf))

@@ -10,6 +10,10 @@
 //   k_md_init_com    one workgroup per frame: centre-of-mass velocity removed, optional rescale to the exact temperature (3N
 //                    degrees of freedom)
 //   k_philox_debug   the generator on caller-given counters and keys (uf3_philox_debug, tests)
+//   k_md_wrap        opt-in periodic wrapping (uf3_md_set_wrap), one thread per atom: pos -= n . cell, img += n with n = floor of
+//                    the fractional coordinate on periodic axes; k_md_unwrap forms pos + img . cell (or folds it back into pos)
+//   k_md_msd_partial, k_md_msd_frame   the mean-squared-displacement sums of one sample (uf3_md_run_msd): one workgroup per chunk
+//                    of the drivers' chunk table, then one per frame that adds the chunks in their order
 //
 // Units: Angstrom, fs, amu, eV, K.  Nothing here uses atomics: the sums are thread-strided partial sums + a tree in LDS, whose
 // order depends on the atom count alone, so thermo records repeat bit for bit.
@@ -209,6 +213,153 @@ __global__ void __launch_bounds__(UF3_MD_THREADS) k_md_init_com(double *vel, con
     for (long long i = lo + threadIdx.x; i < hi; i += UF3_MD_THREADS)
 #pragma unroll
         for (int k = 0; k < 3; k++) vel[3 * i + k] *= scale;
+}
+
+// ---- periodic wrapping with image counts (uf3_md_set_wrap) ------------------------------------------------------------------
+// A wrapping object stores pos and int32 img [N][3]; its position is pos + img . cell with the frame's CURRENT cell (rows are
+// lattice vectors).  k_md_wrap runs in front of every neighbour-list build made for the object and in front of every evaluation
+// on the rebuild-everything route, never between a list build and the steps that use those lists.  The invariant: an evaluation
+// of a wrapping object never sees an atom farther outside its cell than that atom has moved since the last wrap -- at most
+// skin / 2, or the constant-pressure limit -- so the evaluator's image-range rule and the nearest-image rule of the samplers
+// (k_flux_lists) describe the same crystal.  A wrap rounds (pos - n . cell is not exact): a trajectory's last bits depend on
+// where the lists were built.
+struct MdWrapArgs {
+    double *pos;                       // [N][3]
+    int *img;                          // [N][3] image counts
+    const double *cells;               // [n_frames][9] the current cells
+    const unsigned char *pbc;          // [n_frames][3]
+    const int *frame_of;               // [N]
+    long long n;
+    int *changed;                      // set to 1 by every thread that moved its atom (may be null)
+};
+
+// the cell's rows crossed pairwise, nrm[k] . a_k = vol: the fractional coordinate k of x is x . nrm[k] / vol (taken against the
+// cell, not against edge lengths)
+__device__ __forceinline__ double md_cell_normals(const double *c, double nrm[3][3]) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double *a = c + 3 * ((k + 1) % 3), *b = c + 3 * ((k + 2) % 3);
+        nrm[k][0] = a[1] * b[2] - a[2] * b[1];
+        nrm[k][1] = a[2] * b[0] - a[0] * b[2];
+        nrm[k][2] = a[0] * b[1] - a[1] * b[0];
+    }
+    return c[0] * nrm[0][0] + c[1] * nrm[0][1] + c[2] * nrm[0][2];
+}
+
+// Idempotent up to one case: a coordinate that lands within an ulp of a face may be wrapped once more by the next call, which
+// is harmless (it is the same crystal either way).  An atom inside the cell, a non-periodic axis and a non-periodic frame are
+// left alone bit for bit.
+__global__ void __launch_bounds__(256) k_md_wrap(MdWrapArgs A) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    const int f = A.frame_of[i];
+    const unsigned char *per = A.pbc + 3 * (size_t)f;
+    if (!(per[0] | per[1] | per[2])) return;
+    const double *c = A.cells + 9 * (size_t)f;
+    double nrm[3][3], x[3];
+    const double vol = md_cell_normals(c, nrm);
+#pragma unroll
+    for (int k = 0; k < 3; k++) x[k] = A.pos[3 * i + k];
+    int n[3] = {0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if (!per[k]) continue;
+        const double fl = floor((x[0] * nrm[k][0] + x[1] * nrm[k][1] + x[2] * nrm[k][2]) / vol);
+        if (fabs(fl) <= 1.0e9) n[k] = (int)fl;          // (a singular cell gives no number: left alone)
+    }
+    if (!(n[0] | n[1] | n[2])) return;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if (!n[k]) continue;
+#pragma unroll
+        for (int d = 0; d < 3; d++) x[d] = fma(-(double)n[k], c[3 * k + d], x[d]);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) { A.pos[3 * i + k] = x[k]; A.img[3 * i + k] += n[k]; }
+    if (A.changed) *A.changed = 1;
+}
+
+// pos + img . cell of one atom (img null: pos)
+__device__ __forceinline__ void md_unwrapped(const double *pos, const int *img, const double *cells, const int *frame_of, long long i,
+                                             double x[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) x[k] = pos[3 * i + k];
+    if (!img) return;
+    const double *c = cells + 9 * (size_t)frame_of[i];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const int n = img[3 * i + k];
+        if (!n) continue;
+#pragma unroll
+        for (int d = 0; d < 3; d++) x[d] = fma((double)n, c[3 * k + d], x[d]);
+    }
+}
+
+// out = pos + img . cell; fold: out is pos itself and img becomes zero (uf3_md_set_wrap off)
+__global__ void __launch_bounds__(256) k_md_unwrap(MdWrapArgs A, double *out, int fold) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    double x[3];
+    md_unwrapped(A.pos, A.img, A.cells, A.frame_of, i, x);
+#pragma unroll
+    for (int k = 0; k < 3; k++) out[3 * i + k] = x[k];
+    if (fold && (A.img[3 * i] | A.img[3 * i + 1] | A.img[3 * i + 2])) {
+        A.img[3 * i] = 0; A.img[3 * i + 1] = 0; A.img[3 * i + 2] = 0;
+        if (A.changed) *A.changed = 1;
+    }
+}
+
+// ---- mean-squared displacement (uf3_md_run_msd) -------------------------------------------------------------------------------
+// One record per sample and frame of 4 S + 4 doubles, S the basis' species count: per species sum |dr|^2, sum dx, sum dy, sum dz
+// over its atoms, dr = pos + img . cell - origin; then sum m dr (3) and sum m.  No atomics: the order of every sum depends on
+// the atom counts alone, so records repeat bit for bit.  The reductions go species by species through 4 x 256 doubles of LDS.
+struct MdMsdArgs {
+    const double *pos, *origin, *mass, *cells;     // cells: [n_frames][9], read only when img is not null
+    const int *img;                                // null: the object never wrapped
+    const signed char *spec;                       // [N] species index (-1: outside the basis, in the mass sums only)
+    const int *frame_of, *blk_n, *frame_blk;       // the chunk table
+    const long long *blk_lo;
+    double *partial;                               // [n_blocks][4 S + 4]
+    double *rec;                                   // [n_frames][4 S + 4]
+    int S;
+};
+
+__global__ void __launch_bounds__(UF3_MD_THREADS) k_md_msd_partial(MdMsdArgs A) {
+    __shared__ double lds[4 * UF3_MD_THREADS];
+    const int b = blockIdx.x, t = threadIdx.x, W = 4 * A.S + 4;
+    double d[3] = {0.0, 0.0, 0.0}, m = 0.0;
+    int s = -2;
+    if (t < A.blk_n[b]) {
+        const long long i = A.blk_lo[b] + t;
+        md_unwrapped(A.pos, A.img, A.cells, A.frame_of, i, d);
+#pragma unroll
+        for (int k = 0; k < 3; k++) d[k] -= A.origin[3 * i + k];
+        m = A.mass[i];
+        s = A.spec[i];
+    }
+    const double d2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+    for (int sp = 0; sp <= A.S; sp++) {
+        const bool last = sp == A.S;               // the mass-weighted sums of every atom
+        const bool mine = last ? s != -2 : s == sp;
+        double q[4] = {0.0, 0.0, 0.0, 0.0};
+        if (mine) {
+            q[0] = last ? m * d[0] : d2; q[1] = last ? m * d[1] : d[0]; q[2] = last ? m * d[2] : d[1]; q[3] = last ? m : d[2];
+        }
+        md_block_sum<4>(q, lds);
+        if (t == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) A.partial[(size_t)b * W + 4 * sp + k] = q[k];
+        }
+    }
+}
+
+// one workgroup per frame: entry k of the record is thread k's sum of the chunks' entries, in chunk order
+__global__ void __launch_bounds__(64) k_md_msd_frame(MdMsdArgs A) {
+    const int f = blockIdx.x, k = threadIdx.x, W = 4 * A.S + 4;
+    if (k >= W) return;
+    double s = 0.0;
+    for (int b = A.frame_blk[f]; b < A.frame_blk[f + 1]; b++) s += A.partial[(size_t)b * W + k];
+    A.rec[(size_t)f * W + k] = s;
 }
 
 __global__ void k_philox_debug(long long n, const uint4 *ctr, const uint2 *key, uint4 *out) {

@@ -4,7 +4,9 @@
 evaluator's (``UFCalculator``'s model, its MD route with a neighbour-list skin), the integrator is one fused kernel between
 two force calls.  Many small replicas in one batch cost no more machinery than one large frame.
 
-Units: Angstrom, fs, amu, eV, K.  Positions are kept unwrapped (``get_positions(wrap=True)`` wraps a copy).  Random numbers
+Units: Angstrom, fs, amu, eV, K.  Positions are reported unwrapped (``get_positions(wrap=True)`` wraps a copy); with
+``wrap=True`` the object stores them wrapped next to integer image counts (``get_images``) and atoms may cross cell faces:
+diffusion, a melt.  ``run(n, msd_every=k)`` samples the mean-squared displacement on the device.  Random numbers
 are counter-based (Philox4x32-10 on (atom, absolute step, draw), keyed by the seed), so ``run(60)`` equals
 ``run(25); run(35)`` and the trajectory does not depend on how the batch is launched.
 
@@ -24,6 +26,12 @@ every k-th step; ``heat_flux_autocorrelation`` and ``green_kubo`` turn the serie
 
     rec = md.run(200000, flux_every=10)
     kappa = green_kubo(rec['heat_flux'][:, 0], 10 * md.timestep_fs, md.volumes[0], 300.0, max_lag=2000)
+
+Diffusion: a wrapping object and the mean-squared displacement of every k-th step, per species and over all atoms.
+
+    dyn = MolecularDynamics(calc, atoms_list, 1.0, masses=..., temperature_K=2500, friction_per_fs=0.01, wrap=True)
+    rec = dyn.run(100000, msd_every=10)
+    D = diffusion_coefficient(rec['msd_all'][:, 0], 10 * dyn.timestep_fs)             # Angstrom^2 / fs
 
 Each ``run`` starts with one neighbour-list build (it sets the context's skin for its own duration and puts the caller's
 back).  A basis without 3-body terms never takes the evaluator's MD route and rebuilds its lists on every step: correct,
@@ -94,6 +102,52 @@ def temperature(kinetic_energy_eV, n_atoms):
 
 
 WHO = "MolecularDynamics"
+
+
+def msd_records(raw, species_counts, first_step, every):
+    """The entries ``run(..., msd_every=k)`` adds, from raw records [n, n_frames, 4 S + 4] (``uf3_md_run_msd``: per species
+    sum |dr|^2, sum dx, sum dy, sum dz; then sum m dr (3) and sum m) and the atoms of every species in every frame
+    ``species_counts`` [n_frames, S]: ``msd`` [n, n_frames, S] the per-species mean (NaN for a species a frame lacks),
+    ``msd_all`` [n, n_frames] the mean over all atoms, ``msd_com_removed`` and ``msd_all_com_removed`` of the same two shapes:
+    the mean of |dr_i - dr_cm|^2 = (1/N) sum |dr_i|^2 - 2 dr_cm . <dr> + |dr_cm|^2 with the frame's mass-weighted
+    dr_cm = sum m dr / sum m, and ``msd_step``."""
+    raw = np.asarray(raw, dtype=float)
+    cnt = np.asarray(species_counts, dtype=float)
+    n_sp = cnt.shape[1]
+    if raw.ndim != 3 or raw.shape[1] != cnt.shape[0] or raw.shape[2] != 4 * n_sp + 4:
+        raise ValueError(f"msd_records: raw must be [n, {cnt.shape[0]}, {4 * n_sp + 4}], got {list(raw.shape)}")
+    per = raw[..., :4 * n_sp].reshape(raw.shape[0], raw.shape[1], n_sp, 4)
+    sq, lin = per[..., 0], per[..., 1:]                                      # [n, nf, S], [n, nf, S, 3]
+    cm = raw[..., 4 * n_sp:4 * n_sp + 3] / raw[..., 4 * n_sp + 3:]           # [n, nf, 3]
+    cm2 = np.sum(cm * cm, axis=-1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        n_s = np.where(cnt > 0, cnt, np.nan)[None]                           # [1, nf, S]
+        msd = sq / n_s
+        com_s = msd - 2.0 * np.einsum("nfd,nfsd->nfs", cm, lin) / n_s + cm2[..., None]
+    n_all = cnt.sum(axis=1)[None]
+    msd_all = sq.sum(axis=2) / n_all
+    com_all = msd_all - 2.0 * np.einsum("nfd,nfd->nf", cm, lin.sum(axis=2)) / n_all + cm2
+    return dict(msd=msd, msd_all=msd_all, msd_com_removed=com_s, msd_all_com_removed=com_all,
+                msd_step=first_step + every * np.arange(1, raw.shape[0] + 1, dtype=np.int64))
+
+
+def diffusion_coefficient(msd, sample_time_fs, fit_from=0.5):
+    """Einstein's D = slope / 6 in Angstrom^2 / fs of a mean-squared displacement series ``msd`` [n, ...] (Angstrom^2) sampled
+    every ``sample_time_fs``: the least-squares slope of a straight line (with intercept) through the samples from fraction
+    ``fit_from`` of the record to its end; sample k lies at time (k + 1) ``sample_time_fs``.  Returns an array of the trailing
+    shape (a float for a 1-d series)."""
+    who = "diffusion_coefficient"
+    y = np.asarray(msd, dtype=float)
+    dt = check_real(who, "sample_time_fs", sample_time_fs, strict=True)
+    frac = check_real(who, "fit_from", fit_from, hi=1.0)
+    if y.ndim < 1 or y.shape[0] < 2:
+        raise ValueError(f"{who}: msd must hold at least two samples along its first axis, got {list(y.shape)}")
+    lo = min(int(np.floor(frac * y.shape[0])), y.shape[0] - 2)
+    t = dt * np.arange(lo + 1, y.shape[0] + 1, dtype=float)
+    tc = t - t.mean()
+    yy = y[lo:]
+    slope = np.tensordot(tc, yy - yy.mean(axis=0), axes=(0, 0)) / np.dot(tc, tc)
+    return slope / 6.0 if np.ndim(slope) else float(slope) / 6.0
 
 
 def resolve_masses(frames, masses=None):
@@ -167,17 +221,28 @@ def npt_records(raw, n_atoms, first_step, every):
 class MolecularDynamics(Driver):
     """Velocity Verlet / Langevin / constant-pressure dynamics of a batch of frames on the device (module text above).
 
-    Atoms outside the cell: positions are kept unwrapped and go to the evaluator as they are, and the evaluator takes the
-    reference's finite image range around the positions as given (``include/uf3_hip.h``, above ``uf3_md_create``; DESIGN.md
-    section 7).  An atom that leaves its cell during a run (diffusion, a melt) loses the interactions that range no longer reaches from where it
-    is: energies and forces are then ``evaluate_frames``' of the unwrapped positions, not the wrapped crystal's.  Start from
-    wrapped frames, and before atoms can cross a cell face stop, ``set_positions(get_positions(wrap=True))`` and go on."""
+    Atoms outside the cell.  ``wrap=True`` (or ``dyn.wrap = True``): the object stores wrapped positions and int32 image counts;
+    its position is ``pos + images @ cell`` with the current cell, which is what ``get_positions()`` and ``get_atoms()`` return.
+    Positions are folded into the cell on the device in front of every neighbour-list build made for the object (and in front
+    of every evaluation when the lists are rebuilt every time: ``skin=0``, 2-body bases), never between a build and the steps on
+    its lists, so no evaluation sees an atom farther outside its cell than it has moved since the last wrap (at most skin / 2)
+    and atoms may cross cell faces freely.  A wrap rounds: the last bits of a wrapping trajectory depend on where the lists
+    were built (the skin, the run boundaries); it is deterministic for a given sequence of calls, and ``run(60)`` agrees with
+    ``run(25); run(35)`` to 1e-10, not bit for bit.  ``set_positions`` takes positions as given and zeroes the image counts;
+    turning ``wrap`` off folds the image counts back into the positions.
+
+    ``wrap=False``, the default, for which the hazard remains: positions are kept unwrapped and go to the evaluator as they
+    are, and the evaluator takes the reference's finite image range around the positions as given (``include/uf3_hip.h``, above
+    ``uf3_md_create``).  An atom that leaves its cell during such a run loses the interactions that range no
+    longer reaches from where it is: energies and forces are then ``evaluate_frames``' of the unwrapped positions, not the
+    wrapped crystal's.  Use ``wrap=True`` for anything that diffuses."""
     KIND, WHO = "md", WHO
 
     def __init__(self, calculator, atoms_or_list, timestep_fs, masses=None, temperature_K=0.0, friction_per_fs=0.0, seed=0,
                  skin=0.5, device=None, pressure_eV_A3=None, barostat_time_fs=None, barostat_friction_per_fs=0.0,
-                 piston_temperature_K=None):
+                 piston_temperature_K=None, wrap=False):
         # every argument is checked before the device is touched
+        wrap = self._check_wrap(wrap)
         self.timestep_fs = check_real(WHO, "timestep_fs", timestep_fs, strict=True)
         self.temperature_K = check_real(WHO, "temperature_K", temperature_K)
         self.friction_per_fs = check_real(WHO, "friction_per_fs", friction_per_fs)
@@ -210,6 +275,26 @@ class MolecularDynamics(Driver):
         self._grade_w_host = self._grade_w_dev = None
         vel = None if vel is None else np.ascontiguousarray(vel)
         self._create(calculator, device, [_lib._p(self._batch.pos), _lib._p(vel), _lib._p(self._batch.z), _lib._p(self.masses)])
+        if wrap:
+            self.wrap = True
+
+    @staticmethod
+    def _check_wrap(value):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"MolecularDynamics: wrap must be True or False, got {value!r}")
+        return bool(value)
+
+    @property
+    def wrap(self):
+        """Whether the object wraps (class text).  Setting it True wraps now and in front of every list build from then on;
+        setting it False folds the image counts into the positions."""
+        return getattr(self, "_wrap", False)
+
+    @wrap.setter
+    def wrap(self, value):
+        value = self._check_wrap(value)
+        self.ctx.check(self.ctx.lib.uf3_md_set_wrap(self._live(), int(value)))
+        self._wrap = value
 
     def _check_barostat(self, pressure, tau, gamma_p, t_piston):
         """The constant-pressure arguments, checked as a set (nothing touches the device); returns what a run passes on."""
@@ -285,6 +370,19 @@ class MolecularDynamics(Driver):
                 pos[off[k]:off[k + 1]] = frac @ cell
         return pos
 
+    def get_images(self):
+        """[N, 3] int: the image counts of a wrapping object, position = stored position + images @ cell (zeros with
+        ``wrap=False``)."""
+        img = np.zeros((self._batch.n_atoms, 3), dtype=np.int32)
+        self.ctx.check(self.ctx.lib.uf3_md_get_wrapped(self._live(), None, _lib._p(img)))
+        return img.astype(np.int64)
+
+    def set_msd_origin(self, positions=None):
+        """The origin of ``run(..., msd_every=k)``'s displacements: [N, 3] Angstrom, default the current (unwrapped) positions.
+        A sampling run of an object that never got one starts from where that run starts."""
+        p = None if positions is None else self._state_array("positions", positions)
+        self.ctx.check(self.ctx.lib.uf3_md_msd_origin(self._live(), _lib._p(p)))
+
     def get_velocities(self):
         """[N, 3] Angstrom / fs."""
         return self._get("vel")
@@ -331,7 +429,7 @@ class MolecularDynamics(Driver):
         s = self.seed if seed is None else check_int(WHO, "seed", seed, 0, (1 << 64) - 1)
         self.ctx.check(self.ctx.lib.uf3_md_init_velocities(self._live(), t, s, int(bool(exact))))
 
-    def run(self, n_steps, thermo_every=0, stress=False, flux_every=0, grade_every=0, grade_stop=None):
+    def run(self, n_steps, thermo_every=0, stress=False, flux_every=0, grade_every=0, grade_stop=None, msd_every=0):
         """``n_steps`` steps (Langevin when ``friction_per_fs`` > 0, else NVE; at a pressure NPT / NPH).  Returns the thermo
         records of every ``thermo_every``-th step (see ``thermo_records``; empty arrays when ``thermo_every`` is 0).  At a
         pressure the records always carry stress and pressure (of that step's volume), volume, cell_scale and conserved.
@@ -346,12 +444,20 @@ class MolecularDynamics(Driver):
         ``grade`` exceeds it -- the whole batch stops; ``steps_done`` steps were made, every record is cut to them, the state is
         that of ``run(steps_done)`` and a later ``run`` goes on from it.  The trajectory and the thermo records do not depend on
         the sampling.  W is the calculator's ``model.whitening()`` (``ValueError`` without a posterior), uploaded once per
-        object.  Not at a pressure and not together with ``flux_every``: ``UF3Error`` (UF3_EINVAL)."""
+        object.  Not at a pressure and not together with ``flux_every``: ``UF3Error`` (UF3_EINVAL).
+        ``msd_every`` > 0: after every ``msd_every``-th step the mean-squared displacement of the closed state from the origin
+        (``set_msd_origin``; ``uf3_md_run_msd``), summed on the device without atomics: ``msd`` [n_samples, n_frames, S] per
+        species of the basis (ascending atomic number; NaN for a species a frame lacks), ``msd_all`` [n_samples, n_frames],
+        ``msd_com_removed`` and ``msd_all_com_removed`` (the frame's mass-weighted centre-of-mass displacement taken out),
+        ``msd_step`` and the raw sums ``msd_sums`` (``msd_records``).  Needs ``wrap=True`` as soon as atoms may leave their cell.
+        The trajectory and the thermo records do not depend on it.  Not at a pressure and not together with ``flux_every`` or
+        ``grade_every``: ``UF3Error`` (UF3_EINVAL)."""
         n_steps = check_int(WHO, "n_steps", n_steps)
         every = check_int(WHO, "thermo_every", thermo_every)
         flux_every = check_int(WHO, "flux_every", flux_every)
         grade_every = check_int(WHO, "grade_every", grade_every)
         grade_stop = 0.0 if grade_stop is None else check_real(WHO, "grade_stop", grade_stop, lo=None)
+        msd_every = check_int(WHO, "msd_every", msd_every)
         pressure = getattr(self, "pressure_eV_A3", None)        # (a bare object, as tests/test_md_host.py makes, has no barostat)
         if flux_every and pressure is not None:
             raise _lib.UF3Error(1, "uf3_md_run_flux: the heat current is sampled at constant volume only (flux_every with "
@@ -361,6 +467,11 @@ class MolecularDynamics(Driver):
                                    "pressure_eV_A3)")
         if grade_every and flux_every:
             raise _lib.UF3Error(1, "uf3_md_run_grade: grade_every and flux_every do not go into one run")
+        if msd_every and pressure is not None:
+            raise _lib.UF3Error(1, "uf3_md_run_msd: the mean-squared displacement is sampled at constant volume only (msd_every "
+                                   "with pressure_eV_A3)")
+        if msd_every and (flux_every or grade_every):
+            raise _lib.UF3Error(1, "uf3_md_run_msd: msd_every does not go into one run with flux_every or grade_every")
         w_host = self.calculator.model.whitening() if grade_every else None    # (the ValueError, before anything touches the device)
         dt = check_real(WHO, "timestep_fs", self.timestep_fs, strict=True)
         temp = check_real(WHO, "temperature_K", self.temperature_K)
@@ -388,6 +499,9 @@ class MolecularDynamics(Driver):
         elif grade_every:
             gr = np.zeros((n_steps // grade_every, n_frames, 2))
             self.ctx.check(lib.uf3_md_run_grade(*args, self._grade_w(w_host), grade_every, grade_stop, ring(gr), C.byref(done)))
+        elif msd_every:
+            ms = np.zeros((n_steps // msd_every, n_frames, 4 * self._dbasis.n_species + 4))
+            self.ctx.check(lib.uf3_md_run_msd(*args, msd_every, ring(ms)))
         else:
             self.ctx.check(lib.uf3_md_run(*args))
         done = done.value                   # (fewer than asked only when a grade sample stopped the run: every record is cut to them)
@@ -403,7 +517,16 @@ class MolecularDynamics(Driver):
             out["grade_atom"] = gr[:, :, 1].astype(np.int64)
             out["grade_step"] = first + grade_every * np.arange(1, len(gr) + 1, dtype=np.int64)
             out["steps_done"] = done
+        elif msd_every:
+            out.update(msd_records(ms, self._species_counts(), first, msd_every))
+            out["msd_sums"] = ms
         return out
+
+    def _species_counts(self):
+        """[n_frames, S] the atoms of every species of the basis (ascending atomic number) in every frame."""
+        zs = [atomic_numbers[e] for e in self.calculator.bspline_config.chemical_system.element_list]
+        off = self._batch.offsets
+        return np.array([[int(np.sum(self._batch.z[off[k]:off[k + 1]] == q)) for q in zs] for k in range(self._batch.n_frames)])
 
     def _grade_w(self, w_host):
         """Device address of the whitening matrix: uploaded once per object (again after a refit made a new one)."""
