@@ -7,6 +7,10 @@ The basis description is read from any object exposing the reference's
 ``BSplineBasis`` attribute names (``knots_map``, ``symmetry``, ``template_mask``,
 ``flat_weights``, ``leading_trim`` ...), so the same wrapper runs on the
 reference's own class (golden capture) and on ``uf3_amd``'s.
+
+The C source builds twice: ``libuf3oracle.so`` (fp64; ``featurize``, ``evaluate``) and ``libuf3oracle_x.so`` (``long double``
+values on fp64 decisions; ``featurize_x``, ``evaluate_x``, which also return the magnitude M of every entry -- see
+uf3_oracle.c and tests/_precision.py).
 """
 import ctypes as C
 import os
@@ -15,6 +19,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
+_LIB_X = None
 
 _SYMBOLS = ("X H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga "
             "Ge As Se Br Kr Rb Sr Y Zr Nb Mo Tc Ru Rh Pd Ag Cd In Sn Sb Te I Xe Cs Ba La Ce Pr Nd "
@@ -41,25 +46,47 @@ class _Frame(C.Structure):
                 ("cell", C.c_void_p), ("pbc", C.c_void_p)]
 
 
-def build(force=False):
-    """Compile libuf3oracle.so next to the source (gcc, seconds)."""
-    so = os.path.join(_HERE, "libuf3oracle.so")
+def build(force=False, name="libuf3oracle.so"):
+    """Compile libuf3oracle.so (or ``name``) next to the source (gcc, seconds)."""
+    so = os.path.join(_HERE, name)
     src = os.path.join(_HERE, "uf3_oracle.c")
     if force or not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        subprocess.check_call(["make", "-C", _HERE, "-B", "libuf3oracle.so"],
+        subprocess.check_call(["make", "-C", _HERE, "-B", name],
                               stdout=subprocess.DEVNULL)
+    return so
+
+
+def _load(name):
+    so = C.CDLL(build(name=name))
+    for f in ("uf3o_featurize", "uf3o_featurize_x", "uf3o_eval", "uf3o_eval_virial", "uf3o_eval_x", "uf3o_real_mant_dig"):
+        getattr(so, f).restype = C.c_int
+    so.uf3o_supercell.restype = C.c_int64
     return so
 
 
 def lib():
     global _LIB
     if _LIB is None:
-        _LIB = C.CDLL(build())
-        _LIB.uf3o_featurize.restype = C.c_int
-        _LIB.uf3o_eval.restype = C.c_int
-        _LIB.uf3o_eval_virial.restype = C.c_int
-        _LIB.uf3o_supercell.restype = C.c_int64
+        _LIB = _load("libuf3oracle.so")
     return _LIB
+
+
+def lib_x():
+    """The extended build of the same source (``real`` = long double, 64-bit mantissa).  Only its ``*_x`` entries are called:
+    its arrays of values are ``np.longdouble``."""
+    global _LIB_X
+    if _LIB_X is None:
+        if np.finfo(np.longdouble).nmant + 1 < 64 or np.dtype(np.longdouble).itemsize != C.sizeof(C.c_longdouble):
+            raise RuntimeError("np.longdouble is not the C long double with a 64-bit mantissa on this platform")
+        _LIB_X = _load("libuf3oracle_x.so")
+        if _LIB_X.uf3o_real_mant_dig() < 64:
+            raise RuntimeError("libuf3oracle_x.so was built without an extended type")
+    return _LIB_X
+
+
+def mant_dig(extended=True):
+    """Mantissa bits of the arithmetic type of the extended (or the fp64) build."""
+    return int((lib_x() if extended else lib()).uf3o_real_mant_dig())
 
 
 def _ptr(a):
@@ -130,6 +157,57 @@ class _FrameView:
         f.n_atoms = len(self.z)
         f.pos, f.z, f.cell, f.pbc = _ptr(self.pos), _ptr(self.z), _ptr(self.cell), _ptr(self.pbc)
         self.c = f
+
+
+def _rows_x(so, dtype, ob, atoms, virial, pieces):
+    fv = _FrameView(atoms)
+    n, F = fv.c.n_atoms, ob.n_feat
+    val = {"xe": np.zeros(F, dtype), "xf": np.zeros((n, 3, F), dtype), "xv": np.zeros((6, F), dtype) if virial else None}
+    mag = {k: (np.zeros(v.shape) if v is not None else None) for k, v in val.items()}
+    pair_cnt, n3_cnt = np.zeros(max(1, ob.spec.n_pairs), dtype=np.int64), np.zeros(1, dtype=np.int64)
+    rc = so.uf3o_featurize_x(C.byref(ob.spec), C.byref(fv.c), _ptr(val["xe"]), _ptr(val["xf"]), _ptr(val["xv"]),
+                             _ptr(mag["xe"]), _ptr(mag["xf"]), _ptr(mag["xv"]), C.c_int(int(pieces)), _ptr(pair_cnt),
+                             _ptr(n3_cnt))
+    if rc:
+        raise RuntimeError(f"uf3o_featurize_x rc={rc}")
+    if not virial:
+        del val["xv"], mag["xv"]
+    val["pair_cnt"], val["n3_cnt"] = pair_cnt[:ob.spec.n_pairs].copy(), int(n3_cnt[0])
+    return val, mag
+
+
+def featurize_x(ob, atoms, virial=False, extended=True, pieces=False):
+    """
+    The rows of ``featurize`` from the extended build: ``(values, magnitudes)``, two dicts with keys ``xe`` [F], ``xf`` [N,3,F]
+    and, with ``virial=True``, ``xv`` [6,F] (the strain derivative of the energy row, Voigt, the convention of
+    ``evaluate(virial=True)``).  Values are ``np.longdouble``; a magnitude M (float64) is the first-order running error bound of
+    its entry (uf3_oracle.c): a result computed in fp64 lies within a modest multiple of ``2**-53 * M`` of the value.
+    ``values`` also holds ``pair_cnt`` [P] and ``n3_cnt``, the numbers of pairs and 3-body list entries summed.
+    ``extended=False`` runs the same entry of the fp64 build (values float64, the same magnitudes to rounding).
+    ``pieces=True`` widens the magnitudes of the 3-body columns to those of leg functions evaluated from local cubic pieces in
+    powers of the distance from the interval's lower knot (uf3_oracle.c: piece_abs), for the routes that do so.
+    """
+    if extended:
+        return _rows_x(lib_x(), np.longdouble, ob, atoms, virial, pieces)
+    return _rows_x(lib(), np.float64, ob, atoms, virial, pieces)
+
+
+def evaluate_x(ob, atoms, coefficients, virial=True, extended=True):
+    """``evaluate`` from the extended build: ``(values, magnitudes)``, dicts with keys ``e`` (scalar), ``f`` [N,3] and, with
+    ``virial=True``, ``v`` [6]; see ``featurize_x``."""
+    so, dtype = (lib_x(), np.longdouble) if extended else (lib(), np.float64)
+    c1, c2, c3 = split_coefficients(ob, coefficients)
+    fv = _FrameView(atoms)
+    e, f, v = np.zeros(1, dtype), np.zeros((fv.c.n_atoms, 3), dtype), np.zeros(6, dtype) if virial else None
+    me, mf, mv = np.zeros(1), np.zeros((fv.c.n_atoms, 3)), np.zeros(6) if virial else None
+    rc = so.uf3o_eval_x(C.byref(ob.spec), C.byref(fv.c), _ptr(c1), _ptr(c2), _ptr(c3), _ptr(e), _ptr(f), _ptr(v),
+                        _ptr(me), _ptr(mf), _ptr(mv))
+    if rc:
+        raise RuntimeError(f"uf3o_eval_x rc={rc}")
+    val, mag = {"e": e[0], "f": f}, {"e": me[0], "f": mf}
+    if virial:
+        val["v"], mag["v"] = v, mv
+    return val, mag
 
 
 def featurize(ob, atoms, energy=True, forces=True, indices=False):

@@ -38,10 +38,42 @@
  * reference's tests, and captures made by importing the reference in the build
  * container (tests/golden/make_golden.py).  See tests/test_oracle_golden.py.
  */
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+
+/*
+ * One source, two builds (oracle/Makefile).  `real` is the type of every VALUE: differences of positions and knots, norms,
+ * Cox-de Boor, direction cosines, products, accumulators.  libuf3oracle.so is built with real = double and is the oracle of
+ * the parity tests; libuf3oracle_x.so is built with -DUF3O_REAL='long double' (64-bit mantissa) and is what
+ * tests/_precision.py measures both the fp64 build and the kernels against.  Every DECISION -- cut-offs, the 3-body list range,
+ * leg masks, strict support masks, the half-open knot intervals of the recursion, searchsorted -- is taken on the fp64 distance
+ * by the expressions of the fp64 build, in both builds, so that both sum the same terms.  The inputs of both are the same
+ * doubles: the tiled supercell positions as build_supercell rounds them, the knots, the coefficients.
+ *
+ * The *_x entries return, beside every output entry, a magnitude M (double): a first-order running error bound,
+ *
+ *     M = sum over the entry's terms t of ( |t|_abs + sum over the term's distances r of rho_r |dt/dr|_abs ),
+ *
+ * where |.|_abs replaces every subtraction inside a term by the sum of the absolute values of its operands (the two summands
+ * of a derivative element, the three products of a 3-body force term, |cos|, |coefficient|), and the second part is the term's
+ * sensitivity to a relative rounding of its distances: rho_r = r for a pair distance and for the two centre legs of a triplet,
+ * rho_r = r_ij + r_ik for the third leg (any fp64 formulation of r_jk -- a difference of tiled positions rounded at
+ * |p + offset|, or of centre-relative vectors -- inherits roundings of the order of the lengths it is formed from).  A result
+ * computed in fp64 is expected within a modest multiple of 2^-53 M of the exact value: tests/_precision.py.
+ */
+#ifndef UF3O_REAL
+#define UF3O_REAL double
+#endif
+typedef UF3O_REAL real;
+_Static_assert(sizeof(real) == sizeof(double) || LDBL_MANT_DIG >= 64, "the extended build needs a 64-bit mantissa");
+#define rsqrt_(x) _Generic((real)0, long double: sqrtl, default: sqrt)(x)
+#define rabs(x) _Generic((real)0, long double: fabsl, default: fabs)(x)
+
+/* mantissa bits of `real` in this build (53 in libuf3oracle.so; LDBL_MANT_DIG in libuf3oracle_x.so) */
+int uf3o_real_mant_dig(void) { return sizeof(real) == sizeof(double) ? DBL_MANT_DIG : LDBL_MANT_DIG; }
 
 typedef struct {
     int n_species;            /* S, ascending Z */
@@ -220,30 +252,88 @@ static double dist3(const double *a, const double *b) {
     double d0 = a[0] - b[0], d1 = a[1] - b[1], d2 = a[2] - b[2];
     return sqrt(d0 * d0 + d1 * d1 + d2 * d2);
 }
+/* the same distance as a VALUE: from the same doubles, in `real` (dist3 itself where real is double) */
+static real rdist3(const double *a, const double *b) {
+    real d0 = (real)a[0] - b[0], d1 = (real)a[1] - b[1], d2 = (real)a[2] - b[2];
+    return rsqrt_(d0 * d0 + d1 * d1 + d2 * d2);
+}
 
 /* ------------------------------------------------------------ basis elements */
 /* Cox-de Boor on the element's own knots t[0..4]; degree k basis starting at knot s */
-static double bspl(const double *t, int s, int k, double x) {
-    if (k == 0) return (t[s] <= x && x < t[s + 1]) ? 1.0 : 0.0;
-    double a = 0.0, b = 0.0, d1 = t[s + k] - t[s], d2 = t[s + k + 1] - t[s + 1];
-    if (d1 > 0) a = (x - t[s]) / d1 * bspl(t, s, k - 1, x);
-    if (d2 > 0) b = (t[s + k + 1] - x) / d2 * bspl(t, s + 1, k - 1, x);
+/* (xd: the fp64 distance, which picks the knot interval; x: the distance as a value) */
+static real bspl(const double *t, int s, int k, double xd, real x) {
+    if (k == 0) return (t[s] <= xd && xd < t[s + 1]) ? 1.0 : 0.0;
+    real a = 0.0, b = 0.0, d1 = (real)t[s + k] - t[s], d2 = (real)t[s + k + 1] - t[s + 1];
+    if (d1 > 0) a = (x - t[s]) / d1 * bspl(t, s, k - 1, xd, x);
+    if (d2 > 0) b = (t[s + k + 1] - x) / d2 * bspl(t, s + 1, k - 1, xd, x);
     return a + b;
 }
 /* value (nu=0) or first derivative (nu=1) of the cubic element on knots t[0..4]; 0 outside [t0,t4] */
-static double basis_element(const double *t, double x, int nu) {
-    if (!(x >= t[0] && x <= t[4])) return 0.0;   /* extrapolate=False -> NaN -> 0 */
-    if (nu == 0) return bspl(t, 0, 3, x);
-    double a = 0.0, b = 0.0, d1 = t[3] - t[0], d2 = t[4] - t[1];
-    if (d1 > 0) a = 3.0 / d1 * bspl(t, 0, 2, x);
-    if (d2 > 0) b = 3.0 / d2 * bspl(t, 1, 2, x);
+static real basis_element(const double *t, double xd, real x, int nu) {
+    if (!(xd >= t[0] && xd <= t[4])) return 0.0;   /* extrapolate=False -> NaN -> 0 */
+    if (nu == 0) return bspl(t, 0, 3, xd, x);
+    real a = 0.0, b = 0.0, d1 = (real)t[3] - t[0], d2 = (real)t[4] - t[1];
+    if (d1 > 0) a = 3.0 / d1 * bspl(t, 0, 2, xd, x);
+    if (d2 > 0) b = 3.0 / d2 * bspl(t, 1, 2, xd, x);
     return a - b;
+}
+/* for the magnitudes: |B'|_abs (the derivative's two summands added, not subtracted) and |B''|_abs (likewise, down to the four
+   linear elements) of the cubic element.  The value itself is a sum of non-negative products: |B|_abs = B. */
+static void basis_element_abs(const double *t, double xd, real x, real *d1abs, real *d2abs) {
+    *d1abs = *d2abs = 0.0;
+    if (!(xd >= t[0] && xd <= t[4])) return;
+    real lin[3], q[2], qd[2];
+    for (int s = 0; s < 3; s++) lin[s] = bspl(t, s, 1, xd, x);
+    for (int s = 0; s < 2; s++) {
+        real e1 = (real)t[s + 2] - t[s], e2 = (real)t[s + 3] - t[s + 1];
+        q[s] = bspl(t, s, 2, xd, x);
+        qd[s] = (e1 > 0 ? 2.0 / e1 * lin[s] : 0.0) + (e2 > 0 ? 2.0 / e2 * lin[s + 1] : 0.0);
+    }
+    real c1 = (real)t[3] - t[0], c2 = (real)t[4] - t[1];
+    if (c1 > 0) { *d1abs += 3.0 / c1 * q[0]; *d2abs += 3.0 / c1 * qd[0]; }
+    if (c2 > 0) { *d1abs += 3.0 / c2 * q[1]; *d2abs += 3.0 / c2 * qd[1]; }
 }
 /* np.searchsorted(knots, x, side='left') */
 static int searchsorted_left(const double *t, int n, double x) {
     int lo = 0, hi = n;
     while (lo < hi) { int mid = (lo + hi) / 2; if (t[mid] < x) lo = mid + 1; else hi = mid; }
     return lo;
+}
+
+/*
+ * The same three magnitudes for a leg function that is evaluated from its local cubic PIECE: the kernels that keep window rows
+ * (k_featurize3 and the grouped matrix-core launch; uf3_hip.hip "window rows", uf3_feat3.h f3_eval) store, per knot interval
+ * (t_i, t_i+1], the four coefficients of every function alive there in powers of u = x - t_i and run Horner's rule with fused
+ * multiply-adds.  Horner's error is bounded by a small multiple of u_fp64 times  p~(u) = sum_k |c_k| u^k  (Higham, Accuracy and
+ * Stability of Numerical Algorithms, section 5.1), NOT times |p(u)|: for the functions that decay on the interval the
+ * coefficients alternate, p~ stays O(1) while p itself goes to 0 like (t_i+1 - x)^3, and the value carries an absolute error of
+ * order u_fp64 however small it is.  (Cox-de Boor, a sum of non-negative products, has no such term: its |B|_abs is B.)  That
+ * is inherent in the choice of pieces about the interval's lower knot, a documented design choice, so
+ * for those routes the magnitudes are widened by the quantity the choice is sensitive to, which follows from the inputs alone
+ * (knots and distance): m0 = p~(u), m1 = sum_k k |c_k| u^(k-1), m2 = sum_k k (k-1) |c_k| u^(k-2), each taken where it exceeds
+ * the Cox-de Boor magnitude.  The coefficients come from the recursion itself, carried out on polynomials in u on the interval
+ * that holds x.
+ */
+static void piece_abs(const double *t, double xd, real x, real *m0, real *m1, real *m2) {
+    int m = -1;
+    for (int s = 0; s < 4; s++) if (t[s] <= xd && xd < t[s + 1]) m = s;
+    *m0 = *m1 = *m2 = 0.0;
+    if (m < 0) return;
+    real P[4][4] = {{0}};
+    P[m][0] = 1.0;
+    for (int k = 1; k <= 3; k++)
+        for (int s = 0; s + k <= 3; s++) {
+            real np[4] = {0}, d1 = (real)t[s + k] - t[s], d2 = (real)t[s + k + 1] - t[s + 1];
+            for (int j = 0; j < 4; j++) {
+                if (d1 > 0) { np[j] += ((real)t[m] - t[s]) / d1 * P[s][j]; if (j < 3) np[j + 1] += P[s][j] / d1; }
+                if (d2 > 0) { np[j] += ((real)t[s + k + 1] - t[m]) / d2 * P[s + 1][j]; if (j < 3) np[j + 1] -= P[s + 1][j] / d2; }
+            }
+            for (int j = 0; j < 4; j++) P[s][j] = np[j];
+        }
+    real u = rabs(x - t[m]), c0 = rabs(P[0][0]), c1 = rabs(P[0][1]), c2 = rabs(P[0][2]), c3 = rabs(P[0][3]);
+    *m0 = c0 + u * (c1 + u * (c2 + u * c3));
+    *m1 = c1 + u * (2.0 * c2 + u * 3.0 * c3);
+    *m2 = 2.0 * c2 + u * 6.0 * c3;
 }
 
 static int species_index(const uf3o_spec *s, int z) {
@@ -261,6 +351,16 @@ static int trio_index(const uf3o_spec *s, int zc, int za, int zb) {
     return -1;
 }
 
+/* Voigt order (xx, yy, zz, yz, xz, xy) */
+static const int VOIGT[6][2] = {{0, 0}, {1, 1}, {2, 2}, {1, 2}, {0, 2}, {0, 1}};
+
+/* feature rows of one frame: values and, beside a value, its magnitudes (any may be NULL) */
+typedef struct {
+    real *xe, *xf, *xv;       /* [F], [N][3][F], [6][F] */
+    double *me, *mf, *mv;
+    int pieces;               /* the 3-body magnitudes of a route that evaluates leg functions from local pieces: piece_abs */
+} rows_t;
+
 /* ------------------------------------------------------------------ 2-body */
 /*
  * Energy row: sum over real i, supercell j of B_b(d) for the pair block of (Z_i, Z_j),
@@ -269,11 +369,17 @@ static int trio_index(const uf3o_spec *s, int zc, int za, int zb) {
  * supercell pairs with a real end (distances.py:116-141, bspline.py:877-895).  A (ghost x, real y)
  * pair is the periodic image of the (real y', ghost x') pair seen from y, so both delta terms of
  * atom m are collected while visiting m's own neighbours.
+ * Strain rows (no counterpart in the reference; the convention of eval_worker's virial6): the derivative of the energy row,
+ * sum over the same directed pairs of B'_b(d) r_a r_b / d.
+ * Magnitudes: a term B'(d) w with a weight w of degree 0 or 1 in the bond vector (a cosine, r_a r_b / d) has
+ * |t|_abs = |B'|_abs |w| and d |dt/dd|_abs = d |B''|_abs |w| + |B'|_abs |w|.
  * Optional dump: per pair block, (i, j) supercell indices in np.where order.
  */
-static void two_body(const uf3o_spec *s, const supercell_t *sc, const grid_t *g,
-                     double *xe, double *xf, int64_t *pair_cnt, int64_t *pair_ij, int64_t pair_cap) {
+static void two_body(const uf3o_spec *s, const supercell_t *sc, const grid_t *g, const rows_t *o,
+                     int64_t *pair_cnt, int64_t *pair_ij, int64_t pair_cap) {
     int *cand = NULL, cap = 0, N = sc->n_atoms, F = s->n_feat;
+    real *xe = o->xe, *xf = o->xf, *xv = o->xv;
+    int want_m = o->me || o->mf || o->mv;
     const double **knots = (const double **)malloc(sizeof(double *) * (size_t)(s->n_pairs + 1));
     const double *kp = s->pair_knots;
     for (int p = 0; p < s->n_pairs; p++) { knots[p] = kp; kp += s->pair_nk[p]; }
@@ -296,18 +402,32 @@ static void two_body(const uf3o_spec *s, const supercell_t *sc, const grid_t *g,
                 }
                 pair_cnt[p]++;
             }
+            real dr = rdist3(ri, rj);
             int nb = s->pair_nk[p] - 4;
             for (int b = s->lead2; b < nb - s->trail2; b++) {
                 const double *t = knots[p] + b;
-                if (xe) xe[s->pair_col[p] + b] += basis_element(t, d, 0);
-                if (xf && d > t[0] && d < t[4]) {           /* strict support mask, bspline.py:884 */
-                    double dv = basis_element(t, d, 1);
-                    for (int k = 0; k < 3; k++) {
-                        double cosk = (rj[k] - ri[k]) / d;
+                real a1 = 0.0, a2 = 0.0;
+                if (want_m) basis_element_abs(t, d, dr, &a1, &a2);
+                if (xe) {
+                    real val = basis_element(t, d, dr, 0);
+                    xe[s->pair_col[p] + b] += val;
+                    if (o->me) o->me[s->pair_col[p] + b] += (double)(val + dr * a1);
+                }
+                if ((xf || xv) && d > t[0] && d < t[4]) {           /* strict support mask, bspline.py:884 */
+                    real dv = basis_element(t, d, dr, 1);
+                    real gm = 2.0 * a1 + dr * a2;
+                    if (xf) for (int k = 0; k < 3; k++) {
+                        real cosk = ((real)rj[k] - ri[k]) / dr;
                         /* pair (i,j): m=i term  -B'*(-1)*cos ; mirrored pair (j',i): m=i term -B'*(+1)*(-cos) */
-                        double *dst = xf + ((size_t)i * 3 + k) * F + s->pair_col[p] + b;
+                        real *dst = xf + ((size_t)i * 3 + k) * F + s->pair_col[p] + b;
                         *dst += dv * cosk;
                         *dst += dv * cosk;
+                        if (o->mf) o->mf[((size_t)i * 3 + k) * F + s->pair_col[p] + b] += (double)(2.0 * gm * rabs(cosk));
+                    }
+                    if (xv) for (int v = 0; v < 6; v++) {
+                        real da = (real)rj[VOIGT[v][0]] - ri[VOIGT[v][0]], db = (real)rj[VOIGT[v][1]] - ri[VOIGT[v][1]];
+                        xv[(size_t)v * F + s->pair_col[p] + b] += dv * da * db / dr;
+                        if (o->mv) o->mv[(size_t)v * F + s->pair_col[p] + b] += (double)(gm * rabs(da * db) / dr);
                     }
                 }
             }
@@ -384,21 +504,93 @@ static void trio_views(const uf3o_spec *s, trio_view *v, double *rmin3, double *
     *rmax3 = hi;
 }
 
-/* values (and derivatives) of the four candidate bases of leg `d` at r (angles.py:545-566, 607-630) */
-static int leg_values(const trio_view *v, int d, double r, int lead, int trail, double *val, double *der) {
-    int first = searchsorted_left(v->k[d], v->nk[d], r) - 4;
+/* the four candidate bases of one leg at r: values, derivatives and, for the magnitudes, |B'|_abs and |B''|_abs */
+typedef struct { real v[4], d[4], a1[4], a2[4], m0[4], m1[4], m2[4]; } leg_t;   /* m: v, a1, a2, or widened (piece_abs) */
+
+/* values (and derivatives) of the four candidate bases of leg `d` at r (angles.py:545-566, 607-630); rd: the fp64 distance;
+   mag: 0 no magnitudes, 1 Cox-de Boor's (m0 = the value), 2 widened to those of the local piece */
+static int leg_values(const trio_view *v, int d, double rd, real r, int lead, int trail, leg_t *g, int der, int mag) {
+    int first = searchsorted_left(v->k[d], v->nk[d], rd) - 4;
     for (int a = 0; a < 4; a++) {
         int b = first + a;
-        val[a] = 0.0; if (der) der[a] = 0.0;
+        g->v[a] = 0.0; g->d[a] = 0.0; g->a1[a] = 0.0; g->a2[a] = 0.0; g->m0[a] = 0.0; g->m1[a] = 0.0; g->m2[a] = 0.0;
         if (b < lead || b >= v->dim[d] - trail) continue;   /* trimmed, or wrapped negative index */
-        val[a] = basis_element(v->k[d] + b, r, 0);
-        if (der) der[a] = basis_element(v->k[d] + b, r, 1);
+        g->v[a] = basis_element(v->k[d] + b, rd, r, 0);
+        if (der) g->d[a] = basis_element(v->k[d] + b, rd, r, 1);
+        if (mag) {
+            basis_element_abs(v->k[d] + b, rd, r, &g->a1[a], &g->a2[a]);
+            g->m0[a] = g->v[a]; g->m1[a] = g->a1[a]; g->m2[a] = g->a2[a];
+        }
+        if (mag == 2) {
+            real p0, p1, p2;
+            piece_abs(v->k[d] + b, rd, r, &p0, &p1, &p2);
+            if (p0 > g->m0[a]) g->m0[a] = p0;
+            if (p1 > g->m1[a]) g->m1[a] = p1;
+            if (p2 > g->m2[a]) g->m2[a] = p2;
+        }
     }
     return first;
 }
 
+/*
+ * Magnitudes of one product of three leg functions, times |c|: q[0] the value, q[1..3] the three first partials, q[4..9] the
+ * second partials 00, 01, 02, 11, 12, 22 -- each with |B'|_abs, |B''|_abs in place of B', B''.
+ */
+/* magnitude of a product of three factors of magnitudes a, b, c whose error magnitudes are ma >= a, mb >= b, mc >= c: to first
+   order one factor's excess at a time (a b c itself where nothing is widened) */
+static real wprod(real a, real ma, real b, real mb, real c, real mc) {
+    return a * b * c + (ma - a) * b * c + a * (mb - b) * c + a * b * (mc - c);
+}
+static void q_add(real *q, real c, const leg_t *l, const leg_t *m, const leg_t *n, int x, int y, int w) {
+#define F0(g, i) g->v[i], g->m0[i]
+#define F1(g, i) g->a1[i], g->m1[i]
+#define F2(g, i) g->a2[i], g->m2[i]
+    q[0] += c * wprod(F0(l, x), F0(m, y), F0(n, w));
+    q[1] += c * wprod(F1(l, x), F0(m, y), F0(n, w));
+    q[2] += c * wprod(F0(l, x), F1(m, y), F0(n, w));
+    q[3] += c * wprod(F0(l, x), F0(m, y), F1(n, w));
+    q[4] += c * wprod(F2(l, x), F0(m, y), F0(n, w));
+    q[5] += c * wprod(F1(l, x), F1(m, y), F0(n, w));
+    q[6] += c * wprod(F1(l, x), F0(m, y), F1(n, w));
+    q[7] += c * wprod(F0(l, x), F2(m, y), F0(n, w));
+    q[8] += c * wprod(F0(l, x), F1(m, y), F1(n, w));
+    q[9] += c * wprod(F0(l, x), F0(m, y), F2(n, w));
+#undef F0
+#undef F1
+#undef F2
+}
+/* M of an energy term V(r_ij, r_ik, r_jk): |V|_abs + sum_legs rho_leg |dV/dr_leg|_abs, rho = (r_ij, r_ik, r_ij + r_ik) */
+static real mag_value(const real *q, const real *r) {
+    return q[0] + r[0] * q[1] + r[1] * q[2] + (r[0] + r[1]) * q[3];
+}
+/*
+ * M of a gradient term g_0 w_0 + g_1 w_1 + g_2 w_2 (g_l = dV/dr_l; w_l a direction cosine of leg l, or r_a r_b / r of leg l:
+ * of degree 0 or 1 in the leg's vector, so that r_l |dw_l/dr_l| = |w_l|): the three products with absolute values, and per leg
+ * rho_l times ( sum_l' |d2V/dr_l dr_l'|_abs |w_l'| + |g_l|_abs |w_l| / r_l ).  wa: |w|.
+ */
+static real mag_grad(const real *q, const real *wa, const real *r) {
+    real rho[3] = {r[0], r[1], r[0] + r[1]};
+    return q[1] * wa[0] + q[2] * wa[1] + q[3] * wa[2]
+         + rho[0] * (wa[0] * (q[4] + q[1] / r[0]) + wa[1] * q[5] + wa[2] * q[6])
+         + rho[1] * (wa[0] * q[5] + wa[1] * (q[7] + q[2] / r[1]) + wa[2] * q[8])
+         + rho[2] * (wa[0] * q[6] + wa[1] * q[8] + wa[2] * (q[9] + q[3] / r[2]));
+}
+
 /* fold the symmetry images, keep template bins, weight (bspline.py:664-690), accumulate into out */
-static void compress_add(const uf3o_spec *s, const trio_view *v, int t, const double *grid, double *out, double sign) {
+static void compress_add(const uf3o_spec *s, const trio_view *v, int t, const real *grid, real *out, real sign) {
+    int M = v->dim[1], N = v->dim[2], sym = s->trio_sym[t];
+    for (int c = 0; c < s->trio_ncol[t]; c++) {
+        int64_t u = v->mask[c];
+        int l = (int)(u / ((int64_t)M * N)), m = (int)((u / N) % M), n = (int)(u % N);
+        int64_t img[6];
+        int ni = sym_images(sym, l, m, n, M, N, img);
+        real val = 0.0;
+        for (int q = 0; q < ni; q++) val += grid[img[q]];
+        out[s->trio_col[t] + c] += sign * val * v->w[c];
+    }
+}
+/* the same fold of a grid of magnitudes, with |weight| */
+static void compress_add_abs(const uf3o_spec *s, const trio_view *v, int t, const double *grid, double *out) {
     int M = v->dim[1], N = v->dim[2], sym = s->trio_sym[t];
     for (int c = 0; c < s->trio_ncol[t]; c++) {
         int64_t u = v->mask[c];
@@ -407,7 +599,7 @@ static void compress_add(const uf3o_spec *s, const trio_view *v, int t, const do
         int ni = sym_images(sym, l, m, n, M, N, img);
         double val = 0.0;
         for (int q = 0; q < ni; q++) val += grid[img[q]];
-        out[s->trio_col[t] + c] += sign * val * v->w[c];
+        out[s->trio_col[t] + c] += val * fabs(v->w[c]);
     }
 }
 
@@ -419,24 +611,34 @@ static int wrap_idx(int i, int n) { return i < 0 ? i + n : i; }  /* numpy negati
  * centre keeps only triplets whose first-listed neighbour is real (angles.py:451-460).
  * Neighbour pairs: r_min3 < d <= r_max3.  j<k by supercell index, then the two neighbours are put in
  * ascending-Z order (stable), interaction = (Z_i; Z_j, Z_k); legs masked t[0] <= r <= t[-1].
+ * Strain rows: real centres, the three legs of the centre's own triplet (as eval_worker's virial6).
  */
-static void three_body(const uf3o_spec *s, const supercell_t *sc, const grid_t *g,
-                       double *xe, double *xf, int64_t *n3_cnt, int64_t *n3_ij, int64_t n3_cap) {
+static void three_body(const uf3o_spec *s, const supercell_t *sc, const grid_t *g, const rows_t *o,
+                       int64_t *n3_cnt, int64_t *n3_ij, int64_t n3_cap) {
     int T = s->n_trios, N = sc->n_atoms, F = s->n_feat;
+    real *xe = o->xe, *xf = o->xf, *xv = o->xv;
     trio_view *v = (trio_view *)malloc(sizeof(trio_view) * (size_t)T);
     double rmin3, rmax3;
     trio_views(s, v, &rmin3, &rmax3);
-    double **egrid = (double **)malloc(sizeof(double *) * (size_t)T);
-    for (int t = 0; t < T; t++) egrid[t] = (double *)calloc((size_t)v[t].dim[0] * v[t].dim[1] * v[t].dim[2], sizeof(double));
+    real **egrid = (real **)malloc(sizeof(real *) * (size_t)T), **vgrid = (real **)calloc((size_t)T, sizeof(real *));
+    double **megrid = (double **)calloc((size_t)T, sizeof(double *)), **mvgrid = (double **)calloc((size_t)T, sizeof(double *));
+    for (int t = 0; t < T; t++) {
+        size_t sz = (size_t)v[t].dim[0] * v[t].dim[1] * v[t].dim[2];
+        egrid[t] = (real *)calloc(sz, sizeof(real));
+        if (xv) vgrid[t] = (real *)calloc(6 * sz, sizeof(real));
+        if (xe && o->me) megrid[t] = (double *)calloc(sz, sizeof(double));
+        if (xv && o->mv) mvgrid[t] = (double *)calloc(6 * sz, sizeof(double));
+    }
     int *cand = NULL, cap = 0, *nbr = NULL, nbr_cap = 0;
     double *nbr_d = NULL;
     int64_t cnt = 0;
+    int want_m = ((xe && o->me) || (xf && o->mf) || (xv && o->mv)) ? (o->pieces ? 2 : 1) : 0;
 
     int n_centres = xf ? sc->m : N;
     for (int pass = 0; pass < (xf ? 2 : 1); pass++) {
-        /* pass 0: energy over real centres; pass 1: forces over all centres */
+        /* pass 0: energy (and strain rows) over real centres; pass 1: forces over all centres */
         int nc_max = pass == 0 ? N : n_centres;
-        if (pass == 0 && !xe && !n3_cnt) continue;
+        if (pass == 0 && !xe && !xv && !n3_cnt) continue;
         for (int i = 0; i < nc_max; i++) {
             const double *ri = sc->pos + 3 * (size_t)i;
             int nc = gather_candidates(sc, g, ri, &cand, &cap), nn = 0;
@@ -455,7 +657,7 @@ static void three_body(const uf3o_spec *s, const supercell_t *sc, const grid_t *
                     }
                 }
             }
-            if (pass == 0 && !xe) continue;
+            if (pass == 0 && !xe && !xv) continue;
             int ghost = i >= N;
             for (int a = 0; a < nn; a++) {
                 for (int b = 0; b < nn; b++) {
@@ -475,16 +677,38 @@ static void three_body(const uf3o_spec *s, const supercell_t *sc, const grid_t *
                     if (!(rij >= tv->k[0][0] && rij <= tv->k[0][tv->nk[0] - 1])) continue;
                     if (!(rik >= tv->k[1][0] && rik <= tv->k[1][tv->nk[1] - 1])) continue;
                     if (!(rjk >= tv->k[2][0] && rjk <= tv->k[2][tv->nk[2] - 1])) continue;
-                    double vl[4], vm[4], vn[4], dl[4], dm[4], dn[4];
+                    real r[3] = {rdist3(ri, rj), rdist3(ri, rk), rdist3(rj, rk)};
+                    leg_t gl, gm, gn;
                     int L = tv->dim[0], M = tv->dim[1], Nn = tv->dim[2];
-                    int il = leg_values(tv, 0, rij, s->lead3, s->trail3, vl, pass ? dl : NULL);
-                    int im = leg_values(tv, 1, rik, s->lead3, s->trail3, vm, pass ? dm : NULL);
-                    int in = leg_values(tv, 2, rjk, s->lead3, s->trail3, vn, pass ? dn : NULL);
+                    int der = pass || xv;
+                    int il = leg_values(tv, 0, rij, r[0], s->lead3, s->trail3, &gl, der, want_m);
+                    int im = leg_values(tv, 1, rik, r[1], s->lead3, s->trail3, &gm, der, want_m);
+                    int in = leg_values(tv, 2, rjk, r[2], s->lead3, s->trail3, &gn, der, want_m);
+                    const real *vl = gl.v, *vm = gm.v, *vn = gn.v, *dl = gl.d, *dm = gm.d, *dn = gn.d;
+                    size_t sz = (size_t)L * M * Nn;
                     if (pass == 0) {
                         for (int x = 0; x < 4; x++) for (int y = 0; y < 4; y++) for (int w = 0; w < 4; w++) {
-                            double val = vl[x] * vm[y] * vn[w];
-                            if (val == 0.0) continue;
-                            egrid[t][((size_t)wrap_idx(il + x, L) * M + wrap_idx(im + y, M)) * Nn + wrap_idx(in + w, Nn)] += val;
+                            size_t u = ((size_t)wrap_idx(il + x, L) * M + wrap_idx(im + y, M)) * Nn + wrap_idx(in + w, Nn);
+                            real q[10] = {0};
+                            if (want_m) q_add(q, 1.0, &gl, &gm, &gn, x, y, w);
+                            if (xe) {
+                                real val = vl[x] * vm[y] * vn[w];
+                                if (val != 0.0) {
+                                    egrid[t][u] += val;
+                                    if (megrid[t]) megrid[t][u] += (double)mag_value(q, r);
+                                }
+                            }
+                            if (xv) for (int e = 0; e < 6; e++) {
+                                int ca = VOIGT[e][0], cb = VOIGT[e][1];
+                                real wij = ((real)rj[ca] - ri[ca]) * ((real)rj[cb] - ri[cb]) / r[0];
+                                real wik = ((real)rk[ca] - ri[ca]) * ((real)rk[cb] - ri[cb]) / r[1];
+                                real wjk = ((real)rk[ca] - rj[ca]) * ((real)rk[cb] - rj[cb]) / r[2];
+                                vgrid[t][e * sz + u] += dl[x] * vm[y] * vn[w] * wij + vl[x] * dm[y] * vn[w] * wik + vl[x] * vm[y] * dn[w] * wjk;
+                                if (mvgrid[t]) {
+                                    real wa[3] = {rabs(wij), rabs(wik), rabs(wjk)};
+                                    mvgrid[t][e * sz + u] += (double)mag_grad(q, wa, r);
+                                }
+                            }
                         }
                     } else {
                         /* direction cosines restricted to real atoms (distances.py:354-363) */
@@ -495,19 +719,25 @@ static void three_body(const uf3o_spec *s, const supercell_t *sc, const grid_t *
                             /* an atom may appear once only in a triplet, but two of i,j,k can be images
                                of one real atom only as distinct supercell indices, so m matches one slot */
                             for (int c3 = 0; c3 < 3; c3++) {
-                                double dij = ((m == j) - (m == i)) * (rj[c3] - ri[c3]) / rij;
-                                double dik = ((m == k) - (m == i)) * (rk[c3] - ri[c3]) / rik;
-                                double djk = ((m == k) - (m == j)) * (rk[c3] - rj[c3]) / rjk;
+                                real dij = ((m == j) - (m == i)) * ((real)rj[c3] - ri[c3]) / r[0];
+                                real dik = ((m == k) - (m == i)) * ((real)rk[c3] - ri[c3]) / r[1];
+                                real djk = ((m == k) - (m == j)) * ((real)rk[c3] - rj[c3]) / r[2];
                                 if (dij == 0 && dik == 0 && djk == 0) continue;
+                                real wa[3] = {rabs(dij), rabs(dik), rabs(djk)};
                                 /* force_grid[m][c] -= val, then compress_3B: a raw bin u reaches every
                                    column whose symmetry images contain u, times that column's weight */
-                                double *row = xf + ((size_t)m * 3 + c3) * F + s->trio_col[t];
+                                real *row = xf + ((size_t)m * 3 + c3) * F + s->trio_col[t];
+                                double *mrow = o->mf ? o->mf + ((size_t)m * 3 + c3) * F + s->trio_col[t] : NULL;
                                 for (int x = 0; x < 4; x++) for (int y = 0; y < 4; y++) for (int w = 0; w < 4; w++) {
-                                    double val = dl[x] * vm[y] * vn[w] * dij + vl[x] * dm[y] * vn[w] * dik + vl[x] * vm[y] * dn[w] * djk;
+                                    real val = dl[x] * vm[y] * vn[w] * dij + vl[x] * dm[y] * vn[w] * dik + vl[x] * vm[y] * dn[w] * djk;
                                     if (val == 0.0) continue;
                                     size_t u = ((size_t)wrap_idx(il + x, L) * M + wrap_idx(im + y, M)) * Nn + wrap_idx(in + w, Nn);
-                                    for (int e = tv->inv_start[u]; e < tv->inv_start[u + 1]; e++)
+                                    double mag = 0.0;
+                                    if (mrow) { real q[10] = {0}; q_add(q, 1.0, &gl, &gm, &gn, x, y, w); mag = (double)mag_grad(q, wa, r); }
+                                    for (int e = tv->inv_start[u]; e < tv->inv_start[u + 1]; e++) {
                                         row[tv->inv_col[e]] -= val * tv->w[tv->inv_col[e]];
+                                        if (mrow) mrow[tv->inv_col[e]] += mag * fabs(tv->w[tv->inv_col[e]]);
+                                    }
                                 }
                             }
                         }
@@ -516,25 +746,24 @@ static void three_body(const uf3o_spec *s, const supercell_t *sc, const grid_t *
             }
         }
     }
-    if (xe) for (int t = 0; t < T; t++) compress_add(s, v + t, t, egrid[t], xe, 1.0);
+    for (int t = 0; t < T; t++) {
+        size_t sz = (size_t)v[t].dim[0] * v[t].dim[1] * v[t].dim[2];
+        if (xe) compress_add(s, v + t, t, egrid[t], xe, 1.0);
+        if (megrid[t]) compress_add_abs(s, v + t, t, megrid[t], o->me);
+        for (int e = 0; e < 6; e++) {
+            if (xv) compress_add(s, v + t, t, vgrid[t] + e * sz, xv + (size_t)e * F, 1.0);
+            if (mvgrid[t]) compress_add_abs(s, v + t, t, mvgrid[t] + e * sz, o->mv + (size_t)e * F);
+        }
+    }
     if (n3_cnt) *n3_cnt = cnt;
-    for (int t = 0; t < T; t++) free(egrid[t]);
-    free(egrid); free(cand); free(nbr); free(nbr_d); free_trio_views(s, v);
+    for (int t = 0; t < T; t++) { free(egrid[t]); free(vgrid[t]); free(megrid[t]); free(mvgrid[t]); }
+    free(egrid); free(vgrid); free(megrid); free(mvgrid); free(cand); free(nbr); free(nbr_d); free_trio_views(s, v);
 }
 
 /* ------------------------------------------------------------------- entry */
-/*
- * Feature rows of one frame (process.py:293-367 without the y column):
- *   xe [F]        1-body counts | 2-body | 3-body         (NULL to skip)
- *   xf [N][3][F]  1-body zeros  | 2-body | 3-body         (NULL to skip)
- * Index dumps (any may be NULL):
- *   pair_cnt [P], pair_ij [P][pair_cap][2]   2-body (i, j) per pair block
- *   n3_cnt [1],  n3_ij [n3_cap][2]           identify_ij(square=False) pairs
- *   sc_info [8]: n_img, m, fac[3], cnt[3]
- */
-int uf3o_featurize(const uf3o_spec *s, const uf3o_frame *f, double *xe, double *xf,
-                   int64_t *pair_cnt, int64_t *pair_ij, int64_t pair_cap,
-                   int64_t *n3_cnt, int64_t *n3_ij, int64_t n3_cap, int64_t *sc_info) {
+static int featurize_worker(const uf3o_spec *s, const uf3o_frame *f, const rows_t *o,
+                            int64_t *pair_cnt, int64_t *pair_ij, int64_t pair_cap,
+                            int64_t *n3_cnt, int64_t *n3_ij, int64_t n3_cap, int64_t *sc_info) {
     supercell_t sc;
     grid_t g;
     for (int a = 0; a < f->n_atoms; a++) if (species_index(s, f->z[a]) < 0) return 2;
@@ -548,14 +777,21 @@ int uf3o_featurize(const uf3o_spec *s, const uf3o_frame *f, double *xe, double *
         if (rmax3 > h) h = rmax3;
     }
     build_grid(&sc, h * (1.0 + 1e-9) + 1e-9, &g);
-    size_t F = (size_t)s->n_feat;
-    if (xe) {
-        memset(xe, 0, sizeof(double) * F);
-        for (int a = 0; a < f->n_atoms; a++) xe[species_index(s, f->z[a])] += 1.0;
+    size_t F = (size_t)s->n_feat, NF = F * 3 * (size_t)f->n_atoms;
+    if (o->xe) {
+        for (size_t q = 0; q < F; q++) o->xe[q] = 0.0;
+        if (o->me) memset(o->me, 0, sizeof(double) * F);
+        for (int a = 0; a < f->n_atoms; a++) {
+            o->xe[species_index(s, f->z[a])] += 1.0;
+            if (o->me) o->me[species_index(s, f->z[a])] += 1.0;
+        }
     }
-    if (xf) memset(xf, 0, sizeof(double) * F * 3 * (size_t)f->n_atoms);
-    two_body(s, &sc, &g, xe, xf, pair_cnt, pair_ij, pair_cap);
-    if (s->n_trios > 0) three_body(s, &sc, &g, xe, xf, n3_cnt, n3_ij, n3_cap);
+    if (o->xf) for (size_t q = 0; q < NF; q++) o->xf[q] = 0.0;
+    if (o->xf && o->mf) memset(o->mf, 0, sizeof(double) * NF);
+    if (o->xv) for (size_t q = 0; q < 6 * F; q++) o->xv[q] = 0.0;
+    if (o->xv && o->mv) memset(o->mv, 0, sizeof(double) * 6 * F);
+    two_body(s, &sc, &g, o, pair_cnt, pair_ij, pair_cap);
+    if (s->n_trios > 0) three_body(s, &sc, &g, o, n3_cnt, n3_ij, n3_cap);
     else if (n3_cnt) *n3_cnt = 0;
     if (sc_info) {
         sc_info[0] = sc.n_img; sc_info[1] = sc.m;
@@ -563,6 +799,35 @@ int uf3o_featurize(const uf3o_spec *s, const uf3o_frame *f, double *xe, double *
     }
     free_grid(&g); free_supercell(&sc);
     return 0;
+}
+
+/*
+ * Feature rows of one frame (process.py:293-367 without the y column):
+ *   xe [F]        1-body counts | 2-body | 3-body         (NULL to skip)
+ *   xf [N][3][F]  1-body zeros  | 2-body | 3-body         (NULL to skip)
+ * Index dumps (any may be NULL):
+ *   pair_cnt [P], pair_ij [P][pair_cap][2]   2-body (i, j) per pair block
+ *   n3_cnt [1],  n3_ij [n3_cap][2]           identify_ij(square=False) pairs
+ *   sc_info [8]: n_img, m, fac[3], cnt[3]
+ * (Rows are arrays of `real`: double in libuf3oracle.so.)
+ */
+int uf3o_featurize(const uf3o_spec *s, const uf3o_frame *f, real *xe, real *xf,
+                   int64_t *pair_cnt, int64_t *pair_ij, int64_t pair_cap,
+                   int64_t *n3_cnt, int64_t *n3_ij, int64_t n3_cap, int64_t *sc_info) {
+    rows_t o = {xe, xf, NULL, NULL, NULL, NULL, 0};
+    return featurize_worker(s, f, &o, pair_cnt, pair_ij, pair_cap, n3_cnt, n3_ij, n3_cap, sc_info);
+}
+
+/*
+ * The rows with the strain rows xv [6][F] (Voigt; d(energy row)/d(strain), the convention of uf3o_eval_virial) and the
+ * magnitudes me [F], mf [N][3][F], mv [6][F] (doubles; NULL to skip, each only beside its row); pair_cnt [P] and n3_cnt [1] as
+ * above, to show that both builds sum the same terms.  pieces != 0: the magnitudes of the 3-body columns for a route that
+ * evaluates leg functions from local cubic pieces (piece_abs); the values do not depend on it.
+ */
+int uf3o_featurize_x(const uf3o_spec *s, const uf3o_frame *f, real *xe, real *xf, real *xv,
+                     double *me, double *mf, double *mv, int pieces, int64_t *pair_cnt, int64_t *n3_cnt) {
+    rows_t o = {xe, xf, xv, me, mf, mv, pieces};
+    return featurize_worker(s, f, &o, pair_cnt, NULL, 0, n3_cnt, NULL, 0, NULL);
 }
 
 /* supercell positions / species in reference order; returns m (call with out=NULL to size) */
@@ -578,32 +843,35 @@ int64_t uf3o_supercell(const uf3o_frame *f, double r_cut, double *pos_out, int *
 }
 
 /* ------------------------------------------------------------- evaluator */
-/* tensor-product cubic spline value / first partials from a full coefficient grid */
-static void spline3(const trio_view *tv, const double *c, double rl, double rm, double rn, double *val, double *grad) {
-    double vl[4], vm[4], vn[4], dl[4], dm[4], dn[4];
+/* tensor-product cubic spline value / first partials from a full coefficient grid; q (may be NULL): the magnitudes of q_add,
+   summed over the 64 products with |coefficient| */
+static void spline3(const trio_view *tv, const double *c, const double *rd, const real *r, real *val, real *grad, real *q) {
+    leg_t gl, gm, gn;
     int L = tv->dim[0], M = tv->dim[1], N = tv->dim[2];
-    int il = leg_values(tv, 0, rl, 0, 0, vl, dl), im = leg_values(tv, 1, rm, 0, 0, vm, dm), in = leg_values(tv, 2, rn, 0, 0, vn, dn);
-    double v = 0, g0 = 0, g1 = 0, g2 = 0;
+    int il = leg_values(tv, 0, rd[0], r[0], 0, 0, &gl, 1, q != NULL), im = leg_values(tv, 1, rd[1], r[1], 0, 0, &gm, 1, q != NULL),
+        in = leg_values(tv, 2, rd[2], r[2], 0, 0, &gn, 1, q != NULL);
+    const real *vl = gl.v, *vm = gm.v, *vn = gn.v, *dl = gl.d, *dm = gm.d, *dn = gn.d;
+    real v = 0, g0 = 0, g1 = 0, g2 = 0;
+    if (q) for (int x = 0; x < 10; x++) q[x] = 0.0;
     for (int x = 0; x < 4; x++) for (int y = 0; y < 4; y++) for (int w = 0; w < 4; w++) {
         int a = il + x, b = im + y, d = in + w;
         if (a < 0 || b < 0 || d < 0 || a >= L || b >= M || d >= N) continue;
-        double cc = c[((size_t)a * M + b) * N + d];
+        real cc = c[((size_t)a * M + b) * N + d];
         v += cc * vl[x] * vm[y] * vn[w];
         g0 += cc * dl[x] * vm[y] * vn[w];
         g1 += cc * vl[x] * dm[y] * vn[w];
         g2 += cc * vl[x] * vm[y] * dn[w];
+        if (q) q_add(q, rabs(cc), &gl, &gm, &gn, x, y, w);
     }
     *val = v; grad[0] = g0; grad[1] = g1; grad[2] = g2;
 }
 
-/* Voigt order (xx, yy, zz, yz, xz, xy) */
-static const int VOIGT[6][2] = {{0, 0}, {1, 1}, {2, 2}, {1, 2}, {0, 2}, {0, 1}};
-
-/* virial6 += g * r (x) r / |r| for one energy term g(|r|) of the bond vector r (Voigt) */
-static void strain_add(double *virial6, double g, const double *ra, const double *rb, double r) {
+/* virial6 += g * r (x) r / |r| for one energy term g(|r|) of the bond vector r (Voigt); m6 (may be NULL) += gm |r_a r_b| / |r| */
+static void strain_add(real *virial6, double *m6, real g, real gm, const double *ra, const double *rb, real r) {
     for (int v = 0; v < 6; v++) {
         int a = VOIGT[v][0], b = VOIGT[v][1];
-        virial6[v] += g * (rb[a] - ra[a]) * (rb[b] - ra[b]) / r;
+        virial6[v] += g * ((real)rb[a] - ra[a]) * ((real)rb[b] - ra[b]) / r;
+        if (m6) m6[v] += (double)(gm * rabs(((real)rb[a] - ra[a]) * ((real)rb[b] - ra[b])) / r);
     }
 }
 
@@ -615,9 +883,10 @@ static void strain_add(double *virial6, double g, const double *ra, const double
  * construction of the reference's numerical stress (calculator.py:399-404) -- from the energy terms alone: every term
  * V(r_1 .. r_k) of the sum over real i and supercell j (pairs) or real centres (trios) contributes
  * sum_legs dV/dr_l r_l,a r_l,b / r_l, with r_l the leg's image vector.
+ * me [1], mf [N][3], mv [6] (may be NULL, each only beside its value): the magnitudes.
  */
 static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
-                       double *energy, double *forces, double *virial6) {
+                       real *energy, real *forces, real *virial6, double *me, double *mf, double *mv) {
     supercell_t sc;
     grid_t g;
     for (int a = 0; a < f->n_atoms; a++) if (species_index(s, f->z[a]) < 0) return 2;
@@ -628,10 +897,16 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
     for (int p = 0; p < s->n_pairs; p++) if (s->pair_rmax[p] > h) h = s->pair_rmax[p];
     if (T) { trio_views(s, v, &rmin3, &rmax3); if (rmax3 > h) h = rmax3; }
     build_grid(&sc, h * (1.0 + 1e-9) + 1e-9, &g);
-    double e = 0.0;
-    if (forces) memset(forces, 0, sizeof(double) * 3 * (size_t)N);
-    if (virial6) memset(virial6, 0, sizeof(double) * 6);
-    for (int a = 0; a < N; a++) e += c1[species_index(s, f->z[a])];
+    real e = 0.0;
+    double em = 0.0;
+    if (!forces) mf = NULL;
+    if (!virial6) mv = NULL;
+    int want_m = me || mf || mv;
+    if (forces) for (int q = 0; q < 3 * N; q++) forces[q] = 0.0;
+    if (virial6) for (int q = 0; q < 6; q++) virial6[q] = 0.0;
+    if (mf) memset(mf, 0, sizeof(double) * 3 * (size_t)N);
+    if (mv) memset(mv, 0, sizeof(double) * 6);
+    for (int a = 0; a < N; a++) { e += c1[species_index(s, f->z[a])]; em += fabs(c1[species_index(s, f->z[a])]); }
     /* pair part */
     const double **pk = (const double **)malloc(sizeof(double *) * (size_t)(s->n_pairs + 1));
     const double **pc = (const double **)malloc(sizeof(double *) * (size_t)(s->n_pairs + 1));
@@ -647,17 +922,28 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
             const double *rj = sc.pos + 3 * (size_t)j;
             double d = dist3(ri, rj), rmin = s->pair_rmin[p] > 0 ? s->pair_rmin[p] : 0.0;
             if (!(d > rmin && d < s->pair_rmax[p])) continue;
+            real dr = rdist3(ri, rj);
             int nb = s->pair_nk[p] - 4, first = searchsorted_left(pk[p], s->pair_nk[p], d) - 4;
-            double phi = 0, dphi = 0;
+            real phi = 0, dphi = 0, pa = 0, ga = 0, ha = 0;
             for (int a = 0; a < 4; a++) {
                 int b = first + a;
                 if (b < 0 || b >= nb) continue;
-                phi += pc[p][b] * basis_element(pk[p] + b, d, 0);
-                dphi += pc[p][b] * basis_element(pk[p] + b, d, 1);
+                phi += pc[p][b] * basis_element(pk[p] + b, d, dr, 0);
+                dphi += pc[p][b] * basis_element(pk[p] + b, d, dr, 1);
+                if (want_m) {
+                    real a1, a2, ca = fabs(pc[p][b]);
+                    basis_element_abs(pk[p] + b, d, dr, &a1, &a2);
+                    pa += ca * basis_element(pk[p] + b, d, dr, 0); ga += ca * a1; ha += ca * a2;
+                }
             }
             e += phi;
-            if (forces) for (int k = 0; k < 3; k++) forces[3 * i + k] += 2.0 * dphi * (rj[k] - ri[k]) / d;
-            if (virial6) strain_add(virial6, dphi, ri, rj, d);
+            em += (double)(pa + dr * ga);
+            real gm = 2.0 * ga + dr * ha;       /* |dphi|_abs + d |d(dphi w)/dd|_abs over |w|, as in two_body */
+            if (forces) for (int k = 0; k < 3; k++) {
+                forces[3 * i + k] += 2.0 * dphi * ((real)rj[k] - ri[k]) / dr;
+                if (mf) mf[3 * i + k] += (double)(2.0 * gm * rabs((real)rj[k] - ri[k]) / dr);
+            }
+            if (virial6) strain_add(virial6, mv, dphi, gm, ri, rj, dr);
         }
     }
     /* trio part: real centres for the energy, all centres (ghost: real j) for the forces */
@@ -692,13 +978,22 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
                 if (!(rij >= tv->k[0][0] && rij <= tv->k[0][tv->nk[0] - 1])) continue;
                 if (!(rik >= tv->k[1][0] && rik <= tv->k[1][tv->nk[1] - 1])) continue;
                 if (!(rjk >= tv->k[2][0] && rjk <= tv->k[2][tv->nk[2] - 1])) continue;
-                double val, gr[3];
-                spline3(tv, tc[t], rij, rik, rjk, &val, gr);
-                if (!ghost) e += val;
+                double rd[3] = {rij, rik, rjk};
+                real r[3] = {rdist3(ri, rj), rdist3(ri, rk), rdist3(rj, rk)};
+                real val, gr[3], q[10];
+                spline3(tv, tc[t], rd, r, &val, gr, want_m ? q : NULL);
+                if (!ghost) { e += val; if (want_m) em += (double)mag_value(q, r); }
                 if (virial6 && !ghost) {          /* legs ij, ik, jk of the centre's own triplet */
-                    strain_add(virial6, gr[0], ri, rj, rij);
-                    strain_add(virial6, gr[1], ri, rk, rik);
-                    strain_add(virial6, gr[2], rj, rk, rjk);
+                    strain_add(virial6, NULL, gr[0], 0.0, ri, rj, r[0]);
+                    strain_add(virial6, NULL, gr[1], 0.0, ri, rk, r[1]);
+                    strain_add(virial6, NULL, gr[2], 0.0, rj, rk, r[2]);
+                    if (mv) for (int e6 = 0; e6 < 6; e6++) {
+                        int ca = VOIGT[e6][0], cb = VOIGT[e6][1];
+                        real wa[3] = {rabs(((real)rj[ca] - ri[ca]) * ((real)rj[cb] - ri[cb])) / r[0],
+                                      rabs(((real)rk[ca] - ri[ca]) * ((real)rk[cb] - ri[cb])) / r[1],
+                                      rabs(((real)rk[ca] - rj[ca]) * ((real)rk[cb] - rj[cb])) / r[2]};
+                        mv[e6] += (double)mag_grad(q, wa, r);
+                    }
                 }
                 if (forces) {
                     int idx[3] = {i, j, k};
@@ -706,10 +1001,11 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
                         int m = idx[who];
                         if (m >= N) continue;
                         for (int c3 = 0; c3 < 3; c3++) {
-                            double dij = ((m == j) - (m == i)) * (rj[c3] - ri[c3]) / rij;
-                            double dik = ((m == k) - (m == i)) * (rk[c3] - ri[c3]) / rik;
-                            double djk = ((m == k) - (m == j)) * (rk[c3] - rj[c3]) / rjk;
+                            real dij = ((m == j) - (m == i)) * ((real)rj[c3] - ri[c3]) / r[0];
+                            real dik = ((m == k) - (m == i)) * ((real)rk[c3] - ri[c3]) / r[1];
+                            real djk = ((m == k) - (m == j)) * ((real)rk[c3] - rj[c3]) / r[2];
                             forces[3 * m + c3] -= dij * gr[0] + dik * gr[1] + djk * gr[2];
+                            if (mf) { real wa[3] = {rabs(dij), rabs(dik), rabs(djk)}; mf[3 * m + c3] += (double)mag_grad(q, wa, r); }
                         }
                     }
                 }
@@ -718,18 +1014,27 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
         free(nbr); free(nbr_d); free((void *)tc);
     }
     if (energy) *energy = e;
+    if (me) *me = em;
     free(cand); free((void *)pk); free((void *)pc); if (v) free_trio_views(s, v);
     free_grid(&g); free_supercell(&sc);
     return 0;
 }
 
+/* (energy, forces, virial6 are `real`: double in libuf3oracle.so) */
 int uf3o_eval(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
-              double *energy, double *forces) {
-    return eval_worker(s, f, c1, c2, c3, energy, forces, NULL);
+              real *energy, real *forces) {
+    return eval_worker(s, f, c1, c2, c3, energy, forces, NULL, NULL, NULL, NULL);
 }
 
 /* uf3o_eval plus the strain derivative virial6 [6] (eV, Voigt xx, yy, zz, yz, xz, xy; stress = virial6 / volume) */
 int uf3o_eval_virial(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
-                     double *energy, double *forces, double *virial6) {
-    return eval_worker(s, f, c1, c2, c3, energy, forces, virial6);
+                     real *energy, real *forces, real *virial6) {
+    return eval_worker(s, f, c1, c2, c3, energy, forces, virial6, NULL, NULL, NULL);
 }
+
+/* uf3o_eval_virial plus the magnitudes me [1], mf [N][3], mv [6] */
+int uf3o_eval_x(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
+                real *energy, real *forces, real *virial6, double *me, double *mf, double *mv) {
+    return eval_worker(s, f, c1, c2, c3, energy, forces, virial6, me, mf, mv);
+}
+

@@ -1,0 +1,228 @@
+"""
+The extended-precision harness: feature rows, energies, forces and strain derivatives against the oracle's extended build
+(``oracle/libuf3oracle_x.so``: the oracle's own source with ``long double`` values and fp64 decisions), entry by entry, in units
+of the entry's own first-order error bound.
+
+``ratio(got, truth, M)`` is ``max |got - truth| / (u M)`` with ``u = 2**-53`` and M the magnitude the extended oracle returns
+beside every entry (uf3_oracle.c: the sum over the entry's terms of the term with absolute values taken wherever it takes signs,
+plus its sensitivity to a relative rounding of each of its distances).  No entry is left out; an entry whose M is 0 has no
+term at all and must be exactly 0.
+
+The bound.  ``RHO_O`` records, per kind of output, the worst ratio of the **fp64 oracle** against the extended one over
+``CASES`` -- measured on the CPU, kept honest by tests/test_precision_host.py.  A device result passes at
+``GAMMA[kind] = 16 max(rho_o, 1)``: the margin of 16 covers what the kernels legitimately do differently from Cox-de Boor on
+tiled positions (local cubic pieces, FMA contraction, ``fast_rcp`` and ``norm3_leg`` at about an ulp each, another order of
+summation), each a bounded number of extra roundings per term.  The bound is never derived from a device result.
+
+One documented design choice is not a bounded number of roundings per term: the launches that evaluate leg functions from
+local cubic pieces in powers of ``x - t_i`` (k_featurize3, the grouped matrix-core launch) carry Horner's absolute error on
+values that are themselves tiny.  For those routes alone M is the oracle's widened one (``ratios(..., pieces=True)``;
+uf3_oracle.c: piece_abs holds the derivation); GAMMA is the same.
+"""
+import functools
+import json
+
+import numpy as np
+
+from oracle import oracle as O
+from uf3_amd import synthetic
+from uf3_amd.data import composition
+from uf3_amd.data.atoms import Atoms
+from uf3_amd.representation import bspline
+from _on_knots import coefficients
+from _util import SPECIES_CASES, basis_from_meta, load_case
+from test_feat3_pad_clamp import CELLS, ELEMENTS, _basis as clamp_basis, _frame as clamp_frame
+
+U = np.longdouble(2.0) ** -53
+KINDS = ("xe", "xf", "xv", "e", "f", "v")        # energy rows, force rows, virial rows; energies, forces, virials
+
+# Worst ratio of the fp64 oracle (libuf3oracle.so) against the extended build over CASES, per kind, as printed by
+# tests/test_precision_host.py::test_fp64_oracle_stays_within_the_recorded_table.  Measured 2026-10-20 (x86-64, gcc -O2
+# -ffp-contract=off, 80-bit long double): xe 1.33, xf 1.77, xv 1.35, e 0.529, f 0.252, v 0.349 -- recorded rounded up.
+RHO_O = {"xe": 1.5, "xf": 2.0, "xv": 1.5, "e": 0.6, "f": 0.3, "v": 0.4}
+GAMMA = {k: 16.0 * max(v, 1.0) for k, v in RHO_O.items()}
+
+
+def ratio(got, truth, M):
+    """max |got - truth| / (u M) over ALL entries, in np.longdouble.  Where M == 0 no term reaches the entry: ``got`` must be
+    exactly zero there (asserted), and the entry counts with ratio 0."""
+    got = np.asarray(got, dtype=np.longdouble)
+    truth = np.asarray(truth, dtype=np.longdouble)
+    M = np.asarray(M, dtype=np.longdouble)
+    assert got.shape == truth.shape == M.shape, (got.shape, truth.shape, M.shape)
+    assert np.all(np.isfinite(got)) and np.all(M >= 0)
+    none = M == 0
+    assert not np.any(got[none]), "an entry no term reaches is not exactly zero"
+    if not got.size:
+        return 0.0
+    err = np.abs(got - truth)
+    return float((np.where(none, 0, err) / np.where(none, 1, U * M)).max())
+
+
+# ------------------------------------------------------------------------------------------------ frames clear of steps
+def clear_of_discontinuities(basis, atoms, eps=1e-9):
+    """No distance of the frame lies within ``eps`` of a point where the rows are discontinuous in it: a pair ``r_min`` or
+    ``r_max``, the ends of the 3-body list range, and an end of a leg (centre legs and ``r_jk``) whose kept functions do not
+    vanish there -- an untrimmed leading end, or a trailing end trimmed by fewer than 3.  (Interior knots need no clearance: a
+    cubic spline is C2 there.)  Returns the smallest clearance found; raises AssertionError otherwise."""
+    ob = O.OracleBasis(basis)
+    pos, _, _ = O.supercell(atoms, basis.r_cut)
+    n = len(atoms)
+    d = np.linalg.norm(pos[None, :, :] - pos[:n, None, :], axis=-1)
+    pair_d = d[d > 0]
+    steps2 = sorted({max(float(v), 0.0) for v in ob.pair_rmin} | {float(v) for v in ob.pair_rmax})
+    clear = min([np.abs(pair_d - s).min() for s in steps2] + [np.inf]) if pair_d.size else np.inf
+    assert clear > eps, ("pair distance at a pair cut-off", clear)
+    if basis.degree < 3 or not ob.trios:
+        return float(clear)
+    seqs = [[np.asarray(k, float) for k in basis.knots_map[t]] for t in ob.trios]
+    rmin3 = max(min(k.min() for ks in seqs for k in ks), 0.0)
+    rmax3 = max(k.max() for ks in seqs for k in ks[:2])
+    c = min(np.abs(pair_d - rmin3).min(), np.abs(pair_d - rmax3).min())
+    assert c > eps, ("distance at an end of the 3-body list range", c)
+    clear = min(clear, c)
+    lead, trail = int(basis.leading_trim[3]), int(basis.trailing_trim[3])
+    ends = set()
+    for ks in seqs:
+        for k in ks:
+            if lead == 0:
+                ends.add(float(k[0]))
+            if trail < 3:
+                ends.add(float(k[-1]))
+    if not ends:
+        return float(clear)
+    legs = [pair_d[pair_d <= rmax3 * (1 + 1e-6)]]
+    for i in range(n):
+        nb = np.flatnonzero((d[i] > 0) & (d[i] <= rmax3 * (1 + 1e-6)))
+        if len(nb) > 1:
+            x = pos[nb]
+            legs.append(np.linalg.norm(x[:, None] - x[None], axis=-1)[np.triu_indices(len(nb), 1)])
+    legs = np.concatenate(legs)
+    c = min(np.abs(legs - e).min() for e in ends)
+    assert c > eps, ("leg at an end whose kept functions do not vanish", c)
+    return float(min(clear, c))
+
+
+# ------------------------------------------------------------------------------------------------ the cases
+def _uneven_basis(lead):
+    """the knot sequences of test_bond_factorised_launch_with_non_uniform_knot_sequences (tests/test_gpu_parity.py)"""
+    def clamped(lo, hi, n_int, power):
+        inner = lo + (hi - lo) * np.linspace(0.0, 1.0, n_int + 1) ** power
+        return np.concatenate([[lo] * 3, inner, [hi] * 3])
+
+    cs = composition.ChemicalSystem(['Mo', 'W'], 3)
+    pairs, trios = cs.interactions_map[2], cs.interactions_map[3]
+    knots = {p: clamped(0.001, 5.5, 15, 1.3) for p in pairs}
+    for t in trios:
+        knots[t] = [clamped(1.5, 3.5, 6, 1.5), clamped(1.5, 7.0, 12, 0.75)]
+    return bspline.BSplineBasis(cs, knots_map=knots, leading_trim={2: 0, 3: lead}, trailing_trim={2: 3, 3: 3})
+
+
+def _resolution_basis(res3, elements=('Mo', 'W')):
+    """kept windows of (res - 3) bins a centre leg: [5, 5, 10] -> 2 x 2 x 7, [7, 7, 14] -> 4 x 4 x 11 (two rounds of positions),
+    [8, 8, 16] -> 5 x 5 x 13 (three)"""
+    cs = composition.ChemicalSystem(list(elements), 3)
+    pairs, trios = cs.interactions_map[2], cs.interactions_map[3]
+    return bspline.BSplineBasis(
+        cs, r_min_map={**{p: 0.001 for p in pairs}, **{t: [1.5, 1.5, 1.5] for t in trios}},
+        r_max_map={**{p: 5.5 for p in pairs}, **{t: [3.5, 3.5, 7.0] for t in trios}},
+        resolution_map={**{p: 15 for p in pairs}, **{t: list(res3) for t in trios}},
+        leading_trim={2: 0, 3: 3}, trailing_trim={2: 3, 3: 3})
+
+
+def _mixed_boundary_frames():
+    """the cluster, the slab with atoms outside its cell and the 3-atom triclinic cell thinner than the cut-off of
+    test_ragged_batch_mixed_boundary_conditions (tests/test_gpu_parity.py), drawn as there"""
+    rng = np.random.default_rng(3)
+    cell = np.array([[4.1, 0.3, 0.0], [-0.5, 3.9, 0.2], [0.4, -0.3, 4.4]])
+    cluster = Atoms(numbers=rng.choice([42, 74], 9), positions=rng.uniform(0, 5.5, (9, 3)))
+    slab = Atoms(numbers=rng.choice([42, 74], 12), positions=rng.uniform(-1, 7, (12, 3)),
+                 cell=np.diag([6.3, 6.9, 20.0]), pbc=[True, True, False])
+    thin = Atoms(numbers=rng.choice([42, 74], 3), positions=rng.uniform(0, 4, (3, 3)), cell=cell, pbc=True)
+    return cluster, slab, thin
+
+
+@functools.lru_cache(maxsize=None)
+def cases():
+    """name -> (basis, atoms, what the case is for): the smallest cells that reach every kernel instance.  Every frame is
+    asserted clear of discontinuities where its reference is made (``reference``)."""
+    out = {}
+    for name, lattice, reps, a, numbers, seed, r3, _, cap in CELLS:
+        if name in ("mow_cap16_r4", "mow_dilated_cap16"):          # (slot coverage of the pad clamp: the same instance)
+            continue
+        out[name] = (clamp_basis([ELEMENTS[z] for z in sorted(numbers)], r3), clamp_frame(lattice, reps, a, numbers, seed),
+                     f"3 x 9 windows, list capacity {cap}")
+    mow54 = clamp_frame("bcc", (3, 3, 3), 3.165, [42, 74], 300)
+    out["mow_lead0"] = (clamp_basis(["Mo", "W"], 3.5, lead3=0), mow54, "6 x 12 windows, three rounds, F = 1798")
+    out["mow_2x7"] = (_resolution_basis([5, 5, 10]), mow54, "2 x 7 windows (the reference's default 3-body resolution)")
+    out["mow_4x11"] = (_resolution_basis([7, 7, 14]), mow54, "4 x 11 windows, two rounds")
+    out["w_5x13"] = (_resolution_basis([8, 8, 16], ('W',)), clamp_frame("bcc", (3, 3, 3), 3.165, [74], 303),
+                     "5 x 13 windows, three rounds")
+    uneven = synthetic.lattice_frame("bcc", (3, 3, 4), 3.165, [42, 74], 87, rattle=0.15)
+    out["uneven_lead3"] = (_uneven_basis(3), uneven, "uneven knot sequences")
+    out["uneven_lead0"] = (_uneven_basis(0), uneven, "uneven knot sequences, no leading trim")
+    _, meta, atoms = load_case("case_bcc24_s4")
+    assert sorted(set(atoms.get_atomic_numbers().tolist())) == SPECIES_CASES["case_bcc24_s4"]
+    out["bcc24_s4"] = (basis_from_meta(meta), atoms, "four species")
+    _, meta, atoms = load_case("case_w16_sym3")             # (trimmed at both ends, as test_matrix_core_and_generic_trio_kernels_agree)
+    meta = json.loads(json.dumps(meta))
+    meta["basis_kwargs"]["leading_trim"], meta["basis_kwargs"]["trailing_trim"] = {"2": 0, "3": 3}, {"2": 3, "3": 3}
+    out["w16_sym3"] = (basis_from_meta(meta), atoms, "three equal legs: the six-fold symmetry fold")
+    cluster, slab, thin = _mixed_boundary_frames()
+    lead0 = synthetic.notebook_basis(['Mo', 'W'], lead3=0)
+    out["triclinic_thin"] = (lead0, thin, "3-atom triclinic cell thinner than the cut-off")
+    out["slab_outside"] = (lead0, slab, "slab with atoms outside its cell")
+    out["cluster"] = (lead0, cluster, "open cluster")
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    """(ob, coefficients, values, magnitudes) of a case from the extended oracle, computed once and shared (read-only): the keys
+    of KINDS, rows from ``featurize_x(virial=True)``, e / f / v from ``evaluate_x``.  ``magnitudes["pieces"]`` holds the row
+    magnitudes widened for the routes that evaluate leg functions from local cubic pieces (``ratios(..., pieces=True)``)."""
+    basis, atoms, _ = cases()[name]
+    assert len(atoms) <= 130
+    clear_of_discontinuities(basis, atoms)
+    ob = O.OracleBasis(basis)
+    coeff = coefficients(basis)
+    val, mag = O.featurize_x(ob, atoms, virial=True)
+    ev, em = O.evaluate_x(ob, atoms, coeff, virial=True)
+    val.update(ev)
+    mag.update(em)
+    wide = O.featurize_x(ob, atoms, virial=True, pieces=True)[1]
+    for k in ("xe", "xf", "xv"):
+        assert np.all(wide[k] >= mag[k]) and np.array_equal(wide[k] == 0, mag[k] == 0)
+    mag["pieces"] = wide
+    for d in (val, mag, wide):
+        for v in d.values():
+            if isinstance(v, np.ndarray):
+                v.setflags(write=False)
+    return ob, coeff, val, mag
+
+
+def fp64_oracle(name):
+    """the fp64 build's results of a case, keys of KINDS (the virial rows from the fp64 build's own ``*_x`` entry)"""
+    basis, atoms, _ = cases()[name]
+    ob, coeff, _, _ = reference(name)
+    rows = O.featurize(ob, atoms)
+    e, f, v = O.evaluate(ob, atoms, coeff, virial=True)
+    xv = O.featurize_x(ob, atoms, virial=True, extended=False)[0]
+    assert np.array_equal(xv["xe"], rows["xe"]) and np.array_equal(xv["xf"], rows["xf"])
+    return {"xe": rows["xe"], "xf": rows["xf"], "xv": xv["xv"], "e": e, "f": f, "v": v,
+            "pair_cnt": xv["pair_cnt"], "n3_cnt": xv["n3_cnt"]}
+
+
+def ratios(got, name, kinds=None, pieces=False):
+    """{kind: ratio} of the results ``got`` (a dict with keys of KINDS) of a case against its reference.  ``pieces``: the rows
+    come from a route that evaluates the 3-body leg functions from local cubic pieces in powers of the distance from the
+    interval's lower knot (k_featurize3, the grouped matrix-core launch), whose absolute error does not shrink with the
+    value: M is the oracle's widened one (uf3_oracle.c: piece_abs).  Every other route is held to the plain M."""
+    _, _, val, mag = reference(name)
+    if pieces:
+        mag = {**mag, **mag["pieces"]}
+    return {k: ratio(got[k], val[k], mag[k]) for k in (kinds or KINDS) if k in got and got[k] is not None}
+
+
+def fmt(r):
+    return ", ".join(f"{k} {v:.3g}" for k, v in r.items())

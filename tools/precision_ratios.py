@@ -1,0 +1,62 @@
+#!/usr/bin/env python
+"""
+Collect the ``[precision] route, case: kind ratio, ...`` lines of a ``pytest -s tests/test_gpu_precision.py`` run into
+``profiles/precision_ratios.json``: route by case by kind, the worst ratio where a line repeats, beside the bound the run was
+held to.  A ratio is ``max |device - extended oracle| / (2^-53 M)`` over every entry of a result (tests/_precision.py).
+
+    python -m pytest -m gpu -s tests/test_gpu_precision.py | tee precision.log
+    python tools/precision_ratios.py precision.log [-o profiles/precision_ratios.json]
+"""
+import argparse
+import json
+import os
+import re
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LINE = re.compile(r"\[precision\] (?P<route>.+), (?P<case>\w+): (?P<kinds>(?:\w+ [-+.\deE]+(?:, )?)+)\s*$")
+
+
+def collect(lines):
+    out = {}
+    for line in lines:
+        m = LINE.search(line)
+        if not m or m.group("route").startswith(("fp64 oracle", "planted")):
+            continue
+        slot = out.setdefault(m.group("route"), {}).setdefault(m.group("case"), {})
+        for item in m.group("kinds").split(", "):
+            kind, value = item.split()
+            slot[kind] = max(slot.get(kind, 0.0), float(value))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("log", nargs="+")
+    ap.add_argument("-o", "--out", default=os.path.join(ROOT, "profiles", "precision_ratios.json"))
+    args = ap.parse_args()
+    lines = []
+    for path in args.log:
+        with open(path, errors="replace") as f:
+            lines += f.read().splitlines()
+    routes = collect(lines)
+    if not routes:
+        sys.exit("no [precision] lines found")
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+    import _precision as P
+    worst = {}
+    for cases in routes.values():
+        for kinds in cases.values():
+            for k, v in kinds.items():
+                worst[k] = max(worst.get(k, 0.0), v)
+    doc = {"what": "worst |device - extended oracle| / (2^-53 M) over every entry, per route, case and kind of output "
+                   "(xe, xf, xv: energy, force, virial rows; e, f, v: energy, forces, virial); tests/test_gpu_precision.py",
+           "rho_o": P.RHO_O, "gamma": P.GAMMA, "worst": worst, "routes": routes}
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"{len(routes)} routes, worst {worst} -> {args.out}")
+
+
+if __name__ == "__main__":
+    main()

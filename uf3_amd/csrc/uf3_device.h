@@ -320,7 +320,9 @@ __device__ __forceinline__ double norm3_rn(double dx, double dy, double dz) {
 // tests/test_gpu_on_knots.py holds every kernel that calls this to distances on, and 1 and 2 x 2^-42 A either side of, every
 // knot and leg end (with the result taken one ulp high, every test of a basis with leading trim 0 fails there).  Where r_jk is
 // no double the fused radicand may put a distance within rounding of t0 on the other side than cdist's
-// sum: accepted, not tested.  The root comes from the hardware estimate + one Newton step + one correction (8 instructions; the
+// sum: accepted.  Away from such an end the VALUES that follow from this r_jk are held, entry by entry, to the extended-precision
+// oracle (tests/test_gpu_precision.py); its error weight for the third leg is r_ij + r_ik, the lengths any fp64 r_jk is formed
+// from, and the measured ratios are in profiles/precision_ratios.json.  The root comes from the hardware estimate + one Newton step + one correction (8 instructions; the
 // IEEE library root with its scaling for subnormal arguments is 20, and the walk takes one per triplet role).
 __device__ __forceinline__ double norm3_leg(double dx, double dy, double dz) {
     const double s = fma(dz, dz, fma(dy, dy, dx * dx));
