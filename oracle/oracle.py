@@ -9,8 +9,8 @@ The basis description is read from any object exposing the reference's
 reference's own class (golden capture) and on ``uf3_amd``'s.
 
 The C source builds twice: ``libuf3oracle.so`` (fp64; ``featurize``, ``evaluate``) and ``libuf3oracle_x.so`` (``long double``
-values on fp64 decisions; ``featurize_x``, ``evaluate_x``, which also return the magnitude M of every entry -- see
-uf3_oracle.c and tests/_precision.py).
+values on fp64 decisions; ``featurize_x``, ``evaluate_x``, ``hessian_x``, ``site_terms_x``, ``site_rows_x``, which also return the magnitude M of every
+entry -- see uf3_oracle.c and tests/_precision.py).
 """
 import ctypes as C
 import os
@@ -58,7 +58,8 @@ def build(force=False, name="libuf3oracle.so"):
 
 def _load(name):
     so = C.CDLL(build(name=name))
-    for f in ("uf3o_featurize", "uf3o_featurize_x", "uf3o_eval", "uf3o_eval_virial", "uf3o_eval_x", "uf3o_real_mant_dig"):
+    for f in ("uf3o_featurize", "uf3o_featurize_x", "uf3o_eval", "uf3o_eval_virial", "uf3o_eval_x", "uf3o_real_mant_dig",
+              "uf3o_hessian_x", "uf3o_site_terms_x", "uf3o_site_rows_x"):
         getattr(so, f).restype = C.c_int
     so.uf3o_supercell.restype = C.c_int64
     return so
@@ -207,6 +208,84 @@ def evaluate_x(ob, atoms, coefficients, virial=True, extended=True):
     val, mag = {"e": e[0], "f": f}, {"e": me[0], "f": mf}
     if virial:
         val["v"], mag["v"] = v, mv
+    return val, mag
+
+
+def supercell_radius(ob, atoms):
+    """The radius the supercell of ``hessian_x``, ``site_terms_x`` and ``site_rows_x`` is built for: the basis' ``r_cut``, plus
+    how far the farthest atom lies from its image inside the cell.  Those entries describe the frame with every atom counted as
+    its image inside the cell (as the device entries they check do), while the supercell tiles the positions as given around
+    the cell: the wider radius keeps every image that a real atom's terms reach.  A frame inside its cell: ``r_cut`` itself."""
+    fv = _FrameView(atoms)
+    pad = 0.0
+    if fv.pbc.any() and abs(np.linalg.det(fv.cell)) > 0:
+        frac = fv.pos @ np.linalg.inv(fv.cell)
+        out = np.where(fv.pbc.astype(bool)[None, :], np.floor(frac + 1e-9 * (frac < 0) - 1e-9 * (frac >= 1)), 0.0)
+        pad = float(np.linalg.norm(out @ fv.cell, axis=1).max()) if len(out) else 0.0
+    return float(ob.basis.r_cut) + pad
+
+
+def _kind(extended):
+    return (lib_x(), np.longdouble) if extended else (lib(), np.float64)
+
+
+def hessian_x(ob, atoms, coefficients, strain=True, extended=True):
+    """Second derivatives of ``evaluate``'s energy (uf3_hessian.h) from the extended build: ``(values, magnitudes)``, dicts with
+    keys ``H`` [3N,3N] and, with ``strain=True``, ``mixed`` [3N,6] and ``born`` [6,6]; see ``featurize_x``."""
+    so, dtype = _kind(extended)
+    c1, c2, c3 = split_coefficients(ob, coefficients)
+    fv = _FrameView(atoms)
+    n3 = 3 * fv.c.n_atoms
+    val = {"H": np.zeros((n3, n3), dtype), "mixed": np.zeros((n3, 6), dtype) if strain else None,
+           "born": np.zeros((6, 6), dtype) if strain else None}
+    mag = {k: (np.zeros(v.shape) if v is not None else None) for k, v in val.items()}
+    rc = so.uf3o_hessian_x(C.byref(ob.spec), C.byref(fv.c), _ptr(c1), _ptr(c2), _ptr(c3), C.c_double(supercell_radius(ob, atoms)),
+                           _ptr(val["H"]), _ptr(val["mixed"]), _ptr(val["born"]), _ptr(mag["H"]), _ptr(mag["mixed"]),
+                           _ptr(mag["born"]))
+    if rc:
+        raise RuntimeError(f"uf3o_hessian_x rc={rc}")
+    if not strain:
+        for d in (val, mag):
+            del d["mixed"], d["born"]
+    return val, mag
+
+
+def site_terms_x(ob, atoms, coefficients, velocities=None, extended=True):
+    """Site energies, site virials and each centre's share of the heat current's potential part (uf3_flux.h) from the extended
+    build: ``(values, magnitudes)``, dicts with keys ``U`` [N], ``W`` [N,3,3] and, with ``velocities`` [N,3], ``jp`` [N,3];
+    ``values["e"]`` / ``magnitudes["e"]``: the frame's energy from the same loop.  See ``featurize_x``."""
+    so, dtype = _kind(extended)
+    c1, c2, c3 = split_coefficients(ob, coefficients)
+    fv = _FrameView(atoms)
+    n = fv.c.n_atoms
+    vel = None if velocities is None else np.ascontiguousarray(np.asarray(velocities, dtype=np.float64).reshape(n, 3))
+    val = {"U": np.zeros(n, dtype), "W": np.zeros((n, 3, 3), dtype), "jp": np.zeros((n, 3), dtype) if vel is not None else None}
+    mag = {k: (np.zeros(v.shape) if v is not None else None) for k, v in val.items()}
+    e, me = np.zeros(1, dtype), np.zeros(1)
+    rc = so.uf3o_site_terms_x(C.byref(ob.spec), C.byref(fv.c), _ptr(c1), _ptr(c2), _ptr(c3),
+                              C.c_double(supercell_radius(ob, atoms)), _ptr(vel), _ptr(val["U"]), _ptr(val["W"]), _ptr(val["jp"]),
+                              _ptr(mag["U"]), _ptr(mag["W"]), _ptr(mag["jp"]), _ptr(e), _ptr(me))
+    if rc:
+        raise RuntimeError(f"uf3o_site_terms_x rc={rc}")
+    if vel is None:
+        del val["jp"], mag["jp"]
+    val["e"], mag["e"] = e[0], me[0]
+    return val, mag
+
+
+def site_rows_x(ob, atoms, extended=True):
+    """Site rows (uf3_site_rows.h) from the extended build: ``(values, magnitudes)``, dicts with keys ``b`` [N,F] -- the energy
+    row's terms credited to their centre, folded into columns as ``featurize_x`` folds them -- and ``xe`` [F], the energy row of
+    the same walk.  See ``featurize_x``."""
+    so, dtype = _kind(extended)
+    fv = _FrameView(atoms)
+    n, F = fv.c.n_atoms, ob.n_feat
+    val = {"b": np.zeros((n, F), dtype), "xe": np.zeros(F, dtype)}
+    mag = {"b": np.zeros((n, F)), "xe": np.zeros(F)}
+    rc = so.uf3o_site_rows_x(C.byref(ob.spec), C.byref(fv.c), C.c_double(supercell_radius(ob, atoms)), _ptr(val["b"]),
+                             _ptr(mag["b"]), _ptr(val["xe"]), _ptr(mag["xe"]))
+    if rc:
+        raise RuntimeError(f"uf3o_site_rows_x rc={rc}")
     return val, mag
 
 

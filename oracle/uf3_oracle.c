@@ -273,9 +273,35 @@ static real basis_element(const double *t, double xd, real x, int nu) {
     if (!(xd >= t[0] && xd <= t[4])) return 0.0;   /* extrapolate=False -> NaN -> 0 */
     if (nu == 0) return bspl(t, 0, 3, xd, x);
     real a = 0.0, b = 0.0, d1 = (real)t[3] - t[0], d2 = (real)t[4] - t[1];
+    if (nu == 2) {      /* the recursion once more: the quadratic elements' derivatives from the linear elements */
+        real qd[2];
+        for (int s = 0; s < 2; s++) {
+            real e1 = (real)t[s + 2] - t[s], e2 = (real)t[s + 3] - t[s + 1];
+            qd[s] = (e1 > 0 ? 2.0 / e1 * bspl(t, s, 1, xd, x) : 0.0) - (e2 > 0 ? 2.0 / e2 * bspl(t, s + 1, 1, xd, x) : 0.0);
+        }
+        if (d1 > 0) a = 3.0 / d1 * qd[0];
+        if (d2 > 0) b = 3.0 / d2 * qd[1];
+        return a - b;
+    }
     if (d1 > 0) a = 3.0 / d1 * bspl(t, 0, 2, xd, x);
     if (d2 > 0) b = 3.0 / d2 * bspl(t, 1, 2, xd, x);
     return a - b;
+}
+/* |B'''|_abs of the cubic element: the third derivative is constant on a knot interval (a step function), so this is the
+   interval's own -- every subtraction of the recursion down to the degree-0 elements replaced by an addition */
+static real basis_element_abs3(const double *t, double xd, real x) {
+    if (!(xd >= t[0] && xd <= t[4])) return 0.0;
+    real la[3], d3 = 0.0;
+    for (int s = 0; s < 3; s++) {
+        real g1 = (real)t[s + 1] - t[s], g2 = (real)t[s + 2] - t[s + 1];
+        la[s] = (g1 > 0 ? bspl(t, s, 0, xd, x) / g1 : 0.0) + (g2 > 0 ? bspl(t, s + 1, 0, xd, x) / g2 : 0.0);
+    }
+    for (int s = 0; s < 2; s++) {
+        real e1 = (real)t[s + 2] - t[s], e2 = (real)t[s + 3] - t[s + 1], c = (real)t[s + 3] - t[s];
+        real qdd = (e1 > 0 ? 2.0 / e1 * la[s] : 0.0) + (e2 > 0 ? 2.0 / e2 * la[s + 1] : 0.0);
+        if (c > 0) d3 += 3.0 / c * qdd;
+    }
+    return d3;
 }
 /* for the magnitudes: |B'|_abs (the derivative's two summands added, not subtracted) and |B''|_abs (likewise, down to the four
    linear elements) of the cubic element.  The value itself is a sum of non-negative products: |B|_abs = B. */
@@ -359,6 +385,9 @@ typedef struct {
     real *xe, *xf, *xv;       /* [F], [N][3][F], [6][F] */
     double *me, *mf, *mv;
     int pieces;               /* the 3-body magnitudes of a route that evaluates leg functions from local pieces: piece_abs */
+    real *xb;                 /* [N][F] site rows: the energy row's terms credited to their centre (with xe and me) */
+    double *mb;
+    double sc_r;              /* supercell radius in place of the basis' r_cut (0: r_cut) */
 } rows_t;
 
 /* ------------------------------------------------------------------ 2-body */
@@ -404,14 +433,26 @@ static void two_body(const uf3o_spec *s, const supercell_t *sc, const grid_t *g,
             }
             real dr = rdist3(ri, rj);
             int nb = s->pair_nk[p] - 4;
-            for (int b = s->lead2; b < nb - s->trail2; b++) {
+            for (int b = o->xb ? 0 : s->lead2; b < (o->xb ? nb : nb - s->trail2); b++) {
                 const double *t = knots[p] + b;
                 real a1 = 0.0, a2 = 0.0;
                 if (want_m) basis_element_abs(t, d, dr, &a1, &a2);
+                if (b < s->lead2 || b >= nb - s->trail2) {
+                    /* a trimmed pair function: no entry of the energy row, but a column of the site row, which holds
+                       b_i . c = U_i for EVERY coefficient vector and the evaluator takes all pair coefficients (uf3_site_rows.h) */
+                    real val = basis_element(t, d, dr, 0);
+                    o->xb[(size_t)i * F + s->pair_col[p] + b] += val;
+                    o->mb[(size_t)i * F + s->pair_col[p] + b] += (double)(val + dr * a1);
+                    continue;
+                }
                 if (xe) {
                     real val = basis_element(t, d, dr, 0);
                     xe[s->pair_col[p] + b] += val;
                     if (o->me) o->me[s->pair_col[p] + b] += (double)(val + dr * a1);
+                    if (o->xb) {
+                        o->xb[(size_t)i * F + s->pair_col[p] + b] += val;
+                        o->mb[(size_t)i * F + s->pair_col[p] + b] += (double)(val + dr * a1);
+                    }
                 }
                 if ((xf || xv) && d > t[0] && d < t[4]) {           /* strict support mask, bspline.py:884 */
                     real dv = basis_element(t, d, dr, 1);
@@ -505,7 +546,8 @@ static void trio_views(const uf3o_spec *s, trio_view *v, double *rmin3, double *
 }
 
 /* the four candidate bases of one leg at r: values, derivatives and, for the magnitudes, |B'|_abs and |B''|_abs */
-typedef struct { real v[4], d[4], a1[4], a2[4], m0[4], m1[4], m2[4]; } leg_t;   /* m: v, a1, a2, or widened (piece_abs) */
+typedef struct { real v[4], d[4], a1[4], a2[4], m0[4], m1[4], m2[4];              /* m: v, a1, a2, or widened (piece_abs) */
+                 real dd[4], a3[4]; } leg_t;                                     /* der = 2: B'' and (with mag) |B'''|_abs */
 
 /* values (and derivatives) of the four candidate bases of leg `d` at r (angles.py:545-566, 607-630); rd: the fp64 distance;
    mag: 0 no magnitudes, 1 Cox-de Boor's (m0 = the value), 2 widened to those of the local piece */
@@ -514,9 +556,11 @@ static int leg_values(const trio_view *v, int d, double rd, real r, int lead, in
     for (int a = 0; a < 4; a++) {
         int b = first + a;
         g->v[a] = 0.0; g->d[a] = 0.0; g->a1[a] = 0.0; g->a2[a] = 0.0; g->m0[a] = 0.0; g->m1[a] = 0.0; g->m2[a] = 0.0;
+        g->dd[a] = 0.0; g->a3[a] = 0.0;
         if (b < lead || b >= v->dim[d] - trail) continue;   /* trimmed, or wrapped negative index */
         g->v[a] = basis_element(v->k[d] + b, rd, r, 0);
         if (der) g->d[a] = basis_element(v->k[d] + b, rd, r, 1);
+        if (der == 2) { g->dd[a] = basis_element(v->k[d] + b, rd, r, 2); if (mag) g->a3[a] = basis_element_abs3(v->k[d] + b, rd, r); }
         if (mag) {
             basis_element_abs(v->k[d] + b, rd, r, &g->a1[a], &g->a2[a]);
             g->m0[a] = g->v[a]; g->m1[a] = g->a1[a]; g->m2[a] = g->a2[a];
@@ -629,6 +673,13 @@ static void three_body(const uf3o_spec *s, const supercell_t *sc, const grid_t *
         if (xe && o->me) megrid[t] = (double *)calloc(sz, sizeof(double));
         if (xv && o->mv) mvgrid[t] = (double *)calloc(6 * sz, sizeof(double));
     }
+    /* site rows: the energy grids of one centre at a time, folded into its row when the centre is done */
+    real **bgrid = o->xb ? (real **)malloc(sizeof(real *) * (size_t)T) : NULL;
+    double **mbgrid = o->xb ? (double **)malloc(sizeof(double *) * (size_t)T) : NULL;
+    for (int t = 0; bgrid && t < T; t++) {
+        size_t sz = (size_t)v[t].dim[0] * v[t].dim[1] * v[t].dim[2];
+        bgrid[t] = (real *)calloc(sz, sizeof(real)); mbgrid[t] = (double *)calloc(sz, sizeof(double));
+    }
     int *cand = NULL, cap = 0, *nbr = NULL, nbr_cap = 0;
     double *nbr_d = NULL;
     int64_t cnt = 0;
@@ -696,6 +747,7 @@ static void three_body(const uf3o_spec *s, const supercell_t *sc, const grid_t *
                                 if (val != 0.0) {
                                     egrid[t][u] += val;
                                     if (megrid[t]) megrid[t][u] += (double)mag_value(q, r);
+                                    if (bgrid) { bgrid[t][u] += val; mbgrid[t][u] += (double)mag_value(q, r); }
                                 }
                             }
                             if (xv) for (int e = 0; e < 6; e++) {
@@ -744,8 +796,16 @@ static void three_body(const uf3o_spec *s, const supercell_t *sc, const grid_t *
                     }
                 }
             }
+            if (pass == 0 && bgrid) for (int t = 0; t < T; t++) {
+                size_t sz = (size_t)v[t].dim[0] * v[t].dim[1] * v[t].dim[2];
+                compress_add(s, v + t, t, bgrid[t], o->xb + (size_t)i * F, 1.0);
+                compress_add_abs(s, v + t, t, mbgrid[t], o->mb + (size_t)i * F);
+                for (size_t u = 0; u < sz; u++) { bgrid[t][u] = 0.0; mbgrid[t][u] = 0.0; }
+            }
         }
     }
+    for (int t = 0; bgrid && t < T; t++) { free(bgrid[t]); free(mbgrid[t]); }
+    free(bgrid); free(mbgrid);
     for (int t = 0; t < T; t++) {
         size_t sz = (size_t)v[t].dim[0] * v[t].dim[1] * v[t].dim[2];
         if (xe) compress_add(s, v + t, t, egrid[t], xe, 1.0);
@@ -767,7 +827,7 @@ static int featurize_worker(const uf3o_spec *s, const uf3o_frame *f, const rows_
     supercell_t sc;
     grid_t g;
     for (int a = 0; a < f->n_atoms; a++) if (species_index(s, f->z[a]) < 0) return 2;
-    build_supercell(f, s->r_cut, &sc);
+    build_supercell(f, o->sc_r > 0 ? o->sc_r : s->r_cut, &sc);
     double rmin3 = 0, rmax3 = 0, h = 0;
     for (int p = 0; p < s->n_pairs; p++) if (s->pair_rmax[p] > h) h = s->pair_rmax[p];
     if (s->n_trios > 0) {
@@ -784,6 +844,13 @@ static int featurize_worker(const uf3o_spec *s, const uf3o_frame *f, const rows_
         for (int a = 0; a < f->n_atoms; a++) {
             o->xe[species_index(s, f->z[a])] += 1.0;
             if (o->me) o->me[species_index(s, f->z[a])] += 1.0;
+        }
+    }
+    if (o->xb) {
+        for (size_t q = 0; q < F * (size_t)f->n_atoms; q++) { o->xb[q] = 0.0; o->mb[q] = 0.0; }
+        for (int a = 0; a < f->n_atoms; a++) {
+            o->xb[(size_t)a * F + species_index(s, f->z[a])] += 1.0;
+            o->mb[(size_t)a * F + species_index(s, f->z[a])] += 1.0;
         }
     }
     if (o->xf) for (size_t q = 0; q < NF; q++) o->xf[q] = 0.0;
@@ -814,7 +881,7 @@ static int featurize_worker(const uf3o_spec *s, const uf3o_frame *f, const rows_
 int uf3o_featurize(const uf3o_spec *s, const uf3o_frame *f, real *xe, real *xf,
                    int64_t *pair_cnt, int64_t *pair_ij, int64_t pair_cap,
                    int64_t *n3_cnt, int64_t *n3_ij, int64_t n3_cap, int64_t *sc_info) {
-    rows_t o = {xe, xf, NULL, NULL, NULL, NULL, 0};
+    rows_t o = {xe, xf, NULL, NULL, NULL, NULL, 0, NULL, NULL, 0.0};
     return featurize_worker(s, f, &o, pair_cnt, pair_ij, pair_cap, n3_cnt, n3_ij, n3_cap, sc_info);
 }
 
@@ -826,8 +893,24 @@ int uf3o_featurize(const uf3o_spec *s, const uf3o_frame *f, real *xe, real *xf,
  */
 int uf3o_featurize_x(const uf3o_spec *s, const uf3o_frame *f, real *xe, real *xf, real *xv,
                      double *me, double *mf, double *mv, int pieces, int64_t *pair_cnt, int64_t *n3_cnt) {
-    rows_t o = {xe, xf, xv, me, mf, mv, pieces};
+    rows_t o = {xe, xf, xv, me, mf, mv, pieces, NULL, NULL, 0.0};
     return featurize_worker(s, f, &o, pair_cnt, NULL, 0, n3_cnt, NULL, 0, NULL);
+}
+
+/*
+ * Site rows b [N][F] with magnitudes mb: the energy row's terms credited to their centre -- the one-body 1 of atom i, its
+ * directed pair entries, the triplets it is the centre of (uf3_site_rows.h's partition: b_i . c = U_i of uf3o_site_terms_x) --
+ * each folded into columns exactly as the energy row is; beside them the energy row xe [F] and me of the same walk
+ * (sum_i b_i = xe up to the order of the additions).  One difference, uf3_site_rows.h's: a pair function that the basis trims
+ * has no entry in the energy row but keeps its column in the site row, because b_i . c = U_i holds for EVERY flat coefficient
+ * vector and the evaluator takes all pair coefficients; sum_i b_i = xe on the columns the energy row keeps, and xe is exactly
+ * zero on the others.  A column no term of atom i reaches has b = 0 and M = 0.  sc_r: the
+ * radius the supercell is built for (>= the basis' r_cut; wider where atoms lie outside their cell, so that every image a
+ * real atom's terms reach is there: these rows are those of the frame with every atom counted as its image inside the cell).
+ */
+int uf3o_site_rows_x(const uf3o_spec *s, const uf3o_frame *f, double sc_r, real *xb, double *mb, real *xe, double *me) {
+    rows_t o = {xe, NULL, NULL, me, NULL, NULL, 0, xb, mb, sc_r};
+    return featurize_worker(s, f, &o, NULL, NULL, 0, NULL, NULL, 0, NULL);
 }
 
 /* supercell positions / species in reference order; returns m (call with out=NULL to size) */
@@ -876,6 +959,211 @@ static void strain_add(real *virial6, double *m6, real g, real gm, const double 
 }
 
 /*
+ * ---- per-centre and second-derivative outputs of the evaluator's term loop (uf3o_site_terms_x, uf3o_hessian_x) -------------
+ *
+ * A term of the energy is a function V of nl leg lengths (a pair term: one leg; a triplet: ij, ik, jk) between ns slots (slot 0
+ * the centre, then its neighbour images); leg q runs from slot legs[q][0] to slot legs[q][1], sg[q][s] = +1 / -1 / 0 is
+ * d r_q / d(slot s) in units of the leg's unit vector u_q.  In leg space the term has the value, the gradient g_q and the
+ * symmetric leg Hessian K_qq', from B-spline values, first and second derivatives by the recursion (basis_element, nu = 0, 1, 2).
+ *
+ * Every output entry below is linear in g or bilinear in (K, g) with geometric weights that the entry fixes:
+ *     first order   e = sum_q g_q w_q                                       (site virials, the heat current's potential part)
+ *     second order  e = sum_qq' K_qq' X_q Y_q' + sum_q g_q Z_q              (H, mixed, born)
+ * Magnitudes, by the definition at the top of this file (absolute values wherever a term takes signs, plus the sensitivity to a
+ * relative rounding of each leg length, rho = r for a pair leg and a centre leg, r_ij + r_ik for the third leg):
+ *     M1 = sum_q |g_q|_abs |w_q|_abs + sum_l rho_l ( sum_q |K_lq|_abs |w_q|_abs + |g_l|_abs |w_l|_abs / r_l )
+ * which is mag_grad's expression (a pair: (2 |phi'|_abs + r |phi''|_abs) |w|, two_body's gm), and
+ *     M2 = sum_qq' |K_qq'|_abs |X_q| |Y_q'| + sum_q |g_q|_abs |Z_q|_abs
+ *        + sum_l rho_l ( sum_qq' |T_qq'l|_abs |X_q| |Y_q'| + sum_q |K_ql|_abs |Z_q|_abs
+ *                        + ( sum_q' (|K_lq'|_abs |X_l| |Y_q'| + |K_q'l|_abs |X_q'| |Y_l|) + 2 |g_l|_abs |Z_l|_abs ) / r_l )
+ * T = d3V / dr_q dr_q' dr_l: the derivative of K with respect to a leg length.  For a cubic spline the third derivative of a leg
+ * function is a step function; its |.|_abs is the interval's own (basis_element_abs3).  The last line is the weights' own
+ * sensitivity: a weight X_l or Y_l is of degree 0 or 1 in the vector of leg l (a cosine, d_a d_b / r) and counts once, as in
+ * mag_grad; Z_l is a quotient of products of the leg's components by its length ((I - uu^T) / r and its strain analogues) and
+ * counts twice.  |w|_abs, |Z|_abs: the weight with every subtraction inside it replaced by an addition (I - uu^T -> I + |u||u|^T,
+ * d_ik[a] - d_ij[a] -> |d_ik[a]| + |d_ij[a]|).  An entry that no term reaches keeps M = 0.
+ */
+typedef struct {
+    int nl, ns;
+    int legs[3][2];
+    real d[3][3], r[3], rho[3];        /* leg vectors (from -> to), lengths, rounding weights */
+    real g[3], K[3][3];                /* leg gradient, leg Hessian (K only for the second-order outputs) */
+    real ga[3], Ka[3][3], Ta[3][3][3]; /* |.|_abs of g, K and T */
+} term_t;
+
+typedef struct {
+    double sc_r;                       /* supercell radius in place of the basis' r_cut (0: r_cut) */
+    int n;                             /* real atoms */
+    const double *vel;                 /* [N][3] or NULL */
+    real *U, *W, *J;                   /* [N], [N][9], [N][3] (J only with vel); NULL: not wanted */
+    double *mU, *mW, *mJ;
+    real *H, *L, *B;                   /* [3N][3N], [3N][6], [6][6]; NULL: not wanted */
+    double *mH, *mL, *mB;
+} sink_t;
+
+static real m1_of(const term_t *t, const real *wa) {
+    real m = 0.0;
+    for (int q = 0; q < t->nl; q++) m += t->ga[q] * wa[q];
+    for (int l = 0; l < t->nl; l++) {
+        real s = t->ga[l] * wa[l] / t->r[l];
+        for (int q = 0; q < t->nl; q++) s += t->Ka[l][q] * wa[q];
+        m += t->rho[l] * s;
+    }
+    return m;
+}
+static real e2_of(const term_t *t, const real *X, const real *Y, const real *Z) {
+    real e = 0.0;
+    for (int q = 0; q < t->nl; q++) for (int p = 0; p < t->nl; p++) e += t->K[q][p] * X[q] * Y[p];
+    for (int q = 0; q < t->nl; q++) e += t->g[q] * Z[q];
+    return e;
+}
+static real m2_of(const term_t *t, const real *X, const real *Y, const real *Za) {
+    real m = 0.0, xa[3], ya[3];
+    int nl = t->nl;
+    for (int q = 0; q < nl; q++) { xa[q] = rabs(X[q]); ya[q] = rabs(Y[q]); }
+    for (int q = 0; q < nl; q++) for (int p = 0; p < nl; p++) m += t->Ka[q][p] * xa[q] * ya[p];
+    for (int q = 0; q < nl; q++) m += t->ga[q] * Za[q];
+    for (int l = 0; l < nl; l++) {
+        real s = 0.0, geo = 2.0 * t->ga[l] * Za[l];
+        for (int q = 0; q < nl; q++) for (int p = 0; p < nl; p++) s += t->Ta[q][p][l] * xa[q] * ya[p];
+        for (int q = 0; q < nl; q++) s += t->Ka[q][l] * Za[q];
+        for (int p = 0; p < nl; p++) geo += t->Ka[l][p] * xa[l] * ya[p] + t->Ka[p][l] * xa[p] * ya[l];
+        m += t->rho[l] * (s + geo / t->r[l]);
+    }
+    return m;
+}
+/* the strain direction of Voigt component v applied to d: d(d)/dt_v = E_v d, eps_ab = eps_ba = t / 2 off the diagonal */
+static void strain_dir(int v, const real *d, real *o) {
+    int a = VOIGT[v][0], b = VOIGT[v][1];
+    o[0] = o[1] = o[2] = 0.0;
+    if (a == b) o[a] = d[a];
+    else { o[a] = 0.5 * d[b]; o[b] = 0.5 * d[a]; }
+}
+
+/* one term of centre i into the sinks; par[s]: the parent atom of slot s; val, mval: the term's value and its magnitude */
+static void sink_term(const sink_t *k, int i, const int *par, const term_t *t, real val, real mval) {
+    int nl = t->nl, ns = t->ns, N = k->n;
+    real u[3][3], sg[3][3] = {{0}};
+    for (int q = 0; q < nl; q++) {
+        for (int c = 0; c < 3; c++) u[q][c] = t->d[q][c] / t->r[q];
+        sg[q][t->legs[q][1]] += 1.0; sg[q][t->legs[q][0]] -= 1.0;
+    }
+    if (k->U) { k->U[i] += val; k->mU[i] += (double)mval; }
+    /* slot s >= 1 lies at d_s from the centre: the vector of the centre leg that ends in it (leg s - 1 in both kinds of term);
+       dU_i / dr_s = sum_q g_q sg[q][s] u_q */
+    if (k->W) for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) {
+        real w[3], wa[3], e = 0.0;
+        for (int q = 0; q < nl; q++) {
+            real c = 0.0, ca = 0.0;
+            for (int s = 1; s < ns; s++) { c += sg[q][s] * t->d[s - 1][a]; ca += rabs(sg[q][s] * t->d[s - 1][a]); }
+            w[q] = c * u[q][b]; wa[q] = ca * rabs(u[q][b]);
+            e += t->g[q] * w[q];
+        }
+        k->W[(size_t)i * 9 + 3 * a + b] += e;
+        k->mW[(size_t)i * 9 + 3 * a + b] += (double)m1_of(t, wa);
+    }
+    if (k->J) for (int a = 0; a < 3; a++) {
+        real wa[3], e = 0.0;
+        for (int q = 0; q < nl; q++) {
+            real c = 0.0, ca = 0.0;
+            for (int s = 1; s < ns; s++) {
+                const double *vs = k->vel + 3 * (size_t)par[s];
+                real uv = 0.0, uva = 0.0;
+                for (int b = 0; b < 3; b++) { uv += u[q][b] * vs[b]; uva += rabs(u[q][b] * vs[b]); }
+                c += sg[q][s] * t->d[s - 1][a] * uv; ca += rabs(sg[q][s] * t->d[s - 1][a]) * uva;
+            }
+            wa[q] = ca;
+            e += t->g[q] * c;
+        }
+        k->J[(size_t)i * 3 + a] -= e;
+        k->mJ[(size_t)i * 3 + a] += (double)m1_of(t, wa);
+    }
+    if (!k->H) return;
+    size_t ld = 3 * (size_t)N;
+    real w6[3][6], ed[3][6][3];
+    for (int q = 0; q < nl; q++) for (int v = 0; v < 6; v++) {
+        w6[q][v] = t->d[q][VOIGT[v][0]] * t->d[q][VOIGT[v][1]] / t->r[q];
+        strain_dir(v, t->d[q], ed[q][v]);
+    }
+    real X[3], Y[3], Z[3], Za[3];
+    for (int s = 0; s < ns; s++) for (int a = 0; a < 3; a++) {
+        for (int q = 0; q < nl; q++) X[q] = sg[q][s] * u[q][a];
+        /* H: X = sg_s u[a], Y = sg_s' u[b], Z = sg_s sg_s' (delta_ab - u_a u_b) / r */
+        for (int s2 = 0; s2 < ns; s2++) for (int b = 0; b < 3; b++) {
+            for (int q = 0; q < nl; q++) {
+                Y[q] = sg[q][s2] * u[q][b];
+                Z[q] = sg[q][s] * sg[q][s2] * ((a == b ? 1.0 : 0.0) - u[q][a] * u[q][b]) / t->r[q];
+                Za[q] = rabs(sg[q][s] * sg[q][s2]) * ((a == b ? 1.0 : 0.0) + rabs(u[q][a] * u[q][b])) / t->r[q];
+            }
+            size_t at = (3 * (size_t)par[s] + a) * ld + 3 * (size_t)par[s2] + b;
+            k->H[at] += e2_of(t, X, Y, Z);
+            k->mH[at] += (double)m2_of(t, X, Y, Za);
+        }
+        /* mixed: Y = d_a d_b / r of the Voigt component, Z = sg_s (P E_v d)[a] / r, P = I - uu^T */
+        if (k->L) for (int v = 0; v < 6; v++) {
+            for (int q = 0; q < nl; q++) {
+                real ue = 0.0, uea = 0.0;
+                for (int c = 0; c < 3; c++) { ue += u[q][c] * ed[q][v][c]; uea += rabs(u[q][c] * ed[q][v][c]); }
+                Y[q] = w6[q][v];
+                Z[q] = sg[q][s] * (ed[q][v][a] - u[q][a] * ue) / t->r[q];
+                Za[q] = rabs(sg[q][s]) * (rabs(ed[q][v][a]) + rabs(u[q][a]) * uea) / t->r[q];
+            }
+            size_t at = (3 * (size_t)par[s] + a) * 6 + v;
+            k->L[at] += e2_of(t, X, Y, Z);
+            k->mL[at] += (double)m2_of(t, X, Y, Za);
+        }
+    }
+    /* born: X = w_v1, Y = w_v2, Z = d2 r / dt_v1 dt_v2 = ((E_v1 d) . (E_v2 d) - w_v1 w_v2) / r  (d is linear in t) */
+    if (k->B) for (int v1 = 0; v1 < 6; v1++) for (int v2 = 0; v2 < 6; v2++) {
+        for (int q = 0; q < nl; q++) {
+            real ee = 0.0, eea = 0.0;
+            for (int c = 0; c < 3; c++) { ee += ed[q][v1][c] * ed[q][v2][c]; eea += rabs(ed[q][v1][c] * ed[q][v2][c]); }
+            X[q] = w6[q][v1]; Y[q] = w6[q][v2];
+            Z[q] = (ee - w6[q][v1] * w6[q][v2]) / t->r[q];
+            Za[q] = (eea + rabs(w6[q][v1] * w6[q][v2])) / t->r[q];
+        }
+        k->B[6 * v1 + v2] += e2_of(t, X, Y, Z);
+        k->mB[6 * v1 + v2] += (double)m2_of(t, X, Y, Za);
+    }
+}
+
+/* leg Hessian K and |T|_abs of a triplet: spline3's contraction with B'' (leg_values, der = 2) and |B'''|_abs */
+static void spline3_d2(const trio_view *tv, const double *c, const double *rd, const real *r, term_t *t) {
+    leg_t g[3];
+    int L = tv->dim[0], M = tv->dim[1], N = tv->dim[2], first[3];
+    for (int q = 0; q < 3; q++) first[q] = leg_values(tv, q, rd[q], r[q], 0, 0, &g[q], 2, 1);
+    for (int q = 0; q < 3; q++) for (int p = 0; p < 3; p++) { t->K[q][p] = 0.0; for (int l = 0; l < 3; l++) t->Ta[q][p][l] = 0.0; }
+    for (int x = 0; x < 4; x++) for (int y = 0; y < 4; y++) for (int w = 0; w < 4; w++) {
+        int a = first[0] + x, b = first[1] + y, d = first[2] + w, at[3] = {x, y, w};
+        if (a < 0 || b < 0 || d < 0 || a >= L || b >= M || d >= N) continue;
+        real cc = c[((size_t)a * M + b) * N + d], ca = rabs(cc);
+        real f[3][3], fa[3][4];     /* per leg: value / first / second derivative, and the |.|_abs of orders 0 .. 3 */
+        for (int q = 0; q < 3; q++) {
+            f[q][0] = g[q].v[at[q]]; f[q][1] = g[q].d[at[q]]; f[q][2] = g[q].dd[at[q]];
+            fa[q][0] = g[q].v[at[q]]; fa[q][1] = g[q].a1[at[q]]; fa[q][2] = g[q].a2[at[q]]; fa[q][3] = g[q].a3[at[q]];
+        }
+        for (int q = 0; q < 3; q++) for (int p = q; p < 3; p++) {
+            int o[3] = {0, 0, 0};
+            o[q]++; o[p]++;
+            t->K[q][p] += cc * f[0][o[0]] * f[1][o[1]] * f[2][o[2]];
+            for (int l = p; l < 3; l++) {
+                int o3[3] = {o[0], o[1], o[2]};
+                o3[l]++;
+                t->Ta[q][p][l] += ca * fa[0][o3[0]] * fa[1][o3[1]] * fa[2][o3[2]];
+            }
+        }
+    }
+    for (int q = 0; q < 3; q++) for (int p = 0; p < q; p++) t->K[q][p] = t->K[p][q];
+    for (int q = 0; q < 3; q++) for (int p = 0; p < 3; p++) for (int l = 0; l < 3; l++) {
+        int a = q, b = p, d = l, h;       /* sorted */
+        if (a > b) { h = a; a = b; b = h; }
+        if (b > d) { h = b; b = d; d = h; }
+        if (a > b) { h = a; a = b; b = h; }
+        t->Ta[q][p][l] = t->Ta[a][b][d];
+    }
+}
+
+/*
  * Energy and forces of a fitted model (calculator.py:156-343).
  *   c1 [S] one-body, c2 concatenated pair coefficient vectors (nk-4 each, ALL bases),
  *   c3 concatenated full L*M*N grids (decompress_3B output) per trio.
@@ -886,11 +1174,11 @@ static void strain_add(real *virial6, double *m6, real g, real gm, const double 
  * me [1], mf [N][3], mv [6] (may be NULL, each only beside its value): the magnitudes.
  */
 static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
-                       real *energy, real *forces, real *virial6, double *me, double *mf, double *mv) {
+                       real *energy, real *forces, real *virial6, double *me, double *mf, double *mv, const sink_t *sk) {
     supercell_t sc;
     grid_t g;
     for (int a = 0; a < f->n_atoms; a++) if (species_index(s, f->z[a]) < 0) return 2;
-    build_supercell(f, s->r_cut, &sc);
+    build_supercell(f, sk && sk->sc_r > 0 ? sk->sc_r : s->r_cut, &sc);
     int T = s->n_trios, N = sc.n_atoms;
     trio_view *v = T ? (trio_view *)malloc(sizeof(trio_view) * (size_t)T) : NULL;
     double rmin3 = 0, rmax3 = 0, h = 0;
@@ -901,12 +1189,13 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
     double em = 0.0;
     if (!forces) mf = NULL;
     if (!virial6) mv = NULL;
-    int want_m = me || mf || mv;
+    int want_m = me || mf || mv || sk;
     if (forces) for (int q = 0; q < 3 * N; q++) forces[q] = 0.0;
     if (virial6) for (int q = 0; q < 6; q++) virial6[q] = 0.0;
     if (mf) memset(mf, 0, sizeof(double) * 3 * (size_t)N);
     if (mv) memset(mv, 0, sizeof(double) * 6);
     for (int a = 0; a < N; a++) { e += c1[species_index(s, f->z[a])]; em += fabs(c1[species_index(s, f->z[a])]); }
+    if (sk && sk->U) for (int a = 0; a < N; a++) { sk->U[a] += c1[species_index(s, f->z[a])]; sk->mU[a] += fabs(c1[species_index(s, f->z[a])]); }
     /* pair part */
     const double **pk = (const double **)malloc(sizeof(double *) * (size_t)(s->n_pairs + 1));
     const double **pc = (const double **)malloc(sizeof(double *) * (size_t)(s->n_pairs + 1));
@@ -924,7 +1213,7 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
             if (!(d > rmin && d < s->pair_rmax[p])) continue;
             real dr = rdist3(ri, rj);
             int nb = s->pair_nk[p] - 4, first = searchsorted_left(pk[p], s->pair_nk[p], d) - 4;
-            real phi = 0, dphi = 0, pa = 0, ga = 0, ha = 0;
+            real phi = 0, dphi = 0, pa = 0, ga = 0, ha = 0, ddphi = 0, ta = 0;
             for (int a = 0; a < 4; a++) {
                 int b = first + a;
                 if (b < 0 || b >= nb) continue;
@@ -935,6 +1224,10 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
                     basis_element_abs(pk[p] + b, d, dr, &a1, &a2);
                     pa += ca * basis_element(pk[p] + b, d, dr, 0); ga += ca * a1; ha += ca * a2;
                 }
+                if (sk && sk->H) {
+                    ddphi += pc[p][b] * basis_element(pk[p] + b, d, dr, 2);
+                    ta += (real)fabs(pc[p][b]) * basis_element_abs3(pk[p] + b, d, dr);
+                }
             }
             e += phi;
             em += (double)(pa + dr * ga);
@@ -944,6 +1237,13 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
                 if (mf) mf[3 * i + k] += (double)(2.0 * gm * rabs((real)rj[k] - ri[k]) / dr);
             }
             if (virial6) strain_add(virial6, mv, dphi, gm, ri, rj, dr);
+            if (sk) {
+                term_t t = {.nl = 1, .ns = 2, .legs = {{0, 1}}, .r = {dr}, .rho = {dr}, .g = {dphi}, .K = {{ddphi}},
+                            .ga = {ga}, .Ka = {{ha}}, .Ta = {{{ta}}}};
+                int par[2] = {i, j % N};
+                for (int c3 = 0; c3 < 3; c3++) t.d[0][c3] = (real)rj[c3] - ri[c3];
+                sink_term(sk, i, par, &t, phi, pa + dr * ga);
+            }
         }
     }
     /* trio part: real centres for the energy, all centres (ghost: real j) for the forces */
@@ -983,6 +1283,17 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
                 real val, gr[3], q[10];
                 spline3(tv, tc[t], rd, r, &val, gr, want_m ? q : NULL);
                 if (!ghost) { e += val; if (want_m) em += (double)mag_value(q, r); }
+                if (sk && !ghost) {
+                    term_t tm = {.nl = 3, .ns = 3, .legs = {{0, 1}, {0, 2}, {1, 2}}, .r = {r[0], r[1], r[2]},
+                                .rho = {r[0], r[1], r[0] + r[1]}, .g = {gr[0], gr[1], gr[2]}, .ga = {q[1], q[2], q[3]},
+                                .Ka = {{q[4], q[5], q[6]}, {q[5], q[7], q[8]}, {q[6], q[8], q[9]}}};
+                    int par[3] = {i, j % N, k % N};
+                    for (int c3 = 0; c3 < 3; c3++) {
+                        tm.d[0][c3] = (real)rj[c3] - ri[c3]; tm.d[1][c3] = (real)rk[c3] - ri[c3]; tm.d[2][c3] = (real)rk[c3] - rj[c3];
+                    }
+                    if (sk->H) spline3_d2(tv, tc[t], rd, r, &tm);
+                    sink_term(sk, i, par, &tm, val, mag_value(q, r));
+                }
                 if (virial6 && !ghost) {          /* legs ij, ik, jk of the centre's own triplet */
                     strain_add(virial6, NULL, gr[0], 0.0, ri, rj, r[0]);
                     strain_add(virial6, NULL, gr[1], 0.0, ri, rk, r[1]);
@@ -1023,18 +1334,51 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
 /* (energy, forces, virial6 are `real`: double in libuf3oracle.so) */
 int uf3o_eval(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
               real *energy, real *forces) {
-    return eval_worker(s, f, c1, c2, c3, energy, forces, NULL, NULL, NULL, NULL);
+    return eval_worker(s, f, c1, c2, c3, energy, forces, NULL, NULL, NULL, NULL, NULL);
 }
 
 /* uf3o_eval plus the strain derivative virial6 [6] (eV, Voigt xx, yy, zz, yz, xz, xy; stress = virial6 / volume) */
 int uf3o_eval_virial(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
                      real *energy, real *forces, real *virial6) {
-    return eval_worker(s, f, c1, c2, c3, energy, forces, virial6, NULL, NULL, NULL);
+    return eval_worker(s, f, c1, c2, c3, energy, forces, virial6, NULL, NULL, NULL, NULL);
 }
 
 /* uf3o_eval_virial plus the magnitudes me [1], mf [N][3], mv [6] */
 int uf3o_eval_x(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
                 real *energy, real *forces, real *virial6, double *me, double *mf, double *mv) {
-    return eval_worker(s, f, c1, c2, c3, energy, forces, virial6, me, mf, mv);
+    return eval_worker(s, f, c1, c2, c3, energy, forces, virial6, me, mf, mv, NULL);
 }
 
+
+/*
+ * Site terms (uf3_flux.h's partition; the evaluator's own term loop with per-centre outputs): U [N] the one-body term of i, its
+ * directed pair terms and the triplets it is the centre of; W [N][9], W_i[a][b] = sum_terms sum_s d_s[a] (dU_i / dr_s)[b] over the
+ * neighbour images s of a term, d_s from the centre to the image; J [N][3] (with vel [N][3], else NULL), each centre's share of
+ * J_pot = -sum_terms sum_s d_s (dU_i / dr_s . v_s), an image carrying its parent's velocity.  mU, mW, mJ: the magnitudes.
+ * Also the frame's energy and its magnitude (energy, me: the sums the same loop makes).  sc_r: as uf3o_site_rows_x.
+ */
+int uf3o_site_terms_x(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3, double sc_r,
+                      const double *vel, real *U, real *W, real *J, double *mU, double *mW, double *mJ, real *energy, double *me) {
+    int N = f->n_atoms;
+    sink_t k = {.sc_r = sc_r, .n = N, .vel = vel, .U = U, .W = W, .J = vel ? J : NULL, .mU = mU, .mW = mW, .mJ = mJ};
+    for (int q = 0; q < N; q++) { U[q] = 0.0; mU[q] = 0.0; }
+    for (int q = 0; q < 9 * N; q++) { W[q] = 0.0; mW[q] = 0.0; }
+    if (k.J) for (int q = 0; q < 3 * N; q++) { J[q] = 0.0; mJ[q] = 0.0; }
+    return eval_worker(s, f, c1, c2, c3, energy, NULL, NULL, me, NULL, NULL, &k);
+}
+
+/*
+ * Second derivatives of the evaluator's energy (uf3_hessian.h: real i with every image j in the pair range, real centres with
+ * unordered pairs of their 3-body neighbours; an image moves with its parent, par = supercell index mod N): H [3N][3N],
+ * mixed [3N][6] = d2E / dx dt_v, born [6][6] = d2E / dt_u dt_v at fixed fractional coordinates (t the strain of
+ * uf3o_eval_virial), and their magnitudes.  mixed / born may be NULL (each with its magnitude).
+ */
+int uf3o_hessian_x(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3, double sc_r,
+                   real *H, real *mixed, real *born, double *mH, double *mL, double *mB) {
+    size_t n3 = 3 * (size_t)f->n_atoms;
+    sink_t k = {.sc_r = sc_r, .n = f->n_atoms, .H = H, .L = mixed, .B = born, .mH = mH, .mL = mL, .mB = mB};
+    for (size_t q = 0; q < n3 * n3; q++) { H[q] = 0.0; mH[q] = 0.0; }
+    if (mixed) for (size_t q = 0; q < n3 * 6; q++) { mixed[q] = 0.0; mL[q] = 0.0; }
+    if (born) for (int q = 0; q < 36; q++) { born[q] = 0.0; mB[q] = 0.0; }
+    return eval_worker(s, f, c1, c2, c3, NULL, NULL, NULL, NULL, NULL, NULL, &k);
+}

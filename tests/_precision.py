@@ -14,6 +14,11 @@ The bound.  ``RHO_O`` records, per kind of output, the worst ratio of the **fp64
 tiled positions (local cubic pieces, FMA contraction, ``fast_rcp`` and ``norm3_leg`` at about an ulp each, another order of
 summation), each a bounded number of extra roundings per term.  The bound is never derived from a device result.
 
+The second-derivative and per-centre kinds -- ``H``, ``mixed``, ``born`` (k_hessian; ``oracle.hessian_x``), ``U``, ``W``, ``jp``
+(k_flux_site_terms; ``oracle.site_terms_x``) and ``b`` (k_site_rows; ``oracle.site_rows_x``) -- are held in the same way, by the
+same rule: ``reference(name)`` computes them on first use.  Those three kernels describe the frame with every atom counted as
+its image inside the cell, and so do these oracle entries (``oracle.supercell_radius``).
+
 One documented design choice is not a bounded number of roundings per term: the launches that evaluate leg functions from
 local cubic pieces in powers of ``x - t_i`` (k_featurize3, the grouped matrix-core launch) carry Horner's absolute error on
 values that are themselves tiny.  For those routes alone M is the oracle's widened one (``ratios(..., pieces=True)``;
@@ -35,11 +40,17 @@ from test_feat3_pad_clamp import CELLS, ELEMENTS, _basis as clamp_basis, _frame 
 
 U = np.longdouble(2.0) ** -53
 KINDS = ("xe", "xf", "xv", "e", "f", "v")        # energy rows, force rows, virial rows; energies, forces, virials
+# Hessian, mixed position / strain derivatives, clamped-ion strain term; site energies, site virials, each centre's share of J_pot;
+# site rows
+KINDS_D2 = ("H", "mixed", "born", "U", "W", "jp", "b")
 
 # Worst ratio of the fp64 oracle (libuf3oracle.so) against the extended build over CASES, per kind, as printed by
 # tests/test_precision_host.py::test_fp64_oracle_stays_within_the_recorded_table.  Measured 2026-10-20 (x86-64, gcc -O2
 # -ffp-contract=off, 80-bit long double): xe 1.33, xf 1.77, xv 1.35, e 0.529, f 0.252, v 0.349 -- recorded rounded up.
 RHO_O = {"xe": 1.5, "xf": 2.0, "xv": 1.5, "e": 0.6, "f": 0.3, "v": 0.4}
+# The same for KINDS_D2, as printed by tests/test_precision_host.py::test_fp64_oracle_stays_within_the_recorded_table_d2.
+# Measured 2026-10-20 (the same build): H 0.968, mixed 0.308, born 0.243, U 0.175, W 0.378, jp 0.253, b 1.66 -- recorded rounded up.
+RHO_O.update({"H": 1.0, "mixed": 0.4, "born": 0.3, "U": 0.2, "W": 0.4, "jp": 0.3, "b": 2.0})
 GAMMA = {k: 16.0 * max(v, 1.0) for k, v in RHO_O.items()}
 
 
@@ -60,11 +71,15 @@ def ratio(got, truth, M):
 
 
 # ------------------------------------------------------------------------------------------------ frames clear of steps
-def clear_of_discontinuities(basis, atoms, eps=1e-9):
+def clear_of_discontinuities(basis, atoms, eps=1e-9, second=False):
     """No distance of the frame lies within ``eps`` of a point where the rows are discontinuous in it: a pair ``r_min`` or
     ``r_max``, the ends of the 3-body list range, and an end of a leg (centre legs and ``r_jk``) whose kept functions do not
     vanish there -- an untrimmed leading end, or a trailing end trimmed by fewer than 3.  (Interior knots need no clearance: a
-    cubic spline is C2 there.)  Returns the smallest clearance found; raises AssertionError otherwise."""
+    cubic spline is C2 there.)  ``second``: for the second-derivative kinds (H, mixed, born) a leg end is a step wherever a kept
+    function's SECOND derivative does not vanish there: a leading or a trailing end trimmed by fewer than 3 (at an end knot of
+    multiplicity 4 the q-th function from the end vanishes like the q-th power of the distance from it).  A pair ``r_max``
+    trimmed by 3 is no step for them either; ``r_min`` and ``r_max`` are cleared as steps in any case.
+    Returns the smallest clearance found; raises AssertionError otherwise."""
     ob = O.OracleBasis(basis)
     pos, _, _ = O.supercell(atoms, basis.r_cut)
     n = len(atoms)
@@ -85,7 +100,7 @@ def clear_of_discontinuities(basis, atoms, eps=1e-9):
     ends = set()
     for ks in seqs:
         for k in ks:
-            if lead == 0:
+            if lead == 0 or (second and lead < 3):
                 ends.add(float(k[0]))
             if trail < 3:
                 ends.add(float(k[-1]))
@@ -176,11 +191,48 @@ def cases():
     return out
 
 
+def velocities(name):
+    """the seeded velocities [N, 3] (Angstrom / fs) the heat current of a case is taken at"""
+    n = len(cases()[name][1])
+    return np.random.default_rng(1000 + sorted(cases()).index(name)).normal(0.0, 0.01, (n, 3))
+
+
+_D2_GROUPS = (("H", "mixed", "born"), ("U", "W", "jp"), ("b",))
+
+
+def _d2(name, ob, coeff, kind, extended=True):
+    """(values, magnitudes) of the group of KINDS_D2 that holds ``kind``, from the extended (or the fp64) oracle"""
+    basis, atoms, _ = cases()[name]
+    if kind in _D2_GROUPS[0]:
+        return O.hessian_x(ob, atoms, coeff, strain=True, extended=extended)
+    if kind in _D2_GROUPS[1]:
+        val, mag = O.site_terms_x(ob, atoms, coeff, velocities(name), extended=extended)
+        return {k: val[k] for k in _D2_GROUPS[1]}, {k: mag[k] for k in _D2_GROUPS[1]}
+    val, mag = O.site_rows_x(ob, atoms, extended=extended)
+    return {"b": val["b"]}, {"b": mag["b"]}
+
+
+class _Lazy(dict):
+    """values (or magnitudes) of a case: the keys of KINDS from the start, a group of KINDS_D2 computed when one of its keys is
+    first asked for -- once per case, into both dicts, read-only"""
+
+    def __init__(self, first, fill):
+        super().__init__(first)
+        self._fill = fill
+
+    def __missing__(self, key):
+        if key not in KINDS_D2:
+            raise KeyError(key)
+        self._fill(key)
+        return dict.__getitem__(self, key)
+
+
 @functools.lru_cache(maxsize=None)
 def reference(name):
     """(ob, coefficients, values, magnitudes) of a case from the extended oracle, computed once and shared (read-only): the keys
-    of KINDS, rows from ``featurize_x(virial=True)``, e / f / v from ``evaluate_x``.  ``magnitudes["pieces"]`` holds the row
-    magnitudes widened for the routes that evaluate leg functions from local cubic pieces (``ratios(..., pieces=True)``)."""
+    of KINDS, rows from ``featurize_x(virial=True)``, e / f / v from ``evaluate_x``; and, computed on first use, the keys of
+    KINDS_D2 from ``hessian_x``, ``site_terms_x`` (at ``velocities(name)``) and ``site_rows_x``.  ``magnitudes["pieces"]`` holds
+    the row magnitudes widened for the routes that evaluate leg functions from local cubic pieces (``ratios(..., pieces=True)``)."""
     basis, atoms, _ = cases()[name]
     assert len(atoms) <= 130
     clear_of_discontinuities(basis, atoms)
@@ -198,6 +250,18 @@ def reference(name):
         for v in d.values():
             if isinstance(v, np.ndarray):
                 v.setflags(write=False)
+
+    def fill(kind):
+        if kind in _D2_GROUPS[0]:
+            clear_of_discontinuities(basis, atoms, second=True)
+        v2, m2 = _d2(name, ob, coeff, kind)
+        for k in v2:
+            v2[k].setflags(write=False)
+            m2[k].setflags(write=False)
+            dict.__setitem__(val, k, v2[k])
+            dict.__setitem__(mag, k, m2[k])
+
+    val, mag = _Lazy(val, fill), _Lazy(mag, fill)
     return ob, coeff, val, mag
 
 
@@ -213,6 +277,12 @@ def fp64_oracle(name):
             "pair_cnt": xv["pair_cnt"], "n3_cnt": xv["n3_cnt"]}
 
 
+def fp64_oracle_d2(name, kind):
+    """the fp64 build's results of the group of KINDS_D2 that holds ``kind``"""
+    ob, coeff, _, _ = reference(name)
+    return _d2(name, ob, coeff, kind, extended=False)[0]
+
+
 def ratios(got, name, kinds=None, pieces=False):
     """{kind: ratio} of the results ``got`` (a dict with keys of KINDS) of a case against its reference.  ``pieces``: the rows
     come from a route that evaluates the 3-body leg functions from local cubic pieces in powers of the distance from the
@@ -221,7 +291,7 @@ def ratios(got, name, kinds=None, pieces=False):
     _, _, val, mag = reference(name)
     if pieces:
         mag = {**mag, **mag["pieces"]}
-    return {k: ratio(got[k], val[k], mag[k]) for k in (kinds or KINDS) if k in got and got[k] is not None}
+    return {k: ratio(got[k], val[k], mag[k]) for k in (kinds or KINDS + KINDS_D2) if k in got and got[k] is not None}
 
 
 def fmt(r):

@@ -1,11 +1,14 @@
 #!/usr/bin/env python
 """
-Collect the ``[precision] route, case: kind ratio, ...`` lines of a ``pytest -s tests/test_gpu_precision.py`` run into
-``profiles/precision_ratios.json``: route by case by kind, the worst ratio where a line repeats, beside the bound the run was
-held to.  A ratio is ``max |device - extended oracle| / (2^-53 M)`` over every entry of a result (tests/_precision.py).
+Collect the ``[precision] route, case: kind ratio, ...`` lines of a ``pytest -s tests/test_gpu_precision.py
+tests/test_gpu_precision_d2.py`` run into ``profiles/precision_ratios.json``: route by case by kind, the worst ratio where a line
+repeats, beside the bound the run was held to.  A ratio is ``max |device - extended oracle| / (2^-53 M)`` over every entry of a
+result (tests/_precision.py).  Several logs may be given (one per test file, say): their routes are merged.
 
-    python -m pytest -m gpu -s tests/test_gpu_precision.py | tee precision.log
+    python -m pytest -m gpu -s tests/test_gpu_precision.py tests/test_gpu_precision_d2.py | tee precision.log
     python tools/precision_ratios.py precision.log [-o profiles/precision_ratios.json]
+
+``--update`` keeps the routes already in the output file that the logs do not mention (a run of one of the two test files).
 """
 import argparse
 import json
@@ -34,6 +37,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("log", nargs="+")
     ap.add_argument("-o", "--out", default=os.path.join(ROOT, "profiles", "precision_ratios.json"))
+    ap.add_argument("--update", action="store_true", help="keep the output file's routes that the logs do not mention")
     args = ap.parse_args()
     lines = []
     for path in args.log:
@@ -42,6 +46,9 @@ def main():
     routes = collect(lines)
     if not routes:
         sys.exit("no [precision] lines found")
+    if args.update and os.path.exists(args.out):
+        with open(args.out) as f:
+            routes = {**json.load(f)["routes"], **routes}
     sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
     import _precision as P
     worst = {}
@@ -50,7 +57,9 @@ def main():
             for k, v in kinds.items():
                 worst[k] = max(worst.get(k, 0.0), v)
     doc = {"what": "worst |device - extended oracle| / (2^-53 M) over every entry, per route, case and kind of output "
-                   "(xe, xf, xv: energy, force, virial rows; e, f, v: energy, forces, virial); tests/test_gpu_precision.py",
+                   "(xe, xf, xv: energy, force, virial rows; e, f, v: energy, forces, virial: tests/test_gpu_precision.py; "
+                   "H, mixed, born: Hessian, position / strain and strain / strain derivatives; U, W, jp: site energies, site "
+                   "virials, the heat current's potential part; b: site rows: tests/test_gpu_precision_d2.py)",
            "rho_o": P.RHO_O, "gamma": P.GAMMA, "worst": worst, "routes": routes}
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1, sort_keys=True)
