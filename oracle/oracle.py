@@ -9,7 +9,7 @@ The basis description is read from any object exposing the reference's
 reference's own class (golden capture) and on ``uf3_amd``'s.
 
 The C source builds twice: ``libuf3oracle.so`` (fp64; ``featurize``, ``evaluate``) and ``libuf3oracle_x.so`` (``long double``
-values on fp64 decisions; ``featurize_x``, ``evaluate_x``, ``hessian_x``, ``site_terms_x``, ``site_rows_x``, which also return the magnitude M of every
+values on fp64 decisions; ``featurize_x``, ``evaluate_x``, ``hessian_x``, ``site_terms_x``, ``site_rows_x``, ``mc_delta_x``, which also return the magnitude M of every
 entry -- see uf3_oracle.c and tests/_precision.py).
 """
 import ctypes as C
@@ -59,7 +59,7 @@ def build(force=False, name="libuf3oracle.so"):
 def _load(name):
     so = C.CDLL(build(name=name))
     for f in ("uf3o_featurize", "uf3o_featurize_x", "uf3o_eval", "uf3o_eval_virial", "uf3o_eval_x", "uf3o_real_mant_dig",
-              "uf3o_hessian_x", "uf3o_site_terms_x", "uf3o_site_rows_x"):
+              "uf3o_hessian_x", "uf3o_site_terms_x", "uf3o_site_rows_x", "uf3o_mc_delta_x", "uf3o_mc_terms_x"):
         getattr(so, f).restype = C.c_int
     so.uf3o_supercell.restype = C.c_int64
     return so
@@ -193,14 +193,14 @@ def featurize_x(ob, atoms, virial=False, extended=True, pieces=False):
     return _rows_x(lib(), np.float64, ob, atoms, virial, pieces)
 
 
-def evaluate_x(ob, atoms, coefficients, virial=True, extended=True):
+def evaluate_x(ob, atoms, coefficients, virial=True, extended=True, forces=True):
     """``evaluate`` from the extended build: ``(values, magnitudes)``, dicts with keys ``e`` (scalar), ``f`` [N,3] and, with
-    ``virial=True``, ``v`` [6]; see ``featurize_x``."""
+    ``virial=True``, ``v`` [6]; see ``featurize_x``.  ``forces=False`` (with ``virial=False``): the energy alone, ``f`` None."""
     so, dtype = (lib_x(), np.longdouble) if extended else (lib(), np.float64)
     c1, c2, c3 = split_coefficients(ob, coefficients)
     fv = _FrameView(atoms)
-    e, f, v = np.zeros(1, dtype), np.zeros((fv.c.n_atoms, 3), dtype), np.zeros(6, dtype) if virial else None
-    me, mf, mv = np.zeros(1), np.zeros((fv.c.n_atoms, 3)), np.zeros(6) if virial else None
+    e, f, v = np.zeros(1, dtype), np.zeros((fv.c.n_atoms, 3), dtype) if forces else None, np.zeros(6, dtype) if virial else None
+    me, mf, mv = np.zeros(1), np.zeros((fv.c.n_atoms, 3)) if forces else None, np.zeros(6) if virial else None
     rc = so.uf3o_eval_x(C.byref(ob.spec), C.byref(fv.c), _ptr(c1), _ptr(c2), _ptr(c3), _ptr(e), _ptr(f), _ptr(v),
                         _ptr(me), _ptr(mf), _ptr(mv))
     if rc:
@@ -287,6 +287,61 @@ def site_rows_x(ob, atoms, extended=True):
     if rc:
         raise RuntimeError(f"uf3o_site_rows_x rc={rc}")
     return val, mag
+
+
+MC_MODES = {"swap": 0, "transmute": 1}
+MC_TERM_FIELDS = ("pass", "kind", "centre", "p1", "p2", "value", "magnitude", "distance", "legs_exchanged", "leg_fp32", "r_ij", "r_ik")
+
+
+def _mc_second(mode, j_or_species):
+    """the second column of a move list as int32: atom indices (swap) or atomic numbers (transmute; symbols accepted)"""
+    if MC_MODES[mode] == 0:
+        return np.ascontiguousarray(j_or_species, dtype=np.int32).reshape(-1)
+    return np.ascontiguousarray([_Z[q] if isinstance(q, str) else int(q) for q in np.atleast_1d(j_or_species)], dtype=np.int32)
+
+
+def mc_delta_x(ob, atoms, coefficients, i, j_or_species, mode, extended=True):
+    """Energy differences of Monte Carlo moves on the frame's species (uf3_mc.h's definition; uf3_oracle.c: uf3o_mc_delta_x):
+    ``mode`` "swap" exchanges the species of atoms ``i[k]`` and ``j_or_species[k]``, "transmute" gives atom ``i[k]`` the element
+    ``j_or_species[k]`` (symbol or atomic number).  Returns ``(dE, M)``, both [n_moves]: dE the sum of the terms that contain a
+    moved atom for the new species minus for the old ones (``np.longdouble``; float64 with ``extended=False``), M the sum of
+    those terms' magnitudes over both assignments.  A move that changes nothing has dE = M = 0 exactly."""
+    so, dtype = _kind(extended)
+    c1, c2, c3 = split_coefficients(ob, coefficients)
+    fv = _FrameView(atoms)
+    a = np.ascontiguousarray(i, dtype=np.int32).reshape(-1)
+    b = _mc_second(mode, j_or_species)
+    if len(a) != len(b):
+        raise ValueError("mc_delta_x: as many first atoms as second atoms or species")
+    dE, M = np.zeros(len(a), dtype), np.zeros(len(a))
+    rc = so.uf3o_mc_delta_x(C.byref(ob.spec), C.byref(fv.c), _ptr(c1), _ptr(c2), _ptr(c3), C.c_int64(len(a)), _ptr(a), _ptr(b),
+                            C.c_int(MC_MODES[mode]), _ptr(dE), _ptr(M))
+    if rc:
+        raise RuntimeError(f"uf3o_mc_delta_x rc={rc}")
+    return dE, M
+
+
+def mc_terms_x(ob, atoms, coefficients, i, j_or_species, mode, extended=False):
+    """One move with the terms it is made of: ``(dE, M, terms)``, ``terms`` [n, len(MC_TERM_FIELDS)] float64 in the order of the
+    oracle's term loop, the pass over the old species (``pass`` 0) before the pass over the new ones (1).  ``kind``: 1 one-body,
+    2 directed pair term, 3 triplet; ``centre``, ``p1``, ``p2``: the parent atoms (-1: none); ``distance``: the pair distance, or
+    r_jk of a triplet; ``legs_exchanged`` / ``leg_fp32``: the triplet's value with its l and m leg lengths exchanged / with its l
+    leg length rounded through fp32 (for planted defects); ``r_ij``, ``r_ik``: a triplet's centre legs in the order (l, m).  dE = sum(value | pass 1) - sum(value | pass 0) up to summation order."""
+    so, dtype = _kind(extended)
+    c1, c2, c3 = split_coefficients(ob, coefficients)
+    fv = _FrameView(atoms)
+    second = int(_mc_second(mode, [j_or_species])[0])
+    dE, M, n = np.zeros(1, dtype), np.zeros(1), np.zeros(1, dtype=np.int64)
+    cap = 0
+    while True:
+        terms = np.zeros((max(cap, 1), len(MC_TERM_FIELDS)))
+        rc = so.uf3o_mc_terms_x(C.byref(ob.spec), C.byref(fv.c), _ptr(c1), _ptr(c2), _ptr(c3), C.c_int(int(i)), C.c_int(second),
+                                C.c_int(MC_MODES[mode]), _ptr(dE), _ptr(M), _ptr(terms), C.c_int64(len(terms)), _ptr(n))
+        if rc:
+            raise RuntimeError(f"uf3o_mc_terms_x rc={rc}")
+        if int(n[0]) <= len(terms):
+            return dE[0], M[0], terms[:int(n[0])].copy()
+        cap = int(n[0])
 
 
 def featurize(ob, atoms, energy=True, forces=True, indices=False):

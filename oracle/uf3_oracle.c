@@ -585,7 +585,7 @@ static int leg_values(const trio_view *v, int d, double rd, real r, int lead, in
 static real wprod(real a, real ma, real b, real mb, real c, real mc) {
     return a * b * c + (ma - a) * b * c + a * (mb - b) * c + a * b * (mc - c);
 }
-static void q_add(real *q, real c, const leg_t *l, const leg_t *m, const leg_t *n, int x, int y, int w) {
+static void q_add_n(real *q, real c, const leg_t *l, const leg_t *m, const leg_t *n, int x, int y, int w, int nq) {
 #define F0(g, i) g->v[i], g->m0[i]
 #define F1(g, i) g->a1[i], g->m1[i]
 #define F2(g, i) g->a2[i], g->m2[i]
@@ -593,6 +593,7 @@ static void q_add(real *q, real c, const leg_t *l, const leg_t *m, const leg_t *
     q[1] += c * wprod(F1(l, x), F0(m, y), F0(n, w));
     q[2] += c * wprod(F0(l, x), F1(m, y), F0(n, w));
     q[3] += c * wprod(F0(l, x), F0(m, y), F1(n, w));
+    if (nq <= 4) return;                  /* (a caller that takes mag_value alone: the value and the three first partials) */
     q[4] += c * wprod(F2(l, x), F0(m, y), F0(n, w));
     q[5] += c * wprod(F1(l, x), F1(m, y), F0(n, w));
     q[6] += c * wprod(F1(l, x), F0(m, y), F1(n, w));
@@ -602,6 +603,9 @@ static void q_add(real *q, real c, const leg_t *l, const leg_t *m, const leg_t *
 #undef F0
 #undef F1
 #undef F2
+}
+static void q_add(real *q, real c, const leg_t *l, const leg_t *m, const leg_t *n, int x, int y, int w) {
+    q_add_n(q, c, l, m, n, x, y, w, 10);
 }
 /* M of an energy term V(r_ij, r_ik, r_jk): |V|_abs + sum_legs rho_leg |dV/dr_leg|_abs, rho = (r_ij, r_ik, r_ij + r_ik) */
 static real mag_value(const real *q, const real *r) {
@@ -928,7 +932,7 @@ int64_t uf3o_supercell(const uf3o_frame *f, double r_cut, double *pos_out, int *
 /* ------------------------------------------------------------- evaluator */
 /* tensor-product cubic spline value / first partials from a full coefficient grid; q (may be NULL): the magnitudes of q_add,
    summed over the 64 products with |coefficient| */
-static void spline3(const trio_view *tv, const double *c, const double *rd, const real *r, real *val, real *grad, real *q) {
+static void spline3_n(const trio_view *tv, const double *c, const double *rd, const real *r, real *val, real *grad, real *q, int nq) {
     leg_t gl, gm, gn;
     int L = tv->dim[0], M = tv->dim[1], N = tv->dim[2];
     int il = leg_values(tv, 0, rd[0], r[0], 0, 0, &gl, 1, q != NULL), im = leg_values(tv, 1, rd[1], r[1], 0, 0, &gm, 1, q != NULL),
@@ -944,9 +948,12 @@ static void spline3(const trio_view *tv, const double *c, const double *rd, cons
         g0 += cc * dl[x] * vm[y] * vn[w];
         g1 += cc * vl[x] * dm[y] * vn[w];
         g2 += cc * vl[x] * vm[y] * dn[w];
-        if (q) q_add(q, rabs(cc), &gl, &gm, &gn, x, y, w);
+        if (q) q_add_n(q, rabs(cc), &gl, &gm, &gn, x, y, w, nq);
     }
     *val = v; grad[0] = g0; grad[1] = g1; grad[2] = g2;
+}
+static void spline3(const trio_view *tv, const double *c, const double *rd, const real *r, real *val, real *grad, real *q) {
+    spline3_n(tv, c, rd, r, val, grad, q, 10);
 }
 
 /* virial6 += g * r (x) r / |r| for one energy term g(|r|) of the bond vector r (Voigt); m6 (may be NULL) += gm |r_a r_b| / |r| */
@@ -999,7 +1006,43 @@ typedef struct {
     double *mU, *mW, *mJ;
     real *H, *L, *B;                   /* [3N][3N], [3N][6], [6][6]; NULL: not wanted */
     double *mH, *mL, *mB;
+    struct touch_s *mc;                /* the terms that contain an atom of a Monte Carlo move (uf3o_mc_delta_x); NULL: not wanted */
 } sink_t;
+
+/*
+ * ---- the terms a Monte Carlo move touches (uf3o_mc_delta_x; uf3_mc.h) ---------------------------------------------------------
+ * touch [N]: 1 for the real atoms of T.  The term loop hands over every term whose parent atoms (centre included) contain an atom
+ * of T, and no other: E and M are the sums of their values and of their magnitudes mval, in the loop's own order.  Terms without
+ * an atom of T are skipped before they are evaluated, and so are the centres that cannot reach T (the lists are symmetric under
+ * lattice translations: a centre has an image of t within the list range exactly when t has an image of the centre within it).
+ * rec (may be NULL): one record of UF3O_MC_TERM_W doubles per term, for the planted defects of tests/test_mc_precision_host.py:
+ *   pass (0 old species, 1 new) | kind (1 one-body, 2 pair, 3 triplet) | centre | parent of slot 1 | parent of slot 2 (-1) |
+ *   value | magnitude | distance (pair: d; triplet: r_jk) | the triplet with its l and m leg lengths exchanged | the triplet with
+ *   its l leg length rounded through fp32 | r_ij | r_ik (triplets; 0 otherwise)
+ */
+#define UF3O_MC_TERM_W 12
+typedef struct touch_s {
+    const unsigned char *touch;
+    unsigned char *reach;              /* [N] scratch: centres with an image of an atom of T within the list range */
+    real E;
+    double M;
+    int pass;
+    double *rec;
+    int64_t n_rec, cap;
+    double x_d, x_swap, x_f32, x_ra, x_rb; /* the extra fields of the term about to be handed over */
+} touch_t;
+
+static void touch_term(touch_t *m, int kind, int i, int p1, int p2, real val, real mval) {
+    m->E += val; m->M += (double)mval;
+    if (m->rec) {
+        if (m->n_rec < m->cap) {
+            double *o = m->rec + UF3O_MC_TERM_W * (size_t)m->n_rec;
+            o[0] = m->pass; o[1] = kind; o[2] = i; o[3] = p1; o[4] = p2; o[5] = (double)val; o[6] = (double)mval;
+            o[7] = m->x_d; o[8] = m->x_swap; o[9] = m->x_f32; o[10] = m->x_ra; o[11] = m->x_rb;
+        }
+        m->n_rec++;
+    }
+}
 
 static real m1_of(const term_t *t, const real *wa) {
     real m = 0.0;
@@ -1043,6 +1086,7 @@ static void strain_dir(int v, const real *d, real *o) {
 /* one term of centre i into the sinks; par[s]: the parent atom of slot s; val, mval: the term's value and its magnitude */
 static void sink_term(const sink_t *k, int i, const int *par, const term_t *t, real val, real mval) {
     int nl = t->nl, ns = t->ns, N = k->n;
+    if (k->mc) { touch_term(k->mc, t->ns, i, par[1], t->ns > 2 ? par[2] : -1, val, mval); return; }
     real u[3][3], sg[3][3] = {{0}};
     for (int q = 0; q < nl; q++) {
         for (int c = 0; c < 3; c++) u[q][c] = t->d[q][c] / t->r[q];
@@ -1196,6 +1240,20 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
     if (mv) memset(mv, 0, sizeof(double) * 6);
     for (int a = 0; a < N; a++) { e += c1[species_index(s, f->z[a])]; em += fabs(c1[species_index(s, f->z[a])]); }
     if (sk && sk->U) for (int a = 0; a < N; a++) { sk->U[a] += c1[species_index(s, f->z[a])]; sk->mU[a] += fabs(c1[species_index(s, f->z[a])]); }
+    touch_t *mc = sk ? sk->mc : NULL;
+    if (mc) {
+        int *cd = NULL, ccap = 0;
+        for (int a = 0; a < N; a++) mc->reach[a] = mc->touch[a];
+        for (int a = 0; a < N; a++) {
+            if (!mc->touch[a]) continue;
+            mc->x_d = mc->x_swap = mc->x_f32 = mc->x_ra = mc->x_rb = 0.0;
+            touch_term(mc, 1, a, -1, -1, c1[species_index(s, f->z[a])], fabs(c1[species_index(s, f->z[a])]));
+            int nc = gather_candidates(&sc, &g, sc.pos + 3 * (size_t)a, &cd, &ccap);
+            for (int c = 0; c < nc; c++)
+                if (dist3(sc.pos + 3 * (size_t)a, sc.pos + 3 * (size_t)cd[c]) <= h * (1.0 + 1e-9)) mc->reach[cd[c] % N] = 1;
+        }
+        free(cd);
+    }
     /* pair part */
     const double **pk = (const double **)malloc(sizeof(double *) * (size_t)(s->n_pairs + 1));
     const double **pc = (const double **)malloc(sizeof(double *) * (size_t)(s->n_pairs + 1));
@@ -1203,11 +1261,13 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
       for (int p = 0; p < s->n_pairs; p++) { pk[p] = kp; pc[p] = cp; kp += s->pair_nk[p]; cp += s->pair_nk[p] - 4; } }
     int *cand = NULL, cap = 0;
     for (int i = 0; i < N; i++) {
+        if (mc && !mc->reach[i]) continue;
         const double *ri = sc.pos + 3 * (size_t)i;
         int nc = gather_candidates(&sc, &g, ri, &cand, &cap);
         for (int c = 0; c < nc; c++) {
             int j = cand[c], p = pair_index(s, sc.z[i], sc.z[j]);
             if (p < 0) continue;
+            if (mc && !(mc->touch[i] || mc->touch[j % N])) continue;
             const double *rj = sc.pos + 3 * (size_t)j;
             double d = dist3(ri, rj), rmin = s->pair_rmin[p] > 0 ? s->pair_rmin[p] : 0.0;
             if (!(d > rmin && d < s->pair_rmax[p])) continue;
@@ -1242,6 +1302,7 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
                             .ga = {ga}, .Ka = {{ha}}, .Ta = {{{ta}}}};
                 int par[2] = {i, j % N};
                 for (int c3 = 0; c3 < 3; c3++) t.d[0][c3] = (real)rj[c3] - ri[c3];
+                if (mc) { mc->x_d = d; mc->x_swap = mc->x_f32 = mc->x_ra = mc->x_rb = 0.0; }
                 sink_term(sk, i, par, &t, phi, pa + dr * ga);
             }
         }
@@ -1253,6 +1314,7 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
         int *nbr = NULL, nbr_cap = 0; double *nbr_d = NULL;
         int n_centres = forces ? sc.m : N;
         for (int i = 0; i < n_centres; i++) {
+            if (mc && !mc->reach[i % N]) continue;
             const double *ri = sc.pos + 3 * (size_t)i;
             int nc = gather_candidates(&sc, &g, ri, &cand, &cap), nn = 0;
             for (int c = 0; c < nc; c++) {
@@ -1267,6 +1329,7 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
                 int j = nbr[a], k = nbr[b];
                 if (!(j < k)) continue;
                 if (ghost && j >= N) continue;
+                if (mc && !(mc->touch[i % N] || mc->touch[j % N] || mc->touch[k % N])) continue;
                 double rij = nbr_d[a], rik = nbr_d[b];
                 int zj = sc.z[j], zk = sc.z[k];
                 if (zj > zk) { int ti = j; j = k; k = ti; ti = zj; zj = zk; zk = ti; double td = rij; rij = rik; rik = td; }
@@ -1281,7 +1344,7 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
                 double rd[3] = {rij, rik, rjk};
                 real r[3] = {rdist3(ri, rj), rdist3(ri, rk), rdist3(rj, rk)};
                 real val, gr[3], q[10];
-                spline3(tv, tc[t], rd, r, &val, gr, want_m ? q : NULL);
+                spline3_n(tv, tc[t], rd, r, &val, gr, want_m ? q : NULL, mc ? 4 : 10);
                 if (!ghost) { e += val; if (want_m) em += (double)mag_value(q, r); }
                 if (sk && !ghost) {
                     term_t tm = {.nl = 3, .ns = 3, .legs = {{0, 1}, {0, 2}, {1, 2}}, .r = {r[0], r[1], r[2]},
@@ -1292,6 +1355,13 @@ static int eval_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1
                         tm.d[0][c3] = (real)rj[c3] - ri[c3]; tm.d[1][c3] = (real)rk[c3] - ri[c3]; tm.d[2][c3] = (real)rk[c3] - rj[c3];
                     }
                     if (sk->H) spline3_d2(tv, tc[t], rd, r, &tm);
+                    if (mc && mc->rec) {        /* the planted defects' variants of this triplet */
+                        double rd_s[3] = {rd[1], rd[0], rd[2]}, rd_f[3] = {(double)(float)rd[0], rd[1], rd[2]};
+                        real r_s[3] = {r[1], r[0], r[2]}, r_f[3] = {(real)rd_f[0], r[1], r[2]}, vx, gx[3];
+                        mc->x_d = rjk; mc->x_ra = rij; mc->x_rb = rik;
+                        spline3(tv, tc[t], rd_s, r_s, &vx, gx, NULL); mc->x_swap = (double)vx;
+                        spline3(tv, tc[t], rd_f, r_f, &vx, gx, NULL); mc->x_f32 = (double)vx;
+                    }
                     sink_term(sk, i, par, &tm, val, mag_value(q, r));
                 }
                 if (virial6 && !ghost) {          /* legs ij, ik, jk of the centre's own triplet */
@@ -1381,4 +1451,84 @@ int uf3o_hessian_x(const uf3o_spec *s, const uf3o_frame *f, const double *c1, co
     if (mixed) for (size_t q = 0; q < n3 * 6; q++) { mixed[q] = 0.0; mL[q] = 0.0; }
     if (born) for (int q = 0; q < 36; q++) { born[q] = 0.0; mB[q] = 0.0; }
     return eval_worker(s, f, c1, c2, c3, NULL, NULL, NULL, NULL, NULL, NULL, &k);
+}
+
+/*
+ * Energy differences of Monte Carlo moves on fixed positions (uf3_mc.h: mc_delta through k_mc_delta and k_mc_trials).
+ * A move is a swap of the species of the real atoms i and j (mode 0; j_or_species holds j) or the transmutation of atom i to the
+ * atomic number j_or_species (mode 1).  T = {i, j} or {i}, by real atom; z' is z after the move.
+ *
+ *     dE = E_touch(z') - E_touch(z),   E_touch = the sum of exactly those terms of eval_worker's term loop -- one-body terms, directed
+ *          pair terms (real i, supercell j), triplets of real centres -- whose parent atoms, centre included, contain an atom of T.
+ *
+ * Every other term has the same value before and after the move, so dE is the difference of the two whole energies; it is never
+ * formed from them.  The loop runs twice, once per species assignment, with the sink of touch_t.
+ *
+ * The magnitude.  An fp64 evaluation of dE by ANY bookkeeping (the device's weights 2 and 1 on pair entries, its lists of
+ * affected centres) adds and subtracts the touched terms of both assignments, each computed from its own distances.  By the
+ * definition at the top of this file each touched term t contributes |t|_abs + sum_r rho_r |dt/dr|_abs -- the mval the loop
+ * already hands to its sinks -- whichever sign it enters with, and a term of z is as much an operand as a term of z':
+ *
+ *     M = M_touch(z') + M_touch(z),   M_touch = the sum of mval over the same terms as E_touch.
+ *
+ * The untouched terms cancel exactly before they are ever computed and must NOT enter M: with them M would be M_e(z) + M_e(z'),
+ * of the order of the frame's energy, and the bound would again hide a missing term.  M <= M_e(z) + M_e(z') always, strictly for
+ * every frame with an atom out of reach of T.
+ *
+ * A move with i == j, or between like species (a transmutation to the atom's own species), changes no term: dE = 0 and M = 0
+ * exactly, without a walk.  Swapping (i, j) and (j, i) is the same T and the same z': the same bits.
+ *
+ * terms (may be NULL; only with n_moves == 1): [term_cap][UF3O_MC_TERM_W] the records of touch_t for both passes; n_terms [1] the
+ * number of terms met (may exceed term_cap: call again).
+ */
+static int mc_worker(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
+                     int64_t n_moves, const int *mi, const int *mj, int mode, real *dE, double *M,
+                     double *terms, int64_t term_cap, int64_t *n_terms) {
+    int N = f->n_atoms, rc = 0;
+    if (mode != 0 && mode != 1) return 3;
+    if (terms && n_moves != 1) return 3;
+    for (int64_t q = 0; q < n_moves; q++) {
+        if (mi[q] < 0 || mi[q] >= N) return 3;
+        if (mode == 0 ? (mj[q] < 0 || mj[q] >= N) : species_index(s, mj[q]) < 0) return 3;
+    }
+    unsigned char *touch = (unsigned char *)calloc((size_t)(N > 0 ? N : 1), 1), *reach = (unsigned char *)calloc((size_t)(N > 0 ? N : 1), 1);
+    int *zn = (int *)malloc(sizeof(int) * (size_t)(N > 0 ? N : 1));
+    if (n_terms) *n_terms = 0;
+    for (int64_t q = 0; q < n_moves && !rc; q++) {
+        int i = mi[q], j = mode == 0 ? mj[q] : -1;
+        dE[q] = 0.0; M[q] = 0.0;
+        if (mode == 0 ? (i == j || f->z[i] == f->z[j]) : f->z[i] == mj[q]) continue;
+        memcpy(zn, f->z, sizeof(int) * (size_t)N);
+        if (mode == 0) { zn[i] = f->z[j]; zn[j] = f->z[i]; } else zn[i] = mj[q];
+        memset(touch, 0, (size_t)N);
+        touch[i] = 1;
+        if (j >= 0) touch[j] = 1;
+        uf3o_frame fn = *f;
+        fn.z = zn;
+        touch_t t = {.touch = touch, .reach = reach, .rec = terms, .cap = term_cap};
+        sink_t k = {.n = N, .mc = &t};
+        real e[2] = {0.0, 0.0};
+        double m[2] = {0.0, 0.0};
+        for (int pass = 0; pass < 2 && !rc; pass++) {
+            t.E = 0.0; t.M = 0.0; t.pass = pass;
+            rc = eval_worker(s, pass ? &fn : f, c1, c2, c3, NULL, NULL, NULL, NULL, NULL, NULL, &k);
+            e[pass] = t.E; m[pass] = t.M;
+        }
+        dE[q] = e[1] - e[0];
+        M[q] = m[1] + m[0];
+        if (n_terms) *n_terms = t.n_rec;
+    }
+    free(touch); free(reach); free(zn);
+    return rc;
+}
+
+int uf3o_mc_delta_x(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
+                    int64_t n_moves, const int *i, const int *j_or_species, int mode, real *dE, double *M) {
+    return mc_worker(s, f, c1, c2, c3, n_moves, i, j_or_species, mode, dE, M, NULL, 0, NULL);
+}
+
+/* one move with the records of its terms (touch_t) */
+int uf3o_mc_terms_x(const uf3o_spec *s, const uf3o_frame *f, const double *c1, const double *c2, const double *c3,
+                    int i, int j_or_species, int mode, real *dE, double *M, double *terms, int64_t term_cap, int64_t *n_terms) {
+    return mc_worker(s, f, c1, c2, c3, 1, &i, &j_or_species, mode, dE, M, terms, term_cap, n_terms);
 }

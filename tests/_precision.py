@@ -19,6 +19,9 @@ The second-derivative and per-centre kinds -- ``H``, ``mixed``, ``born`` (k_hess
 same rule: ``reference(name)`` computes them on first use.  Those three kernels describe the frame with every atom counted as
 its image inside the cell, and so do these oracle entries (``oracle.supercell_radius``).
 
+Monte Carlo energy differences -- kind ``dE`` (mc_delta through k_mc_delta and k_mc_trials; ``oracle.mc_delta_x``) -- have
+cases and moves of their own (``mc_cases``, ``mc_moves``, ``mc_reference`` at the end of this file) and the same rule.
+
 One documented design choice is not a bounded number of roundings per term: the launches that evaluate leg functions from
 local cubic pieces in powers of ``x - t_i`` (k_featurize3, the grouped matrix-core launch) carry Horner's absolute error on
 values that are themselves tiny.  For those routes alone M is the oracle's widened one (``ratios(..., pieces=True)``;
@@ -296,3 +299,221 @@ def ratios(got, name, kinds=None, pieces=False):
 
 def fmt(r):
     return ", ".join(f"{k} {v:.3g}" for k, v in r.items())
+
+
+# ================================================================================================ Monte Carlo energy differences
+# kind "dE": mc_delta (uf3_mc.h, through k_mc_delta and k_mc_trials) against oracle.mc_delta_x.  M of a move is the sum of the
+# magnitudes of the terms that contain a moved atom, over both species assignments (uf3_oracle.c: mc_worker holds the derivation);
+# the terms the move leaves alone are in neither dE nor M.
+#
+# Worst ratio of the fp64 oracle entry against the extended one over every move of MC_CASES, both modes, as printed by
+# tests/test_mc_precision_host.py::test_fp64_entry_stays_within_the_recorded_table.  Measured 2026-10-20 (x86-64, gcc -O2
+# -ffp-contract=off, 80-bit long double): dE 0.169 (uneven_lead0, transmute) -- recorded rounded up.  It is far below 1 because M
+# adds the magnitudes of several hundred terms as if their roundings all pointed one way, while the oracle's own sum errs like a
+# random walk; GAMMA stays at its floor of 16.
+RHO_O["dE"] = 0.2
+GAMMA["dE"] = 16.0 * max(RHO_O["dE"], 1.0)
+MC_MODES = ("swap", "transmute")
+
+
+def _compressed(reps, a, seed, rattle, numbers=(42, 74)):
+    """a bcc cell at a lattice constant far below the physical one: the way to long 3-body lists with few atoms"""
+    return synthetic.lattice_frame("bcc", reps, a, list(numbers), seed=seed, rattle=rattle, strain=0.0)
+
+
+def mc_counts(basis, atoms):
+    """From the geometry alone, with the oracle's supercell: ``n3`` [N] entries of every atom's 3-body list, ``in3`` / ``in2``
+    [N, N] how many images of atom j lie in atom i's 3-body range / within the largest pair r_max (the device table's two
+    lists: uf3_hip.hip mc_build_table)."""
+    ob = O.OracleBasis(basis)
+    pos, _, _ = O.supercell(atoms, basis.r_cut)
+    n = len(atoms)
+    in2, in3 = np.zeros((n, n), dtype=np.int64), np.zeros((n, n), dtype=np.int64)
+    r2 = float(ob.pair_rmax.max())
+    if basis.degree > 2 and ob.trios:
+        seqs = [[np.asarray(k, float) for k in basis.knots_map[t]] for t in ob.trios]
+        rmin3, rmax3 = max(min(k.min() for ks in seqs for k in ks), 0.0), max(k.max() for ks in seqs for k in ks[:2])
+    else:
+        rmin3, rmax3 = 0.0, -1.0
+    parent = np.arange(len(pos)) % n
+    for i in range(n):
+        d = np.linalg.norm(pos - pos[i], axis=1)
+        d[i] = -1.0
+        np.add.at(in2[i], parent[(d >= 0) & (d < r2)], 1)
+        np.add.at(in3[i], parent[(d > rmin3) & (d <= rmax3)], 1)
+    return {"n3": in3.sum(1), "in2": in2, "in3": in3}
+
+
+@functools.lru_cache(maxsize=None)
+def limit_frames(target=512):
+    """(frame whose longest 3-body list holds exactly ``target`` entries, frame whose longest holds ``target + 1``): a rattled
+    16-atom bcc cell of Mo and W (an 8-atom cell and its translate of the other species) scaled as a whole.  Its lattice constant is bisected between a cell whose longest list is
+    longer than ``target`` and one where it is not; from that crossing the constant is walked in steps of 2e-6 A to either side
+    until each count is met at a constant whose neighbours 1e-7 A away give the same count (a list loses one entry as the cell
+    grows -- or two at once, an atom's own image and its mirror image -- so a count can be stepped over: then the next seed).
+    The counts of the frames returned are those of ``mc_counts``, and the frames are clear of discontinuities."""
+    basis = cases()["mow_lead0"][0]
+    rmin3, rmax3 = 1.5, 3.5
+    for seed in range(900, 940):
+        half = _compressed((2, 2, 1), 1.0, seed, rattle=0.02)
+        hc = np.asarray(half.get_cell())
+        zh = np.asarray(half.get_atomic_numbers())
+        # the 8-atom cell twice along c, atom k + 8 the translate of atom k with the other species: both have the same lists, so
+        # the swap of the atom with the longest list and its translate fills the candidate list to its last slot
+        unit = Atoms(numbers=np.concatenate([zh, 42 + 74 - zh]), positions=np.concatenate([half.get_positions(), half.get_positions() + hc[2]]),
+                     cell=hc * np.array([[1.0], [1.0], [2.0]]), pbc=True)
+        p = np.asarray(unit.get_positions())
+        shifts = np.array([[x, y, z] for x in range(-6, 7) for y in range(-6, 7) for z in range(-6, 7)], dtype=float) @ np.asarray(unit.get_cell())
+        d = np.sort(np.linalg.norm((p[None, :, None, :] + shifts[None, None, :, :]) - p[:, None, None, :], axis=-1).reshape(len(p), -1), axis=1)
+
+        def frame(a):
+            return Atoms(numbers=unit.get_atomic_numbers(), positions=p * a, cell=np.asarray(unit.get_cell()) * a, pbc=True)
+
+        def longest(a):                                   # (the unit cell's sorted distances, the range scaled instead)
+            return max(int(np.searchsorted(row, rmax3 / a, side="right") - np.searchsorted(row, rmin3 / a, side="right")) for row in d)
+        lo, hi = 0.80, 0.95                               # longest(lo) > target >= longest(hi)
+        assert longest(lo) > target + 1 and longest(hi) < target
+        for _ in range(40):
+            mid = 0.5 * (lo + hi)
+            lo, hi = (mid, hi) if longest(mid) > target else (lo, mid)
+        found = {}
+        for a in np.concatenate([hi + 2e-6 * np.arange(1, 2000), lo - 2e-6 * np.arange(1, 2000)]):
+            c = longest(float(a))
+            if c in (target, target + 1) and c not in found and longest(a - 1e-7) == c == longest(a + 1e-7):
+                f = frame(float(a))
+                try:
+                    clear_of_discontinuities(basis, f)
+                except AssertionError:
+                    continue
+                if int(mc_counts(basis, f)["n3"].max()) == c:
+                    found[c] = f
+            if len(found) == 2:
+                return found[target], found[target + 1]
+    raise AssertionError("no seed gives both counts")
+
+
+@functools.lru_cache(maxsize=None)
+def mc_cases():
+    """name -> (basis, atoms, what it is for, most moves of a mode).  The evaluator cases of ``cases()``, a 2-body model, the
+    three-equal-legs basis made binary, eight species, and the shapes that reach mc_delta's structural edges (host-side counts:
+    tests/test_gpu_precision_mc.py asserts each before the device is touched)."""
+    from test_gpu_species import ELEMENTS as SPECIES_ELEMENTS, _all_species_frame, _z
+    out = {}
+    for name in ("mow_cap16", "mow_cap32", "mow_lead0", "uneven_lead3", "uneven_lead0", "triclinic_thin", "cluster", "slab_outside",
+                 "bcc24_s4"):
+        basis, atoms, what = cases()[name]
+        out[name] = (basis, atoms, what, 100)
+    # three equal legs made binary: Mo-Mo-Mo and W-W-W keep the six-fold fold, Mo-W-W and W-Mo-Mo fold l <-> m, the others none
+    _, meta, w16 = load_case("case_w16_sym3")
+    cs = composition.ChemicalSystem(["Mo", "W"], 3)
+    kw = meta["basis_kwargs"]
+    pairs, trios = cs.interactions_map[2], cs.interactions_map[3]
+    sym3 = bspline.BSplineBasis(
+        cs, r_min_map={**{p: kw["r_min_map"]["W-W"] for p in pairs}, **{t: kw["r_min_map"]["W-W-W"] for t in trios}},
+        r_max_map={**{p: kw["r_max_map"]["W-W"] for p in pairs}, **{t: kw["r_max_map"]["W-W-W"] for t in trios}},
+        resolution_map={**{p: kw["resolution_map"]["W-W"] for p in pairs}, **{t: kw["resolution_map"]["W-W-W"] for t in trios}},
+        leading_trim={2: 0, 3: 3}, trailing_trim={2: 3, 3: 3})
+    assert sorted(sym3.symmetry.values()) == [1, 1, 2, 2, 3, 3]
+    z = np.random.default_rng(16).permutation(np.resize([42, 74], len(w16)))
+    out["w16_sym3_binary"] = (sym3, Atoms(numbers=z, positions=w16.get_positions(), cell=w16.get_cell(), pbc=w16.get_pbc()),
+                              "three equal legs, two species: symmetry folds 3, 2 and 1 in one basis", 100)
+    cs2 = composition.ChemicalSystem(["Mo", "W"], 2)
+    two = bspline.BSplineBasis(cs2, r_min_map={p: 0.001 for p in cs2.interactions_map[2]}, r_max_map={p: 5.5 for p in cs2.interactions_map[2]},
+                               resolution_map={p: 15 for p in cs2.interactions_map[2]}, leading_trim={2: 0}, trailing_trim={2: 3})
+    out["mow_2body"] = (two, cases()["mow_lead0"][1], "a 2-body model: T = 0, no candidate list", 100)
+    els = SPECIES_ELEMENTS[8]
+    out["bcc24_s8"] = (synthetic.notebook_basis(els), _all_species_frame(_z(els), (2, 2, 3), 3.165, 68),
+                       "eight species: every row of trio_of, seven transmutations an atom", 100)
+    mow = cases()["mow_lead0"][0]                             # 3-body range (1.5, 3.5], pair range 5.5: one object for the shapes below
+    out["mow288"] = (mow, synthetic.lattice_frame("bcc", (6, 6, 4), 3.165, [42, 74], seed=288, rattle=0.05, strain=0.0),
+                     "288 atoms: the strided species load, atoms past 255", 60)
+    out["dense432"] = (mow, _compressed((6, 6, 6), 1.34, 432, rattle=0.03),
+                       "compressed bcc 6 x 6 x 6: candidate lists past one round, more than 200 distinct centres", 4)
+    out["thin16_r3"] = (mow, _compressed((2, 2, 2), 1.03, 163, rattle=0.02),
+                        "16 atoms, cell of 2 A against a reach of 7: n_c past 512, every atom dozens of times", 1)
+    out["thin16_r4"] = (mow, _compressed((2, 2, 2), 0.93, 164, rattle=0.02), "the same, n_c past 768", 1)
+    out["limit512"] = (mow, limit_frames()[0], "longest 3-body list exactly 512: n_c = 1026, pair index 130815", 1)
+    return out
+
+
+MC_CLASSES = ("three_body", "pair_only", "apart", "images")
+
+
+def mc_move_classes(basis, atoms):
+    """{class: [(i, j)]} of every ordered pair of unlike atoms, from the geometry: j in i's 3-body range; in pair range only; in
+    neither; met through two or more periodic images (or i among its own neighbours)."""
+    c = mc_counts(basis, atoms)
+    z = np.asarray(atoms.get_atomic_numbers())
+    out = {k: [] for k in MC_CLASSES}
+    for i in range(len(z)):
+        for j in range(len(z)):
+            if z[i] == z[j]:
+                continue
+            if c["in3"][i, j] > 0:
+                out["three_body"].append((i, j))
+            elif c["in2"][i, j] > 0:
+                out["pair_only"].append((i, j))
+            else:
+                out["apart"].append((i, j))
+            if c["in2"][i, j] >= 2 or c["in2"][i, i] > 0:
+                out["images"].append((i, j))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def mc_moves(name, mode):
+    """The chosen moves of a case: ``(i, second, label)`` lists.  Swaps: as many of every class of ``mc_move_classes`` as the
+    case's budget allows (seeded), then the null moves: i == j and like species.  Transmutations: chosen atoms (the first of the
+    chosen swaps' atoms) to every other species of the basis, then to their own."""
+    basis, atoms, _, budget = mc_cases()[name]
+    z = np.asarray(atoms.get_atomic_numbers())
+    rng = np.random.default_rng(1 + sorted(mc_cases()).index(name))
+    classes = mc_move_classes(basis, atoms)
+    chosen = []
+    if name == "limit512":                                    # the atom with the longest list and its translate (limit_frames)
+        k = int(np.argmax(mc_counts(basis, atoms)["n3"])) % 8
+        chosen.append((k, k + 8, "last_slot"))
+    for k in MC_CLASSES:
+        pool = classes[k]
+        if budget < 4 and set(pool) & {m[:2] for m in chosen}:  # (a dear frame: one move may stand for several classes)
+            continue
+        take = rng.choice(len(pool), min(len(pool), max(1, budget // 4)), replace=False) if pool else []
+        chosen += [(int(pool[q][0]), int(pool[q][1]), k) for q in take]
+    if name == "mow288":                                      # (at least a third of the moves reach past atom 255)
+        high = [m for k in MC_CLASSES for m in classes[k] if max(m) >= 256]
+        take = rng.choice(len(high), min(len(high), budget // 2), replace=False)
+        chosen += [(int(high[q][0]), int(high[q][1]), "past_255") for q in take]
+    if mode == "swap":
+        like = [(i, j) for i in range(len(z)) for j in range(len(z)) if i != j and z[i] == z[j]]
+        nulls = [(i, i, "null") for i in sorted({m[0] for m in chosen})[:3] or [0]]
+        nulls += [(int(like[q][0]), int(like[q][1]), "null") for q in (rng.choice(len(like), min(len(like), 3), replace=False) if like else [])]
+        return tuple(chosen + nulls)
+    els = list(basis.chemical_system.element_list)
+    sym = {composition.atomic_numbers[e]: e for e in els}
+    atoms_chosen = list(dict.fromkeys([m[0] for m in chosen] + [m[1] for m in chosen] + list(range(len(z)))))
+    n_atoms = max(1, min(len(z), budget // max(1, len(els) - 1)))
+    if name == "mow288":
+        atoms_chosen = [a for a in atoms_chosen if a >= 256][:n_atoms // 2] + atoms_chosen
+    out = []
+    for a in atoms_chosen[:n_atoms]:
+        out += [(int(a), e, "transmute") for e in els if e != sym[int(z[a])]]
+    out += [(int(a), sym[int(z[a])], "null") for a in atoms_chosen[:3]]
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=None)
+def mc_reference(name, mode):
+    """The chosen moves of a case with their extended dE and M, computed once and shared (read-only): dict(i, second, label, dE,
+    M, ob, coeff).  The frame is asserted clear of discontinuities: the clearance is a property of the geometry and holds for
+    both species assignments of every move."""
+    basis, atoms, _, _ = mc_cases()[name]
+    clear_of_discontinuities(basis, atoms)
+    ob = O.OracleBasis(basis)
+    coeff = coefficients(basis)
+    moves = mc_moves(name, mode)
+    i = np.array([m[0] for m in moves], dtype=np.int64)
+    second = [m[1] for m in moves]
+    dE, M = O.mc_delta_x(ob, atoms, coeff, i, second, mode)
+    for a in (i, dE, M):
+        a.setflags(write=False)
+    return {"i": i, "second": second, "label": [m[2] for m in moves], "dE": dE, "M": M, "ob": ob, "coeff": coeff}

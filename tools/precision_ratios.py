@@ -1,14 +1,14 @@
 #!/usr/bin/env python
 """
 Collect the ``[precision] route, case: kind ratio, ...`` lines of a ``pytest -s tests/test_gpu_precision.py
-tests/test_gpu_precision_d2.py`` run into ``profiles/precision_ratios.json``: route by case by kind, the worst ratio where a line
+tests/test_gpu_precision_d2.py tests/test_gpu_precision_mc.py`` run into ``profiles/precision_ratios.json``: route by case by kind, the worst ratio where a line
 repeats, beside the bound the run was held to.  A ratio is ``max |device - extended oracle| / (2^-53 M)`` over every entry of a
 result (tests/_precision.py).  Several logs may be given (one per test file, say): their routes are merged.
 
-    python -m pytest -m gpu -s tests/test_gpu_precision.py tests/test_gpu_precision_d2.py | tee precision.log
+    python -m pytest -m gpu -s tests/test_gpu_precision.py tests/test_gpu_precision_d2.py tests/test_gpu_precision_mc.py | tee precision.log
     python tools/precision_ratios.py precision.log [-o profiles/precision_ratios.json]
 
-``--update`` keeps the routes already in the output file that the logs do not mention (a run of one of the two test files).
+``--update`` keeps the routes already in the output file that the logs do not mention (a run of one of the three test files).
 """
 import argparse
 import json
@@ -59,7 +59,8 @@ def main():
     doc = {"what": "worst |device - extended oracle| / (2^-53 M) over every entry, per route, case and kind of output "
                    "(xe, xf, xv: energy, force, virial rows; e, f, v: energy, forces, virial: tests/test_gpu_precision.py; "
                    "H, mixed, born: Hessian, position / strain and strain / strain derivatives; U, W, jp: site energies, site "
-                   "virials, the heat current's potential part; b: site rows: tests/test_gpu_precision_d2.py)",
+                   "virials, the heat current's potential part; b: site rows: tests/test_gpu_precision_d2.py; dE: Monte Carlo energy "
+                   "differences, and the running energy of a chain in units of its own bound's sum: tests/test_gpu_precision_mc.py)",
            "rho_o": P.RHO_O, "gamma": P.GAMMA, "worst": worst, "routes": routes}
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1, sort_keys=True)
