@@ -884,6 +884,33 @@ int uf3_hessian_dev(uf3_basis *basis, const uf3_frames *frames, const double *d_
  * S = k_B (x / (e^x - 1) - log(1 - e^-x)), C_v = k_B x^2 e^x / (e^x - 1)^2; T = 0: F = U = zpe, S = C_v = 0; each sum divided by
  * sum_q w_q.  h = 4.135667696e-3 eV / THz, k_B = 8.617333262e-5 eV / K.  Fixed-order sums.  Errors (UF3_EINVAL): nq < 1, a
  * negative or non-finite temperature or cut-off, null pointers.
+ *
+ * Eigenvectors on the mesh.
+ * uf3_phonon_mesh_vec: uf3_phonon_mesh's arguments, lam and status (bit for bit what uf3_phonon_mesh writes: the same rotations in
+ * the same order), plus the cell [3][3] (rows: lattice vectors, A; a host array in both entries), cutoff_thz and
+ *   evec [nq][3N][3N][2]   V(q): row (3 i + alpha), mode, (re, im); column s is an orthonormal eigenvector of lam[s].  V starts at
+ *                          I and takes every Jacobi rotation, diag(1, conj u) included; skipped pivots rotate nothing
+ *   gvel [nq][3N][3]       group velocities d f / d k in THz A (1 THz A = 100 m / s), k the Cartesian wave vector without 2 pi:
+ *                          g_a = Re(v_s^H (dD / dq_a) v_s) with dD / dq_a = sum w (2 pi i n_a) exp(2 pi i q.n) fc / sqrt(m_i m_j)
+ *                          Hermitised like D (same terms, owners and order), d lam / d k_c = sum_a g_a cell[a][c],
+ *                          v_c = 15.633302 (d lam / d k_c) / (2 sqrt|lam_s|); modes with |f_s| <= cutoff_thz get 0
+ * Either output may be NULL, not both; the cell and the cut-off are looked at only with gvel.  Inside a degenerate cluster of
+ * modes the diagonal g depends on the basis the Jacobi sweeps ended in: only the cluster's SUM of velocities is defined, and
+ * nothing resolves it.  Both outputs are bitwise repeatable and do not depend on how a mesh is cut into calls.  V lives beside D
+ * in LDS (32 (3N)^2 bytes): the limit with vectors is N <= 21 (3N = 63, 127 KB); larger cells are refused, there is no
+ * global-memory route.  Errors (UF3_EINVAL): uf3_phonon_mesh's, N above 21, both outputs NULL, and with gvel a cell that is
+ * singular or not finite or a cut-off that is negative or not finite.
+ *
+ * uf3_phonon_pdos: out [n_modes][n_samples], g_c(f) = sum_q w_q sum_s |V_cs|^2 exp(-(f - f_s)^2 / 2 sigma^2) / (sigma sqrt(2 pi)) /
+ * sum_q w_q for every channel c = 3 i + alpha, from lam [nq][n_modes] and evec as uf3_phonon_mesh_vec writes it.  Fixed-order
+ * partial sums, bitwise repeatable; V(-q) = conj V(q), so a mesh reduced by time reversal takes its integer weights unchanged.
+ * Errors (UF3_EINVAL): n_modes not a multiple of 3 in [3, 63], nq < 1, sigma <= 0, missing samples, null pointers.
+ *
+ * uf3_phonon_tdisp: out [n_temps][N][6], the mean-square displacement tensors in A^2 (xx, yy, zz, yz, xz, xy):
+ * U_i^{ab}(T) = (1 / sum w_q) sum_q w_q sum_s E_s(T) / (m_i lam_s) Re(V_{3i+a,s} conj V_{3i+b,s}), E_s = h f_s (1 / 2 + 1 / (e^x - 1)),
+ * x = h f_s / k_B T (uf3_phonon_thermo's constants and forms; T = 0: the zero-point term).  inv_sqrt_mass [N] is a host array in
+ * both entries.  Modes with f <= cutoff_thz are left out and *excluded is their summed weight.  Fixed-order sums.  Errors
+ * (UF3_EINVAL): N outside [1, 21], nq < 1, a negative or non-finite temperature or cut-off, masses not positive, null pointers.
  */
 int uf3_phonon_mesh(uf3_ctx *ctx, int32_t n_atoms, int64_t n_sc_atoms, const double *fc, const double *inv_sqrt_mass,
                     int64_t n_terms, const int32_t *terms, const double *term_w, int64_t nq, const double *q, double *lam,
@@ -899,6 +926,22 @@ int uf3_phonon_thermo(uf3_ctx *ctx, int32_t n_modes, int64_t nq, const double *l
                       const double *temps, double cutoff_thz, double *out, double *zpe, int64_t *excluded);
 int uf3_phonon_thermo_dev(uf3_ctx *ctx, int32_t n_modes, int64_t nq, const double *d_lam, const int64_t *d_wq, int32_t n_temps,
                           const double *temps, double cutoff_thz, double *d_out, double *d_zpe, int64_t *d_excluded);
+int uf3_phonon_mesh_vec(uf3_ctx *ctx, int32_t n_atoms, int64_t n_sc_atoms, const double *fc, const double *inv_sqrt_mass,
+                        int64_t n_terms, const int32_t *terms, const double *term_w, int64_t nq, const double *q, double *lam,
+                        int32_t *status, const double *cell, double cutoff_thz, double *evec, double *gvel);
+int uf3_phonon_mesh_vec_dev(uf3_ctx *ctx, int32_t n_atoms, int64_t n_sc_atoms, const double *d_fc, const double *d_inv_sqrt_mass,
+                            int64_t n_terms, const int32_t *terms, const double *term_w, int64_t nq, const double *d_q,
+                            double *d_lam, int32_t *d_status, const double *cell, double cutoff_thz, double *d_evec, double *d_gvel);
+int uf3_phonon_pdos(uf3_ctx *ctx, int32_t n_modes, int64_t nq, const double *lam, const double *evec, const int64_t *wq,
+                    int32_t n_samples, const double *samples, double sigma, double *out);
+int uf3_phonon_pdos_dev(uf3_ctx *ctx, int32_t n_modes, int64_t nq, const double *d_lam, const double *d_evec, const int64_t *d_wq,
+                        int32_t n_samples, const double *samples, double sigma, double *d_out);
+int uf3_phonon_tdisp(uf3_ctx *ctx, int32_t n_atoms, int64_t nq, const double *lam, const double *evec, const int64_t *wq,
+                     const double *inv_sqrt_mass, int32_t n_temps, const double *temps, double cutoff_thz, double *out,
+                     int64_t *excluded);
+int uf3_phonon_tdisp_dev(uf3_ctx *ctx, int32_t n_atoms, int64_t nq, const double *d_lam, const double *d_evec, const int64_t *d_wq,
+                         const double *inv_sqrt_mass, int32_t n_temps, const double *temps, double cutoff_thz, double *d_out,
+                         int64_t *d_excluded);
 
 /*
  * Dense helpers behind the module-level functions of uf3.representation.distances / angles, for frames small enough

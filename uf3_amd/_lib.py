@@ -35,7 +35,8 @@ EXPORTS = ["uf3_ctx_create", "uf3_ctx_destroy", "uf3_ctx_set_stream", "uf3_ctx_s
            "uf3_neb_create", "uf3_neb_destroy", "uf3_neb_run", "uf3_neb_get_state", "uf3_idpp_create", "uf3_ssneb_create", "uf3_neb_get_cell_state",
            "uf3_mc_create", "uf3_mc_destroy", "uf3_mc_run", "uf3_mc_delta", "uf3_mc_set_positions", "uf3_mc_get_state",
            "uf3_phonon_mesh", "uf3_phonon_mesh_dev", "uf3_phonon_dos", "uf3_phonon_dos_dev", "uf3_phonon_thermo",
-           "uf3_phonon_thermo_dev",
+           "uf3_phonon_thermo_dev", "uf3_phonon_mesh_vec", "uf3_phonon_mesh_vec_dev", "uf3_phonon_pdos", "uf3_phonon_pdos_dev",
+           "uf3_phonon_tdisp", "uf3_phonon_tdisp_dev",
            "uf3_site_terms", "uf3_site_terms_dev", "uf3_heat_flux", "uf3_heat_flux_dev", "uf3_md_run_flux",
            "uf3_featurize_virial", "uf3_featurize_virial_dev",
            "uf3_leverage", "uf3_leverage_dev",
@@ -240,6 +241,12 @@ def load():
             getattr(lib, name).argtypes = [vp, i32, i64, vp, vp, i32, vp, vp, i32, vp, dbl, vp]
         for name in ("uf3_phonon_thermo", "uf3_phonon_thermo_dev"):
             getattr(lib, name).argtypes = [vp, i32, i64, vp, vp, i32, vp, dbl, vp, vp, vp]
+        for name in ("uf3_phonon_mesh_vec", "uf3_phonon_mesh_vec_dev"):
+            getattr(lib, name).argtypes = [vp, i32, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, dbl, vp, vp]
+        for name in ("uf3_phonon_pdos", "uf3_phonon_pdos_dev"):
+            getattr(lib, name).argtypes = [vp, i32, i64, vp, vp, vp, i32, vp, dbl, vp]
+        for name in ("uf3_phonon_tdisp", "uf3_phonon_tdisp_dev"):
+            getattr(lib, name).argtypes = [vp, i32, i64, vp, vp, vp, vp, i32, vp, dbl, vp, vp]
         for name in ("uf3_site_terms", "uf3_site_terms_dev"):
             getattr(lib, name).argtypes = [vp, C.POINTER(Frames), vp, vp, vp, vp, vp, vp, vp]
         for name in ("uf3_heat_flux", "uf3_heat_flux_dev"):

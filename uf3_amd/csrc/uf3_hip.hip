@@ -6246,31 +6246,50 @@ extern "C" int uf3_site_grade(uf3_basis *b, const uf3_frames *fr, const double *
 }
 
 // ------------------------------------------------------------------------------ phonons on a q-mesh (uf3_phonon.h)
+// the eigenvector entry's extras: the cell (host, [3][3], only looked at with d_gvel), the velocity cut-off, the two outputs
+struct PhVecOut { const double *cell; double cutoff; double *d_evec, *d_gvel; };
+
 static int phonon_mesh_impl(uf3_ctx *c, int32_t n_atoms, int64_t n_sc, const double *d_fc, const double *d_ism, int64_t n_terms,
                             const int32_t *terms, const double *term_w, int64_t nq, const double *d_q, double *d_lam,
-                            int32_t *d_status) {
-    if (!c) return fail(nullptr, UF3_EINVAL, "uf3_phonon_mesh: ctx is NULL");
-    if (n_atoms < 1) return fail(c, UF3_EINVAL, "uf3_phonon_mesh: no atoms");
+                            int32_t *d_status, const PhVecOut *vec = nullptr) {
+    const std::string who = vec ? "uf3_phonon_mesh_vec: " : "uf3_phonon_mesh: ";
+    if (!c) return fail(nullptr, UF3_EINVAL, who + "ctx is NULL");
+    if (n_atoms < 1) return fail(c, UF3_EINVAL, who + "no atoms");
     if (n_atoms > PH_MAX_ATOMS)
-        return fail(c, UF3_EINVAL, "uf3_phonon_mesh: " + std::to_string(n_atoms) + " atoms in the cell, the limit is " +
+        return fail(c, UF3_EINVAL, who + "" + std::to_string(n_atoms) + " atoms in the cell, the limit is " +
                                        std::to_string(PH_MAX_ATOMS) + " (D(q), 16 (3N)^2 bytes, is held in LDS)");
-    if (nq < 1 || nq > (int64_t)1 << 30) return fail(c, UF3_EINVAL, "uf3_phonon_mesh: nq must be in [1, 2^30]");
+    if (vec && n_atoms > PH_VEC_MAX_ATOMS)
+        return fail(c, UF3_EINVAL, who + std::to_string(n_atoms) + " atoms in the cell, the limit with eigenvectors is " +
+                                       std::to_string(PH_VEC_MAX_ATOMS) + " (V is held beside D(q) in LDS, 32 (3N)^2 bytes)");
+    if (nq < 1 || nq > (int64_t)1 << 30) return fail(c, UF3_EINVAL, who + "nq must be in [1, 2^30]");
     if (n_sc < n_atoms || n_sc % n_atoms || n_sc > (int64_t)1 << 24)
-        return fail(c, UF3_EINVAL, "uf3_phonon_mesh: the supercell's atom count must be a multiple of the cell's");
-    if (n_terms < 1 || n_terms > (int64_t)1 << 28) return fail(c, UF3_EINVAL, "uf3_phonon_mesh: n_terms must be in [1, 2^28]");
+        return fail(c, UF3_EINVAL, who + "the supercell's atom count must be a multiple of the cell's");
+    if (n_terms < 1 || n_terms > (int64_t)1 << 28) return fail(c, UF3_EINVAL, who + "n_terms must be in [1, 2^28]");
     if (!d_fc || !d_ism || !terms || !term_w || !d_q || !d_lam || !d_status)
-        return fail(c, UF3_EINVAL, "uf3_phonon_mesh: null argument");
+        return fail(c, UF3_EINVAL, who + "null argument");
+    if (vec) {
+        if (!vec->d_evec && !vec->d_gvel) return fail(c, UF3_EINVAL, who + "neither output asked for (evec and gvel both NULL)");
+        if (vec->d_gvel) {
+            if (!vec->cell) return fail(c, UF3_EINVAL, who + "group velocities need the cell");
+            const double *h = vec->cell;
+            const double det = h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6]) + h[2] * (h[3] * h[7] - h[4] * h[6]);
+            bool finite = std::isfinite(det);
+            for (int k = 0; k < 9; k++) finite = finite && std::isfinite(h[k]);
+            if (!finite || det == 0.0) return fail(c, UF3_EINVAL, who + "the cell must be finite and not singular");
+            if (!(vec->cutoff >= 0.0) || !std::isfinite(vec->cutoff)) return fail(c, UF3_EINVAL, who + "the cut-off must be finite and not negative");
+        }
+    }
     const int N = n_atoms, nb = N * N;
     // stable counting sort of the terms by block (i, p mod N)
     std::vector<int> off((size_t)nb + 1, 0);
     for (int64_t e = 0; e < n_terms; e++) {
         const int32_t *t = terms + 5 * e;
         if (t[0] < 0 || t[0] >= N || t[1] < 0 || t[1] >= n_sc)
-            return fail(c, UF3_EINVAL, "uf3_phonon_mesh: term " + std::to_string(e) + " names atom (" + std::to_string(t[0]) + ", " +
+            return fail(c, UF3_EINVAL, who + "term " + std::to_string(e) + " names atom (" + std::to_string(t[0]) + ", " +
                                            std::to_string(t[1]) + ") outside the cell's " + std::to_string(N) + " or the supercell's " +
                                            std::to_string(n_sc) + " atoms");
         if (std::abs(t[2]) > (1 << 20) || std::abs(t[3]) > (1 << 20) || std::abs(t[4]) > (1 << 20) || !std::isfinite(term_w[e]))
-            return fail(c, UF3_EINVAL, "uf3_phonon_mesh: term " + std::to_string(e) + " has a lattice vector beyond 2^20 cells or a weight that is not finite");
+            return fail(c, UF3_EINVAL, who + "term " + std::to_string(e) + " has a lattice vector beyond 2^20 cells or a weight that is not finite");
         off[(size_t)t[0] * N + t[1] % N + 1]++;
     }
     for (int k = 0; k < nb; k++) off[k + 1] += off[k];
@@ -6297,16 +6316,24 @@ static int phonon_mesh_impl(uf3_ctx *c, int32_t n_atoms, int64_t n_sc, const dou
     A.fc = d_fc; A.inv_sqrt_mass = d_ism; A.terms = (const PhTerm *)ws; A.term_w = (const double *)(ws + b_t);
     A.block_off = (const int *)(ws + b_t + b_w); A.q = d_q; A.lam = d_lam; A.status = d_status;
     A.nq = nq; A.ld = 3 * n_sc; A.natoms = N;
+    A.evec = vec ? vec->d_evec : nullptr; A.gvel = vec ? vec->d_gvel : nullptr; A.cutoff = vec ? vec->cutoff : 0.0;
+    for (int k = 0; k < 9; k++) A.cell[k] = vec && vec->d_gvel ? vec->cell[k] : 0.0;
     uf3_env_refresh();
     const bool force_wave = uf3_env("UF3_PHONON_WAVE") != nullptr;      // measurements: the wave-per-q kernel at 3N <= 6 as well
     if (N <= 2 && !force_wave) {
         const unsigned g = (unsigned)((nq + 63) / 64);
-        if (N == 1) hipLaunchKernelGGL(k_ph_mesh_lane<1>, dim3(g), dim3(64), 0, st, A);
+        if (vec && N == 1) hipLaunchKernelGGL((k_ph_mesh_lane<1, true>), dim3(g), dim3(64), 0, st, A);
+        else if (vec) hipLaunchKernelGGL((k_ph_mesh_lane<2, true>), dim3(g), dim3(64), 0, st, A);
+        else if (N == 1) hipLaunchKernelGGL(k_ph_mesh_lane<1>, dim3(g), dim3(64), 0, st, A);
         else hipLaunchKernelGGL(k_ph_mesh_lane<2>, dim3(g), dim3(64), 0, st, A);
+    } else if (vec) {
+        const size_t lds = ph_wave_lds(3 * N, true);
+        if (lds > 65536) HIPCHK(c, lds_opt_in<k_ph_mesh_wave<true>>(c->device, lds));
+        hipLaunchKernelGGL(k_ph_mesh_wave<true>, dim3((unsigned)nq), dim3(64), lds, st, A);
     } else {
         const size_t lds = ph_wave_lds(3 * N);
-        if (lds > 65536) HIPCHK(c, lds_opt_in<k_ph_mesh_wave>(c->device, lds));
-        hipLaunchKernelGGL(k_ph_mesh_wave, dim3((unsigned)nq), dim3(64), lds, st, A);
+        if (lds > 65536) HIPCHK(c, lds_opt_in<k_ph_mesh_wave<false>>(c->device, lds));
+        hipLaunchKernelGGL(k_ph_mesh_wave<false>, dim3((unsigned)nq), dim3(64), lds, st, A);
     }
     HIPCHK(c, hipGetLastError());
     return UF3_OK;
@@ -6336,6 +6363,40 @@ extern "C" int uf3_phonon_mesh(uf3_ctx *c, int32_t n_atoms, int64_t n_sc_atoms, 
                               S.at<double>(s_q), S.at<double>(s_l), S.at<int32_t>(s_s));
     if (rc) return rc;
     HIPCHK(c, S.out({{s_l, lam}, {s_s, status}}));
+    return UF3_OK;
+}
+
+extern "C" int uf3_phonon_mesh_vec_dev(uf3_ctx *c, int32_t n_atoms, int64_t n_sc_atoms, const double *d_fc, const double *d_inv_sqrt_mass,
+                                       int64_t n_terms, const int32_t *terms, const double *term_w, int64_t nq, const double *d_q,
+                                       double *d_lam, int32_t *d_status, const double *cell, double cutoff_thz, double *d_evec,
+                                       double *d_gvel) {
+    const PhVecOut V{cell, cutoff_thz, d_evec, d_gvel};
+    return phonon_mesh_impl(c, n_atoms, n_sc_atoms, d_fc, d_inv_sqrt_mass, n_terms, terms, term_w, nq, d_q, d_lam, d_status, &V);
+}
+
+extern "C" int uf3_phonon_mesh_vec(uf3_ctx *c, int32_t n_atoms, int64_t n_sc_atoms, const double *fc, const double *inv_sqrt_mass,
+                                   int64_t n_terms, const int32_t *terms, const double *term_w, int64_t nq, const double *q, double *lam,
+                                   int32_t *status, const double *cell, double cutoff_thz, double *evec, double *gvel) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "uf3_phonon_mesh_vec: ctx is NULL");
+    if (!fc || !inv_sqrt_mass || !q || !lam || !status) return fail(c, UF3_EINVAL, "uf3_phonon_mesh_vec: null argument");
+    if (n_atoms < 1 || n_atoms > PH_VEC_MAX_ATOMS || nq < 1 || nq > (int64_t)1 << 30 || n_sc_atoms < n_atoms || n_sc_atoms > (int64_t)1 << 24 ||
+        (!evec && !gvel)) {
+        const PhVecOut V{cell, cutoff_thz, evec, gvel};
+        return phonon_mesh_impl(c, n_atoms, n_sc_atoms, fc, inv_sqrt_mass, n_terms, terms, term_w, nq, q, lam, status, &V);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n3 = 3 * (size_t)n_atoms;
+    Stage S(c->ph_io, c->stream);
+    const int s_fc = S.add(8 * n3 * 3 * (size_t)n_sc_atoms), s_m = S.add(8 * (size_t)n_atoms), s_q = S.add(24 * (size_t)nq),
+              s_l = S.add(8 * n3 * (size_t)nq), s_s = S.add(4 * (size_t)nq), s_v = S.add(16 * n3 * n3 * (size_t)nq, evec != nullptr),
+              s_g = S.add(24 * n3 * (size_t)nq, gvel != nullptr);
+    HIPCHK(c, S.alloc());
+    HIPCHK(c, S.in({{s_fc, fc}, {s_m, inv_sqrt_mass}, {s_q, q}}));
+    const PhVecOut V{cell, cutoff_thz, S.at<double>(s_v), S.at<double>(s_g)};
+    int rc = phonon_mesh_impl(c, n_atoms, n_sc_atoms, S.at<double>(s_fc), S.at<double>(s_m), n_terms, terms, term_w, nq,
+                              S.at<double>(s_q), S.at<double>(s_l), S.at<int32_t>(s_s), &V);
+    if (rc) return rc;
+    HIPCHK(c, S.out({{s_l, lam}, {s_s, status}, {s_v, evec}, {s_g, gvel}}));
     return UF3_OK;
 }
 
@@ -6474,6 +6535,120 @@ extern "C" int uf3_phonon_thermo(uf3_ctx *c, int32_t n_modes, int64_t nq, const 
                                 S.at<double>(s_z), S.at<int64_t>(s_e));
     if (rc) return rc;
     HIPCHK(c, S.out({{s_o, out}, {s_z, zpe}, {s_e, excluded}}));
+    return UF3_OK;
+}
+
+static int phonon_pdos_impl(uf3_ctx *c, int32_t n_modes, int64_t nq, const double *d_lam, const double *d_evec, const int64_t *d_wq,
+                            int32_t n_samples, const double *samples, double sigma, double *d_out) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "uf3_phonon_pdos: ctx is NULL");
+    if (n_modes < 1 || n_modes > 3 * PH_VEC_MAX_ATOMS || n_modes % 3)
+        return fail(c, UF3_EINVAL, "uf3_phonon_pdos: modes per q-point must be a multiple of 3 in [3, " + std::to_string(3 * PH_VEC_MAX_ATOMS) + "]");
+    if (nq < 1 || nq > (int64_t)1 << 30) return fail(c, UF3_EINVAL, "uf3_phonon_pdos: nq must be in [1, 2^30]");
+    if (!d_lam || !d_evec || !d_out) return fail(c, UF3_EINVAL, "uf3_phonon_pdos: null argument");
+    if (n_samples < 1 || n_samples > (1 << 24) || !samples) return fail(c, UF3_EINVAL, "uf3_phonon_pdos: needs n_samples in [1, 2^24] and sample frequencies");
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(c, UF3_EINVAL, "uf3_phonon_pdos: sigma must be positive and finite");
+    for (int k = 0; k < n_samples; k++)
+        if (!std::isfinite(samples[k])) return fail(c, UF3_EINVAL, "uf3_phonon_pdos: sample frequencies must be finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    long long *d_wsum;
+    double *d_samples, *d_none;
+    int rc = phonon_small_inputs(c, d_wq, nq, samples, (size_t)n_samples, nullptr, 0, &d_wsum, &d_samples, &d_none);
+    if (rc) return rc;
+    // chunks: a function of the mode count alone (at most 256 of them, whole tiles)
+    const long long total = (long long)nq * n_modes;
+    long long chunk = std::max<long long>(4096, (total + 255) / 256);
+    chunk = (chunk + PH_DOS_TILE - 1) / PH_DOS_TILE * PH_DOS_TILE;
+    const int n_chunks = (int)((total + chunk - 1) / chunk);
+    HIPCHK(c, c->ph_part.ensure(8 * (size_t)n_chunks * (size_t)n_modes * (size_t)n_samples));
+    double *part = c->ph_part.as<double>();
+    const unsigned gs = (unsigned)((n_samples + 255) / 256), gc = (unsigned)((n_modes + PH_PDOS_CH - 1) / PH_PDOS_CH);
+    hipLaunchKernelGGL(k_ph_pdos_part, dim3(gs, (unsigned)n_chunks, gc), dim3(256), 0, st, d_lam, d_evec, (const long long *)d_wq, total,
+                       (int)n_modes, chunk, (const double *)d_samples, (int)n_samples, 1.0 / sigma, part);
+    hipLaunchKernelGGL(k_ph_pdos_sum, dim3(gs, (unsigned)n_modes), dim3(256), 0, st, (const double *)part, n_chunks, (int)n_modes,
+                       (int)n_samples, 1.0 / sigma, (const long long *)d_wsum, d_out);
+    HIPCHK(c, hipGetLastError());
+    return UF3_OK;
+}
+
+extern "C" int uf3_phonon_pdos_dev(uf3_ctx *c, int32_t n_modes, int64_t nq, const double *d_lam, const double *d_evec, const int64_t *d_wq,
+                                   int32_t n_samples, const double *samples, double sigma, double *d_out) {
+    return phonon_pdos_impl(c, n_modes, nq, d_lam, d_evec, d_wq, n_samples, samples, sigma, d_out);
+}
+
+extern "C" int uf3_phonon_pdos(uf3_ctx *c, int32_t n_modes, int64_t nq, const double *lam, const double *evec, const int64_t *wq,
+                               int32_t n_samples, const double *samples, double sigma, double *out) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "uf3_phonon_pdos: ctx is NULL");
+    if (!lam || !evec || !out || n_modes < 1 || n_modes > 3 * PH_VEC_MAX_ATOMS || n_modes % 3 || nq < 1 || nq > (int64_t)1 << 30 || n_samples < 1 ||
+        n_samples > (1 << 24))
+        return phonon_pdos_impl(c, n_modes, nq, lam, evec, wq, n_samples, samples, sigma, out);
+    HIPCHK(c, hipSetDevice(c->device));
+    Stage S(c->ph_io, c->stream);
+    const size_t nm = (size_t)n_modes;
+    const int s_l = S.add(8 * nm * (size_t)nq), s_v = S.add(16 * nm * nm * (size_t)nq), s_w = S.add(8 * (size_t)nq, wq != nullptr),
+              s_o = S.add(8 * nm * (size_t)n_samples);
+    HIPCHK(c, S.alloc());
+    HIPCHK(c, S.in({{s_l, lam}, {s_v, evec}, {s_w, wq}}));
+    int rc = phonon_pdos_impl(c, n_modes, nq, S.at<double>(s_l), S.at<double>(s_v), S.at<int64_t>(s_w), n_samples, samples, sigma,
+                              S.at<double>(s_o));
+    if (rc) return rc;
+    HIPCHK(c, S.out({{s_o, out}}));
+    return UF3_OK;
+}
+
+// inv_sqrt_mass [N] is one of the small host arrays here, in both entries
+static int phonon_tdisp_impl(uf3_ctx *c, int32_t n_atoms, int64_t nq, const double *d_lam, const double *d_evec, const int64_t *d_wq,
+                             const double *inv_sqrt_mass, int32_t n_temps, const double *temps, double cutoff_thz, double *d_out,
+                             int64_t *d_excluded) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "uf3_phonon_tdisp: ctx is NULL");
+    if (n_atoms < 1 || n_atoms > PH_VEC_MAX_ATOMS)
+        return fail(c, UF3_EINVAL, "uf3_phonon_tdisp: the cell's atom count must be in [1, " + std::to_string(PH_VEC_MAX_ATOMS) + "]");
+    if (nq < 1 || nq > (int64_t)1 << 30) return fail(c, UF3_EINVAL, "uf3_phonon_tdisp: nq must be in [1, 2^30]");
+    if (n_temps < 1 || n_temps > 65535) return fail(c, UF3_EINVAL, "uf3_phonon_tdisp: the number of temperatures must be in [1, 65535]");
+    if (!d_lam || !d_evec || !inv_sqrt_mass || !temps || !d_out || !d_excluded) return fail(c, UF3_EINVAL, "uf3_phonon_tdisp: null argument");
+    for (int k = 0; k < n_temps; k++)
+        if (!(temps[k] >= 0.0) || !std::isfinite(temps[k]))
+            return fail(c, UF3_EINVAL, "uf3_phonon_tdisp: temperatures must be finite and not negative");
+    for (int k = 0; k < n_atoms; k++)
+        if (!(inv_sqrt_mass[k] > 0.0) || !std::isfinite(inv_sqrt_mass[k]))
+            return fail(c, UF3_EINVAL, "uf3_phonon_tdisp: inverse root masses must be positive and finite");
+    if (!(cutoff_thz >= 0.0) || !std::isfinite(cutoff_thz)) return fail(c, UF3_EINVAL, "uf3_phonon_tdisp: the cut-off must be finite and not negative");
+    HIPCHK(c, hipSetDevice(c->device));
+    long long *d_wsum;
+    double *d_t, *d_m;
+    int rc = phonon_small_inputs(c, d_wq, nq, temps, (size_t)n_temps, inv_sqrt_mass, (size_t)n_atoms, &d_wsum, &d_t, &d_m);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_ph_tdisp, dim3((unsigned)n_temps, (unsigned)n_atoms), dim3(256), 0, c->stream, d_lam, d_evec, (const long long *)d_wq,
+                       (long long)nq * 3 * n_atoms, 3 * (int)n_atoms, (const double *)d_m, (const double *)d_t, cutoff_thz,
+                       (const long long *)d_wsum, d_out, (long long *)d_excluded);
+    HIPCHK(c, hipGetLastError());
+    return UF3_OK;
+}
+
+extern "C" int uf3_phonon_tdisp_dev(uf3_ctx *c, int32_t n_atoms, int64_t nq, const double *d_lam, const double *d_evec, const int64_t *d_wq,
+                                    const double *inv_sqrt_mass, int32_t n_temps, const double *temps, double cutoff_thz, double *d_out,
+                                    int64_t *d_excluded) {
+    return phonon_tdisp_impl(c, n_atoms, nq, d_lam, d_evec, d_wq, inv_sqrt_mass, n_temps, temps, cutoff_thz, d_out, d_excluded);
+}
+
+extern "C" int uf3_phonon_tdisp(uf3_ctx *c, int32_t n_atoms, int64_t nq, const double *lam, const double *evec, const int64_t *wq,
+                                const double *inv_sqrt_mass, int32_t n_temps, const double *temps, double cutoff_thz, double *out,
+                                int64_t *excluded) {
+    if (!c) return fail(nullptr, UF3_EINVAL, "uf3_phonon_tdisp: ctx is NULL");
+    if (!lam || !evec || !out || !excluded || n_atoms < 1 || n_atoms > PH_VEC_MAX_ATOMS || nq < 1 || nq > (int64_t)1 << 30 || n_temps < 1 ||
+        n_temps > 65535)
+        return phonon_tdisp_impl(c, n_atoms, nq, lam, evec, wq, inv_sqrt_mass, n_temps, temps, cutoff_thz, out, excluded);
+    HIPCHK(c, hipSetDevice(c->device));
+    Stage S(c->ph_io, c->stream);
+    const size_t nm = 3 * (size_t)n_atoms;
+    const int s_l = S.add(8 * nm * (size_t)nq), s_v = S.add(16 * nm * nm * (size_t)nq), s_w = S.add(8 * (size_t)nq, wq != nullptr),
+              s_o = S.add(48 * (size_t)n_atoms * (size_t)n_temps), s_e = S.add(8);
+    HIPCHK(c, S.alloc());
+    HIPCHK(c, S.in({{s_l, lam}, {s_v, evec}, {s_w, wq}}));
+    int rc = phonon_tdisp_impl(c, n_atoms, nq, S.at<double>(s_l), S.at<double>(s_v), S.at<int64_t>(s_w), inv_sqrt_mass, n_temps, temps,
+                               cutoff_thz, S.at<double>(s_o), S.at<int64_t>(s_e));
+    if (rc) return rc;
+    HIPCHK(c, S.out({{s_o, out}, {s_e, excluded}}));
     return UF3_OK;
 }
 

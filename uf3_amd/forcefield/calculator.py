@@ -523,3 +523,26 @@ class UFCalculator(_Base):
         from . import harmonic
         return harmonic.thermal_properties(self, atoms, temperatures, mesh, n_super=n_super, masses=masses,
                                            cutoff_THz=cutoff_THz, **kwargs)
+
+    def get_phonon_pdos(self, atoms, mesh=(20, 20, 20), n_super=5, masses=None, sigma=None, by="atom", **kwargs):
+        """Projected phonon density of states on a q-mesh (``harmonic.projected_dos``, its dict): ``frequencies``, ``pdos``
+        [n_groups, n_samples], ``labels`` and the total ``dos``, grouped ``by`` "atom", "species" or "channel"; eigenvectors,
+        smearing and sums on the device (phonopy's ``run_projected_dos``, with Gaussians).  Cells of at most 21 atoms.
+        Masses: as for ``get_phonon_data``."""
+        from . import harmonic
+        return harmonic.projected_dos(self, atoms, mesh, n_super=n_super, masses=masses, sigma=sigma, by=by, **kwargs)
+
+    def get_thermal_displacements(self, atoms, temperatures, mesh=(20, 20, 20), n_super=5, masses=None, cutoff_THz=1e-3, **kwargs):
+        """Mean-square thermal displacement tensors at ``temperatures`` (K) from a q-mesh (``harmonic.thermal_displacements``,
+        its dict): ``U`` [n_T, N, 3, 3] and ``u_iso`` [n_T, N] in A^2, ``n_excluded`` (phonopy's
+        ``run_thermal_displacement_matrices``).  Cells of at most 21 atoms.  Masses: as for ``get_phonon_data``."""
+        from . import harmonic
+        return harmonic.thermal_displacements(self, atoms, temperatures, mesh, n_super=n_super, masses=masses,
+                                              cutoff_THz=cutoff_THz, **kwargs)
+
+    def get_group_velocities(self, atoms, qpoints, n_super=5, masses=None, cutoff_THz=1e-3):
+        """Phonon frequencies [nq, 3N] (THz) and group velocities [nq, 3N, 3] (THz A = 100 m / s) at reduced wave vectors
+        ``qpoints`` (``harmonic.group_velocities``): Hellmann-Feynman on the device's eigenvectors; inside a degenerate
+        cluster of modes only the sum of the velocities is defined.  Masses: as for ``get_phonon_data``."""
+        from . import harmonic
+        return harmonic.group_velocities(self, atoms, qpoints, n_super=n_super, masses=masses, cutoff_THz=cutoff_THz)

@@ -311,8 +311,9 @@ def band_structure(calc, atoms, path=None, n_super=5, resolution=30, masses=None
 # ------------------------------------------------------------------------------------------- phonons on a q-mesh (device)
 # DESIGN.md section 3.12.  D(q) and its eigenvalues at every q-point of a mesh, the density of states and the harmonic
 # thermodynamics run on the device (uf3_phonon_mesh / _dos / _thermo); the force constants come from one uf3_hessian call per
-# structure.  Out of scope: eigenvectors on the mesh (projected DOS, thermal displacements), the tetrahedron method, point-group
-# reduction of the mesh, non-analytic (LO-TO) corrections, the quasi-harmonic volume loop, plotting.
+# structure.  Eigenvectors on the mesh (projected DOS, thermal displacements, group velocities): further down.  Out of scope:
+# the tetrahedron method, point-group reduction of the mesh, non-analytic (LO-TO) corrections, the quasi-harmonic volume loop,
+# plotting.
 def qmesh(mesh, gamma_centred=True, time_reversal=True):
     """Regular mesh of reduced wave vectors: ``(q [nq, 3] in [0, 1), weights int64 [nq])``.  q_k = a_k / n_k, a_k = 0 .. n_k - 1,
     or (a_k + 1/2) / n_k with ``gamma_centred=False``.  With ``time_reversal`` one of each pair (q, -q mod 1) is kept with
@@ -520,7 +521,7 @@ def density_of_states(calc, atoms, mesh, n_super=5, masses=None, sigma=None, fre
                                         RuntimeWarning: the structure is dynamically unstable
       ``sigma``, ``qpoints``, ``weights``, ``mode_frequencies`` [nq, 3N]
     Gaussian smearing where phonopy's default is the tetrahedron method; no point-group reduction of the mesh (time reversal
-    only); no projected DOS.
+    only); the projected DOS is ``projected_dos``.
     """
     lam, q, w = _mesh_lambda(calc, atoms, mesh, None, n_super, masses, gamma_centred, time_reversal, "density_of_states")
     f = eigenvalues_to_frequencies(lam)
@@ -562,6 +563,270 @@ def thermal_properties(calc, atoms, temperatures, mesh, n_super=5, masses=None, 
                       "out of the sums: the structure is dynamically unstable", RuntimeWarning)
     res["n_imaginary"] = n_imag
     return res
+
+
+# ------------------------------------------------------------------------------- eigenvectors on the q-mesh (device)
+# DESIGN.md section 3.23.  uf3_phonon_mesh_vec returns V(q) and the group velocities beside the eigenvalues (the same bits as
+# uf3_phonon_mesh); uf3_phonon_pdos and uf3_phonon_tdisp reduce V over the mesh.  A mesh whose vectors do not fit in one
+# allocation goes through in q-slabs of ``vector_slab(3N)`` points, a function of 3N alone: every q is independent in the
+# eigensolver, and the reductions add their slabs' partial results in slab order, so nothing depends on free memory.
+VEC_MAX_ATOMS = 21                     # uf3_phonon_mesh_vec: V beside D(q) in LDS, 32 (3N)^2 bytes (3N = 63: 127 KB of 160)
+VEC_SLAB_BYTES = 1 << 28               # eigenvectors of one q-slab: at most 256 MiB
+
+
+def vector_slab(n_modes):
+    """q-points per slab of the eigenvector routes: ``2^28 // (16 n_modes^2)`` -- 256 MiB of complex vectors."""
+    return max(1, VEC_SLAB_BYTES // (16 * int(n_modes) ** 2))
+
+
+def _vec_limit(n):
+    if n > VEC_MAX_ATOMS:
+        raise ValueError(f"harmonic: eigenvectors on the q-mesh take cells of at most {VEC_MAX_ATOMS} atoms (V is held beside D(q) "
+                         f"in LDS), this one has {n}")
+
+
+def _mesh_vec_call(ctx, n, n_sc, flat, inv_sqrt_m, terms, w, q, cell, cutoff, want_vec, want_vel):
+    lam = np.empty((len(q), 3 * n))
+    status = np.empty(len(q), dtype=np.int32)
+    vec = np.empty((len(q), 3 * n, 3 * n), dtype=np.complex128) if want_vec else None
+    vel = np.empty((len(q), 3 * n, 3)) if want_vel else None
+    addr = _lib._addr
+    ctx.check(ctx.lib.uf3_phonon_mesh_vec(ctx.handle, n, n_sc, addr(flat), addr(inv_sqrt_m), len(terms), addr(terms), addr(w), len(q),
+                                          addr(q), addr(lam), addr(status), addr(cell), float(cutoff), addr(vec), addr(vel)))
+    if np.any(status < 0):
+        bad = np.flatnonzero(status < 0)
+        raise RuntimeError(f"harmonic.mesh_eigenvectors: the Jacobi iteration did not converge within its sweep cap at {len(bad)} "
+                           f"q-point(s), the first q = {q[bad[0]].tolist()}")
+    return lam, status, vec, vel
+
+
+def _mesh_vec_setup(fc_rows, atoms, qpoints, n_super, masses, what):
+    n = _frame(atoms)
+    _vec_limit(n)
+    fc = np.asarray(fc_rows, dtype=float)
+    n_sc = n * int(n_super) ** 3
+    if fc.shape != (n, n_sc, 3, 3):
+        raise ValueError(f"harmonic.{what}: fc_rows must be [{n}, {n_sc}, 3, 3], got {fc.shape}")
+    q = np.ascontiguousarray(np.atleast_2d(np.asarray(qpoints, dtype=float)))
+    if q.ndim != 2 or q.shape[1] != 3 or len(q) < 1:
+        raise ValueError(f"harmonic.{what}: qpoints must be [nq, 3] with nq >= 1")
+    m = np.asarray(masses, dtype=float).reshape(-1)
+    if m.shape != (n,) or np.any(m <= 0):
+        raise ValueError(f"harmonic.{what}: one positive mass per atom")
+    flat = np.ascontiguousarray(fc.transpose(0, 2, 1, 3).reshape(3 * n, 3 * n_sc))
+    inv_sqrt_m = np.ascontiguousarray(1.0 / np.sqrt(m))
+    terms, w = image_terms(atoms, n_super)
+    cell = np.ascontiguousarray(np.asarray(atoms.get_cell(), dtype=float).reshape(3, 3))
+    return n, n_sc, flat, inv_sqrt_m, terms, w, q, cell
+
+
+def mesh_eigenvectors(fc_rows, atoms, qpoints, n_super, masses, velocities=False, device=None, cutoff_THz=1e-3, vectors=True):
+    """Eigenpairs of D(q) on the device (``uf3_phonon_mesh_vec``): ``(lam [nq, 3N] ascending, vec [nq, 3N, 3N] complex)`` and,
+    with ``velocities=True``, ``vel [nq, 3N, 3]`` (THz A; 1 THz A = 100 m / s).  Arguments as for ``mesh_eigenvalues``, whose
+    ``lam`` this returns bit for bit; ``vec[k][:, s]`` is an orthonormal eigenvector of ``lam[k, s]`` (row 3 i + alpha: atom i,
+    Cartesian alpha; the convention of ``dynamical_matrices``, without the phase exp(2 pi i q.r_i)).  vel = d f / d k by
+    Hellmann-Feynman, k the Cartesian wave vector without 2 pi; modes with |f| <= ``cutoff_THz`` get 0.  Inside a degenerate
+    cluster of modes any orthonormal basis is a correct answer, and the velocities of its members depend on the basis the
+    Jacobi sweeps ended in: only the cluster's sum is defined.  ``vectors=False`` (with velocities) leaves vec out (None).
+    The q-points go through in slabs of ``vector_slab(3N)`` = 2^28 // (16 (3N)^2) points (256 MiB of vectors); the result
+    does not depend on the cut.  Cells of more than ``VEC_MAX_ATOMS`` = 21 atoms raise ValueError, a q-point that does not
+    converge RuntimeError."""
+    if not vectors and not velocities:
+        raise ValueError("harmonic.mesh_eigenvectors: nothing asked for (vectors=False without velocities)")
+    if not float(cutoff_THz) >= 0:
+        raise ValueError("harmonic.mesh_eigenvectors: cutoff_THz must be >= 0")
+    n, n_sc, flat, ism, terms, w, q, cell = _mesh_vec_setup(fc_rows, atoms, qpoints, n_super, masses, "mesh_eigenvectors")
+    ctx = _mesh_context(device)
+    slab = vector_slab(3 * n)
+    parts = [_mesh_vec_call(ctx, n, n_sc, flat, ism, terms, w, np.ascontiguousarray(q[k:k + slab]), cell, cutoff_THz, vectors,
+                            velocities) for k in range(0, len(q), slab)]
+    lam, _, vec, vel = (parts[0] if len(parts) == 1 else
+                        tuple(None if parts[0][j] is None else np.concatenate([p[j] for p in parts]) for j in range(4)))
+    return (lam, vec, vel) if velocities else (lam, vec)
+
+
+def pdos_from_eigenvectors(lam, vec, weights=None, samples=None, sigma=None, device=None):
+    """``uf3_phonon_pdos``: [n_modes, n_samples], the Gaussian-smeared DOS of every channel 3 i + alpha, from lam [nq, n_modes]
+    and vec [nq, n_modes, n_modes] as ``mesh_eigenvectors`` returns them; normalised like ``dos_from_eigenvalues``."""
+    lam = np.ascontiguousarray(lam, dtype=float)
+    vec = np.ascontiguousarray(vec, dtype=np.complex128)
+    if lam.ndim != 2 or lam.size == 0 or vec.shape != lam.shape + (lam.shape[1],):
+        raise ValueError("harmonic.pdos_from_eigenvectors: lam must be [nq, n_modes] and vec [nq, n_modes, n_modes]")
+    nq, nm = lam.shape
+    w = _weights(weights, nq)
+    samples = np.ascontiguousarray(samples, dtype=float).reshape(-1)
+    if sigma is None or not float(sigma) > 0:
+        raise ValueError("harmonic.pdos_from_eigenvectors: sigma must be positive")
+    out = np.zeros((nm, len(samples)))
+    ctx = _mesh_context(device)
+    addr = _lib._addr
+    ctx.check(ctx.lib.uf3_phonon_pdos(ctx.handle, nm, nq, addr(lam), addr(vec), addr(w), len(samples), addr(samples), float(sigma),
+                                      addr(out)))
+    return out
+
+
+def tdisp_from_eigenvectors(lam, vec, masses, temperatures, weights=None, cutoff_THz=1e-3, device=None):
+    """``uf3_phonon_tdisp``: ``(U6 [nT, N, 6] in A^2 -- xx, yy, zz, yz, xz, xy --, n_excluded)`` from lam [nq, 3N], vec
+    [nq, 3N, 3N] and per-atom masses (amu)."""
+    lam = np.ascontiguousarray(lam, dtype=float)
+    vec = np.ascontiguousarray(vec, dtype=np.complex128)
+    if lam.ndim != 2 or lam.size == 0 or lam.shape[1] % 3 or vec.shape != lam.shape + (lam.shape[1],):
+        raise ValueError("harmonic.tdisp_from_eigenvectors: lam must be [nq, 3N] and vec [nq, 3N, 3N]")
+    nq, nm = lam.shape
+    m = np.asarray(masses, dtype=float).reshape(-1)
+    if m.shape != (nm // 3,) or np.any(m <= 0):
+        raise ValueError("harmonic.tdisp_from_eigenvectors: one positive mass per atom")
+    w = _weights(weights, nq)
+    T = np.ascontiguousarray(np.atleast_1d(np.asarray(temperatures, dtype=float)).reshape(-1))
+    if len(T) < 1 or not np.all(np.isfinite(T)) or np.any(T < 0):
+        raise ValueError("harmonic.tdisp_from_eigenvectors: temperatures must be finite and >= 0")
+    if not float(cutoff_THz) >= 0:
+        raise ValueError("harmonic.tdisp_from_eigenvectors: cutoff_THz must be >= 0")
+    ism = np.ascontiguousarray(1.0 / np.sqrt(m))
+    out = np.empty((len(T), nm // 3, 6))
+    n_excl = np.empty(1, dtype=np.int64)
+    ctx = _mesh_context(device)
+    addr = _lib._addr
+    ctx.check(ctx.lib.uf3_phonon_tdisp(ctx.handle, nm // 3, nq, addr(lam), addr(vec), addr(w), addr(ism), len(T), addr(T),
+                                       float(cutoff_THz), addr(out), addr(n_excl)))
+    return out, int(n_excl[0])
+
+
+def _slabs(calc, atoms, mesh, n_super, masses, gamma_centred, time_reversal, what):
+    """(generator of (lam, vec, w) per q-slab; q, w, m): one Hessian call, then ``mesh_eigenvectors`` slab by slab."""
+    _periodic(atoms, what)
+    n = _frame(atoms)
+    _vec_limit(n)
+    m = _masses(atoms, masses)
+    q, w = _mesh_points(mesh, None, gamma_centred, time_reversal)
+    fc = _supercell_rows(calc, atoms, n_super)
+    slab = vector_slab(3 * n)
+
+    def gen():
+        for k in range(0, len(q), slab):
+            lam, vec = mesh_eigenvectors(fc, atoms, q[k:k + slab], n_super, m, device=calc.device)
+            yield lam, vec, w[k:k + slab]
+    return gen, q, w, m
+
+
+def group_pdos(channels, atoms, by):
+    """Sum the channel-resolved PDOS [3N, n_samples] into groups: ``(pdos [n_groups, n_samples], labels)``.  ``by="channel"``: as
+    is, labels (i, "x" | "y" | "z"); ``"atom"``: the three channels of an atom, labels the atom indices; ``"species"``: the
+    atoms of a chemical symbol in order of first appearance, labels the symbols (atomic numbers when the frame has none)."""
+    channels = np.asarray(channels, dtype=float)
+    n = channels.shape[0] // 3
+    if by == "channel":
+        return channels, [(i, "xyz"[a]) for i in range(n) for a in range(3)]
+    per_atom = channels.reshape(n, 3, -1).sum(axis=1)
+    if by == "atom":
+        return per_atom, list(range(n))
+    if by == "species":
+        try:
+            names = list(atoms.get_chemical_symbols())
+        except AttributeError:
+            names = [int(z) for z in atoms.get_atomic_numbers()]
+        labels = list(dict.fromkeys(names))
+        return np.array([per_atom[[k for k, s in enumerate(names) if s == lab]].sum(axis=0) for lab in labels]), labels
+    raise ValueError(f"harmonic.projected_dos: by must be 'atom', 'species' or 'channel', got {by!r}")
+
+
+def projected_dos(calc, atoms, mesh, n_super=5, masses=None, sigma=None, frequencies=None, n_samples=401, cutoff_THz=1e-3,
+                  gamma_centred=True, time_reversal=True, by="atom"):
+    """
+    Projected phonon density of states on a q-mesh, all on the device.  dict:
+      ``frequencies`` [n_samples] THz, ``sigma``    as ``density_of_states``
+      ``pdos`` [n_groups, n_samples]                g_c(f) = Sigma_q w_q Sigma_s |V_cs|^2 gaussian(f - f_s) / Sigma_q w_q summed over the
+                                                    channels of a group; ``by``: "atom", "species" or "channel" (``group_pdos``)
+      ``labels``                                    one per group
+      ``dos`` [n_samples]                           the total: the sum of the groups (V is unitary)
+      ``channels`` [3N, n_samples], ``n_imaginary``, ``qpoints``, ``weights``, ``mode_frequencies``
+    Inside a degenerate cluster the vectors are one orthonormal basis of many, which the PDOS does not see: such modes share
+    their frequency.  Meshes go through in q-slabs of ``vector_slab(3N)`` = 2^28 // (16 (3N)^2) points, added in slab order.
+    Cells of more than 21 atoms raise ValueError.
+    """
+    if by not in ("atom", "species", "channel"):
+        raise ValueError(f"harmonic.projected_dos: by must be 'atom', 'species' or 'channel', got {by!r}")
+    gen, q, w, _ = _slabs(calc, atoms, mesh, n_super, masses, gamma_centred, time_reversal, "projected_dos")
+    slabs = list(gen()) if len(q) <= vector_slab(3 * _frame(atoms)) else None
+    # the sample range needs every frequency first: with more than one slab the vectors are computed twice, not kept
+    f = eigenvalues_to_frequencies(np.concatenate([s[0] for s in (slabs if slabs is not None else gen())]))
+    f_max = max(float(np.abs(f).max()), 1e-6)
+    sigma = f_max / 100.0 if sigma is None else float(sigma)
+    if not sigma > 0:
+        raise ValueError("harmonic.projected_dos: sigma must be positive")
+    if frequencies is None:
+        frequencies = np.linspace(float(f.min()) - 6 * sigma, float(f.max()) + 6 * sigma, int(n_samples))
+    frequencies = np.ascontiguousarray(frequencies, dtype=float)
+    wsum = float(w.sum())
+    channels = None
+    for lam, vec, ws in (slabs if slabs is not None else gen()):
+        part = pdos_from_eigenvectors(lam, vec, ws, samples=frequencies, sigma=sigma, device=calc.device)
+        part = part if len(ws) == len(w) else part * (float(ws.sum()) / wsum)
+        channels = part if channels is None else channels + part
+    pdos, labels = group_pdos(channels, atoms, by)
+    n_imag = int((w[:, None] * (f < -float(cutoff_THz))).sum())
+    if n_imag:
+        warnings.warn(f"harmonic.projected_dos: {n_imag} imaginary mode(s) on the mesh (lowest {f.min():.4g} THz): the "
+                      "structure is dynamically unstable", RuntimeWarning)
+    return {"frequencies": frequencies, "pdos": pdos, "labels": labels, "dos": channels.sum(axis=0), "channels": channels,
+            "n_imaginary": n_imag, "sigma": sigma, "qpoints": q, "weights": w, "mode_frequencies": f}
+
+
+def voigt6_to_tensors(u6):
+    """[..., 6] (xx, yy, zz, yz, xz, xy) -> symmetric [..., 3, 3]."""
+    u6 = np.asarray(u6, dtype=float)
+    U = np.empty(u6.shape[:-1] + (3, 3))
+    for k, (a, b) in enumerate(_VOIGT):
+        U[..., a, b] = U[..., b, a] = u6[..., k]
+    return U
+
+
+def thermal_displacements(calc, atoms, temperatures, mesh, n_super=5, masses=None, cutoff_THz=1e-3, gamma_centred=True,
+                          time_reversal=True):
+    """
+    Mean-square thermal displacement tensors (Debye-Waller factors) in the harmonic approximation, on the device.  dict:
+      ``U`` [n_T, N, 3, 3] A^2    U_i^{ab}(T) = (1 / Sigma w_q) Sigma_q w_q Sigma_s E_s(T) / (m_i lam_s) Re(V_{3i+a,s} conj V_{3i+b,s}),
+                                  E_s = h f_s (1/2 + 1 / (e^x - 1)), x = h f_s / k_B T; T = 0: the zero-point motion
+      ``u_iso`` [n_T, N] A^2      tr U / 3
+      ``n_excluded``              summed q-weight of the modes with f <= cutoff_THz, left out (Gamma's acoustic modes, whose
+                                  term diverges; imaginary modes too), ``n_imaginary`` as ``thermal_properties``
+      ``temperatures``
+    Meshes go through in q-slabs of ``vector_slab(3N)`` = 2^28 // (16 (3N)^2) points, added in slab order.  Cells of more than
+    21 atoms raise ValueError.
+    """
+    gen, q, w, m = _slabs(calc, atoms, mesh, n_super, masses, gamma_centred, time_reversal, "thermal_displacements")
+    T = np.ascontiguousarray(np.atleast_1d(np.asarray(temperatures, dtype=float)).reshape(-1))
+    wsum = float(w.sum())
+    u6, n_excl, lams = None, 0, []
+    for lam, vec, ws in gen():
+        part, nx = tdisp_from_eigenvectors(lam, vec, m, T, ws, cutoff_THz=cutoff_THz, device=calc.device)
+        part = part if len(ws) == len(w) else part * (float(ws.sum()) / wsum)
+        u6 = part if u6 is None else u6 + part
+        n_excl += nx
+        lams.append(lam)
+    f = eigenvalues_to_frequencies(np.concatenate(lams))
+    n_imag = int((w[:, None] * (f < -float(cutoff_THz))).sum())
+    if n_imag:
+        warnings.warn(f"harmonic.thermal_displacements: {n_imag} imaginary mode(s) on the mesh (lowest {f.min():.4g} THz) are left "
+                      "out of the sums: the structure is dynamically unstable", RuntimeWarning)
+    U = voigt6_to_tensors(u6)
+    return {"temperatures": T, "U": U, "u_iso": np.trace(U, axis1=-2, axis2=-1) / 3.0, "n_excluded": int(n_excl),
+            "n_imaginary": n_imag}
+
+
+def group_velocities(calc, atoms, qpoints, n_super=5, masses=None, cutoff_THz=1e-3):
+    """Phonon group velocities at reduced wave vectors ``qpoints`` [nq, 3]: ``(frequencies [nq, 3N] THz ascending, velocities
+    [nq, 3N, 3] THz A)``, v = d f / d k with k the Cartesian wave vector without 2 pi (1 THz A = 100 m / s), from the device's
+    eigenvectors by Hellmann-Feynman (``mesh_eigenvectors``; no finite differences).  Modes with |f| <= ``cutoff_THz`` get 0
+    (Gamma's acoustic modes, where the slope is not defined).  Inside a degenerate cluster of modes only the sum of the
+    members' velocities is defined; they are not diagonalised there."""
+    _periodic(atoms, "group_velocities")
+    m = _masses(atoms, masses)
+    _vec_limit(_frame(atoms))
+    fc = _supercell_rows(calc, atoms, n_super)
+    lam, _, vel = mesh_eigenvectors(fc, atoms, qpoints, n_super, m, velocities=True, device=calc.device, cutoff_THz=cutoff_THz,
+                                    vectors=False)
+    return eigenvalues_to_frequencies(lam), vel
 
 
 # ----------------------------------------------------------------------------------------------------- elastic constants
