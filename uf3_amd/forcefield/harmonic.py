@@ -106,27 +106,115 @@ def supercell(atoms, n_super):
     return Atoms(numbers=numbers, positions=sc_pos.reshape(-1, 3), cell=cell * n_super, pbc=True)
 
 
+def _pair_reduced(sup):
+    """``(red, M)``: a basis ``red = M @ sup`` of the lattice of ``sup``'s rows, M integer with det +-1, in which no row gets
+    shorter by adding a multiple of another (Gauss's reduction, pair by pair until nothing changes).  It only keeps the search
+    of ``nearest_images`` small on a skewed description; any basis of the lattice gives the same images."""
+    red = np.array(sup, dtype=float)
+    M = np.eye(3, dtype=np.int64)
+    changed = True
+    while changed:
+        changed = False
+        for a in range(3):
+            for b in range(3):
+                k = int(np.rint((red[a] @ red[b]) / (red[b] @ red[b]))) if a != b else 0
+                if k:
+                    new = red[a] - k * red[b]
+                    if new @ new < (red[a] @ red[a]) * (1.0 - 1e-12):
+                        red[a], changed = new, True
+                        M[a] -= k * M[b]
+    return M.astype(float) @ np.asarray(sup, dtype=float), M
+
+
+_IMAGE_CHUNK = 1 << 22                 # candidate translations held at a time by nearest_images
+
+
+def nearest_images(sup, v, tol=1e-5):
+    """The translations of the lattice of ``sup``'s rows that bring the separations ``v`` [P, 3] nearest to the origin:
+    ``(pair int64 [m], K int64 [m, 3], mult int64 [P], examined int64 [P])`` -- for every pair, in order, each integer triple K
+    with ``|v + K @ sup| <= min + tol``, in the order of the triple; ``mult`` their number and ``examined`` the number of
+    candidate translations the pair's search box holds.
+
+    Every such translation is found, for any basis of the lattice and any ``v`` (atoms outside their cell included); the search
+    is sized from the geometry.  With ``red = M @ sup`` the pair-reduced basis, ``v`` is taken into red's fractional
+    [-1/2, 1/2)^3, which gives a lattice image of length L; an image no longer than L + tol has |fractional coordinate a| <=
+    (L + tol) / h_a, h_a the spacing of red's lattice planes a, and those integer boxes are the candidates: 8 to 27 per pair
+    on a compact cell.  The lengths are those of ``(v + K @ sup)`` evaluated in that order."""
+    sup = np.asarray(sup, dtype=float).reshape(3, 3)
+    v = np.asarray(v, dtype=float).reshape(-1, 3)
+    red, M = _pair_reduced(sup)
+    inv = np.linalg.inv(red)
+    per_h = np.sqrt((inv * inv).sum(axis=0))                     # 1 / h_a: |column a of red^-1|
+    f = v @ inv
+    if not np.all(np.abs(f) < 2.0 ** 52):
+        raise ValueError("harmonic.nearest_images: a separation is not finite, or too many cells long to resolve a lattice vector")
+    n0 = -np.floor(f + 0.5)
+    fr = f + n0
+    reach = (np.sqrt((((fr @ red)) ** 2).sum(axis=1)) + tol)[:, None] * per_h[None, :] * (1.0 + 1e-9) + 1e-12
+    lo = np.ceil(-reach - fr).astype(np.int64)
+    hi = np.floor(reach - fr).astype(np.int64)
+    assert np.all(hi >= lo)
+    n0 = n0.astype(np.int64)
+    examined = (hi - lo + 1).prod(axis=1)
+    pairs, Ks, mult = [], [], np.empty(len(v), dtype=np.int64)
+    start = 0
+    while start < len(v):
+        # as many pairs at a time as keep the padded box of candidates within _IMAGE_CHUNK
+        stop, width = start, np.zeros(3, dtype=np.int64)
+        if (len(v) - start) * int((hi - lo + 1)[start:].max(axis=0).prod()) <= _IMAGE_CHUNK:
+            stop, width = len(v), (hi - lo + 1)[start:].max(axis=0)
+        while stop < len(v):
+            wider = np.maximum(width, hi[stop] - lo[stop] + 1)
+            if stop > start and (stop + 1 - start) * int(wider.prod()) > _IMAGE_CHUNK:
+                break
+            width, stop = wider, stop + 1
+        off = np.array(list(itertools.product(*(range(int(x)) for x in width))), dtype=np.int64)      # [W, 3], triple order
+        valid = np.all(off[None, :, :] <= (hi - lo)[start:stop, None, :], axis=-1)
+        K = ((n0 + lo)[start:stop, None, :] + off[None, :, :]) @ M                                 # triples of sup's own rows
+        w = v[start:stop, None, :] + (K.reshape(-1, 3).astype(float) @ sup).reshape(K.shape)
+        d = np.where(valid, np.sqrt((w * w).sum(axis=-1)), np.inf)
+        near = d <= d.min(axis=-1, keepdims=True) + tol
+        p_idx, c_idx = np.nonzero(near)
+        mult[start:stop] = near.sum(axis=-1)
+        pairs.append(p_idx + start)
+        Ks.append(K[p_idx, c_idx])
+        start = stop
+    pair, K = np.concatenate(pairs), np.concatenate(Ks)
+    order = np.lexsort((K[:, 2], K[:, 1], K[:, 0], pair))
+    return pair[order], K[order], mult, examined
+
+
+def _cell_images(cell, pos, n_super, tol):
+    """``nearest_images`` for every primitive atom i against the atoms of the n_super^3 supercell: a generator of
+    ``(i, p int64 [m], K int64 [m, 3], n int64 [m, 3], mult int64 [m])``, the records of atom i in the order p, then triple; K
+    the supercell translation and n = shift + n_super K the triple of the image's lattice vector R = n @ cell.  The separations
+    are ((shift @ cell + pos_j) - pos_i), in that order."""
+    shifts_i = np.array(list(itertools.product(range(n_super), repeat=3)), dtype=np.int64)
+    base = shifts_i.astype(float) @ cell
+    sup = cell * n_super
+    n = len(pos)
+    for i in range(n):
+        v = ((base[:, None, :] + pos[None, :, :]) - pos[i]).reshape(-1, 3)
+        p, K, mult, _ = nearest_images(sup, v, tol)
+        yield i, p, K, shifts_i[p // n] + n_super * K, mult[p]
+
+
 def minimum_image_weights(cell, pos, n_super, tol=1e-5):
     """For every primitive atom i and supercell atom p = (image, j): the lattice vectors R (Cartesian, [3]) of the equivalent
     images of p nearest to atom i, each with weight 1 / multiplicity (phonopy's convention).  Returns a list over (i, p) of
-    (R [k, 3], weight) -- R is the primitive-lattice vector from the cell of i to the chosen image of p's cell."""
+    (R [k, 3], weight) -- R is the primitive-lattice vector from the cell of i to the chosen image of p's cell.  All the images
+    within ``tol`` of the nearest one are found (``nearest_images``), however the cell is described -- skewed, turned, or with
+    atoms outside it."""
     cell = np.asarray(cell, dtype=float).reshape(3, 3)
     pos = np.asarray(pos, dtype=float).reshape(-1, 3)
-    n = len(pos)
+    n_super = int(n_super)
     shifts = np.array(list(itertools.product(range(n_super), repeat=3)), dtype=float)
     sup = cell * n_super
-    around = np.array(list(itertools.product((-2, -1, 0, 1, 2), repeat=3)), dtype=float) @ sup
     out = []
-    for i in range(n):
-        row = []
-        for t in shifts:
-            base = t @ cell
-            for j in range(n):
-                v = base + pos[j] - pos[i] + around
-                d = np.linalg.norm(v, axis=1)
-                near = d <= d.min() + tol
-                row.append((base + around[near], 1.0 / int(near.sum())))
-        out.append(row)
+    for _, p, K, _, _ in _cell_images(cell, pos, n_super, tol):
+        R = (shifts[p // len(pos)] @ cell) + K.astype(float) @ sup
+        cuts = np.flatnonzero(np.diff(p)) + 1
+        out.append([(r, 1.0 / len(r)) for r in np.split(R, cuts)])
     return out
 
 
@@ -338,32 +426,25 @@ def qmesh(mesh, gamma_centred=True, time_reversal=True):
 def image_terms(atoms, n_super, tol=1e-5):
     """``minimum_image_weights`` as a flat list for the device: ``(terms int32 [n_terms, 5], weights [n_terms])``, one record
     (i, p, n0, n1, n2) per chosen image -- primitive atom i, supercell atom p, and the lattice vector R = n @ cell of that
-    image as integers (R is ``base + around[near]`` there, an integer combination of the cell's rows) -- in the order of that
-    function: i, then p, then the images in its order."""
+    image as integers, an integer combination of the cell's rows -- in the order of that function: i, then p, then the images
+    in the order of the triple.  Any valid description of the cell is accepted (``nearest_images``); a triple that does not fit
+    an int32 raises ValueError."""
     n_super = int(n_super)
     if n_super < 1:
         raise ValueError("harmonic: n_super must be >= 1")
     cell = np.asarray(atoms.get_cell(), dtype=float).reshape(3, 3)
     pos = np.asarray(atoms.get_positions(), dtype=float).reshape(-1, 3)
-    n = len(pos)
-    shifts_i = np.array(list(itertools.product(range(n_super), repeat=3)), dtype=np.int64)
-    around_i = np.array(list(itertools.product((-2, -1, 0, 1, 2), repeat=3)), dtype=np.int64)
-    base = shifts_i.astype(float) @ cell
-    around = around_i.astype(float) @ (cell * n_super)
     terms, weights = [], []
-    for i in range(n):
-        # v [image, j, around, 3], evaluated in minimum_image_weights's order: ((base + pos_j) - pos_i) + around
-        v = ((base[:, None, :] + pos[None, :, :]) - pos[i])[:, :, None, :] + around[None, None, :, :]
-        d = np.sqrt((v * v).sum(axis=-1))
-        near = d <= d.min(axis=-1, keepdims=True) + tol
-        t_idx, j_idx, k_idx = np.nonzero(near)
-        mult = near.sum(axis=-1)
-        rec = np.empty((len(t_idx), 5), dtype=np.int32)
+    for i, p, _, nvec, mult in _cell_images(cell, pos, n_super, tol):
+        if np.abs(nvec).max() > np.iinfo(np.int32).max:
+            raise ValueError("harmonic.image_terms: a lattice vector's integer components do not fit 32 bits; wrap the atoms "
+                             "into the cell")
+        rec = np.empty((len(p), 5), dtype=np.int32)
         rec[:, 0] = i
-        rec[:, 1] = t_idx * n + j_idx
-        rec[:, 2:] = shifts_i[t_idx] + n_super * around_i[k_idx]
+        rec[:, 1] = p
+        rec[:, 2:] = nvec
         terms.append(rec)
-        weights.append(1.0 / mult[t_idx, j_idx])
+        weights.append(1.0 / mult)
     return np.ascontiguousarray(np.concatenate(terms)), np.ascontiguousarray(np.concatenate(weights))
 
 
