@@ -575,6 +575,34 @@ int uf3_md_get_wrapped(uf3_md *md, double *pos, int32_t *images);
 int uf3_md_msd_origin(uf3_md *md, const double *origin);
 int uf3_md_run_msd(uf3_md *md, int64_t n_steps, double dt_fs, double temperature_K, double friction_per_fs, uint64_t seed,
                    double skin, int64_t thermo_every, int with_stress, double *thermo, int64_t msd_every, double *msd);
+/* Switching runs: molecular dynamics on H(lambda) = K + lambda U_uf3 + (1 - lambda) U_E with lambda moving during the run
+ * (non-equilibrium thermodynamic integration; kernels in uf3_ti.h).  U_E = 1/2 sum_i k_i |x_i - x0_i|^2 is an
+ * Einstein crystal on the reference sites x0 (Angstrom) with per-atom springs k_i (eV / Angstrom^2); all k_i = 0 leaves the
+ * scaled model alone (reversible scaling).
+ *   uf3_md_set_reference  ref_pos [N][3], finite; NULL: the current positions.  spring [N], finite and >= 0; NULL: all zero.
+ *                         Allocates the feature's device memory: an object that never switches has none of it.
+ *   uf3_md_run_switch     n_steps steps of the scheme of uf3_md_run (velocity Verlet; BAOAB when friction_per_fs > 0, 1/fs)
+ *                         with dt_fs (fs), every frame at its own temperature temperatures_K [n_frames] (K, >= 0) and its own
+ *                         lambda_f(j) = lambda_a[f] + (lambda_b[f] - lambda_a[f]) schedule[j] for the states j = 0 .. n_steps
+ *                         of the run; lambda_a, lambda_b [n_frames] and schedule [n_steps + 1] finite and in [0, 1].  Step
+ *                         j -> j + 1 kicks with F_i(j) = lambda_f(j) F_uf3,i - (1 - lambda_f(j)) k_i (x_i - x0_i), drifts,
+ *                         evaluates, and kicks with F(j + 1).  With D_f = U_uf3,f - U_E,f the work is
+ *                         W_f += (lambda_f(j + 1) - lambda_f(j)) (D_f(j) + D_f(j + 1)) / 2 (eV), summed on the device in step
+ *                         order; work [n_frames] receives the work of THIS call, so a switch made in two calls on the two
+ *                         halves of a schedule adds up to one call's.  fix_com != 0 keeps every frame's momentum where it is:
+ *                         the mixed force loses m_i / M_f times its sum over the frame, and the O-step's noise dv_i = sig_i xi_i
+ *                         loses sum_j m_j dv_j / M_f.  every > 0: records [n_steps / every][n_frames][5] =
+ *                         [lambda, U_uf3, U_E, KE, W so far] (eV) of the closed state after every every-th step; every = 0:
+ *                         records NULL.  seed, skin and the absolute step counter are uf3_md_run's: the normals are those of
+ *                         (atom, absolute step, draws 0 / 1), and a switch goes on from where a run stopped.  No atomics; the
+ *                         order of every sum depends on the atom counts alone: work and records repeat bit for bit.
+ * UF3_EINVAL with a message: an object that wraps (a spring needs the unwrapped displacement; solids do not diffuse), an
+ * object that runs at a pressure, uf3_md_run_switch before uf3_md_set_reference, and any argument outside the above (checked
+ * in parameter order). */
+int uf3_md_set_reference(uf3_md *md, const double *ref_pos, const double *spring);
+int uf3_md_run_switch(uf3_md *md, int64_t n_steps, double dt_fs, const double *temperatures_K, double friction_per_fs, uint64_t seed,
+                      double skin, const double *lambda_a, const double *lambda_b, const double *schedule, int fix_com,
+                      int64_t every, double *records, double *work);
 int uf3_philox_debug(uf3_ctx *ctx, int64_t n, const uint32_t *counters, const uint32_t *keys, uint32_t *out);
 
 /*

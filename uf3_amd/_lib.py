@@ -41,10 +41,11 @@ EXPORTS = ["uf3_ctx_create", "uf3_ctx_destroy", "uf3_ctx_set_stream", "uf3_ctx_s
            "uf3_featurize_virial", "uf3_featurize_virial_dev",
            "uf3_leverage", "uf3_leverage_dev",
            "uf3_site_rows", "uf3_site_rows_dev", "uf3_site_grade", "uf3_site_grade_dev", "uf3_md_run_grade",
-           "uf3_md_set_wrap", "uf3_md_get_wrapped", "uf3_md_msd_origin", "uf3_md_run_msd"]
+           "uf3_md_set_wrap", "uf3_md_get_wrapped", "uf3_md_msd_origin", "uf3_md_run_msd",
+           "uf3_md_set_reference", "uf3_md_run_switch"]
 
 
-SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_virial_rows.h", "uf3_leverage.h", "uf3_site_rows.h", "uf3_device.h", "uf3_md.h", "uf3_hessian.h", "uf3_relax.h", "uf3_phonon.h", "uf3_npt.h", "uf3_neb.h", "uf3_idpp.h", "uf3_mc.h", "uf3_flux.h", os.path.join("..", "..", "include", "uf3_hip.h"))
+SOURCES = ("uf3_hip.hip", "uf3_kernels.h", "uf3_feat3.h", "uf3_virial_rows.h", "uf3_leverage.h", "uf3_site_rows.h", "uf3_device.h", "uf3_md.h", "uf3_ti.h", "uf3_hessian.h", "uf3_relax.h", "uf3_phonon.h", "uf3_npt.h", "uf3_neb.h", "uf3_idpp.h", "uf3_mc.h", "uf3_flux.h", os.path.join("..", "..", "include", "uf3_hip.h"))
 
 
 def source_build_id(csrc_dir=None):
@@ -261,6 +262,8 @@ def load():
         lib.uf3_md_get_wrapped.argtypes = [vp, vp, vp]
         lib.uf3_md_msd_origin.argtypes = [vp, vp]
         lib.uf3_md_run_msd.argtypes = [vp, i64, dbl, dbl, dbl, C.c_uint64, dbl, i64, C.c_int, vp, i64, vp]
+        lib.uf3_md_set_reference.argtypes = [vp, vp, vp]
+        lib.uf3_md_run_switch.argtypes = [vp, i64, dbl, vp, dbl, C.c_uint64, dbl, vp, vp, vp, C.c_int, i64, vp, vp]
         _lib = lib
         return lib
 

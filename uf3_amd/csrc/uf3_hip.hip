@@ -25,6 +25,7 @@
 #include "uf3_virial_rows.h"
 #include "uf3_leverage.h"
 #include "uf3_md.h"
+#include "uf3_ti.h"
 #include "uf3_npt.h"
 #include "uf3_hessian.h"
 #include "uf3_relax.h"
@@ -4000,6 +4001,10 @@ struct uf3_md : Batch {
     std::vector<signed char> spec;
     DevBuf msd_spec, msd_origin, msd_partial, msd_ring;
     bool msd_origin_set = false;
+    // switching runs (uf3_md_set_reference, uf3_md_run_switch, uf3_ti.h): reference sites and springs, the chunks' partial sums,
+    // the frames' scratch (lambda, U_E, D, W, the projections' vectors), the run's per-frame parameters and its schedule
+    DevBuf ti_x0, ti_spring, ti_partial, ti_frame, ti_par, ti_sched;
+    bool ti_ready = false;
     ListWork fx;
     ~uf3_md() { fx.release(); }
     const double *cells_now() const { return npt_ready ? cells_dev.as<double>() : wrap_cells.as<double>(); }
@@ -4547,6 +4552,149 @@ extern "C" int uf3_md_run_msd(uf3_md *md, int64_t n_steps, double dt_fs, double 
     if (rc) return rc;
     return md_run_entry(md, n_steps, dt_fs, temperature_K, friction_per_fs, seed, skin, thermo_every, with_stress, thermo,
                         MdMsdSampler(md, n_steps, msd_every, msd), "uf3_md_run_msd");
+}
+
+// ------------------------------------------------------------------------------ switching runs (uf3_md_run_switch, uf3_ti.h)
+// The same state and the same loop (md_steps); the ensemble's force is the model's mixed with an Einstein crystal's, and after
+// every force call k_ti_partial / k_ti_frame close the state: lambda, U_E, the work, the projections of the step opened next.
+static int ti_refused(uf3_md *md, const std::string &who) {
+    uf3_ctx *c = md->c;
+    if (md->wrap)
+        return fail(c, UF3_EINVAL, who + ": the object wraps its positions (a spring needs the unwrapped displacement from its site, and "
+                                         "a solid does not diffuse): turn wrap off");
+    if (md->npt_ready) return fail(c, UF3_EINVAL, who + ": the object runs at a pressure: a switch is made at constant volume");
+    return UF3_OK;
+}
+
+extern "C" int uf3_md_set_reference(uf3_md *md, const double *ref_pos, const double *spring) {
+    const std::string who = "uf3_md_set_reference";
+    if (!md) return fail(nullptr, UF3_EINVAL, who + ": null md");
+    uf3_ctx *c = md->c;
+    int rc = ti_refused(md, who);
+    if (rc) return rc;
+    const size_t n = (size_t)md->natoms;
+    if (ref_pos && !md_finite(ref_pos, 3 * n)) return fail(c, UF3_EINVAL, who + ": ref_pos must be finite");
+    if (spring)
+        for (size_t i = 0; i < n; i++)
+            if (!(spring[i] >= 0.0) || !std::isfinite(spring[i])) return fail(c, UF3_EINVAL, who + ": spring must be finite and >= 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = md_chunks(md, who);
+    if (rc) return rc;
+    const size_t nf = (size_t)md->n_frames;
+    md->ti_ready = false;
+    if (md->ti_x0.ensure(24 * n) || md->ti_spring.ensure(8 * n) || md->ti_partial.ensure(8 * (size_t)md->chunks.n_blocks * UF3_TI_PART) ||
+        md->ti_frame.ensure(8 * 10 * nf) || md->ti_par.ensure(8 * 3 * nf))
+        return fail(c, UF3_ENOMEM, who + ": out of device memory");
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(md->ti_x0.p, ref_pos ? (const void *)ref_pos : md->pos.p, 24 * n, ref_pos ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    if (spring) HIPCHK(c, hipMemcpyAsync(md->ti_spring.p, spring, 8 * n, hipMemcpyHostToDevice, s));
+    else HIPCHK(c, hipMemsetAsync(md->ti_spring.p, 0, 8 * n, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    md->ti_ready = true;
+    return UF3_OK;
+}
+
+// the switching ensemble: MdVerlet's five members with k_ti_step in k_md_step's place and the frame kernels behind every force call
+struct MdSwitch {
+    uf3_md *md; TiArgs A; bool langevin; int64_t n_steps, t0; double *work;
+    MdSwitch(uf3_md *md, int64_t n_steps, double dt, double gamma, uint64_t seed, int fix_com, double *work)
+        : md(md), langevin(gamma > 0.0), n_steps(n_steps), t0(md->step), work(work) {
+        const ChunkTable &ct = md->chunks;
+        const size_t nf = (size_t)md->n_frames;
+        A.pos = md->pos.as<double>(); A.vel = md->vel.as<double>(); A.frc = md->frc.as<double>(); A.inv_m = md->inv_m.as<double>();
+        A.mass = md->mass.as<double>(); A.kin = nullptr; A.x0 = md->ti_x0.as<double>(); A.spring = md->ti_spring.as<double>();
+        A.frame_of = ct.frame_of.as<int>(); A.blk_n = ct.blk_n.as<int>(); A.frame_blk = ct.frame_blk.as<int>();
+        A.blk_lo = ct.blk_lo.as<long long>(); A.energies = md->energies.as<double>();
+        A.kT = md->ti_par.as<double>(); A.lam_a = A.kT + nf; A.lam_b = A.kT + 2 * nf; A.sched = md->ti_sched.as<double>();
+        A.partial = md->ti_partial.as<double>();
+        A.lam = md->ti_frame.as<double>(); A.ue = A.lam + nf; A.d = A.lam + 2 * nf; A.w = A.lam + 3 * nf; A.cf = A.lam + 4 * nf; A.cn = A.lam + 7 * nf;
+        A.n = md->natoms; A.dt = dt; A.c = std::exp(-gamma * dt); A.seed = (unsigned long long)seed; A.step = 0; A.j = 0;
+        A.fix_com = fix_com ? 1 : 0; A.noise = 0; A.close = A.open = 0;
+    }
+    // closes state j of the run (the positions the forces belong to)
+    int frame(int64_t j) {
+        uf3_ctx *c = md->c;
+        A.j = j; A.step = (unsigned long long)(t0 + j); A.noise = langevin && A.fix_com && j < n_steps;
+        hipLaunchKernelGGL(k_ti_partial, dim3((unsigned)md->chunks.n_blocks), dim3(UF3_MD_THREADS), 0, c->stream, A);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k_ti_frame, dim3((unsigned)md->n_frames), dim3(64), 0, c->stream, A);
+        HIPCHK(c, hipGetLastError());
+        return UF3_OK;
+    }
+    int prepare(int64_t n_rec) {
+        if (n_rec) HIPCHK(md->c, md->kin.ensure(56 * (size_t)md->natoms));
+        A.kin = md->kin.as<double>();
+        if (!md->forces_valid) { int rc = md_forces(md, false); if (rc) return rc; }
+        return frame(0);
+    }
+    int launch(int close, int open, int64_t step, int64_t record) {
+        uf3_ctx *c = md->c;
+        A.step = (unsigned long long)step; A.close = close; A.open = open;
+        const dim3 g((unsigned)((md->natoms + 255) / 256)), blk(256);
+        with_bool(langevin, [&](auto L) { return with_bool(record >= 0, [&](auto T) {
+            hipLaunchKernelGGL((k_ti_step<L, T>), g, blk, 0, c->stream, A);
+            return (int)UF3_OK; }); });
+        HIPCHK(c, hipGetLastError());
+        if (record >= 0) {
+            hipLaunchKernelGGL(k_ti_record, dim3((unsigned)md->n_frames), dim3(UF3_MD_THREADS), 0, c->stream, A,
+                               (const int64_t *)md->offsets_dev.as<int64_t>(), md->ring.as<double>() + (size_t)record * md->n_frames * UF3_TI_REC);
+            HIPCHK(c, hipGetLastError());
+        }
+        return UF3_OK;
+    }
+    int forces(int64_t k) {
+        int rc = md_forces(md, false);
+        return rc ? rc : frame(k);
+    }
+    void moved() { md->forces_valid = false; }
+    int copy_out() {
+        HIPCHK(md->c, hipMemcpyAsync(work, A.w, 8 * (size_t)md->n_frames, hipMemcpyDeviceToHost, md->c->stream));
+        return UF3_OK;
+    }
+};
+
+extern "C" int uf3_md_run_switch(uf3_md *md, int64_t n_steps, double dt_fs, const double *temperatures_K, double friction_per_fs,
+                                 uint64_t seed, double skin, const double *lambda_a, const double *lambda_b, const double *schedule,
+                                 int fix_com, int64_t every, double *records, double *work) {
+    const std::string who = "uf3_md_run_switch";
+    if (!md) return fail(nullptr, UF3_EINVAL, who + ": null md");
+    uf3_ctx *c = md->c;
+    int rc = ti_refused(md, who);
+    if (rc) return rc;
+    if (!md->ti_ready) return fail(c, UF3_EINVAL, who + ": no reference: call uf3_md_set_reference first");
+    const size_t nf = (size_t)md->n_frames;
+    if (n_steps < 0) return fail(c, UF3_EINVAL, who + ": n_steps must be >= 0");
+    if (!(dt_fs > 0.0) || !std::isfinite(dt_fs)) return fail(c, UF3_EINVAL, who + ": dt must be positive and finite");
+    if (!temperatures_K) return fail(c, UF3_EINVAL, who + ": null argument (temperatures_K)");
+    for (size_t f = 0; f < nf; f++)
+        if (!(temperatures_K[f] >= 0.0) || !std::isfinite(temperatures_K[f])) return fail(c, UF3_EINVAL, who + ": temperatures must be finite and >= 0");
+    if (!(friction_per_fs >= 0.0) || !std::isfinite(friction_per_fs)) return fail(c, UF3_EINVAL, who + ": friction must be finite and >= 0");
+    if (!(skin >= 0.0) || skin > 4.0) return fail(c, UF3_EINVAL, who + ": skin must lie in [0, 4] Angstrom");
+    if (!lambda_a || !lambda_b) return fail(c, UF3_EINVAL, who + ": null argument (lambda_a / lambda_b)");
+    for (const double *lam : {lambda_a, lambda_b})
+        for (size_t f = 0; f < nf; f++)
+            if (!(lam[f] >= 0.0 && lam[f] <= 1.0)) return fail(c, UF3_EINVAL, who + ": lambda must be finite and lie in [0, 1]");
+    if (!schedule) return fail(c, UF3_EINVAL, who + ": null argument (schedule)");
+    for (int64_t j = 0; j <= n_steps; j++)
+        if (!(schedule[j] >= 0.0 && schedule[j] <= 1.0)) return fail(c, UF3_EINVAL, who + ": schedule entries must be finite and lie in [0, 1]");
+    if (every < 0) return fail(c, UF3_EINVAL, who + ": every must be >= 0");
+    rc = md_records_check(c, who, "switch", "records", every ? n_steps / every : 0, records);
+    if (rc) return rc;
+    if (!work) return fail(c, UF3_EINVAL, who + ": null argument (work)");
+    for (size_t f = 0; f < nf; f++) work[f] = 0.0;
+    if (n_steps == 0) return UF3_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<double> par(3 * nf);
+    for (size_t f = 0; f < nf; f++) { par[f] = UF3_MD_KB * temperatures_K[f]; par[nf + f] = lambda_a[f]; par[2 * nf + f] = lambda_b[f]; }
+    if (md->ti_sched.ensure(8 * (size_t)(n_steps + 1))) return fail(c, UF3_ENOMEM, who + ": out of device memory");
+    HIPCHK(c, hipMemcpyAsync(md->ti_par.p, par.data(), 8 * 3 * nf, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(md->ti_sched.p, schedule, 8 * (size_t)(n_steps + 1), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // (par goes out of scope)
+    return with_run_skin(c, skin, [&] {
+        MdSwitch E(md, n_steps, dt_fs, friction_per_fs, seed, fix_com, work);
+        MdSampler none;
+        return md_steps(md, n_steps, every, UF3_TI_REC, records, E, none);
+    });
 }
 
 // ------------------------------------------------------------------------------ constant pressure (uf3_md_run_npt, uf3_npt.h)

@@ -524,6 +524,14 @@ class UFCalculator(_Base):
         return harmonic.thermal_properties(self, atoms, temperatures, mesh, n_super=n_super, masses=masses,
                                            cutoff_THz=cutoff_THz, **kwargs)
 
+    def get_free_energy(self, atoms, temperature_K, masses=None, **kwargs):
+        """Anharmonic Helmholtz free energy of ``atoms`` at ``temperature_K`` (K; a list gives one value each) in eV per cell, by
+        switching molecular dynamics between the model and an Einstein crystal on the device
+        (``free_energy.frenkel_ladd``, whose dict this returns: ``free_energy``, its ``standard_error``, the per-replica
+        ``delta_F`` and the ``dissipation``).  Classical nuclei; masses as for ``get_phonon_data``."""
+        from . import free_energy
+        return free_energy.frenkel_ladd(self, atoms, temperature_K, masses=masses, **kwargs)
+
     def get_phonon_pdos(self, atoms, mesh=(20, 20, 20), n_super=5, masses=None, sigma=None, by="atom", **kwargs):
         """Projected phonon density of states on a q-mesh (``harmonic.projected_dos``, its dict): ``frequencies``, ``pdos``
         [n_groups, n_samples], ``labels`` and the total ``dos``, grouped ``by`` "atom", "species" or "channel"; eigenvectors,

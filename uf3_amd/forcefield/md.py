@@ -522,6 +522,103 @@ class MolecularDynamics(Driver):
             out["msd_sums"] = ms
         return out
 
+    # ---- switching (free energies: uf3_amd.forcefield.free_energy) ----------------------------------------------------------
+    def _per_atom_spring(self, spring):
+        """``spring`` (None, a scalar, ``{symbol or Z: k}`` or [N]) as the library takes it: None or float64 [N], eV / A^2."""
+        if spring is None:
+            return None
+        if isinstance(spring, dict):
+            table = {}
+            for key, value in spring.items():
+                zk = int(key) if isinstance(key, numbers.Integral) else atomic_numbers.get(str(key))
+                if zk is None:
+                    raise ValueError(f"MolecularDynamics: unknown element {key!r} in spring")
+                table[zk] = check_real(WHO, f"spring[{key!r}]", value)
+            missing = sorted({int(q) for q in self._batch.z} - set(table))
+            if missing:
+                raise ValueError(f"MolecularDynamics: no spring for {', '.join(chemical_symbols[q] for q in missing)}")
+            return np.array([table[int(q)] for q in self._batch.z], dtype=float)
+        if np.ndim(spring) == 0:
+            k = check_real(WHO, "spring", spring)               # (refused before the batch is looked at)
+            return np.full(self._batch.n_atoms, k)
+        k = np.ascontiguousarray(np.asarray(spring, dtype=float).reshape(-1))
+        if k.size != self._batch.n_atoms:
+            raise ValueError(f"MolecularDynamics: {k.size} springs for {self._batch.n_atoms} atoms")
+        if not np.all(np.isfinite(k)) or np.any(k < 0):
+            raise ValueError("MolecularDynamics: spring must be finite and >= 0")
+        return k
+
+    def set_reference(self, positions=None, spring=None):
+        """The Einstein crystal ``switch`` couples the model to: reference sites ``positions`` [N, 3] Angstrom (default the
+        current positions) and spring constants ``spring`` in eV / A^2: a scalar, ``{symbol: k}`` or a per-atom array; None is
+        no spring at all, which leaves the scaled model alone (reversible scaling).  Not for a wrapping object and not at a
+        pressure (``UF3Error``, UF3_EINVAL)."""
+        k = self._per_atom_spring(spring)
+        p = None if positions is None else self._state_array("positions", positions)
+        self._refuse_switch("uf3_md_set_reference")
+        self.ctx.check(self.ctx.lib.uf3_md_set_reference(self._live(), _lib._p(p), _lib._p(k)))
+        self.spring = k
+
+    def _refuse_switch(self, who):
+        # (the library knows a wrapping object and one that has run at a pressure; one that only will is known here)
+        if getattr(self, "pressure_eV_A3", None) is not None:
+            raise _lib.UF3Error(1, f"{who}: the object runs at a pressure: a switch is made at constant volume")
+
+    def switch(self, n_steps, lambda_start, lambda_end, schedule="smooth", temperatures_K=None, fix_com=True, every=0):
+        """``n_steps`` steps on H(lambda) = K + lambda U_uf3 + (1 - lambda) U_E, U_E the Einstein crystal of ``set_reference``,
+        with lambda moving from ``lambda_start`` to ``lambda_end`` (scalars or one value per frame, in [0, 1]) along
+        ``schedule``: ``"linear"``, ``"smooth"`` (``free_energy.switching_schedule``) or ``n_steps + 1`` values in [0, 1], the
+        fraction of the way at every state of the run.  ``temperatures_K``: one value per frame (default the object's for all);
+        the integrator, friction, seed and step counter are ``run``'s.  ``fix_com`` keeps every frame's momentum where
+        ``initialize_velocities`` put it (force and noise are projected).  Returns ``work`` [n_frames], the switching work
+        sum (lambda(j + 1) - lambda(j)) (D(j) + D(j + 1)) / 2 with D = U_uf3 - U_E, accumulated on the device, and the records
+        of every ``every``-th step, each [n_records, n_frames]: ``lambda``, ``potential_energy`` (U_uf3), ``einstein_energy``,
+        ``kinetic_energy``, ``work_so_far``; and ``step``.  eV throughout."""
+        from uf3_amd.forcefield.free_energy import switching_schedule
+        n_steps = check_int(WHO, "n_steps", n_steps)
+        every = check_int(WHO, "every", every)
+        if not isinstance(fix_com, (bool, np.bool_)):
+            raise ValueError(f"MolecularDynamics: fix_com must be True or False, got {fix_com!r}")
+        lam = []
+        for name, value in (("lambda_start", lambda_start), ("lambda_end", lambda_end)):
+            a = np.asarray(value, dtype=float)
+            if a.ndim > 1 or not np.all(np.isfinite(a)) or np.any(a < 0) or np.any(a > 1):
+                raise ValueError(f"MolecularDynamics: {name} must be a number or one per frame, finite and in [0, 1], got {value!r}")
+            lam.append(a)
+        if isinstance(schedule, str):
+            sched = switching_schedule(n_steps, schedule)
+        else:
+            sched = np.ascontiguousarray(np.asarray(schedule, dtype=float))
+            if sched.shape != (n_steps + 1,):
+                raise ValueError(f"MolecularDynamics: schedule must hold n_steps + 1 = {n_steps + 1} values, got {list(sched.shape)}")
+            if not np.all(np.isfinite(sched)) or np.any(sched < 0) or np.any(sched > 1):
+                raise ValueError("MolecularDynamics: schedule entries must be finite and in [0, 1]")
+        dt = check_real(WHO, "timestep_fs", self.timestep_fs, strict=True)
+        gamma = check_real(WHO, "friction_per_fs", self.friction_per_fs)
+        skin = check_real(WHO, "skin", self.skin, hi=4.0)
+        seed = check_int(WHO, "seed", self.seed, 0, (1 << 64) - 1)
+        temps = np.asarray(self.temperature_K if temperatures_K is None else temperatures_K, dtype=float)
+        if temps.ndim > 1 or not np.all(np.isfinite(temps)) or np.any(temps < 0):
+            raise ValueError(f"MolecularDynamics: temperatures_K must be a number or one per frame, finite and >= 0, got {temperatures_K!r}")
+        n_frames = self._batch.n_frames
+        per_frame = []
+        for name, a in (("lambda_start", lam[0]), ("lambda_end", lam[1]), ("temperatures_K", temps)):
+            if a.ndim == 1 and a.size != n_frames:
+                raise ValueError(f"MolecularDynamics: {name} holds {a.size} values for {n_frames} frames")
+            per_frame.append(np.ascontiguousarray(np.broadcast_to(a, (n_frames,)), dtype=float))
+        lam_a, lam_b, temps = per_frame
+        self._refuse_switch("uf3_md_run_switch")
+        handle, lib, first = self._live(), self.ctx.lib, self.step
+        raw = np.zeros((n_steps // every if every else 0, n_frames, 5))
+        work = np.zeros(n_frames)
+        self.ctx.check(lib.uf3_md_run_switch(handle, n_steps, dt, _lib._p(temps), gamma, seed, skin, _lib._p(lam_a), _lib._p(lam_b),
+                                             _lib._p(sched), int(bool(fix_com)), every, _lib._p(raw) if len(raw) else None,
+                                             _lib._p(work)))
+        out = {"work": work, "step": first + max(every, 1) * np.arange(1, len(raw) + 1, dtype=np.int64)}
+        for k, name in enumerate(("lambda", "potential_energy", "einstein_energy", "kinetic_energy", "work_so_far")):
+            out[name] = raw[..., k].copy()
+        return out
+
     def _species_counts(self):
         """[n_frames, S] the atoms of every species of the basis (ascending atomic number) in every frame."""
         zs = [atomic_numbers[e] for e in self.calculator.bspline_config.chemical_system.element_list]
