@@ -162,6 +162,15 @@ int uf3_fit_first_chunk(uf3_fit *fit, double fraction);
  * holds at most max_atoms atoms (<= 0: 320000) unless it is a single frame. */
 int uf3_fit_plan_debug(int32_t n_frames, const int64_t *atom_counts, int64_t max_atoms, double first_fraction,
                        int32_t *chunk_ends, int32_t *n_chunks);
+/* The plan the evaluator makes for one launch of its centre / gather kernel, computed on the host alone (no device, no context;
+ * test surface): from the 3-body list capacity, the route (two_pass, md_step), the basis' sizes (n2 pair coefficients, n_recs knot
+ * records, cw_bytes of window table), whether the basis allows the per-bond-table instances (tab_ok) and the context holds its
+ * window table (has_window), the device's LDS grant lds_max and the switches (bit 0 UF3_EVAL_NO_TAB, 1 UF3_EVAL_NO_CW,
+ * 2 UF3_EVAL_NO_CAP16).  Out: instance (bit 0 CW, 1 WIN, 2 TAB, 3 capacity 16 as a constant), the dynamic LDS of a workgroup,
+ * the per-wave part of it (CW only, else 0) and fits (0: the launch would be refused, list too long for LDS). */
+int uf3_eval_plan_debug(int32_t cap, int two_pass, int md_step, int64_t n2, int64_t n_recs, int64_t cw_bytes, int tab_ok,
+                        int has_window, int32_t lds_max, int switches, int32_t *instance, int64_t *lds, int64_t *lds_per_wave,
+                        int32_t *fits);
 
 /* RCCL behind the C ABI (round 5; SURVEY 8b's `uf3_gram_allreduce`).  One process per GPU.  The one exchange of the path is
  * the SUM over the ranks of the packed normal-equation pieces [G_e | G_f | o_e | o_f | m_e | m_f] (and, for a decomposed

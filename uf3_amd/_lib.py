@@ -26,7 +26,7 @@ EXPORTS = ["uf3_ctx_create", "uf3_ctx_destroy", "uf3_ctx_set_stream", "uf3_ctx_s
            "uf3_pair_geometry", "uf3_distance_matrix", "uf3_direction_cosines",
            "uf3_ctx_md_skin", "uf3_ctx_md_stats",
            "uf3_featurize_ld_dev", "uf3_fit_create", "uf3_fit_destroy", "uf3_fit_reset", "uf3_fit_add", "uf3_fit_pack", "uf3_fit_info", "uf3_fit_use_flat", "uf3_fit_first_chunk",
-           "uf3_fit_plan_debug",
+           "uf3_fit_plan_debug", "uf3_eval_plan_debug",
            "uf3_comm_unique_id", "uf3_comm_init", "uf3_comm_destroy", "uf3_comm_info", "uf3_allreduce_sum_f64", "uf3_gram_allreduce",
            "uf3_pair_histogram", "uf3_pair_histogram_dev", "uf3_scan_solve_dev",
            "uf3_md_create", "uf3_md_destroy", "uf3_md_set_state", "uf3_md_get_state", "uf3_md_init_velocities", "uf3_md_run",
@@ -165,6 +165,8 @@ def load():
         lib.uf3_fit_use_flat.argtypes = [vp, vp]
         lib.uf3_fit_first_chunk.argtypes = [vp, dbl]
         lib.uf3_fit_plan_debug.argtypes = [i32, vp, i64, dbl, vp, vp]
+        lib.uf3_eval_plan_debug.argtypes = [i32, C.c_int, C.c_int, i64, i64, i64, C.c_int, C.c_int, i32, C.c_int,
+                                            C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]
         lib.uf3_comm_unique_id.argtypes = [vp, vp]
         lib.uf3_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
         lib.uf3_comm_destroy.argtypes = [vp]

@@ -10,6 +10,21 @@
 #define UF3_MAX_PAIRS 36
 #define WAVE 64
 
+// The words of a context's status block (ints in device memory, written by kernels, read by the host) as the evaluator and the
+// MD list build use them.  The block is shared: the featurizer's launches use words 2, 3 and 4 under OTHER meanings --
+// 2: candidates a pair walk needed, 3: extension-list capacity needed, 4: an atom far outside its cell was met (poll_pending) --
+// which is safe because no call mixes the two and every call zeroes the words it reads.  (Kernel bodies still index by number.)
+enum StatusWord {
+    ST_ERROR = 0,        // 1: an atom too far outside its periodic cell; 2: an element outside the basis (check_flags)
+    ST_N3_NEED = 1,      // longest 3-body list met where one outgrew the capacity (k_build_n3, the fused build of k_eval)
+    ST_MD_OUTRUN = 2,    // MD evaluator: an atom beyond skin / 2 of where the lists were built, of another species, or lists
+                         // clipped by a build nobody waited for (k_sup_reverse): the step's results are void
+    ST_MD_WARN = 3,      // MD evaluator: an atom beyond the early-warning displacement -- rebuild before the next step
+    ST_SUP_NEED = 5,     // md_build: longest superset list k_build_sup met
+    ST_N3_SEEN = 6,      // n3_tune: longest 3-body list of a build that fitted (k_max_count)
+    ST_TAIL_COUNT = 12   // k_frame_sum: workgroups done, so that the last one signals the host
+};
+
 // One record per knot interval i (t_i < x <= t_{i+1}): the six knots and the six
 // reciprocal knot differences the de Boor-Cox triangle needs.  96 bytes, 16-B aligned.
 struct KnotRec {

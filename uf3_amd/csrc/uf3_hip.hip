@@ -1259,8 +1259,8 @@ static int check_flags(uf3_ctx *c) {
     if (!c->flags.p) return UF3_OK;
     int fl[4] = {0, 0, 0, 0};
     HIPCHK(c, hipMemcpy(fl, c->flags.p, sizeof(fl), hipMemcpyDeviceToHost));
-    if (fl[0] == 2) { hipMemset(c->flags.p, 0, sizeof(fl)); return fail(c, UF3_ESPECIES, "frame contains an element outside the basis"); }
-    if (fl[0] == 1) { hipMemset(c->flags.p, 0, sizeof(fl)); return fail(c, UF3_EINVAL, "atom too far outside the periodic cell (|wrap| > 250)"); }
+    if (fl[ST_ERROR] == 2) { hipMemset(c->flags.p, 0, sizeof(fl)); return fail(c, UF3_ESPECIES, "frame contains an element outside the basis"); }
+    if (fl[ST_ERROR] == 1) { hipMemset(c->flags.p, 0, sizeof(fl)); return fail(c, UF3_EINVAL, "atom too far outside the periodic cell (|wrap| > 250)"); }
     return UF3_OK;
 }
 
@@ -1305,6 +1305,10 @@ static int n3_alloc(uf3_ctx *c, int natoms, int cap, N3Lists &n3) {
     return UF3_OK;
 }
 
+// The capacity a list gets after one of `need` entries outgrew it: 8 entries of headroom, a multiple of 8 (the evaluator's 3-body
+// lists and the MD route's superset lists alike)
+static int cap_for(int need) { return (need + 8 + 7) / 8 * 8; }
+
 static int n3_cap_estimate(const uf3_basis *b, double dens) {
     double r = b->host.rmax3;
     double est = dens > 0 ? 4.18879 * r * r * r * dens : 24.0;
@@ -1317,10 +1321,10 @@ static int n3_tune(uf3_ctx *c, const N3Lists &n3, int natoms) {
     hipStream_t st = c->stream;
     int *flags = c->flags.as<int>();
     c->n3_tuned = true;
-    HIPCHK(c, hipMemsetAsync(flags + 6, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_max_count, dim3(64), dim3(256), 0, st, n3.cnt, natoms, flags + 6);
+    HIPCHK(c, hipMemsetAsync(flags + ST_N3_SEEN, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_max_count, dim3(64), dim3(256), 0, st, n3.cnt, natoms, flags + ST_N3_SEEN);
     int seen = 0;
-    HIPCHK(c, hipMemcpyAsync(&seen, flags + 6, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&seen, flags + ST_N3_SEEN, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     c->n3_cap = std::max(8, (seen + 7) / 8 * 8);
     return UF3_OK;
@@ -1624,15 +1628,14 @@ static size_t virial_lds_bytes(int cap, int n_pair_cols, int mode) {
 // moved to (this limit - the launch's other LDS) / 6 per row.
 #define UF3_VROWS_LDS (((size_t)160 * 1024 - 1024) / 2)
 
-// Which instances of the featurizer's and the evaluator's kernels the library holds -- the dispatch below (launch_featurize,
-// feat3_stage, virial_rows_stage, eval_impl) names exactly these:
+// Which instances of the featurizer's kernels the library holds -- the dispatch below (launch_featurize, feat3_stage,
+// virial_rows_stage) names exactly these (the evaluator's k_eval: above launch_eval):
 //   k_featurize<WANT_E, WANT_F, RECS_LDS, MODE, IMG>  WANT_E or WANT_F, modes 0 .. 9; modes 10 and 11 (mode 7 with grouped windows
 //       only, mode 9 banded only) for force launches only.  IMG launches (the image-range rule) are force launches of modes
 //       1 .. 9 and carry the knot records in HBM only
 //   k_featurize3<WANT_E, EF, NR, CAP>  (EF, NR) = (3, 1), (4, 2), (5, 3), (6, 3); the list capacity at run time (CAP 0) or 16 as a
 //       constant, 24 and 32 for EF = 3 only
 //   k_virial_rows<MODE>  modes 0 .. 5
-//   k_eval<false, VIR, CAP, MD, TAB, CW, WIN>  CAP 0 or 16; CW and WIN are TAB instances, and CW exists on the MD route only
 static int launch_featurize(uf3_ctx *c, bool want_e, bool want_f, bool recs_lds, int launch_mode, bool img, unsigned grid,
                             size_t lds, const FeatArgs &A) {
     auto go = [&](auto E, auto Fo, auto R, auto M, auto I) {
@@ -2200,25 +2203,25 @@ static int md_build(uf3_basis *b, const uf3_frames *fr, const double *d_pos, con
         const int cap = md.cap;
         HIPCHK(c, md.ent.ensure(sizeof(SupEntry) * (size_t)natoms * cap));
         HIPCHK(c, md.cnt.ensure(sizeof(int) * (size_t)natoms));
-        if (!(P.small_prepared && attempt == 0)) HIPCHK(c, hipMemsetAsync(flags + 5, 0, sizeof(int), st));    // (the one-workgroup cell-list kernel has zeroed it)
+        if (!(P.small_prepared && attempt == 0)) HIPCHK(c, hipMemsetAsync(flags + ST_SUP_NEED, 0, sizeof(int), st));    // (the one-workgroup cell-list kernel has zeroed it)
         const size_t lds = (size_t)cap * 16;
         if ((int)lds > c->lds_max) return fail(c, UF3_EOVERFLOW, "MD neighbour list does not fit in LDS");
         hipLaunchKernelGGL(k_build_sup, dim3((unsigned)((natoms + 7) / 8 * 8)), dim3(64), lds, st, b->dev, P.geoms, P.frame_of, P.cl,
-                           d_pos, natoms, r_sup2, md.ent.as<SupEntry>(), md.cnt.as<int>(), cap, flags + 5);
+                           d_pos, natoms, r_sup2, md.ent.as<SupEntry>(), md.cnt.as<int>(), cap, flags + ST_SUP_NEED);
         HIPCHK(c, hipGetLastError());
         if (defer) break;
         int fl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         HIPCHK(c, hipMemcpyAsync(fl, flags, sizeof(fl), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         c->pin_in_busy = false;
-        if (fl[0]) return check_flags(c);
-        if (fl[5] <= cap) { md.cap_tuned = true; md.verify_next = false; break; }
+        if (fl[ST_ERROR]) return check_flags(c);
+        if (fl[ST_SUP_NEED] <= cap) { md.cap_tuned = true; md.verify_next = false; break; }
         if (attempt >= 5) return fail(c, UF3_EOVERFLOW, "MD neighbour capacity did not converge");
-        md.cap = (fl[5] + 8 + 7) / 8 * 8;
+        md.cap = cap_for(fl[ST_SUP_NEED]);
     }
     hipLaunchKernelGGL(k_sup_reverse, dim3((unsigned)(((natoms + 15) / 16 + 7) / 8 * 8)), dim3(256), 0, st, md.ent.as<SupEntry>(),
-                       (const int *)md.cnt.as<int>(), md.cap, natoms, P.geoms, P.frame_of, P.spec, (const int *)(flags + 5),
-                       defer ? flags + 2 : (int *)nullptr);
+                       (const int *)md.cnt.as<int>(), md.cap, natoms, P.geoms, P.frame_of, P.spec, (const int *)(flags + ST_SUP_NEED),
+                       defer ? flags + ST_MD_OUTRUN : (int *)nullptr);
     HIPCHK(c, hipGetLastError());
     // inbox of every (atom, list position): zeroed when (re)allocated -- stamps start at 1
     {
@@ -2280,155 +2283,351 @@ extern "C" int uf3_ctx_md_stats(uf3_ctx *c, int64_t *builds, int64_t *steps, int
     return UF3_OK;
 }
 
+// ---- one evaluator call, in stages ---------------------------------------------
+// eval_impl is a retry loop around: eval_route (which route), md_stage or prepare (the lists and inputs in place), eval_model
+// (the model on the device), eval_plan (which k_eval instance, how much LDS), launch_eval / launch_collect / the frame sum (the
+// launches), wait_seq and eval_verdict (does the result stand).  eval_host is the second loop around it, for host arrays.
+
+// What a caller asks of eval_impl besides frames, model and outputs.  The defaults are a whole batch whose status words
+// eval_impl looks at itself; a call site names what it sets.
+struct EvalCall {
+    int64_t atom_begin = 0, atom_end = -1;  // the atoms whose terms are wanted (-1: to the end of the batch)
+    bool centre_share = false;              // uf3_eval_centres: a block of centres, not of atoms (see EvalRoute::centres)
+    // eval_host's calls: the status words travel with the results and eval_host gives the verdict
+    int *deferred_cap = nullptr;            // out: the list capacity nobody has checked yet (0: none); eval_impl does not wait
+    int *flags_tail = nullptr;              // device block behind the results: the last kernel copies the status words there
+    double *mirror = nullptr;               // pinned block the last kernel writes results, forces and its sequence number into
+};
+
+// The route of a call, decided once.
+struct EvalRoute {
+    int64_t atom_lo, atom_hi;   // the range, its end resolved
+    bool whole;                 // ... and whether it is the batch
+    // a block of CENTRES (uf3_eval_centres): the two-pass route on the block -- every triplet once, at its centre inside the
+    // block; the collection pass then serves the block and its halo (the atoms the block's lists mention), whose lists are
+    // built for that purpose.  Rows of all other atoms stay zero; the shares of disjoint blocks add up to the frame.
+    bool centres;
+    // whole batch (or block of centres) with forces and 3-body terms: every triplet once, at its centre, + a collection pass;
+    // otherwise the gather instances -- a block of atoms (its neighbours' centres may lie outside the block): every atom walks
+    // the triplets it belongs to
+    bool two_pass;
+    // two-pass route, list capacity known: the centre pass builds each atom's 3-body list from the candidates of its own pair
+    // walk (no k_build_n3 launch, one neighbourhood scan less)
+    bool fuse;
+    // MD route: the candidates of every atom from the context's persistent lists instead of a cell-list walk (see md_build)
+    bool md_step;
+    // a block of centres with the fused list build zeroes rows, list counts and halo marks in ONE launch (k_zero3)
+    bool zero3;
+};
+static int eval_route(const uf3_basis *b, const uf3_frames *fr, const EvalCall &call, bool forces, EvalRoute &R) {
+    uf3_ctx *c = b->ctx;
+    const int64_t total = (fr && fr->atom_offsets && fr->n_frames >= 1) ? fr->atom_offsets[fr->n_frames] : -1;
+    // (the one range check: prepare refuses a batch without a total, and a batch that passes it -- or matches the key of the
+    // MD lists, whose offsets are compared -- holds exactly `total` atoms.  An open end with a begin past the total, which only
+    // the check behind the staging used to catch, is caught here: no entry can ask for it today, they refuse an open end)
+    if (total >= 0 && (call.atom_begin < 0 || call.atom_begin > total ||
+                       (call.atom_end >= 0 && (call.atom_begin > call.atom_end || call.atom_end > total))))
+        return fail(c, UF3_EINVAL, "uf3_eval_atoms: atom range outside the batch");
+    const bool three = forces && b->host.T > 0;
+    R.atom_lo = call.atom_begin;
+    R.atom_hi = call.atom_end < 0 ? total : call.atom_end;
+    R.whole = call.atom_begin == 0 && (call.atom_end < 0 || call.atom_end == total);
+    R.centres = call.centre_share && !R.whole && three && call.atom_end > call.atom_begin;
+    R.two_pass = (R.whole || R.centres) && three && !uf3_env("UF3_EVAL_GATHER");
+    R.fuse = R.two_pass && c->n3_tuned && c->n3_cap > 0 && !uf3_env("UF3_SEPARATE_N3");
+    R.md_step = c->md.skin > 0.0 && R.fuse && !uf3_env("UF3_NO_MD");      // (a block of centres too: round 5)
+    R.zero3 = R.centres && R.fuse && !R.md_step && !uf3_env("UF3_NO_HALO");
+    return UF3_OK;
+}
+
+// MD route: everything a step reads is put in place, in exactly one of five ways -- new lists (which bring their own inputs), or
+// the lists stand and only positions | species and zeroed status words are due -- and `P` describes it (md_prepared).
+// was_clean: the words are known to be zero (the previous call was an MD step of the host entry that set none).
+static int md_stage(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, bool was_clean, Prepared &P) {
+    uf3_ctx *c = b->ctx;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->md.stale || !md_key_matches(c->md, b, fr)) {
+        int rc = md_build(b, fr, d_pos, d_z, P, true);
+        if (rc) return rc;
+    } else if (c->md.live) {
+        // (the integrator's frame kernel has zeroed the step's status words and its move kernel has raised those of the list test)
+    } else if (c->staged_in_dev && d_pos == (const double *)c->stage_cur) {
+        // positions | species are in the device block already (upload_frames, through the BAR).  k_md_fetch also zeroed the
+        // step's status words: needed only when they are not known to be zero (was_clean: the host has just read them)
+        c->staged_in_dev = 0;
+        if (!was_clean)
+            hipLaunchKernelGGL(k_md_fetch, dim3(1), dim3(64), 0, st, (const int4 *)nullptr, (int4 *)nullptr, 0, c->flags.as<int>());
+    } else if (c->pin_in_pending && d_pos == (const double *)c->stage_cur) {
+        // a small batch staged by upload_frames: positions | species are still in the caller's pinned block
+        const size_t at = c->pin_in_pending;
+        c->pin_in_pending = 0;
+        if (c->md.natoms <= UF3_SMALL_ATOMS && !uf3_env("UF3_NO_ZERO_COPY")) {
+            hipLaunchKernelGGL(k_md_fetch, dim3(1), dim3(256), 0, st, (const int4 *)c->pin_in.p, (int4 *)c->stage_cur, (int)(at / 16),
+                               c->flags.as<int>());
+            c->pin_in_busy = true;
+        } else {
+            HIPCHK(c, hipMemcpyAsync(c->stage_cur, c->pin_in.p, at, hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipEventRecord(c->pin_in_done, st));
+            HIPCHK(c, hipMemsetAsync(c->flags.as<int>() + ST_N3_NEED, 0, 4 * sizeof(int), st));
+        }
+    } else
+        HIPCHK(c, hipMemsetAsync(c->flags.as<int>() + ST_N3_NEED, 0, 4 * sizeof(int), st));
+    md_prepared(c, P);
+    return UF3_OK;
+}
+
+// The model on the device: c1 | c2 | c3 in c->coeff, and the window table of the CW / WIN instances where the model allows one
+// (c->cw_of).  An MD loop passes the same model every step: it is uploaded -- and the caller's buffers waited for, the one
+// hipStreamSynchronize -- only when it differs from the host shadow; the unchanged path is three memcmps.
+static int eval_model(uf3_basis *b, const double *c1, const double *c2, const double *c3, const double *&model) {
+    uf3_ctx *c = b->ctx;
+    hipStream_t st = c->stream;
+    const size_t n1 = (size_t)b->host.S, n2 = b->c2_len, n3 = b->c3_len;
+    HIPCHK(c, c->coeff.ensure(8 * (n1 + n2 + n3 + 1)));
+    double *dc = c->coeff.as<double>();
+    model = dc;
+    std::vector<double> &sh = c->coeff_shadow;
+    const bool same = c->coeff_dev == (const void *)dc && sh.size() == n1 + n2 + n3 && !memcmp(sh.data(), c1, 8 * n1) &&
+                      (!n2 || !memcmp(sh.data() + n1, c2, 8 * n2)) && (!n3 || !memcmp(sh.data() + n1 + n2, c3, 8 * n3));
+    if (same) return UF3_OK;
+    sh.resize(n1 + n2 + n3);
+    memcpy(sh.data(), c1, 8 * n1);
+    if (n2) memcpy(sh.data() + n1, c2, 8 * n2);
+    if (n3) memcpy(sh.data() + n1 + n2, c3, 8 * n3);
+    c->coeff_dev = nullptr;
+    HIPCHK(c, hipMemcpyAsync(dc, sh.data(), 8 * sh.size(), hipMemcpyHostToDevice, st));
+    // the window table of the CW instances: only when every coefficient outside the kept-bin window of the centre legs is
+    // exactly zero (bins without a column decompress to zero: any fitted or loaded model; arbitrary grids keep the global rows)
+    c->cw_of = nullptr;
+    std::vector<double> tab;
+    if (b->eval_cw_ok && n3) {
+        const double *g3 = sh.data() + n1 + n2;
+        const int lo = b->cw_lo, ext = b->cw_ext, dm = b->cw_dim_m, dn = b->cw_dim_n;
+        tab.assign((size_t)b->cw_bytes / 8, 0.0);
+        bool zero_outside = true;
+        for (size_t t = 0; t < b->cw_lut_off.size() && zero_outside; t++) {
+            const double *g = g3 + b->cw_lut_off[t];
+            for (int l = 0; l < b->cw_dim_l[t] && zero_outside; l++)
+                for (int mm = 0; mm < dm && zero_outside; mm++) {
+                    const bool in = l >= lo && l < lo + ext && mm >= lo && mm < lo + ext;
+                    const double *row = g + ((size_t)l * dm + mm) * dn;
+                    if (in) std::memcpy(tab.data() + ((t * ext + (l - lo)) * ext + (mm - lo)) * dn, row, 8 * (size_t)dn);
+                    else for (int q = 0; q < dn; q++) zero_outside = zero_outside && row[q] == 0.0;
+                }
+        }
+        if (zero_outside) {
+            HIPCHK(c, c->coeff_cw.ensure((size_t)b->cw_bytes));
+            HIPCHK(c, hipMemcpyAsync(c->coeff_cw.p, tab.data(), (size_t)b->cw_bytes, hipMemcpyHostToDevice, st));
+            c->cw_of = b;
+        }
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+    c->coeff_dev = dc;
+    return UF3_OK;
+}
+
+// The plan of one k_eval launch: which instance, how much dynamic LDS.  A pure function of numbers -- no context, no basis, no
+// HIP call (uf3_eval_plan_debug is its test surface) -- and the only place that states the bytes of the three LDS layouts.
+enum { EVAL_NO_TAB = 1, EVAL_NO_CW = 2, EVAL_NO_CAP16 = 4 };      // the switches UF3_EVAL_NO_TAB / _NO_CW / _NO_CAP16, as bits
+struct EvalPlan {
+    bool gather, md;            // the route's part of the instance: !two_pass | candidates from the persistent lists
+    bool cw, win, tab, cap16;   // centre legs from a window table in LDS | in global memory | from per-bond tables; capacity 16 as a constant
+    size_t lds;                 // dynamic LDS of the workgroup
+    size_t lds_per_wave;        // CW: bytes of the per-wave arrays of its multi-wave workgroup (else 0)
+    bool fits;                  // false: a one-wave layout larger than the device grants
+};
+static EvalPlan eval_plan(size_t cap, bool two_pass, bool md_step, size_t n2, size_t n_recs, size_t cw_bytes, bool tab_ok,
+                          bool has_window, int lds_max, int switches) {
+    EvalPlan p = {};
+    p.gather = !two_pass; p.md = md_step;
+    // own list (32 + 20 B per entry), queue of bonds, force on the entries (24), walk-order entries + keys (48)
+    const size_t lds_plain = cap * 32 + (5 * cap + 2) * 4 + 16 + 2 * WAVE * EVAL_Q * sizeof(double) + cap * 24 + cap * 48;
+    // TAB instances (centre legs from per-bond tables, k_eval): + leg n's knot records, + the tables when they do not fit
+    // over the queue.  Chosen by the basis alone -- not by the capacity -- unless the longer layout does not fit at all
+    const size_t lds_tab = lds_plain + 16 + EVAL_TAB_KN * sizeof(KnotRec) + (cap > EVAL_TAB_CAP ? 136 * cap + 16 : 0);
+    p.tab = two_pass && tab_ok && (int)lds_tab <= lds_max && !(switches & EVAL_NO_TAB);
+    // CW instances (MD route only: measured 197 against 190 M atom-steps/s there, a loss on the plain route): EVAL_CW_WAVES
+    // one-atom waves per workgroup around one copy of the window table, every knot record and the pair coefficients
+    const size_t cw_per_wave = ((md_step ? lds_plain - cap * 48 : lds_plain) + 15) / 16 * 16;      // (the walk-order arrays: fused builds only)
+    const size_t lds_cw = cw_bytes + n_recs * sizeof(KnotRec) + (n2 * 8 + 15) / 16 * 16 + EVAL_CW_WAVES * cw_per_wave;
+    p.cw = p.tab && md_step && has_window && cap <= 16 &&      /* (lists of <= 16 entries: the force gather's stage, k_eval) */
+           lds_cw <= UF3_LDS_LIMIT / (EVAL_CW_WAVES > 8 ? 1 : 2) && !(switches & EVAL_NO_CW);
+    // WIN instances: the same window table read through global memory by the one-wave TAB instances CW does not serve
+    p.win = p.tab && !p.cw && has_window && !(switches & EVAL_NO_CW);
+    p.cap16 = two_pass && cap == 16 && !(switches & EVAL_NO_CAP16);
+    p.lds = p.cw ? lds_cw : (p.tab ? lds_tab : lds_plain);
+    p.lds_per_wave = p.cw ? cw_per_wave : 0;
+    p.fits = p.cw || (int)p.lds <= lds_max;      // (CW asks for more than the default grant itself: launch_lds)
+    return p;
+}
+
+extern "C" int uf3_eval_plan_debug(int32_t cap, int two_pass, int md_step, int64_t n2, int64_t n_recs, int64_t cw_bytes, int tab_ok,
+                                   int has_window, int32_t lds_max, int switches, int32_t *instance, int64_t *lds,
+                                   int64_t *lds_per_wave, int32_t *fits) {
+    if (cap < 1 || n2 < 0 || n_recs < 0 || cw_bytes < 0 || lds_max < 0 || !instance || !lds || !lds_per_wave || !fits)
+        return fail(nullptr, UF3_EINVAL, "uf3_eval_plan_debug: bad argument");
+    const EvalPlan p = eval_plan((size_t)cap, two_pass != 0, md_step != 0, (size_t)n2, (size_t)n_recs, (size_t)cw_bytes, tab_ok != 0,
+                                 has_window != 0, lds_max, switches);
+    *instance = (p.cw ? 1 : 0) | (p.win ? 2 : 0) | (p.tab ? 4 : 0) | (p.cap16 ? 8 : 0);
+    *lds = (int64_t)p.lds; *lds_per_wave = (int64_t)p.lds_per_wave; *fits = p.fits;
+    return UF3_OK;
+}
+
+// Which instances of k_eval the library holds -- this dispatch names exactly these:
+//   k_eval<false, VIR, CAP, MD, TAB, CW, WIN>  CAP 0 or 16; CW and WIN are TAB instances, and CW exists on the MD route only
+//   k_eval<true, VIR>  the gather instances
+// instance: strain derivative | list capacity 16 as a constant | candidates from the persistent lists | centre legs from per-bond
+// tables (one set of 3-body legs, T <= 64, short lists: the usual case).  One wave per centre, CW: EVAL_CW_WAVES of them
+static int launch_eval(uf3_ctx *c, const EvalPlan &p, const EvalArgs &A, int64_t n_centres) {
+    hipStream_t st = c->stream;
+    const size_t lds = p.lds;
+    const dim3 eg((unsigned)((n_centres + 7) / 8 * 8));
+    const dim3 eg_cw((unsigned)(((n_centres + EVAL_CW_WAVES - 1) / EVAL_CW_WAVES + 7) / 8 * 8));
+    if (!p.gather)
+        return with_bool(A.virial != 0, [&](auto VIR) {
+        return with_bool(p.cap16, [&](auto C16) {
+        return with_bool(p.md, [&](auto MD) {
+            constexpr int CAP = C16 ? 16 : 0;
+            if (p.cw) {
+                // (MD route only: with the walk-order arrays of the fused list build the waves' own LDS is 7.1 KB each, and two
+                // 8-wave workgroups + two copies of the tables do not fit a CU -- 168 of 160 KB; not instantiated)
+                if constexpr (MD)
+                    HIPCHK(c, (launch_lds<k_eval<false, VIR, CAP, true, true, true>>(c, eg_cw, dim3(64 * EVAL_CW_WAVES), lds, A)));
+                else
+                    return fail(c, UF3_EINVAL, "k_eval<CW> outside the MD route");
+            }
+            else if (p.win) hipLaunchKernelGGL((k_eval<false, VIR, CAP, MD, true, false, true>), eg, dim3(64), lds, st, A);
+            else if (p.tab) hipLaunchKernelGGL((k_eval<false, VIR, CAP, MD, true>), eg, dim3(64), lds, st, A);
+            else hipLaunchKernelGGL((k_eval<false, VIR, CAP, MD, false>), eg, dim3(64), lds, st, A);
+            return (int)UF3_OK;
+        }); }); });
+    if (n_centres <= 0) return UF3_OK;
+    if (A.virial) hipLaunchKernelGGL((k_eval<true, true>), eg, dim3(64), lds, st, A);
+    else hipLaunchKernelGGL((k_eval<true, false>), eg, dim3(64), lds, st, A);
+    return UF3_OK;
+}
+
+// The collection pass behind the centre pass of the two-pass route: every atom gathers what the centres put on it -- one of three
+// kernels, by who has lists and where the shares wait.  A block of centres off the MD route first gets its halo's lists.
+// part_sums: the whole-batch pass of the MD route also leaves per-workgroup sums for the frame sum to add.
+static int launch_collect(uf3_basis *b, const Prepared &P, const EvalRoute &R, const double *d_pos, bool part_sums, EvalArgs &A) {
+    uf3_ctx *c = b->ctx;
+    hipStream_t st = c->stream;
+    const dim3 grid((unsigned)(((P.natoms + 15) / 16 + 7) / 8 * 8));
+    if (R.centres && !R.md_step) {
+        // the block's lists exist now (the centre pass built them, or prepare did): the halo's, then the collection pass over
+        // block + halo
+        if (R.fuse || uf3_env("UF3_NO_HALO")) {
+            int rh = build_halo_lists(b, P, A.n3, d_pos, (int)R.atom_lo, (int)R.atom_hi, R.zero3);
+            if (rh) return rh;
+        }
+        A.halo_mark = c->halo.as<int>();
+    }
+    if (R.md_step && R.centres)      // every atom checks itself; the block and the atoms its centres wrote to collect
+        hipLaunchKernelGGL(k_eval_collect_md_halo, dim3((unsigned)((P.natoms + 15) / 16)), dim3(256), 0, st, A);
+    else if (R.md_step) {
+        if (part_sums) {
+            const size_t n_wg = ((size_t)P.natoms + 15) / 16;
+            HIPCHK(c, c->part_sums.ensure(8 * (7 * n_wg + 2)));
+            A.part_e = c->part_sums.as<double>(); A.part_v = A.part_e + n_wg; A.part_off = (long long *)(A.part_v + 6 * n_wg);
+        }
+        hipLaunchKernelGGL(k_eval_collect_md, grid, dim3(256), 0, st, A);
+    }
+    else hipLaunchKernelGGL(k_eval_collect, grid, dim3(256), 0, st, A);
+    return UF3_OK;
+}
+
+// The polled wait of a call whose last kernel stores the call's sequence number, behind system-scope fences, into a pinned word:
+// a few us sooner than the stream's completion signal reaches the host.  Bounded (2 ms); false: not seen -- the caller falls
+// back on hipStreamSynchronize.
+static bool wait_seq(const unsigned *word, unsigned seq) {
+    const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
+    for (int spin = 0; ; spin++) {
+        if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return true;
+        if ((spin & 255) == 255 && std::chrono::steady_clock::now() > t_end) return false;
+    }
+}
+
+// What the status words `fl` of a finished evaluation say, and the consequences every caller shares: an error word is turned into
+// its error (rc), the early warning marks the MD lists stale, a 3-body list longer than the capacity used raises n3_cap.
+// EVAL_OUTRUN and EVAL_REGROWN void the results; how the call is repeated -- and how often -- is the caller's.
+enum EvalVerdict { EVAL_DONE, EVAL_OUTRUN, EVAL_REGROWN, EVAL_ERROR };
+static EvalVerdict eval_verdict(uf3_ctx *c, const int *fl, int cap_used, bool md_step, int &rc) {
+    if (fl[ST_ERROR]) { rc = check_flags(c); return EVAL_ERROR; }
+    // an atom beyond skin / 2 of where the lists were built (or of another species), or lists clipped by a build nobody waited for
+    if (md_step && fl[ST_MD_OUTRUN]) return EVAL_OUTRUN;
+    if (md_step && fl[ST_MD_WARN]) c->md.stale = true;       // (early warning: rebuild in front of the next step)
+    if (cap_used && fl[ST_N3_NEED] > cap_used) { c->n3_cap = cap_for(fl[ST_N3_NEED]); return EVAL_REGROWN; }
+    return EVAL_DONE;
+}
+
 static int eval_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z, const double *c1,
                      const double *c2, const double *c3, double *d_energies, double *d_forces, double *d_virials,
-                     int64_t atom_begin = 0, int64_t atom_end = -1, int *deferred_cap = nullptr, int *flags_tail = nullptr,
-                     double *mirror = nullptr, bool centre_share = false) {
+                     const EvalCall &call = EvalCall()) {
     uf3_ctx *c = b->ctx;
     uf3_env_refresh();
     if (!d_pos || !d_z || !c1 || !d_energies) return fail(c, UF3_EINVAL, "uf3_eval: null argument");
     if ((b->c2_len && !c2) || (b->c3_len && !c3)) return fail(c, UF3_EINVAL, "uf3_eval: missing coefficients");
-    // whole batch with forces and 3-body terms: every triplet once, at its centre, + a collection pass; a block of
-    // atoms (its neighbours' centres may lie outside the block): every atom walks the triplets it belongs to.
-    // Two-pass route, list capacity known: the centre pass builds each atom's 3-body list from the candidates of
-    // its own pair walk (no k_build_n3 launch, one neighbourhood scan less).
-    const int64_t total = (fr && fr->atom_offsets && fr->n_frames >= 1) ? fr->atom_offsets[fr->n_frames] : -1;
-    if (total >= 0 && (atom_begin < 0 || (atom_end >= 0 && (atom_begin > atom_end || atom_end > total))))
-        return fail(c, UF3_EINVAL, "uf3_eval_atoms: atom range outside the batch");
-    const bool whole = atom_begin == 0 && (atom_end < 0 || atom_end == total);
-    // a block of CENTRES (uf3_eval_centres): the two-pass route on the block -- every triplet once, at its centre inside the
-    // block; the collection pass then serves the block and its halo (the atoms the block's lists mention), whose lists are
-    // built for that purpose.  Rows of all other atoms stay zero; the shares of disjoint blocks add up to the frame.
-    const bool centres = centre_share && !whole && d_forces && b->host.T > 0 && atom_end > atom_begin;
-    const bool two_pass = (whole || centres) && d_forces && b->host.T > 0 && !uf3_env("UF3_EVAL_GATHER");
-    const bool fuse = two_pass && c->n3_tuned && c->n3_cap > 0 && !uf3_env("UF3_SEPARATE_N3");
+    EvalRoute R;
+    int rc = eval_route(b, fr, call, d_forces != nullptr, R);
+    if (rc) return rc;
     Prepared P;
-    int rc;
     hipStream_t st = c->stream;
-    // MD route: the candidates of every atom from the context's persistent lists instead of a cell-list walk (see md_build)
-    const bool md_step = c->md.skin > 0.0 && fuse && (whole || centres) && !uf3_env("UF3_NO_MD");     // (a block of centres too: round 5)
-    c->md_step = md_step;
+    c->md_step = R.md_step;
     const bool was_clean = c->md.flags_clean;      // (true only straight after an MD step of eval_host that set no status word)
     c->md.flags_clean = false;
-    if (c->md.live && (!md_step || c->md.stale || !md_key_matches(c->md, b, fr))) {
+    if (c->md.live && (!R.md_step || c->md.stale || !md_key_matches(c->md, b, fr))) {
         rc = md_live_fetch(c, fr);                  // (a list build or the rebuild route is due: both read the cells on the host)
         if (rc) return rc;
     }
-    if (md_step) {
-        HIPCHK(c, hipSetDevice(c->device));
-        if (c->md.stale || !md_key_matches(c->md, b, fr)) {
-            rc = md_build(b, fr, d_pos, d_z, P, true);
-            if (rc) return rc;
-        } else if (c->md.live) {
-            // (the integrator's frame kernel has zeroed the step's status words and its move kernel has raised those of the list test)
-        } else if (c->staged_in_dev && d_pos == (const double *)c->stage_cur) {
-            // positions | species are in the device block already (upload_frames, through the BAR).  k_md_fetch also zeroed the
-            // step's status words: needed only when they are not known to be zero (was_clean: the previous call was an MD step
-            // of the host entry that set none -- the host has just read them)
-            c->staged_in_dev = 0;
-            if (!was_clean)
-                hipLaunchKernelGGL(k_md_fetch, dim3(1), dim3(64), 0, st, (const int4 *)nullptr, (int4 *)nullptr, 0, c->flags.as<int>());
-        } else if (c->pin_in_pending && d_pos == (const double *)c->stage_cur) {
-            // a small batch staged by upload_frames: positions | species are still in the caller's pinned block
-            const size_t at = c->pin_in_pending;
-            c->pin_in_pending = 0;
-            if (c->md.natoms <= UF3_SMALL_ATOMS && !uf3_env("UF3_NO_ZERO_COPY")) {
-                hipLaunchKernelGGL(k_md_fetch, dim3(1), dim3(256), 0, st, (const int4 *)c->pin_in.p, (int4 *)c->stage_cur, (int)(at / 16),
-                                   c->flags.as<int>());
-                c->pin_in_busy = true;
-            } else {
-                HIPCHK(c, hipMemcpyAsync(c->stage_cur, c->pin_in.p, at, hipMemcpyHostToDevice, st));
-                HIPCHK(c, hipEventRecord(c->pin_in_done, st));
-                HIPCHK(c, hipMemsetAsync(c->flags.as<int>() + 1, 0, 4 * sizeof(int), st));
-            }
-        } else
-            HIPCHK(c, hipMemsetAsync(c->flags.as<int>() + 1, 0, 4 * sizeof(int), st));
-        md_prepared(c, P);
+    if (R.md_step) {
+        rc = md_stage(b, fr, d_pos, d_z, was_clean, P);
+        if (rc) return rc;
     } else {
         if (c->md.wrap) {                           // (the rebuild-everything route: every evaluation builds its lists)
             rc = c->md.wrap(d_pos);
             if (rc) return rc;
         }
-        rc = prepare(b, fr, d_pos, d_z, !fuse, P, deferred_cap != nullptr, atom_begin, whole ? -1 : atom_end);
+        rc = prepare(b, fr, d_pos, d_z, !R.fuse, P, call.deferred_cap != nullptr, call.atom_begin, R.whole ? -1 : call.atom_end);
         if (rc) return rc;
     }
-    if (deferred_cap) *deferred_cap = P.deferred ? P.n3.cap : 0;
-    size_t n1 = (size_t)b->host.S, n2 = b->c2_len, n3 = b->c3_len;
-    HIPCHK(c, c->coeff.ensure(8 * (n1 + n2 + n3 + 1)));
-    double *dc = c->coeff.as<double>();
-    // an MD loop passes the same model every step: upload (and wait for the caller's buffers) only when they changed
-    std::vector<double> &sh = c->coeff_shadow;
-    const bool same = c->coeff_dev == (const void *)dc && sh.size() == n1 + n2 + n3 && !memcmp(sh.data(), c1, 8 * n1) &&
-                      (!n2 || !memcmp(sh.data() + n1, c2, 8 * n2)) && (!n3 || !memcmp(sh.data() + n1 + n2, c3, 8 * n3));
-    if (!same) {
-        sh.resize(n1 + n2 + n3);
-        memcpy(sh.data(), c1, 8 * n1);
-        if (n2) memcpy(sh.data() + n1, c2, 8 * n2);
-        if (n3) memcpy(sh.data() + n1 + n2, c3, 8 * n3);
-        c->coeff_dev = nullptr;
-        HIPCHK(c, hipMemcpyAsync(dc, sh.data(), 8 * sh.size(), hipMemcpyHostToDevice, st));
-        // the window table of the CW instances: only when every coefficient outside the kept-bin window of the centre legs is
-        // exactly zero (bins without a column decompress to zero: any fitted or loaded model; arbitrary grids keep the global rows)
-        c->cw_of = nullptr;
-        std::vector<double> tab;
-        if (b->eval_cw_ok && n3) {
-            const double *g3 = sh.data() + n1 + n2;
-            const int lo = b->cw_lo, ext = b->cw_ext, dm = b->cw_dim_m, dn = b->cw_dim_n;
-            tab.assign((size_t)b->cw_bytes / 8, 0.0);
-            bool zero_outside = true;
-            for (size_t t = 0; t < b->cw_lut_off.size() && zero_outside; t++) {
-                const double *g = g3 + b->cw_lut_off[t];
-                for (int l = 0; l < b->cw_dim_l[t] && zero_outside; l++)
-                    for (int mm = 0; mm < dm && zero_outside; mm++) {
-                        const bool in = l >= lo && l < lo + ext && mm >= lo && mm < lo + ext;
-                        const double *row = g + ((size_t)l * dm + mm) * dn;
-                        if (in) std::memcpy(tab.data() + ((t * ext + (l - lo)) * ext + (mm - lo)) * dn, row, 8 * (size_t)dn);
-                        else for (int q = 0; q < dn; q++) zero_outside = zero_outside && row[q] == 0.0;
-                    }
-            }
-            if (zero_outside) {
-                HIPCHK(c, c->coeff_cw.ensure((size_t)b->cw_bytes));
-                HIPCHK(c, hipMemcpyAsync(c->coeff_cw.p, tab.data(), (size_t)b->cw_bytes, hipMemcpyHostToDevice, st));
-                c->cw_of = b;
-            }
-        }
-        HIPCHK(c, hipStreamSynchronize(st));
-        c->coeff_dev = dc;
-    }
+    if (call.deferred_cap) *call.deferred_cap = P.deferred ? P.n3.cap : 0;
+    const double *dc;
+    rc = eval_model(b, c1, c2, c3, dc);
+    if (rc) return rc;
+    const size_t n1 = (size_t)b->host.S, n2 = b->c2_len;
     HIPCHK(c, c->e_atom.ensure(8 * (size_t)P.natoms * (d_virials ? 7 : 1)));
-    if (atom_end < 0) atom_end = P.natoms;
-    if (atom_begin < 0 || atom_begin > atom_end || atom_end > P.natoms)
-        return fail(c, UF3_EINVAL, "uf3_eval_atoms: atom range outside the batch");
     // (atoms outside the range: the per-frame sums run over the range only)
-    EvalArgs A;
+    EvalArgs A = {};
     A.B = b->dev; A.geoms = P.geoms; A.frame_of = P.frame_of; A.cl = P.cl; A.n3 = P.n3;
     if (!A.n3.cap) A.n3.cap = 1;
     A.pos = d_pos; A.spec = P.spec; A.c1 = dc; A.c2 = dc + n1; A.c3 = dc + n1 + n2;
     A.e_atom = c->e_atom.as<double>(); A.forces = d_forces; A.natoms = P.natoms;
-    A.atom_lo = (int)atom_begin; A.atom_hi = (int)atom_end;
+    A.atom_lo = (int)R.atom_lo; A.atom_hi = (int)R.atom_hi;
     A.virial = d_virials ? A.e_atom + P.natoms : nullptr;
-    A.nbr_f = nullptr; A.n3_need = nullptr; A.fuse_n3 = 0;
-    A.halo_mark = nullptr;
-    A.c3w = nullptr; A.cw_bytes = 0; A.cw_zero = 0; A.cw_lo = 0; A.cw_ext = 0; A.lds_per_wave = 0; A.cw_recs_bytes = 0; A.cw_c2 = 0;
-    A.part_e = nullptr; A.part_v = nullptr; A.part_off = nullptr;
-    // (rows of atoms that no centre of the block touches: zero.  A block of centres with the fused list build zeroes rows, list
-    // counts and halo marks in ONE launch inside the loop below)
-    const bool zero3 = centres && fuse && !md_step && !uf3_env("UF3_NO_HALO");
-    if (centre_share && !whole && d_forces && !zero3 && !md_step)
+    // (rows of atoms that no centre of the block touches: zero -- here, or by k_zero3 inside the loop below, or, on the MD route,
+    // on every attempt)
+    if (call.centre_share && !R.whole && d_forces && !R.zero3 && !R.md_step)
         HIPCHK(c, hipMemsetAsync(d_forces, 0, 24 * (size_t)P.natoms, st));
+    const int switches = (uf3_env("UF3_EVAL_NO_TAB") ? EVAL_NO_TAB : 0) | (uf3_env("UF3_EVAL_NO_CW") ? EVAL_NO_CW : 0) |
+                         (uf3_env("UF3_EVAL_NO_CAP16") ? EVAL_NO_CAP16 : 0);
+    const bool no_spin = c->timing || uf3_env("UF3_NO_TAIL_SPIN");        // (event timing queues a record behind the chain)
+    // one whole frame on the MD route, large: the collection pass also leaves per-workgroup sums of the atoms' energies (and strain
+    // derivatives), and the frame sum adds those -- natoms / 16 values instead of natoms (12 -> 4 us at 50 k atoms)
+    const bool part_sums = R.md_step && R.whole && P.n_frames == 1 && P.natoms >= 8192 && !call.mirror && !uf3_env("UF3_NO_PART_SUMS");
     {
         Timed tm(c, T_EVAL);
         for (int attempt = 0; ; attempt++) {
             c->tail_signalled = false;
-            bool part_sums = false;
-            if (fuse) {
+            if (R.fuse) {
                 rc = n3_alloc(c, P.natoms, c->n3_cap, A.n3);
                 if (rc) return rc;
                 A.fuse_n3 = 1;
-                A.n3_need = c->flags.as<int>() + 1;
-                if (!P.flags_zeroed || attempt) HIPCHK(c, hipMemsetAsync(A.n3_need, 0, (md_step ? 3 : 1) * sizeof(int), st));
+                A.n3_need = c->flags.as<int>() + ST_N3_NEED;
+                if (!P.flags_zeroed || attempt) HIPCHK(c, hipMemsetAsync(A.n3_need, 0, (R.md_step ? 3 : 1) * sizeof(int), st));
             }
-            if (md_step) {
+            if (R.md_step) {
                 const uf3_ctx::MdState &md = c->md;
                 A.fuse_n3 = 0;
                 A.geoms = P.geoms; A.frame_of = P.frame_of; A.spec = P.spec;
@@ -2436,13 +2635,12 @@ static int eval_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, co
                 A.pos_ref = md.pos_ref.as<double>(); A.z_now = d_z;
                 const double hard = 0.5 * md.skin * (1.0 - 1e-9), soft = 0.7 * hard;
                 A.md_hard2 = hard * hard; A.md_soft2 = soft * soft;
-                A.md_flags = c->flags.as<int>() + 2;
+                A.md_flags = c->flags.as<int>() + ST_MD_OUTRUN;
                 c->md.steps++;
                 HIPCHK(c, c->md.surv.ensure(sizeof(int) * (size_t)P.natoms * A.n3.cap));
                 A.md_inbox = c->md.inbox.as<double>(); A.md_surv = c->md.surv.as<int>();
                 A.md_stamp = (double)c->md.steps;
-                A.md_mark = nullptr; A.md_mark_now = 0;
-                if (centres) {
+                if (R.centres) {
                     // marks of the atoms the block's centres write to: zeroed when (re)allocated, launch numbers only grow
                     const void *before = c->md.mark.p;
                     HIPCHK(c, c->md.mark.ensure(sizeof(int) * (size_t)P.natoms));
@@ -2452,174 +2650,102 @@ static int eval_impl(uf3_basis *b, const uf3_frames *fr, const double *d_pos, co
                 }
             }
             const size_t cap = (size_t)A.n3.cap;
-            // own list (32 + 20 B per entry), queue of bonds, force on the entries (24), walk-order entries + keys (48)
-            const size_t lds_plain = cap * 32 + (5 * cap + 2) * 4 + 16 + 2 * WAVE * EVAL_Q * sizeof(double) + cap * 24 + cap * 48;
-            // TAB instances (centre legs from per-bond tables, k_eval): + leg n's knot records, + the tables when they do not fit
-            // over the queue.  Chosen by the basis alone -- not by the capacity -- unless the longer layout does not fit at all
-            const size_t lds_tab = lds_plain + 16 + EVAL_TAB_KN * sizeof(KnotRec) + (cap > EVAL_TAB_CAP ? 136 * cap + 16 : 0);
-            const bool tab = two_pass && b->eval_tab_ok && (int)lds_tab <= c->lds_max && !uf3_env("UF3_EVAL_NO_TAB");
-            // CW instances (MD route only: measured 197 against 190 M atom-steps/s there, a loss on the plain route): EVAL_CW_WAVES
-            // one-atom waves per workgroup around one copy of the window table, every knot record and the pair coefficients
-            const size_t cw_per_wave = ((md_step ? lds_plain - cap * 48 : lds_plain) + 15) / 16 * 16;      // (the walk-order arrays: fused builds only)
-            const size_t cw_recs = b->n_recs * sizeof(KnotRec), cw_c2b = (n2 * 8 + 15) / 16 * 16;
-            const size_t lds_cw = (size_t)b->cw_bytes + cw_recs + cw_c2b + EVAL_CW_WAVES * cw_per_wave;
-            const bool cw = tab && md_step && c->cw_of == (const void *)b && cap <= 16 &&      /* (lists of <= 16 entries: the force gather's stage, k_eval) */
-                             lds_cw <= UF3_LDS_LIMIT / (EVAL_CW_WAVES > 8 ? 1 : 2) && !uf3_env("UF3_EVAL_NO_CW");
-            const size_t lds = cw ? lds_cw : (tab ? lds_tab : lds_plain);
-            // WIN instances: the same window table read through global memory by the one-wave TAB instances CW does not serve
-            const bool win = tab && !cw && c->cw_of == (const void *)b && !uf3_env("UF3_EVAL_NO_CW");
-            if (win) { A.c3w = c->coeff_cw.as<double>(); A.cw_lo = b->cw_lo; A.cw_ext = b->cw_ext; }
-            if (cw) {
+            const EvalPlan plan = eval_plan(cap, R.two_pass, R.md_step, n2, b->n_recs, (size_t)b->cw_bytes, b->eval_tab_ok,
+                                            c->cw_of == (const void *)b, c->lds_max, switches);
+            if (!plan.fits) return fail(c, UF3_EOVERFLOW, "3-body neighbour list does not fit in LDS");
+            if (plan.win) { A.c3w = c->coeff_cw.as<double>(); A.cw_lo = b->cw_lo; A.cw_ext = b->cw_ext; }
+            if (plan.cw) {
                 A.c3w = c->coeff_cw.as<double>(); A.cw_bytes = b->cw_bytes; A.cw_zero = b->cw_zero; A.cw_lo = b->cw_lo; A.cw_ext = b->cw_ext;
-                A.lds_per_wave = (int)cw_per_wave; A.cw_recs_bytes = (int)cw_recs; A.cw_c2 = (int)n2;
+                A.lds_per_wave = (int)plan.lds_per_wave; A.cw_recs_bytes = (int)(b->n_recs * sizeof(KnotRec)); A.cw_c2 = (int)n2;
             }
-            if (!cw && (int)lds > c->lds_max) return fail(c, UF3_EOVERFLOW, "3-body neighbour list does not fit in LDS");
-            bool cap16 = false;
-            if (two_pass) {
-                if (!md_step) {
+            if (R.two_pass) {
+                if (!R.md_step) {
                     HIPCHK(c, c->nbr_f.ensure(24 * (size_t)P.natoms * cap));
                     A.nbr_f = c->nbr_f.as<double>();
                 }
                 // (a block of centres on the MD route: its halo's rows are sums into zeros -- again on every attempt)
-                if (md_step && centres) HIPCHK(c, hipMemsetAsync(d_forces, 0, 24 * (size_t)P.natoms, st));
-                const int64_t n_centres = atom_end - atom_begin;
-                if (zero3) {
+                if (R.md_step && R.centres) HIPCHK(c, hipMemsetAsync(d_forces, 0, 24 * (size_t)P.natoms, st));
+                if (R.zero3) {
                     HIPCHK(c, c->halo.ensure(sizeof(int) * ((size_t)P.natoms + 4)));
                     const size_t words = 8 * (size_t)P.natoms;
                     hipLaunchKernelGGL(k_zero3, dim3((unsigned)std::min<size_t>((words + 255) / 256, 4096)), dim3(256), 0, st,
                                        (unsigned *)d_forces, 6 * (size_t)P.natoms, (unsigned *)A.n3.cnt, (size_t)P.natoms,
                                        (unsigned *)c->halo.p, (size_t)P.natoms);
                 }
-                else if (centres && fuse && !md_step) HIPCHK(c, hipMemsetAsync(A.n3.cnt, 0, sizeof(int) * (size_t)P.natoms, st));   // (lists not built: empty)
-                const dim3 eg((unsigned)((n_centres + 7) / 8 * 8));
-                {
-                    // instance: strain derivative | list capacity 16 as a constant | candidates from the persistent lists | centre
-                    // legs from per-bond tables (one set of 3-body legs, T <= 64, short lists: the usual case)
-                    // (which of the combinations exist: the comment block "Which instances ... the library holds")
-                    cap16 = cap == 16 && !uf3_env("UF3_EVAL_NO_CAP16");
-                    const dim3 eg_cw((unsigned)(((n_centres + EVAL_CW_WAVES - 1) / EVAL_CW_WAVES + 7) / 8 * 8));
-                    const int rl = with_bool(A.virial != 0, [&](auto VIR) {
-                    return with_bool(cap16, [&](auto C16) {
-                    return with_bool(md_step, [&](auto MD) {
-                        constexpr int CAP = C16 ? 16 : 0;
-                        if (cw) {
-                            // (MD route only: with the walk-order arrays of the fused list build the waves' own LDS is 7.1 KB each, and two
-                            // 8-wave workgroups + two copies of the tables do not fit a CU -- 168 of 160 KB; not instantiated)
-                            if constexpr (MD)
-                                HIPCHK(c, (launch_lds<k_eval<false, VIR, CAP, true, true, true>>(c, eg_cw, dim3(64 * EVAL_CW_WAVES), lds, A)));
-                            else
-                                return fail(c, UF3_EINVAL, "k_eval<CW> outside the MD route");
-                        }
-                        else if (win) hipLaunchKernelGGL((k_eval<false, VIR, CAP, MD, true, false, true>), eg, dim3(64), lds, st, A);
-                        else if (tab) hipLaunchKernelGGL((k_eval<false, VIR, CAP, MD, true>), eg, dim3(64), lds, st, A);
-                        else hipLaunchKernelGGL((k_eval<false, VIR, CAP, MD, false>), eg, dim3(64), lds, st, A);
-                        return (int)UF3_OK;
-                    }); }); });
-                    if (rl) return rl;
-                }
-                if (fuse && deferred_cap) *deferred_cap = (int)cap;
-                if (centres && !md_step) {
-                    // the block's lists exist now (this launch built them, or prepare did): the halo's, then the collection
-                    // pass over block + halo
-                    if (fuse || uf3_env("UF3_NO_HALO")) { int rh = build_halo_lists(b, P, A.n3, d_pos, (int)atom_begin, (int)atom_end, zero3); if (rh) return rh; }
-                    A.halo_mark = c->halo.as<int>();
-                }
-                if (md_step && centres)      // every atom checks itself; the block and the atoms its centres wrote to collect
-                    hipLaunchKernelGGL(k_eval_collect_md_halo, dim3((unsigned)((P.natoms + 15) / 16)), dim3(256), 0, st, A);
-                else if (md_step) {
-                    // one whole frame, large: the collection pass also leaves per-workgroup sums of the atoms' energies (and strain
-                    // derivatives), and the frame sum adds those -- natoms / 16 values instead of natoms (12 -> 4 us at 50 k atoms)
-                    part_sums = P.n_frames == 1 && whole && P.natoms >= 8192 && !mirror && !uf3_env("UF3_NO_PART_SUMS");
-                    if (part_sums) {
-                        const size_t n_wg = ((size_t)P.natoms + 15) / 16;
-                        HIPCHK(c, c->part_sums.ensure(8 * (7 * n_wg + 2)));
-                        A.part_e = c->part_sums.as<double>(); A.part_v = A.part_e + n_wg; A.part_off = (long long *)(A.part_v + 6 * n_wg);
-                    }
-                    hipLaunchKernelGGL(k_eval_collect_md, dim3((unsigned)(((P.natoms + 15) / 16 + 7) / 8 * 8)), dim3(256), 0, st, A);
-                }
-                else hipLaunchKernelGGL(k_eval_collect, dim3((unsigned)(((P.natoms + 15) / 16 + 7) / 8 * 8)), dim3(256), 0, st, A);
-            } else if (atom_end > atom_begin) {
-                if (A.virial) hipLaunchKernelGGL((k_eval<true, true>), dim3((unsigned)((atom_end - atom_begin + 7) / 8 * 8)), dim3(64), lds, st, A);
-                else hipLaunchKernelGGL((k_eval<true, false>), dim3((unsigned)((atom_end - atom_begin + 7) / 8 * 8)), dim3(64), lds, st, A);
+                else if (R.centres && R.fuse && !R.md_step) HIPCHK(c, hipMemsetAsync(A.n3.cnt, 0, sizeof(int) * (size_t)P.natoms, st));   // (lists not built: empty)
+            }
+            rc = launch_eval(c, plan, A, R.atom_hi - R.atom_lo);
+            if (rc) return rc;
+            if (R.two_pass) {
+                if (R.fuse && call.deferred_cap) *call.deferred_cap = (int)cap;
+                rc = launch_collect(b, P, R, d_pos, part_sums, A);
+                if (rc) return rc;
             }
             // (UF3_DEBUG_LDS: which k_eval instance ran -- tests assert the route they mean to reach; atom range, centre range
             // and whole batch alike)
-            if (c->env_debug_lds && atom_end > atom_begin)
+            if (c->env_debug_lds && R.atom_hi > R.atom_lo)
                 fprintf(stderr, "uf3: k_eval cw=%d win=%d tab=%d gather=%d md=%d cap16=%d vir=%d centres=%d part_sums=%d cap=%d atoms=%lld\n",
-                        (int)cw, (int)win, (int)tab, (int)!two_pass, (int)md_step, (int)cap16, (int)(A.virial != nullptr), (int)centres,
-                        (int)part_sums, (int)cap, (long long)(atom_end - atom_begin));
-            // (one workgroup per frame and component: wide for big frames, the loop is a latency chain)
-            const int sum_threads = P.natoms / P.n_frames >= 2048 ? 1024 : 256;
-            // (into the caller's pinned block: the launch's last workgroup signals the host itself; flags[12] counts workgroups)
+                        (int)plan.cw, (int)plan.win, (int)plan.tab, (int)plan.gather, (int)plan.md, (int)plan.cap16, (int)(A.virial != nullptr),
+                        (int)R.centres, (int)part_sums, (int)cap, (long long)(R.atom_hi - R.atom_lo));
+            // How the call's end reaches the host.  Into the caller's pinned block (mirror): the launch's last workgroup signals the
+            // host itself; the tail-count word counts workgroups.
             // INVARIANT of the polled completion (eval_host returns without hipStreamSynchronize once the sequence number shows):
             // k_frame_sum is the LAST launch of the call's chain, and its sequence store, behind system-scope fences, the last
             // access of that chain to pin_in / pin_out -- the next call's memcpy into those blocks relies on it.  Anything queued
             // behind this launch (a timing event, a second mirror write) must clear `tail_signalled` so that the host waits
             // for the stream instead.
-            unsigned seq = 0;
-            if (mirror && !c->timing && !uf3_env("UF3_NO_TAIL_SPIN")) {        // (event timing queues a record behind the chain)
-                if (++c->eval_seq == 0) c->eval_seq = 1;
-                seq = c->eval_seq;
-                c->tail_signalled = true;
-            }
-            // a device-resident call that looks at its status words before it returns (the fused list build, the MD route): the
+            // A device-resident call that looks at its status words before it returns (the fused list build, the MD route): the
             // last kernel puts them, and the call's sequence number behind them, into a pinned block the host polls -- no copy
             // of 16 bytes through the runtime's staging and no wait for the stream's completion signal (~10 us of an MD step)
+            const bool own_verdict = R.fuse && !call.deferred_cap;
             int *flags_host = nullptr;
             unsigned *seq_host = nullptr;
-            if (!mirror && !flags_tail && fuse && !deferred_cap && !c->timing && !uf3_env("UF3_NO_TAIL_SPIN")) {
-                HIPCHK(c, c->pin_eval.ensure(64));
-                flags_host = (int *)c->pin_eval.p; seq_host = (unsigned *)c->pin_eval.p + 4;
+            unsigned seq = 0;
+            if (!no_spin && (call.mirror || (own_verdict && !call.flags_tail))) {
                 if (++c->eval_seq == 0) c->eval_seq = 1;
                 seq = c->eval_seq;
-            }
-            if (part_sums)
-                hipLaunchKernelGGL(k_frame_sum, dim3(1, d_virials ? 7 : 1), dim3(1024), 0, st, (const double *)A.part_e,
-                                   (const double *)A.part_v, (const int64_t *)A.part_off, d_energies, d_virials, (const int *)c->flags.as<int>(), flags_host ? flags_host : flags_tail,
-                                   mirror, (const double *)d_forces, d_forces ? 3 * P.natoms : 0, 0, (P.natoms + 15) / 16, seq, c->flags.as<int>() + 12,
-                                   seq_host);
-            else
-            hipLaunchKernelGGL(k_frame_sum, dim3(P.n_frames, d_virials ? 7 : 1), dim3(sum_threads), 0, st, A.e_atom,
-                               A.virial, P.d_offsets, d_energies, d_virials, (const int *)c->flags.as<int>(), flags_host ? flags_host : flags_tail,
-                               mirror, (const double *)d_forces, d_forces ? 3 * P.natoms : 0, (int)atom_begin, (int)atom_end, seq, c->flags.as<int>() + 12,
-                               seq_host);
-            if (fuse && !deferred_cap) {
-                // the lists were part of this launch: did they fit?  (Asked after everything is queued -- all kernels
-                // are safe on clipped lists -- so that the GPU does not idle while the host looks.)
-                int fl[4] = {0, 0, 0, 0};
-                bool arrived = false;
-                if (seq_host) {
-                    const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-                    for (int spin = 0; !arrived; spin++) {
-                        arrived = __atomic_load_n(seq_host, __ATOMIC_ACQUIRE) == seq;
-                        if (!arrived && (spin & 255) == 255 && std::chrono::steady_clock::now() > t_end) break;
-                    }
-                    if (!arrived) HIPCHK(c, hipStreamSynchronize(st));
-                    std::memcpy(fl, flags_host, sizeof(fl));
-                } else {
-                    HIPCHK(c, hipMemcpyAsync(fl, c->flags.p, sizeof(fl), hipMemcpyDeviceToHost, st));
-                    HIPCHK(c, hipStreamSynchronize(st));
-                }
-                if (fl[0]) return check_flags(c);
-                if (md_step && fl[2]) {
-                    // an atom beyond skin / 2 of where the lists were built (or of another species): the results are void --
-                    // new lists from these positions, and again
-                    if (attempt >= 5) return fail(c, UF3_EOVERFLOW, "MD neighbour lists did not settle");
-                    c->md.redone++;
-                    if (c->md.live) { rc = md_live_fetch(c, fr); if (rc) return rc; }
-                    rc = md_build(b, fr, d_pos, d_z, P);
-                    if (rc) return rc;
-                    md_prepared(c, P);
-                    continue;
-                }
-                if (md_step && fl[3]) c->md.stale = true;        // (early warning: rebuild in front of the next step)
-                if (fl[1] > (int)cap) {
-                    if (attempt >= 5) return fail(c, UF3_EOVERFLOW, "3-body neighbour capacity did not converge");
-                    c->n3_cap = (fl[1] + 8 + 7) / 8 * 8;
-                    continue;
+                if (call.mirror) c->tail_signalled = true;
+                else {
+                    HIPCHK(c, c->pin_eval.ensure(64));
+                    flags_host = (int *)c->pin_eval.p; seq_host = (unsigned *)c->pin_eval.p + 4;
                 }
             }
-            break;
+            {
+                // the per-atom values of every frame over the range -- or, behind a collection pass that left them, its per-workgroup
+                // sums as ONE frame of (natoms + 15) / 16 values (one workgroup per frame and component: wide for big frames, the loop
+                // is a latency chain)
+                const int n_wg = (P.natoms + 15) / 16;
+                const int sum_threads = P.natoms / P.n_frames >= 2048 ? 1024 : 256;        // (part sums: a frame of >= 8192 atoms)
+                hipLaunchKernelGGL(k_frame_sum, dim3(part_sums ? 1 : P.n_frames, d_virials ? 7 : 1), dim3(sum_threads), 0, st,
+                                   part_sums ? (const double *)A.part_e : A.e_atom, part_sums ? (const double *)A.part_v : A.virial,
+                                   part_sums ? (const int64_t *)A.part_off : P.d_offsets, d_energies, d_virials,
+                                   (const int *)c->flags.as<int>(), flags_host ? flags_host : call.flags_tail, call.mirror,
+                                   (const double *)d_forces, d_forces ? 3 * P.natoms : 0, part_sums ? 0 : (int)R.atom_lo,
+                                   part_sums ? n_wg : (int)R.atom_hi, seq, c->flags.as<int>() + ST_TAIL_COUNT, seq_host);
+            }
+            if (!own_verdict) break;
+            // the lists were part of this launch: did they fit?  (Asked after everything is queued -- all kernels
+            // are safe on clipped lists -- so that the GPU does not idle while the host looks.)
+            int fl[4] = {0, 0, 0, 0};
+            if (seq_host) {
+                if (!wait_seq(seq_host, seq)) HIPCHK(c, hipStreamSynchronize(st));
+                std::memcpy(fl, flags_host, sizeof(fl));
+            } else {
+                HIPCHK(c, hipMemcpyAsync(fl, c->flags.p, sizeof(fl), hipMemcpyDeviceToHost, st));
+                HIPCHK(c, hipStreamSynchronize(st));
+            }
+            const EvalVerdict v = eval_verdict(c, fl, (int)cap, R.md_step, rc);
+            if (v == EVAL_ERROR) return rc;
+            if (v == EVAL_DONE) break;
+            if (v == EVAL_OUTRUN) {
+                // the results are void -- new lists from these positions, and again
+                if (attempt >= 5) return fail(c, UF3_EOVERFLOW, "MD neighbour lists did not settle");
+                c->md.redone++;
+                if (c->md.live) { rc = md_live_fetch(c, fr); if (rc) return rc; }
+                rc = md_build(b, fr, d_pos, d_z, P);
+                if (rc) return rc;
+                md_prepared(c, P);
+            } else if (attempt >= 5) return fail(c, UF3_EOVERFLOW, "3-body neighbour capacity did not converge");
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -2639,9 +2765,11 @@ extern "C" int uf3_eval_virial_dev(uf3_basis *b, const uf3_frames *fr, const dou
     return eval_impl(b, fr, d_pos, d_z, c1, c2, c3, d_energies, d_forces, d_virials);
 }
 
+// host arrays in and out: the batch staged on the device, eval_impl on it, the results back.  `call`: range and centre_share; the
+// three fields of a host call are set here
 static int eval_host(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1,
                      const double *c2, const double *c3, double *energies, double *forces, double *virials,
-                     int64_t atom_begin = 0, int64_t atom_end = -1, bool centre_share = false) {
+                     EvalCall call = EvalCall()) {
     uf3_ctx *c = b->ctx;
     uf3_env_refresh();
     if (!energies) return fail(c, UF3_EINVAL, "uf3_eval: null energies");
@@ -2653,48 +2781,37 @@ static int eval_host(uf3_basis *b, const uf3_frames *fr, const double *pos, cons
     const size_t nf = (size_t)fr->n_frames, bf = forces ? 24 * (size_t)natoms : 0, total = 8 * nf * 7 + bf;
     HIPCHK(c, c->stage_out.ensure(total + 16));
     double *d_e = c->stage_out.as<double>(), *d_v = d_e + nf, *d_f = d_e + 7 * nf;
-    if (forces && (atom_begin != 0 || (atom_end >= 0 && atom_end != natoms)))   // rows of other ranks' atoms: zero
+    if (forces && (call.atom_begin != 0 || (call.atom_end >= 0 && call.atom_end != natoms)))   // rows of other ranks' atoms: zero
         HIPCHK(c, hipMemsetAsync(d_f, 0, bf, c->stream));
     if (total + 16 <= UF3_PIN_LIMIT) {
         // small batch (an MD step): results and the neighbour stage's status words come back in ONE download and ONE
         // wait -- the lists are built at the remembered capacity and the evaluation runs on them right away; if they
         // overflowed (or a species / wrap error was flagged) the results are discarded and the call repeated / failed
         HIPCHK(c, c->pin_out.ensure(total + 32));
-        int *d_flags_tail = (int *)((char *)c->stage_out.p + total);
+        const int *fl = (const int *)((const char *)c->pin_out.p + total);
+        unsigned *seq_word = (unsigned *)((char *)c->pin_out.p + total + 16);
+        int cap_used = 0;
+        call.deferred_cap = &cap_used;
+        call.flags_tail = (int *)((char *)c->stage_out.p + total);
         for (int attempt = 0; attempt < 6; attempt++) {
-            int cap_used = 0;
             // (up to the one-workgroup cell-list limit the last kernel writes the results into the pinned block itself; the
             // mirror's layout has the forces right behind the 7 nf sums, as d_e does)
             const bool zero_copy = natoms <= UF3_SMALL_ATOMS && !uf3_env("UF3_NO_ZERO_COPY");
-            *(volatile unsigned *)((char *)c->pin_out.p + total + 16) = 0;
+            call.mirror = zero_copy ? (double *)c->pin_out.p : nullptr;
+            cap_used = 0;
+            *(volatile unsigned *)seq_word = 0;
             rc = eval_impl(b, fr, (const double *)c->stage_cur, c->d_stage_z, c1, c2, c3, d_e, forces ? d_f : nullptr,
-                           virials ? d_v : nullptr, atom_begin, atom_end, &cap_used, d_flags_tail,
-                           zero_copy ? (double *)c->pin_out.p : nullptr, centre_share);
+                           virials ? d_v : nullptr, call);
             if (rc) return rc;
             if (!zero_copy) HIPCHK(c, hipMemcpyAsync(c->pin_out.p, d_e, total + 16, hipMemcpyDeviceToHost, c->stream));
-            bool arrived = false;
-            if (zero_copy && c->tail_signalled) {
-                // the tail kernel's last store, behind a system-scope fence, is this call's sequence number: poll the pinned
-                // block for it (a few us sooner than the stream's completion signal reaches the host); bounded, then the
-                // ordinary wait
-                const unsigned *word = (const unsigned *)((const char *)c->pin_out.p + total + 16);
-                const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-                for (int spin = 0; !arrived; spin++) {
-                    arrived = __atomic_load_n(word, __ATOMIC_ACQUIRE) == c->eval_seq;
-                    if (!arrived && (spin & 255) == 255 && std::chrono::steady_clock::now() > t_end) break;
-                }
-            }
-            if (!arrived) HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (!(zero_copy && c->tail_signalled && wait_seq(seq_word, c->eval_seq))) HIPCHK(c, hipStreamSynchronize(c->stream));
             c->pin_in_busy = false;
             poll_pending(c, true);           // (remembered, see above)
-            {
-                const int *fl = (const int *)((const char *)c->pin_out.p + total);
-                if (fl[0]) return check_flags(c);
-                if (c->md_step && fl[2]) { c->md.valid = false; c->md.verify_next = true; c->md.redone++; continue; }      // (lists outrun, or clipped by a build nobody waited for: rebuilt by the repeat, with the host looking)
-                if (c->md_step && fl[3]) c->md.stale = true;
-                if (cap_used && fl[1] > cap_used) { c->n3_cap = (fl[1] + 8 + 7) / 8 * 8; continue; }
-                c->md.flags_clean = c->md_step && !fl[1] && !fl[2] && !fl[3];
-            }
+            const EvalVerdict v = eval_verdict(c, fl, cap_used, c->md_step, rc);
+            if (v == EVAL_ERROR) return rc;
+            if (v == EVAL_OUTRUN) { c->md.valid = false; c->md.verify_next = true; c->md.redone++; }      // (rebuilt by the repeat, with the host looking)
+            if (v != EVAL_DONE) continue;
+            c->md.flags_clean = c->md_step && !fl[ST_N3_NEED] && !fl[ST_MD_OUTRUN] && !fl[ST_MD_WARN];
             const double *h = (const double *)c->pin_out.p;
             std::memcpy(energies, h, 8 * nf);
             if (virials) std::memcpy(virials, h + nf, 48 * nf);
@@ -2704,7 +2821,7 @@ static int eval_host(uf3_basis *b, const uf3_frames *fr, const double *pos, cons
         return fail(c, UF3_EOVERFLOW, "3-body neighbour capacity did not converge");
     }
     rc = eval_impl(b, fr, (const double *)c->stage_cur, c->d_stage_z, c1, c2, c3, d_e, forces ? d_f : nullptr,
-                   virials ? d_v : nullptr, atom_begin, atom_end, nullptr, nullptr, nullptr, centre_share);
+                   virials ? d_v : nullptr, call);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(energies, d_e, 8 * nf, hipMemcpyDeviceToHost, c->stream));
     if (virials) HIPCHK(c, hipMemcpyAsync(virials, d_v, 48 * nf, hipMemcpyDeviceToHost, c->stream));
@@ -2731,7 +2848,9 @@ extern "C" int uf3_eval_atoms_dev(uf3_basis *b, const uf3_frames *fr, const doub
                                   int64_t atom_end, double *d_energies, double *d_forces, double *d_virials) {
     if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
     if (atom_end < 0) return fail(b->ctx, UF3_EINVAL, "uf3_eval_atoms: atom range outside the batch");
-    return eval_impl(b, fr, d_pos, d_z, c1, c2, c3, d_energies, d_forces, d_virials, atom_begin, atom_end);
+    EvalCall call;
+    call.atom_begin = atom_begin; call.atom_end = atom_end;
+    return eval_impl(b, fr, d_pos, d_z, c1, c2, c3, d_energies, d_forces, d_virials, call);
 }
 
 extern "C" int uf3_eval_atoms(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1,
@@ -2739,7 +2858,9 @@ extern "C" int uf3_eval_atoms(uf3_basis *b, const uf3_frames *fr, const double *
                               double *energies, double *forces, double *virials) {
     if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
     if (atom_end < 0) return fail(b->ctx, UF3_EINVAL, "uf3_eval_atoms: atom range outside the batch");
-    return eval_host(b, fr, pos, z, c1, c2, c3, energies, forces, virials, atom_begin, atom_end);
+    EvalCall call;
+    call.atom_begin = atom_begin; call.atom_end = atom_end;
+    return eval_host(b, fr, pos, z, c1, c2, c3, energies, forces, virials, call);
 }
 
 extern "C" int uf3_eval_centres_dev(uf3_basis *b, const uf3_frames *fr, const double *d_pos, const int32_t *d_z,
@@ -2747,7 +2868,9 @@ extern "C" int uf3_eval_centres_dev(uf3_basis *b, const uf3_frames *fr, const do
                                     int64_t atom_end, double *d_energies, double *d_forces, double *d_virials) {
     if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
     if (atom_end < 0) return fail(b->ctx, UF3_EINVAL, "uf3_eval_centres: atom range outside the batch");
-    return eval_impl(b, fr, d_pos, d_z, c1, c2, c3, d_energies, d_forces, d_virials, atom_begin, atom_end, nullptr, nullptr, nullptr, true);
+    EvalCall call;
+    call.atom_begin = atom_begin; call.atom_end = atom_end; call.centre_share = true;
+    return eval_impl(b, fr, d_pos, d_z, c1, c2, c3, d_energies, d_forces, d_virials, call);
 }
 
 extern "C" int uf3_eval_centres(uf3_basis *b, const uf3_frames *fr, const double *pos, const int32_t *z, const double *c1,
@@ -2755,7 +2878,9 @@ extern "C" int uf3_eval_centres(uf3_basis *b, const uf3_frames *fr, const double
                                 double *energies, double *forces, double *virials) {
     if (!b) return fail(nullptr, UF3_EINVAL, "null basis");
     if (atom_end < 0) return fail(b->ctx, UF3_EINVAL, "uf3_eval_centres: atom range outside the batch");
-    return eval_host(b, fr, pos, z, c1, c2, c3, energies, forces, virials, atom_begin, atom_end, true);
+    EvalCall call;
+    call.atom_begin = atom_begin; call.atom_end = atom_end; call.centre_share = true;
+    return eval_host(b, fr, pos, z, c1, c2, c3, energies, forces, virials, call);
 }
 
 extern "C" int uf3_allreduce_sum_f64(uf3_ctx *c, double *d_buf, int64_t n);
