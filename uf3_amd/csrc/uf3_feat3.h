@@ -148,6 +148,9 @@ __device__ __forceinline__ int f3_eval(const double *rows, const Feat3Leg &lg, d
 // (CAP: the list capacity as a compile-time constant -- 16, what a tuned context settles on for bcc / fcc cells -- or 0 for
 // the launch's run-time value: with it every per-wave LDS array sits at a constant offset from two bases, offsets that go into
 // the LDS instructions' immediate fields instead of scalar registers the kernel has too few of)
+#ifndef F3_CHAIN
+#define F3_CHAIN 15        // which of the four shortenings of the atom's load chain are on (in the kernel; all, but for A/B builds)
+#endif
 #ifndef F3_WIDE_MINW
 #define F3_WIDE_MINW 2     // waves per SIMD the wide-window instances (NR > 1) are bounded for
 #endif
@@ -165,6 +168,12 @@ k_featurize3(Feat3Args A) {
     // cost two scalar spills each in two instances).  DESIGN.md section 3.6.
     constexpr bool TRIP1 = NR != 2, LIST1 = NR == 1;
     typedef std::conditional_t<TRIP1, F3LdsSingles, F3LdsDoubles> F3TripReads;
+    // The atom's chain of dependent loads, shortened (F3_CHAIN, bit by bit): 1 the walk's gathered entry comes whole, parent and
+    // shift in one load; 2 the atom's scalars in one group and its own entries, row and species byte in another, neither waiting
+    // for the count; 4 a neighbour's row of species offsets asked for at once; 8 a block's fold table with its head.
+    // (2 stays off in the two-round instances without the energy row: there it costs four to five vector registers, and the
+    // generic one a wave per SIMD.  DESIGN.md section 3.6.)
+    constexpr bool CH_KE = F3_CHAIN & 1, CH_OWN = (F3_CHAIN & 2) && (WANT_E || NR != 2), CH_ROWS = F3_CHAIN & 4, CH_FSRC = F3_CHAIN & 8;
     extern __shared__ __align__(16) unsigned char smem[];
     const BasisDev *B = A.B;
     // (cap: what the LDS arrays are laid out for -- the longest list this instance serves; ent_stride: entries per atom in the
@@ -245,8 +254,14 @@ k_featurize3(Feat3Args A) {
     for (int m0 = block_first; m0 < block_end; m0 += WPB) {
         const int m = m0 + wave;
         const bool active = m < block_end;
+        // the atom's scalars with the workgroup's energy-row check, one wait for all (an idle wave of the last round asks for the
+        // block's last atom: nothing past the end of an array)
+        const int mc = CH_OWN ? min(m, block_end - 1) : m;
+        int fr_c = 0, n_own_c = 0;
+        if (CH_OWN) { fr_c = load_const(A.frame_of + mc); n_own_c = load_const(A.n3.cnt + mc); }
         if (e_lds) {
             int f_first = load_const(A.frame_of + m0);
+            if (CH_OWN) asm volatile("" : "+s"(fr_c), "+s"(n_own_c), "+s"(f_first));
             if (f_first != erow_frame) {
                 __syncthreads();
                 if (erow_frame >= 0)
@@ -259,26 +274,66 @@ k_featurize3(Feat3Args A) {
             }
         }
         if (!active) continue;
-        const int fr = load_const(A.frame_of + m);
+        const int fr = CH_OWN ? fr_c : load_const(A.frame_of + m);
         const int sm = ((const __attribute__((address_space(4))) signed char *)(unsigned long long)A.spec)[m];
         ESink es;
         es.lds = erow; es.glob = WANT_E ? A.x_e + (size_t)fr * F : nullptr; es.direct = !e_lds || (fr != erow_frame);
 
         // ---- own 3-body list -> LDS; species offsets of the neighbours' lists ----------------------------------------
-        const int n_own = load_const(A.n3.cnt + m);
-        wave_sync();
-        for (int e = lane; e < n_own; e += WAVE) {
-            const N3Entry en = A.n3.ent[(size_t)m * ent_stride + e];
+        const int n_own = CH_OWN ? n_own_c : load_const(A.n3.cnt + m);
+        auto own_entry = [&](int e, const N3Entry &en) {
             ox[e] = en.dx; oy[e] = en.dy; oz[e] = en.dz; orr[e] = en.r; oir[e] = 1.0 / en.r;
             int s0, s1, s2;
             unpack3(en.shiftc, s0, s1, s2);
             oparent[e] = en.parent; oshift[e] = pack3(-s0, -s1, -s2);      // (m's image as the neighbour's list names it)
-        }
-        if (lane <= S) so[lane] = A.n3.spoff[(size_t)m * (UF3_MAX_SPECIES + 1) + lane];
-        wave_sync();
-        for (int e = lane; e < n_own; e += WAVE) {
-            const int *src = A.n3.spoff + (size_t)oparent[e] * (UF3_MAX_SPECIES + 1);
-            for (int sp = 0; sp <= S; sp++) ospoff[e * (S + 1) + sp] = src[sp];
+        };
+        // the neighbour's row of species offsets: all nine words of the row are there whatever S is, and are asked for together
+        // (S afresh per atom: as loop invariants the nine compares below are kept in nine scalar pairs, and spilled)
+        int s_row = S;
+        if (CH_ROWS) asm volatile("" : "+s"(s_row));
+        auto own_row = [&](int e, int parent) {
+            const int *src = A.n3.spoff + (size_t)parent * (UF3_MAX_SPECIES + 1);
+            if (CH_ROWS) {
+                int w[UF3_MAX_SPECIES + 1];
+#pragma unroll
+                for (int sp = 0; sp <= UF3_MAX_SPECIES; sp++) w[sp] = src[sp];
+                // (all nine here, in front of the first store: left alone the compiler sinks each load to the store that uses it,
+                // a wait apiece)
+                static_assert(UF3_MAX_SPECIES == 8, "nine words a row");
+                asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7]), "+v"(w[8]));
+#pragma unroll
+                for (int sp = 0; sp <= UF3_MAX_SPECIES; sp++) if (sp <= s_row) ospoff[e * (S + 1) + sp] = w[sp];
+            } else {
+                for (int sp = 0; sp <= S; sp++) ospoff[e * (S + 1) + sp] = src[sp];
+            }
+        };
+        if (CH_OWN) {
+            // the first 64 entries and the atom's own row in one group with its species byte (asked for a few lines up, behind
+            // the test for an idle wave), none of them waited for before all are out, and asked for before the count is known: the slots m * ent_stride ... + cap are the atom's (ent_stride >= cap), and what a lane at
+            // or past n_own receives is looked at by nothing.  Every lane asks -- lanes past the capacity and past S for the last
+            // slot and word again -- so there is no masked region between the loads.
+            // (the atom's offsets and the lane afresh per atom: what is derived from them here is made here, not hoisted into
+            // registers that live across the atom loop -- with them hoisted the one-round instances spill vector registers, as the
+            // parent did for a hoisted per-lane address of its own.  DESIGN.md section 3.6 shows what each tie buys in the listing.)
+            size_t own_at = (size_t)m * ent_stride, so_at = (size_t)m * (UF3_MAX_SPECIES + 1);
+            int ln = lane;
+            asm volatile("" : "+s"(own_at), "+s"(so_at), "+v"(ln));
+            const N3Entry *own = A.n3.ent + own_at;
+            const N3Entry en = own[(unsigned)min(ln, cap - 1)];
+            const int so_v = A.n3.spoff[so_at + (unsigned)min(ln, S)];
+            wave_sync();
+            if (ln < n_own) own_entry(ln, en);
+            if (ln <= S) so[ln] = so_v;
+            for (int e = ln + WAVE; e < n_own; e += WAVE) own_entry(e, own[(unsigned)e]);
+            if (ln < n_own) own_row(ln, en.parent);
+            wave_sync();
+            for (int e = ln + WAVE; e < n_own; e += WAVE) own_row(e, oparent[e]);
+        } else {
+            wave_sync();
+            for (int e = lane; e < n_own; e += WAVE) own_entry(e, A.n3.ent[(size_t)m * ent_stride + e]);
+            if (lane <= S) so[lane] = A.n3.spoff[(size_t)m * (UF3_MAX_SPECIES + 1) + lane];
+            wave_sync();
+            for (int e = lane; e < n_own; e += WAVE) own_row(e, oparent[e]);
         }
         // ---- T_f of every own bond: rows over the whole window of the centre legs, zero where the bond's four functions are
         // not (and all zero when the bond is outside the legs' range) -------------------------------------------------------
@@ -310,7 +365,12 @@ k_featurize3(Feat3Args A) {
             const TrioDev *td = A.trios + t;
             typedef int int8_v __attribute__((ext_vector_type(8)));
             const int8_v hv = *(const __attribute__((address_space(4))) int8_v *)(unsigned long long)&td->head;
+            // (the block's fold table is asked for at the block's top and held in a scalar down to the fold, which no longer
+            // waits.  The compiler still issues the load behind the head's wait -- two waits in a row here, not one: DESIGN.md
+            // section 3.6)
+            int t_fs = CH_FSRC ? load_const(A.trio_fsrc + t) : 0;
             const int t_ncol = hv[2], t_sc = hv[3], t_sa = hv[4], t_sb = hv[5], t_col = hv[6];
+            if (CH_FSRC) asm volatile("" : "+s"(t_fs) : "s"(t_sc));
             const bool centre = t_sc == sm, nbr = t_sa == sm || t_sb == sm;
             if (!centre && !nbr) { zero_rows(A.x_f, m, A.ld, t_col, t_ncol); continue; }
             const bool tr = t_sa != t_sb && sm == t_sb;              // transposed: the fixed bond sits on leg m
@@ -508,8 +568,17 @@ k_featurize3(Feat3Args A) {
                         const int kk = nbase[lo] + (q - noff[lo]);
                         const int pc = oparent[e];
                         const double oex = F3_LIST(ox, e), oey = F3_LIST(oy, e), oez = F3_LIST(oz, e), oer = F3_LIST(orr, e);
-                        const N3Entry ke = A.n3.ent[(size_t)pc * ent_stride + kk];
-                        valid = !(ke.parent == m && ke.shiftc == oshift[e]);                  // k is m itself
+                        const N3Entry *kp = A.n3.ent + (size_t)pc * ent_stride + kk;
+                        const N3Entry ke = *kp;
+                        if (CH_KE) {
+                            // parent and shift as one 8-byte load in the group of the entry's other loads, and both compares on
+                            // loaded values: no second load, under a mask, behind the wait for the first
+                            typedef int int2_v __attribute__((ext_vector_type(2)));
+                            const int2_v ps = *(const int2_v *)&kp->parent;
+                            valid = !((ps.x == m) & (ps.y == oshift[e]));                      // k is m itself
+                        } else {
+                            valid = !(ke.parent == m && ke.shiftc == oshift[e]);
+                        }
                         const double ex = oex + ke.dx, ey = oey + ke.dy, ez = oez + ke.dz;   // m -> k
                         const double rn = norm3_leg(ex, ey, ez), rk = ke.r;
                         valid = valid & (oer > leg_p.t0) & (oer < leg_p.tlast) & (rk > leg_p.t0) & (rk < leg_p.tlast) &
@@ -624,7 +693,7 @@ k_featurize3(Feat3Args A) {
             if (UF3_SKIP(16)) continue;
             // ---- fold: the rows of the window -> LDS, the block's columns sum their (one or two) source bins -----------------
             wave_sync();
-            const unsigned short *ft = fsrc_l + load_const(A.trio_fsrc + t) + (size_t)(tr ? 2 * t_ncol : 0);
+            const unsigned short *ft = fsrc_l + (CH_FSRC ? t_fs : load_const(A.trio_fsrc + t)) + (size_t)(tr ? 2 * t_ncol : 0);
             if (NR == 1) {
                 // (pairs: a lane's two rows side by side -- [half][f][32 positions] x (x, y | z, energy))
 #pragma unroll
