@@ -172,6 +172,27 @@ int uf3_eval_plan_debug(int32_t cap, int two_pass, int md_step, int64_t n2, int6
                         int has_window, int32_t lds_max, int switches, int32_t *instance, int64_t *lds, int64_t *lds_per_wave,
                         int32_t *fits);
 
+/* The plan uf3_basis_create makes of a spec -- every table it uploads and every fact its launches read --, computed on the host
+ * alone (no device, no context; test surface).  switches: bit 0 UF3_NO_MFMA_FEAT, bit 1 UF3_NO_FEAT3.  table: 0 the summary
+ * below; 1 the host mirror (BasisDev, its device pointers null); 2 knot records with the grouped layouts' window rows behind them;
+ * 3 lut; 4 colsrc; 5 dsrc; 6 gsrc; 7 trios (TrioDev); 8 / 9 / 10 k_featurize3's window rows, fold tables and per-trio offsets
+ * (empty unless feat3_ok); 11 the per-species column lists; 12 block_bounds; 13 / 14 the evaluator's cw_lut_off and cw_dim_l.
+ * *len: the table's bytes; out (NULL: the length only) receives them, cap its room.  A spec uf3_basis_create refuses is refused
+ * here with the same message (uf3_last_error(NULL)). */
+typedef struct uf3_basis_plan_summary {
+    int64_t c2_len, c3_len, n_recs, n_pair_recs, trio_rec_lo, wrow_lo, n_dsrc, n_gsrc;
+    double r_cut;
+    double f3_leg[2][3];          /* k_featurize3's centre leg | leg n: t0, tlast, inv_h */
+    int32_t f3_leg_nk[2], f3_leg_row0[2];
+    int32_t n_wrows, modes, vmodes, all_grouped7, all_banded9, feat3_ok, eval_tab_ok, eval_cw_ok;
+    int32_t cw_lo, cw_ext, cw_dim_m, cw_dim_n, cw_zero, cw_bytes;
+    int32_t f3_lo_p, f3_ext_p, f3_lo_n, f3_ext_n, f3_nr, n_f3rows, n_f3src;
+    int32_t pairs_uniform, trio_legs_uniform;
+    int32_t sp_ncols[8];
+    int32_t dense_stride[16], dense_stride_f[16], dense_grouped[16], dense_dump[16];
+} uf3_basis_plan_summary;
+int uf3_basis_plan_debug(const uf3_basis_spec *spec, int switches, int table, void *out, int64_t cap, int64_t *len);
+
 /* RCCL behind the C ABI (round 5; SURVEY 8b's `uf3_gram_allreduce`).  One process per GPU.  The one exchange of the path is
  * the SUM over the ranks of the packed normal-equation pieces [G_e | G_f | o_e | o_f | m_e | m_f] (and, for a decomposed
  * frame, of [forces | energy | strain derivative]); the reference returns per-chunk results to the parent process and adds them

@@ -15,13 +15,13 @@ import numpy as np
 import pytest
 
 from uf3_amd import _lib, synthetic
-from uf3_amd.data import composition
 from uf3_amd.data.atoms import Atoms
 from uf3_amd.forcefield import calculator
 from uf3_amd.forcefield.md import MolecularDynamics
 from uf3_amd.regression import least_squares as ls
-from uf3_amd.representation import bspline, process
+from uf3_amd.representation import process
 import _site_rows_ref as SR
+from _bases import wide_basis as _wide_basis
 from _util import GOLDEN, wrapped
 
 pytestmark = pytest.mark.gpu
@@ -85,16 +85,6 @@ def report(monkeypatch, capfd):
     drop()
     yield read
     drop()
-
-
-@functools.lru_cache(maxsize=None)
-def _wide_basis():
-    """W with an untrimmed leading edge and a fine 3-body grid, built large on purpose: 16 rows of it do not fit the fused
-    kernel's LDS (F > 608, the largest F whose tile fits 80 KB beside the index arrays)."""
-    cs = composition.ChemicalSystem(["W"], 3)
-    t = ("W", "W", "W")
-    return bspline.BSplineBasis(cs, r_min_map={("W", "W"): 0.5, t: [1.0, 1.0, 1.0]}, r_max_map={("W", "W"): 5.0, t: [3.6, 3.6, 7.2]},
-                                resolution_map={("W", "W"): 12, t: [10, 10, 18]}, leading_trim=0, trailing_trim=3)
 
 
 def _w16():

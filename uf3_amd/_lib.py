@@ -26,7 +26,7 @@ EXPORTS = ["uf3_ctx_create", "uf3_ctx_destroy", "uf3_ctx_set_stream", "uf3_ctx_s
            "uf3_pair_geometry", "uf3_distance_matrix", "uf3_direction_cosines",
            "uf3_ctx_md_skin", "uf3_ctx_md_stats",
            "uf3_featurize_ld_dev", "uf3_fit_create", "uf3_fit_destroy", "uf3_fit_reset", "uf3_fit_add", "uf3_fit_pack", "uf3_fit_info", "uf3_fit_use_flat", "uf3_fit_first_chunk",
-           "uf3_fit_plan_debug", "uf3_eval_plan_debug",
+           "uf3_fit_plan_debug", "uf3_eval_plan_debug", "uf3_basis_plan_debug",
            "uf3_comm_unique_id", "uf3_comm_init", "uf3_comm_destroy", "uf3_comm_info", "uf3_allreduce_sum_f64", "uf3_gram_allreduce",
            "uf3_pair_histogram", "uf3_pair_histogram_dev", "uf3_scan_solve_dev",
            "uf3_md_create", "uf3_md_destroy", "uf3_md_set_state", "uf3_md_get_state", "uf3_md_init_velocities", "uf3_md_run",
@@ -167,6 +167,7 @@ def load():
         lib.uf3_fit_plan_debug.argtypes = [i32, vp, i64, dbl, vp, vp]
         lib.uf3_eval_plan_debug.argtypes = [i32, C.c_int, C.c_int, i64, i64, i64, C.c_int, C.c_int, i32, C.c_int,
                                             C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]
+        lib.uf3_basis_plan_debug.argtypes = [C.POINTER(BasisSpec), C.c_int, C.c_int, vp, i64, C.POINTER(i64)]
         lib.uf3_comm_unique_id.argtypes = [vp, vp]
         lib.uf3_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
         lib.uf3_comm_destroy.argtypes = [vp]
@@ -469,6 +470,57 @@ class DeviceBasis:
             pass
 
 
+def flatten_raw(species_z, pairs=None, trios=(), r_cut=None):
+    """The arguments of ``RawDeviceBasis`` -> (BasisSpec, keep-alive arrays).  Pure host bookkeeping."""
+    zs = [int(z) for z in species_z]
+    assert zs == sorted(set(zs)) and zs, "species_z: ascending atomic numbers"
+    pairs = {tuple(sorted((int(a), int(b)))): v for (a, b), v in (pairs or {}).items()}
+    keep = {}
+    keep["species_z"] = np.array(zs, dtype=np.int32)
+    all_pairs = [(zs[i], zs[j]) for i in range(len(zs)) for j in range(i, len(zs))]
+    ranges = [pairs.get(p, (0.0, 0.0)) for p in all_pairs]
+    keep["pair_z"] = np.array(all_pairs, dtype=np.int32).reshape(-1, 2)
+    keep["pair_nk"] = np.full(len(all_pairs), 8, dtype=np.int32)
+    # (a spline space is not needed for neighbour queries: the shortest legal knot vector over the range)
+    keep["pair_knots"] = np.ascontiguousarray(np.concatenate(
+        [np.repeat([max(float(lo), 0.0), max(float(hi), max(float(lo), 0.0) + 1.0)], 4) for lo, hi in ranges]))
+    keep["pair_rmin"] = np.array([float(lo) for lo, _ in ranges])
+    keep["pair_rmax"] = np.array([float(hi) for _, hi in ranges])
+    col = len(zs)
+    keep["pair_col"] = np.arange(col, col + 4 * len(all_pairs), 4, dtype=np.int32)
+    col += 4 * len(all_pairs)
+    trio_col, trio_ncol, luts, knots, nk = [], [], [], [], []
+    for zt, ks, lut in trios:
+        ks = [np.asarray(k, dtype=np.float64) for k in ks]
+        lut = np.ascontiguousarray(lut, dtype=np.int32).ravel()
+        assert lut.size == int(np.prod([len(k) - 4 for k in ks]))
+        ncol = int(lut.max()) + 1 if lut.size and lut.max() >= 0 else 1
+        trio_col.append(col)
+        trio_ncol.append(ncol)
+        col += ncol
+        luts.append(lut)
+        knots.extend(ks)
+        nk.append([len(k) for k in ks])
+    keep["trio_z"] = np.array([list(zt) for zt, _, _ in trios], dtype=np.int32).reshape(-1, 3)
+    keep["trio_nk"] = np.array(nk, dtype=np.int32).reshape(-1, 3)
+    keep["trio_knots"] = np.ascontiguousarray(np.concatenate(knots)) if knots else np.zeros(1)
+    keep["trio_col"] = np.array(trio_col, dtype=np.int32)
+    keep["trio_ncol"] = np.array(trio_ncol, dtype=np.int32)
+    keep["trio_lut"] = np.ascontiguousarray(np.concatenate(luts)) if luts else np.zeros(1, np.int32)
+    s = BasisSpec()
+    s.n_species, s.n_pairs, s.n_trios = len(zs), len(all_pairs), len(trios)
+    for name in ("species_z", "pair_z", "pair_nk", "pair_knots", "pair_rmin", "pair_rmax", "pair_col",
+                 "trio_z", "trio_nk", "trio_knots", "trio_col", "trio_ncol", "trio_lut"):
+        setattr(s, name, _p(keep[name]))
+    s.lead2, s.trail2 = 0, 0
+    s.n_feat = col
+    if r_cut is None:
+        r_cut = max([float(hi) for _, hi in ranges] + [float(k[-1]) for k in knots] + [1e-6])
+    s.r_cut = float(r_cut)
+    keep["pairs"] = all_pairs
+    return s, keep
+
+
 class RawDeviceBasis:
     """Device tables from a hand-made description instead of a ``BSplineBasis``: what the module-level functions of
     ``uf3_amd.representation.distances`` / ``angles`` need -- pair ranges without a spline space, or 3-body knot sets
@@ -483,57 +535,12 @@ class RawDeviceBasis:
 
     def __init__(self, species_z, pairs=None, trios=(), r_cut=None, ctx=None):
         self.ctx = ctx or get_context()
-        zs = [int(z) for z in species_z]
-        assert zs == sorted(set(zs)) and zs, "species_z: ascending atomic numbers"
-        pairs = {tuple(sorted((int(a), int(b)))): v for (a, b), v in (pairs or {}).items()}
-        keep = {}
-        keep["species_z"] = np.array(zs, dtype=np.int32)
-        all_pairs = [(zs[i], zs[j]) for i in range(len(zs)) for j in range(i, len(zs))]
-        self.pairs = all_pairs
-        ranges = [pairs.get(p, (0.0, 0.0)) for p in all_pairs]
-        keep["pair_z"] = np.array(all_pairs, dtype=np.int32).reshape(-1, 2)
-        keep["pair_nk"] = np.full(len(all_pairs), 8, dtype=np.int32)
-        # (a spline space is not needed for neighbour queries: the shortest legal knot vector over the range)
-        keep["pair_knots"] = np.ascontiguousarray(np.concatenate(
-            [np.repeat([max(float(lo), 0.0), max(float(hi), max(float(lo), 0.0) + 1.0)], 4) for lo, hi in ranges]))
-        keep["pair_rmin"] = np.array([float(lo) for lo, _ in ranges])
-        keep["pair_rmax"] = np.array([float(hi) for _, hi in ranges])
-        col = len(zs)
-        keep["pair_col"] = np.arange(col, col + 4 * len(all_pairs), 4, dtype=np.int32)
-        col += 4 * len(all_pairs)
-        trio_col, trio_ncol, luts, knots, nk = [], [], [], [], []
-        for zt, ks, lut in trios:
-            ks = [np.asarray(k, dtype=np.float64) for k in ks]
-            lut = np.ascontiguousarray(lut, dtype=np.int32).ravel()
-            assert lut.size == int(np.prod([len(k) - 4 for k in ks]))
-            ncol = int(lut.max()) + 1 if lut.size and lut.max() >= 0 else 1
-            trio_col.append(col)
-            trio_ncol.append(ncol)
-            col += ncol
-            luts.append(lut)
-            knots.extend(ks)
-            nk.append([len(k) for k in ks])
-        self.trio_col, self.trio_ncol = trio_col, trio_ncol
-        keep["trio_z"] = np.array([list(zt) for zt, _, _ in trios], dtype=np.int32).reshape(-1, 3)
-        keep["trio_nk"] = np.array(nk, dtype=np.int32).reshape(-1, 3)
-        keep["trio_knots"] = np.ascontiguousarray(np.concatenate(knots)) if knots else np.zeros(1)
-        keep["trio_col"] = np.array(trio_col, dtype=np.int32)
-        keep["trio_ncol"] = np.array(trio_ncol, dtype=np.int32)
-        keep["trio_lut"] = np.ascontiguousarray(np.concatenate(luts)) if luts else np.zeros(1, np.int32)
-        s = BasisSpec()
-        s.n_species, s.n_pairs, s.n_trios = len(zs), len(all_pairs), len(trios)
-        for name in ("species_z", "pair_z", "pair_nk", "pair_knots", "pair_rmin", "pair_rmax", "pair_col",
-                     "trio_z", "trio_nk", "trio_knots", "trio_col", "trio_ncol", "trio_lut"):
-            setattr(s, name, _p(keep[name]))
-        s.lead2, s.trail2 = 0, 0
-        s.n_feat = col
-        if r_cut is None:
-            r_cut = max([float(hi) for _, hi in ranges] + [float(k[-1]) for k in knots] + [1e-6])
-        s.r_cut = float(r_cut)
-        self.spec, self._keep = s, keep
-        self.n_feat, self.n_species = col, len(zs)
+        self.spec, self._keep = flatten_raw(species_z, pairs, trios, r_cut)
+        self.pairs = self._keep["pairs"]
+        self.trio_col, self.trio_ncol = self._keep["trio_col"].tolist(), self._keep["trio_ncol"].tolist()
+        self.n_feat, self.n_species = self.spec.n_feat, self.spec.n_species
         h = C.c_void_p()
-        self.ctx.check(self.ctx.lib.uf3_basis_create(self.ctx.handle, C.byref(s), C.byref(h)))
+        self.ctx.check(self.ctx.lib.uf3_basis_create(self.ctx.handle, C.byref(self.spec), C.byref(h)))
         self.handle = h
         self._pid = os.getpid()
 

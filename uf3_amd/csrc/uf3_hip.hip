@@ -9,6 +9,7 @@
 #include <cstring>
 #include <limits>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -63,6 +64,17 @@ struct Buf {
     }
     void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
     template <class T> T *as() const { return (T *)p; }
+};
+
+struct DevBuf : Buf {                           // a buffer that a driver or a basis owns: freed with its owner
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+};
+template <class T>
+struct DevTable : DevBuf {                      // ... read as the table of T it holds
+    operator T *() const { return as<T>(); }
 };
 
 // grow-only pinned host memory: small transfers go through it so that they are true asynchronous copies (a copy
@@ -245,21 +257,14 @@ struct uf3_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[4];
 };
 
-struct uf3_basis {
-    uf3_ctx *ctx = nullptr;
-    BasisDev host;              // host mirror (device pointers inside)
-    BasisDev *dev = nullptr;
-    TrioDev *d_trios = nullptr;
-    KnotRec *d_recs = nullptr;
-    int *d_lut = nullptr;
-    int *d_colsrc = nullptr;
-    int *d_dsrc = nullptr;           // colsrc as offsets into the dumped dense window (MFMA specialisation)
-    unsigned short *d_gsrc = nullptr; // grouped windows: fold tables (FeatArgs::gsrc)
+// What uf3_basis_create decides about a basis besides its tables (basis_plan, below): the facts the launches read.  A BasisPlan is
+// these facts plus the host image of every table; a uf3_basis is these facts plus the device copies of the tables, which it owns.
+struct BasisFacts {
+    BasisDev host;              // host mirror (in a plan: its three device pointers null)
     size_t n_gsrc = 0;
     bool all_grouped7 = false;       // every mode-7 trio stages grouped windows (its force launches do not touch dsrc)
     bool all_banded9 = false;        // every mode-9 trio runs banded (trio_block_banded) with its bands on the column tiles 0, 1, 2
     size_t n_dsrc = 0;
-    int *d_sp_cols = nullptr;        // [S][F]: the columns of the blocks species s takes part in, ascending (uf3_gram_force_rows_dev)
     int sp_ncols[UF3_MAX_SPECIES] = {0};
     std::vector<int> block_bounds;   // column boundaries of interaction blocks (for column windows)
     size_t c2_len = 0, c3_len = 0, n_recs = 0;
@@ -282,14 +287,26 @@ struct uf3_basis {
     int cw_lo = 0, cw_ext = 0, cw_dim_m = 0, cw_dim_n = 0, cw_zero = 0, cw_bytes = 0;
     std::vector<int> cw_lut_off;     // per trio: where its full grid starts in c3
     std::vector<int> cw_dim_l;
-    double *d_f3rows = nullptr;      // window rows of the centre legs and of leg n
     int n_f3rows = 0;
-    unsigned short *d_f3src = nullptr;   // fold tables
     int n_f3src = 0;
-    int *d_f3off = nullptr;          // [T] a trio's table
-    Feat3Leg f3_leg_p, f3_leg_n;
+    Feat3Leg f3_leg_p{}, f3_leg_n{};
     int f3_lo_p = 0, f3_ext_p = 0, f3_lo_n = 0, f3_ext_n = 0;
     int f3_nr = 0;                   // rounds of 32 window positions of the launch that serves the window (1: default trims; 2, 3: wider)
+};
+
+struct uf3_basis : BasisFacts {
+    uf3_ctx *ctx = nullptr;
+    DevTable<BasisDev> dev;
+    DevTable<TrioDev> d_trios;
+    DevTable<KnotRec> d_recs;
+    DevTable<int> d_lut;
+    DevTable<int> d_colsrc;
+    DevTable<int> d_dsrc;            // colsrc as offsets into the dumped dense window (MFMA specialisation)
+    DevTable<unsigned short> d_gsrc; // grouped windows: fold tables (FeatArgs::gsrc)
+    DevTable<int> d_sp_cols;         // [S][F]: the columns of the blocks species s takes part in, ascending (uf3_gram_force_rows_dev)
+    DevTable<double> d_f3rows;       // k_featurize3: window rows of the centre legs and of leg n
+    DevTable<unsigned short> d_f3src; // ... fold tables
+    DevTable<int> d_f3off;           // ... [T] a trio's table
 };
 
 // ------------------------------------------------------------------------------ environment switches
@@ -546,8 +563,39 @@ extern "C" int uf3_ctx_timing_read(uf3_ctx *c, double *feat_ms, int64_t *feat_la
 }
 
 // ------------------------------------------------------------------------------ basis
-// Interval records of one knot sequence; identical sequences (common: the same settings on every pair / trio)
-// share one run of the table, which keeps it small enough to live in LDS.
+// uf3_basis_create is check, plan, upload, publish.  basis_plan derives every table and every fact on the host alone -- a pure
+// function of the spec and of two switches, composed of stages that each decide one thing --; uf3_basis_plan_debug
+// returns its tables without a device, and tests/test_basis_plan_host.py pins them.
+enum { BASIS_NO_MFMA_FEAT = 1, BASIS_NO_FEAT3 = 2 };      // the switches UF3_NO_MFMA_FEAT / UF3_NO_FEAT3, as bits
+struct BasisPlan : BasisFacts {            // + the host image of every table uf3_basis_create uploads
+    std::vector<KnotRec> recs;             // knot records of the pairs, then of the trio legs, then the window rows of the grouped layouts
+    std::vector<int> lut;                  // raw bin -> global column, or -1
+    std::vector<int> colsrc, dsrc;         // per column: the raw bins that feed it (l | m << 8 | n << 16) | their offsets in the dumped dense window
+    std::vector<unsigned short> gsrc;      // fold tables of the grouped windows
+    std::vector<TrioDev> trios;
+    std::vector<double> f3rows;            // k_featurize3: window rows,
+    std::vector<unsigned short> f3src;     // ... fold tables
+    std::vector<int> f3off;                // ... and [T] where a trio's table starts
+    std::vector<int> sp_cols;              // [S][F] the columns of the blocks a species takes part in
+};
+
+static bool same_leg(const LegDev &a, const LegDev &b) {
+    return a.rec_off == b.rec_off && a.nk == b.nk && a.t0 == b.t0 && a.tlast == b.tlast && a.inv_h == b.inv_h;
+}
+
+// Where `run` lies in `table`, appended when no offset that is a multiple of `step` holds an identical run: tables that repeat
+// (the same settings on every pair / trio, the same symmetry on the same layout) are stored once and stay small enough for LDS.
+// Padding behind a run is the caller's.
+template <class T>
+static int intern_run(std::vector<T> &table, const std::vector<T> &run, size_t step) {
+    for (size_t off = 0; off + run.size() <= table.size(); off += step)
+        if (std::equal(run.begin(), run.end(), table.begin() + off, [](const T &a, const T &b) { return std::memcmp(&a, &b, sizeof(T)) == 0; }))
+            return (int)off;
+    table.insert(table.end(), run.begin(), run.end());
+    return (int)(table.size() - run.size());
+}
+
+// Interval records of one knot sequence; identical sequences share one run of the table.
 static void fill_leg(LegDev &leg, const double *t, int nk, std::vector<KnotRec> &recs) {
     leg.nk = nk;
     leg.t0 = t[0];
@@ -566,10 +614,7 @@ static void fill_leg(LegDev &leg, const double *t, int nk, std::vector<KnotRec> 
         }
         mine.push_back(r);
     }
-    for (size_t off = 0; off + mine.size() <= recs.size(); off++)
-        if (std::memcmp(&recs[off], mine.data(), sizeof(KnotRec) * mine.size()) == 0) { leg.rec_off = (int)off; return; }
-    leg.rec_off = (int)recs.size();
-    recs.insert(recs.end(), mine.begin(), mine.end());
+    leg.rec_off = intern_run(recs, mine, 1);
 }
 
 // Coefficients, in powers of u = x - t[i], of the cubic B-spline basis function j on the knot interval (t[i], t[i+1]]:
@@ -596,6 +641,27 @@ static void bspline_piece(const double *t, int j, int i, double c[4]) {
     for (int e = 0; e < 4; e++) c[e] = (double)cur[0][e];
 }
 
+// Window rows of one leg, appended to `rows`: for every knot interval i = 3 .. nk - 5 one row of 18 doubles [t_i, t_i+1 |
+// 4 functions x (c0 c1 c2 c3)] -- the polynomial pieces, in powers of x - t_i, of four consecutive basis functions of a window of
+// the leg's functions.  window(i, w_lo, w_ext, sb) names the window the interval's row serves (first function, extent) and the
+// window slot sb of the first of the four: the one thing the users differ in.  Zeros where a function is past the window or
+// vanishes on the interval.  A kernel evaluates a record's window slots straight from the row.  Returns the number of rows.
+template <class Window>
+static int window_rows(const double *tk, int nk, Window window, std::vector<double> &rows) {
+    for (int i = 3; i <= nk - 5; i++) {
+        double row[18] = {0};
+        row[0] = tk[i]; row[1] = tk[i + 1];
+        int w_lo, w_ext, sb;
+        window(i, w_lo, w_ext, sb);
+        for (int fq = 0; fq < 4 && sb + fq < w_ext; fq++) {
+            const int j = w_lo + sb + fq;
+            if (j >= i - 3 && j <= i && j >= 0 && j <= nk - 5) bspline_piece(tk, j, i, row + 2 + 4 * fq);
+        }
+        rows.insert(rows.end(), row, row + 18);
+    }
+    return std::max(0, nk - 7);
+}
+
 // Range tests on the squared distance.  The kernels form s = (dx dx + dy dy) + dz dz without fused operations and take the
 // correctly rounded root, so that "d < r" agrees with the reference's cdist to the last bit; the root is monotonic in s, so
 // the same decisions can be taken on s itself against thresholds found here, and the root is left to the few candidates kept.
@@ -612,42 +678,63 @@ static double sq_root_ge(double r) {          // the smallest double s with sqrt
     return s;
 }
 
-extern "C" int uf3_basis_create(uf3_ctx *c, const uf3_basis_spec *s, uf3_basis **out) {
-    uf3_env_refresh();
-    if (!c || !s || !out) return fail(c, UF3_EINVAL, "uf3_basis_create: null argument");
-    if (s->n_species < 1 || s->n_species > UF3_MAX_SPECIES)
-        return fail(c, UF3_EINVAL, "uf3_basis_create: 1..8 species supported");
-    if (s->n_pairs != s->n_species * (s->n_species + 1) / 2)
-        return fail(c, UF3_EINVAL, "uf3_basis_create: n_pairs must be S(S+1)/2");
-    HIPCHK(c, hipSetDevice(c->device));
-    uf3_basis *b = new uf3_basis();
-    b->ctx = c;
-    b->r_cut = s->r_cut;
-    BasisDev &h = b->host;
-    std::memset(&h, 0, sizeof(h));
-    h.S = s->n_species; h.P = s->n_pairs; h.T = s->n_trios; h.F = s->n_feat;
-    h.lead2 = s->lead2; h.trail2 = s->trail2;
-    std::memset(h.z2s, -1, sizeof(h.z2s));
-    for (int i = 0; i < h.S; i++) {
-        int z = s->species_z[i];
-        if (z < 1 || z >= 120 || (i && z <= s->species_z[i - 1])) { delete b; return fail(c, UF3_EINVAL, "species_z must be ascending atomic numbers"); }
-        h.z2s[z] = (signed char)i;
+// Every refusal of a spec but one (more knot intervals than the grouped windows can number: plan_window_rows), before anything is
+// derived: the stages below index by what the spec says.  The message, or nothing.
+static std::string basis_check(const uf3_basis_spec *s) {
+    const int S = s->n_species, T = s->n_trios;
+    if (S < 1 || S > UF3_MAX_SPECIES) return "uf3_basis_create: 1..8 species supported";
+    if (s->n_pairs != S * (S + 1) / 2) return "uf3_basis_create: n_pairs must be S(S+1)/2";
+    int z2s[120];
+    for (int &v : z2s) v = -1;
+    for (int i = 0; i < S; i++) {
+        const int z = s->species_z[i];
+        if (z < 1 || z >= 120 || (i && z <= s->species_z[i - 1])) return "species_z must be ascending atomic numbers";
+        z2s[z] = i;
     }
-    for (auto &v : h.pair_of) v = -1;
-    for (auto &v : h.trio_of) v = -1;
-    std::vector<KnotRec> recs;
-    std::vector<int> bounds;
-    for (int i = 0; i <= h.S; i++) bounds.push_back(i);
+    auto species = [&](int z) { return z > 0 && z < 120 ? z2s[z] : -1; };
+    int top = S;                                 // where the last column block ends
+    for (int p = 0; p < s->n_pairs; p++) {
+        const int nk = s->pair_nk[p], col = s->pair_col[p];
+        if (species(s->pair_z[2 * p]) < 0 || species(s->pair_z[2 * p + 1]) < 0 || nk < 8 || col < 0) return "bad pair block";
+        top = std::max(top, col + nk - 4);
+    }
+    if (T < 0) return "bad trio block";
+    for (int t = 0; t < T; t++) {
+        const int sc = species(s->trio_z[3 * t]), sa = species(s->trio_z[3 * t + 1]), sb = species(s->trio_z[3 * t + 2]);
+        if (sc < 0 || sa < 0 || sb < 0 || sa > sb || s->trio_col[t] < 0 || s->trio_ncol[t] < 0) return "bad trio block";
+        for (int d = 0; d < 3; d++) if (s->trio_nk[3 * t + d] < 8) return "trio knot vector too short";
+        top = std::max(top, s->trio_col[t] + s->trio_ncol[t]);
+    }
+    std::vector<int> most(T, 0);                 // per trio: the most raw bins that feed one of its columns
+    const int32_t *lut = s->trio_lut;
+    for (int t = 0; t < T; t++) {
+        const int *nk = s->trio_nk + 3 * t, ncol = s->trio_ncol[t];
+        const size_t n = (size_t)(nk[0] - 4) * (nk[1] - 4) * (nk[2] - 4);
+        std::vector<int> fed(ncol, 0);
+        for (size_t q = 0; q < n; q++) {
+            const int v = lut[q];
+            if (v >= ncol) return "trio_lut entry out of range";
+            if (v >= 0) most[t] = std::max(most[t], ++fed[v]);
+        }
+        lut += n;
+    }
+    for (int t = 0; t < T; t++) {
+        for (int d = 0; d < 3; d++) if (s->trio_nk[3 * t + d] - 4 > 255) return "3-body grid dimension > 255";
+        if (most[t] > 6) return "a 3-body column is fed by more than 6 raw bins";
+    }
+    if (top != s->n_feat) return "column blocks do not add up to n_feat";
+    return "";
+}
+
+static void plan_pairs(const uf3_basis_spec *s, BasisPlan &P) {
+    BasisDev &h = P.host;
     const double *kp = s->pair_knots;
     h.rmax2 = 0;
     for (int p = 0; p < h.P; p++) {
-        int za = s->pair_z[2 * p], zb = s->pair_z[2 * p + 1];
-        int a = (za > 0 && za < 120) ? h.z2s[za] : -1, bb = (zb > 0 && zb < 120) ? h.z2s[zb] : -1;
-        int nk = s->pair_nk[p];
-        if (a < 0 || bb < 0 || nk < 8) { delete b; return fail(c, UF3_EINVAL, "bad pair block"); }
+        const int a = h.z2s[s->pair_z[2 * p]], bb = h.z2s[s->pair_z[2 * p + 1]], nk = s->pair_nk[p];
         h.pair_of[a * UF3_MAX_SPECIES + bb] = h.pair_of[bb * UF3_MAX_SPECIES + a] = (short)p;
         PairDev &pd = h.pairs[p];
-        fill_leg(pd.leg, kp, nk, recs);
+        fill_leg(pd.leg, kp, nk, P.recs);
         pd.col = s->pair_col[p];
         pd.nb = nk - 4;
         pd.sa = std::min(a, bb); pd.sb = std::max(a, bb);
@@ -655,30 +742,30 @@ extern "C" int uf3_basis_create(uf3_ctx *c, const uf3_basis_spec *s, uf3_basis *
         pd.rmax = s->pair_rmax[p];
         pd.s_lo = sq_root_le(pd.rmin); pd.s_hi = sq_root_ge(pd.rmax);
         h.rmax2 = std::max(h.rmax2, pd.rmax);
-        bounds.push_back(pd.col + pd.nb);
-        b->c2_len += (size_t)pd.nb;
+        P.block_bounds.push_back(pd.col + pd.nb);
+        P.c2_len += (size_t)pd.nb;
         kp += nk;
     }
-    b->n_pair_recs = recs.size();
-    std::vector<TrioDev> trios(h.T);
-    std::vector<const double *> legn_knots(h.T, nullptr);        // knots of leg n of every trio
-    std::vector<const double *> leg_knots(3 * (size_t)h.T, nullptr);   // ... and of every leg
+    P.n_pair_recs = P.recs.size();
+}
+
+// The legs, grid and place in the LUT of every trio, and the 3-body list range.  Returns the knots of every leg, [3 t + leg].
+static std::vector<const double *> plan_trio_legs(const uf3_basis_spec *s, BasisPlan &P) {
+    BasisDev &h = P.host;
+    P.trios.resize(h.T);
+    std::vector<const double *> knots(3 * (size_t)h.T, nullptr);
     const double *tp = s->trio_knots;
     double lo3 = 1e300, hi3 = -1e300;
     size_t lut_len = 0;
     for (int t = 0; t < h.T; t++) {
-        int zc = s->trio_z[3 * t], za = s->trio_z[3 * t + 1], zb = s->trio_z[3 * t + 2];
-        int sc = h.z2s[zc], sa = h.z2s[za], sb = h.z2s[zb];
-        if (sc < 0 || sa < 0 || sb < 0 || sa > sb) { delete b; return fail(c, UF3_EINVAL, "bad trio block"); }
+        const int sc = h.z2s[s->trio_z[3 * t]], sa = h.z2s[s->trio_z[3 * t + 1]], sb = h.z2s[s->trio_z[3 * t + 2]];
         h.trio_of[(sc * UF3_MAX_SPECIES + sa) * UF3_MAX_SPECIES + sb] = (short)t;
         h.trio_of[(sc * UF3_MAX_SPECIES + sb) * UF3_MAX_SPECIES + sa] = (short)t;
-        TrioDev &td = trios[t];
+        TrioDev &td = P.trios[t];
         for (int d = 0; d < 3; d++) {
-            int nk = s->trio_nk[3 * t + d];
-            if (nk < 8) { delete b; return fail(c, UF3_EINVAL, "trio knot vector too short"); }
-            fill_leg(td.leg[d], tp, nk, recs);
-            if (d == 2) legn_knots[t] = tp;
-            leg_knots[3 * (size_t)t + d] = tp;
+            const int nk = s->trio_nk[3 * t + d];
+            fill_leg(td.leg[d], tp, nk, P.recs);
+            knots[3 * (size_t)t + d] = tp;
             for (int q = 0; q < nk; q++) {
                 lo3 = std::min(lo3, tp[q]);
                 if (d < 2) hi3 = std::max(hi3, tp[q]);     // angles.py:322-325: centre legs only
@@ -691,416 +778,469 @@ extern "C" int uf3_basis_create(uf3_ctx *c, const uf3_basis_spec *s, uf3_basis *
         td.sc = sc; td.sa = sa; td.sb = sb;
         td.lut_off = (int)lut_len;
         lut_len += (size_t)td.dim_l * td.dim_m * td.dim_n;
-        bounds.push_back(td.col + td.ncol);
+        P.block_bounds.push_back(td.col + td.ncol);
     }
-    b->c3_len = lut_len;
+    P.c3_len = lut_len;
+    P.lut.assign(lut_len ? lut_len : 1, -1);
     h.rmin3 = h.T ? std::max(lo3, 0.0) : 0.0;
     h.rmax3 = h.T ? hi3 : 0.0;
     h.s3_lo = sq_root_le(h.rmin3); h.s3_hi = sq_root_le(h.rmax3);
     h.rsearch = std::max(h.rmax2, h.rmax3);
-    std::vector<int> lut(lut_len ? lut_len : 1, -1);
-    for (int t = 0; t < h.T; t++) {
-        size_t n = (size_t)trios[t].dim_l * trios[t].dim_m * trios[t].dim_n;
-        const int32_t *src = s->trio_lut + trios[t].lut_off;
-        for (size_t q = 0; q < n; q++) {
-            int v = src[q];
-            if (v >= trios[t].ncol) { delete b; return fail(c, UF3_EINVAL, "trio_lut entry out of range"); }
-            lut[trios[t].lut_off + q] = v < 0 ? -1 : trios[t].col + v;
-        }
-    }
-    // per column: the distinct raw bins (symmetry images) that feed it, for the output-stationary kernel
-    std::vector<int> colsrc, dsrc;
-    for (int t = 0; t < h.T; t++) {
-        TrioDev &td = trios[t];
-        if (td.dim_l > 255 || td.dim_m > 255 || td.dim_n > 255) { delete b; return fail(c, UF3_EINVAL, "3-body grid dimension > 255"); }
-        std::vector<std::vector<int>> per_col(td.ncol);
-        size_t n = (size_t)td.dim_l * td.dim_m * td.dim_n;
-        for (size_t q = 0; q < n; q++) {
-            int v = s->trio_lut[td.lut_off + q];
-            if (v < 0) continue;
-            int l = (int)(q / ((size_t)td.dim_m * td.dim_n)), m = (int)((q / td.dim_n) % td.dim_m), nn = (int)(q % td.dim_n);
-            per_col[v].push_back(l | (m << 8) | (nn << 16));
-        }
-        size_t mx = 1;
-        for (auto &v : per_col) mx = std::max(mx, v.size());
-        td.nsrc = mx <= 1 ? 1 : (mx <= 2 ? 2 : 6);
-        if (mx > 6) { delete b; return fail(c, UF3_EINVAL, "a 3-body column is fed by more than 6 raw bins"); }
-        td.src_off = (int)colsrc.size();
-        // bounding box of the feeding raw bins; small boxes go to the MFMA specialisation (mode 6)
-        int lo[3] = {1 << 20, 1 << 20, 1 << 20}, hi[3] = {-1, -1, -1};
-        for (auto &v : per_col) for (int sp : v) {
-            int idx[3] = {sp & 255, (sp >> 8) & 255, (sp >> 16) & 255};
-            for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], idx[a]); hi[a] = std::max(hi[a], idx[a]); }
-        }
-        td.dense = 0;
-        for (int a = 0; a < 3; a++) { td.lo[a] = hi[a] < 0 ? 0 : lo[a]; td.ext[a] = hi[a] < 0 ? 1 : hi[a] - lo[a] + 1; }
-        // rows (c, l) x columns (m, n) of the window in 16 x 16 tiles: (1,1) (1,2) (1,<=4) (<=2,<=6) have a matrix-core
-        // specialisation (modes 6-9); wider windows stay on the generic kernels
-        DenseLayout dl = dense_layout(td.ext[0], td.ext[1], td.ext[2]);
-        const int dmode = dense_mode_for(td.ext[0], td.ext[1], td.ext[2]);
-        if (dmode && !uf3_env("UF3_NO_MFMA_FEAT")) {
-            td.dense = dmode;
-            b->dense_stride[dmode] = std::max(b->dense_stride[dmode], dl.stride);
-            b->dense_dump[dmode] = std::max(b->dense_dump[dmode], td.ext[0] * dl.cw);
-        }
-        td.grouped = 0; td.gthr0 = -1e300; td.gthr2 = 1e300;
-        if (td.dense == 7 && td.ext[1] == 3 && td.ext[0] <= 3 && td.ext[2] >= 6 && td.ext[2] <= 9 && td.nsrc <= 2 && td.ncol <= 128) {
-            // first window bin f = interval - 3 - lo_n: f <= 1 -> group 0 (bins 0..4), f >= 4 -> group 2 (bins 4..8)
-            const double *tn = legn_knots[t];
-            const int nk = td.leg[2].nk, i_lo = 3, i_hi = nk - 5;
-            const int i0 = td.lo[2] + 4, i2 = td.lo[2] + 7;       // last interval of group 0, first of group 2
-            td.grouped = 1;
-            if (i0 >= i_lo) td.gthr0 = tn[std::min(i0, i_hi) + 1];
-            if (i2 <= i_hi) td.gthr2 = tn[std::max(i2, i_lo)];
-        }
-        // wide windows (mode 9, two row tiles): cut the intervals of leg n into at most three bands whose records touch at most
-        // three neighbouring column tiles (trio_block_banded); windows that do not fit keep the dense loop
-        td.banded = 0; td.band_tile[0] = td.band_tile[1] = td.band_tile[2] = 0;
-        if (td.dense == 9 && dl.stride == 64 && (4 * td.ext[0] + 15) / 16 == 2) {
-            const double *tn = legn_knots[t];
-            const int i_lo = 3, i_hi = td.leg[2].nk - 5, n_ct = (td.ext[1] * td.ext[2] + 15) / 16;
-            auto tiles_of = [&](int i, int &t0, int &t1) {
-                const int f = i - 3 - td.lo[2], n0 = std::max(f, 0), n1 = std::min(f + 3, td.ext[2] - 1);
-                if (n0 > n1) return false;
-                t0 = (n0 * td.ext[1]) / 16; t1 = ((n1 + 1) * td.ext[1] - 1) / 16;
-                return true;
-            };
-            int band_first[4] = {i_lo, -1, -1, -1}, band_lo[3] = {-1, -1, -1}, nb = 0;
-            bool ok = true;
-            for (int i = i_lo; i <= i_hi && ok; i++) {
-                int t0, t1;
-                if (!tiles_of(i, t0, t1)) continue;                       // (an interval outside the window: any band)
-                if (band_lo[nb] < 0) band_lo[nb] = t0;
-                if (t1 - band_lo[nb] + 1 > 3) {                           // does not fit the open band: start the next one
-                    if (++nb > 2) { ok = false; break; }
-                    band_first[nb] = i; band_lo[nb] = t0;
-                    if (t1 - t0 + 1 > 3) ok = false;
-                }
-            }
-            if (ok) {
-                td.banded = 1;
-                td.gthr0 = nb >= 1 ? tn[band_first[1]] : 1e300;           // r_n <= t_i: interval < i
-                td.gthr2 = nb >= 2 ? tn[band_first[2]] : 1e300;
-                for (int q = 0; q < 3; q++) td.band_tile[q] = std::max(0, std::min(band_lo[q] < 0 ? 0 : band_lo[q], std::max(0, n_ct - 3)));
-                b->dense_grouped[9] = true;
-            }
-        }
-        if (td.dense) b->dense_stride_f[td.dense] = std::max(b->dense_stride_f[td.dense], td.grouped ? 34 : dl.stride);
-        if (td.grouped && (td.leg[0].nk > 255 || td.leg[1].nk > 255 || td.leg[2].nk > 255 || recs.size() > 65535)) td.grouped = 0;   // (GroupedLayout packs them)
-        if (td.dense && td.grouped) b->dense_grouped[td.dense] = true;
-        td.thr0 = -1e300; td.thr2 = 1e300;
-        if (td.dense && dense_ct(td.dense) == 2) {
-            // intervals of leg n in order: tile 0 only, ..., tile 1 only (an interval i holds t_i < r <= t_{i+1})
-            const double *tn = legn_knots[t];
-            auto tiles_of = [&](int i) {
-                const int f = i - 3 - td.lo[2], n0 = std::max(f, 0), n1 = std::min(f + 3, td.ext[2] - 1);
-                if (n0 > n1) return 0;
-                return ((n0 * td.ext[1]) < 16 ? 1 : 0) | (((n1 + 1) * td.ext[1] - 1) >= 16 ? 2 : 0);
-            };
-            const int i_lo = 3, i_hi = td.leg[2].nk - 5;
-            int i0 = i_lo - 1, i2 = i_hi + 1;
-            while (i0 + 1 <= i_hi && !(tiles_of(i0 + 1) & 2)) i0++;      // last interval of the leading run without tile 1
-            while (i2 - 1 >= i_lo && !(tiles_of(i2 - 1) & 1)) i2--;      // first interval of the trailing run without tile 0
-            if (i0 >= i_lo) td.thr0 = tn[i0 + 1];
-            if (i2 <= i_hi) td.thr2 = tn[i2];
-        }
-        b->modes |= 1 << (td.dense ? td.dense : td.nsrc == 1 ? (td.ncol > WAVE ? 2 : 1) : (td.nsrc == 2 ? (td.ncol > WAVE ? 4 : 3) : 5));
-        b->vmodes |= 1 << (td.nsrc == 1 ? (td.ncol > WAVE ? 2 : 1) : (td.nsrc == 2 ? (td.ncol > WAVE ? 4 : 3) : 5));
-        for (auto &v : per_col) for (int k = 0; k < td.nsrc; k++) {
-            int sp = k < (int)v.size() ? v[k] : -1;
-            colsrc.push_back(sp);
-            // offset inside one component's dumped rows: row l (width cw), columns n-major (n * ext_m + m)
-            dsrc.push_back(sp < 0 || !td.dense ? -1
-                           : ((sp & 255) - td.lo[0]) * dl.cw + (((sp >> 16) & 255) - td.lo[2]) * td.ext[1] + (((sp >> 8) & 255) - td.lo[1]));
-        }
-    }
-    // grouped windows: number the distinct window layouts and write the fold tables -- per column, for (source 0 | 1) x
-    // (group 0 | 1 | 2), the double index of the source bin inside the dumped group tiles ([group][row 4 c + l][16 columns],
-    // component 0) or 15, an entry no record touches
-    std::vector<unsigned short> gsrc;
-    {
-        std::vector<int> layout_rep;                 // first trio of every layout
-        for (int t = 0; t < h.T; t++) {
-            TrioDev &td = trios[t];
-            td.layout = -1; td.gsrc_off = 0;
-            if (!td.grouped) continue;
-            auto same_leg = [](const LegDev &a, const LegDev &b2) {
-                return a.rec_off == b2.rec_off && a.nk == b2.nk && a.t0 == b2.t0 && a.tlast == b2.tlast && a.inv_h == b2.inv_h;
-            };
-            for (size_t q = 0; q < layout_rep.size() && td.layout < 0; q++) {
-                const TrioDev &o = trios[layout_rep[q]];
-                bool same = o.gthr0 == td.gthr0 && o.gthr2 == td.gthr2;
-                for (int a = 0; a < 3; a++) same = same && o.lo[a] == td.lo[a] && o.ext[a] == td.ext[a] && same_leg(o.leg[a], td.leg[a]);
-                if (same) td.layout = (int)q;
-            }
-            if (td.layout < 0) { td.layout = (int)layout_rep.size(); layout_rep.push_back(t); }
-            if (td.layout > 254) { td.grouped = 0; td.layout = -1; continue; }     // (never in practice: the ordinary two-tile path)
-            std::vector<unsigned short> mine;
-            for (int col = 0; col < td.ncol; col++)
-                for (int q = 0; q < 2; q++) {
-                    const int sp = q < td.nsrc ? colsrc[td.src_off + col * td.nsrc + q] : -1;
-                    for (int grp = 0; grp < 3; grp++) {
-                        unsigned short a = 15;
-                        if (sp >= 0) {
-                            const int l_rel = (sp & 255) - td.lo[0], m_rel = ((sp >> 8) & 255) - td.lo[1], n_rel = ((sp >> 16) & 255) - td.lo[2];
-                            const int nl = n_rel - 2 * grp;
-                            if (nl >= 0 && nl < 5) a = (unsigned short)(grp * 256 + l_rel * 16 + nl * td.ext[1] + m_rel);
-                        }
-                        mine.push_back(a);
-                    }
-                }
-            // (identical tables -- the same symmetry on the same layout -- are stored once: small enough for LDS)
-            td.gsrc_off = -1;
-            for (size_t off = 0; off + mine.size() <= gsrc.size() && td.gsrc_off < 0; off += 2)
-                if (std::equal(mine.begin(), mine.end(), gsrc.begin() + off)) td.gsrc_off = (int)off;
-            if (td.gsrc_off < 0) {
-                td.gsrc_off = (int)gsrc.size();
-                gsrc.insert(gsrc.end(), mine.begin(), mine.end());
-                while (gsrc.size() & 1) gsrc.push_back(15);      // (blocks start on a 4-byte boundary)
-            }
-        }
-        // Window rows of the grouped layouts, appended to the knot records (so they travel to LDS with them): for every leg and
-        // knot interval i one row of 18 doubles [t_i, t_i+1 | 4 functions x (c0 c1 c2 c3)] -- the polynomial pieces, in powers of
-        // x - t_i, of four consecutive basis functions of the leg's window (leg n: the window of the GROUP interval i belongs
-        // to), starting at window slot sb: 0 for the legs l and m (three slots: the fourth function is not stored), and
-        // clamp(i - 3 - window start, 0, 1) for leg n (five slots: every function alive on the interval is among the four, the
-        // fifth slot is zero).  Zeros where a function is past the window or vanishes on the interval.  The staging pass
-        // evaluates a record's window slots straight from the row, every slot of every record is written in every pass, and
-        // nothing has to be cleared (trio_block_grouped).  TrioDev::wrow: the number of a leg's first row.
-        b->wrow_lo = recs.size();
-        std::vector<double> wrows;
-        int n_rows = 0;
-        for (size_t q = 0; q < layout_rep.size(); q++) {
-            const int t = layout_rep[q];
-            TrioDev &rep = trios[t];
-            for (int a = 0; a < 3; a++) {
-                const double *tk = leg_knots[3 * (size_t)t + a];
-                const int nk = rep.leg[a].nk;
-                rep.wrow[a] = n_rows;
-                for (int i = 3; i <= nk - 5; i++, n_rows++) {
-                    double row[18] = {0};
-                    row[0] = tk[i]; row[1] = tk[i + 1];
-                    int w_lo = rep.lo[a], w_ext = a == 0 ? rep.ext[0] : 3, sb = 0;
-                    if (a == 2) {
-                        const int f = i - 3 - rep.lo[2], grp = f <= 1 ? 0 : (f >= 4 ? 2 : 1);
-                        w_lo = rep.lo[2] + 2 * grp; w_ext = std::min(5, rep.ext[2] - 2 * grp);
-                        sb = std::max(0, std::min(1, f - 2 * grp));
-                    }
-                    for (int fq = 0; fq < 4 && sb + fq < w_ext; fq++) {
-                        const int j = w_lo + sb + fq;
-                        if (j >= i - 3 && j <= i && j >= 0 && j <= nk - 5) bspline_piece(tk, j, i, row + 2 + 4 * fq);
-                    }
-                    wrows.insert(wrows.end(), row, row + 18);
-                }
-            }
-        }
-        // (rows of nine 16-byte pairs, one behind the other: lanes that read pair k of different rows hit different banks -- 9 is
-        // odd, rows 16 apart share one)
-        b->n_wrows = n_rows;
-        while (wrows.size() % 12) wrows.push_back(0.0);
-        for (size_t q = 0; q < wrows.size(); q += 12) {
-            KnotRec kr;
-            std::memcpy(&kr, &wrows[q], sizeof kr);
-            recs.push_back(kr);
-        }
-        for (auto &td : trios)
-            if (td.grouped && td.layout >= 0) for (int a = 0; a < 3; a++) td.wrow[a] = trios[layout_rep[td.layout]].wrow[a];
-        if (n_rows > 65535)                                                 // (GroupedLayout packs the row numbers in 16 bits)
-            for (auto &td : trios) if (td.grouped) { delete b; return fail(c, UF3_EINVAL, "too many knot intervals for the grouped windows"); }
-    }
-    std::sort(bounds.begin(), bounds.end());
-    bounds.erase(std::unique(bounds.begin(), bounds.end()), bounds.end());
-    if (bounds.back() != h.F) { delete b; return fail(c, UF3_EINVAL, "column blocks do not add up to n_feat"); }
-    b->block_bounds = bounds;
+    return knots;
+}
 
-    b->n_recs = recs.size();
-    b->trio_rec_lo = recs.size();
-    for (auto &td : trios) for (int d = 0; d < 3; d++) b->trio_rec_lo = std::min(b->trio_rec_lo, (size_t)td.leg[d].rec_off);
-    HIPCHK(c, hipMalloc(&b->d_recs, sizeof(KnotRec) * std::max<size_t>(1, recs.size())));
-    HIPCHK(c, hipMemcpy(b->d_recs, recs.data(), sizeof(KnotRec) * recs.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc(&b->d_lut, sizeof(int) * lut.size()));
-    HIPCHK(c, hipMemcpy(b->d_lut, lut.data(), sizeof(int) * lut.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc(&b->d_colsrc, sizeof(int) * std::max<size_t>(1, colsrc.size())));
-    if (!colsrc.empty()) HIPCHK(c, hipMemcpy(b->d_colsrc, colsrc.data(), sizeof(int) * colsrc.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc(&b->d_dsrc, sizeof(int) * std::max<size_t>(1, dsrc.size())));
-    if (!dsrc.empty()) HIPCHK(c, hipMemcpy(b->d_dsrc, dsrc.data(), sizeof(int) * dsrc.size(), hipMemcpyHostToDevice));
-    b->n_dsrc = dsrc.size();
-    b->n_gsrc = gsrc.size();
-    b->all_grouped7 = true;
-    for (auto &td : trios) if (td.dense == 7 && !td.grouped) b->all_grouped7 = false;
-    b->all_banded9 = true;
-    for (auto &td : trios)      // (the banded-only launch names its accumulator tiles at compile time: bands on the tiles 0, 1, 2)
-        if (td.dense == 9 && !(td.banded && td.band_tile[0] == 0 && td.band_tile[1] == 1 && td.band_tile[2] == 2)) b->all_banded9 = false;
-    HIPCHK(c, hipMalloc(&b->d_gsrc, sizeof(unsigned short) * std::max<size_t>(8, gsrc.size() + 8)));
-    if (!gsrc.empty()) HIPCHK(c, hipMemcpy(b->d_gsrc, gsrc.data(), sizeof(unsigned short) * gsrc.size(), hipMemcpyHostToDevice));
-    for (auto &td : trios)
-        td.head = TrioHead{td.dense, td.nsrc, td.ncol, td.sc, td.sa, td.sb, td.col,
-                           td.grouped ? ((td.layout + 1) | (td.gsrc_off << 8))
-                                      : (td.banded ? (1 | (td.band_tile[0] << 8) | (td.band_tile[1] << 12) | (td.band_tile[2] << 16)) : 0)};
-    HIPCHK(c, hipMalloc(&b->d_trios, sizeof(TrioDev) * std::max<size_t>(1, trios.size())));
-    if (!trios.empty())
-        HIPCHK(c, hipMemcpy(b->d_trios, trios.data(), sizeof(TrioDev) * trios.size(), hipMemcpyHostToDevice));
-    h.trios = b->d_trios; h.recs = b->d_recs; h.lut = b->d_lut;
+// One walk of a trio's part of the LUT: its entries as global columns, and per column the distinct raw bins (symmetry images) that
+// feed it, l | m << 8 | n << 16, for the output-stationary kernels.  With them nsrc and the window: the bounding box of those bins.
+static std::vector<std::vector<int>> trio_sources(const uf3_basis_spec *s, TrioDev &td, std::vector<int> &lut) {
+    std::vector<std::vector<int>> per_col(td.ncol);
+    const size_t n = (size_t)td.dim_l * td.dim_m * td.dim_n;
+    for (size_t q = 0; q < n; q++) {
+        const int v = s->trio_lut[td.lut_off + q];
+        lut[td.lut_off + q] = v < 0 ? -1 : td.col + v;
+        if (v < 0) continue;
+        const int l = (int)(q / ((size_t)td.dim_m * td.dim_n)), m = (int)((q / td.dim_n) % td.dim_m), nn = (int)(q % td.dim_n);
+        per_col[v].push_back(l | (m << 8) | (nn << 16));
+    }
+    size_t mx = 1;
+    for (auto &v : per_col) mx = std::max(mx, v.size());
+    td.nsrc = mx <= 1 ? 1 : (mx <= 2 ? 2 : 6);
+    int lo[3] = {1 << 20, 1 << 20, 1 << 20}, hi[3] = {-1, -1, -1};
+    for (auto &v : per_col) for (int sp : v) {
+        const int idx[3] = {sp & 255, (sp >> 8) & 255, (sp >> 16) & 255};
+        for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], idx[a]); hi[a] = std::max(hi[a], idx[a]); }
+    }
+    for (int a = 0; a < 3; a++) { td.lo[a] = hi[a] < 0 ? 0 : lo[a]; td.ext[a] = hi[a] < 0 ? 1 : hi[a] - lo[a] + 1; }
+    return per_col;
+}
+
+// rows (c, l) x columns (m, n) of the window in 16 x 16 tiles: (1,1) (1,2) (1,<=4) (<=2,<=6) have a matrix-core specialisation
+// (modes 6-9); wider windows stay on the generic kernels
+static void trio_dense_mode(TrioDev &td, const DenseLayout &dl, unsigned switches, BasisPlan &P) {
+    td.dense = (switches & BASIS_NO_MFMA_FEAT) ? 0 : dense_mode_for(td.ext[0], td.ext[1], td.ext[2]);
+    if (!td.dense) return;
+    P.dense_stride[td.dense] = std::max(P.dense_stride[td.dense], dl.stride);
+    P.dense_dump[td.dense] = std::max(P.dense_dump[td.dense], td.ext[0] * dl.cw);
+}
+
+// 3 x 3 x 6..9 windows of mode 7 stage grouped n windows; tn: the knots of leg n, n_knot_recs: the knot records of all legs
+static void trio_grouped(TrioDev &td, const DenseLayout &dl, const double *tn, size_t n_knot_recs, BasisPlan &P) {
+    td.grouped = 0; td.gthr0 = -1e300; td.gthr2 = 1e300;
+    if (td.dense == 7 && td.ext[1] == 3 && td.ext[0] <= 3 && td.ext[2] >= 6 && td.ext[2] <= 9 && td.nsrc <= 2 && td.ncol <= 128) {
+        // first window bin f = interval - 3 - lo_n: f <= 1 -> group 0 (bins 0..4), f >= 4 -> group 2 (bins 4..8)
+        const int nk = td.leg[2].nk, i_lo = 3, i_hi = nk - 5;
+        const int i0 = td.lo[2] + 4, i2 = td.lo[2] + 7;       // last interval of group 0, first of group 2
+        td.grouped = 1;
+        if (i0 >= i_lo) td.gthr0 = tn[std::min(i0, i_hi) + 1];
+        if (i2 <= i_hi) td.gthr2 = tn[std::max(i2, i_lo)];
+    }
+    if (td.dense) P.dense_stride_f[td.dense] = std::max(P.dense_stride_f[td.dense], td.grouped ? 34 : dl.stride);
+    if (td.grouped && (td.leg[0].nk > 255 || td.leg[1].nk > 255 || td.leg[2].nk > 255 || n_knot_recs > 65535)) td.grouped = 0;   // (GroupedLayout packs them)
+    if (td.dense && td.grouped) P.dense_grouped[td.dense] = true;
+}
+
+// The column tiles (16 n-major columns each) that the records of knot interval i of leg n touch; false: the interval lies outside
+// the window
+static bool tiles_of(const TrioDev &td, int i, int &t0, int &t1) {
+    const int f = i - 3 - td.lo[2], n0 = std::max(f, 0), n1 = std::min(f + 3, td.ext[2] - 1);
+    if (n0 > n1) return false;
+    t0 = (n0 * td.ext[1]) / 16; t1 = ((n1 + 1) * td.ext[1] - 1) / 16;
+    return true;
+}
+
+// wide windows (mode 9, two row tiles): cut the intervals of leg n into at most three bands whose records touch at most three
+// neighbouring column tiles (trio_block_banded); windows that do not fit keep the dense loop
+static void trio_bands(TrioDev &td, const DenseLayout &dl, const double *tn, BasisPlan &P) {
+    td.banded = 0; td.band_tile[0] = td.band_tile[1] = td.band_tile[2] = 0;
+    if (!(td.dense == 9 && dl.stride == 64 && (4 * td.ext[0] + 15) / 16 == 2)) return;
+    const int i_lo = 3, i_hi = td.leg[2].nk - 5, n_ct = (td.ext[1] * td.ext[2] + 15) / 16;
+    int band_first[4] = {i_lo, -1, -1, -1}, band_lo[3] = {-1, -1, -1}, nb = 0;
+    for (int i = i_lo; i <= i_hi; i++) {
+        int t0, t1;
+        if (!tiles_of(td, i, t0, t1)) continue;                   // (an interval outside the window: any band)
+        if (band_lo[nb] < 0) band_lo[nb] = t0;
+        if (t1 - band_lo[nb] + 1 > 3) {                           // does not fit the open band: start the next one
+            if (++nb > 2 || t1 - t0 + 1 > 3) return;
+            band_first[nb] = i; band_lo[nb] = t0;
+        }
+    }
+    td.banded = 1;
+    td.gthr0 = nb >= 1 ? tn[band_first[1]] : 1e300;               // r_n <= t_i: interval < i
+    td.gthr2 = nb >= 2 ? tn[band_first[2]] : 1e300;
+    for (int q = 0; q < 3; q++) td.band_tile[q] = std::max(0, std::min(band_lo[q] < 0 ? 0 : band_lo[q], std::max(0, n_ct - 3)));
+    P.dense_grouped[9] = true;
+}
+
+// two column tiles: the intervals of leg n in order are tile 0 only, ..., tile 1 only (an interval i holds t_i < r <= t_{i+1})
+static void trio_tile_thresholds(TrioDev &td, const double *tn) {
+    td.thr0 = -1e300; td.thr2 = 1e300;
+    if (!(td.dense && dense_ct(td.dense) == 2)) return;
+    const int i_lo = 3, i_hi = td.leg[2].nk - 5;
+    auto misses = [&](int i, int tile) { int t0, t1; return !tiles_of(td, i, t0, t1) || (tile ? t1 < 1 : t0 > 0); };
+    int i0 = i_lo - 1, i2 = i_hi + 1;
+    while (i0 + 1 <= i_hi && misses(i0 + 1, 1)) i0++;      // last interval of the leading run without tile 1
+    while (i2 - 1 >= i_lo && misses(i2 - 1, 0)) i2--;      // first interval of the trailing run without tile 0
+    if (i0 >= i_lo) td.thr0 = tn[i0 + 1];
+    if (i2 <= i_hi) td.thr2 = tn[i2];
+}
+
+// the output-stationary instance (1 .. 5, of k_featurize and of k_virial_rows alike) that serves a trio
+static int generic_mode(const TrioDev &td) { return td.nsrc == 1 ? (td.ncol > WAVE ? 2 : 1) : (td.nsrc == 2 ? (td.ncol > WAVE ? 4 : 3) : 5); }
+
+// Per trio: column sources, window, and the layout its launches use
+static void plan_trio_layouts(const uf3_basis_spec *s, unsigned switches, const std::vector<const double *> &knots, BasisPlan &P) {
+    const size_t n_knot_recs = P.recs.size();
+    for (int t = 0; t < P.host.T; t++) {
+        TrioDev &td = P.trios[t];
+        const double *tn = knots[3 * (size_t)t + 2];
+        const std::vector<std::vector<int>> per_col = trio_sources(s, td, P.lut);
+        const DenseLayout dl = dense_layout(td.ext[0], td.ext[1], td.ext[2]);
+        trio_dense_mode(td, dl, switches, P);
+        trio_grouped(td, dl, tn, n_knot_recs, P);
+        trio_bands(td, dl, tn, P);
+        trio_tile_thresholds(td, tn);
+        P.modes |= 1 << (td.dense ? td.dense : generic_mode(td));
+        P.vmodes |= 1 << generic_mode(td);
+        td.src_off = (int)P.colsrc.size();
+        for (auto &v : per_col) for (int k = 0; k < td.nsrc; k++) {
+            const int sp = k < (int)v.size() ? v[k] : -1;
+            P.colsrc.push_back(sp);
+            // offset inside one component's dumped rows: row l (width cw), columns n-major (n * ext_m + m)
+            P.dsrc.push_back(sp < 0 || !td.dense ? -1
+                             : ((sp & 255) - td.lo[0]) * dl.cw + (((sp >> 16) & 255) - td.lo[2]) * td.ext[1] + (((sp >> 8) & 255) - td.lo[1]));
+        }
+    }
+}
+
+// Grouped windows: number the distinct window layouts (by first appearance; returns the first trio of every layout) and write the
+// fold tables -- per column, for (source 0 | 1) x (group 0 | 1 | 2), the double index of the source bin inside the dumped group
+// tiles ([group][row 4 c + l][16 columns], component 0) or 15, an entry no record touches
+static std::vector<int> plan_grouped_folds(BasisPlan &P) {
+    std::vector<int> layout_rep;
+    for (int t = 0; t < P.host.T; t++) {
+        TrioDev &td = P.trios[t];
+        td.layout = -1; td.gsrc_off = 0;
+        if (!td.grouped) continue;
+        for (size_t q = 0; q < layout_rep.size() && td.layout < 0; q++) {
+            const TrioDev &o = P.trios[layout_rep[q]];
+            bool same = o.gthr0 == td.gthr0 && o.gthr2 == td.gthr2;
+            for (int a = 0; a < 3; a++) same = same && o.lo[a] == td.lo[a] && o.ext[a] == td.ext[a] && same_leg(o.leg[a], td.leg[a]);
+            if (same) td.layout = (int)q;
+        }
+        if (td.layout < 0) { td.layout = (int)layout_rep.size(); layout_rep.push_back(t); }
+        if (td.layout > 254) { td.grouped = 0; td.layout = -1; continue; }     // (never in practice: the ordinary two-tile path)
+        std::vector<unsigned short> mine;
+        for (int col = 0; col < td.ncol; col++)
+            for (int q = 0; q < 2; q++) {
+                const int sp = q < td.nsrc ? P.colsrc[td.src_off + col * td.nsrc + q] : -1;
+                for (int grp = 0; grp < 3; grp++) {
+                    unsigned short a = 15;
+                    if (sp >= 0) {
+                        const int l_rel = (sp & 255) - td.lo[0], m_rel = ((sp >> 8) & 255) - td.lo[1], n_rel = ((sp >> 16) & 255) - td.lo[2];
+                        const int nl = n_rel - 2 * grp;
+                        if (nl >= 0 && nl < 5) a = (unsigned short)(grp * 256 + l_rel * 16 + nl * td.ext[1] + m_rel);
+                    }
+                    mine.push_back(a);
+                }
+            }
+        td.gsrc_off = intern_run(P.gsrc, mine, 2);
+        while (P.gsrc.size() & 1) P.gsrc.push_back(15);      // (blocks start on a 4-byte boundary)
+    }
+    return layout_rep;
+}
+
+// Window rows (window_rows) of the grouped layouts, appended to the knot records so that they travel to LDS with them.  The legs l
+// and m: three slots from slot 0 (the fourth function is not stored).  Leg n: the window of the GROUP interval i belongs to, five
+// slots from slot clamp(i - 3 - window start, 0, 1) -- every function alive on the interval is among the four, the fifth slot is
+// zero.  Every slot of every record is written in every staging pass, and nothing has to be cleared (trio_block_grouped).
+// TrioDev::wrow: the number of a leg's first row.
+static bool plan_window_rows(const std::vector<const double *> &knots, const std::vector<int> &layout_rep, BasisPlan &P, std::string &err) {
+    P.wrow_lo = P.recs.size();
+    std::vector<double> wrows;
+    int n_rows = 0;
+    for (const int t : layout_rep) {
+        TrioDev &rep = P.trios[t];
+        for (int a = 0; a < 3; a++) {
+            rep.wrow[a] = n_rows;
+            n_rows += window_rows(knots[3 * (size_t)t + a], rep.leg[a].nk, [&](int i, int &w_lo, int &w_ext, int &sb) {
+                w_lo = rep.lo[a]; w_ext = a == 0 ? rep.ext[0] : 3; sb = 0;
+                if (a == 2) {
+                    const int f = i - 3 - rep.lo[2], grp = f <= 1 ? 0 : (f >= 4 ? 2 : 1);
+                    w_lo = rep.lo[2] + 2 * grp; w_ext = std::min(5, rep.ext[2] - 2 * grp);
+                    sb = std::max(0, std::min(1, f - 2 * grp));
+                }
+            }, wrows);
+        }
+    }
+    // (rows of nine 16-byte pairs, one behind the other: lanes that read pair k of different rows hit different banks -- 9 is
+    // odd, rows 16 apart share one)
+    P.n_wrows = n_rows;
+    while (wrows.size() % 12) wrows.push_back(0.0);
+    for (size_t q = 0; q < wrows.size(); q += 12) {
+        KnotRec kr;
+        std::memcpy(&kr, &wrows[q], sizeof kr);
+        P.recs.push_back(kr);
+    }
+    for (auto &td : P.trios)
+        if (td.grouped && td.layout >= 0) for (int a = 0; a < 3; a++) td.wrow[a] = P.trios[layout_rep[td.layout]].wrow[a];
+    if (n_rows > 65535)                                                 // (GroupedLayout packs the row numbers in 16 bits)
+        for (auto &td : P.trios) if (td.grouped) { err = "too many knot intervals for the grouped windows"; return false; }
+    return true;
+}
+
+// What is uniform over the pairs and over the trios, and with it which instances the evaluator may run
+static void plan_eval(BasisPlan &P) {
+    BasisDev &h = P.host;
+    const std::vector<TrioDev> &trios = P.trios;
     h.pairs_uniform = 1;
     for (int a = 0; a < UF3_MAX_SPECIES * UF3_MAX_SPECIES; a++) h.pair_col[a] = h.pair_of[a] >= 0 ? h.pairs[h.pair_of[a]].col : 0;
-    for (int p2 = 1; p2 < h.P && h.pairs_uniform; p2++) {
-        const PairDev &a = h.pairs[0], &q = h.pairs[p2];
-        if (a.leg.rec_off != q.leg.rec_off || a.leg.nk != q.leg.nk || a.leg.t0 != q.leg.t0 || a.leg.tlast != q.leg.tlast ||
-            a.leg.inv_h != q.leg.inv_h || a.rmin != q.rmin || a.rmax != q.rmax || a.nb != q.nb) h.pairs_uniform = 0;
+    for (int p = 1; p < h.P && h.pairs_uniform; p++) {
+        const PairDev &a = h.pairs[0], &q = h.pairs[p];
+        if (!same_leg(a.leg, q.leg) || a.rmin != q.rmin || a.rmax != q.rmax || a.nb != q.nb) h.pairs_uniform = 0;
     }
     h.trio_legs_uniform = h.T > 0;
     for (int t = 1; t < h.T && h.trio_legs_uniform; t++) {
-        for (int d = 0; d < 3; d++) {
-            const LegDev &a = trios[0].leg[d], &q = trios[t].leg[d];
-            if (a.rec_off != q.rec_off || a.nk != q.nk || a.t0 != q.t0 || a.tlast != q.tlast || a.inv_h != q.inv_h) h.trio_legs_uniform = 0;
-        }
+        for (int d = 0; d < 3; d++) if (!same_leg(trios[0].leg[d], trios[t].leg[d])) h.trio_legs_uniform = 0;
         if (trios[t].dim_l != trios[0].dim_l || trios[t].dim_m != trios[0].dim_m || trios[t].dim_n != trios[0].dim_n) h.trio_legs_uniform = 0;
     }
     // k_eval<TAB>: one set of 3-body legs, the trio tables in one register each, leg n's knot records in the workgroup's LDS
-    b->eval_tab_ok = h.trio_legs_uniform && h.T <= WAVE && trios[0].leg[2].nk - 7 <= EVAL_TAB_KN;
-    if (b->eval_tab_ok && h.T > 0) {
-        const TrioDev &t0 = trios[0];
-        bool ok = t0.lo[0] == t0.lo[1] && t0.ext[0] == t0.ext[1] && t0.ext[0] >= 1;
-        for (int t = 0; t < h.T && ok; t++) {
-            const TrioDev &td = trios[t];
-            ok = td.lo[0] == t0.lo[0] && td.lo[1] == t0.lo[0] && td.ext[0] == t0.ext[0] && td.ext[1] == t0.ext[0] &&
-                 td.dim_m == t0.dim_m && td.dim_n == t0.dim_n && td.dim_l == t0.dim_l;
-        }
-        if (ok) {
-            const int ext = t0.ext[0], dn = t0.dim_n;
-            const size_t table = (size_t)h.T * ext * ext * dn * 8;
-            const size_t zero = ((size_t)(3 * ext + 3) * dn * 8 + 32 + 15) / 16 * 16;        // (any row offset + one row's 32 bytes)
-            const size_t total = (table + zero + 1023) / 1024 * 1024;
-            ok = total <= 40 * 1024 && ext == EVAL_CW_EXT;        // (UF3_EVAL_NO_CW is looked at per call, where the instance is chosen)
-            if (ok) {
-                b->cw_lo = t0.lo[0]; b->cw_ext = ext; b->cw_dim_m = t0.dim_m; b->cw_dim_n = dn;
-                b->cw_zero = (int)table; b->cw_bytes = (int)total;
-                for (int t = 0; t < h.T; t++) { b->cw_lut_off.push_back(trios[t].lut_off); b->cw_dim_l.push_back(trios[t].dim_l); }
-            }
-        }
-        b->eval_cw_ok = ok;
+    P.eval_tab_ok = h.trio_legs_uniform && h.T <= WAVE && trios[0].leg[2].nk - 7 <= EVAL_TAB_KN;
+    if (!P.eval_tab_ok) return;
+    // k_eval<CW>: one window on every trio, centre legs alike, table + zero run small enough
+    const TrioDev &t0 = trios[0];
+    bool ok = t0.lo[0] == t0.lo[1] && t0.ext[0] == t0.ext[1] && t0.ext[0] >= 1;
+    for (int t = 0; t < h.T && ok; t++) {
+        const TrioDev &td = trios[t];
+        ok = td.lo[0] == t0.lo[0] && td.lo[1] == t0.lo[0] && td.ext[0] == t0.ext[0] && td.ext[1] == t0.ext[0] &&
+             td.dim_m == t0.dim_m && td.dim_n == t0.dim_n && td.dim_l == t0.dim_l;
     }
-    // ---- k_featurize3 (uf3_feat3.h): one window layout for all trios, centre legs alike, a W window of at most 31 positions;
-    // trios with two equal neighbour species must fold symmetrically in (l, m)
-    {
-        bool ok = h.T > 0 && h.trio_legs_uniform && !uf3_env("UF3_NO_FEAT3");
-        auto same_leg = [](const LegDev &a, const LegDev &q) {
-            return a.rec_off == q.rec_off && a.nk == q.nk && a.t0 == q.t0 && a.tlast == q.tlast && a.inv_h == q.inv_h;
-        };
+    if (ok) {
+        const int ext = t0.ext[0], dn = t0.dim_n;
+        const size_t table = (size_t)h.T * ext * ext * dn * 8;
+        const size_t zero = ((size_t)(3 * ext + 3) * dn * 8 + 32 + 15) / 16 * 16;        // (any row offset + one row's 32 bytes)
+        const size_t total = (table + zero + 1023) / 1024 * 1024;
+        ok = total <= 40 * 1024 && ext == EVAL_CW_EXT;        // (UF3_EVAL_NO_CW is looked at per call, where the instance is chosen)
         if (ok) {
-            const TrioDev &t0 = trios[0];
-            // the instantiated shapes (rows of the centre-leg window, rounds of 32 positions): (3, 1) (4, 2) (5, 3) (6, 3)
-            const int ep = t0.ext[0], en = t0.ext[2], np = ep * en;
-            // (a round of 32 positions holds whole rows of the summed leg: 32 / ext_n of them)
-            b->f3_nr = ep <= 3 ? 1 : (ep == 4 ? 2 : 3);          // (windows of one or two rows -- the reference's default resolution
-                                                                  // keeps 2 x 2 x 7 bins -- run in the three-row launch)
-            const int prr = en > 0 && en <= 32 ? std::min(ep, 32 / en) : 0;
-            (void)np;
-            const bool shape = prr > 0 && prr * b->f3_nr >= ep &&
-                               ((ep >= 1 && ep <= 3 && prr * en <= 31 && en <= 9) || (ep == 4 && en <= 11) || ((ep == 5 || ep == 6) && en <= 13));
-            ok = t0.lo[0] == t0.lo[1] && t0.ext[0] == t0.ext[1] && same_leg(t0.leg[0], t0.leg[1]) && shape &&
-                 t0.leg[0].nk >= 8 && t0.leg[2].nk >= 8;
-            for (int t = 0; t < h.T && ok; t++) {
-                const TrioDev &td = trios[t];
-                for (int a = 0; a < 3; a++) ok = ok && td.lo[a] == t0.lo[a] && td.ext[a] == t0.ext[a];
-                ok = ok && td.nsrc <= 2 && td.ncol >= 1;
-                if (ok && td.sa == td.sb)               // (l, m, n) and (m, l, n) feed the same column
-                    for (int col = 0; col < td.ncol && ok; col++)
-                        for (int q = 0; q < td.nsrc && ok; q++) {
-                            const int sp = colsrc[td.src_off + col * td.nsrc + q];
-                            if (sp < 0) continue;
-                            const int swapped = ((sp >> 8) & 255) | ((sp & 255) << 8) | (sp & 0xff0000);
-                            bool found = false;
-                            for (int q2 = 0; q2 < td.nsrc; q2++) found = found || colsrc[td.src_off + col * td.nsrc + q2] == swapped;
-                            ok = found;
-                        }
-            }
+            P.cw_lo = t0.lo[0]; P.cw_ext = ext; P.cw_dim_m = t0.dim_m; P.cw_dim_n = dn;
+            P.cw_zero = (int)table; P.cw_bytes = (int)total;
+            for (int t = 0; t < h.T; t++) { P.cw_lut_off.push_back(trios[t].lut_off); P.cw_dim_l.push_back(trios[t].dim_l); }
         }
-        if (ok) {
-            const TrioDev &t0 = trios[0];
-            b->f3_lo_p = t0.lo[0]; b->f3_ext_p = t0.ext[0]; b->f3_lo_n = t0.lo[2]; b->f3_ext_n = t0.ext[2];
-            std::vector<double> rows;
-            int n_rows = 0;
-            for (int kind = 0; kind < 2; kind++) {
-                const int a = kind == 0 ? 0 : 2;
-                const double *tk = leg_knots[a];
-                const int nk = t0.leg[a].nk, w_lo = t0.lo[a], w_ext = t0.ext[a];
-                Feat3Leg &lg = kind == 0 ? b->f3_leg_p : b->f3_leg_n;
-                lg.t0 = t0.leg[a].t0; lg.tlast = t0.leg[a].tlast; lg.inv_h = t0.leg[a].inv_h; lg.nk = nk; lg.row0 = n_rows;
-                for (int i = 3; i <= nk - 5; i++, n_rows++) {
-                    // four consecutive functions of the window, the first at slot clamp(i - 3 - window start, 0, ext - 4); zeros
-                    // where a function lies past the window or vanishes on the interval
-                    double row[18] = {0};
-                    row[0] = tk[i]; row[1] = tk[i + 1];
-                    const int sb = std::max(0, std::min(std::max(0, w_ext - 4), i - 3 - w_lo));
-                    for (int fq = 0; fq < 4 && sb + fq < w_ext; fq++) {
-                        const int j = w_lo + sb + fq;
-                        if (j >= i - 3 && j <= i && j >= 0 && j <= nk - 5) bspline_piece(tk, j, i, row + 2 + 4 * fq);
+    }
+    P.eval_cw_ok = ok;
+}
+
+// k_featurize3 (uf3_feat3.h) serves a basis with one window layout for all trios, centre legs alike, a window of an instantiated
+// shape; trios with two equal neighbour species must fold symmetrically in (l, m).  (f3_nr is set as soon as the legs are uniform,
+// whatever the answer: as it always was)
+static bool plan_feat3_ok(unsigned switches, BasisPlan &P) {
+    const BasisDev &h = P.host;
+    if (!(h.T > 0 && h.trio_legs_uniform && !(switches & BASIS_NO_FEAT3))) return false;
+    const TrioDev &t0 = P.trios[0];
+    // the instantiated shapes (rows of the centre-leg window, rounds of 32 positions): (3, 1) (4, 2) (5, 3) (6, 3)
+    const int ep = t0.ext[0], en = t0.ext[2];
+    P.f3_nr = ep <= 3 ? 1 : (ep == 4 ? 2 : 3);          // (windows of one or two rows -- the reference's default resolution keeps
+                                                         // 2 x 2 x 7 bins -- run in the three-row launch)
+    // (a round of 32 positions holds whole rows of the summed leg: 32 / ext_n of them)
+    const int prr = en > 0 && en <= 32 ? std::min(ep, 32 / en) : 0;
+    const bool shape = prr > 0 && prr * P.f3_nr >= ep &&
+                       ((ep >= 1 && ep <= 3 && prr * en <= 31 && en <= 9) || (ep == 4 && en <= 11) || ((ep == 5 || ep == 6) && en <= 13));
+    bool ok = t0.lo[0] == t0.lo[1] && t0.ext[0] == t0.ext[1] && same_leg(t0.leg[0], t0.leg[1]) && shape &&
+              t0.leg[0].nk >= 8 && t0.leg[2].nk >= 8;
+    for (int t = 0; t < h.T && ok; t++) {
+        const TrioDev &td = P.trios[t];
+        for (int a = 0; a < 3; a++) ok = ok && td.lo[a] == t0.lo[a] && td.ext[a] == t0.ext[a];
+        ok = ok && td.nsrc <= 2 && td.ncol >= 1;
+        if (!(ok && td.sa == td.sb)) continue;
+        const int *src = &P.colsrc[td.src_off];           // (l, m, n) and (m, l, n) feed the same column
+        for (int col = 0; col < td.ncol && ok; col++)
+            for (int q = 0; q < td.nsrc && ok; q++) {
+                const int sp = src[col * td.nsrc + q];
+                if (sp < 0) continue;
+                const int swapped = ((sp >> 8) & 255) | ((sp & 255) << 8) | (sp & 0xff0000);
+                bool found = false;
+                for (int q2 = 0; q2 < td.nsrc; q2++) found = found || src[col * td.nsrc + q2] == swapped;
+                ok = found;
+            }
+    }
+    return ok;
+}
+
+// ... and its tables: the window rows (window_rows) of the centre legs and of leg n -- the first of the four functions at window
+// slot clamp(i - 3 - window start, 0, ext - 4) --, and per trio the fold table [orientation 0 | 1][column][source 0 | 1] -> index of
+// the source bin in the fold's dump.  False: the fold tables outgrow their 16 KB of LDS.
+static bool plan_feat3_tables(const std::vector<const double *> &knots, BasisPlan &P) {
+    const BasisDev &h = P.host;
+    const TrioDev &t0 = P.trios[0];
+    P.f3_lo_p = t0.lo[0]; P.f3_ext_p = t0.ext[0]; P.f3_lo_n = t0.lo[2]; P.f3_ext_n = t0.ext[2];
+    for (int kind = 0; kind < 2; kind++) {
+        const int a = kind == 0 ? 0 : 2, w_lo_a = t0.lo[a], w_ext_a = t0.ext[a];
+        Feat3Leg &lg = kind == 0 ? P.f3_leg_p : P.f3_leg_n;
+        lg.t0 = t0.leg[a].t0; lg.tlast = t0.leg[a].tlast; lg.inv_h = t0.leg[a].inv_h; lg.nk = t0.leg[a].nk; lg.row0 = P.n_f3rows;
+        P.n_f3rows += window_rows(knots[a], lg.nk, [&](int i, int &w_lo, int &w_ext, int &sb) {
+            w_lo = w_lo_a; w_ext = w_ext_a; sb = std::max(0, std::min(std::max(0, w_ext - 4), i - 3 - w_lo));
+        }, P.f3rows);
+    }
+    P.f3off.assign(h.T, 0);
+    for (int t = 0; t < h.T; t++) {
+        const TrioDev &td = P.trios[t];
+        std::vector<unsigned short> mine;
+        for (int o = 0; o < 2; o++)
+            for (int col = 0; col < td.ncol; col++)
+                for (int q = 0; q < 2; q++) {
+                    const int sp = q < td.nsrc ? P.colsrc[td.src_off + col * td.nsrc + q] : -1;
+                    // (a column's missing second source: position 31 of row 0 -- never a window position in the
+                    // one-round launch --, or the zero behind the dumped rows)
+                    const int ps = 32 * P.f3_nr;
+                    unsigned short e = (unsigned short)(P.f3_nr == 1 ? 31 : td.ext[0] * ps);
+                    if (sp >= 0) {
+                        const int l = (sp & 255) - td.lo[0], m = ((sp >> 8) & 255) - td.lo[1], n = ((sp >> 16) & 255) - td.lo[2];
+                        const int prr = std::min(td.ext[0], 32 / td.ext[2]), j = o == 0 ? m : l;
+                        e = (unsigned short)((o == 0 ? l : m) * ps + (j / prr) * 32 + (j % prr) * td.ext[2] + n);
                     }
-                    rows.insert(rows.end(), row, row + 18);
+                    mine.push_back(e);
                 }
-            }
-            b->n_f3rows = n_rows;
-            std::vector<unsigned short> fsrc;
-            std::vector<int> foff(h.T, 0);
-            for (int t = 0; t < h.T; t++) {
-                const TrioDev &td = trios[t];
-                std::vector<unsigned short> mine;
-                for (int o = 0; o < 2; o++)
-                    for (int col = 0; col < td.ncol; col++)
-                        for (int q = 0; q < 2; q++) {
-                            const int sp = q < td.nsrc ? colsrc[td.src_off + col * td.nsrc + q] : -1;
-                            // (a column's missing second source: position 31 of row 0 -- never a window position in the
-                            // one-round launch --, or the zero behind the dumped rows)
-                            const int ps = 32 * b->f3_nr;
-                            unsigned short e = (unsigned short)(b->f3_nr == 1 ? 31 : td.ext[0] * ps);
-                            if (sp >= 0) {
-                                const int l = (sp & 255) - td.lo[0], m = ((sp >> 8) & 255) - td.lo[1], n = ((sp >> 16) & 255) - td.lo[2];
-                                const int prr = std::min(td.ext[0], 32 / td.ext[2]), j = o == 0 ? m : l;
-                                e = (unsigned short)((o == 0 ? l : m) * ps + (j / prr) * 32 + (j % prr) * td.ext[2] + n);
-                            }
-                            mine.push_back(e);
-                        }
-                int at = -1;
-                for (size_t off = 0; off + mine.size() <= fsrc.size() && at < 0; off += 2)
-                    if (std::equal(mine.begin(), mine.end(), fsrc.begin() + off)) at = (int)off;
-                if (at < 0) { at = (int)fsrc.size(); fsrc.insert(fsrc.end(), mine.begin(), mine.end()); }
-                foff[t] = at;
-            }
-            while (fsrc.size() & 1) fsrc.push_back(31);
-            ok = fsrc.size() * 2 <= 16384;
-            if (ok) {
-                b->n_f3src = (int)fsrc.size();
-                HIPCHK(c, hipMalloc(&b->d_f3rows, sizeof(double) * rows.size()));
-                HIPCHK(c, hipMemcpy(b->d_f3rows, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
-                HIPCHK(c, hipMalloc(&b->d_f3src, sizeof(unsigned short) * fsrc.size()));
-                HIPCHK(c, hipMemcpy(b->d_f3src, fsrc.data(), sizeof(unsigned short) * fsrc.size(), hipMemcpyHostToDevice));
-                HIPCHK(c, hipMalloc(&b->d_f3off, sizeof(int) * foff.size()));
-                HIPCHK(c, hipMemcpy(b->d_f3off, foff.data(), sizeof(int) * foff.size(), hipMemcpyHostToDevice));
-            }
-        }
-        b->feat3_ok = ok;
-        if (ok) b->modes |= 1 << 12;
+        P.f3off[t] = intern_run(P.f3src, mine, 2);
     }
-    // the force rows of an atom of species s are zero outside the blocks s takes part in (and in the one-body columns)
-    {
-        std::vector<int> sp_cols((size_t)h.S * h.F, 0);
-        for (int sp = 0; sp < h.S; sp++) {
-            std::vector<char> in(h.F, 0);
-            for (int p2 = 0; p2 < h.P; p2++)
-                if (h.pairs[p2].sa == sp || h.pairs[p2].sb == sp) for (int q = 0; q < h.pairs[p2].nb; q++) in[h.pairs[p2].col + q] = 1;
-            for (auto &td : trios)
-                if (td.sc == sp || td.sa == sp || td.sb == sp) for (int q = 0; q < td.ncol; q++) in[td.col + q] = 1;
-            int n = 0;
-            for (int q = 0; q < h.F; q++) if (in[q]) sp_cols[(size_t)sp * h.F + n++] = q;
-            b->sp_ncols[sp] = n;
-        }
-        HIPCHK(c, hipMalloc(&b->d_sp_cols, sizeof(int) * sp_cols.size()));
-        HIPCHK(c, hipMemcpy(b->d_sp_cols, sp_cols.data(), sizeof(int) * sp_cols.size(), hipMemcpyHostToDevice));
+    while (P.f3src.size() & 1) P.f3src.push_back(31);
+    if (P.f3src.size() * 2 <= 16384) { P.n_f3src = (int)P.f3src.size(); return true; }
+    P.f3rows.clear(); P.f3src.clear(); P.f3off.clear();       // (nothing of it is uploaded)
+    return false;
+}
+
+// the force rows of an atom of species s are zero outside the blocks s takes part in (and in the one-body columns)
+static void plan_species_columns(BasisPlan &P) {
+    const BasisDev &h = P.host;
+    P.sp_cols.assign((size_t)h.S * h.F, 0);
+    for (int sp = 0; sp < h.S; sp++) {
+        std::vector<char> in(h.F, 0);
+        for (int p = 0; p < h.P; p++)
+            if (h.pairs[p].sa == sp || h.pairs[p].sb == sp) for (int q = 0; q < h.pairs[p].nb; q++) in[h.pairs[p].col + q] = 1;
+        for (auto &td : P.trios)
+            if (td.sc == sp || td.sa == sp || td.sb == sp) for (int q = 0; q < td.ncol; q++) in[td.col + q] = 1;
+        int n = 0;
+        for (int q = 0; q < h.F; q++) if (in[q]) P.sp_cols[(size_t)sp * h.F + n++] = q;
+        P.sp_ncols[sp] = n;
     }
-    HIPCHK(c, hipMalloc(&b->dev, sizeof(BasisDev)));
-    HIPCHK(c, hipMemcpy(b->dev, &h, sizeof(BasisDev), hipMemcpyHostToDevice));
-    *out = b;
+}
+
+// P: a fresh plan.  False with the refusal in err.
+static bool basis_plan(const uf3_basis_spec *s, unsigned switches, BasisPlan &P, std::string &err) {
+    err = basis_check(s);
+    if (!err.empty()) return false;
+    P.r_cut = s->r_cut;
+    BasisDev &h = P.host;
+    std::memset(&h, 0, sizeof(h));
+    h.S = s->n_species; h.P = s->n_pairs; h.T = s->n_trios; h.F = s->n_feat;
+    h.lead2 = s->lead2; h.trail2 = s->trail2;
+    std::memset(h.z2s, -1, sizeof(h.z2s));
+    for (int i = 0; i < h.S; i++) h.z2s[s->species_z[i]] = (signed char)i;
+    for (auto &v : h.pair_of) v = -1;
+    for (auto &v : h.trio_of) v = -1;
+    for (int i = 0; i <= h.S; i++) P.block_bounds.push_back(i);
+    plan_pairs(s, P);
+    const std::vector<const double *> knots = plan_trio_legs(s, P);
+    plan_trio_layouts(s, switches, knots, P);
+    if (!plan_window_rows(knots, plan_grouped_folds(P), P, err)) return false;
+    std::sort(P.block_bounds.begin(), P.block_bounds.end());
+    P.block_bounds.erase(std::unique(P.block_bounds.begin(), P.block_bounds.end()), P.block_bounds.end());
+    P.n_recs = P.recs.size();
+    P.trio_rec_lo = P.recs.size();
+    for (auto &td : P.trios) for (int d = 0; d < 3; d++) P.trio_rec_lo = std::min(P.trio_rec_lo, (size_t)td.leg[d].rec_off);
+    P.n_dsrc = P.dsrc.size();
+    P.n_gsrc = P.gsrc.size();
+    P.all_grouped7 = P.all_banded9 = true;
+    for (auto &td : P.trios) {
+        if (td.dense == 7 && !td.grouped) P.all_grouped7 = false;
+        // (the banded-only launch names its accumulator tiles at compile time: bands on the tiles 0, 1, 2)
+        if (td.dense == 9 && !(td.banded && td.band_tile[0] == 0 && td.band_tile[1] == 1 && td.band_tile[2] == 2)) P.all_banded9 = false;
+        td.head = TrioHead{td.dense, td.nsrc, td.ncol, td.sc, td.sa, td.sb, td.col,       // (layouts and bands are final)
+                           td.grouped ? ((td.layout + 1) | (td.gsrc_off << 8))
+                                      : (td.banded ? (1 | (td.band_tile[0] << 8) | (td.band_tile[1] << 12) | (td.band_tile[2] << 16)) : 0)};
+    }
+    plan_eval(P);
+    P.feat3_ok = plan_feat3_ok(switches, P) && plan_feat3_tables(knots, P);
+    if (P.feat3_ok) P.modes |= 1 << 12;
+    plan_species_columns(P);
+    return true;
+}
+
+// One table of a basis on the device: room for `room` >= n elements (kernels may read past the logical end), n of them copied in
+template <class T>
+static hipError_t upload(DevTable<T> &d, const T *src, size_t n, size_t room) {
+    const hipError_t e = hipMalloc(&d.p, sizeof(T) * room);
+    if (e != hipSuccess) return e;
+    d.cap = sizeof(T) * room;
+    return n ? hipMemcpy(d.p, src, sizeof(T) * n, hipMemcpyHostToDevice) : hipSuccess;
+}
+template <class T>
+static hipError_t upload(DevTable<T> &d, const std::vector<T> &v, size_t room = 0) { return upload(d, v.data(), v.size(), std::max(room, v.size())); }
+
+extern "C" int uf3_basis_create(uf3_ctx *c, const uf3_basis_spec *s, uf3_basis **out) {
+    uf3_env_refresh();
+    if (!c || !s || !out) return fail(c, UF3_EINVAL, "uf3_basis_create: null argument");
+    const unsigned switches = (uf3_env("UF3_NO_MFMA_FEAT") ? BASIS_NO_MFMA_FEAT : 0) | (uf3_env("UF3_NO_FEAT3") ? BASIS_NO_FEAT3 : 0);
+    BasisPlan P;
+    std::string err;
+    if (!basis_plan(s, switches, P, err)) return fail(c, UF3_EINVAL, err);
+    HIPCHK(c, hipSetDevice(c->device));
+    std::unique_ptr<uf3_basis> b(new uf3_basis());      // (a failed upload frees what the earlier ones allocated)
+    b->ctx = c;
+    HIPCHK(c, upload(b->d_recs, P.recs, 1));
+    HIPCHK(c, upload(b->d_lut, P.lut));
+    HIPCHK(c, upload(b->d_colsrc, P.colsrc, 1));
+    HIPCHK(c, upload(b->d_dsrc, P.dsrc, 1));
+    HIPCHK(c, upload(b->d_gsrc, P.gsrc, P.gsrc.size() + 8));
+    HIPCHK(c, upload(b->d_trios, P.trios, 1));
+    if (P.feat3_ok) {
+        HIPCHK(c, upload(b->d_f3rows, P.f3rows));
+        HIPCHK(c, upload(b->d_f3src, P.f3src));
+        HIPCHK(c, upload(b->d_f3off, P.f3off));
+    }
+    HIPCHK(c, upload(b->d_sp_cols, P.sp_cols));
+    P.host.trios = b->d_trios; P.host.recs = b->d_recs; P.host.lut = b->d_lut;
+    static_cast<BasisFacts &>(*b) = P;
+    HIPCHK(c, upload(b->dev, &b->host, 1, 1));
+    *out = b.release();
+    return UF3_OK;
+}
+
+// table: 0 the summary (uf3_basis_plan_summary), then the host mirror, recs, lut, colsrc, dsrc, gsrc, trios, f3rows, f3src, f3off,
+// sp_cols, block_bounds, cw_lut_off, cw_dim_l -- what basis_plan made of the spec, and nothing else
+extern "C" int uf3_basis_plan_debug(const uf3_basis_spec *s, int switches, int table, void *out, int64_t cap, int64_t *len) {
+    if (!s || !len || cap < 0) return fail(nullptr, UF3_EINVAL, "uf3_basis_plan_debug: bad argument");
+    BasisPlan P;
+    std::string err;
+    if (!basis_plan(s, (unsigned)switches, P, err)) return fail(nullptr, UF3_EINVAL, err);
+    uf3_basis_plan_summary o;
+    std::memset(&o, 0, sizeof o);
+    o.c2_len = (int64_t)P.c2_len; o.c3_len = (int64_t)P.c3_len; o.n_recs = (int64_t)P.n_recs; o.n_pair_recs = (int64_t)P.n_pair_recs;
+    o.trio_rec_lo = (int64_t)P.trio_rec_lo; o.wrow_lo = (int64_t)P.wrow_lo; o.n_dsrc = (int64_t)P.n_dsrc; o.n_gsrc = (int64_t)P.n_gsrc;
+    o.r_cut = P.r_cut;
+    const Feat3Leg *legs[2] = {&P.f3_leg_p, &P.f3_leg_n};
+    for (int k = 0; k < 2; k++) {
+        o.f3_leg[k][0] = legs[k]->t0; o.f3_leg[k][1] = legs[k]->tlast; o.f3_leg[k][2] = legs[k]->inv_h;
+        o.f3_leg_nk[k] = legs[k]->nk; o.f3_leg_row0[k] = legs[k]->row0;
+    }
+    o.n_wrows = P.n_wrows; o.modes = P.modes; o.vmodes = P.vmodes; o.all_grouped7 = P.all_grouped7; o.all_banded9 = P.all_banded9;
+    o.feat3_ok = P.feat3_ok; o.eval_tab_ok = P.eval_tab_ok; o.eval_cw_ok = P.eval_cw_ok;
+    o.cw_lo = P.cw_lo; o.cw_ext = P.cw_ext; o.cw_dim_m = P.cw_dim_m; o.cw_dim_n = P.cw_dim_n; o.cw_zero = P.cw_zero; o.cw_bytes = P.cw_bytes;
+    o.f3_lo_p = P.f3_lo_p; o.f3_ext_p = P.f3_ext_p; o.f3_lo_n = P.f3_lo_n; o.f3_ext_n = P.f3_ext_n; o.f3_nr = P.f3_nr;
+    o.n_f3rows = P.n_f3rows; o.n_f3src = P.n_f3src;
+    o.pairs_uniform = P.host.pairs_uniform; o.trio_legs_uniform = P.host.trio_legs_uniform;
+    for (int k = 0; k < UF3_MAX_SPECIES; k++) o.sp_ncols[k] = P.sp_ncols[k];
+    for (int k = 0; k < 16; k++) {
+        o.dense_stride[k] = P.dense_stride[k]; o.dense_stride_f[k] = P.dense_stride_f[k];
+        o.dense_grouped[k] = P.dense_grouped[k]; o.dense_dump[k] = P.dense_dump[k];
+    }
+    auto bytes_of = [](const auto &v) { return std::pair<const void *, size_t>(v.data(), v.size() * sizeof(v[0])); };
+    const std::pair<const void *, size_t> tables[] = {
+        {&o, sizeof o}, {&P.host, sizeof(BasisDev)}, bytes_of(P.recs), bytes_of(P.lut), bytes_of(P.colsrc), bytes_of(P.dsrc),
+        bytes_of(P.gsrc), bytes_of(P.trios), bytes_of(P.f3rows), bytes_of(P.f3src), bytes_of(P.f3off), bytes_of(P.sp_cols),
+        bytes_of(P.block_bounds), bytes_of(P.cw_lut_off), bytes_of(P.cw_dim_l)};
+    if (table < 0 || table >= (int)(sizeof tables / sizeof tables[0])) return fail(nullptr, UF3_EINVAL, "uf3_basis_plan_debug: no such table");
+    *len = (int64_t)tables[table].second;
+    if (!out) return UF3_OK;
+    if ((size_t)cap < tables[table].second) return fail(nullptr, UF3_EINVAL, "uf3_basis_plan_debug: buffer too small");
+    std::memcpy(out, tables[table].first, tables[table].second);
     return UF3_OK;
 }
 
@@ -1110,13 +1250,11 @@ extern "C" int uf3_basis_featurizer_modes(const uf3_basis *b, int32_t *mask) {
     return UF3_OK;
 }
 
-extern "C" void uf3_basis_destroy(uf3_basis *b) {
+extern "C" void uf3_basis_destroy(uf3_basis *handle) {
+    const std::unique_ptr<uf3_basis> b(handle);      // (its tables free themselves when it goes, after the two calls below)
     if (!b) return;
     hipSetDevice(b->ctx->device);
     hipStreamSynchronize(b->ctx->stream);
-    hipFree(b->dev); hipFree(b->d_trios); hipFree(b->d_recs); hipFree(b->d_lut); hipFree(b->d_colsrc); hipFree(b->d_dsrc); hipFree(b->d_gsrc); hipFree(b->d_sp_cols);
-    hipFree(b->d_f3rows); hipFree(b->d_f3src); hipFree(b->d_f3off);
-    delete b;
 }
 
 // ------------------------------------------------------------------------------ frame geometry
@@ -3954,13 +4092,6 @@ extern "C" int uf3_direction_cosines(uf3_ctx *c, const double *sup_pos, int64_t 
 
 // ------------------------------------------------------------------------------ what the library-owned drivers share
 // (uf3_md, uf3_relax, uf3_neb and uf3_mc below: a batch with its model and its buffers, stepped between calls of eval_impl)
-struct DevBuf : Buf {                           // a buffer that a driver owns: freed with its owner
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-};
-
 struct Batch {
     uf3_basis *b = nullptr;
     uf3_ctx *c = nullptr;
